@@ -14,7 +14,17 @@ and the forward rasterisation of RGB and mask.  Inputs (RGB, mask, constraints) 
 the timed region.  Workload = BASELINE.json configs[1]: single-segment DAVIS-shaped mask, fd=1.
 Frames shard across ranks with no collective: weak scaling, value = all frames / max time.
 
-One JSON line on rank 0: metric/value/... plus
+A plain run sets up, warms up, times the K steps and prints one JSON line on rank 0: metric / value / unit /
+ms_per_step / ... and the workload's bookkeeping.
+
+  --dump-outputs DIR : after the timed steps, rank 0 writes what its last step computed -- what FrameSolver.results()
+                 hands a caller for every solve of the batch -- as DIR/<name>.npy, float32, stacked over the solves:
+                 offset [S,H,W,2], angle [S,H,W], flow [S,H,W,2], warped_rgb [S,H,W,3], warped_mask [S,H,W] and cost
+                 [S] (float64).  Above 64 MB in all, each array is replaced by a fixed sample of its flattened elements
+                 (the same share of every array, indices drawn by a generator seeded with 0 and sorted), so two builds
+                 run with the same arguments are compared element for element.  The inputs depend on the arguments only.
+
+  --full       : also everything that takes runs of its own, added to the same line:
   roofline     : dominant PCG kernel.  achieved / peak / frac = SURVEY 8(d)'s figure: algorithmic bytes per launch /
                  average launch duration measured with HIP events around every launch (a separate, un-graphed pass)
                  against the 8 TB/s HBM peak.  The resident kernel keeps the PCG state on chip, so that figure exceeds 1
@@ -64,8 +74,13 @@ def parse():
                     help="configs[2]/[4]: K segments per frame, each its own ARAP solve (para_gen.py --multseg); "
                          "--batch then counts frames, K x batch solves run per step")
     ap.add_argument("--fd", type=int, default=1, help="frame distance of the synthetic matches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: the kernel-timing (roofline) pass, copy "
+                         "bandwidth, the warp stage alone, the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: leave out the kernel-timing pass")
     ap.add_argument("--stamps", action="store_true",
                     help="diagnostic (needs ARAPOPT_STAMPS=1): print the per-phase times of the resident kernel's last launch")
     return ap.parse_args()
@@ -74,6 +89,25 @@ def parse():
 def _field_hash(offset, angle):
     return hashlib.sha256(np.ascontiguousarray(offset, np.float32).tobytes() +
                           np.ascontiguousarray(angle, np.float32).tobytes()).hexdigest()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(fs, n, out_dir):
+    """--dump-outputs: the results of slots 0 .. n-1 as out_dir/<name>.npy (see the module docstring)"""
+    res = [fs.results(b) for b in range(n)]
+    arrays = {k: np.stack([r[k] for r in res]).astype(np.float32)
+              for k in ("offset", "angle", "flow", "warped_rgb", "warped_mask")}
+    total = sum(v.nbytes for v in arrays.values())
+    arrays["cost"] = np.asarray([r["cost"] for r in res], np.float64)
+    room = DUMP_BYTES - arrays["cost"].nbytes - 4096          # (the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        if k != "cost" and total > room:                      # the same share of every array, fixed indices
+            keep = v.size * room // total
+            v = v.ravel()[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def _time_oracle(spec, threads, numIter, nIter, lIter, first_only=False):
@@ -200,6 +234,8 @@ def main():
     # n_gpus = WORLD_SIZE while the caller asked for another N would be a scaling point that measures something else).
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if a.gpus > 1:
             sys.exit(launch_ranks(a))
@@ -299,10 +335,12 @@ def main():
     pcg_per_frame = stats["pcg_iterations_per_frame"]
     n_active = stats["active_vertices"] / B          # per frame (all its segments)
     n_grid = W * H
-    # result of the timed steps, frame 0 (its first segment), for the parity check below: taken NOW, before the
-    # kernel-timing pass re-solves with another schedule
+    # what the last timed step computed, and frame 0 (its first segment) of it for the parity check below: taken NOW,
+    # before the kernel-timing pass re-solves with another schedule
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(fs, S, a.dump_outputs)
     parity_hash = None
-    if rank == 0 and not a.no_cpu_baseline and world == 1:
+    if rank == 0 and a.full and not a.no_cpu_baseline and world == 1:
         r_timed = fs.results(0, want_rgb=False)
         parity_hash = _field_hash(r_timed["offset"], r_timed["angle"])
         del r_timed
@@ -334,7 +372,7 @@ def main():
     if rank == 0:
         # ---- roofline of the dominant kernel: HIP events around every launch (un-graphed pass) ----------
         r0 = None
-        if not a.no_kernel_timing:
+        if a.full and not a.no_kernel_timing:
             tl = min(lIter, 400)
             G = 8                                      # Gauss-Newton steps timed: 2 solves x 4 steps of tl PCG iterations
             st.set_kernel_timing(True)
@@ -494,7 +532,7 @@ def main():
                                              "wait_frac": float((us[1] + us[3]) / us.sum()), "workgroups": int(used.sum()),
                                              "note": "instrumented build (ARAPOPT_STAMPS=1), last resident launch; a workgroup that "
                                                      "finishes a phase before its CU-mate counts the mate's remaining phase time as wait"}}))
-        if not a.no_cpu_baseline and world == 1:               # the CPU side is timed at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:    # the CPU side is timed at N = 1 only
             f0 = frames[0]
             spec = dict(W=W, H=H, seed=f0["seed"], K=K, fd=a.fd, full=(a.workload == "full"), multseg=bool(a.multseg),
                         active=float(n_active))

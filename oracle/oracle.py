@@ -47,6 +47,12 @@ def ref_warp_binary():
     return p if os.path.exists(p) else None
 
 
+def ref_file(name):
+    """a file of the reference staged under oracle/_ref/ by build() (`make ref`), or None"""
+    p = os.path.join(_HERE, "_ref", name)
+    return p if os.path.exists(p) else None
+
+
 def set_trig(t):
     """cos/sin of the standalone kernel-level functions: 0 libm (default), 1 spec routine"""
     lib().oracle_set_trig(C.c_int(int(t)))

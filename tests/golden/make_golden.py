@@ -8,6 +8,7 @@ warp part):   python tests/golden/make_golden.py
  2. warp_synth/ : inputs (PNG, .flo) and the outputs of the REFERENCE's own warp_image, compiled from
     /root/reference/ARAP/warping/src by oracle/Makefile into oracle/_ref/warp_image, on a synthetic
     flow with fold-overs and out-of-frame targets.
+ 3. warp_live/ : the outputs of the same binary on the random folded flow of helpers.warp_live_case().
 """
 import os
 import subprocess
@@ -80,6 +81,16 @@ def main():
     subprocess.check_call([ref, os.path.join(d, "iRGB.png"), os.path.join(d, "iMsk.png"),
                            os.path.join(d, "iFlo.flo"), os.path.join(d, "wRGB.png"), os.path.join(d, "wMsk.png")])
     print("warp_synth written with", ref)
+
+    # ---- warp: reference binary on the random folded flow of test_warp_oracle_vs_live_reference_binary ---------
+    d = os.path.join(HERE, "warp_live")
+    os.makedirs(d, exist_ok=True)
+    wrgb, wmsk = helpers.run_ref_warp(ref, *helpers.warp_live_case(), d)
+    for n in ("i.png", "m.png", "f.flo", "o.png", "om.png"):
+        os.remove(os.path.join(d, n))
+    Image.fromarray(wrgb).save(os.path.join(d, "wRGB.png"))
+    Image.fromarray(wmsk).save(os.path.join(d, "wMsk.png"))
+    print("warp_live written with", ref)
 
 
 if __name__ == "__main__":

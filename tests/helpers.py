@@ -41,6 +41,32 @@ def neg_det_quads(flow, act):
     return int(((det < 0) & q).sum())
 
 
+def warp_live_case():
+    """input of the warp test against the reference's warp_image on a fresh random folded flow (tests/test_oracle.py);
+    the binary's outputs on it are kept in tests/golden/warp_live/ (tests/golden/make_golden.py)"""
+    rng = np.random.default_rng(5)
+    W, H = 70, 50
+    rgb = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
+    mask = np.where(rng.random((H, W)) < 0.15, 255, 0).astype(np.uint8)
+    fl = (rng.normal(size=(H, W, 2)) * 3.0).astype(np.float32)
+    fl[mask != 0] = 0
+    return rgb, mask, fl
+
+
+def run_ref_warp(ref, rgb, mask, fl, d):
+    """the reference's warp_image (oracle/_ref/) on (rgb, mask, fl), files in directory d -> (warped rgb, warped mask)"""
+    import os
+    import subprocess
+    from PIL import Image
+    from arap_flow_amd import flo
+    p = lambda n: os.path.join(str(d), n)
+    Image.fromarray(rgb).save(p("i.png"))
+    Image.fromarray(np.stack([mask] * 3, -1)).save(p("m.png"))
+    flo.flow_write(p("f.flo"), fl)
+    subprocess.check_call([ref, p("i.png"), p("m.png"), p("f.flo"), p("o.png"), p("om.png")], stdout=subprocess.DEVNULL)
+    return np.array(Image.open(p("o.png")).convert("RGB")), np.array(Image.open(p("om.png")).convert("L"))
+
+
 def load_cat512(golden_dir):
     import os
     from PIL import Image

@@ -185,7 +185,7 @@ def test_bench_contract_json_line(tmp_path):
     """bench.py prints ONE JSON line with the contract's keys (tiny schedule and frames here)"""
     import json
     out = _run([osp.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--size", "214", "120",
-                "--schedule", "2", "2", "30"], str(tmp_path))
+                "--schedule", "2", "2", "30", "--full"], str(tmp_path))
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -209,6 +209,37 @@ def test_bench_contract_json_line(tmp_path):
     assert c["kind"] == "port" and c["cores"] >= 1
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path, oracle):
+    """a plain bench run times exactly --steps steps and adds nothing that takes runs of its own; --dump-outputs writes
+    what the last timed step computed, and frame 0 of it is the oracle's result bit for bit"""
+    import json
+    W, H, sched = 214, 120, (2, 2, 30)
+    d = tmp_path / "out"
+    out = _run([osp.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--size", str(W), str(H),
+                "--schedule"] + [str(v) for v in sched] + ["--dump-outputs", str(d)], str(tmp_path))
+    lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0 and r["ms_per_step"] > 0
+    assert abs(r["value"] - 2 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+    for k in ("roofline", "cpu_baseline", "parity_check", "warp_stage"):
+        assert k not in r, k
+    got = {k: np.load(d / (k + ".npy")) for k in ("offset", "angle", "flow", "warped_rgb", "warped_mask", "cost")}
+    assert got["offset"].shape == (2, H, W, 2) and got["angle"].shape == (2, H, W) and got["cost"].shape == (2,)
+    assert got["warped_rgb"].shape == (2, H, W, 3) and got["warped_mask"].shape == (2, H, W)
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    f0 = synth.make_frame(W, H, seed=0, K=1, fd=1)
+    O, A, costs = oracle.frame(f0["mask_red"], f0["constraints"], numIter=sched[0], nIterations=sched[1], lIterations=sched[2],
+                               dtype=np.float32, mode=1, trig=1)
+    assert np.array_equal(got["offset"][0], O) and np.array_equal(got["angle"][0], A)
+    ys, xs = np.mgrid[0:H, 0:W]
+    assert np.array_equal(got["flow"][0], O - np.stack([xs, ys], -1).astype(np.float32))
+    o_rgb, o_msk = oracle.warp_offset(f0["rgb"], f0["mask_red"], O)
+    assert np.array_equal(got["warped_rgb"][0], o_rgb) and np.array_equal(got["warped_mask"][0], o_msk)
+
+
 def test_bench_two_ranks_under_torch_distributed_run(tmp_path):
     """The driver's N > 1 command line, rehearsed on one GPU: two ranks launched by torch.distributed.run share the
     card (ARAP_BENCH_BACKEND=gloo moves only the timing barrier and the max-over-ranks off RCCL, which wants one GPU
@@ -219,7 +250,7 @@ def test_bench_two_ranks_under_torch_distributed_run(tmp_path):
     env = dict(os.environ, ARAP_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), osp.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--batch", "2", "--size", "214", "120", "--schedule", "2", "2", "30"]
+           "--batch", "2", "--size", "214", "120", "--schedule", "2", "2", "30", "--full"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

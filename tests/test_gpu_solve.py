@@ -87,8 +87,9 @@ def test_problem_define_accepts_only_the_arap_energy(gpu_state, tmp_path):
     bad = tmp_path / "other.t"
     bad.write_text('local W,H = Dim("W",0), Dim("H",1)\nlocal X = Unknown("X",opt_float,{W,H},0)\nEnergy(X(0,0))\n')
     assert lib.Opt_ProblemDefine(st, str(bad).encode(), b"gaussNewtonGPU") is None
-    ref_plan = "/root/reference/arap_plan.t"                                       # build container only
-    if os.path.exists(ref_plan):
+    from oracle import oracle as orc
+    ref_plan = orc.ref_file("arap_plan.t")                                         # staged by build() under oracle/_ref/
+    if ref_plan is not None:
         p = lib.Opt_ProblemDefine(st, ref_plan.encode(), b"gaussNewtonGPU")
         assert p is not None
         lib.Opt_ProblemDelete(st, p)

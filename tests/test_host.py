@@ -188,22 +188,29 @@ def test_resident_deal_packs_narrow_and_wide_solves():
 def test_c_program_against_the_reference_header_links_with_the_library(tmp_path):
     """A C file that includes the REFERENCE's own ARAP/API/release/include/Opt.h and calls its ten functions must
     compile and link against libarapopt.so unchanged (the drop-in boundary).  Run here it gets NULL from
-    Opt_NewState (no HIP device, no CPU fallback) and stops there.  Skipped where /root/reference is absent."""
+    Opt_NewState (no HIP device, no CPU fallback) and stops there; where a device is visible it gets a state and stops
+    there too (the calls after it are linked, never run: their problem parameters are not set up).  The header is the
+    copy build() stages under oracle/_ref/; skipped where build() had no reference tree to take it from."""
     import subprocess
     from arap_flow_amd import build
-    inc = "/root/reference/ARAP/API/release/include"
-    if not os.path.exists(os.path.join(inc, "Opt.h")):
-        pytest.skip("reference tree not present")
+    from oracle import oracle as orc
+    hdr = orc.ref_file(os.path.join("include", "Opt.h"))
+    if hdr is None:
+        pytest.skip("oracle/_ref/include/Opt.h not staged by build() here (no reference tree)")
+    inc = os.path.dirname(hdr)
     lib = build.build()
     src = tmp_path / "dropin.c"
     src.write_text(r'''
 #include <stdio.h>
 #include "Opt.h"
-int main(void)
+int main(int argc, char** argv)
 {
+    (void)argv;
     Opt_InitializationParameters ip = {0, 0, 0, 0};
     Opt_State* st = Opt_NewState(ip);
     if (!st) { printf("no state\n"); return 0; }
+    printf("state\n");
+    if (argc < 2) return 0;
     unsigned dims[2] = {64, 64};
     int n = 2, l = 10;
     void* params[7] = {0};
@@ -224,8 +231,10 @@ int main(void)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + inc, str(src), "-o", str(exe),
                            "-L" + os.path.dirname(lib), "-larapopt", "-Wl,-rpath," + os.path.dirname(lib),
                            "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"])
+    import torch
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "no state" in r.stdout, r.stdout + r.stderr
+    want = "state" if torch.cuda.device_count() > 0 else "no state"
+    assert r.returncode == 0 and r.stdout.splitlines() == [want], r.stdout + r.stderr
 
 
 def test_resident_tile_lists_cover_every_active_vertex_once():

@@ -133,24 +133,17 @@ def test_warp_oracle_vs_reference_binary_outputs(oracle, golden_dir):
     assert np.array_equal(wrgb, ref_rgb)                                 # bit exact vs the reference's own code
 
 
-def test_warp_oracle_vs_live_reference_binary(oracle, tmp_path):
-    """When oracle/_ref/warp_image exists (build container), run it on a fresh random folded flow."""
-    import subprocess
-    from arap_flow_amd import flo
+def test_warp_oracle_vs_live_reference_binary(oracle, tmp_path, golden_dir):
+    """The reference's warp_image on a fresh random folded flow: run live where build() made oracle/_ref/warp_image
+    (and its result must equal the recorded one), else its outputs recorded in tests/golden/warp_live/."""
+    rgb, mask, fl = helpers.warp_live_case()
+    d = os.path.join(golden_dir, "warp_live")
+    ref_rgb = np.array(Image.open(os.path.join(d, "wRGB.png")).convert("RGB"))
+    ref_msk = np.array(Image.open(os.path.join(d, "wMsk.png")).convert("L"))
     ref = oracle.ref_warp_binary()
-    if ref is None:
-        pytest.skip("oracle/_ref/warp_image not built here")
-    rng = np.random.default_rng(5)
-    W, H = 70, 50
-    rgb = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    mask = np.where(rng.random((H, W)) < 0.15, 255, 0).astype(np.uint8)
-    fl = (rng.normal(size=(H, W, 2)) * 3.0).astype(np.float32)
-    fl[mask != 0] = 0
-    Image.fromarray(rgb).save(tmp_path / "i.png")
-    Image.fromarray(np.stack([mask] * 3, -1)).save(tmp_path / "m.png")
-    flo.flow_write(str(tmp_path / "f.flo"), fl)
-    subprocess.check_call([ref, str(tmp_path / "i.png"), str(tmp_path / "m.png"), str(tmp_path / "f.flo"),
-                           str(tmp_path / "o.png"), str(tmp_path / "om.png")], stdout=subprocess.DEVNULL)
+    if ref is not None:
+        live_rgb, live_msk = helpers.run_ref_warp(ref, rgb, mask, fl, tmp_path)
+        assert np.array_equal(live_rgb, ref_rgb) and np.array_equal(live_msk, ref_msk)
     wrgb, wmsk = oracle.warp(rgb, mask, fl)
-    assert np.array_equal(wrgb, np.array(Image.open(tmp_path / "o.png").convert("RGB")))
-    assert np.array_equal(wmsk, np.array(Image.open(tmp_path / "om.png").convert("L")))
+    assert np.array_equal(wrgb, ref_rgb)
+    assert np.array_equal(wmsk, ref_msk)

@@ -96,3 +96,45 @@ def test_bench_refuses_a_world_size_that_differs_from_gpus(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")], cwd=str(tmp_path), env=env,
                        capture_output=True, text=True, timeout=60)          # default --gpus 1 under a 2-rank launcher
     assert r.returncode == 2
+
+
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs without a GPU: a stand-in solver hands out results.  A small batch is written whole, in
+    float32 / float64; the default 854x480 batch of 8 exceeds 64 MB and is cut to a sample that is the same from run to
+    run and taken at the same flat indices of every array."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Solver:
+        def __init__(self, W, H):
+            self.W, self.H = W, H
+
+        def results(self, b):
+            rng = np.random.default_rng(b)
+            H, W = self.H, self.W
+            off = rng.normal(size=(H, W, 2)).astype(np.float32)
+            return dict(offset=off, angle=rng.normal(size=(H, W)).astype(np.float32), flow=off - 1.0,
+                        warped_rgb=rng.integers(0, 256, (H, W, 3)).astype(np.uint8),
+                        warped_mask=rng.integers(0, 2, (H, W)).astype(np.uint8), cost=float(b) + 0.5)
+
+    names = ("offset", "angle", "flow", "warped_rgb", "warped_mask", "cost")
+    small = Solver(40, 30)
+    bench.dump_outputs(small, 3, str(tmp_path / "small"))
+    for k in names:
+        v = np.load(tmp_path / "small" / (k + ".npy"))
+        assert v.dtype in (np.float32, np.float64)
+        assert np.array_equal(v, np.stack([np.asarray(small.results(b)[k], np.float64) for b in range(3)]))
+    big = Solver(854, 480)
+    for run in ("a", "b"):
+        bench.dump_outputs(big, 8, str(tmp_path / run))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in names)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        assert open(tmp_path / "a" / f, "rb").read() == open(tmp_path / "b" / f, "rb").read()
+    off, flow = np.load(tmp_path / "a" / "offset.npy"), np.load(tmp_path / "a" / "flow.npy")
+    assert off.ndim == 1 and off.size > 1 << 20 and np.array_equal(flow, off - 1.0)
+    assert np.array_equal(np.load(tmp_path / "a" / "cost.npy"), np.arange(8) + 0.5)

@@ -90,7 +90,7 @@ def main():
     os.chdir("/tmp")
     os.environ["TMPDIR"] = "/tmp"
     from tools import profile_key
-    args = CONFIGS[a.name] + a.extra
+    args = ["--full"] + CONFIGS[a.name] + a.extra          # the roofline pass and the CPU leg are what it records
     # written under gpurun_out/ (the only directory that travels back from the GPU box); copy into profiles/ afterwards
     prof = os.path.join(ROOT, "gpurun_out", "profiles")
     os.makedirs(prof, exist_ok=True)

@@ -9,7 +9,7 @@ for lib in libs:
     env = dict(os.environ)
     if lib != "default":
         env["ARAPOPT_LIB"] = lib if os.path.isabs(lib) else os.path.join(ROOT, lib)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, env=env, capture_output=True, text=True)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if not line:
         print(lib, "FAILED", r.stderr[-400:]); continue
