@@ -160,10 +160,39 @@ __device__ __forceinline__ double wave_sum_l63(double v)
     return v;
 }
 
+// The same tree for a wavefront whose 64 lanes are all active (the resident kernel's sums): the lanes a DPP step leaves
+// without a source keep whatever the destination register held instead of +0.0 -- and no such lane is ever an operand of
+// lane 63's value (every step of lane 63's cone reads a lane of its own row, then lanes 15 / 31), so lane 63 adds the same
+// operands in the same order as wave_sum_l63.  Not having to set the destinations to +0.0 first saves two VALU instructions
+// per step (a step: s_nop 1, two v_mov_b32_dpp, v_add_f64).  Only lane 63 is valid: every other lane may hold anything.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_add_f64_full(double v)
+{
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, ROW_MASK, 0xf, false);
+    return v + __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_sum_l63_full(double v)
+{
+    v = dpp_add_f64_full<0x111, 0xf>(v);
+    v = dpp_add_f64_full<0x112, 0xf>(v);
+    v = dpp_add_f64_full<0x114, 0xf>(v);
+    v = dpp_add_f64_full<0x118, 0xf>(v);
+    v = dpp_add_f64_full<0x142, 0xa>(v);
+    v = dpp_add_f64_full<0x143, 0xc>(v);
+    return v;
+}
+
 // the same sum, returned in every lane (v_readlane of lane 63)
 __device__ __forceinline__ double wave_sum(double v)
 {
     v = wave_sum_l63(v);
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
+                            __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+__device__ __forceinline__ double wave_sum_full(double v)
+{
+    v = wave_sum_l63_full(v);
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
                             __builtin_amdgcn_readlane(__double2loint(v), 63));
 }

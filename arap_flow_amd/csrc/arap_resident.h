@@ -201,11 +201,14 @@ __device__ __forceinline__ double block_sum_uniform(double t)
 __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned long long* gran_group, int rank,
                                           int wgs, float* bcast /* LDS, 2 floats */, unsigned* err, float& out,
                                           bool fast = false, double* out_d = nullptr, bool nowait = false,
-                                          unsigned long long* tm = nullptr /* diagnostic: publish / poll / tail cycles */)
+                                          unsigned long long* tm = nullptr /* diagnostic: publish / poll / tail cycles, ... */,
+                                          unsigned long long* tarr = nullptr /* diagnostic: sum of the publish times (100 MHz) */)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned long long c0 = 0ull, c1;
     if (wave == 0) {
-        unsigned long long c0 = tm ? __builtin_amdgcn_s_memtime() : 0ull, c1;
+        if (tm) c0 = __builtin_amdgcn_s_memtime();
+        if (tarr) *tarr += __builtin_amdgcn_s_memrealtime();     // (the same clock on every XCD: arrival order in a group)
         // the whole group waits for the slowest publisher: this wave's few instructions go first on its SIMD
         __builtin_amdgcn_s_setprio(3);
         unsigned long long* buf = gran_group + (size_t)(epoch & 1u) * wgs * RES_GS;
@@ -242,8 +245,12 @@ __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned 
             if (ok) break;
             if (RES_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
         }
-        if (tm) { c1 = __builtin_amdgcn_s_memtime(); tm[1] += c1 - c0; c0 = c1; }
-        v = wave_sum_l63(v);
+        if (tm) { c1 = __builtin_amdgcn_s_memtime(); tm[1] += c1 - c0; c0 = c1; asm volatile("" : "+v"(v)); }
+        v = wave_sum_l63_full(v);
+        if (tm) {                                     // (lane tree: a part of the tail; the asm keeps the stamp behind the tree)
+            asm volatile("" :: "v"(v));
+            c1 = __builtin_amdgcn_s_memtime(); tm[4] += c1 - c0;
+        }
         if (lane == 63) {
             // value with the sign bit of the second word as the "timed out" flag (one ds_write_b64); the slot
             // alternates with the epoch, so the next call's write cannot overtake a slow reader of this one
@@ -253,11 +260,15 @@ __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned 
             if (!ok) atomicExch(err, 0xDEAD0000u | (epoch & 0xffffu));
         }
         __builtin_amdgcn_s_setprio(0);
-        if (tm) { c1 = __builtin_amdgcn_s_memtime(); tm[2] += c1 - c0; }
+        if (tm) { c1 = __builtin_amdgcn_s_memtime(); tm[2] += c1 - c0; c0 = c1; }
     }
     __syncthreads();
     const float2 bc = *(const float2*)(bcast + 2 * (epoch & 1u));
     out = bc.x;
+    if (tm && wave == 0) {                    // broadcast as wave 0 sees it: barrier + LDS read (the read waited for)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        tm[5] += __builtin_amdgcn_s_memtime() - c0;
+    }
     return bc.y != 0.0f;
 }
 
@@ -301,7 +312,7 @@ __device__ __forceinline__ bool group_sum_h(double part, unsigned epoch, unsigne
             if (ok) break;
             if (RES_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
         }
-        const double ssub = wave_sum(v);                                      // uniform
+        const double ssub = wave_sum_full(v);                                 // uniform
         unsigned long long* buf2 = gran2 + (size_t)(epoch & 1u) * (8 * RES_GRAN2_STRIDE);
         if (ok && srank == 0 && lane < 2) {
             const unsigned long long bits = (unsigned long long)__double_as_longlong(ssub);
@@ -328,7 +339,7 @@ __device__ __forceinline__ bool group_sum_h(double part, unsigned epoch, unsigne
                 if (RES_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
             }
         }
-        v = wave_sum_l63(v);
+        v = wave_sum_l63_full(v);
         if (lane == 63) {
             *(float2*)(bcast + 2 * (epoch & 1u)) = make_float2((float)v, ok2 ? 1.0f : 0.0f);
             if (!ok2) atomicExch(err, 0xDEAD8000u | (epoch & 0x7fffu));
@@ -393,7 +404,7 @@ __device__ __forceinline__ bool group_sum_x(double part, unsigned epoch, unsigne
             if (ok) break;
             if (RES_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
         }
-        v = wave_sum_l63(v);
+        v = wave_sum_l63_full(v);
         if (lane == 63) {
             *(float2*)(bcast + 2 * (epoch & 1u)) = make_float2((float)v, ok ? 1.0f : 0.0f);
             if (!ok) atomicExch(err, 0xDEAD4000u | (epoch & 0x3fffu));
@@ -423,20 +434,28 @@ __device__ __forceinline__ void halo_append(bool take, unsigned short val, unsig
 // block-wide sum of a double over the 4 wavefronts; result valid in LANES 2 AND 3 of wave 0 (the lanes that publish
 // it, group_sum).  Lane k of wave 0 reads the sums of wavefronts k & 3 and (k & 3) ^ 1 -- two independent ds_read_b64, four
 // VGPRs -- adds them (lanes 0, 1: w0 + w1; lanes 2, 3: w2 + w3; the same bits in both lanes of a pair) and one DPP step
-// (row_shr:2) makes (w2 + w3) + (w0 + w1) in lanes 2 and 3.  (Lane 0 reading all four took two ds_read2_b64 into eight
-// VGPRs and four dependent additions; with fewer registers to spare the compiler issued the second read after the first
-// had returned: one more LDS round trip on the critical path of every group sum, 2 % of the run.)
-__device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 doubles */)
+// (row_shr:2) makes (w2 + w3) + (w0 + w1) in lanes 2 and 3 (every other lane of wave 0 holds something undefined: the
+// wave trees and this step are the full-wave DPP forms, arap_device.h: wave_sum_l63_full).  (Lane 0 reading all four
+// took two ds_read2_b64 into eight VGPRs and four dependent additions; with fewer registers to spare the compiler issued
+// the second read after the first had returned: one more LDS round trip on the critical path of every group sum, 2 % of
+// the run.)
+__device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 doubles */,
+                                             unsigned long long* tb = nullptr /* diagnostic: wave tree / LDS + barrier / final level (clocks, wave 0) */)
 {
     static_assert(RES_THREADS / 64 == 4, "one pair sum and one DPP step add four wavefronts");
-    v = wave_sum_l63(v);
+    unsigned long long c0 = 0ull, c1;
+    if (tb) { c0 = __builtin_amdgcn_s_memtime(); asm volatile("" : "+v"(v)); }      // (the tree starts after the stamp)
+    v = wave_sum_l63_full(v);
+    if (tb) { asm volatile("" :: "v"(v)); c1 = __builtin_amdgcn_s_memtime(); tb[0] += c1 - c0; c0 = c1; }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 63) wsum[wave] = v;
     __syncthreads();
     double t = 0.0;
     if (wave == 0) {
         const double a = wsum[lane & 3], b = wsum[(lane & 3) ^ 1];
-        t = dpp_add_f64<0x112, 0xf>(a + b);
+        if (tb) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); c1 = __builtin_amdgcn_s_memtime(); tb[1] += c1 - c0; c0 = c1; }
+        t = dpp_add_f64_full<0x112, 0xf>(a + b);
+        if (tb) { asm volatile("" :: "v"(t)); c1 = __builtin_amdgcn_s_memtime(); tb[2] += c1 - c0; }
     }
     return t;
 }
@@ -456,7 +475,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 {
     static_assert(NS >= 1 && NS <= RES_SLOTS, "slots");
     unsigned long long tA = 0, tS1 = 0, tB = 0, tS2 = 0, tU = 0, t0 = 0, t1 = 0;
-    unsigned long long tm[4] = {0, 0, 0, 0}, tbs = 0, tzr = 0;     // STAMPS: inside the group sums (shader clocks; wave 0)
+    unsigned long long tm[6] = {0, 0, 0, 0, 0, 0}, tbs = 0, tzr = 0;     // STAMPS: inside the group sums (shader clocks; wave 0)
+    unsigned long long tbp[3] = {0, 0, 0}, tarr[2] = {0, 0};   // STAMPS: parts of the block sums; summed publish times of the two sums
 #define RES_STAMP(acc) do { if (STAMPS) { t1 = __builtin_amdgcn_s_memrealtime(); acc += t1 - t0; t0 = t1; } } while (0)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // Group of this workgroup: dealt by the host (ResWg).  Speed only (never correctness): workgroups are dealt
@@ -882,12 +902,12 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         RES_STAMP(tA);
         {
             const unsigned long long cb = STAMPS ? __builtin_amdgcn_s_memtime() : 0ull;
-            const double bs = block_sum8(acc, wsum);
+            const double bs = block_sum8(acc, wsum, STAMPS ? tbp : nullptr);
             if (STAMPS) tbs += __builtin_amdgcn_s_memtime() - cb;
             alive = hierx ? group_sum_x(block_sum_uniform(bs), 2u * l + 2u, gran_group, granx_group, rank, wgs, bcast, rd.err, sigma, subfast)
                   : hier  ? group_sum_h(block_sum_uniform(bs), 2u * l + 2u, gran_group, gran2, rank, wgs, bcast, rd.err, sigma, subfast)
                           : group_sum(bs, 2u * l + 2u, gran_group, rank, wgs, bcast, rd.err, sigma, fast, nullptr, rd.nowait != 0,
-                                      STAMPS ? tm : nullptr);
+                                      STAMPS ? tm : nullptr, STAMPS ? tarr : nullptr);
         }
         if (!alive) break;
         RES_STAMP(tS1);
@@ -923,7 +943,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         RES_STAMP(tB);
         {
             const unsigned long long cb = STAMPS ? __builtin_amdgcn_s_memtime() : 0ull;
-            const double bs = block_sum8(acc, wsum);
+            const double bs = block_sum8(acc, wsum, STAMPS ? tbp : nullptr);
             if (STAMPS) tbs += __builtin_amdgcn_s_memtime() - cb;
             // (past the barrier of the block sum: the staged border z is complete.)  Waves 1-3 publish it, every
             // component a {tag, bits} granule, while wave 0 is busy with the group sum; nothing waits for these stores --
@@ -950,7 +970,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             alive = hierx ? group_sum_x(block_sum_uniform(bs), 2u * l + 3u, gran_group, granx_group, rank, wgs, bcast, rd.err, rhoNew, subfast)
                   : hier  ? group_sum_h(block_sum_uniform(bs), 2u * l + 3u, gran_group, gran2, rank, wgs, bcast, rd.err, rhoNew, subfast)
                           : group_sum(bs, 2u * l + 3u, gran_group, rank, wgs, bcast, rd.err, rhoNew, fast, nullptr, rd.nowait != 0,
-                                      STAMPS ? tm : nullptr);
+                                      STAMPS ? tm : nullptr, STAMPS ? tarr + 1 : nullptr);
         }
         if (!alive) break;
         RES_STAMP(tS2);
@@ -1054,6 +1074,16 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         unsigned long long* o = rd.stamps + (size_t)blockIdx.x * 16;
         o[8] = tbs; o[9] = tm[0]; o[10] = tm[1]; o[11] = tm[2]; o[12] = tm[3]; o[13] = tzr;     // block sums, publish, poll, tail (clocks); sweeps; repeated looks at the z tags (wave 0)
         o[0] = tA; o[1] = tS1; o[2] = tB; o[3] = tS2; o[4] = tU; o[5] = (unsigned long long)tp; { unsigned pc = 0; for (int q = 0; q < 16; ++q) pc += __popc(nbits[q]); o[6] = (unsigned long long)nh | ((unsigned long long)pc << 32) | ((unsigned long long)*nremote << 48); } o[7] = (fast ? 1ull : 0ull) | (zfast ? 2ull : 0ull) | (hier ? 4ull : 0ull) | (subfast ? 8ull : 0ull);
+        // second table (ArapFlow_SolverStampParts): the parts of the on-chip chain at both ends of a group sum (shader clocks of
+        // wave 0, summed over both sums of every iteration), the summed publish times of the two sums (s_memrealtime, one clock
+        // for the whole device: a workgroup's mean arrival against its group's), where the workgroup ran (HW_ID: CU, SIMD..., and
+        // the XCC id), its tile count, halo cells and border-export granules.  Group sums of groups that span XCDs are not split.
+        unsigned long long* q = rd.stamps + (size_t)RES_WGS * 16 + (size_t)blockIdx.x * 16;
+        q[0] = tbp[0]; q[1] = tbp[1]; q[2] = tbp[2]; q[3] = tm[4]; q[4] = tm[5]; q[5] = tarr[0]; q[6] = tarr[1];
+        q[7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4) |                   // HW_REG_HW_ID
+               ((unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15u) << 32);   // HW_REG_XCC_ID
+        q[8] = (unsigned long long)tp; q[9] = (unsigned long long)nh; q[10] = (unsigned long long)tp * RES_ZG;
+        q[11] = (unsigned long long)rank | ((unsigned long long)wgs << 16) | ((unsigned long long)b << 32); q[12] = (unsigned long long)L;
     }
     if (!alive) return;
     // ---- epilogue: the last iteration's delta += alpha p; then the step itself -- PCGLinearUpdate (:552-557) and the cos/sin

@@ -247,6 +247,11 @@ int ArapFlow_SolverLeanStream(ArapFlow_Solver* s);
  * out[512][16] = per workgroup {phase A, wait 1, phase B, wait 2, update} summed 100 MHz ticks of the
  * last resident launch, tiles per workgroup, halo cells.  Returns -1 when stamps are off. */
 int ArapFlow_SolverStamps(ArapFlow_Solver* s, uint64_t* out);
+/* Diagnostic only, same build: out[512][16] = per workgroup the parts of the on-chip chain of its group sums (block sum:
+ * wave tree, LDS + barrier, final level; lane tree, broadcast: shader clocks of wave 0), the summed publish times of the
+ * two sums of an iteration (100 MHz), HW_ID | XCC id << 32, tiles, halo cells, border-export granules, rank | group size
+ * << 16 | batch slot << 32, PCG iterations of the launch.  Returns -1 when stamps are off. */
+int ArapFlow_SolverStampParts(ArapFlow_Solver* s, uint64_t* out);
 
 /* warp_image (ARAP/warping/src/main.cpp:145-225) on DEVICE buffers: rgb uint8[H][W][3], mask_red
  * uint8[H][W], flow float[H][W][2] -> out_rgb uint8[H][W][3], out_mask uint8[H][W].

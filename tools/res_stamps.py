@@ -42,3 +42,50 @@ rows = sorted(zip(o[g0, 5], (out[:, 6] & 0xffffffff).astype(np.float64)[g0], *(o
 print("XCD 0 workgroups: tiles halo | phaseA wait1 phaseB wait2 update | local index")
 for r in rows:
     print("%3d %5d | %5.2f %5.2f %5.2f %5.2f %5.2f | %2d" % (r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]))
+
+# ---- second table (ArapFlow_SolverStampParts): the on-chip chain at both ends of a group sum, and who arrives last ----
+q = np.zeros((512, 16), np.uint64)
+assert st.lib.ArapFlow_SolverStampParts(fs.h, q.ctypes.data) == 0
+qf = q.astype(np.float64)
+one = used & ((out[:, 7] & 4) == 0)         # the split clocks are taken in group_sum (groups on one XCD) only
+per = qf[one] / (2.0 * L)                     # per sum: both sums of every iteration are summed
+print("per group sum, shader clocks (wave 0, mean over %d workgroups):" % int(one.sum()))
+print("  entry: wave tree %.0f | LDS + barrier %.0f | final level %.0f    exit: lane tree %.0f | broadcast (barrier + read) %.0f" % (
+    per[:, 0].mean(), per[:, 1].mean(), per[:, 2].mean(), per[:, 3].mean(), per[:, 4].mean()))
+print("  (LDS + barrier includes the wait for the workgroup's slowest wavefront; each part includes one s_memtime)")
+# arrival: mean publish time of a workgroup over the launch's iterations, against its group's mean (100 MHz -> us)
+rank = (q[:, 11] & 0xffff).astype(np.int64)
+wgs = ((q[:, 11] >> 16) & 0xffff).astype(np.int64)
+slot = (q[:, 11] >> 32).astype(np.int64)
+tiles, halo, exg = qf[:, 8], qf[:, 9], qf[:, 10]
+hw = q[:, 7]
+cukey = ((hw >> 32) << 16) | ((hw >> 8) & 0xff)          # XCC id, SE / SH / CU of HW_ID
+first = np.zeros(512, bool)                               # the CU's first workgroup (lower blockIdx) of the two it holds
+for k in np.unique(cukey[used]):
+    m = np.flatnonzero(used & (cukey == k))
+    first[m.min()] = True
+arr = np.zeros((512, 2))
+for g in np.unique(slot[used]):
+    m = used & (slot == g)
+    for s_ in range(2):
+        t = (q[m, 5 + s_] - q[m, 5 + s_].min()).astype(np.float64) / L      # (integer difference first: the sums are ~1e15)
+        arr[m, s_] = (t - t.mean()) * 0.01
+am = arr[used]
+print("arrival at the group sums, us after the group's mean arrival (mean over the iterations), all workgroups:")
+for s_, nm in enumerate(["sum 1 (sigma)", "sum 2 (rho)"]):
+    print("  %-14s min %+.3f  p25 %+.3f  median %+.3f  p75 %+.3f  max %+.3f   spread per group (max - min): mean %.3f" % (
+        (nm,) + tuple(np.percentile(am[:, s_], [0, 25, 50, 75, 100])) +
+        (np.mean([np.ptp(arr[used & (slot == g), s_]) for g in np.unique(slot[used])]),)))
+def corr(a, b):
+    return float(np.corrcoef(a, b)[0, 1]) if a.std() > 0 and b.std() > 0 else float("nan")
+for s_, nm in enumerate(["sum 1", "sum 2"]):
+    print("  %s: correlation of the arrival with tiles %+.2f, halo cells %+.2f, export granules %+.2f, first of its CU %+.2f;"
+          " mean arrival of the CU's first / second workgroup %+.3f / %+.3f us" % (
+              nm, corr(am[:, s_], tiles[used]), corr(am[:, s_], halo[used]), corr(am[:, s_], exg[used]),
+              corr(am[:, s_], first[used].astype(float)), arr[used & first, s_].mean(), arr[used & ~first, s_].mean()))
+g0 = slot[used].min()
+m = np.flatnonzero(used & (slot == g0))
+print("group of batch slot %d (%d workgroups), sorted by arrival at sum 1: rank tiles halo export CU-mate | arrival sum 1 / sum 2 (us)" % (g0, len(m)))
+for i in m[np.argsort(arr[m, 0])]:
+    print("  %3d %3d %4d %4d %-6s | %+.3f %+.3f" % (rank[i], tiles[i], halo[i], exg[i], "first" if first[i] else "second",
+                                                  arr[i, 0], arr[i, 1]))
