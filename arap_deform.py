@@ -4,6 +4,9 @@
   python arap_deform.py RGB Mask Constraint Flow warped_RGB warped_Mask       (one frame)
   python arap_deform.py listfile                                              (one solve per line, 6 paths)
 
+A list line may carry optional tokens after its six paths: bwd=PATH.flo (backward flow), occ=PATH.png (forward
+occlusion), occ_bwd=PATH.png (backward occlusion); other trailing tokens are ignored.
+
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
 same border pins, same outputs (.flo + two PNGs).  ARAP_PLAN may name the reference's arap_plan.t; it is then
 checked by Opt_ProblemDefine (anything that is not the ARAP energy is rejected); unset = built-in energy.
@@ -29,10 +32,13 @@ def usage():
 
 def main(argv):
     from arap_flow_amd import opt, pipeline
+    extras = None
     if len(argv) == 7:
         lines = [tuple(argv[1:7])]
     elif len(argv) == 2:
-        lines = pipeline.read_list(argv[1])
+        lines_ex = pipeline.read_list_ex(argv[1])
+        lines = [ln for ln, _ in lines_ex]
+        extras = [ex for _, ex in lines_ex]
     else:
         print("Invalid Input!")
         usage()
@@ -52,7 +58,7 @@ def main(argv):
         if not pr:
             return 1
         state.lib.Opt_ProblemDelete(state.handle, pr)
-    pipeline.deform_list(state, lines, 19, 8, 400)
+    pipeline.deform_list(state, lines, 19, 8, 400, extras=extras)
     state.close()
     return 0
 

@@ -64,7 +64,14 @@ SYMBOLS = [
     ("ArapFlow_SolverStampParts", _I, [_VP, _VP]),
     ("ArapFlow_WarpScratchBytes", C.c_uint64, [_U, _U]),
     ("ArapFlow_Warp", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("ArapFlow_SolverSetOutputs", _I, [_VP, _I]),
+    ("ArapFlow_SolverGetExtraResults", _I, [_VP, _U, _VP, _VP, _VP]),
+    ("ArapFlow_SolverHostExtraResults", _I, [_VP, _U, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP)]),
+    ("ArapFlow_WarpExScratchBytes", C.c_uint64, [_U, _U]),
+    ("ArapFlow_WarpEx", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 ]
+
+OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h
 
 _LIB = None
 

@@ -1,0 +1,195 @@
+// arap_occ.h -- backward flow and occlusion maps from the warp rasteriser (gfx950).
+//
+// Definitions: DESIGN.md "Backward flow and occlusion".  All kernels take the same WarpJob array as k_warp_raster /
+// k_warp_resolve (arap_warp.h) and only run when a caller asked for the outputs; with the outputs off none of them is
+// launched.  Integer atomics only (a count per cell); every output is a function of the inputs alone.
+//
+// Order on the stream:  k_warp_raster -> k_warp_keys -> [k_occ_count -> k_occ_scan -> k_occ_scatter -> k_occ_tri]
+//                       -> k_warp_resolve (which clears the keys k_warp_keys reads).
+#pragma once
+#include "arap_warp.h"
+
+namespace arap {
+
+// quad (qx, qy) is rasterised iff it lies in the grid and its four corners are object (k_warp_raster)
+__device__ __forceinline__ bool quad_on(const uint8_t* mask, int W, int H, int qx, int qy)
+{
+    if (qx < 0 || qy < 0 || qx + 1 >= W || qy + 1 >= H) return false;
+    const size_t i = qx + (size_t)W * qy;
+    return mask[i] == 0 && mask[i + 1] == 0 && mask[i + W] == 0 && mask[i + W + 1] == 0;
+}
+
+// m(v): the largest index of a rasterised triangle with vertex (x, y) as a corner, or -1.  The vertex is p00 of quad
+// (x,y) (triangle 2u only), p01 of quad (x-1,y) and p10 of quad (x,y-1) (both triangles), p11 of quad (x-1,y-1)
+// (triangle 2u+1 only): in decreasing order of the largest index
+__device__ __forceinline__ int own_max_tri(const uint8_t* mask, int W, int H, int x, int y)
+{
+    const int u = x + W * y;
+    if (quad_on(mask, W, H, x, y)) return 2 * u;
+    if (quad_on(mask, W, H, x - 1, y)) return 2 * (u - 1) + 1;
+    if (quad_on(mask, W, H, x, y - 1)) return 2 * (u - W) + 1;
+    if (quad_on(mask, W, H, x - 1, y - 1)) return 2 * (u - W - 1) + 1;
+    return -1;
+}
+
+__device__ __forceinline__ bool in_frame(float2 P, int W, int H)
+{
+    return P.x >= 0.f && P.x <= (float)(W - 1) && P.y >= 0.f && P.y <= (float)(H - 1);     // false on NaN
+}
+
+// Backward pass, before k_warp_resolve.  Per frame-2 pixel q: the winner T(q) = key's triangle; B(q) = s - q with s
+// the source point interpolated at q with the rasteriser's barycentrics; OccBwd(q) = uncovered object pixel; and the
+// forward occlusion of a background pixel = covered.  Each output only if its pointer is set.
+// grid = (ceil(N/256), 1, njobs), block = 256
+__global__ __launch_bounds__(256) void k_warp_keys(const WarpJob* jobs, int W, int N)
+{
+    const WarpJob j = jobs[blockIdx.z];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const unsigned long long k = j.key[i];
+    const int qy = i / W, qx = i - qy * W;
+    if (j.occ && j.mask[i] != 0) j.occ[i] = k ? 255 : 0;
+    if (j.occ_bwd) j.occ_bwd[i] = (!k && j.mask[i] == 0) ? 255 : 0;
+    if (!j.bwd) return;
+    float2 b = make_float2(0.f, 0.f);
+    if (k) {
+        const unsigned t = (unsigned)(k >> 32) - 1u;
+        const int u = (int)(t >> 1);
+        const int uy = u / W, ux = u - uy * W;
+        // corners of triangle t and their grid coordinates: 2u = (p00, p01, p10), 2u+1 = (p10, p01, p11)
+        const int odd = (int)(t & 1u);
+        const int ax = ux, ay = uy + odd, bx = ux + 1, by = uy, cx = ux + odd, cy = uy + 1;
+        const float2 p0 = warp_pos(j, ax, ay, ax + W * ay), p1 = warp_pos(j, bx, by, bx + W * by);
+        const float2 p2 = warp_pos(j, cx, cy, cx + W * cy);
+        const float sx = (float)qx, sy = (float)qy;
+        float b0, b1, b2;
+        if (tri_bary(p0, p1, p2, sx, sy, b0, b1, b2)) {      // (always: the raster passed this test at q)
+            const float srcx = ((float)ax * b0 + (float)bx * b1) + (float)cx * b2;
+            const float srcy = ((float)ay * b0 + (float)by * b1) + (float)cy * b2;
+            b = make_float2(srcx - sx, srcy - sy);
+        }
+    }
+    j.bwd[i] = b;
+}
+
+// Forward occlusion, pass 1: per object vertex v, P(v) out of frame -> Occ = 255; else Occ = 0 and v is counted in
+// cell (floor P.x, floor P.y).  The returned old count is v's rank in the cell, so the scatter needs no atomics.  (Under
+// a smooth warp a cell holds about one vertex: the counts hardly collide, and the compiler's per-wave aggregation of
+// same-address atomics has nothing to merge.)
+// grid = (ceil(N/256), 1, njobs), block = 256
+__global__ __launch_bounds__(256) void k_occ_count(const WarpJob* jobs, int W, int H, int N)
+{
+    const WarpJob j = jobs[blockIdx.z];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N || j.mask[i] != 0) return;
+    const int y = i / W, x = i - y * W;
+    const float2 P = warp_pos(j, x, y, i);
+    const bool in = in_frame(P, W, H);
+    j.occ[i] = in ? 0 : 255;
+    if (!in) return;
+    const int c = (int)floorf(P.x) + W * (int)floorf(P.y);
+    j.rank[i] = atomicAdd(j.cell + c, 1u);
+}
+
+// pass 2: exclusive scan of the N cell counts in place (cell[N] = total).  One workgroup per frame walks the frame in
+// chunks of 4096 counts: 4 per lane (one 16-byte load), wave scan by shuffles, wave totals through LDS.
+// grid = (1, 1, njobs), block = 1024
+__global__ __launch_bounds__(1024) void k_occ_scan(const WarpJob* jobs, int N)
+{
+    const WarpJob j = jobs[blockIdx.z];
+    unsigned* cnt = j.cell;
+    __shared__ unsigned wsum[2][16];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned carry = 0;
+    int par = 0;
+    for (int base = 0; base < N; base += 4096, par ^= 1) {
+        const int i0 = base + 4 * (int)threadIdx.x;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (i0 + 3 < N) v = *(const uint4*)(cnt + i0);      // (cell is 256-byte aligned, i0 % 4 == 0)
+        else {
+            if (i0 < N) v.x = cnt[i0];
+            if (i0 + 1 < N) v.y = cnt[i0 + 1];
+            if (i0 + 2 < N) v.z = cnt[i0 + 2];
+        }
+        const unsigned s = (v.x + v.y) + (v.z + v.w);
+        unsigned inc = s;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned t = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) wsum[par][wid] = inc;
+        __syncthreads();                        // (double-buffered wsum: one barrier per chunk)
+        unsigned pre = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const unsigned t = wsum[par][w];
+            pre += w < wid ? t : 0u;
+            tot += t;
+        }
+        unsigned e = carry + pre + (inc - s);
+        uint4 o4;
+        o4.x = e; e += v.x;
+        o4.y = e; e += v.y;
+        o4.z = e; e += v.z;
+        o4.w = e;
+        if (i0 + 3 < N) *(uint4*)(cnt + i0) = o4;
+        else {
+            if (i0 < N) cnt[i0] = o4.x;
+            if (i0 + 1 < N) cnt[i0 + 1] = o4.y;
+            if (i0 + 2 < N) cnt[i0 + 2] = o4.z;
+        }
+        carry += tot;
+    }
+    if (threadIdx.x == 0) cnt[N] = carry;
+}
+
+// pass 3: every counted vertex to its slot: bin[start(cell) + rank] = {P.x, P.y, v, m(v)}
+// grid = (ceil(N/256), 1, njobs), block = 256
+__global__ __launch_bounds__(256) void k_occ_scatter(const WarpJob* jobs, int W, int H, int N)
+{
+    const WarpJob j = jobs[blockIdx.z];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N || j.mask[i] != 0) return;
+    const int y = i / W, x = i - y * W;
+    const float2 P = warp_pos(j, x, y, i);
+    if (!in_frame(P, W, H)) return;
+    const int c = (int)floorf(P.x) + W * (int)floorf(P.y);
+    j.bin[j.cell[c] + j.rank[i]] = make_int4(__float_as_int(P.x), __float_as_int(P.y), i, own_max_tri(j.mask, W, H, x, y));
+}
+
+__device__ __forceinline__ void occ_tri(const WarpJob& j, int W, int H, int tri, float2 p0, float2 p1, float2 p2)
+{
+    int xa, ya;
+    float maxx, maxy;
+    if (!tri_cells(W, H, p0, p1, p2, xa, ya, maxx, maxy)) return;
+    for (int x = xa; x < W && (float)x <= maxx; ++x)
+        for (int y = ya; y < H && (float)y <= maxy; ++y) {
+            const int c = x + W * y;
+            const unsigned e = j.cell[c + 1];
+            for (unsigned k = j.cell[c]; k < e; ++k) {
+                const int4 v = j.bin[k];
+                if (tri <= v.w) continue;              // one of v's own triangles, or an earlier one
+                float b0, b1, b2;
+                if (tri_bary(p0, p1, p2, __int_as_float(v.x), __int_as_float(v.y), b0, b1, b2)) j.occ[v.z] = 255;
+            }
+        }
+}
+
+// pass 4: every rasterised triangle t tests the vertices binned in the cells raster_tri visits for t: a later
+// triangle that is not one of v's own and that the rasteriser would show at P(v) occludes v.  Only ever writes 255.
+// grid = (ceil(W/64), ceil(H/4), njobs), block = (64,4)
+__global__ __launch_bounds__(256) void k_occ_tri(const WarpJob* jobs, int W, int H)
+{
+    const WarpJob j = jobs[blockIdx.z];
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x + 1 >= W || y + 1 >= H) return;
+    if (!quad_on(j.mask, W, H, x, y)) return;
+    const int i = x + W * y;
+    const float2 p00 = warp_pos(j, x, y, i), p01 = warp_pos(j, x + 1, y, i + 1);
+    const float2 p10 = warp_pos(j, x, y + 1, i + W), p11 = warp_pos(j, x + 1, y + 1, i + W + 1);
+    occ_tri(j, W, H, 2 * i, p00, p01, p10);
+    occ_tri(j, W, H, 2 * i + 1, p10, p01, p11);
+}
+
+}  // namespace arap

@@ -27,6 +27,13 @@ struct WarpJob {                    // one frame
     unsigned long long* key;        // [N] scratch, all zero on entry
     uint8_t* out_rgb;               // [N][3] or NULL
     uint8_t* out_mask;              // [N]
+    // optional outputs of arap_occ.h (DESIGN.md "Backward flow and occlusion"): NULL = not wanted
+    float2* bwd;                    // [N] backward flow, frame-2 domain
+    uint8_t* occ_bwd;               // [N] 255 = revealed background in frame 2
+    uint8_t* occ;                   // [N] 255 = frame-1 pixel occluded in frame 2
+    unsigned* cell;                 // [N+1] scratch of the occlusion query: per-cell counts -> starts, zero on entry
+    unsigned* rank;                 // [N]   scratch: a vertex's rank inside its cell
+    int4* bin;                      // [N]   scratch: binned vertices {P.x, P.y, v, m(v)}
 };
 
 __device__ __forceinline__ float2 warp_pos(const WarpJob& j, int x, int y, int i)
@@ -36,31 +43,52 @@ __device__ __forceinline__ float2 warp_pos(const WarpJob& j, int x, int y, int i
     return make_float2((float)x + f.x, (float)y + f.y);
 }
 
-__device__ __forceinline__ void raster_tri(const WarpJob& j, int W, int H, unsigned tri, float2 p0, float2 p1,
-                                           float2 p2, const float c0[3], const float c1[3], const float c2[3])
+// The rasteriser's inside test and barycentrics of triangle (p0, p1, p2) at the point (sx, sy) (main.cpp:69-104).  The
+// one copy of this expression: raster_tri, the backward pass and the occlusion query (arap_occ.h) all call it, so their
+// float results cannot drift apart.  Returns false where the rasteriser skips the point.
+__device__ __forceinline__ bool tri_bary(float2 p0, float2 p1, float2 p2, float sx, float sy, float& b0, float& b1,
+                                         float& b2)
+{
+    const float X0 = p0.x - sx * 1.0f, X1 = p1.x - sx * 1.0f, X2 = p2.x - sx * 1.0f;
+    const float Y0 = p0.y - sy * 1.0f, Y1 = p1.y - sy * 1.0f, Y2 = p2.y - sy * 1.0f;
+    float d01 = X0 * Y1 - Y0 * X1;
+    float d12 = X1 * Y2 - Y1 * X2;
+    float d20 = X2 * Y0 - Y2 * X0;
+    if ((d01 < 0) & (d12 < 0) & (d20 < 0)) return false;
+    const float OneOverD = 1.f / ((d01 + d12) + d20);
+    d01 *= OneOverD;
+    d12 *= OneOverD;
+    d20 *= OneOverD;
+    if (!(d01 >= 0 && d12 >= 0 && d20 >= 0)) return false;
+    b0 = d12; b1 = d20; b2 = d01;
+    return true;
+}
+
+// the cells raster_tri visits for a triangle: x = xa, xa+1, .. while x < W and x <= maxx (y likewise); false if none
+// (a NaN corner)
+__device__ __forceinline__ bool tri_cells(int W, int H, float2 p0, float2 p1, float2 p2, int& xa, int& ya, float& maxx,
+                                          float& maxy)
 {
     const float minx = floorf(fminf(p0.x, fminf(p1.x, p2.x)));
     const float miny = floorf(fminf(p0.y, fminf(p1.y, p2.y)));
-    const float maxx = ceilf(fmaxf(p0.x, fmaxf(p1.x, p2.x)));
-    const float maxy = ceilf(fmaxf(p0.y, fmaxf(p1.y, p2.y)));
-    if (!(minx == minx && miny == miny && maxx == maxx && maxy == maxy)) return;
-    const int xa = minx < 0.f ? 0 : (minx > (float)W ? W : (int)minx);
-    const int ya = miny < 0.f ? 0 : (miny > (float)H ? H : (int)miny);
+    maxx = ceilf(fmaxf(p0.x, fmaxf(p1.x, p2.x)));
+    maxy = ceilf(fmaxf(p0.y, fmaxf(p1.y, p2.y)));
+    if (!(minx == minx && miny == miny && maxx == maxx && maxy == maxy)) return false;
+    xa = minx < 0.f ? 0 : (minx > (float)W ? W : (int)minx);
+    ya = miny < 0.f ? 0 : (miny > (float)H ? H : (int)miny);
+    return true;
+}
+
+__device__ __forceinline__ void raster_tri(const WarpJob& j, int W, int H, unsigned tri, float2 p0, float2 p1,
+                                           float2 p2, const float c0[3], const float c1[3], const float c2[3])
+{
+    int xa, ya;
+    float maxx, maxy;
+    if (!tri_cells(W, H, p0, p1, p2, xa, ya, maxx, maxy)) return;
     for (int x = xa; x < W && (float)x <= maxx; ++x)
         for (int y = ya; y < H && (float)y <= maxy; ++y) {
-            const float sx = (float)x, sy = (float)y;
-            const float X0 = p0.x - sx * 1.0f, X1 = p1.x - sx * 1.0f, X2 = p2.x - sx * 1.0f;
-            const float Y0 = p0.y - sy * 1.0f, Y1 = p1.y - sy * 1.0f, Y2 = p2.y - sy * 1.0f;
-            float d01 = X0 * Y1 - Y0 * X1;
-            float d12 = X1 * Y2 - Y1 * X2;
-            float d20 = X2 * Y0 - Y2 * X0;
-            if ((d01 < 0) & (d12 < 0) & (d20 < 0)) continue;
-            const float OneOverD = 1.f / ((d01 + d12) + d20);
-            d01 *= OneOverD;
-            d12 *= OneOverD;
-            d20 *= OneOverD;
-            if (!(d01 >= 0 && d12 >= 0 && d20 >= 0)) continue;
-            const float b0 = d12, b1 = d20, b2 = d01;
+            float b0, b1, b2;
+            if (!tri_bary(p0, p1, p2, (float)x, (float)y, b0, b1, b2)) continue;
             unsigned rgbv = 0;
             if (j.rgb) {
 #pragma unroll

@@ -29,6 +29,7 @@
 #include "arap_tiled.h"
 #include "arap_stream.h"
 #include "arap_warp.h"
+#include "arap_occ.h"
 
 using namespace arap;
 
@@ -1537,6 +1538,29 @@ struct FrameDev {              // per-slot images owned by the frame solver
     unsigned long long* key;
 };
 
+struct FrameExt {              // per-slot optional warp outputs + occlusion scratch (ArapFlow_SolverSetOutputs)
+    float2* bwd;
+    uint8_t *occ_bwd, *occ;
+    unsigned *cell, *rank;
+    int4* bin;
+};
+
+// the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
+// the jobs' cell arrays, `cell_bytes` contiguous bytes, zeroed here
+static void enqueue_warp_outputs(hipStream_t stream, const WarpJob* dj, unsigned njobs, int W, int H, int outputs,
+                                 void* cells, size_t cell_bytes)
+{
+    const int N = W * H;
+    const dim3 g1((N + 255) / 256, 1, njobs);
+    hipLaunchKernelGGL(k_warp_keys, g1, dim3(256), 0, stream, dj, W, N);
+    if (!(outputs & ARAPFLOW_OUT_OCCLUSION)) return;
+    HC(hipMemsetAsync(cells, 0, cell_bytes, stream));
+    hipLaunchKernelGGL(k_occ_count, g1, dim3(256), 0, stream, dj, W, H, N);
+    hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, njobs), dim3(1024), 0, stream, dj, N);
+    hipLaunchKernelGGL(k_occ_scatter, g1, dim3(256), 0, stream, dj, W, H, N);
+    hipLaunchKernelGGL(k_occ_tri, dim3((W + 63) / 64, (H + 3) / 4, njobs), dim3(64, 4), 0, stream, dj, W, H);
+}
+
 // resetGPU (CombinedSolver.h:207-221): U = O = (x,y), A = 0, Mask = (float)red
 __global__ __launch_bounds__(256) void k_frame_reset(const FrameDev* fr, int W, int N)
 {
@@ -1602,6 +1626,16 @@ struct ArapFlow_Solver {
     unsigned launches_at_enqueue = 0; // plan->res_launches when the pending solve call was enqueued
     unsigned a_n = 0, a_numIter = 0, a_nIt = 0, a_lIt = 0;
     int a_warp = 0, a_download = 0;
+    // optional warp outputs (ArapFlow_SolverSetOutputs); every buffer is allocated when first asked for
+    int outputs = 0;                 // ARAPFLOW_OUT_* bits for the next warps
+    int warp_outputs = 0;            // ... in effect at the last warp
+    int dl_outputs = 0;              // ... downloaded by the last solve call
+    void* ext = nullptr;             // device: [batch] x FrameExt buffers, then the [batch] cell arrays
+    std::vector<FrameExt> hext;
+    unsigned* ext_cells = nullptr;
+    size_t ext_cell_slot = 0;
+    char* pin_ext = nullptr;         // [batch] x {bwd float2[N], occ_bwd u8[N], occ u8[N]}   (allocated on first download)
+    size_t pin_ext_slot = 0;
 };
 
 static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
@@ -1616,10 +1650,20 @@ static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
         j.mask = f.mask; j.flow_out = f.flow; j.key = f.key;
         j.out_rgb = s->has_rgb[b] ? f.out_rgb : nullptr;
         j.out_mask = f.out_mask;
+        const int o = s->outputs;
+        const FrameExt* e = o ? &s->hext[b] : nullptr;
+        j.bwd = (o & ARAPFLOW_OUT_BACKWARD) ? e->bwd : nullptr;
+        j.occ_bwd = (o & ARAPFLOW_OUT_BACKWARD) ? e->occ_bwd : nullptr;
+        j.occ = (o & ARAPFLOW_OUT_OCCLUSION) ? e->occ : nullptr;
+        j.cell = e ? e->cell : nullptr; j.rank = e ? e->rank : nullptr; j.bin = e ? e->bin : nullptr;
     }
     HC(hipMemcpyAsync(s->djobs, jobs, sizeof(WarpJob) * nframes, hipMemcpyHostToDevice, st->stream));
     const dim3 g((s->W + 63) / 64, (s->H + 3) / 4, nframes);
     hipLaunchKernelGGL(k_warp_raster, g, dim3(64, 4), 0, st->stream, s->djobs, s->W, s->H);
+    if (s->outputs)
+        enqueue_warp_outputs(st->stream, s->djobs, nframes, s->W, s->H, s->outputs, s->ext_cells,
+                             s->ext_cell_slot * nframes);
+    s->warp_outputs = s->outputs;
     hipLaunchKernelGGL(k_warp_resolve, dim3((s->N + 255) / 256, 1, nframes), dim3(256), 0, st->stream, s->djobs,
                        s->N);
 }
@@ -1670,6 +1714,23 @@ static void solver_enqueue(ArapFlow_Solver* s)
             HC(hipMemcpyAsync(o, f.flow, 8 * N, hipMemcpyDeviceToHost, s->copy));
             if (s->has_rgb[b]) HC(hipMemcpyAsync(o + 8 * N, f.out_rgb, 3 * N, hipMemcpyDeviceToHost, s->copy));
             HC(hipMemcpyAsync(o + 11 * N, f.out_mask, N, hipMemcpyDeviceToHost, s->copy));
+        }
+        s->dl_outputs = s->a_warp ? s->outputs : 0;
+        if (s->dl_outputs) {
+            if (!s->pin_ext) {
+                s->pin_ext_slot = align_up(10 * N, 256);
+                HC(hipHostMalloc((void**)&s->pin_ext, s->pin_ext_slot * s->batch, hipHostMallocDefault));
+            }
+            for (unsigned b = 0; b < nframes; ++b) {
+                const FrameExt& e = s->hext[b];
+                char* o = s->pin_ext + s->pin_ext_slot * b;
+                if (s->dl_outputs & ARAPFLOW_OUT_BACKWARD) {
+                    HC(hipMemcpyAsync(o, e.bwd, 8 * N, hipMemcpyDeviceToHost, s->copy));
+                    HC(hipMemcpyAsync(o + 8 * N, e.occ_bwd, N, hipMemcpyDeviceToHost, s->copy));
+                }
+                if (s->dl_outputs & ARAPFLOW_OUT_OCCLUSION)
+                    HC(hipMemcpyAsync(o + 9 * N, e.occ, N, hipMemcpyDeviceToHost, s->copy));
+            }
         }
         HC(hipEventRecord(s->ev_dl, s->copy));
     }
@@ -1760,6 +1821,8 @@ void ArapFlow_SolverFree(ArapFlow_Solver* s)
     if (s->pin_out) (void)hipHostFree(s->pin_out);
     if (s->pin_jobs) (void)hipHostFree(s->pin_jobs);
     if (s->pin_err) (void)hipHostFree(s->pin_err);
+    if (s->pin_ext) (void)hipHostFree(s->pin_ext);
+    if (s->ext) (void)hipFree(s->ext);
     (void)hipFree(s->block);
     delete s;
 }
@@ -1904,6 +1967,71 @@ int ArapFlow_SolverWarp(ArapFlow_Solver* s, unsigned nframes)
     return 0;
 }
 
+int ArapFlow_SolverSetOutputs(ArapFlow_Solver* s, int which)
+{
+    if (!s || (which & ~(ARAPFLOW_OUT_BACKWARD | ARAPFLOW_OUT_OCCLUSION))) return -1;
+    if (s->inflight) { const int rc = ArapFlow_SolverWait(s); if (rc != 0) return rc; }
+    if (which && !s->ext) {
+        HC(hipSetDevice(s->st->device));
+        const size_t N = s->N;
+        const size_t per = align_up(8 * N, 256) + 2 * align_up(N, 256) + align_up(4 * N, 256) + align_up(16 * N, 256);
+        s->ext_cell_slot = align_up(4 * (N + 1), 256);
+        HC(hipMalloc(&s->ext, (per + s->ext_cell_slot) * s->batch));
+        HC(hipMemsetAsync(s->ext, 0, (per + s->ext_cell_slot) * s->batch, s->st->stream));
+        char* c = (char*)s->ext;
+        auto take = [&](size_t b) { char* r = c; c += b; return r; };
+        s->hext.resize(s->batch);
+        for (int b = 0; b < s->batch; ++b) {
+            FrameExt& e = s->hext[b];
+            e.bwd = (float2*)take(align_up(8 * N, 256));
+            e.occ_bwd = (uint8_t*)take(align_up(N, 256)); e.occ = (uint8_t*)take(align_up(N, 256));
+            e.rank = (unsigned*)take(align_up(4 * N, 256)); e.bin = (int4*)take(align_up(16 * N, 256));
+        }
+        s->ext_cells = (unsigned*)c;
+        for (int b = 0; b < s->batch; ++b) s->hext[b].cell = (unsigned*)take(s->ext_cell_slot);
+        HC(hipStreamSynchronize(s->st->stream));
+        if (s->st->own_stream && !s->pin_ext) {   // (as pin_out: downloads will be asked for)
+            s->pin_ext_slot = align_up(10 * N, 256);
+            HC(hipHostMalloc((void**)&s->pin_ext, s->pin_ext_slot * s->batch, hipHostMallocDefault));
+        }
+    }
+    s->outputs = which;
+    return 0;
+}
+
+int ArapFlow_SolverGetExtraResults(ArapFlow_Solver* s, unsigned slot, float* bwd, uint8_t* occ_bwd, uint8_t* occ)
+{
+    if (!s || slot >= (unsigned)s->batch) return -1;
+    if (s->inflight && ArapFlow_SolverWait(s) != 0) return -1;
+    if (((bwd || occ_bwd) && !(s->warp_outputs & ARAPFLOW_OUT_BACKWARD)) ||
+        (occ && !(s->warp_outputs & ARAPFLOW_OUT_OCCLUSION)))
+        return -1;
+    HC(hipStreamSynchronize(s->st->stream));
+    const FrameExt& e = s->hext[slot];
+    const size_t N = s->N;
+    hipStream_t cs = s->copy;
+    if (bwd) HC(hipMemcpyAsync(bwd, e.bwd, 8 * N, hipMemcpyDeviceToHost, cs));
+    if (occ_bwd) HC(hipMemcpyAsync(occ_bwd, e.occ_bwd, N, hipMemcpyDeviceToHost, cs));
+    if (occ) HC(hipMemcpyAsync(occ, e.occ, N, hipMemcpyDeviceToHost, cs));
+    HC(hipStreamSynchronize(cs));
+    return 0;
+}
+
+int ArapFlow_SolverHostExtraResults(ArapFlow_Solver* s, unsigned slot, const float** bwd, const uint8_t** occ_bwd,
+                                    const uint8_t** occ)
+{
+    if (!s || slot >= (unsigned)s->batch || !s->a_download || slot >= s->a_n) return -1;
+    if (s->inflight && ArapFlow_SolverWait(s) != 0) return -1;
+    if (!s->dl_outputs || !s->pin_ext) return -1;
+    const size_t N = s->N;
+    const char* o = s->pin_ext + s->pin_ext_slot * slot;
+    const bool b = s->dl_outputs & ARAPFLOW_OUT_BACKWARD, c = s->dl_outputs & ARAPFLOW_OUT_OCCLUSION;
+    if (bwd) *bwd = b ? (const float*)o : nullptr;
+    if (occ_bwd) *occ_bwd = b ? (const uint8_t*)(o + 8 * N) : nullptr;
+    if (occ) *occ = c ? (const uint8_t*)(o + 9 * N) : nullptr;
+    return 0;
+}
+
 int ArapFlow_SolverHostResults(ArapFlow_Solver* s, unsigned slot, const float** flow, const uint8_t** warped_rgb,
                                const uint8_t** warped_mask)
 {
@@ -2033,6 +2161,42 @@ int ArapFlow_Warp(Opt_State* st, unsigned W, unsigned H, const void* rgb, const 
     HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
     hipLaunchKernelGGL(k_warp_raster, dim3((W + 63) / 64, (H + 3) / 4, 1), dim3(64, 4), 0, st->stream, dj, (int)W,
                        (int)H);
+    hipLaunchKernelGGL(k_warp_resolve, dim3((unsigned)((N + 255) / 256), 1, 1), dim3(256), 0, st->stream, dj,
+                       (int)N);
+    return (int)hipGetLastError();
+}
+
+uint64_t ArapFlow_WarpExScratchBytes(unsigned W, unsigned H)
+{
+    const uint64_t N = (uint64_t)W * H;
+    return align_up(N * 8, 256) + align_up(4 * (N + 1), 256) + align_up(4 * N, 256) + align_up(16 * N, 256) + 256;
+}
+
+int ArapFlow_WarpEx(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* mask_red, const void* flow,
+                    void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ, void* scratch)
+{
+    if (!st || !mask_red || !flow || !out_mask || !scratch || W == 0 || H == 0) return -1;
+    const size_t N = (size_t)W * H;
+    char* c = (char*)scratch;
+    auto take = [&](size_t b) { char* r = c; c += b; return r; };
+    WarpJob j{};
+    j.field = nullptr; j.flow_in = (const float2*)flow;
+    j.rgb = (const uint8_t*)rgb; j.mask = (const uint8_t*)mask_red;
+    j.flow_out = nullptr;
+    j.key = (unsigned long long*)take(align_up(N * 8, 256));
+    j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
+    j.bwd = (float2*)out_bwd; j.occ_bwd = (uint8_t*)out_occ_bwd; j.occ = (uint8_t*)out_occ;
+    j.cell = (unsigned*)take(align_up(4 * (N + 1), 256));
+    j.rank = (unsigned*)take(align_up(4 * N, 256));
+    j.bin = (int4*)take(align_up(16 * N, 256));
+    WarpJob* dj = (WarpJob*)c;
+    const int outputs = (out_bwd || out_occ_bwd ? ARAPFLOW_OUT_BACKWARD : 0) | (out_occ ? ARAPFLOW_OUT_OCCLUSION : 0);
+    HC(hipMemsetAsync(scratch, 0, N * 8, st->stream));
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
+    hipLaunchKernelGGL(k_warp_raster, dim3((W + 63) / 64, (H + 3) / 4, 1), dim3(64, 4), 0, st->stream, dj, (int)W,
+                       (int)H);
+    if (outputs)
+        enqueue_warp_outputs(st->stream, dj, 1, (int)W, (int)H, outputs, j.cell, 4 * (N + 1));
     hipLaunchKernelGGL(k_warp_resolve, dim3((unsigned)((N + 255) / 256), 1, 1), dim3(256), 0, st->stream, dj,
                        (int)N);
     return (int)hipGetLastError();

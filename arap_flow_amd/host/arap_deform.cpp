@@ -3,6 +3,9 @@
 //   ./arap_deform RGB Mask Constraint Flow warped_RGB warped_Mask        (one frame)
 //   ./arap_deform listfile                                               (six paths per line)
 //   ./arap_deform --serve                                                (addition: the same lines on stdin, until EOF)
+// A list or --serve line may carry optional tokens after its six paths (addition, DESIGN.md "Backward flow and
+// occlusion"): bwd=PATH.flo (backward flow), occ=PATH.png (forward occlusion), occ_bwd=PATH.png (backward
+// occlusion), 8-bit 0/255.  Other trailing tokens are ignored, as before.
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
 // here consecutive frames of equal size are handed to the device-resident batched solver, as many as fit one launch
 // (ArapFlow_Solver = CombinedSolver on the GPU: reset, 19-step constraint ramp, 8 GN x 400 PCG, flow, rasteriser).
@@ -39,6 +42,11 @@ extern "C" {
 // one solve = one list-file line (ARAP/deformation/src/main.cpp:4-11,183-191)
 struct SolvePaths {
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
+    std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
+    int outputs() const
+    {
+        return (bwd.empty() && occ_bwd.empty() ? 0 : ARAPFLOW_OUT_BACKWARD) | (occ.empty() ? 0 : ARAPFLOW_OUT_OCCLUSION);
+    }
 };
 
 // the usage text of the reference's executable (main.cpp:13-24), verbatim: it is part of the CLI contract
@@ -110,7 +118,13 @@ static bool load_frame(const SolvePaths& paths, Frame& f)
 static bool parse_line(const std::string& line, SolvePaths& q)
 {
     std::istringstream tok(line);
-    return (bool)(tok >> q.rgb >> q.mask >> q.constraints >> q.flow >> q.warped_rgb >> q.warped_mask);
+    if (!(tok >> q.rgb >> q.mask >> q.constraints >> q.flow >> q.warped_rgb >> q.warped_mask)) return false;
+    for (std::string t; tok >> t;) {
+        if (t.compare(0, 4, "bwd=") == 0) q.bwd = t.substr(4);
+        else if (t.compare(0, 4, "occ=") == 0) q.occ = t.substr(4);
+        else if (t.compare(0, 8, "occ_bwd=") == 0) q.occ_bwd = t.substr(8);
+    }
+    return true;
 }
 
 // ---- where the lines come from: a finished list, or stdin as it arrives (--serve) ------------------------------------
@@ -181,7 +195,7 @@ class FrameSource {
 };
 
 // ---- results: read back from the solver's pinned buffers, encoded and written by worker threads ---------------------
-struct Result { SolvePaths paths; std::vector<float> flow; std::vector<uint8_t> wrgb, wmsk; };
+struct Result { SolvePaths paths; std::vector<float> flow, bwd; std::vector<uint8_t> wrgb, wmsk, occ_bwd, occ; };
 
 class Writer {
   public:
@@ -196,6 +210,11 @@ class Writer {
             if (!arapio::write_png_rgb(r->paths.warped_rgb, w, h, r->wrgb.data(), err)) printf("%s\n", err.c_str());
             if (!arapio::write_png_mask1(r->paths.warped_mask, w, h, r->wmsk.data(), err)) printf("%s\n", err.c_str());
             arapio::write_flo(r->paths.flow, r->flow.data(), w, h);
+            if (!r->paths.bwd.empty()) arapio::write_flo(r->paths.bwd, r->bwd.data(), w, h);
+            if (!r->paths.occ_bwd.empty() && !arapio::write_png_gray8(r->paths.occ_bwd, w, h, r->occ_bwd.data(), err))
+                printf("%s\n", err.c_str());
+            if (!r->paths.occ.empty() && !arapio::write_png_gray8(r->paths.occ, w, h, r->occ.data(), err))
+                printf("%s\n", err.c_str());
             std::lock_guard<std::mutex> g(*pm);
             if (report) printf("Done %s\n", r->paths.flow.c_str());     // --serve: one line per finished solve
             else printf("Saved\n");
@@ -302,6 +321,15 @@ int main(int argc, const char* argv[])
             r->flow.assign(flow, flow + 2 * n);
             r->wrgb.assign(wrgb, wrgb + 3 * n);
             r->wmsk.assign(wmsk, wmsk + n);
+            if (r->paths.outputs()) {
+                const float* bwd; const uint8_t *obwd, *occ;
+                if (ArapFlow_SolverHostExtraResults(L.solver, (unsigned)b, &bwd, &obwd, &occ) != 0) {
+                    printf("ARAP extra results unavailable\n");
+                    return false;
+                }
+                if (bwd) { r->bwd.assign(bwd, bwd + 2 * n); r->occ_bwd.assign(obwd, obwd + n); }
+                if (occ) r->occ.assign(occ, occ + n);
+            }
             writer.submit(r, sw, sh);
         }
         L.batch.clear();
@@ -310,6 +338,12 @@ int main(int argc, const char* argv[])
     };
     auto launch = [&](Lane& L) -> bool {
         if (L.batch.empty()) return true;
+        int outputs = 0;                     // what any line of the batch asks for (off for plain lines: no extra kernel)
+        for (const SolvePaths& q : L.batch) outputs |= q.outputs();
+        if (ArapFlow_SolverSetOutputs(L.solver, outputs) != 0) {
+            printf("ARAP outputs could not be set\n");
+            return false;
+        }
         if (ArapFlow_SolverSolveAsync(L.solver, (unsigned)L.batch.size(), numIter, nonLinearIter, linearIter, 1, 1) != 0) {
             printf("ARAP solve could not be started\n");
             return false;

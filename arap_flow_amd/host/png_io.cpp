@@ -174,6 +174,17 @@ bool write_png_rgb(const std::string& path, int w, int h, const uint8_t* rgb, st
     return write_png(path, w, h, 8, 2, rows, err);
 }
 
+bool write_png_gray8(const std::string& path, int w, int h, const uint8_t* gray, std::string& err)
+{
+    std::vector<uint8_t> rows(((size_t)w + 1) * h);
+    for (int y = 0; y < h; ++y) {
+        uint8_t* r = &rows[((size_t)w + 1) * y];
+        r[0] = 0;                                        // filter type None
+        memcpy(r + 1, gray + (size_t)y * w, (size_t)w);
+    }
+    return write_png(path, w, h, 8, 0, rows, err);
+}
+
 bool write_png_mask1(const std::string& path, int w, int h, const uint8_t* mask, std::string& err)
 {
     const size_t stride = ((size_t)w + 7) / 8;

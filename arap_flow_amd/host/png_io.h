@@ -20,5 +20,6 @@ struct Image {
 bool read_png_rgb(const std::string& path, Image& out, std::string& err);
 bool write_png_rgb(const std::string& path, int w, int h, const uint8_t* rgb, std::string& err);
 bool write_png_mask1(const std::string& path, int w, int h, const uint8_t* mask /* 0 / non-zero */, std::string& err);
+bool write_png_gray8(const std::string& path, int w, int h, const uint8_t* gray, std::string& err);   // 8-bit L
 
 }  // namespace arapio

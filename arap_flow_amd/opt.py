@@ -6,6 +6,7 @@
                    (the reference's own host loop: ramp on the host, one Opt_ProblemSolve per ramp step)
   FrameSolver      the device-resident batched counterpart (ArapFlow_Solver*, include/arap_opt.h part 2)
   warp_image       ARAP/warping/src/main.cpp:145-225 through ArapFlow_Warp
+  warp_image_ex    the same, plus backward flow and occlusion maps (ArapFlow_WarpEx)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -288,6 +289,16 @@ class FrameSolver:
         self.h = self.lib.ArapFlow_SolverCreate(state.handle, self.W, self.H, self.batch)
         if not self.h:
             raise RuntimeError("ArapFlow_SolverCreate failed")
+        self.outputs = 0
+
+    def set_outputs(self, backward=False, occlusion=False):
+        """optional outputs of every later warp (ArapFlow_SolverSetOutputs): backward flow + backward occlusion,
+        forward occlusion.  results() / host_results() then carry backward_flow, occlusion_bwd, occlusion -- when the
+        last warp (or download) computed them; otherwise they return the base results without those keys."""
+        which = (capi.OUT_BACKWARD if backward else 0) | (capi.OUT_OCCLUSION if occlusion else 0)
+        if self.lib.ArapFlow_SolverSetOutputs(self.h, which) != 0:
+            raise RuntimeError("ArapFlow_SolverSetOutputs failed")
+        self.outputs = which
 
     def set_frame(self, slot, mask_red, constraints, rgb=None, border_pins=True):
         mask_red = np.ascontiguousarray(mask_red, np.uint8)
@@ -335,9 +346,19 @@ class FrameSolver:
         def view(ptr, ctype, shape):
             n = int(np.prod(shape))
             return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).reshape(shape)
-        return dict(flow=view(pf, C.c_float, (H, W, 2)),
-                    warped_rgb=view(pr, C.c_uint8, (H, W, 3)) if pr.value else None,
-                    warped_mask=view(pm, C.c_uint8, (H, W)))
+        out = dict(flow=view(pf, C.c_float, (H, W, 2)),
+                   warped_rgb=view(pr, C.c_uint8, (H, W, 3)) if pr.value else None,
+                   warped_mask=view(pm, C.c_uint8, (H, W)))
+        if self.outputs:
+            pb, pob, po = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            rc = self.lib.ArapFlow_SolverHostExtraResults(self.h, slot, C.byref(pb), C.byref(pob), C.byref(po))
+            if rc != 0:                 # (that solve computed or downloaded none: the base results only)
+                return out
+            if pb.value:
+                out.update(backward_flow=view(pb, C.c_float, (H, W, 2)), occlusion_bwd=view(pob, C.c_uint8, (H, W)))
+            if po.value:
+                out.update(occlusion=view(po, C.c_uint8, (H, W)))
+        return out
 
     def warp(self, nframes=None):
         n = self.batch if nframes is None else nframes
@@ -358,7 +379,18 @@ class FrameSolver:
                                                 C.byref(cost))
         if rc != 0:
             raise ValueError("ArapFlow_SolverGetResults: bad arguments")
-        return dict(flow=flow, warped_rgb=wrgb, warped_mask=wmsk, offset=off, angle=ang, cost=cost.value)
+        out = dict(flow=flow, warped_rgb=wrgb, warped_mask=wmsk, offset=off, angle=ang, cost=cost.value)
+        if self.outputs:
+            bwd = np.empty((H, W, 2), np.float32) if self.outputs & capi.OUT_BACKWARD else None
+            obwd = np.empty((H, W), np.uint8) if self.outputs & capi.OUT_BACKWARD else None
+            occ = np.empty((H, W), np.uint8) if self.outputs & capi.OUT_OCCLUSION else None
+            if self.lib.ArapFlow_SolverGetExtraResults(self.h, slot, p(bwd), p(obwd), p(occ)) != 0:
+                return out              # (the last warp did not compute them: the base results only)
+            if bwd is not None:
+                out.update(backward_flow=bwd, occlusion_bwd=obwd)
+            if occ is not None:
+                out.update(occlusion=occ)
+        return out
 
     def stats(self):
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -394,3 +426,32 @@ def warp_image(state, rgb, mask_red, flow):
         raise RuntimeError("ArapFlow_Warp failed: %d" % rc)
     torch.cuda.synchronize()
     return o_rgb.cpu().numpy(), o_msk.cpu().numpy()
+
+
+def warp_image_ex(state, rgb, mask_red, flow, backward=True, occlusion=True):
+    """warp_image plus the optional outputs (ArapFlow_WarpEx): a dict of warped_rgb, warped_mask and, as asked for,
+    backward_flow f32[H,W,2] + occlusion_bwd u8[H,W], occlusion u8[H,W].  rgb may be None."""
+    lib = state.lib
+    H, W = mask_red.shape
+    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
+    d_msk = torch.from_numpy(np.ascontiguousarray(mask_red, np.uint8)).cuda()
+    d_flow = torch.from_numpy(np.ascontiguousarray(flow, np.float32)).cuda()
+    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
+    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
+    o_bwd = torch.empty(H, W, 2, dtype=torch.float32, device="cuda") if backward else None
+    o_obwd = torch.empty(H, W, dtype=torch.uint8, device="cuda") if backward else None
+    o_occ = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occlusion else None
+    scratch = torch.empty(int(lib.ArapFlow_WarpExScratchBytes(W, H)), dtype=torch.uint8, device="cuda")
+    p = lambda t: _dev_ptr(t) if t is not None else None
+    torch.cuda.synchronize()
+    rc = lib.ArapFlow_WarpEx(state.handle, W, H, p(d_rgb), p(d_msk), p(d_flow), p(o_rgb), p(o_msk), p(o_bwd),
+                             p(o_obwd), p(o_occ), p(scratch))
+    if rc != 0:
+        raise RuntimeError("ArapFlow_WarpEx failed: %d" % rc)
+    torch.cuda.synchronize()
+    out = dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy())
+    if backward:
+        out.update(backward_flow=o_bwd.cpu().numpy(), occlusion_bwd=o_obwd.cpu().numpy())
+    if occlusion:
+        out.update(occlusion=o_occ.cpu().numpy())
+    return out

@@ -7,6 +7,8 @@ functions that tests/golden/host/ pins with hand-computed cases:
   warp_files                ARAP/warping/src/main.cpp:302-336      (warp_image)
   cover_scale, fit_bg, add_bg            para_gen.py:36-61      (background compositing)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
+  parse_extra, read_list_ex              optional output tokens of a list line (bwd= occ= occ_bwd=)
+  merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
   resize_crop_geometry, scale_rotate     para_gen.py:253-291
   make_arap_path                         para_gen.py:331-339
@@ -44,6 +46,44 @@ def read_list(path):
     return lines
 
 
+EXTRA_KEYS = ("bwd", "occ", "occ_bwd")
+
+
+def parse_extra(tokens):
+    """optional tokens after a line's paths: bwd=PATH.flo, occ=PATH.png, occ_bwd=PATH.png -> {key: path}.  Any other
+    token is ignored (a line's tokens after the sixth always were)."""
+    out = {}
+    for t in tokens:
+        k, eq, v = t.partition("=")
+        if eq and k in EXTRA_KEYS and v:
+            out[k] = v
+    return out
+
+
+def extra_tokens(extra):
+    """the inverse of parse_extra, in a fixed order"""
+    return ["%s=%s" % (k, extra[k]) for k in EXTRA_KEYS if extra.get(k)]
+
+
+def read_list_ex(path):
+    """read_list plus each line's optional output tokens: [(six paths, {key: path})]"""
+    lines = []
+    with open(path) as f:
+        for line in f:
+            tok = line.split()
+            if not tok:
+                continue
+            if len(tok) < 6:
+                raise ValueError("list line needs 6 paths: %r" % line)
+            lines.append((tuple(tok[:6]), parse_extra(tok[6:])))
+    return lines
+
+
+def save_occ(occ, path):
+    """an occlusion map as an 8-bit L PNG, 0 / 255"""
+    Image.fromarray(np.ascontiguousarray(occ, np.uint8), "L").save(path)
+
+
 def load_rgb(path):
     return np.array(Image.open(path).convert("RGB"))
 
@@ -68,20 +108,29 @@ def _load_line(ln):
     return load_rgb(ln[0]), load_mask_red(ln[1]), opt.load_constraints(ln[2])
 
 
-def _save_result(ln, r):
+def _save_result(ln, r, extra=None):
     Image.fromarray(r["warped_rgb"]).save(ln[4])
     save_mask(r["warped_mask"], ln[5])
     flo.flow_write(ln[3], r["flow"])
+    extra = extra or {}
+    if "bwd" in extra:
+        flo.flow_write(extra["bwd"], r["backward_flow"])
+    if "occ_bwd" in extra:
+        save_occ(r["occlusion_bwd"], extra["occ_bwd"])
+    if "occ" in extra:
+        save_occ(r["occlusion"], extra["occ"])
 
 
-def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, max_batch=FILL_MAX, verbose=True):
+def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, max_batch=FILL_MAX, verbose=True,
+                extras=None):
     """arap_deform over a list (main.cpp:223-238).  Frames of equal size are solved together: the library gives
     every solve a group of the resident launch's workgroups sized by its active tiles, and a launch costs the same
     however full it is, so frames are added to a batch while they still fit ONE launch (8 DAVIS-shaped 854x480
     frames, ~24 --multseg segment solves); FILL_MIN frames per call when the resident path does not apply.
     The GPU does not wait for the host (the structure of arap_flow_amd/host/arap_deform.cpp): two solver objects
     alternate; while one batch is solved the next is decoded (worker threads) and uploaded into the other object, and
-    the previous batch's results are read from pinned memory and encoded (worker threads)."""
+    the previous batch's results are read from pinned memory and encoded (worker threads).
+    `extras`: per line the optional outputs it asks for ({key: path}, parse_extra), or None."""
     from concurrent.futures import ThreadPoolExecutor
     from . import opt
     state.use_own_stream()
@@ -96,7 +145,7 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
             return loading[k].result()
 
         writing = []
-        lanes = [dict(solver=None, batch=[]), dict(solver=None, batch=[])]
+        lanes = [dict(solver=None, batch=[], extra=[]), dict(solver=None, batch=[], extra=[])]
         size = None
 
         def drain(lane):
@@ -104,10 +153,10 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
             if not lane["batch"]:
                 return
             lane["solver"].wait()
-            for b, ln in enumerate(lane["batch"]):
+            for b, (ln, ex) in enumerate(zip(lane["batch"], lane["extra"])):
                 r = lane["solver"].host_results(b)
-                res = dict(flow=r["flow"].copy(), warped_rgb=r["warped_rgb"].copy(), warped_mask=r["warped_mask"].copy())
-                writing.append(pool.submit(_save_result, ln, res))
+                res = {k: v.copy() for k, v in r.items() if v is not None}
+                writing.append(pool.submit(_save_result, ln, res, ex))
                 if verbose:
                     print("Saved")                                          # main.cpp:159
             lane["batch"] = []
@@ -135,6 +184,7 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
             batch = []
             j = i
             while j < len(lines) and len(batch) < max_batch:
+                ex = extras[j] if extras is not None else None
                 ln = lines[j]
                 rgb, mask, cons = frame_at(j)
                 if rgb.shape[:2] != (H, W):
@@ -148,11 +198,15 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
                     if launches > 1 or (launches == 0 and b >= FILL_MIN):
                         break                                   # this frame opens the next batch (its slot is re-set)
                 batch.append(ln)
+                lane["extra"].append(ex)
                 del loading[j]                                  # the device holds it now
                 j += 1
+            want = set().union(*[e or {} for e in lane["extra"]])
+            solver.set_outputs(backward=bool(want & {"bwd", "occ_bwd"}), occlusion="occ" in want)
             solver.solve_async(len(batch), num_iter, non_linear_iter, linear_iter, warp=True, download=True)
             lane["batch"] = batch
-            drain(other)                                        # the previous batch, while this one is being solved
+            drain(other)
+            other["extra"] = []                                        # the previous batch, while this one is being solved
             cur ^= 1
             i = j
         for lane in (lanes[cur], lanes[cur ^ 1]):
@@ -164,12 +218,24 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
                 lane["solver"].close()
 
 
-def warp_files(state, rgb_path, mask_path, flo_path, out_rgb_path, out_mask_path):
-    """warp_image (ARAP/warping/src/main.cpp:302-336)"""
+def warp_files(state, rgb_path, mask_path, flo_path, out_rgb_path, out_mask_path, extra=None):
+    """warp_image (ARAP/warping/src/main.cpp:302-336); `extra` ({key: path}, parse_extra): the optional outputs"""
     from . import opt
     rgb, mask, fl = load_rgb(rgb_path), load_mask_red(mask_path), flo.flow_read(flo_path)
     if fl.shape[:2] != mask.shape or rgb.shape[:2] != mask.shape:
         raise ValueError("image, mask and flow sizes differ")
+    if extra:
+        r = opt.warp_image_ex(state, rgb, mask, fl, backward=bool({"bwd", "occ_bwd"} & set(extra)),
+                              occlusion="occ" in extra)
+        Image.fromarray(r["warped_rgb"]).save(out_rgb_path)
+        save_mask(r["warped_mask"], out_mask_path)
+        if "bwd" in extra:
+            flo.flow_write(extra["bwd"], r["backward_flow"])
+        if "occ_bwd" in extra:
+            save_occ(r["occlusion_bwd"], extra["occ_bwd"])
+        if "occ" in extra:
+            save_occ(r["occlusion"], extra["occ"])
+        return
     wrgb, wmsk = opt.warp_image(state, rgb, mask, fl)
     Image.fromarray(wrgb).save(out_rgb_path)
     save_mask(wmsk, out_mask_path)
@@ -363,3 +429,37 @@ def flatten(arap_seg_paths, remove=True):
         Image.fromarray(rgb.astype(np.uint8).squeeze()).save(out_rgb)
         Image.fromarray(mask.astype(np.uint8)).save(out_mask)     # a 1-bit mask file comes out 0 / 1 valued, as in the reference
     return [e[0] for e in arap_seg_paths]
+
+
+def merge_backward(bwds, covers, objects):
+    """--multseg: the per-segment backward flows (segment, H, W, 2) of one frame become one, exactly: at every pixel the
+    LAST segment whose warped mask covers it wins (the top layer, as merge_segments picks the warped RGB); where no
+    segment covers it the flow is 0 and the backward occlusion is 255 if the pixel was object in frame 1 in any
+    segment.  covers, objects: (segment, H, W) bool.  Returns (backward flow, backward occlusion u8 0/255)."""
+    covers = np.asarray(covers, bool)
+    n = covers.shape[0]
+    any_cover = covers.any(0)
+    winner = (n - 1) - np.argmax(covers[::-1], axis=0)
+    bwd = np.take_along_axis(np.asarray(bwds, np.float32), winner[None, ..., None], axis=0)[0]
+    bwd[~any_cover] = 0
+    occ_bwd = np.where(~any_cover & np.asarray(objects, bool).any(0), 255, 0).astype(np.uint8)
+    return bwd, occ_bwd
+
+
+def flatten_backward(frame_extra, seg_lines, seg_extras, remove=True):
+    """merge_backward at file level, before flatten removes the segments' warped masks: reads every segment's backward
+    flow, warped mask (a line's last path) and frame-1 mask (second path: red channel 0 = object), writes the frame's
+    files named in `frame_extra` ({key: path}) and deletes the segments' backward files."""
+    covers = [np.asarray(Image.open(ln.split(" ")[5])) != 0 for ln in seg_lines]
+    objects = [load_mask_red(ln.split(" ")[1]) == 0 for ln in seg_lines]
+    bwds = [flo.flow_read(e["bwd"]) for e in seg_extras]
+    bwd, occ_bwd = merge_backward(bwds, covers, objects)
+    if "bwd" in frame_extra:
+        flo.flow_write(frame_extra["bwd"], bwd)
+    if "occ_bwd" in frame_extra:
+        save_occ(occ_bwd, frame_extra["occ_bwd"])
+    if remove:
+        for e in seg_extras:
+            for q in e.values():
+                if osp.exists(q):
+                    os.remove(q)

@@ -182,6 +182,25 @@ int ArapFlow_SolverWait(ArapFlow_Solver* s);
 int ArapFlow_SolverHostResults(ArapFlow_Solver* s, unsigned slot, const float** flow, const uint8_t** warped_rgb,
                                const uint8_t** warped_mask);
 
+/* Optional outputs of the warp (DESIGN.md "Backward flow and occlusion"; all off by default, and then no extra kernel
+ * runs).  ArapFlow_SolverSetOutputs(s, which) selects them, with `which` an OR of
+ *   ARAPFLOW_OUT_BACKWARD   backward flow float[H][W][2] (frame 2 -> frame 1; 0 where nothing is drawn) and the
+ *                           backward occlusion uint8[H][W] (255 = frame-2 object pixel left uncovered: revealed)
+ *   ARAPFLOW_OUT_OCCLUSION  forward occlusion uint8[H][W] (255 = frame-1 pixel not visible in frame 2)
+ * for every later ArapFlow_SolverWarp and SolveAsync(.., warp = 1, ..).  The device buffers (about 34 bytes per pixel
+ * and slot, output and scratch) are allocated at the first call that turns an output on.  Returns 0, -1 on bad
+ * arguments.
+ * ArapFlow_SolverGetExtraResults: synchronise and copy one slot's outputs of the last warp to HOST buffers (any may be
+ * NULL); -1 if a requested output was off at that warp.
+ * ArapFlow_SolverHostExtraResults: pointers into the solver's pinned buffers filled by a `download` solve (valid until
+ * the next solve of this solver; NULL for an output that was off); -1 if that solve downloaded none. */
+#define ARAPFLOW_OUT_BACKWARD 1
+#define ARAPFLOW_OUT_OCCLUSION 2
+int ArapFlow_SolverSetOutputs(ArapFlow_Solver* s, int which);
+int ArapFlow_SolverGetExtraResults(ArapFlow_Solver* s, unsigned slot, float* bwd, uint8_t* occ_bwd, uint8_t* occ);
+int ArapFlow_SolverHostExtraResults(ArapFlow_Solver* s, unsigned slot, const float** bwd, const uint8_t** occ_bwd,
+                                    const uint8_t** occ);
+
 /* copyResultToCPU + warpField (CombinedSolver.h:280-366) on the device for slots [0, nframes):
  * flow = Offset - grid, and the forward triangle rasterisation of rgb and mask with the solved
  * Offset as warp field.  Asynchronous. */
@@ -260,6 +279,15 @@ int ArapFlow_SolverStampParts(ArapFlow_Solver* s, uint64_t* out);
 uint64_t ArapFlow_WarpScratchBytes(unsigned W, unsigned H);
 int ArapFlow_Warp(Opt_State* state, unsigned W, unsigned H, const void* rgb, const void* mask_red,
                   const void* flow, void* out_rgb, void* out_mask, void* scratch);
+
+/* ArapFlow_Warp plus the optional outputs on DEVICE buffers, each NULL when not wanted: out_bwd float[H][W][2],
+ * out_occ_bwd uint8[H][W], out_occ uint8[H][W] (see ArapFlow_SolverSetOutputs).  `scratch` is a 256-byte aligned
+ * device buffer of ArapFlow_WarpExScratchBytes(W,H) bytes.  With all three NULL this is ArapFlow_Warp.  Asynchronous
+ * on the state's stream.  Returns 0, -1 on bad arguments, or a HIP error code. */
+uint64_t ArapFlow_WarpExScratchBytes(unsigned W, unsigned H);
+int ArapFlow_WarpEx(Opt_State* state, unsigned W, unsigned H, const void* rgb, const void* mask_red,
+                    const void* flow, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ,
+                    void* scratch);
 
 #ifdef __cplusplus
 }

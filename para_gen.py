@@ -2,6 +2,7 @@
 """para_gen -- Python 3 twin of the reference's dataset generator CLI (para_gen.py:341-653), same flags.
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
+                     [--bwd_flow] [--occ]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -51,6 +52,8 @@ from arap_flow_amd import pipeline          # noqa: E402
 orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen.py:18-26
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
+bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
+EXTRA_OF = dict(bwd_gen="bwd", occbwd_gen="occ_bwd", occ_gen="occ")   # path key -> list-line token
 CPP_BIN = osp.join(HERE, "arap_flow_amd", "bin", "arap_deform")
 
 
@@ -148,24 +151,36 @@ def prepare_pair(args):
     else:
         out1 = im1
     Image.fromarray(out1).save(p["rgb1_gen"])
-    seg_paths = None
+    seg_paths, seg_extras = None, None
     if not flags.multseg:
         mask = np.zeros_like(mk1, dtype=np.uint8)
         mask[mk1 == 0] = pipeline.ARAP_BG                                      # :514-517
         Image.fromarray(mask).save(p["msk1_gen"])
     else:
-        seg_paths = []
+        seg_paths, seg_extras = [], []
         for s, mask in pipeline.split_segments(mk1, valids):                   # :518-540
             p_ = pipeline.replace_ext(p, s, keep_orgs=["rgb1_gen", "cstr_tmp"])
             Image.fromarray(mask).save(p_["msk1_gen"])
             seg_paths.append(pipeline.make_arap_path(p_))
-    return dict(arap_path=arap_path, seg_paths=seg_paths, bg=bgim)
+            seg_extras.append(_extra(p_))
+    return dict(arap_path=arap_path, seg_paths=seg_paths, bg=bgim, extra=_extra(p), seg_extras=seg_extras)
+
+
+def _extra(p):
+    """the optional outputs of one solve, {token key: path}"""
+    return {t: p[k] for k, t in EXTRA_OF.items() if k in p}
+
+
+def _line(arap_path, extra):
+    return " ".join([arap_path] + pipeline.extra_tokens(extra))
 
 
 def finish_frame(args):
     """para_gen.py:202-212 for one frame whose solve(s) are done: flatten the segments, composite the background"""
-    arap_path, seg_paths, bg = args
+    arap_path, seg_paths, bg, extra, seg_extras = args
     if seg_paths is not None:
+        if extra:                                           # (before flatten removes the segments' warped masks)
+            pipeline.flatten_backward(extra, seg_paths, seg_extras)
         pipeline.flatten([(arap_path, seg_paths)])
     if bg is not None:
         pt, mk = arap_path.split(" ")[-2:]
@@ -322,7 +337,8 @@ def scan(flags, input_root, output_root):
     """para_gen.py:384-432"""
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
-                                                           msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir).items()}
+                                                           msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
+                                                           obw=occ_bwd_dir, occ=occ_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
     all_paths = []
     for root, dirs, _ in os.walk(rgb_org):
@@ -343,9 +359,14 @@ def scan(flags, input_root, output_root):
                          cstr_tmp=osp.join(roots["cst"], seq, f + ".txt"), flow_gen=osp.join(roots["flo"], seq, f + ".flo"),
                          rgb1_org=osp.join(rgb_org, seq, f1), msk1_org=osp.join(msk_org, seq, f + ".png"),
                          rgb2_org=osp.join(rgb_org, seq, f2 + ext), msk2_org=osp.join(msk_org, seq, f2 + ".png"))
+                if getattr(flags, "bwd_flow", False):
+                    e.update(bwd_gen=osp.join(roots["bwd"], seq, f + ".flo"), occbwd_gen=osp.join(roots["obw"], seq, f + ".png"))
+                if getattr(flags, "occ", False):
+                    e.update(occ_gen=osp.join(roots["occ"], seq, f + ".png"))
                 e = {k: osp.abspath(v) for k, v in e.items()}
                 e["_seq"], e["_stem"] = seq, f
-                if not flags.resume or not osp.exists(e["flow_gen"]):            # --resume (:431)
+                done = [e["flow_gen"]] + [e[k] for k in EXTRA_OF if k in e]    # every requested output
+                if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
 
@@ -389,11 +410,12 @@ def main(flags):
     all_paths = scan(flags, input_root, output_root)
     print("Scanning data to be processed\t\t%d files [Done]" % len(all_paths))
     os.makedirs(output_root, exist_ok=True)
-    lmdb_paths = []
+    lmdb_paths, ext_paths = [], []
     for p in all_paths:
         q = {k: v for k, v in p.items() if not k.startswith("_")}
         ap = pipeline.make_arap_path(q).split(" ")
         lmdb_paths.append(" ".join([ap[0], ap[4], ap[3]]))
+        ext_paths.append(" ".join([ap[0], ap[4], ap[3]] + [q[k] for k in EXTRA_OF if k in q]))
 
     # backgrounds: drawn without replacement until the list is used up, then refilled (para_gen.py:484-499)
     tmp_paths, picks = [], []
@@ -421,7 +443,8 @@ def main(flags):
             if rec["left"] > 0:
                 return
             counts["frames_done"] += 1
-            posts.append(pool.apply_async(finish_frame, ((rec["arap_path"], rec["seg_paths"], rec["bg"]),)))
+            posts.append(pool.apply_async(finish_frame, ((rec["arap_path"], rec["seg_paths"], rec["bg"], rec["extra"],
+                                                          rec["seg_extras"]),)))
 
     # --dm_bin builtin: the matcher and the solver must not share a GPU at the same time (the solver's resident kernel
     # needs the whole chip: arap_resident.h), so the run has two phases -- every pair is prepared and matched first
@@ -445,14 +468,16 @@ def main(flags):
             if res is None:
                 continue
             lines = [res["arap_path"]] if res["seg_paths"] is None else res["seg_paths"]
+            extras = [res["extra"]] if res["seg_paths"] is None else res["seg_extras"]
             if not lines:
                 continue
-            rec = dict(arap_path=res["arap_path"], seg_paths=res["seg_paths"], bg=res["bg"], left=len(lines))
+            rec = dict(arap_path=res["arap_path"], seg_paths=res["seg_paths"], bg=res["bg"], left=len(lines),
+                       extra=res["extra"], seg_extras=res["seg_extras"])
             with lock:
                 for ln in lines:
                     frames[ln.split(" ")[3]] = rec
-            for ln in lines:
-                workers.put(ln)
+            for ln, ex in zip(lines, extras):
+                workers.put(_line(ln, ex))
             n_solves += len(lines)
             n_frames += 1
         workers.close()
@@ -466,6 +491,9 @@ def main(flags):
                 p.kill()
     out_paths = [ln for ln in lmdb_paths if all(osp.exists(q) for q in ln.split(" "))]   # :588-603
     open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
+    if getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False):     # all_files.list stays as it is; the extra outputs get their own list
+        ext = [ln for ln in ext_paths if all(osp.exists(q) for q in ln.split(" "))]
+        open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt,
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
@@ -475,6 +503,13 @@ def main(flags):
     open(osp.join(output_root, "arap_stats.json"), "w").write(json.dumps(stats))
     print("Finished: %d frames (%d solves) in %.2f s, mean batch %.1f" % (n_frames, n_solves, dt, stats["mean_batch"]))
     return out_paths
+
+
+def own_arap_bin(cmd):
+    """is --arap_bin this repository's driver (the C++ arap_deform, or arap_deform.py under an interpreter)?"""
+    tok = cmd.split()
+    own = {CPP_BIN, osp.join(HERE, "arap_deform.py")}
+    return bool(tok) and (osp.abspath(tok[0]) in own or (len(tok) > 1 and osp.abspath(tok[1]) in own))
 
 
 def parse(argv=None):
@@ -518,7 +553,18 @@ def parse(argv=None):
                         help="Path to the deep matching binary, or 'builtin': this repo's GPU matcher (libarapmatch.so)")
     parser.add_argument("--matches", default=None, help="directory of precomputed matches (instead of --dm_bin)")
     parser.add_argument("--bg_dir", default=None, help="directory of background images")
+    parser.add_argument("--bwd_flow", action="store_true", default=False,
+                        help="also write the backward flow OUT/FlowBwd/<seq>/<frame>.flo and the backward occlusion "
+                             "OUT/OccBwd/<seq>/<frame>.png (DESIGN.md)")
+    parser.add_argument("--occ", action="store_true", default=False,
+                        help="also write the forward occlusion OUT/Occ/<seq>/<frame>.png (DESIGN.md)")
     flags = parser.parse_args(argv)
+    if flags.occ and flags.multseg:
+        parser.error("--occ cannot be combined with --multseg: forward occlusion across segments needs one query over "
+                     "every segment's solve, which this generator does not do (--bwd_flow --multseg is supported)")
+    if (flags.bwd_flow or flags.occ) and not own_arap_bin(flags.arap_bin):
+        parser.error("--bwd_flow / --occ need this repository's arap_deform (C++ or arap_deform.py): a foreign "
+                     "--arap_bin does not write the extra outputs")
     if flags.size is not None:
         flags.size = tuple(int(s) for s in flags.size)
     assert 0 < flags.fd < 20, "Invalid fd number!"

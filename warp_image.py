@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """warp_image -- command-line twin of ARAP/warping/src/main.cpp:302-336.
 
-  python warp_image.py image mask flow warped_image warped_mask
+  python warp_image.py image mask flow warped_image warped_mask [bwd=PATH.flo] [occ=PATH.png] [occ_bwd=PATH.png]
+
+The optional tokens also write the backward flow and the occlusion maps.
 """
 import os
 import sys
@@ -21,13 +23,15 @@ def usage():
 
 
 def main(argv):
-    if len(argv) != 6:
+    from arap_flow_amd import pipeline
+    extra = pipeline.parse_extra(argv[6:])
+    if len(argv) < 6 or not all(pipeline.parse_extra([t]) for t in argv[6:]):
         print("Invalid Input! ", end="")
         usage()
         return 1
-    from arap_flow_amd import opt, pipeline
+    from arap_flow_amd import opt
     state = opt.State()
-    pipeline.warp_files(state, *argv[1:6])
+    pipeline.warp_files(state, *argv[1:6], extra=extra)
     state.close()
     print("Saved")
     return 0
