@@ -6,6 +6,9 @@
 
 A list line may carry optional tokens after its six paths: bwd=PATH.flo (backward flow), occ=PATH.png (forward
 occlusion), occ_bwd=PATH.png (backward occlusion); other trailing tokens are ignored.
+A line whose first word is `layers` is no solve but the layered warp of one frame (DESIGN.md "Layered warp"):
+  layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P]
+It runs once every earlier line of the list is solved and written (its inputs may be their outputs).
 
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
 same border pins, same outputs (.flo + two PNGs).  ARAP_PLAN may name the reference's arap_plan.t; it is then
@@ -32,13 +35,14 @@ def usage():
 
 def main(argv):
     from arap_flow_amd import opt, pipeline
-    extras = None
     if len(argv) == 7:
-        lines = [tuple(argv[1:7])]
+        lines = [("solve", tuple(argv[1:7]), None)]
     elif len(argv) == 2:
-        lines_ex = pipeline.read_list_ex(argv[1])
-        lines = [ln for ln, _ in lines_ex]
-        extras = [ex for _, ex in lines_ex]
+        try:
+            lines = pipeline.read_list_items(argv[1])
+        except ValueError as e:
+            print(e)
+            return 1
     else:
         print("Invalid Input!")
         usage()
@@ -58,7 +62,22 @@ def main(argv):
         if not pr:
             return 1
         state.lib.Opt_ProblemDelete(state.handle, pr)
-    pipeline.deform_list(state, lines, 19, 8, 400, extras=extras)
+    # runs of solve lines go to the batched solver; a layers line waits for the run before it
+    k = 0
+    while k < len(lines):
+        if lines[k][0] == "layers":
+            pipeline.run_layers(state, lines[k][1])
+            print("Saved")
+            k += 1
+            continue
+        e = k
+        while e < len(lines) and lines[e][0] == "solve":
+            e += 1
+        run = lines[k:e]
+        extras = [ex for _, _, ex in run]
+        pipeline.deform_list(state, [ln for _, ln, _ in run], 19, 8, 400,
+                             extras=None if all(ex is None for ex in extras) else extras)
+        k = e
     state.close()
     return 0
 

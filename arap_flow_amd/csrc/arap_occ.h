@@ -37,6 +37,25 @@ __device__ __forceinline__ bool in_frame(float2 P, int W, int H)
     return P.x >= 0.f && P.x <= (float)(W - 1) && P.y >= 0.f && P.y <= (float)(H - 1);     // false on NaN
 }
 
+// B(q) of a covered pixel q = (qx, qy) whose winner is triangle t of job j: s - q with s the source point interpolated
+// at q with the rasteriser's barycentrics.  The one copy: k_warp_keys and the layered key pass (arap_layers.h) call it.
+__device__ __forceinline__ float2 tri_backward(const WarpJob& j, int W, unsigned t, int qx, int qy)
+{
+    const int u = (int)(t >> 1);
+    const int uy = u / W, ux = u - uy * W;
+    // corners of triangle t and their grid coordinates: 2u = (p00, p01, p10), 2u+1 = (p10, p01, p11)
+    const int odd = (int)(t & 1u);
+    const int ax = ux, ay = uy + odd, bx = ux + 1, by = uy, cx = ux + odd, cy = uy + 1;
+    const float2 p0 = warp_pos(j, ax, ay, ax + W * ay), p1 = warp_pos(j, bx, by, bx + W * by);
+    const float2 p2 = warp_pos(j, cx, cy, cx + W * cy);
+    const float sx = (float)qx, sy = (float)qy;
+    float b0, b1, b2;
+    if (!tri_bary(p0, p1, p2, sx, sy, b0, b1, b2)) return make_float2(0.f, 0.f);     // (never: the raster passed this test at q)
+    const float srcx = ((float)ax * b0 + (float)bx * b1) + (float)cx * b2;
+    const float srcy = ((float)ay * b0 + (float)by * b1) + (float)cy * b2;
+    return make_float2(srcx - sx, srcy - sy);
+}
+
 // Backward pass, before k_warp_resolve.  Per frame-2 pixel q: the winner T(q) = key's triangle; B(q) = s - q with s
 // the source point interpolated at q with the rasteriser's barycentrics; OccBwd(q) = uncovered object pixel; and the
 // forward occlusion of a background pixel = covered.  Each output only if its pointer is set.
@@ -51,25 +70,7 @@ __global__ __launch_bounds__(256) void k_warp_keys(const WarpJob* jobs, int W, i
     if (j.occ && j.mask[i] != 0) j.occ[i] = k ? 255 : 0;
     if (j.occ_bwd) j.occ_bwd[i] = (!k && j.mask[i] == 0) ? 255 : 0;
     if (!j.bwd) return;
-    float2 b = make_float2(0.f, 0.f);
-    if (k) {
-        const unsigned t = (unsigned)(k >> 32) - 1u;
-        const int u = (int)(t >> 1);
-        const int uy = u / W, ux = u - uy * W;
-        // corners of triangle t and their grid coordinates: 2u = (p00, p01, p10), 2u+1 = (p10, p01, p11)
-        const int odd = (int)(t & 1u);
-        const int ax = ux, ay = uy + odd, bx = ux + 1, by = uy, cx = ux + odd, cy = uy + 1;
-        const float2 p0 = warp_pos(j, ax, ay, ax + W * ay), p1 = warp_pos(j, bx, by, bx + W * by);
-        const float2 p2 = warp_pos(j, cx, cy, cx + W * cy);
-        const float sx = (float)qx, sy = (float)qy;
-        float b0, b1, b2;
-        if (tri_bary(p0, p1, p2, sx, sy, b0, b1, b2)) {      // (always: the raster passed this test at q)
-            const float srcx = ((float)ax * b0 + (float)bx * b1) + (float)cx * b2;
-            const float srcy = ((float)ay * b0 + (float)by * b1) + (float)cy * b2;
-            b = make_float2(srcx - sx, srcy - sy);
-        }
-    }
-    j.bwd[i] = b;
+    j.bwd[i] = k ? tri_backward(j, W, (unsigned)(k >> 32) - 1u, qx, qy) : make_float2(0.f, 0.f);
 }
 
 // Forward occlusion, pass 1: per object vertex v, P(v) out of frame -> Occ = 255; else Occ = 0 and v is counted in

@@ -79,6 +79,19 @@ __device__ __forceinline__ bool tri_cells(int W, int H, float2 p0, float2 p1, fl
     return true;
 }
 
+// the interpolated colour r << 16 | g << 8 | b of a covered pixel (main.cpp:131-137); the one copy, as tri_bary
+__device__ __forceinline__ unsigned tri_rgb(const float c0[3], const float c1[3], const float c2[3], float b0, float b1,
+                                            float b2)
+{
+    unsigned rgbv = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float v = (c0[k] * b0 + c1[k] * b1) + c2[k] * b2;
+        rgbv = (rgbv << 8) | (unsigned)(unsigned char)v;
+    }
+    return rgbv;
+}
+
 __device__ __forceinline__ void raster_tri(const WarpJob& j, int W, int H, unsigned tri, float2 p0, float2 p1,
                                            float2 p2, const float c0[3], const float c1[3], const float c2[3])
 {
@@ -89,14 +102,7 @@ __device__ __forceinline__ void raster_tri(const WarpJob& j, int W, int H, unsig
         for (int y = ya; y < H && (float)y <= maxy; ++y) {
             float b0, b1, b2;
             if (!tri_bary(p0, p1, p2, (float)x, (float)y, b0, b1, b2)) continue;
-            unsigned rgbv = 0;
-            if (j.rgb) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float v = (c0[k] * b0 + c1[k] * b1) + c2[k] * b2;
-                    rgbv = (rgbv << 8) | (unsigned)(unsigned char)v;
-                }
-            }
+            const unsigned rgbv = j.rgb ? tri_rgb(c0, c1, c2, b0, b1, b2) : 0u;
             const unsigned long long key = ((unsigned long long)(tri + 1u) << 32) | rgbv;
             atomicMax(j.key + (x + (size_t)W * y), key);
         }

@@ -30,6 +30,7 @@
 #include "arap_stream.h"
 #include "arap_warp.h"
 #include "arap_occ.h"
+#include "arap_layers.h"
 
 using namespace arap;
 
@@ -2199,6 +2200,55 @@ int ArapFlow_WarpEx(Opt_State* st, unsigned W, unsigned H, const void* rgb, cons
         enqueue_warp_outputs(st->stream, dj, 1, (int)W, (int)H, outputs, j.cell, 4 * (N + 1));
     hipLaunchKernelGGL(k_warp_resolve, dim3((unsigned)((N + 255) / 256), 1, 1), dim3(256), 0, st->stream, dj,
                        (int)N);
+    return (int)hipGetLastError();
+}
+
+uint64_t ArapFlow_WarpLayersScratchBytes(unsigned W, unsigned H, unsigned n)
+{
+    (void)n;                                 // one key image and one joint binning, however many layers
+    const uint64_t N = (uint64_t)W * H;
+    return align_up(N * 8, 256) + align_up(4 * (N + 1), 256) + align_up(4 * N, 256) + align_up(16 * N, 256) +
+           align_up(N, 256) + 256;
+}
+
+int ArapFlow_WarpLayers(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                        const void* flows, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd,
+                        void* out_occ, void* scratch)
+{
+    if (!st || !masks_red || !flows || !scratch || W == 0 || H == 0 || n == 0 || n > 255) return -1;
+    if (!out_rgb && !out_mask && !out_bwd && !out_occ_bwd && !out_occ) return -1;
+    if (out_rgb && !rgb) return -1;
+    const uint64_t N64 = (uint64_t)W * H;
+    if (N64 >= (1ull << 31) || (out_occ && N64 > (1ull << 24))) return -1;      // key / bin field widths (arap_layers.h)
+    const size_t N = (size_t)N64;
+    char* c = (char*)scratch;
+    auto take = [&](size_t b) { char* r = c; c += b; return r; };
+    WarpJob j{};
+    j.rgb = (const uint8_t*)rgb;
+    j.key = (unsigned long long*)take(align_up(N * 8, 256));
+    j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
+    j.bwd = (float2*)out_bwd; j.occ_bwd = (uint8_t*)out_occ_bwd; j.occ = (uint8_t*)out_occ;
+    j.cell = (unsigned*)take(align_up(4 * (N + 1), 256));
+    j.rank = (unsigned*)take(align_up(4 * N, 256));
+    j.bin = (int4*)take(align_up(16 * N, 256));
+    LayerSet ls{};
+    ls.masks = (const uint8_t*)masks_red; ls.flows = (const float2*)flows; ls.n = (int)n;
+    ls.owner = (uint8_t*)take(align_up(N, 256));
+    WarpJob* dj = (WarpJob*)c;
+    const dim3 g1((unsigned)((N + 255) / 256)), g2((W + 63) / 64, (H + 3) / 4, n);
+    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
+    hipLaunchKernelGGL(k_layers_raster, g2, dim3(64, 4), 0, st->stream, dj, ls, (int)W, (int)H);
+    if (out_bwd || out_occ_bwd || out_occ)
+        hipLaunchKernelGGL(k_layers_keys, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)N);
+    if (out_occ) {
+        HC(hipMemsetAsync(j.cell, 0, 4 * (N + 1), st->stream));
+        hipLaunchKernelGGL(k_layers_count, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)H, (int)N);
+        hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, 1), dim3(1024), 0, st->stream, dj, (int)N);
+        hipLaunchKernelGGL(k_layers_scatter, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)H, (int)N);
+        hipLaunchKernelGGL(k_layers_tri, g2, dim3(64, 4), 0, st->stream, dj, ls, (int)W, (int)H);
+    }
+    hipLaunchKernelGGL(k_layers_resolve, g1, dim3(256), 0, st->stream, dj, (int)N);
     return (int)hipGetLastError();
 }
 

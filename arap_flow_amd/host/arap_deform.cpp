@@ -6,6 +6,10 @@
 // A list or --serve line may carry optional tokens after its six paths (addition, DESIGN.md "Backward flow and
 // occlusion"): bwd=PATH.flo (backward flow), occ=PATH.png (forward occlusion), occ_bwd=PATH.png (backward
 // occlusion), 8-bit 0/255.  Other trailing tokens are ignored, as before.
+// A line whose first word is `layers` is no solve but the layered warp of one frame (DESIGN.md "Layered warp"):
+//   layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P]      (at least one output)
+// It runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
+// inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
 // here consecutive frames of equal size are handed to the device-resident batched solver, as many as fit one launch
 // (ArapFlow_Solver = CombinedSolver on the GPU: reset, 19-step constraint ramp, 8 GN x 400 PCG, flow, rasteriser).
@@ -33,6 +37,8 @@
 #include <unistd.h>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 extern "C" {
 #include "../../include/arap_opt.h"
 }
@@ -47,6 +53,14 @@ struct SolvePaths {
     {
         return (bwd.empty() && occ_bwd.empty() ? 0 : ARAPFLOW_OUT_BACKWARD) | (occ.empty() ? 0 : ARAPFLOW_OUT_OCCLUSION);
     }
+};
+
+// one `layers` line
+struct LayersSpec {
+    std::string rgb;
+    std::vector<std::string> masks, flows;
+    std::string occ, bwd, occ_bwd, rgb2, mask2;
+    std::string first_out;                 // the first output token's path: what --serve reports
 };
 
 // the usage text of the reference's executable (main.cpp:13-24), verbatim: it is part of the CLI contract
@@ -127,12 +141,114 @@ static bool parse_line(const std::string& line, SolvePaths& q)
     return true;
 }
 
+static bool is_layers_line(const std::string& line)
+{
+    std::istringstream tok(line);
+    std::string w;
+    return (tok >> w) && w == "layers";
+}
+
+static bool parse_layers(const std::string& line, LayersSpec& q)
+{
+    std::istringstream tok(line);
+    std::string w;
+    long n = 0;
+    if (!(tok >> w >> q.rgb >> n) || w != "layers" || n < 1 || n > 255) return false;
+    for (long l = 0; l < n; ++l) {
+        std::string m, f;
+        if (!(tok >> m >> f)) return false;
+        q.masks.push_back(m);
+        q.flows.push_back(f);
+    }
+    for (std::string t; tok >> t;) {
+        const size_t eq = t.find('=');
+        if (eq == std::string::npos || eq + 1 >= t.size()) return false;
+        const std::string k = t.substr(0, eq), v = t.substr(eq + 1);
+        std::string* dst = k == "occ" ? &q.occ : k == "bwd" ? &q.bwd : k == "occ_bwd" ? &q.occ_bwd
+                         : k == "rgb2" ? &q.rgb2 : k == "mask2" ? &q.mask2 : nullptr;
+        if (!dst) return false;
+        *dst = v;
+        if (q.first_out.empty()) q.first_out = v;
+    }
+    return !q.first_out.empty();
+}
+
+// the layered warp of one frame, synchronously: read the layers' files, one ArapFlow_WarpLayers on the state's stream
+// (behind whatever solve is in flight there, never beside it), write the outputs asked for
+static bool run_layers(Opt_State* state, const LayersSpec& q)
+{
+    std::string err;
+    arapio::Image rgb;
+    if (!arapio::read_png_rgb(q.rgb, rgb, err)) { printf("%s\n", err.c_str()); return false; }
+    const int w = rgb.w, h = rgb.h;
+    const size_t N = (size_t)w * h, n = q.masks.size();
+    std::vector<uint8_t> masks(n * N);
+    std::vector<float> flows(n * N * 2);
+    for (size_t l = 0; l < n; ++l) {
+        arapio::Image msk;
+        if (!arapio::read_png_rgb(q.masks[l], msk, err)) { printf("%s\n", err.c_str()); return false; }
+        std::vector<float> fl;
+        int fw = 0, fh = 0;
+        if (!arapio::read_flo(q.flows[l], fl, fw, fh)) { printf("Could not read %s\n", q.flows[l].c_str()); return false; }
+        if (msk.w != w || msk.h != h || fw != w || fh != h) {
+            printf("layers: %s / %s differ in size from %s\n", q.masks[l].c_str(), q.flows[l].c_str(), q.rgb.c_str());
+            return false;
+        }
+        for (size_t i = 0; i < N; ++i) masks[l * N + i] = msk.rgb[3 * i];      // red channel
+        memcpy(flows.data() + l * N * 2, fl.data(), N * 8);
+    }
+    const uint64_t scr = ArapFlow_WarpLayersScratchBytes((unsigned)w, (unsigned)h, (unsigned)n);
+    const size_t off_msk = 3 * N, off_flow = (off_msk + n * N + 255) / 256 * 256, off_out = off_flow + n * N * 8;
+    const size_t out_bytes = 3 * N + N + 8 * N + N + N;
+    const size_t off_scr = (off_out + out_bytes + 255) / 256 * 256;
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, off_scr + scr) != hipSuccess) { printf("layers: out of device memory\n"); return false; }
+    char* o = d + off_out;
+    void* o_bwd = q.bwd.empty() ? nullptr : o;                      // (float2: first, off_out is 8-byte aligned)
+    void* o_rgb = q.rgb2.empty() ? nullptr : o + 8 * N;
+    void* o_msk = q.mask2.empty() ? nullptr : o + 11 * N;
+    void* o_obwd = q.occ_bwd.empty() ? nullptr : o + 12 * N;
+    void* o_occ = q.occ.empty() ? nullptr : o + 13 * N;
+    bool ok = hipMemcpy(d, rgb.rgb.data(), 3 * N, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + off_msk, masks.data(), n * N, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + off_flow, flows.data(), n * N * 8, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && ArapFlow_WarpLayers(state, (unsigned)w, (unsigned)h, (unsigned)n, d, d + off_msk, d + off_flow, o_rgb, o_msk,
+                                   o_bwd, o_obwd, o_occ, d + off_scr) == 0;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    std::vector<uint8_t> host(out_bytes);
+    ok = ok && hipMemcpy(host.data(), o, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d);
+    if (!ok) { printf("ArapFlow_WarpLayers failed\n"); return false; }
+    const uint8_t* hp = host.data();
+    if (o_rgb && !arapio::write_png_rgb(q.rgb2, w, h, hp + 8 * N, err)) { printf("%s\n", err.c_str()); return false; }
+    if (o_msk && !arapio::write_png_mask1(q.mask2, w, h, hp + 11 * N, err)) { printf("%s\n", err.c_str()); return false; }
+    if (o_bwd && !arapio::write_flo(q.bwd, (const float*)hp, w, h)) return false;
+    if (o_obwd && !arapio::write_png_gray8(q.occ_bwd, w, h, hp + 12 * N, err)) { printf("%s\n", err.c_str()); return false; }
+    if (o_occ && !arapio::write_png_gray8(q.occ, w, h, hp + 13 * N, err)) { printf("%s\n", err.c_str()); return false; }
+    return true;
+}
+
 // ---- where the lines come from: a finished list, or stdin as it arrives (--serve) ------------------------------------
-struct Loaded { bool ok = false; Frame f; };
+struct Loaded { bool ok = false; Frame f; bool is_layers = false; LayersSpec layers; };
+
+struct Item { bool is_layers = false; SolvePaths solve; LayersSpec layers; };
+
+// a list / --serve line -> item; false for a line that is neither (a bad `layers` line is reported)
+static bool parse_item(const std::string& line, Item& it)
+{
+    if (is_layers_line(line)) {
+        it.is_layers = true;
+        if (parse_layers(line, it.layers)) return true;
+        printf("Invalid layers line: %s\n", line.c_str());
+        fflush(stdout);
+        return false;
+    }
+    return parse_line(line, it.solve);
+}
 
 class FrameSource {
   public:
-    explicit FrameSource(std::vector<SolvePaths> fixed) : eof_(true)
+    explicit FrameSource(std::vector<Item> fixed) : eof_(true)
     {
         for (auto& q : fixed) lines_.push_back(std::move(q));
     }
@@ -140,8 +256,8 @@ class FrameSource {
     {
         reader_ = std::thread([this]() {
             for (std::string line; std::getline(std::cin, line);) {
-                SolvePaths q;
-                if (!parse_line(line, q)) continue;
+                Item q;
+                if (!parse_item(line, q)) continue;
                 { std::lock_guard<std::mutex> g(m_); lines_.push_back(std::move(q)); }
                 cv_.notify_all();
             }
@@ -162,7 +278,7 @@ class FrameSource {
             if (!loading_.empty()) {
                 std::future<Loaded>& f = loading_.front();
                 if (wait_ms < 0) f.wait();
-                else if (f.wait_until(deadline) != std::future_status::ready) return 0;
+                else if (f.wait_until(deadline) == std::future_status::timeout) return 0;
                 out->reset(new Loaded(f.get()));
                 loading_.pop_front();
                 return 1;
@@ -180,15 +296,20 @@ class FrameSource {
     {
         std::lock_guard<std::mutex> g(m_);
         while (!lines_.empty() && loading_.size() < kAhead) {
-            auto q = std::make_shared<SolvePaths>(std::move(lines_.front()));
+            auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            loading_.push_back(std::async(std::launch::async, [q]() { Loaded l; l.ok = load_frame(*q, l.f); return l; }));
+            if (q->is_layers) {              // read when its turn comes: in a list its inputs may not exist yet
+                loading_.push_back(std::async(std::launch::deferred, [q]() {
+                    Loaded l; l.ok = true; l.is_layers = true; l.layers = q->layers; return l; }));
+                continue;
+            }
+            loading_.push_back(std::async(std::launch::async, [q]() { Loaded l; l.ok = load_frame(q->solve, l.f); return l; }));
         }
     }
     static constexpr size_t kAhead = 48;
     std::mutex m_;
     std::condition_variable cv_;
-    std::deque<SolvePaths> lines_;
+    std::deque<Item> lines_;
     std::deque<std::future<Loaded>> loading_;
     bool eof_;
     std::thread reader_;
@@ -222,6 +343,12 @@ class Writer {
         }));
     }
     void finish() { for (auto& t : tasks_) t.get(); tasks_.clear(); }
+    void say(const std::string& line)
+    {
+        std::lock_guard<std::mutex> g(print_);
+        printf("%s\n", line.c_str());
+        fflush(stdout);
+    }
 
   private:
     bool report_;
@@ -240,15 +367,18 @@ int main(int argc, const char* argv[])
     std::unique_ptr<FrameSource> source;
     bool serve = false;
     if (argc == 7) {                                                     // one frame on the command line
-        source.reset(new FrameSource(std::vector<SolvePaths>{SolvePaths{argv[1], argv[2], argv[3], argv[4], argv[5], argv[6]}}));
+        Item one;
+        one.solve = SolvePaths{argv[1], argv[2], argv[3], argv[4], argv[5], argv[6]};
+        source.reset(new FrameSource(std::vector<Item>{one}));
     } else if (argc == 2 && strcmp(argv[1], "--serve") == 0) {
         serve = true;
     } else if (argc == 2) {                                              // list file
         std::ifstream list(argv[1]);
-        std::vector<SolvePaths> lines;
+        std::vector<Item> lines;
         for (std::string line; std::getline(list, line);) {
-            SolvePaths q;
-            if (parse_line(line, q)) lines.push_back(q);
+            Item q;
+            if (parse_item(line, q)) lines.push_back(q);
+            else if (q.is_layers) return 1;
         }
         if (lines.empty()) {
             printf("No file to be processed");
@@ -374,6 +504,17 @@ int main(int argc, const char* argv[])
                 if (got == 0) got = source->next(&fr, L.batch.empty() ? -1 : linger_ms);
             }
             if (got < 0) exhausted = true;
+        }
+        if (fr && fr->is_layers) {
+            // A list: every earlier line is solved and written first (this line's inputs may be their outputs).  --serve:
+            // the sender names only files that exist, so nothing is flushed; the call queues behind the solve in flight.
+            if (!serve) {
+                if (!launch(L) || !drain(other) || !drain(L)) { rc = 1; break; }
+                writer.finish();
+            }
+            if (!run_layers(state, fr->layers)) { rc = 1; break; }
+            writer.say(serve ? "Done " + fr->layers.first_out : std::string("Saved"));
+            continue;
         }
         if (fr) {
             if (!fr->ok) { rc = 1; break; }

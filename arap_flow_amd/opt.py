@@ -455,3 +455,43 @@ def warp_image_ex(state, rgb, mask_red, flow, backward=True, occlusion=True):
     if occlusion:
         out.update(occlusion=o_occ.cpu().numpy())
     return out
+
+
+def warp_layers(state, rgb, masks, flows, bwd=False, occ_bwd=False, occ=True):
+    """the layered warp (ArapFlow_WarpLayers, DESIGN.md "Layered warp"): one pass over the n layers of a frame, the
+    higher index on top.  rgb u8[H,W,3] or None, masks u8[n,H,W] (red channels, 0 = object), flows f32[n,H,W,2] (numpy)
+    -> a dict of the composite warped_rgb (None without rgb), warped_mask and, as asked for, backward_flow f32[H,W,2],
+    occlusion_bwd u8[H,W], occlusion u8[H,W] (the forward occlusion across layers)."""
+    lib = state.lib
+    masks = np.ascontiguousarray(masks, np.uint8)
+    flows = np.ascontiguousarray(flows, np.float32)
+    if masks.ndim != 3 or flows.shape != masks.shape + (2,):
+        raise ValueError("warp_layers: masks [n,H,W] and flows [n,H,W,2] expected")
+    n, H, W = masks.shape
+    if rgb is not None and tuple(np.shape(rgb)) != (H, W, 3):
+        raise ValueError("warp_layers: rgb [H,W,3] expected")
+    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
+    d_msk = torch.from_numpy(masks).cuda()
+    d_flow = torch.from_numpy(flows).cuda()
+    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
+    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
+    o_bwd = torch.empty(H, W, 2, dtype=torch.float32, device="cuda") if bwd else None
+    o_obwd = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occ_bwd else None
+    o_occ = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occ else None
+    scratch = torch.empty(int(lib.ArapFlow_WarpLayersScratchBytes(W, H, n)), dtype=torch.uint8, device="cuda")
+    p = lambda t: _dev_ptr(t) if t is not None else None
+    torch.cuda.synchronize()
+    rc = lib.ArapFlow_WarpLayers(state.handle, W, H, n, p(d_rgb), p(d_msk), p(d_flow), p(o_rgb), p(o_msk), p(o_bwd),
+                                 p(o_obwd), p(o_occ), p(scratch))
+    if rc != 0:
+        raise (ValueError("ArapFlow_WarpLayers: bad arguments") if rc == -1 else
+               RuntimeError("ArapFlow_WarpLayers failed: %d" % rc))
+    torch.cuda.synchronize()
+    out = dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy())
+    if bwd:
+        out.update(backward_flow=o_bwd.cpu().numpy())
+    if occ_bwd:
+        out.update(occlusion_bwd=o_obwd.cpu().numpy())
+    if occ:
+        out.update(occlusion=o_occ.cpu().numpy())
+    return out

@@ -9,6 +9,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   parse_extra, read_list_ex              optional output tokens of a list line (bwd= occ= occ_bwd=)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
+  parse_layers, layers_line, read_list_items, run_layers    the `layers` line: layered warp of one frame (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
   resize_crop_geometry, scale_rotate     para_gen.py:253-291
   make_arap_path                         para_gen.py:331-339
@@ -39,6 +40,8 @@ def read_list(path):
         for line in f:
             tok = line.split()
             if not tok:
+                continue
+            if tok[0] == LAYERS_WORD:                 # no solve: see read_list_items
                 continue
             if len(tok) < 6:
                 raise ValueError("list line needs 6 paths: %r" % line)
@@ -73,10 +76,93 @@ def read_list_ex(path):
             tok = line.split()
             if not tok:
                 continue
+            if tok[0] == LAYERS_WORD:
+                continue
             if len(tok) < 6:
                 raise ValueError("list line needs 6 paths: %r" % line)
             lines.append((tuple(tok[:6]), parse_extra(tok[6:])))
     return lines
+
+
+LAYERS_WORD = "layers"
+LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2")
+
+
+def parse_layers(tokens):
+    """a `layers` line (DESIGN.md "Layered warp"), recognised by its first word:
+        layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P]
+    -> dict(rgb, layers=[(mask, flo)] in layer order (the later on top), out={key: path} in line order).  At least one
+    output; anything else after the layers is an error (a new line form has no old meaning to keep)."""
+    if len(tokens) < 3 or tokens[0] != LAYERS_WORD:
+        raise ValueError("not a layers line: %r" % " ".join(tokens))
+    try:
+        n = int(tokens[2])
+    except ValueError:
+        raise ValueError("layers line: layer count expected, got %r" % tokens[2])
+    if not 1 <= n <= 255 or len(tokens) < 3 + 2 * n:
+        raise ValueError("layers line: 1..255 layers, a mask and a flow each: %r" % " ".join(tokens))
+    out = {}
+    for t in tokens[3 + 2 * n:]:
+        k, eq, v = t.partition("=")
+        if not (eq and k in LAYER_KEYS and v):
+            raise ValueError("layers line: bad output token %r" % t)
+        out[k] = v
+    if not out:
+        raise ValueError("layers line without an output: %r" % " ".join(tokens))
+    return dict(rgb=tokens[1], layers=[(tokens[3 + 2 * l], tokens[4 + 2 * l]) for l in range(n)], out=out)
+
+
+def layers_line(rgb, layers, out):
+    """the inverse of parse_layers; outputs in the order of LAYER_KEYS"""
+    tok = [LAYERS_WORD, rgb, str(len(layers))] + [p for pair in layers for p in pair]
+    return " ".join(tok + ["%s=%s" % (k, out[k]) for k in LAYER_KEYS if out.get(k)])
+
+
+def layers_done_token(spec):
+    """what `arap_deform --serve` reports for a layers line: the path of its first output token"""
+    return next(iter(spec["out"].values()))
+
+
+def read_list_items(path):
+    """every line of a list in order: ("solve", six paths, {key: path}) or ("layers", parse_layers(..))"""
+    items = []
+    with open(path) as f:
+        for line in f:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == LAYERS_WORD:
+                items.append(("layers", parse_layers(tok)))
+                continue
+            if len(tok) < 6:
+                raise ValueError("list line needs 6 paths: %r" % line)
+            items.append(("solve", tuple(tok[:6]), parse_extra(tok[6:])))
+    return items
+
+
+def run_layers(state, spec):
+    """one `layers` line: read the frame's RGB and every layer's mask / flow, one opt.warp_layers, write what the line
+    asks for (occ / occ_bwd: 8-bit L PNG; bwd: .flo; rgb2: RGB PNG; mask2: 1-bit PNG as a solve's warped mask)"""
+    from . import opt
+    rgb = load_rgb(spec["rgb"])
+    masks = [load_mask_red(m) for m, _ in spec["layers"]]
+    flows = [flo.flow_read(f) for _, f in spec["layers"]]
+    for m, f in zip(masks, flows):
+        if m.shape != rgb.shape[:2] or f.shape[:2] != rgb.shape[:2]:
+            raise ValueError("layers line: image, mask and flow sizes differ")
+    out = spec["out"]
+    r = opt.warp_layers(state, rgb, np.stack(masks), np.stack(flows), bwd="bwd" in out, occ_bwd="occ_bwd" in out,
+                        occ="occ" in out)
+    if "rgb2" in out:
+        Image.fromarray(r["warped_rgb"]).save(out["rgb2"])
+    if "mask2" in out:
+        save_mask(r["warped_mask"], out["mask2"])
+    if "bwd" in out:
+        flo.flow_write(out["bwd"], r["backward_flow"])
+    if "occ_bwd" in out:
+        save_occ(r["occlusion_bwd"], out["occ_bwd"])
+    if "occ" in out:
+        save_occ(r["occlusion"], out["occ"])
 
 
 def save_occ(occ, path):

@@ -289,6 +289,22 @@ int ArapFlow_WarpEx(Opt_State* state, unsigned W, unsigned H, const void* rgb, c
                     const void* flow, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ,
                     void* scratch);
 
+/* Layered warp (DESIGN.md "Layered warp"): ONE rasteriser pass over the n layers of a frame -- the --multseg segments in
+ * list order, the higher index on top -- on DEVICE buffers: rgb uint8[H][W][3] shared by all layers (or NULL: no
+ * out_rgb), masks_red uint8[n][H][W] (0 = object), flows float[n][H][W][2].  Outputs, each NULL when not wanted:
+ * the composite out_rgb / out_mask / out_bwd / out_occ_bwd (bit for bit what the host merge of n ArapFlow_WarpEx calls
+ * gives) and out_occ, the forward occlusion ACROSS layers, which n separate calls cannot give: a frame-1 pixel is
+ * occluded when it leaves the frame or a triangle of a higher layer, or a later triangle of its own layer, is drawn over
+ * its landing point; lower layers never occlude.  With n = 1 every output equals ArapFlow_WarpEx's.
+ * `scratch`: 256-byte aligned device buffer of ArapFlow_WarpLayersScratchBytes(W, H, n) bytes.  Asynchronous on the
+ * state's stream.  Returns 0; -1 on bad arguments: n = 0, n > 255, no output at all, out_rgb without rgb,
+ * W * H >= 2^31, or out_occ with W * H > 2^24 (the field widths of the keys and of a binned vertex); else a HIP error
+ * code. */
+uint64_t ArapFlow_WarpLayersScratchBytes(unsigned W, unsigned H, unsigned n);
+int ArapFlow_WarpLayers(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                        const void* flows, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd,
+                        void* out_occ, void* scratch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 """para_gen -- Python 3 twin of the reference's dataset generator CLI (para_gen.py:341-653), same flags.
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
-                     [--bwd_flow] [--occ]
+                     [--bwd_flow] [--occ | --multseg --occ_layers]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -54,6 +54,8 @@ color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
 EXTRA_OF = dict(bwd_gen="bwd", occbwd_gen="occ_bwd", occ_gen="occ")   # path key -> list-line token
+LAYERS_OCC = "occl_gen"            # --multseg --occ_layers: the frame's forward occlusion, made by a `layers` line
+EXT_KEYS = list(EXTRA_OF) + [LAYERS_OCC]                              # every optional output of a frame
 CPP_BIN = osp.join(HERE, "arap_flow_amd", "bin", "arap_deform")
 
 
@@ -163,7 +165,12 @@ def prepare_pair(args):
             Image.fromarray(mask).save(p_["msk1_gen"])
             seg_paths.append(pipeline.make_arap_path(p_))
             seg_extras.append(_extra(p_))
-    return dict(arap_path=arap_path, seg_paths=seg_paths, bg=bgim, extra=_extra(p), seg_extras=seg_extras)
+    layers = None
+    if seg_paths and LAYERS_OCC in p:       # the frame's layers line: segments in list order = ascending label, later on top
+        toks = [ln.split(" ") for ln in seg_paths]
+        layers = pipeline.layers_line(osp.abspath(p["rgb1_gen"]), [(t[1], t[3]) for t in toks], dict(occ=p[LAYERS_OCC]))
+    return dict(arap_path=arap_path, seg_paths=seg_paths, bg=bgim, extra=_extra(p), seg_extras=seg_extras,
+                layers=layers)
 
 
 def _extra(p):
@@ -175,13 +182,22 @@ def _line(arap_path, extra):
     return " ".join([arap_path] + pipeline.extra_tokens(extra))
 
 
+def _done_token(line):
+    """the path a worker reports a line done by: a solve's flow, a layers line's first output"""
+    tok = line.split()
+    if tok[0] == pipeline.LAYERS_WORD:
+        return pipeline.layers_done_token(pipeline.parse_layers(tok))
+    return tok[3]
+
+
 def finish_frame(args):
     """para_gen.py:202-212 for one frame whose solve(s) are done: flatten the segments, composite the background"""
-    arap_path, seg_paths, bg, extra, seg_extras = args
+    arap_path, seg_paths, bg, extra, seg_extras = args[:5]
+    remove = args[5] if len(args) > 5 else True
     if seg_paths is not None:
         if extra:                                           # (before flatten removes the segments' warped masks)
-            pipeline.flatten_backward(extra, seg_paths, seg_extras)
-        pipeline.flatten([(arap_path, seg_paths)])
+            pipeline.flatten_backward(extra, seg_paths, seg_extras, remove=remove)
+        pipeline.flatten([(arap_path, seg_paths)], remove=remove)
     if bg is not None:
         pt, mk = arap_path.split(" ")[-2:]
         im = np.array(Image.open(pt).convert("RGB"))
@@ -204,6 +220,7 @@ class GpuWorkers:
         self.batches = []                      # solves per GPU launch (serve) / per child (batch)
         self.threads, self.procs = [], []
         self.t_ready = None
+        self.owed, self.closing, self.owe_lock = 0, False, threading.Lock()
         for g in gpus:
             t = threading.Thread(target=self._serve_loop if serve else self._batch_loop, args=(g,), daemon=True)
             t.start()
@@ -212,7 +229,27 @@ class GpuWorkers:
     def put(self, line):
         self.lines.put(line)
 
+    def owe(self):
+        """a line will be put later, from a reader thread (a frame's layers line, once its last solve is done): the
+        workers stay open for it"""
+        with self.owe_lock:
+            self.owed += 1
+
+    def put_owed(self, line):
+        with self.owe_lock:
+            self.lines.put(line)
+            self.owed -= 1
+            if self.closing and self.owed == 0:
+                self._post_end()
+
     def close(self):
+        """no further line from the caller: end markers now, or behind the last owed line"""
+        with self.owe_lock:
+            self.closing = True
+            if self.owed == 0:
+                self._post_end()
+
+    def _post_end(self):
         for _ in self.threads:
             self.lines.put(None)
 
@@ -328,7 +365,7 @@ class GpuWorkers:
                 return
             self.batches.append(len(batch))
             for ln in batch:
-                self.on_done(ln.split(" ")[3])
+                self.on_done(_done_token(ln))
             if last:
                 return
 
@@ -363,9 +400,11 @@ def scan(flags, input_root, output_root):
                     e.update(bwd_gen=osp.join(roots["bwd"], seq, f + ".flo"), occbwd_gen=osp.join(roots["obw"], seq, f + ".png"))
                 if getattr(flags, "occ", False):
                     e.update(occ_gen=osp.join(roots["occ"], seq, f + ".png"))
+                if getattr(flags, "occ_layers", False):
+                    e[LAYERS_OCC] = osp.join(roots["occ"], seq, f + ".png")
                 e = {k: osp.abspath(v) for k, v in e.items()}
                 e["_seq"], e["_stem"] = seq, f
-                done = [e["flow_gen"]] + [e[k] for k in EXTRA_OF if k in e]    # every requested output
+                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e]    # every requested output
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -415,7 +454,7 @@ def main(flags):
         q = {k: v for k, v in p.items() if not k.startswith("_")}
         ap = pipeline.make_arap_path(q).split(" ")
         lmdb_paths.append(" ".join([ap[0], ap[4], ap[3]]))
-        ext_paths.append(" ".join([ap[0], ap[4], ap[3]] + [q[k] for k in EXTRA_OF if k in q]))
+        ext_paths.append(" ".join([ap[0], ap[4], ap[3]] + [q[k] for k in EXT_KEYS if k in q]))
 
     # backgrounds: drawn without replacement until the list is used up, then refilled (para_gen.py:484-499)
     tmp_paths, picks = [], []
@@ -433,18 +472,26 @@ def main(flags):
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
     frames = {}                                        # flow path of a solve -> its frame record
     posts, lock = [], threading.Lock()
-    counts = dict(solves_done=0, frames_done=0)
+    counts = dict(solves_done=0, frames_done=0, layers_done=0)
+    remove = not getattr(flags, "keep_segments", False)
 
-    def on_done(flow_path):                            # a worker thread: one solve finished
+    def on_done(path):                                 # a worker thread: one solve (or one layers line) finished
         with lock:
-            rec = frames.pop(flow_path)
-            counts["solves_done"] += 1
-            rec["left"] -= 1
-            if rec["left"] > 0:
-                return
+            rec = frames.pop(path)
+            if rec["left"] == 0:                       # its layers line: the segment files may go now
+                counts["layers_done"] += 1
+            else:
+                counts["solves_done"] += 1
+                rec["left"] -= 1
+                if rec["left"] > 0:
+                    return
+                if rec["layers"] is not None:          # last segment done: the frame's layers line, then finish_frame
+                    frames[_done_token(rec["layers"])] = rec
+                    workers.put_owed(rec["layers"])
+                    return
             counts["frames_done"] += 1
             posts.append(pool.apply_async(finish_frame, ((rec["arap_path"], rec["seg_paths"], rec["bg"], rec["extra"],
-                                                          rec["seg_extras"]),)))
+                                                          rec["seg_extras"], remove),)))
 
     # --dm_bin builtin: the matcher and the solver must not share a GPU at the same time (the solver's resident kernel
     # needs the whole chip: arap_resident.h), so the run has two phases -- every pair is prepared and matched first
@@ -472,7 +519,9 @@ def main(flags):
             if not lines:
                 continue
             rec = dict(arap_path=res["arap_path"], seg_paths=res["seg_paths"], bg=res["bg"], left=len(lines),
-                       extra=res["extra"], seg_extras=res["seg_extras"])
+                       extra=res["extra"], seg_extras=res["seg_extras"], layers=res.get("layers"))
+            if rec["layers"] is not None:
+                workers.owe()
             with lock:
                 for ln in lines:
                     frames[ln.split(" ")[3]] = rec
@@ -491,11 +540,12 @@ def main(flags):
                 p.kill()
     out_paths = [ln for ln in lmdb_paths if all(osp.exists(q) for q in ln.split(" "))]   # :588-603
     open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
-    if getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False):     # all_files.list stays as it is; the extra outputs get their own list
+    if getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False):     # all_files.list stays as it is; the extra outputs get their own list
         ext = [ln for ln in ext_paths if all(osp.exists(q) for q in ln.split(" "))]
         open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     dt = time.time() - t_start
-    stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt,
+    stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
+                 layers_done=counts["layers_done"],
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -558,10 +608,21 @@ def parse(argv=None):
                              "OUT/OccBwd/<seq>/<frame>.png (DESIGN.md)")
     parser.add_argument("--occ", action="store_true", default=False,
                         help="also write the forward occlusion OUT/Occ/<seq>/<frame>.png (DESIGN.md)")
+    parser.add_argument("--occ_layers", action="store_true", default=False,
+                        help="with --multseg: also write the forward occlusion across segments OUT/Occ/<seq>/<frame>.png, "
+                             "from one layered warp per frame (DESIGN.md \"Layered warp\")")
+    parser.add_argument("--keep_segments", action="store_true", default=False,
+                        help="with --multseg: keep the per-segment files after they are merged (for inspection)")
     flags = parser.parse_args(argv)
     if flags.occ and flags.multseg:
         parser.error("--occ cannot be combined with --multseg: forward occlusion across segments needs one query over "
-                     "every segment's solve, which this generator does not do (--bwd_flow --multseg is supported)")
+                     "every segment's solve, which --occ does not do; use --multseg --occ_layers (--bwd_flow --multseg "
+                     "is supported)")
+    if flags.occ_layers and not flags.multseg:
+        parser.error("--occ_layers needs --multseg (a single-object run takes --occ)")
+    if flags.occ_layers and not own_arap_bin(flags.arap_bin):
+        parser.error("--occ_layers needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin "
+                     "does not know the layers line")
     if (flags.bwd_flow or flags.occ) and not own_arap_bin(flags.arap_bin):
         parser.error("--bwd_flow / --occ need this repository's arap_deform (C++ or arap_deform.py): a foreign "
                      "--arap_bin does not write the extra outputs")
