@@ -1,0 +1,142 @@
+// abi_warp.h -- the warp entry points on caller-owned images (ArapFlow_Warp / WarpEx / WarpLayers): the layout of their
+// scratch buffer, stated once for the size functions and for the code that carves it up, and the one enqueue of
+// rasterise -> optional outputs -> resolve that the frame solver's warp shares.
+#pragma once
+
+// the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
+// the jobs' cell arrays, `cell_bytes` contiguous bytes, zeroed here
+static void enqueue_warp_outputs(hipStream_t stream, const WarpJob* dj, unsigned njobs, int W, int H, int outputs,
+                                 void* cells, size_t cell_bytes)
+{
+    const int N = W * H;
+    const dim3 g1((N + 255) / 256, 1, njobs);
+    hipLaunchKernelGGL(k_warp_keys, g1, dim3(256), 0, stream, dj, W, N);
+    if (!(outputs & ARAPFLOW_OUT_OCCLUSION)) return;
+    HC(hipMemsetAsync(cells, 0, cell_bytes, stream));
+    hipLaunchKernelGGL(k_occ_count, g1, dim3(256), 0, stream, dj, W, H, N);
+    hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, njobs), dim3(1024), 0, stream, dj, N);
+    hipLaunchKernelGGL(k_occ_scatter, g1, dim3(256), 0, stream, dj, W, H, N);
+    hipLaunchKernelGGL(k_occ_tri, dim3((W + 63) / 64, (H + 3) / 4, njobs), dim3(64, 4), 0, stream, dj, W, H);
+}
+
+// Scratch of one warp job: the key image, then -- for the occlusion map (WARP_OCC) -- cell counts, ranks and bins, then
+// the layered warp's owner image (WARP_OWNER), each aligned to 256 bytes, and the WarpJob itself in a last 256 bytes.
+// Offsets from the start of the buffer; a part that is absent has zero bytes (its offset equals the next one's).
+enum { WARP_OCC = 1, WARP_OWNER = 2 };
+struct WarpScratch { size_t key, cell, rank, bin, owner, job, total; };
+static WarpScratch warp_scratch(uint64_t W, uint64_t H, int parts)
+{
+    const uint64_t N = W * H;
+    const bool occ = parts & WARP_OCC, own = parts & WARP_OWNER;
+    WarpScratch L{};
+    L.cell = L.key + align_up(N * 8, 256);
+    L.rank = L.cell + (occ ? align_up(4 * (N + 1), 256) : 0);
+    L.bin = L.rank + (occ ? align_up(4 * N, 256) : 0);
+    L.owner = L.bin + (occ ? align_up(16 * N, 256) : 0);
+    L.job = L.owner + (own ? align_up(N, 256) : 0);
+    L.total = L.job + 256;
+    return L;
+}
+
+// point a job at its scratch; returns where the job itself goes on the device
+static WarpJob* warp_job_scratch(WarpJob& j, const WarpScratch& L, void* scratch)
+{
+    char* c = (char*)scratch;
+    j.key = (unsigned long long*)(c + L.key);
+    if (L.rank != L.cell) { j.cell = (unsigned*)(c + L.cell); j.rank = (unsigned*)(c + L.rank); j.bin = (int4*)(c + L.bin); }
+    return (WarpJob*)(c + L.job);
+}
+
+// rasterise `njobs` jobs at `dj`, write the optional outputs (ARAPFLOW_OUT_* bits), resolve
+static void enqueue_warp(hipStream_t stream, const WarpJob* dj, unsigned njobs, int W, int H, int outputs, void* cells,
+                         size_t cell_bytes)
+{
+    const int N = W * H;
+    hipLaunchKernelGGL(k_warp_raster, dim3((W + 63) / 64, (H + 3) / 4, njobs), dim3(64, 4), 0, stream, dj, W, H);
+    if (outputs) enqueue_warp_outputs(stream, dj, njobs, W, H, outputs, cells, cell_bytes);
+    hipLaunchKernelGGL(k_warp_resolve, dim3((N + 255) / 256, 1, njobs), dim3(256), 0, stream, dj, N);
+}
+
+// one flow-field warp with a scratch buffer of warp_scratch(W, H, parts) bytes
+static int warp_flow(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* mask_red, const void* flow,
+                     void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ, void* scratch,
+                     int parts)
+{
+    const size_t N = (size_t)W * H;
+    WarpJob j{};
+    j.field = nullptr; j.flow_in = (const float2*)flow;
+    j.rgb = (const uint8_t*)rgb; j.mask = (const uint8_t*)mask_red;
+    j.flow_out = nullptr;
+    j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
+    j.bwd = (float2*)out_bwd; j.occ_bwd = (uint8_t*)out_occ_bwd; j.occ = (uint8_t*)out_occ;
+    WarpJob* dj = warp_job_scratch(j, warp_scratch(W, H, parts), scratch);
+    const int outputs = (out_bwd || out_occ_bwd ? ARAPFLOW_OUT_BACKWARD : 0) | (out_occ ? ARAPFLOW_OUT_OCCLUSION : 0);
+    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
+    enqueue_warp(st->stream, dj, 1, (int)W, (int)H, outputs, j.cell, 4 * (N + 1));
+    return (int)hipGetLastError();
+}
+
+extern "C" {
+
+uint64_t ArapFlow_WarpScratchBytes(unsigned W, unsigned H) { return warp_scratch(W, H, 0).total; }
+
+int ArapFlow_Warp(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* mask_red, const void* flow,
+                  void* out_rgb, void* out_mask, void* scratch)
+{
+    if (!st || !mask_red || !flow || !out_mask || !scratch) return -1;
+    return warp_flow(st, W, H, rgb, mask_red, flow, out_rgb, out_mask, nullptr, nullptr, nullptr, scratch, 0);
+}
+
+uint64_t ArapFlow_WarpExScratchBytes(unsigned W, unsigned H) { return warp_scratch(W, H, WARP_OCC).total; }
+
+int ArapFlow_WarpEx(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* mask_red, const void* flow,
+                    void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ, void* scratch)
+{
+    if (!st || !mask_red || !flow || !out_mask || !scratch || W == 0 || H == 0) return -1;
+    return warp_flow(st, W, H, rgb, mask_red, flow, out_rgb, out_mask, out_bwd, out_occ_bwd, out_occ, scratch, WARP_OCC);
+}
+
+uint64_t ArapFlow_WarpLayersScratchBytes(unsigned W, unsigned H, unsigned n)
+{
+    (void)n;                                 // one key image and one joint binning, however many layers
+    return warp_scratch(W, H, WARP_OCC | WARP_OWNER).total;
+}
+
+int ArapFlow_WarpLayers(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                        const void* flows, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd,
+                        void* out_occ, void* scratch)
+{
+    if (!st || !masks_red || !flows || !scratch || W == 0 || H == 0 || n == 0 || n > 255) return -1;
+    if (!out_rgb && !out_mask && !out_bwd && !out_occ_bwd && !out_occ) return -1;
+    if (out_rgb && !rgb) return -1;
+    const uint64_t N64 = (uint64_t)W * H;
+    if (N64 >= (1ull << 31) || (out_occ && N64 > (1ull << 24))) return -1;      // key / bin field widths (arap_layers.h)
+    const size_t N = (size_t)N64;
+    const WarpScratch L = warp_scratch(W, H, WARP_OCC | WARP_OWNER);
+    WarpJob j{};
+    j.rgb = (const uint8_t*)rgb;
+    j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
+    j.bwd = (float2*)out_bwd; j.occ_bwd = (uint8_t*)out_occ_bwd; j.occ = (uint8_t*)out_occ;
+    WarpJob* dj = warp_job_scratch(j, L, scratch);
+    LayerSet ls{};
+    ls.masks = (const uint8_t*)masks_red; ls.flows = (const float2*)flows; ls.n = (int)n;
+    ls.owner = (uint8_t*)scratch + L.owner;
+    const dim3 g1((unsigned)((N + 255) / 256)), g2((W + 63) / 64, (H + 3) / 4, n);
+    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
+    hipLaunchKernelGGL(k_layers_raster, g2, dim3(64, 4), 0, st->stream, dj, ls, (int)W, (int)H);
+    if (out_bwd || out_occ_bwd || out_occ)
+        hipLaunchKernelGGL(k_layers_keys, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)N);
+    if (out_occ) {
+        HC(hipMemsetAsync(j.cell, 0, 4 * (N + 1), st->stream));
+        hipLaunchKernelGGL(k_layers_count, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)H, (int)N);
+        hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, 1), dim3(1024), 0, st->stream, dj, (int)N);
+        hipLaunchKernelGGL(k_layers_scatter, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)H, (int)N);
+        hipLaunchKernelGGL(k_layers_tri, g2, dim3(64, 4), 0, st->stream, dj, ls, (int)W, (int)H);
+    }
+    hipLaunchKernelGGL(k_layers_resolve, g1, dim3(256), 0, st->stream, dj, (int)N);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -107,7 +107,7 @@ constexpr unsigned RES_SPIN_LIMIT = 1u << 18;
 #endif
 constexpr int RES_GS = RES_GRAN_STRIDE;
 // (a group of several XCD runs addresses its runs in blocks of 64 workgroups, whatever the size of its last run: the
-//  host reserves whole blocks, arapopt.hip: resident_deal -- at most 7 x 128 such units in a launch, hence 2 x RES_WGS)
+//  host reserves whole blocks, host_resident.h: resident_deal -- at most 7 x 128 such units in a launch, hence 2 x RES_WGS)
 constexpr int RES_GRAN_UNITS = 2 * RES_WGS;
 constexpr int RES_GRAN_L1 = 2 * RES_GRAN_UNITS * RES_GS;
 constexpr int RES_GRAN2_STRIDE = 16;            // u64 per second-level granule pair: one 128-byte line per XCD run
@@ -119,7 +119,7 @@ constexpr int RES_GRAN_PER_LAUNCH = RES_GRAN_X + RES_GRAN_L1;
 #define RES_FLAT_MAX_RUNS 2   // groups of up to this many XCD runs sum with group_sum_x (one hop), wider ones in two levels
 #endif
 
-// One entry per workgroup of a launch, written by the host (arapopt.hip: plan_resident_pack): which solve the
+// One entry per workgroup of a launch, written by the host (host_resident.h: plan_resident_pack): which solve the
 // workgroup works on, its rank in that solve's group, the group's size and where the group's granules start.
 struct ResWg {
     int slot;                   // batch slot of the solve, -1: this workgroup is idle in this launch
@@ -273,7 +273,7 @@ __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned 
 }
 
 // The same sum for a group that spans XCDs (wgs = 64 nsub; XCD run `sub` holds ranks 64 sub .. 64 sub + 63, see
-// arapopt.hip: resident_deal).  A flat all-gather would have every workgroup poll every granule through the fabric
+// host_resident.h: resident_deal).  A flat all-gather would have every workgroup poll every granule through the fabric
 // (256 pollers x 256 granules: measured 3.4 us per wait against 0.85 us inside one XCD).  Two levels instead:
 //   1. all-gather inside the XCD run exactly as above (plain granule stores when the run really sits on one XCD:
 //      `subfast`, checked at run time like `fast`) -> every workgroup of the run knows its run's sum S_sub;
@@ -367,7 +367,7 @@ __device__ __forceinline__ bool group_sum_x(double part, unsigned epoch, unsigne
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave == 0) {
         __builtin_amdgcn_s_setprio(3);
-        // (the last run may be shorter than 64: a solve's home XCD plus a piece elsewhere, arapopt.hip: resident_deal)
+        // (the last run may be shorter than 64: a solve's home XCD plus a piece elsewhere, host_resident.h: resident_deal)
         const int sub = rank >> 6, srank = rank & 63, nsub = (wgs + 63) >> 6;
         unsigned long long* bufl = gran_group + (size_t)sub * (128 * RES_GS) + (size_t)(epoch & 1u) * (64 * RES_GS);
         unsigned long long* bufx = granx_group + (size_t)(epoch & 1u) * wgs * RES_GS;      // [wgs] pairs, rank order
@@ -468,7 +468,7 @@ __device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 do
 // Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), plus the edge weights where they fit
 // (4 per slot up to 7 slots, 2 at 8 and 9): 253 VGPRs at 7 slots, 249 at 9, no scratch.
 // NS = tile slots the loops run over (1 .. RES_SLOTS): the most tiles any workgroup of the LAUNCH holds (the host picks
-// the instantiation per launch, arapopt.hip: launch_resident).  The phases are fully unrolled and branch free over the
+// the instantiation per launch, host_step.h: enqueue_gn_step).  The phases are fully unrolled and branch free over the
 // slots, so their length is proportional to NS: a launch whose solves need 7 tiles per workgroup runs the 7-slot kernel.
 template <bool STAMPS, int NS>
 __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, ResDev rd, int L)

@@ -225,7 +225,7 @@ def test_frame_solver_step_sequencing_quiet_vs_verbose(gpu_state, capfd):
 def test_resident_kernel_longest_pcg_loop_and_the_limit_above_it(gpu_state):
     """The border-z granules of the resident kernel carry 16-bit iteration tags (2 l + 3): launches of up to
     RES_MAX_L = 32 000 PCG iterations run on it (tags up to 64 003, bit-identical to the two-kernel path); one
-    iteration more and the solve takes the two-kernel path (arapopt.hip: plan_resident_eligible)."""
+    iteration more and the solve takes the two-kernel path (host_resident.h: plan_resident_eligible)."""
     from arap_flow_amd import synth
     W, H = 96, 64
     frames = [synth.make_frame(W, H, seed=40 + s, K=1, fd=2) for s in range(3)]
@@ -406,7 +406,7 @@ def test_solver_reuse_across_batches_of_the_same_shape(gpu_state):
 
 def test_resident_packing_of_many_uneven_solves(gpu_state):
     """The host deals every solve a group of the resident launch's 512 workgroups sized by its active-tile count and
-    packs small solves onto one XCD (arapopt.hip: plan_resident_pack).  48 solves of very different sizes need two
+    packs small solves onto one XCD (host_resident.h: plan_resident_pack).  48 solves of very different sizes need two
     launches per step with more than 16 solves in flight; every one equals the two-kernel path bit for bit."""
     from arap_flow_amd import synth
     W, H = 256, 128                                             # 4 x 32 = 128 tiles of 64 x 4

@@ -279,3 +279,20 @@ def test_resident_tile_lists_cover_every_active_vertex_once():
                     if len(cols):
                         assert bx[b] == cols[0]
         assert counts[1] <= counts[0]
+
+
+def test_warp_scratch_sizes_are_the_recorded_ones():
+    """ArapFlow_Warp / WarpEx / WarpLayers ScratchBytes (pure host functions): callers allocate by them, so the values are
+    pinned.  The numbers were recorded from the build before the scratch layout was stated once (abi_warp.h:
+    warp_scratch), not computed from it.  The layered warp's size does not depend on the number of layers."""
+    from arap_flow_amd import build
+    lib = ctypes.CDLL(build.build())
+    for f in (lib.ArapFlow_WarpScratchBytes, lib.ArapFlow_WarpExScratchBytes, lib.ArapFlow_WarpLayersScratchBytes):
+        f.restype = ctypes.c_uint64
+    recorded = {(1, 1): (512, 1280, 1536), (17, 5): (1024, 3584, 3840), (854, 480): (3279616, 13117952, 13528064),
+                (1920, 1080): (16589056, 66355712, 68429312)}
+    for (W, H), (warp, warp_ex, layers) in recorded.items():
+        assert lib.ArapFlow_WarpScratchBytes(W, H) == warp, (W, H)
+        assert lib.ArapFlow_WarpExScratchBytes(W, H) == warp_ex, (W, H)
+        for n in (1, 3, 255):
+            assert lib.ArapFlow_WarpLayersScratchBytes(W, H, n) == layers, (W, H, n)

@@ -3,6 +3,8 @@
     python tools/loop_diff.py asm OUT.s            device assembly of arap_flow_amd/csrc/arapopt.hip as it is now
     python tools/loop_diff.py stats A.s [NS]       instruction mix of the main loop of k_pcg_resident<false, NS> (default 7)
     python tools/loop_diff.py diff A.s B.s [NS]    the two loops side by side with register NAMES normalised
+    python tools/loop_diff.py same A.s B.s         every function and kernel descriptor of A against B's of the same name,
+                                                   whatever their order in the files; exit status 1 on any difference
 
 Why: the loop runs at 253 of 256 VGPRs and ~100 SGPRs, and any change elsewhere in the kernel can change its register
 allocation and instruction order.  Round 3: a build whose loop differed from its predecessor's by ONE s_waitcnt (the second
@@ -65,6 +67,54 @@ def stats(body):
             "v_writelane": c.get("v_writelane_b32", 0), "s_nop": c.get("s_nop", 0), "s_waitcnt": c.get("s_waitcnt", 0)}
 
 
+def functions(path):
+    """{name: text} of every function of a device assembly file, from its "Begin function" line to the next one's, kernel
+    descriptor, resource symbols and "Kernel info" included, plus "<metadata NAME>" per kernel entry of the trailing
+    amdhsa.kernels list ("<head>" / "<tail>": what stands before the first and behind the last).  Labels carry the function's ordinal in the file (.LBB12_3, .Lfunc_end12): dropped, so that a
+    function compares equal wherever it stands.  Lines with the per-compilation __hip_cuid_ symbol are ignored."""
+    lines = [l for l in open(path).read().split("\n") if "__hip_cuid_" not in l]
+    meta = next((i for i, l in enumerate(lines) if l.strip() == ".amdgpu_metadata"), len(lines))
+    out, name, body = {}, "<head>", []
+    for l in lines[:meta]:
+        m = re.search(r"; -- Begin function (\S+)", l)
+        if not m and l.split()[:1] == [".p2alignl"]:                           # padding behind the last function
+            m = re.match("(<tail>)", "<tail>")
+        if m:
+            k = len(body)
+            while k and body[k - 1].split()[:1] in ([".text"], [".section"]):   # the new function's own section line
+                k -= 1
+            out[name] = "\n".join(body[:k])
+            name, body = m.group(1), body[k:]
+        body.append(re.sub(r"(\.LBB|\bBB|\.Lfunc_end|\.Lfunc_begin)\d+", r"\1", l))
+    out[name] = "\n".join(body)
+    entry = []
+    for l in lines[meta:]:
+        if l.startswith(("  - .", "amdhsa.target")) and entry:                 # next entry / end of the list
+            n = next((e.split()[-1] for e in entry if e.strip().startswith(".name:")), "?")
+            out["<metadata %s>" % n] = "\n".join(entry)
+            entry = []
+        if entry or l.startswith("  - ."):
+            entry.append(l)
+    return out
+
+
+def same(a, b):
+    fa, fb = functions(a), functions(b)
+    bad = 0
+    for n in sorted(set(fa) | set(fb)):
+        if n not in fa or n not in fb:
+            print("only in %s: %s" % (b if n in fb else a, n))
+            bad += 1
+        elif fa[n] != fb[n]:
+            d = list(difflib.unified_diff(fa[n].split("\n"), fb[n].split("\n"), a, b, n=1, lineterm=""))
+            print("differs: %s (%d diff lines)" % (n, len(d)))
+            print("\n".join(d[:40]))
+            bad += 1
+    kernels = sum(1 for n in fa if n.startswith("<metadata"))
+    print("%d functions and %d kernel metadata entries compared, %d differ" % (len(fa) - kernels, kernels, bad))
+    return 1 if bad else 0
+
+
 def main():
     a = sys.argv[1:]
     if len(a) >= 2 and a[0] == "asm":
@@ -83,6 +133,8 @@ def main():
             print(l)
             n += 1
         print("(%d diff lines)" % n)
+    elif len(a) >= 3 and a[0] == "same":
+        return same(a[1], a[2])
     else:
         print(__doc__)
         return 2
