@@ -8,10 +8,16 @@
 //   k_pcg_b      : PCGStep2 (:446-489)
 //   k_gn_update  : PCGLinearUpdate (:552-557)    (frame solver: done by the resident launch itself, ResDev::fuse_update)
 //   k_cost       : computeCost (:580-592)
+// Other forms of the two PCG phases, same operation list from the shared pieces of arap_pcg.h (edge term, diagonal,
+// alpha / beta, p double buffer, M^-1_O table, quad accesses):
+//   phase A : k_pcg_a_lds<TX,TY> (arap_tiled.h: pcg_a_tile_body) ; k_pcg_a_grid<TX,TY>, k_pcg_a_march<RB>,
+//             k_pcg_a_march2<RB> (arap_stream.h: pcg_a_tile_body, pcg_a_march_body) ; phase A of k_pcg_resident
+//   phase B : k_pcg_b4 (below) ; k_pcg_b4_lean, k_pcg_b4_r (arap_stream.h) ; phase B of k_pcg_resident
+//   LM kind : k_lm_* (arap_lm.h)
 // Launch shape: workgroup = 64 x 4 threads (4 wavefronts, each 64 consecutive x of one row),
 // grid = (ceil(W/64), ceil(H/4), batch); one thread per mesh vertex.
 #pragma once
-#include "arap_device.h"
+#include "arap_pcg.h"
 
 namespace arap {
 
@@ -133,7 +139,7 @@ __device__ __forceinline__ void gn_init_body(const PlanDev& pd)
         for (int i = (int)v.lb * (TILE_X * TILE_Y) + t; i < pd.res_gran_n; i += (int)v.nlb * (TILE_X * TILE_Y))
             pd.res_gran[i] = 0ull;
     }
-    double* const rho0 = pd.red + ((size_t)v.b * pd.nslots + 0) * NSHARD;
+    double* const rho0 = red_slot(pd, v.b, 0);
     // (a workgroup with nothing to do still reports to the order-fixed sum: arap_device.h, block_reduce_fixed)
     if (!pd.tileact[(size_t)v.b * pd.tilesX * pd.tilesY + v.wg]) { block_reduce_fixed<1>(pd, v.b, v.lb, v.nlb, 0.0, 0.0, rho0, nullptr); return; }
     const Slot sl = pd.slots[v.b];
@@ -172,8 +178,7 @@ __device__ __forceinline__ void gn_init_body(const PlanDev& pd)
             gx = fmaf(wr, ex - fx, gx);
             gy = fmaf(wr, ey - fy, gy);
             ga = fmaf(-wr, fmaf(qx, ex, qy * ey), ga);
-            dO = dO + (wr * wr + wr * wr);
-            dA = fmaf(wr * wr, fmaf(qx, qx, qy * qy), dA);
+            jtj_diag_edge(wr, qx, qy, dO, dA);
         }
         float dOf = dO;
         if (f & F_FIT) {
@@ -212,69 +217,37 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void k_gn_init_resf(PlanDev pd) { g
 // Iteration l, phase A.  p_l = (l == 0) ? p_init : z + beta * p_{l-1}, with
 // beta = rho_l / rho_{l-1} if rho_{l-1} > 0 else 0 (PCGStep3).  Then Ap = J^T J p_l and
 // sigma_l += p_l . Ap (PCGStep1).  p is double-buffered (read `pin`, write `pout`) because the
-// stencil needs the neighbours' p_l, which this kernel recomputes from their z and p_{l-1}.
-// reduction slots of the GN step: 0 = rho_0 ; 2l+1 = sigma_l ; 2l+2 = rho_{l+1}
+// stencil needs the neighbours' p_l, which this kernel recomputes from their z and p_{l-1} (arap_pcg.h: PBuf, next_dir).
 __global__ __launch_bounds__(TILE_X* TILE_Y) void k_pcg_a(PlanDev pd, int l)
 {
     const VIdx v = vidx(pd);
-    double* const sigma_l = pd.red + ((size_t)v.b * pd.nslots + (2 * l + 1)) * NSHARD;
+    double* const sigma_l = red_slot(pd, v.b, 2 * l + 1);
     if (!pd.tileact[(size_t)v.b * pd.tilesX * pd.tilesY + v.wg]) { block_reduce_fixed<1>(pd, v.b, v.lb, v.nlb, 0.0, 0.0, sigma_l, nullptr); return; }
     const Slot sl = pd.slots[v.b];
     const size_t gb = (size_t)v.b * pd.N;
-    const float2* __restrict__ pinO = (l & 1) ? pd.pO1 : pd.pO0;
-    const float* __restrict__ pinA = (l & 1) ? pd.pA1 : pd.pA0;
-    float2* __restrict__ poutO = (l & 1) ? pd.pO0 : pd.pO1;
-    float* __restrict__ poutA = (l & 1) ? pd.pA0 : pd.pA1;
-    float beta = 0.f;
-    if (l > 0) {
-        const double* rs = pd.red + (size_t)v.b * pd.nslots * NSHARD;
-        const float rhoNew = read_scalar(rs + (size_t)(2 * l) * NSHARD);
-        const float rhoOld = read_scalar(rs + (size_t)(2 * l - 2) * NSHARD);
-        if (rhoOld > 0.f) beta = rhoNew / rhoOld;
-    }
+    const PBuf pin = p_in(pd, l), pout = p_out(pd, l);
+    const float beta = pcg_beta(pd, v.b, l);
     const unsigned f = v.in ? pd.flags[v.g] : 0u;
     double d = 0.0;
     if (f & F_ACT) {
         const float wr2 = sl.wr * sl.wr;
-        float2 pO = pinO[v.g];
-        float pA = pinA[v.g];
-        if (l > 0) {
-            const float2 zO = pd.zO[v.g];
-            const float zA = pd.zA[v.g];
-            pO.x = fmaf(beta, pO.x, zO.x);
-            pO.y = fmaf(beta, pO.y, zO.y);
-            pA = fmaf(beta, pA, zA);
-        }
-        poutO[v.g] = pO;
-        poutA[v.g] = pA;
+        float2 pO = pin.O[v.g];
+        float pA = pin.A[v.g];
+        if (l > 0) next_dir(pO, pA, pd.zO[v.g], pd.zA[v.g], beta);
+        pout.O[v.g] = pO;
+        pout.A[v.g] = pA;
         const float2 csi = pd.cs[v.g];
-        const float ci = csi.x, si = csi.y;
         const float2 Ui = sl.U[v.i];
         float ax = 0.f, ay = 0.f, aa = 0.f;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if (!(f & (1u << s))) continue;
             const int n = v.i + noff(s, pd.W);
-            float2 qO = pinO[gb + n];
-            float qA = pinA[gb + n];
-            if (l > 0) {
-                const float2 zO = pd.zO[gb + n];
-                const float zA = pd.zA[gb + n];
-                qO.x = fmaf(beta, qO.x, zO.x);
-                qO.y = fmaf(beta, qO.y, zO.y);
-                qA = fmaf(beta, qA, zA);
-            }
-            const float2 csn = pd.cs[gb + n];
-            const float cn = csn.x, sn = csn.y;
+            float2 qO = pin.O[gb + n];
+            float qA = pin.A[gb + n];
+            if (l > 0) next_dir(qO, qA, pd.zO[gb + n], pd.zA[gb + n], beta);
             const float2 Un = sl.U[n];
-            const float dx = Ui.x - Un.x, dy = Ui.y - Un.y;
-            const float qx = fmaf(-si, dx, -(ci * dy)), qy = fmaf(ci, dx, -(si * dy));
-            const float hx = fmaf(-sn, dx, -(cn * dy)), hy = fmaf(cn, dx, -(sn * dy));
-            const float px = pO.x - qO.x, py = pO.y - qO.y;
-            const float tx = fmaf(-qx, pA, px), ty = fmaf(-qy, pA, py);
-            ax = fmaf(wr2, fmaf(-hx, qA, px + tx), ax);
-            ay = fmaf(wr2, fmaf(-hy, qA, py + ty), ay);
-            aa = fmaf(-wr2, fmaf(qx, tx, qy * ty), aa);
+            jtj_edge(Ui.x - Un.x, Ui.y - Un.y, csi, pO, pA, pd.cs[gb + n], qO, qA, wr2, ax, ay, aa);
         }
         if (f & F_FIT) {
             const float wf2 = sl.wf * sl.wf;
@@ -300,25 +273,20 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void k_pcg_a(PlanDev pd, int l)
 __global__ __launch_bounds__(TILE_X* TILE_Y) void k_pcg_b(PlanDev pd, int l)
 {
     const VIdx v = vidx(pd);
-    double* const rho_next = pd.red + ((size_t)v.b * pd.nslots + (2 * l + 2)) * NSHARD;
+    double* const rho_next = red_slot(pd, v.b, 2 * l + 2);
     double* const q_next = pd.lm ? pd.lmred + (size_t)(l + 1) * NSHARD : nullptr;
     if (!pd.tileact[(size_t)v.b * pd.tilesX * pd.tilesY + v.wg]) {
         if (pd.lm) block_reduce_fixed<2>(pd, v.b, v.lb, v.nlb, 0.0, 0.0, rho_next, q_next);
         else block_reduce_fixed<1>(pd, v.b, v.lb, v.nlb, 0.0, 0.0, rho_next, nullptr);
         return;
     }
-    const float2* __restrict__ pO_ = (l & 1) ? pd.pO0 : pd.pO1;   // written by k_pcg_a(l)
-    const float* __restrict__ pA_ = (l & 1) ? pd.pA0 : pd.pA1;
-    const double* rs = pd.red + (size_t)v.b * pd.nslots * NSHARD;
-    const float rho = read_scalar(rs + (size_t)(2 * l) * NSHARD);
-    const float sigma = read_scalar(rs + (size_t)(2 * l + 1) * NSHARD);
-    float alpha = 0.f;
-    if (sigma > 0.f) alpha = rho / sigma;
+    const PBuf p = p_out(pd, l);                                   // written by phase A of iteration l
+    const float alpha = pcg_alpha(pd, v.b, l);
     const unsigned f = v.in ? pd.flags[v.g] : 0u;
     double d = 0.0, q = 0.0;
     if (f & F_ACT) {
-        const float2 pO = pO_[v.g], ApO = pd.ApO[v.g], mO = pd.preO[v.g];
-        const float pA = pA_[v.g], ApA = pd.ApA[v.g], mA = pd.preA[v.g];
+        const float2 pO = p.O[v.g], ApO = pd.ApO[v.g], mO = pd.preO[v.g];
+        const float pA = p.A[v.g], ApA = pd.ApA[v.g], mA = pd.preA[v.g];
         float2 dO = pd.deltaO[v.g], rO = pd.rO[v.g];
         float dA = pd.deltaA[v.g], rA = pd.rA[v.g];
         dO.x = fmaf(alpha, pO.x, dO.x);
@@ -355,29 +323,16 @@ __global__ __launch_bounds__(256) void k_pcg_b4(PlanDev pd, int l)
     const int q = blockIdx.x * 256 + threadIdx.x;          // quad index
     const int nq = pd.N >> 2;
     const size_t gb = (size_t)b * pd.N;
-    const float4* __restrict__ pO4 = (const float4*)(((l & 1) ? pd.pO0 : pd.pO1) + gb);
-    const float4* __restrict__ pA4 = (const float4*)(((l & 1) ? pd.pA0 : pd.pA1) + gb);
-    const double* rs = pd.red + (size_t)b * pd.nslots * NSHARD;
-    const float rho = read_scalar(rs + (size_t)(2 * l) * NSHARD);
-    const float sigma = read_scalar(rs + (size_t)(2 * l + 1) * NSHARD);
-    float alpha = 0.f;
-    if (sigma > 0.f) alpha = rho / sigma;
+    const PBuf p = p_out(pd, l);
+    const float alpha = pcg_alpha(pd, b, l);
     double d = 0.0;
     const unsigned fw = q < nq ? ((const unsigned*)(pd.flags + gb))[q] : 0u;      // 4 flag bytes
     if (fw & 0x20202020u) {
-        float4* dO4 = (float4*)(pd.deltaO + gb); float4* rO4 = (float4*)(pd.rO + gb); float4* zO4 = (float4*)(pd.zO + gb);
-        float4* dA4 = (float4*)(pd.deltaA + gb); float4* rA4 = (float4*)(pd.rA + gb); float4* zA4 = (float4*)(pd.zA + gb);
-        const float4* ApO4 = (const float4*)(pd.ApO + gb); const float4* mO4 = (const float4*)(pd.preO + gb);
-        const float4* ApA4 = (const float4*)(pd.ApA + gb); const float4* mA4 = (const float4*)(pd.preA + gb);
         float po[8], apo[8], mo[8], dl[8], r[8], z[8], pa[4], apa[4], ma[4], dla[4], ra[4], za[4];
-        *(float4*)&po[0] = pO4[2 * q]; *(float4*)&po[4] = pO4[2 * q + 1];
-        *(float4*)&apo[0] = ApO4[2 * q]; *(float4*)&apo[4] = ApO4[2 * q + 1];
-        *(float4*)&mo[0] = mO4[2 * q]; *(float4*)&mo[4] = mO4[2 * q + 1];
-        *(float4*)&dl[0] = dO4[2 * q]; *(float4*)&dl[4] = dO4[2 * q + 1];
-        *(float4*)&r[0] = rO4[2 * q]; *(float4*)&r[4] = rO4[2 * q + 1];
-        *(float4*)&z[0] = zO4[2 * q]; *(float4*)&z[4] = zO4[2 * q + 1];
-        *(float4*)pa = pA4[q]; *(float4*)apa = ApA4[q]; *(float4*)ma = mA4[q];
-        *(float4*)dla = dA4[q]; *(float4*)ra = rA4[q]; *(float4*)za = zA4[q];
+        ld_quadO(po, p.O + gb, q); ld_quadO(apo, pd.ApO + gb, q); ld_quadO(mo, pd.preO + gb, q);
+        ld_quadO(dl, pd.deltaO + gb, q); ld_quadO(r, pd.rO + gb, q); ld_quadO(z, pd.zO + gb, q);
+        ld_quadA(pa, p.A + gb, q); ld_quadA(apa, pd.ApA + gb, q); ld_quadA(ma, pd.preA + gb, q);
+        ld_quadA(dla, pd.deltaA + gb, q); ld_quadA(ra, pd.rA + gb, q); ld_quadA(za, pd.zA + gb, q);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (!((fw >> (8 * k)) & F_ACT)) continue;
@@ -392,12 +347,10 @@ __global__ __launch_bounds__(256) void k_pcg_b4(PlanDev pd, int l)
             za[k] = ma[k] * ra[k];
             d += (double)dot3(z[2 * k], z[2 * k + 1], za[k], r[2 * k], r[2 * k + 1], ra[k]);
         }
-        dO4[2 * q] = *(float4*)&dl[0]; dO4[2 * q + 1] = *(float4*)&dl[4];
-        rO4[2 * q] = *(float4*)&r[0]; rO4[2 * q + 1] = *(float4*)&r[4];
-        zO4[2 * q] = *(float4*)&z[0]; zO4[2 * q + 1] = *(float4*)&z[4];
-        dA4[q] = *(float4*)dla; rA4[q] = *(float4*)ra; zA4[q] = *(float4*)za;
+        st_quadO(pd.deltaO + gb, q, dl); st_quadO(pd.rO + gb, q, r); st_quadO(pd.zO + gb, q, z);
+        st_quadA(pd.deltaA + gb, q, dla); st_quadA(pd.rA + gb, q, ra); st_quadA(pd.zA + gb, q, za);
     }
-    block_reduce_fixed<1>(pd, b, blockIdx.x, gridDim.x, d, 0.0, pd.red + ((size_t)b * pd.nslots + (2 * l + 2)) * NSHARD, nullptr);
+    block_reduce_fixed<1>(pd, b, blockIdx.x, gridDim.x, d, 0.0, red_slot(pd, b, 2 * l + 2), nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -409,19 +362,15 @@ __device__ __forceinline__ void gn_update_body(const PlanDev& pd, const VIdx& v,
     if (pd.res_err && *pd.res_err) return;          // the resident kernel gave up: leave X as it was (see PlanDev)
     if (!pd.tileact[(size_t)v.b * pd.tilesX * pd.tilesY + v.wg]) return;
     float alpha = 0.f;
-    if (lag_l >= 0) {
-        const double* rs = pd.red + (size_t)v.b * pd.nslots * NSHARD;
-        const float rho = read_scalar(rs + (size_t)(2 * lag_l) * NSHARD);
-        const float sigma = read_scalar(rs + (size_t)(2 * lag_l + 1) * NSHARD);
-        if (sigma > 0.f) alpha = rho / sigma;
-    }
+    if (lag_l >= 0) alpha = pcg_alpha(pd, v.b, lag_l);
     if (!v.in || !(pd.flags[v.g] & F_ACT)) return;
     const Slot sl = pd.slots[v.b];
     float2 d = pd.deltaO[v.g];
     float da = pd.deltaA[v.g];
     if (lag_l >= 0) {
-        const float2 p = ((lag_l & 1) ? pd.pO0 : pd.pO1)[v.g];          // written by phase A of iteration lag_l
-        const float pa = ((lag_l & 1) ? pd.pA0 : pd.pA1)[v.g];
+        const PBuf pb = p_out(pd, lag_l);                               // written by phase A of iteration lag_l
+        const float2 p = pb.O[v.g];
+        const float pa = pb.A[v.g];
         d.x = fmaf(alpha, p.x, d.x);
         d.y = fmaf(alpha, p.y, d.y);
         da = fmaf(alpha, pa, da);
@@ -495,20 +444,8 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void k_export_jtf(PlanDev pd, float
         const float2 r = pd.rO[v.g];
         go = make_float2(-r.x, -r.y);
         ga = -pd.rA[v.g];
-        const float wr = sl.wr, wf = sl.wf;
-        const float2 csi = pd.cs[v.g];
-        const float2 Ui = sl.U[v.i];
-        float DO = 0.f, DA = 0.f;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (!(f & (1u << s))) continue;
-            const float2 Un = sl.U[v.i + noff(s, pd.W)];
-            const float dx = Ui.x - Un.x, dy = Ui.y - Un.y;
-            const float qx = fmaf(-csi.y, dx, -(csi.x * dy)), qy = fmaf(csi.x, dx, -(csi.y * dy));
-            DO = DO + (wr * wr + wr * wr);
-            DA = fmaf(wr * wr, fmaf(qx, qx, qy * qy), DA);
-        }
-        if (f & F_FIT) DO = fmaf(wf, wf, DO);
+        float DO, DA;
+        jtj_diag(pd, sl, v.g, v.i, f, DO, DA);
         d_o = make_float2(DO, DO);
         d_a = DA;
     }

@@ -2,33 +2,13 @@
 // solverGPUGaussNewton.t, `problemSpec:UsesLambda()`): PCGSaveSSq :622-627, PCGComputeCtC :616-621 (computeCtC =
 // diag(J^T J) / trust_region_radius, o.t:2255-2287), PCGFinalizeDiagonal :629-662, PCGStep2_1stHalf / computeAdelta /
 // PCGStep2_2ndHalf :491-535,570-575, computeModelCost :665-678 (o.t:2180-2201).  applyJTJ + CtC*P and the q term of
-// PCGStep2 live in k_pcg_a / k_pcg_b behind PlanDev::lm.  The application never selects this kind
+// PCGStep2 live in k_pcg_a / k_pcg_b behind PlanDev::lm; the edge term and the raw diagonal are arap_pcg.h's.  The application never selects this kind
 // (CombinedSolverBase.h:75-77) and the reference holds no LM output, so its parity is pinned to the CPU
 // restatement only.  Host loop: host_lm.h:plan_step_lm.
 #pragma once
 #include "arap_kernels.h"
 
 namespace arap {
-
-// raw diag(J^T J) of vertex v (the accumulation order of k_gn_init)
-__device__ __forceinline__ void diag_raw(const PlanDev& pd, const Slot& sl, const VIdx& v, unsigned f, float& DO, float& DA)
-{
-    const float wr = sl.wr, wf = sl.wf;
-    const float2 csi = pd.cs[v.g];
-    const float2 Ui = sl.U[v.i];
-    float dO = 0.f, dA = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        if (!(f & (1u << s))) continue;
-        const float2 Un = sl.U[v.i + noff(s, pd.W)];
-        const float dx = Ui.x - Un.x, dy = Ui.y - Un.y;
-        const float qx = fmaf(-csi.y, dx, -(csi.x * dy)), qy = fmaf(csi.x, dx, -(csi.y * dy));
-        dO = dO + (wr * wr + wr * wr);
-        dA = fmaf(wr * wr, fmaf(qx, qx, qy * qy), dA);
-    }
-    if (f & F_FIT) dO = fmaf(wf, wf, dO);
-    DO = dO; DA = dA;
-}
 
 __device__ __forceinline__ float clampf(float x, float lo, float hi)
 {
@@ -42,14 +22,14 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void k_lm_prepare(PlanDev pd, float
                                                                 int first)
 {
     const VIdx v = vidx(pd);
-    double* const rho0 = pd.red + ((size_t)v.b * pd.nslots + 0) * NSHARD;
+    double* const rho0 = red_slot(pd, v.b, 0);
     if (!pd.tileact[(size_t)v.b * pd.tilesX * pd.tilesY + v.wg]) { block_reduce_fixed<2>(pd, v.b, v.lb, v.nlb, 0.0, 0.0, rho0, pd.lmred); return; }
     const Slot sl = pd.slots[v.b];
     const unsigned f = v.in ? pd.flags[v.g] : 0u;
     double d = 0.0, q = 0.0;
     if (f & F_ACT) {
         float DO, DA;
-        diag_raw(pd, sl, v, f, DO, DA);
+        jtj_diag(pd, sl, v.g, v.i, f, DO, DA);
         const float inv_radius = 1.0f / radius;
         if (first) { pd.SSqO[v.g] = pd.preO[v.g]; pd.SSqA[v.g] = pd.preA[v.g]; }
         const float ssO = pd.SSqO[v.g].x, ssA = pd.SSqA[v.g];
@@ -89,7 +69,6 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void k_lm_apply(PlanDev pd, const f
     const float2 pO = inO[v.g];
     const float pA = inA[v.g];
     const float2 csi = pd.cs[v.g];
-    const float ci = csi.x, si = csi.y;
     const float2 Ui = sl.U[v.i];
     float ax = 0.f, ay = 0.f, aa = 0.f;
 #pragma unroll
@@ -98,17 +77,8 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void k_lm_apply(PlanDev pd, const f
         const int n = v.i + noff(s, pd.W);
         const float2 qO = inO[gb + n];
         const float qA = inA[gb + n];
-        const float2 csn = pd.cs[gb + n];
-        const float cn = csn.x, sn = csn.y;
         const float2 Un = sl.U[n];
-        const float dx = Ui.x - Un.x, dy = Ui.y - Un.y;
-        const float qx = fmaf(-si, dx, -(ci * dy)), qy = fmaf(ci, dx, -(si * dy));
-        const float hx = fmaf(-sn, dx, -(cn * dy)), hy = fmaf(cn, dx, -(sn * dy));
-        const float px = pO.x - qO.x, py = pO.y - qO.y;
-        const float tx = fmaf(-qx, pA, px), ty = fmaf(-qy, pA, py);
-        ax = fmaf(wr2, fmaf(-hx, qA, px + tx), ax);
-        ay = fmaf(wr2, fmaf(-hy, qA, py + ty), ay);
-        aa = fmaf(-wr2, fmaf(qx, tx, qy * ty), aa);
+        jtj_edge(Ui.x - Un.x, Ui.y - Un.y, csi, pO, pA, pd.cs[gb + n], qO, qA, wr2, ax, ay, aa);
     }
     if (f & F_FIT) {
         const float wf2 = sl.wf * sl.wf;
@@ -125,27 +95,22 @@ __global__ __launch_bounds__(TILE_X* TILE_Y) void k_lm_step2a(PlanDev pd, int l)
 {
     const VIdx v = vidx(pd);
     if (!pd.tileact[(size_t)v.b * pd.tilesX * pd.tilesY + v.wg]) return;
-    const float2* __restrict__ pO_ = (l & 1) ? pd.pO0 : pd.pO1;
-    const float* __restrict__ pA_ = (l & 1) ? pd.pA0 : pd.pA1;
-    const double* rs = pd.red + (size_t)v.b * pd.nslots * NSHARD;
-    const float rho = read_scalar(rs + (size_t)(2 * l) * NSHARD);
-    const float sigma = read_scalar(rs + (size_t)(2 * l + 1) * NSHARD);
-    float alpha = 0.f;
-    if (sigma > 0.f) alpha = rho / sigma;
+    const PBuf pb = p_out(pd, l);
+    const float alpha = pcg_alpha(pd, v.b, l);
     if (!v.in || !(pd.flags[v.g] & F_ACT)) return;
     float2 d = pd.deltaO[v.g];
-    const float2 p = pO_[v.g];
+    const float2 p = pb.O[v.g];
     d.x = fmaf(alpha, p.x, d.x);
     d.y = fmaf(alpha, p.y, d.y);
     pd.deltaO[v.g] = d;
-    pd.deltaA[v.g] = fmaf(alpha, pA_[v.g], pd.deltaA[v.g]);
+    pd.deltaA[v.g] = fmaf(alpha, pb.A[v.g], pd.deltaA[v.g]);
 }
 
 // PCGStep2_2ndHalf: r = b - A delta ; z = pre r ; rho' ; q = 0.5 delta.(r + b)
 __global__ __launch_bounds__(TILE_X* TILE_Y) void k_lm_step2b(PlanDev pd, int l)
 {
     const VIdx v = vidx(pd);
-    double* const rho_next = pd.red + ((size_t)v.b * pd.nslots + (2 * l + 2)) * NSHARD;
+    double* const rho_next = red_slot(pd, v.b, 2 * l + 2);
     double* const q_next = pd.lmred + (size_t)(l + 1) * NSHARD;
     if (!pd.tileact[(size_t)v.b * pd.tilesX * pd.tilesY + v.wg]) { block_reduce_fixed<2>(pd, v.b, v.lb, v.nlb, 0.0, 0.0, rho_next, q_next); return; }
     const unsigned f = v.in ? pd.flags[v.g] : 0u;

@@ -876,6 +876,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                     aa = fmaf(-w, fmaf(QX, t.x, (QY) * t.y), aa);                                      \
                     (void)cn; (void)sn;                                                                \
                 }
+                // (the four rows below are the sign table of jtj_edge_grid<S>, arap_pcg.h)
                 //     bit no edge    -q          -h          q
                 RES_EDGE(0, 0,     -si,  ci,   -sn,  cn,    si, -ci)      // s=( 1, 0): q=( si,-ci) h=( sn,-cn)
                 RES_EDGE(1, 1,      si, -ci,    sn, -cn,   -si,  ci)      // s=(-1, 0): q=(-si, ci) h=(-sn, cn)

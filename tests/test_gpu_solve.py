@@ -196,6 +196,48 @@ def test_resident_and_two_kernel_paths_are_bit_identical(gpu_state):
             assert a["cost"] == b["cost"]
 
 
+def test_phase_a_variants_of_the_kernel_per_phase_path_are_bit_identical(monkeypatch):
+    """ARAPOPT_STREAM_A (read when a state is created) picks the streaming kernels of the frame solver's kernel-per-phase
+    path: unset = the marching phase A (the lean pair k_pcg_a_march2 + k_pcg_b4_r where most tiles are active, else
+    k_pcg_a_march + k_pcg_b4_lean), 1 = the tiled k_pcg_a_grid, 2 = the k_pcg_a_march pair at any mask.  All of them
+    perform one operation list through the shared device pieces of arap_pcg.h: identical Offset / Angle bits and cost,
+    at a full mask (854x480, K = 0) and at a DAVIS-shaped one."""
+    from arap_flow_amd import synth
+    W, H, nfr, sched = 854, 480, 2, (1, 2, 40)
+    for K in (0, 1):
+        frames = [synth.make_frame(W, H, seed=20 + s, K=max(K, 1), fd=2, full_mask=(K == 0)) for s in range(nfr)]
+        outs = []
+        for knob in (None, "1", "2"):
+            if knob is None:
+                monkeypatch.delenv("ARAPOPT_STREAM_A", raising=False)
+            else:
+                monkeypatch.setenv("ARAPOPT_STREAM_A", knob)
+            st, fs = opt.State(), None
+            try:
+                st.set_resident(False)
+                fs = opt.FrameSolver(st, W, H, batch=nfr)
+                for b, f in enumerate(frames):
+                    fs.set_frame(b, f["mask_red"], f["constraints"])
+                fs.solve(nfr, *sched)
+                outs.append([fs.results(b, want_rgb=False) for b in range(nfr)])
+                stats = fs.stats()
+                assert stats["resident_launches"] == 0
+                # the knob reached this state: either value takes the solve off the lean pair, which the full mask has
+                # when it is unset (the statistics do not tell k_pcg_a_grid from k_pcg_a_march: both are "not lean")
+                if knob is not None:
+                    assert not stats["lean_stream"]
+                elif K == 0:
+                    assert stats["lean_stream"]
+            finally:
+                if fs is not None:
+                    fs.close()
+                st.close()
+        for other in outs[1:]:
+            for a, b in zip(outs[0], other):
+                assert np.array_equal(a["offset"], b["offset"]) and np.array_equal(a["angle"], b["angle"])
+                assert a["cost"] == b["cost"]
+
+
 def test_frame_solver_step_sequencing_quiet_vs_verbose(gpu_state, capfd):
     """A quiet frame solve runs a Gauss-Newton step as [k_gn_init_resf, resident launch that applies the step itself], all
     steps of a ramp step in one graph; a verbose one (the state prints the cost after every step) as [k_gn_prep, k_gn_init,

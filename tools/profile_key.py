@@ -20,8 +20,8 @@ def _code_only(text):
 # the sources a kernel's code comes from: a record stays valid while THOSE are unchanged
 KERNEL_SOURCES = {
     "k_pcg_resident": ("arap_resident.h", "arap_device.h"),
-    "k_pcg_a": ("arap_stream.h", "arap_kernels.h", "arap_tiled.h", "arap_device.h"),
-    "k_pcg_b": ("arap_stream.h", "arap_kernels.h", "arap_device.h"),
+    "k_pcg_a": ("arap_stream.h", "arap_kernels.h", "arap_tiled.h", "arap_pcg.h", "arap_device.h"),
+    "k_pcg_b": ("arap_stream.h", "arap_kernels.h", "arap_pcg.h", "arap_device.h"),
 }
 
 
