@@ -4,11 +4,10 @@
   python arap_deform.py RGB Mask Constraint Flow warped_RGB warped_Mask       (one frame)
   python arap_deform.py listfile                                              (one solve per line, 6 paths)
 
-A list line may carry optional tokens after its six paths: bwd=PATH.flo (backward flow), occ=PATH.png (forward
-occlusion), occ_bwd=PATH.png (backward occlusion); other trailing tokens are ignored.
-A line whose first word is `layers` is no solve but the layered warp of one frame (DESIGN.md "Layered warp"):
-  layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P]
-It runs once every earlier line of the list is solved and written (its inputs may be their outputs).
+A list line may carry optional output tokens after its six paths (backward flow, forward and backward occlusion), and
+a line whose first word is `layers` is no solve but the layered warp of one frame: both forms are defined in
+arap_flow_amd/pipeline.py (SolveLine, parse_layers).  A layers line runs once every earlier line of the list is solved
+and written (its inputs may be their outputs).
 
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
 same border pins, same outputs (.flo + two PNGs).  ARAP_PLAN may name the reference's arap_plan.t; it is then
@@ -36,7 +35,7 @@ def usage():
 def main(argv):
     from arap_flow_amd import opt, pipeline
     if len(argv) == 7:
-        lines = [("solve", tuple(argv[1:7]), None)]
+        lines = [pipeline.SolveLine(*argv[1:7], extra={})]
     elif len(argv) == 2:
         try:
             lines = pipeline.read_list_items(argv[1])
@@ -65,18 +64,15 @@ def main(argv):
     # runs of solve lines go to the batched solver; a layers line waits for the run before it
     k = 0
     while k < len(lines):
-        if lines[k][0] == "layers":
-            pipeline.run_layers(state, lines[k][1])
+        if not isinstance(lines[k], pipeline.SolveLine):
+            pipeline.run_layers(state, lines[k])
             print("Saved")
             k += 1
             continue
         e = k
-        while e < len(lines) and lines[e][0] == "solve":
+        while e < len(lines) and isinstance(lines[e], pipeline.SolveLine):
             e += 1
-        run = lines[k:e]
-        extras = [ex for _, _, ex in run]
-        pipeline.deform_list(state, [ln for _, ln, _ in run], 19, 8, 400,
-                             extras=None if all(ex is None for ex in extras) else extras)
+        pipeline.deform_list(state, lines[k:e], 19, 8, 400)
         k = e
     state.close()
     return 0

@@ -3,21 +3,22 @@
 What the reference's Python 2 scripts and C++ drivers do AROUND the hot path, written from their
 behaviour (the contract each function states in its docstring), with the size / selection arithmetic as pure
 functions that tests/golden/host/ pins with hand-computed cases:
-  read_list / deform_list   ARAP/deformation/src/main.cpp:162-241  (arap_deform: 6 paths per line)
+  SolveLine, parse_line, format_line, done_token, read_list_items    the list line: a solve (6 paths, optional output
+                            tokens bwd= occ= occ_bwd=) or the `layers` line, the layered warp of one frame (addition)
+  deform_list, run_layers   ARAP/deformation/src/main.cpp:162-241  (arap_deform over a list)
   warp_files                ARAP/warping/src/main.cpp:302-336      (warp_image)
   cover_scale, fit_bg, add_bg            para_gen.py:36-61      (background compositing)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
-  parse_extra, read_list_ex              optional output tokens of a list line (bwd= occ= occ_bwd=)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
-  parse_layers, layers_line, read_list_items, run_layers    the `layers` line: layered warp of one frame (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
   resize_crop_geometry, scale_rotate     para_gen.py:253-291
-  make_arap_path                         para_gen.py:331-339
+  make_arap_path, replace_ext            para_gen.py:318-339
 No oracle import; the solve and the rasteriser run on the GPU through arap_flow_amd.opt.
 """
 import os
 import os.path as osp
 import random as rn
+from typing import NamedTuple
 
 import numpy as np
 from PIL import Image
@@ -32,24 +33,25 @@ _ANTIALIAS = getattr(Image, "LANCZOS", None) or Image.ANTIALIAS   # Image.ANTIAL
 # ------------------------------------------------------------------------------------------------------
 # arap_deform
 # ------------------------------------------------------------------------------------------------------
-def read_list(path):
-    """main.cpp:183-191: one solve per line, six whitespace-separated paths
-    rgb mask constraints out_flow out_rgb out_mask"""
-    lines = []
-    with open(path) as f:
-        for line in f:
-            tok = line.split()
-            if not tok:
-                continue
-            if tok[0] == LAYERS_WORD:                 # no solve: see read_list_items
-                continue
-            if len(tok) < 6:
-                raise ValueError("list line needs 6 paths: %r" % line)
-            lines.append(tuple(tok[:6]))
-    return lines
-
-
+# A list line is the unit of work between para_gen.py, arap_deform.py and `arap_deform --serve` (C++ twin: parse_item in
+# host/arap_deform.cpp).  It is a solve line, SolveLine, or a `layers` line, the dict of parse_layers; parse_line reads
+# either from text, format_line writes it back, done_token is the path a worker reports it done by.
 EXTRA_KEYS = ("bwd", "occ", "occ_bwd")
+LAYERS_WORD = "layers"
+LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2")
+
+
+class SolveLine(NamedTuple):
+    """main.cpp:183-191: one solve per line, six whitespace-separated paths
+        rgb mask constraints out_flow out_rgb out_mask [bwd=PATH.flo] [occ=PATH.png] [occ_bwd=PATH.png]
+    `extra`: the optional outputs the line asks for, {key: path} (parse_extra)"""
+    rgb: str
+    mask: str
+    constraints: str
+    flow: str
+    out_rgb: str
+    out_mask: str
+    extra: dict
 
 
 def parse_extra(tokens):
@@ -66,26 +68,6 @@ def parse_extra(tokens):
 def extra_tokens(extra):
     """the inverse of parse_extra, in a fixed order"""
     return ["%s=%s" % (k, extra[k]) for k in EXTRA_KEYS if extra.get(k)]
-
-
-def read_list_ex(path):
-    """read_list plus each line's optional output tokens: [(six paths, {key: path})]"""
-    lines = []
-    with open(path) as f:
-        for line in f:
-            tok = line.split()
-            if not tok:
-                continue
-            if tok[0] == LAYERS_WORD:
-                continue
-            if len(tok) < 6:
-                raise ValueError("list line needs 6 paths: %r" % line)
-            lines.append((tuple(tok[:6]), parse_extra(tok[6:])))
-    return lines
-
-
-LAYERS_WORD = "layers"
-LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2")
 
 
 def parse_layers(tokens):
@@ -118,26 +100,32 @@ def layers_line(rgb, layers, out):
     return " ".join(tok + ["%s=%s" % (k, out[k]) for k in LAYER_KEYS if out.get(k)])
 
 
-def layers_done_token(spec):
-    """what `arap_deform --serve` reports for a layers line: the path of its first output token"""
-    return next(iter(spec["out"].values()))
+def parse_line(line):
+    """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`"""
+    tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == LAYERS_WORD:
+        return parse_layers(tok)
+    if len(tok) < 6:
+        raise ValueError("list line needs 6 paths: %r" % line)
+    return SolveLine(*tok[:6], extra=parse_extra(tok[6:]))
+
+
+def format_line(item):
+    """the inverse of parse_line: the text of a list line, optional tokens in the order of extra_tokens / layers_line"""
+    if isinstance(item, SolveLine):
+        return " ".join(list(item[:6]) + extra_tokens(item.extra))
+    return layers_line(item["rgb"], item["layers"], item["out"])
+
+
+def done_token(item):
+    """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token"""
+    return item.flow if isinstance(item, SolveLine) else next(iter(item["out"].values()))
 
 
 def read_list_items(path):
-    """every line of a list in order: ("solve", six paths, {key: path}) or ("layers", parse_layers(..))"""
-    items = []
+    """every non-blank line of a list file in order, parsed (parse_line)"""
     with open(path) as f:
-        for line in f:
-            tok = line.split()
-            if not tok:
-                continue
-            if tok[0] == LAYERS_WORD:
-                items.append(("layers", parse_layers(tok)))
-                continue
-            if len(tok) < 6:
-                raise ValueError("list line needs 6 paths: %r" % line)
-            items.append(("solve", tuple(tok[:6]), parse_extra(tok[6:])))
-    return items
+        return [parse_line(line) for line in f if line.strip()]
 
 
 def run_layers(state, spec):
@@ -189,16 +177,16 @@ FILL_MIN, FILL_MAX = 8, 32     # frames per solve call: at least / at most (see 
 
 
 def _load_line(ln):
-    """loadData (main.cpp:116-138) of one list line: RGB, red channel of the mask, constraint rows"""
+    """loadData (main.cpp:116-138) of one solve line: RGB, red channel of the mask, constraint rows"""
     from . import opt
-    return load_rgb(ln[0]), load_mask_red(ln[1]), opt.load_constraints(ln[2])
+    return load_rgb(ln.rgb), load_mask_red(ln.mask), opt.load_constraints(ln.constraints)
 
 
-def _save_result(ln, r, extra=None):
-    Image.fromarray(r["warped_rgb"]).save(ln[4])
-    save_mask(r["warped_mask"], ln[5])
-    flo.flow_write(ln[3], r["flow"])
-    extra = extra or {}
+def _save_result(ln, r):
+    Image.fromarray(r["warped_rgb"]).save(ln.out_rgb)
+    save_mask(r["warped_mask"], ln.out_mask)
+    flo.flow_write(ln.flow, r["flow"])
+    extra = ln.extra
     if "bwd" in extra:
         flo.flow_write(extra["bwd"], r["backward_flow"])
     if "occ_bwd" in extra:
@@ -207,16 +195,22 @@ def _save_result(ln, r, extra=None):
         save_occ(r["occlusion"], extra["occ"])
 
 
-def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, max_batch=FILL_MAX, verbose=True,
-                extras=None):
-    """arap_deform over a list (main.cpp:223-238).  Frames of equal size are solved together: the library gives
-    every solve a group of the resident launch's workgroups sized by its active tiles, and a launch costs the same
-    however full it is, so frames are added to a batch while they still fit ONE launch (8 DAVIS-shaped 854x480
+class _Lane:
+    """one of deform_list's two alternating solvers and the lines of the batch it holds: `batch` is filled as frames are
+    accepted into the solver's slots and emptied when their results are handed on (drain), nowhere else"""
+
+    def __init__(self):
+        self.solver, self.batch = None, []
+
+
+def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, max_batch=FILL_MAX, verbose=True):
+    """arap_deform over a list of SolveLines (main.cpp:223-238).  Frames of equal size are solved together: the library
+    gives every solve a group of the resident launch's workgroups sized by its active tiles, and a launch costs the
+    same however full it is, so frames are added to a batch while they still fit ONE launch (8 DAVIS-shaped 854x480
     frames, ~24 --multseg segment solves); FILL_MIN frames per call when the resident path does not apply.
     The GPU does not wait for the host (the structure of arap_flow_amd/host/arap_deform.cpp): two solver objects
     alternate; while one batch is solved the next is decoded (worker threads) and uploaded into the other object, and
-    the previous batch's results are read from pinned memory and encoded (worker threads).
-    `extras`: per line the optional outputs it asks for ({key: path}, parse_extra), or None."""
+    the previous batch's results are read from pinned memory and encoded (worker threads)."""
     from concurrent.futures import ThreadPoolExecutor
     from . import opt
     state.use_own_stream()
@@ -231,21 +225,21 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
             return loading[k].result()
 
         writing = []
-        lanes = [dict(solver=None, batch=[], extra=[]), dict(solver=None, batch=[], extra=[])]
+        lanes = [_Lane(), _Lane()]
         size = None
 
         def drain(lane):
             """wait for the lane's solve, hand copies of its results to the writer threads"""
-            if not lane["batch"]:
+            if not lane.batch:
                 return
-            lane["solver"].wait()
-            for b, (ln, ex) in enumerate(zip(lane["batch"], lane["extra"])):
-                r = lane["solver"].host_results(b)
+            lane.solver.wait()
+            for b, ln in enumerate(lane.batch):
+                r = lane.solver.host_results(b)
                 res = {k: v.copy() for k, v in r.items() if v is not None}
-                writing.append(pool.submit(_save_result, ln, res, ex))
+                writing.append(pool.submit(_save_result, ln, res))
                 if verbose:
                     print("Saved")                                          # main.cpp:159
-            lane["batch"] = []
+            lane.batch = []
             while len(writing) > 48:
                 writing.pop(0).result()
 
@@ -256,27 +250,25 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
             if size != (W, H):
                 for lane in lanes:
                     drain(lane)
-                    if lane["solver"] is not None:
-                        lane["solver"].close()
+                    if lane.solver is not None:
+                        lane.solver.close()
                 if size is not None and verbose:
                     print("Warning: Input image has different size to one in the prebuilt plan.\n"
                           "To avoid re-building the plan and to save time, put images of the same size in the "
                           "same list.\nStarting to re-build plan...")      # CombinedSolver.h:151-153
                 for lane in lanes:
-                    lane["solver"] = opt.FrameSolver(state, W, H, batch=max_batch)
+                    lane.solver = opt.FrameSolver(state, W, H, batch=max_batch)
                 size = (W, H)
             lane, other = lanes[cur], lanes[cur ^ 1]
-            solver = lane["solver"]
-            batch = []
+            solver, batch = lane.solver, lane.batch                     # (empty: drained a round ago)
             j = i
             while j < len(lines) and len(batch) < max_batch:
-                ex = extras[j] if extras is not None else None
                 ln = lines[j]
                 rgb, mask, cons = frame_at(j)
                 if rgb.shape[:2] != (H, W):
                     break
                 if mask.shape != (H, W):
-                    raise ValueError("mask %s has another size than %s" % (ln[1], ln[0]))
+                    raise ValueError("mask %s has another size than %s" % (ln.mask, ln.rgb))
                 b = len(batch)
                 solver.set_frame(b, mask, cons, rgb=rgb, border_pins=True)
                 if b > 0:
@@ -284,15 +276,12 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
                     if launches > 1 or (launches == 0 and b >= FILL_MIN):
                         break                                   # this frame opens the next batch (its slot is re-set)
                 batch.append(ln)
-                lane["extra"].append(ex)
                 del loading[j]                                  # the device holds it now
                 j += 1
-            want = set().union(*[e or {} for e in lane["extra"]])
+            want = set().union(*[ln.extra for ln in batch])
             solver.set_outputs(backward=bool(want & {"bwd", "occ_bwd"}), occlusion="occ" in want)
             solver.solve_async(len(batch), num_iter, non_linear_iter, linear_iter, warp=True, download=True)
-            lane["batch"] = batch
-            drain(other)
-            other["extra"] = []                                        # the previous batch, while this one is being solved
+            drain(other)                                               # the previous batch, while this one is being solved
             cur ^= 1
             i = j
         for lane in (lanes[cur], lanes[cur ^ 1]):
@@ -300,8 +289,8 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
         for f in writing:
             f.result()
         for lane in lanes:
-            if lane["solver"] is not None:
-                lane["solver"].close()
+            if lane.solver is not None:
+                lane.solver.close()
 
 
 def warp_files(state, rgb_path, mask_path, flo_path, out_rgb_path, out_mask_path, extra=None):
@@ -450,9 +439,13 @@ def scale_rotate(im_path, mk_path, size=None):
     return changed, im, mk
 
 
+EXTRA_OF = dict(bwd_gen="bwd", occbwd_gen="occ_bwd", occ_gen="occ")   # para_gen's path key -> list-line token
+
+
 def make_arap_path(p):
-    """para_gen.py:331-339: the list-file line of one solve"""
-    return " ".join(osp.abspath(p[k]) for k in ("rgb1_gen", "msk1_gen", "cstr_tmp", "flow_gen", "rgb2_gen", "msk2_gen"))
+    """para_gen.py:331-339: the list-file line of one solve, from para_gen's path table of the pair (or segment)"""
+    six = [osp.abspath(p[k]) for k in ("rgb1_gen", "msk1_gen", "cstr_tmp", "flow_gen", "rgb2_gen", "msk2_gen")]
+    return SolveLine(*six, extra={t: p[k] for k, t in EXTRA_OF.items() if k in p})
 
 
 def replace_ext(dict_path, seg_num, keep_orgs=()):
@@ -494,13 +487,13 @@ def merge_segments(flows, rgbs, masks):
 
 
 def flatten(arap_seg_paths, remove=True):
-    """para_gen.py:136-175 at file level: for every (frame line, [segment lines]) read the segments' flow / warped RGB /
-    warped mask files (the last three paths of a list line), merge them (merge_segments), write the frame's three
-    files, delete the segments' files.  Returns the frames' list lines."""
+    """para_gen.py:136-175 at file level: for every (frame SolveLine, [segment SolveLines]) read the segments' flow /
+    warped RGB / warped mask files, merge them (merge_segments), write the frame's three files, delete the segments'
+    files.  Returns the frames' lines."""
     for frame_line, seg_lines in arap_seg_paths:
         if len(seg_lines) == 0:
             raise AssertionError("Something wrong with seg_paths")
-        files = [ln.split(" ")[-3:] for ln in seg_lines]
+        files = [(ln.flow, ln.out_rgb, ln.out_mask) for ln in seg_lines]
         flows = [flo.flow_read(f) for f, _, _ in files]
         rgbs = [np.asarray(Image.open(r)) for _, r, _ in files]
         rgbs = [a[..., None] if a.ndim == 2 else a for a in rgbs]
@@ -510,10 +503,10 @@ def flatten(arap_seg_paths, remove=True):
             for trio in files:
                 for q in trio:
                     os.remove(q)
-        out_flow, out_rgb, out_mask = frame_line.split(" ")[-3:]
-        flo.flow_write(out_flow, flow)
-        Image.fromarray(rgb.astype(np.uint8).squeeze()).save(out_rgb)
-        Image.fromarray(mask.astype(np.uint8)).save(out_mask)     # a 1-bit mask file comes out 0 / 1 valued, as in the reference
+        flo.flow_write(frame_line.flow, flow)
+        Image.fromarray(rgb.astype(np.uint8).squeeze()).save(frame_line.out_rgb)
+        # (a 1-bit mask file comes out 0 / 1 valued, as in the reference)
+        Image.fromarray(mask.astype(np.uint8)).save(frame_line.out_mask)
     return [e[0] for e in arap_seg_paths]
 
 
@@ -532,20 +525,20 @@ def merge_backward(bwds, covers, objects):
     return bwd, occ_bwd
 
 
-def flatten_backward(frame_extra, seg_lines, seg_extras, remove=True):
+def flatten_backward(frame_line, seg_lines, remove=True):
     """merge_backward at file level, before flatten removes the segments' warped masks: reads every segment's backward
-    flow, warped mask (a line's last path) and frame-1 mask (second path: red channel 0 = object), writes the frame's
-    files named in `frame_extra` ({key: path}) and deletes the segments' backward files."""
-    covers = [np.asarray(Image.open(ln.split(" ")[5])) != 0 for ln in seg_lines]
-    objects = [load_mask_red(ln.split(" ")[1]) == 0 for ln in seg_lines]
-    bwds = [flo.flow_read(e["bwd"]) for e in seg_extras]
+    flow, warped mask and frame-1 mask (red channel 0 = object), writes the files named in the frame line's `extra` and
+    deletes the segments' backward files."""
+    covers = [np.asarray(Image.open(ln.out_mask)) != 0 for ln in seg_lines]
+    objects = [load_mask_red(ln.mask) == 0 for ln in seg_lines]
+    bwds = [flo.flow_read(ln.extra["bwd"]) for ln in seg_lines]
     bwd, occ_bwd = merge_backward(bwds, covers, objects)
-    if "bwd" in frame_extra:
-        flo.flow_write(frame_extra["bwd"], bwd)
-    if "occ_bwd" in frame_extra:
-        save_occ(occ_bwd, frame_extra["occ_bwd"])
+    if "bwd" in frame_line.extra:
+        flo.flow_write(frame_line.extra["bwd"], bwd)
+    if "occ_bwd" in frame_line.extra:
+        save_occ(occ_bwd, frame_line.extra["occ_bwd"])
     if remove:
-        for e in seg_extras:
-            for q in e.values():
+        for ln in seg_lines:
+            for q in ln.extra.values():
                 if osp.exists(q):
                     os.remove(q)

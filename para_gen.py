@@ -40,6 +40,7 @@ import subprocess
 import sys
 import threading
 import time
+from dataclasses import dataclass
 from multiprocessing import Pool
 
 import numpy as np
@@ -53,9 +54,8 @@ orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
-EXTRA_OF = dict(bwd_gen="bwd", occbwd_gen="occ_bwd", occ_gen="occ")   # path key -> list-line token
 LAYERS_OCC = "occl_gen"            # --multseg --occ_layers: the frame's forward occlusion, made by a `layers` line
-EXT_KEYS = list(EXTRA_OF) + [LAYERS_OCC]                              # every optional output of a frame
+EXT_KEYS = list(pipeline.EXTRA_OF) + [LAYERS_OCC]                     # every optional output of a frame
 CPP_BIN = osp.join(HERE, "arap_flow_amd", "bin", "arap_deform")
 
 
@@ -119,13 +119,28 @@ def cleanup(p):
 # ----------------------------------------------------------------------------------------------------------------
 # front end / back end of one frame pair: run in the --jobs pool
 # ----------------------------------------------------------------------------------------------------------------
+@dataclass
+class Frame:
+    """one frame pair on its way from prepare_pair through main to finish_frame"""
+    line: pipeline.SolveLine       # the pair's list line; its outputs are the frame's outputs
+    segs: list                     # --multseg: the per-segment lines that are solved in its place, else None
+    layers: dict                   # --occ_layers: the frame's layers line (pipeline.parse_layers), else None
+    bg: np.ndarray                 # the background fitted to the frame, or None
+    remove: bool                   # --multseg: delete the segments' files once they are merged
+    left: int = 0                  # main: solves of this frame not yet reported done
+
+    @property
+    def solves(self):
+        return [self.line] if self.segs is None else self.segs
+
+
 def prepare_pair(args):
     """para_gen.py:447-556 for one pair: everything up to its list-file line(s).  Returns None when the pair is
-    dropped (no mask, no valid constraint), else dict(arap_path, seg_paths or None, bg)."""
+    dropped (no mask, no valid constraint), else its Frame."""
     flags, p, bgpath = args
     p = dict(p)
     seq, stem = p.pop("_seq"), p.pop("_stem")
-    arap_path = pipeline.make_arap_path(p)
+    line = pipeline.make_arap_path(p)
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
     im1, mk1, im2, mk2 = preprocess(p, flags.size)
@@ -153,57 +168,33 @@ def prepare_pair(args):
     else:
         out1 = im1
     Image.fromarray(out1).save(p["rgb1_gen"])
-    seg_paths, seg_extras = None, None
+    segs = None
     if not flags.multseg:
         mask = np.zeros_like(mk1, dtype=np.uint8)
         mask[mk1 == 0] = pipeline.ARAP_BG                                      # :514-517
         Image.fromarray(mask).save(p["msk1_gen"])
     else:
-        seg_paths, seg_extras = [], []
+        segs = []
         for s, mask in pipeline.split_segments(mk1, valids):                   # :518-540
             p_ = pipeline.replace_ext(p, s, keep_orgs=["rgb1_gen", "cstr_tmp"])
             Image.fromarray(mask).save(p_["msk1_gen"])
-            seg_paths.append(pipeline.make_arap_path(p_))
-            seg_extras.append(_extra(p_))
+            segs.append(pipeline.make_arap_path(p_))
     layers = None
-    if seg_paths and LAYERS_OCC in p:       # the frame's layers line: segments in list order = ascending label, later on top
-        toks = [ln.split(" ") for ln in seg_paths]
-        layers = pipeline.layers_line(osp.abspath(p["rgb1_gen"]), [(t[1], t[3]) for t in toks], dict(occ=p[LAYERS_OCC]))
-    return dict(arap_path=arap_path, seg_paths=seg_paths, bg=bgim, extra=_extra(p), seg_extras=seg_extras,
-                layers=layers)
+    if segs and LAYERS_OCC in p:            # the frame's layers line: segments in list order = ascending label, later on top
+        layers = dict(rgb=line.rgb, layers=[(sg.mask, sg.flow) for sg in segs], out=dict(occ=p[LAYERS_OCC]))
+    return Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
 
 
-def _extra(p):
-    """the optional outputs of one solve, {token key: path}"""
-    return {t: p[k] for k, t in EXTRA_OF.items() if k in p}
-
-
-def _line(arap_path, extra):
-    return " ".join([arap_path] + pipeline.extra_tokens(extra))
-
-
-def _done_token(line):
-    """the path a worker reports a line done by: a solve's flow, a layers line's first output"""
-    tok = line.split()
-    if tok[0] == pipeline.LAYERS_WORD:
-        return pipeline.layers_done_token(pipeline.parse_layers(tok))
-    return tok[3]
-
-
-def finish_frame(args):
-    """para_gen.py:202-212 for one frame whose solve(s) are done: flatten the segments, composite the background"""
-    arap_path, seg_paths, bg, extra, seg_extras = args[:5]
-    remove = args[5] if len(args) > 5 else True
-    if seg_paths is not None:
-        if extra:                                           # (before flatten removes the segments' warped masks)
-            pipeline.flatten_backward(extra, seg_paths, seg_extras, remove=remove)
-        pipeline.flatten([(arap_path, seg_paths)], remove=remove)
-    if bg is not None:
-        pt, mk = arap_path.split(" ")[-2:]
-        im = np.array(Image.open(pt).convert("RGB"))
-        m = np.array(Image.open(mk))
-        Image.fromarray(pipeline.add_bg(im, m, bg)).save(pt)
-    return arap_path
+def finish_frame(rec):
+    """para_gen.py:202-212 for one Frame whose solve(s) are done: flatten the segments, composite the background"""
+    if rec.segs is not None:
+        if rec.line.extra:                                  # (before flatten removes the segments' warped masks)
+            pipeline.flatten_backward(rec.line, rec.segs, remove=rec.remove)
+        pipeline.flatten([(rec.line, rec.segs)], remove=rec.remove)
+    if rec.bg is not None:
+        im = np.array(Image.open(rec.line.out_rgb).convert("RGB"))
+        m = np.array(Image.open(rec.line.out_mask))
+        Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(rec.line.out_rgb)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -365,7 +356,7 @@ class GpuWorkers:
                 return
             self.batches.append(len(batch))
             for ln in batch:
-                self.on_done(_done_token(ln))
+                self.on_done(pipeline.done_token(pipeline.parse_line(ln)))
             if last:
                 return
 
@@ -451,10 +442,9 @@ def main(flags):
     os.makedirs(output_root, exist_ok=True)
     lmdb_paths, ext_paths = [], []
     for p in all_paths:
-        q = {k: v for k, v in p.items() if not k.startswith("_")}
-        ap = pipeline.make_arap_path(q).split(" ")
-        lmdb_paths.append(" ".join([ap[0], ap[4], ap[3]]))
-        ext_paths.append(" ".join([ap[0], ap[4], ap[3]] + [q[k] for k in EXT_KEYS if k in q]))
+        ln = pipeline.make_arap_path(p)
+        lmdb_paths.append([ln.rgb, ln.out_rgb, ln.flow])
+        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p])
 
     # backgrounds: drawn without replacement until the list is used up, then refilled (para_gen.py:484-499)
     tmp_paths, picks = [], []
@@ -470,28 +460,29 @@ def main(flags):
 
     serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == CPP_BIN)
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
-    frames = {}                                        # flow path of a solve -> its frame record
+    frames = {}                                        # done token of a line a worker holds -> its Frame
     posts, lock = [], threading.Lock()
     counts = dict(solves_done=0, frames_done=0, layers_done=0)
-    remove = not getattr(flags, "keep_segments", False)
+
+    def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
+        frames[pipeline.done_token(item)] = rec
+        put(pipeline.format_line(item))
 
     def on_done(path):                                 # a worker thread: one solve (or one layers line) finished
         with lock:
             rec = frames.pop(path)
-            if rec["left"] == 0:                       # its layers line: the segment files may go now
+            if rec.left == 0:                          # its layers line: the segment files may go now
                 counts["layers_done"] += 1
             else:
                 counts["solves_done"] += 1
-                rec["left"] -= 1
-                if rec["left"] > 0:
+                rec.left -= 1
+                if rec.left > 0:
                     return
-                if rec["layers"] is not None:          # last segment done: the frame's layers line, then finish_frame
-                    frames[_done_token(rec["layers"])] = rec
-                    workers.put_owed(rec["layers"])
+                if rec.layers is not None:             # last segment done: the frame's layers line, then finish_frame
+                    hand_out(rec, rec.layers, workers.put_owed)
                     return
             counts["frames_done"] += 1
-            posts.append(pool.apply_async(finish_frame, ((rec["arap_path"], rec["seg_paths"], rec["bg"], rec["extra"],
-                                                          rec["seg_extras"], remove),)))
+            posts.append(pool.apply_async(finish_frame, (rec,)))
 
     # --dm_bin builtin: the matcher and the solver must not share a GPU at the same time (the solver's resident kernel
     # needs the whole chip: arap_resident.h), so the run has two phases -- every pair is prepared and matched first
@@ -509,25 +500,18 @@ def main(flags):
     n_solves = n_frames = 0
     try:
         jobs = ((flags, p, bg) for p, bg in zip(all_paths, picks))
-        for i, res in enumerate(prepared if prepared is not None else pool.imap(prepare_pair, jobs, chunksize=1)):
+        for i, rec in enumerate(prepared if prepared is not None else pool.imap(prepare_pair, jobs, chunksize=1)):
             print("%.3f%%" % (float(i) * 100 / len(all_paths)))
             workers.check()
-            if res is None:
+            if rec is None or not rec.solves:
                 continue
-            lines = [res["arap_path"]] if res["seg_paths"] is None else res["seg_paths"]
-            extras = [res["extra"]] if res["seg_paths"] is None else res["seg_extras"]
-            if not lines:
-                continue
-            rec = dict(arap_path=res["arap_path"], seg_paths=res["seg_paths"], bg=res["bg"], left=len(lines),
-                       extra=res["extra"], seg_extras=res["seg_extras"], layers=res.get("layers"))
-            if rec["layers"] is not None:
+            rec.left = len(rec.solves)
+            if rec.layers is not None:
                 workers.owe()
             with lock:
-                for ln in lines:
-                    frames[ln.split(" ")[3]] = rec
-            for ln, ex in zip(lines, extras):
-                workers.put(_line(ln, ex))
-            n_solves += len(lines)
+                for ln in rec.solves:
+                    hand_out(rec, ln, workers.put)
+            n_solves += len(rec.solves)
             n_frames += 1
         workers.close()
         workers.join()
@@ -538,10 +522,10 @@ def main(flags):
         for p in workers.procs:
             if p.poll() is None:
                 p.kill()
-    out_paths = [ln for ln in lmdb_paths if all(osp.exists(q) for q in ln.split(" "))]   # :588-603
+    out_paths = [" ".join(ln) for ln in lmdb_paths if all(osp.exists(q) for q in ln)]    # :588-603
     open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
     if getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False):     # all_files.list stays as it is; the extra outputs get their own list
-        ext = [ln for ln in ext_paths if all(osp.exists(q) for q in ln.split(" "))]
+        ext = [" ".join(ln) for ln in ext_paths if all(osp.exists(q) for q in ln)]
         open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],

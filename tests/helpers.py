@@ -22,6 +22,12 @@ def random_problem(W, H, seed, generic_urshape=True, mask_frac=0.25, ncons=12):
     return dict(O=f32(O), A=f32(A), U=f32(U), C=f32(C), M=f32(M), wf=np.float32(10.0), wr=np.float32(0.1))
 
 
+def para_gen_flags(extra):
+    """para_gen.py's parsed flags for a run over precomputed matches, plus the arguments in `extra`"""
+    import para_gen
+    return para_gen.parse(["--input", "in", "--output", "out", "--matches", "m"] + extra)
+
+
 def rel_l2(a, b):
     a = np.asarray(a, np.float64).ravel()
     b = np.asarray(b, np.float64).ravel()

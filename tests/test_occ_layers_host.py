@@ -11,6 +11,7 @@ import pytest
 import occ_layers_ref as lref
 import occ_ref
 from arap_flow_amd import pipeline
+from helpers import para_gen_flags as _parse
 
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 KEYS = ("warped_rgb", "warped_mask", "backward_flow", "occlusion_bwd", "occlusion")
@@ -77,36 +78,80 @@ def test_layers_line_round_trip_and_old_lines_unchanged(tmp_path):
     six = "r.png m.png c.txt f.flo w.png wm.png"
     lay = "layers /a/r.png 2 /a/m1.png /a/f1.flo /a/m2.png /a/f2.flo bwd=/o/b.flo occ=/o/o.png"
     (tmp_path / "l.txt").write_text("%s\n%s occ=/x.png\n%s\n%s tail\n" % (six, six, lay, six))
-    assert pipeline.read_list(str(tmp_path / "l.txt")) == [tuple(six.split())] * 3
-    assert [e for _, e in pipeline.read_list_ex(str(tmp_path / "l.txt"))] == [{}, dict(occ="/x.png"), {}]
     items = pipeline.read_list_items(str(tmp_path / "l.txt"))
-    assert [i[0] for i in items] == ["solve", "solve", "layers", "solve"]
-    spec = items[2][1]
+    assert [isinstance(i, pipeline.SolveLine) for i in items] == [True, True, False, True]    # a layers line is no solve
+    solves = items[:2] + items[3:]
+    assert [ln[:6] for ln in solves] == [tuple(six.split())] * 3
+    assert [ln.extra for ln in solves] == [{}, dict(occ="/x.png"), {}]
+    spec = items[2]
     assert spec["rgb"] == "/a/r.png" and spec["layers"] == [("/a/m1.png", "/a/f1.flo"), ("/a/m2.png", "/a/f2.flo")]
     assert spec["out"] == dict(bwd="/o/b.flo", occ="/o/o.png")
-    assert pipeline.layers_done_token(spec) == "/o/b.flo"        # the first output token on the line
+    assert pipeline.done_token(spec) == "/o/b.flo"               # the first output token on the line
     again = pipeline.parse_layers(pipeline.layers_line(spec["rgb"], spec["layers"], spec["out"]).split())
     assert again["layers"] == spec["layers"] and again["out"] == spec["out"]
-    assert pipeline.layers_done_token(again) == "/o/o.png"       # layers_line writes occ first
-    for bad in ("layers r.png 2 m1 f1 m2 f2",                     # no output
-                "layers r.png 2 m1 f1 m2 occ=o.png",             # a layer short
-                "layers r.png 0 occ=o.png", "layers r.png x m f occ=o.png", "layers r.png 1 m f junk",
-                "layers r.png 1 m f occ="):
+    assert pipeline.done_token(again) == "/o/o.png"              # layers_line writes occ first
+    for bad in BAD_LAYERS:
         with pytest.raises(ValueError):
             pipeline.parse_layers(bad.split())
 
 
-def test_cpp_twin_refuses_a_bad_layers_line(tmp_path):
+BAD_LAYERS = ("layers r.png 2 m1 f1 m2 f2",                       # no output
+              "layers r.png 2 m1 f1 m2 occ=o.png",               # a layer short
+              "layers r.png 0 occ=o.png", "layers r.png x m f occ=o.png", "layers r.png 1 m f junk",
+              "layers r.png 1 m f occ=")
+
+SIX = "/a/r.png /a/m.png /a/c.txt /o/f.flo /o/w.png /o/wm.png"
+LAY = "layers /a/r.png 2 /a/m1.png /o/f1.flo /a/m2.png /o/f2.flo"
+# (line, what format_line makes of it, the path a worker reports it done by)
+ALL3 = SIX + " bwd=/o/b.flo occ=/o/o.png occ_bwd=/o/ob.png"
+LINES = [(SIX, SIX, "/o/f.flo"),
+         (ALL3, ALL3, "/o/f.flo"),
+         (SIX + " occ=/o/o.png tail", SIX + " occ=/o/o.png", "/o/f.flo"),             # an unknown token is dropped
+         (LAY + " occ=/o/o.png bwd=/o/b.flo", LAY + " occ=/o/o.png bwd=/o/b.flo", "/o/o.png"),
+         # outputs in another order than layers_line's: the worker reports the first ON THE LINE, the text is re-ordered
+         (LAY + " mask2=/o/m2.png bwd=/o/b.flo occ=/o/o.png", LAY + " occ=/o/o.png bwd=/o/b.flo mask2=/o/m2.png",
+          "/o/m2.png")]
+
+
+def test_list_line_round_trip_and_done_token():
+    """parse_line / format_line / done_token over both line forms: a line in canonical token order comes back as it
+    was; the formatted text of any line is a fixed point and parses to the same item"""
+    for text, canonical, done in LINES:
+        item = pipeline.parse_line(text)
+        assert pipeline.format_line(item) == canonical
+        assert pipeline.done_token(item) == done
+        assert pipeline.parse_line(text.split()) == item                       # tokens or text
+        again = pipeline.parse_line(canonical)
+        assert again == item and pipeline.format_line(again) == canonical
+    assert pipeline.parse_line(LINES[2][0]).extra == dict(occ="/o/o.png")
+    assert pipeline.done_token(pipeline.parse_line(LINES[4][1])) == "/o/o.png"  # ... of the re-ordered text: occ first
+    for bad in BAD_LAYERS:
+        with pytest.raises(ValueError):
+            pipeline.parse_line(bad)
+    with pytest.raises(ValueError, match="list line needs 6 paths"):
+        pipeline.parse_line("only three paths")
+
+
+def _cpp_list(tmp_path, text):
     import subprocess
     from arap_flow_amd import build
-    (tmp_path / "l.txt").write_text("layers r.png 2 m1 f1 m2 f2\n")
-    r = subprocess.run([build.build_host()[0], str(tmp_path / "l.txt")], capture_output=True, text=True, timeout=120)
+    (tmp_path / "l.txt").write_text(text)
+    return subprocess.run([build.build_host()[0], str(tmp_path / "l.txt")], capture_output=True, text=True, timeout=120)
+
+
+def test_cpp_twin_refuses_a_bad_layers_line(tmp_path):
+    r = _cpp_list(tmp_path, "layers r.png 2 m1 f1 m2 f2\n")
     assert r.returncode == 1 and "Invalid layers line" in r.stdout
 
 
-def _parse(extra):
-    import para_gen
-    return para_gen.parse(["--input", "in", "--output", "out", "--matches", "m"] + extra)
+def test_cpp_twin_reads_the_same_lines(tmp_path):
+    """the C++ driver's list reader accepts what format_line writes (it then stops at the first input file, which does
+    not exist) and refuses every layers line that parse_line refuses"""
+    good = _cpp_list(tmp_path, "".join(c + "\n" for _, c, _ in LINES))
+    assert good.returncode != 0 and "Invalid" not in good.stdout
+    for bad in BAD_LAYERS:
+        r = _cpp_list(tmp_path, bad + "\n")
+        assert r.returncode == 1 and "Invalid layers line: " + bad in r.stdout
 
 
 def test_para_gen_occ_layers_flag(capsys):

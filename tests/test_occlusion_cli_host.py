@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from arap_flow_amd import pipeline
+from helpers import para_gen_flags as _parse
 
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 
@@ -16,10 +17,9 @@ def test_extra_tokens_parse_and_old_lines_keep_their_meaning(tmp_path):
     six = "r.png m.png c.txt f.flo w.png wm.png"
     (tmp_path / "l.txt").write_text("%s\n%s bwd=/a/b.flo occ=/a/o.png junk occ_bwd=/a/ob.png\n%s extra words\n" %
                                     (six, six, six))
-    assert pipeline.read_list(str(tmp_path / "l.txt")) == [tuple(six.split())] * 3
-    ex = pipeline.read_list_ex(str(tmp_path / "l.txt"))
-    assert [e for _, e in ex] == [{}, dict(bwd="/a/b.flo", occ="/a/o.png", occ_bwd="/a/ob.png"), {}]
-    assert all(ln == tuple(six.split()) for ln, _ in ex)
+    ex = pipeline.read_list_items(str(tmp_path / "l.txt"))
+    assert [ln[:6] for ln in ex] == [tuple(six.split())] * 3
+    assert [ln.extra for ln in ex] == [{}, dict(bwd="/a/b.flo", occ="/a/o.png", occ_bwd="/a/ob.png"), {}]
     assert pipeline.parse_extra(["occ=", "bwd", "x=y"]) == {}
     e = dict(occ="o.png", bwd="b.flo")
     assert pipeline.parse_extra(pipeline.extra_tokens(e)) == e
@@ -38,11 +38,6 @@ def test_warp_image_tokens_both_twins(tmp_path, cmd):
     good = subprocess.run(prog + five + ["bwd=" + str(tmp_path / "b.flo"), "occ=" + str(tmp_path / "o.png")],
                           capture_output=True, text=True, timeout=120)
     assert good.returncode != 0 and "Invalid Input!" not in good.stdout
-
-
-def _parse(extra):
-    import para_gen
-    return para_gen.parse(["--input", "in", "--output", "out", "--matches", "m"] + extra)
 
 
 def test_para_gen_refusals():

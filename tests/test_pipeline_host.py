@@ -52,14 +52,16 @@ def test_read_list_and_make_path(tmp_path):
     from arap_flow_amd import pipeline
     p = dict(rgb1_gen="a/r.png", msk1_gen="a/m.png", cstr_tmp="a/c.txt", flow_gen="a/f.flo", rgb2_gen="a/w.png",
              msk2_gen="a/wm.png")
-    line = pipeline.make_arap_path(p)
+    rec = pipeline.make_arap_path(p)
+    line = pipeline.format_line(rec)
     assert len(line.split(" ")) == 6 and all(osp.isabs(q) for q in line.split(" "))
+    assert rec[:6] == tuple(osp.abspath(p[k]) for k in p) and rec.extra == {}
     lf = tmp_path / "l.txt"
     lf.write_text(line + "\n\n" + line + "\n")
-    assert len(pipeline.read_list(str(lf))) == 2
+    assert pipeline.read_list_items(str(lf)) == [rec, rec]
     lf.write_text("only three paths here\n")
     with pytest.raises(ValueError):
-        pipeline.read_list(str(lf))
+        pipeline.read_list_items(str(lf))
     q = pipeline.replace_ext(p, 2, keep_orgs=["rgb1_gen", "cstr_tmp"])
     assert q["rgb1_gen"] == "a/r.png" and q["msk1_gen"] == "a/m_seg2.png" and q["flow_gen"] == "a/f_seg2.flo"
 
@@ -88,7 +90,64 @@ def test_split_segments_and_flatten(tmp_path):
     assert fl[10, 15, 0] == 2 and rgb[10, 15, 0] == 100                  # overlap: the later segment wins
     assert fl[5, 5, 0] == 1 and rgb[5, 5, 0] == 50 and fl[0, 0, 0] == 0
     assert set(np.unique(wm)) == {0, 1}                                  # 0/1 valued, as the reference writes it
-    assert not osp.exists(seg_lines[0].split(" ")[3])                    # per-segment files are removed
+    assert not osp.exists(seg_lines[0].flow)                             # per-segment files are removed
+
+
+def test_deform_list_saves_every_result_with_its_own_line(monkeypatch):
+    """deform_list's two alternating lanes over 5 frames of one size, two to a batch, with a stand-in solver: the result
+    read from slot b of a lane is saved under the line (and so the optional outputs) that was set into that slot, and
+    every batch asks the solver for what its own lines want"""
+    from arap_flow_amd import opt, pipeline
+    six = "r%d.png m%d.png c%d.txt f%d.flo w%d.png wm%d.png"
+    extras = [{}, dict(bwd="b1.flo"), dict(occ="o2.png"), dict(occ_bwd="ob3.png"), dict(bwd="b4.flo", occ="o4.png")]
+    lines = [pipeline.parse_line(" ".join([six.replace("%d", str(k))] + pipeline.extra_tokens(e)))
+             for k, e in enumerate(extras)]
+    assert [ln.extra for ln in lines] == extras
+    calls, saved = [], []
+
+    class Solver:
+        def __init__(self, state, W, H, batch):
+            assert (W, H, batch) == (6, 4, 2)
+            self.slots, self.solved = {}, None
+
+        def set_frame(self, b, mask, cons, rgb=None, border_pins=False):
+            self.slots[b] = cons                         # (the stand-in loader's "constraints": the line's number)
+
+        def launches_for(self, n):
+            return 1
+
+        def set_outputs(self, backward, occlusion):
+            calls.append(("set_outputs", backward, occlusion))
+
+        def solve_async(self, n, *a, **k):
+            calls.append(("solve_async", [self.slots[b] for b in range(n)]))
+            self.solved = [self.slots[b] for b in range(n)]
+
+        def wait(self):
+            calls.append(("wait", self.solved))
+
+        def host_results(self, b):
+            return dict(flow=np.array([self.solved[b]]), backward_flow=None)
+
+        def close(self):
+            calls.append(("close",))
+
+    class State:
+        def use_own_stream(self):
+            pass
+
+    monkeypatch.setattr(opt, "FrameSolver", Solver)
+    monkeypatch.setattr(pipeline, "_load_line",
+                        lambda ln: (np.zeros((4, 6, 3), np.uint8), np.zeros((4, 6), np.uint8), lines.index(ln)))
+    monkeypatch.setattr(pipeline, "_save_result", lambda ln, r: saved.append((int(r["flow"][0]), ln)))
+    pipeline.deform_list(State(), lines, max_batch=2, verbose=False)
+    assert sorted(k for k, _ in saved) == [0, 1, 2, 3, 4]
+    for k, ln in saved:
+        assert ln is lines[k] and ln.extra == extras[k]
+    assert [c for c in calls if c[0] != "wait"] == [
+        ("set_outputs", True, False), ("solve_async", [0, 1]), ("set_outputs", True, True), ("solve_async", [2, 3]),
+        ("set_outputs", True, True), ("solve_async", [4]), ("close",), ("close",)]
+    assert [c[1] for c in calls if c[0] == "wait"] == [[0, 1], [2, 3], [4]]
 
 
 def test_add_bg_and_fit_bg():
