@@ -69,11 +69,16 @@ SYMBOLS = [
     ("ArapFlow_SolverHostExtraResults", _I, [_VP, _U, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP)]),
     ("ArapFlow_WarpExScratchBytes", C.c_uint64, [_U, _U]),
     ("ArapFlow_WarpEx", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("ArapFlow_SolverSetSnapshots", _I, [_VP, C.POINTER(C.c_uint), _U]),
+    ("ArapFlow_SolverGetSnapshot", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP]),
+    ("ArapFlow_SolverHostSnapshot", _I, [_VP, _U, _U, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP)]),
+    ("ArapFlow_WarpStep", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ArapFlow_WarpLayersScratchBytes", C.c_uint64, [_U, _U, _U]),
     ("ArapFlow_WarpLayers", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 ]
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h
+MAX_SNAPSHOTS = 8                       # ARAPFLOW_MAX_SNAPSHOTS
 
 _LIB = None
 

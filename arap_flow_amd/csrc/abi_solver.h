@@ -10,6 +10,10 @@ struct FrameExt {              // per-slot optional warp outputs + occlusion scr
     unsigned *cell, *rank;
     int4* bin;
 };
+struct MidDev {                // per snapshot and slot (ArapFlow_SolverSetSnapshots): the state and its four outputs
+    float2 *state, *flow, *step;
+    uint8_t *rgb, *mask;
+};
 }  // namespace arap
 
 // Every entry point that touches a slot's images or results first waits for the solve (or warp) in flight, if any:
@@ -55,7 +59,56 @@ struct ArapFlow_Solver {
     size_t ext_cell_slot = 0;
     char* pin_ext = nullptr;         // [batch] x {bwd float2[N], occ_bwd u8[N], occ u8[N]}   (allocated on first download)
     size_t pin_ext_slot = 0;
+    // in-between frames (ArapFlow_SolverSetSnapshots, DESIGN.md "In-between frames"); nothing is allocated while off
+    unsigned snap_n = 0, snap_steps[ARAPFLOW_MAX_SNAPSHOTS] = {};   // the set for the next solves
+    unsigned a_snap_n = 0, a_snap_steps[ARAPFLOW_MAX_SNAPSHOTS] = {};   // ... of the solve call pending or last done
+    unsigned taken_n = 0;            // states the last solve call copied (they stay valid until the next one)
+    unsigned warp_snap_n = 0;        // snapshots the last warp wrote outputs for
+    unsigned dl_snap_n = 0;          // ... the last solve call downloaded
+    void* mid = nullptr;             // device: [mid_cap][batch] x MidDev buffers, then [mid_cap][batch] WarpJobs
+    unsigned mid_cap = 0;            // snapshots `mid`, `pin_mid_jobs` (and `pin_mid`, once there) are sized for
+    std::vector<MidDev> hmid;        // [k * batch + slot]
+    WarpJob* dmid_jobs = nullptr;
+    WarpJob* pin_mid_jobs = nullptr;
+    char* pin_mid = nullptr;         // [mid_cap][batch] x {flow float2[N], step float2[N], rgb u8[3N], mask u8[N]}
+    size_t pin_mid_slot = 0;
 };
+
+// pinned staging of the snapshot downloads (as solver_pin_out: when first needed)
+static void solver_pin_mid(ArapFlow_Solver* s)
+{
+    if (s->pin_mid) return;
+    s->pin_mid_slot = align_up(20 * (size_t)s->N, 256);
+    HC(hipHostMalloc((void**)&s->pin_mid, s->pin_mid_slot * s->mid_cap * s->batch, hipHostMallocDefault));
+}
+// device buffers of `n` snapshots: 8 B per vertex, snapshot and slot for the state, 20 B for the four outputs
+static void solver_mid_alloc(ArapFlow_Solver* s, unsigned n)
+{
+    if (n <= s->mid_cap) return;
+    HC(hipSetDevice(s->st->device));
+    if (s->mid) HC(hipFree(s->mid));
+    if (s->pin_mid_jobs) HC(hipHostFree(s->pin_mid_jobs));
+    if (s->pin_mid) HC(hipHostFree(s->pin_mid));
+    s->pin_mid = nullptr;
+    const size_t N = s->N, B = s->batch;
+    const size_t sz2 = align_up(8 * N, 256), sz3 = align_up(3 * N, 256), szb = align_up(N, 256);
+    const size_t per = 3 * sz2 + sz3 + szb, jobs = align_up(sizeof(WarpJob) * n * B, 256);
+    HC(hipMalloc(&s->mid, per * n * B + jobs));
+    HC(hipMemsetAsync(s->mid, 0, per * n * B + jobs, s->st->stream));
+    char* c = (char*)s->mid;
+    auto take = [&](size_t b) { char* r = c; c += b; return r; };
+    s->hmid.resize(n * B);
+    for (MidDev& m : s->hmid) {
+        m.state = (float2*)take(sz2); m.flow = (float2*)take(sz2); m.step = (float2*)take(sz2);
+        m.rgb = (uint8_t*)take(sz3); m.mask = (uint8_t*)take(szb);
+    }
+    s->dmid_jobs = (WarpJob*)c;
+    HC(hipHostMalloc((void**)&s->pin_mid_jobs, sizeof(WarpJob) * n * B, hipHostMallocDefault));
+    HC(hipStreamSynchronize(s->st->stream));
+    s->mid_cap = n;
+    s->taken_n = s->warp_snap_n = s->dl_snap_n = 0;
+    if (s->st->own_stream) solver_pin_mid(s);   // (as pin_out: downloads will be asked for)
+}
 
 static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
 {
@@ -79,6 +132,29 @@ static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
     HC(hipMemcpyAsync(s->djobs, jobs, sizeof(WarpJob) * nframes, hipMemcpyHostToDevice, st->stream));
     enqueue_warp(st->stream, s->djobs, nframes, s->W, s->H, s->outputs, s->ext_cells, s->ext_cell_slot * nframes);
     s->warp_outputs = s->outputs;
+    // the in-between frames of the last solve: one warp pass per snapshot over the slots, on the field S_{i_k}, with the
+    // step towards the next state; the slot's key image serves every pass (k_warp_resolve left it cleared)
+    const unsigned n = s->taken_n;
+    s->warp_snap_n = n;
+    if (n == 0) return;
+    WarpJob* mj = s->pin_mid_jobs;
+    for (unsigned k = 0; k < n; ++k)
+        for (unsigned b = 0; b < nframes; ++b) {
+            const FrameDev& f = s->hfr[b];
+            const MidDev& m = s->hmid[(size_t)k * s->batch + b];
+            WarpJob j{};
+            j.field = m.state;
+            j.rgb = s->has_rgb[b] ? f.rgb : nullptr;
+            j.mask = f.mask; j.flow_out = m.flow; j.key = f.key;
+            j.out_rgb = s->has_rgb[b] ? m.rgb : nullptr;
+            j.out_mask = m.mask;
+            j.field_b = k + 1 < n ? s->hmid[(size_t)(k + 1) * s->batch + b].state : f.O;
+            j.step = m.step;
+            mj[(size_t)k * nframes + b] = j;
+        }
+    HC(hipMemcpyAsync(s->dmid_jobs, mj, sizeof(WarpJob) * n * nframes, hipMemcpyHostToDevice, st->stream));
+    for (unsigned k = 0; k < n; ++k)
+        enqueue_warp(st->stream, s->dmid_jobs + (size_t)k * nframes, nframes, s->W, s->H, 0, nullptr, 0, true);
 }
 
 // pinned staging of the downloads, allocated when first needed: at creation / SetOutputs in the asynchronous use
@@ -121,7 +197,15 @@ static void solver_enqueue(ArapFlow_Solver* s)
         plan_init(p);
         if (!plan_steps_batched(p))
             while (plan_step(p) != 0) {}
+        // a snapshot of ramp step i + 1: Offset is current here on every path (the resident launch and k_gn_update both
+        // apply the step to Offset itself), so the state is a copy between two ramp steps' launches
+        for (unsigned k = 0; k < s->a_snap_n; ++k)
+            if (s->a_snap_steps[k] == i + 1)
+                for (unsigned b = 0; b < nframes; ++b)
+                    HC(hipMemcpyAsync(s->hmid[(size_t)k * s->batch + b].state, s->hfr[b].O, sizeof(float2) * s->N,
+                                      hipMemcpyDeviceToDevice, st->stream));
     }
+    s->taken_n = s->a_snap_n;
     if (s->a_warp) solver_enqueue_warp(s, nframes);
     if (p->res_capable) {
         *s->pin_err = 0u;
@@ -152,6 +236,20 @@ static void solver_enqueue(ArapFlow_Solver* s)
                 if (s->dl_outputs & ARAPFLOW_OUT_OCCLUSION)
                     HC(hipMemcpyAsync(o + 9 * N, e.occ, N, hipMemcpyDeviceToHost, s->copy));
             }
+        }
+        s->dl_snap_n = s->a_warp ? s->taken_n : 0;
+        if (s->dl_snap_n) {
+            solver_pin_mid(s);
+            for (unsigned k = 0; k < s->dl_snap_n; ++k)
+                for (unsigned b = 0; b < nframes; ++b) {
+                    const size_t kb = (size_t)k * s->batch + b;
+                    const MidDev& m = s->hmid[kb];
+                    char* o = s->pin_mid + s->pin_mid_slot * kb;
+                    HC(hipMemcpyAsync(o, m.flow, 8 * N, hipMemcpyDeviceToHost, s->copy));
+                    HC(hipMemcpyAsync(o + 8 * N, m.step, 8 * N, hipMemcpyDeviceToHost, s->copy));
+                    if (s->has_rgb[b]) HC(hipMemcpyAsync(o + 16 * N, m.rgb, 3 * N, hipMemcpyDeviceToHost, s->copy));
+                    HC(hipMemcpyAsync(o + 19 * N, m.mask, N, hipMemcpyDeviceToHost, s->copy));
+                }
         }
         HC(hipEventRecord(s->ev_dl, s->copy));
     }
@@ -241,6 +339,9 @@ void ArapFlow_SolverFree(ArapFlow_Solver* s)
     if (s->pin_err) (void)hipHostFree(s->pin_err);
     if (s->pin_ext) (void)hipHostFree(s->pin_ext);
     if (s->ext) (void)hipFree(s->ext);
+    if (s->mid) (void)hipFree(s->mid);
+    if (s->pin_mid_jobs) (void)hipHostFree(s->pin_mid_jobs);
+    if (s->pin_mid) (void)hipHostFree(s->pin_mid);
     (void)hipFree(s->block);
     delete s;
 }
@@ -310,9 +411,13 @@ int ArapFlow_SolverSolveAsync(ArapFlow_Solver* s, unsigned nframes, unsigned num
                               unsigned lIterations, int warp, int download)
 {
     if (!s || nframes == 0 || nframes > (unsigned)s->batch || numIter == 0) return -1;
+    if (s->snap_n && s->snap_steps[s->snap_n - 1] > numIter) return -1;     // (increasing: the last is the largest)
     if (ArapFlow_SolverWait(s) != 0) return -1;
     Opt_State* st = s->st;
     HC(hipSetDevice(st->device));
+    s->a_snap_n = s->snap_n;
+    memcpy(s->a_snap_steps, s->snap_steps, sizeof(s->snap_steps));
+    solver_mid_alloc(s, s->snap_n);                           // (the first solve that needs it; nothing with none)
     const bool paused = st->res_cooldown > 0;                 // this call runs on the two-kernel path: counts as one
     s->a_n = nframes; s->a_numIter = numIter; s->a_nIt = nIterations; s->a_lIt = lIterations;
     s->a_warp = warp; s->a_download = download;
@@ -403,6 +508,50 @@ int ArapFlow_SolverSetOutputs(ArapFlow_Solver* s, int which)
         if (s->st->own_stream) solver_pin_ext(s);   // (as pin_out: downloads will be asked for)
     }
     s->outputs = which;
+    return 0;
+}
+
+int ArapFlow_SolverSetSnapshots(ArapFlow_Solver* s, const unsigned* steps, unsigned n)
+{
+    if (!s || n > ARAPFLOW_MAX_SNAPSHOTS || (n && !steps)) return -1;
+    for (unsigned k = 0; k < n; ++k)
+        if (steps[k] < 1 || (k && steps[k] <= steps[k - 1])) return -1;
+    if (const int rc = ArapFlow_SolverWait(s)) return rc;
+    s->snap_n = n;
+    for (unsigned k = 0; k < n; ++k) s->snap_steps[k] = steps[k];
+    return 0;
+}
+
+int ArapFlow_SolverGetSnapshot(ArapFlow_Solver* s, unsigned slot, unsigned k, float* flow, uint8_t* rgb, uint8_t* mask,
+                               float* step)
+{
+    if (!s || slot >= (unsigned)s->batch) return -1;
+    if (ArapFlow_SolverWait(s) != 0) return -1;
+    if (k >= s->warp_snap_n || (rgb && !s->has_rgb[slot])) return -1;
+    HC(hipStreamSynchronize(s->st->stream));
+    const MidDev& m = s->hmid[(size_t)k * s->batch + slot];
+    const size_t N = s->N;
+    hipStream_t cs = s->copy;
+    if (flow) HC(hipMemcpyAsync(flow, m.flow, 8 * N, hipMemcpyDeviceToHost, cs));
+    if (rgb) HC(hipMemcpyAsync(rgb, m.rgb, 3 * N, hipMemcpyDeviceToHost, cs));
+    if (mask) HC(hipMemcpyAsync(mask, m.mask, N, hipMemcpyDeviceToHost, cs));
+    if (step) HC(hipMemcpyAsync(step, m.step, 8 * N, hipMemcpyDeviceToHost, cs));
+    HC(hipStreamSynchronize(cs));
+    return 0;
+}
+
+int ArapFlow_SolverHostSnapshot(ArapFlow_Solver* s, unsigned slot, unsigned k, const float** flow, const uint8_t** rgb,
+                                const uint8_t** mask, const float** step)
+{
+    if (!s || slot >= (unsigned)s->batch || !s->a_download || slot >= s->a_n) return -1;
+    if (ArapFlow_SolverWait(s) != 0) return -1;
+    if (k >= s->dl_snap_n || !s->pin_mid) return -1;
+    const size_t N = s->N;
+    const char* o = s->pin_mid + s->pin_mid_slot * ((size_t)k * s->batch + slot);
+    if (flow) *flow = (const float*)o;
+    if (step) *step = (const float*)(o + 8 * N);
+    if (rgb) *rgb = s->has_rgb[slot] ? (const uint8_t*)(o + 16 * N) : nullptr;
+    if (mask) *mask = (const uint8_t*)(o + 19 * N);
     return 0;
 }
 

@@ -47,13 +47,15 @@ static WarpJob* warp_job_scratch(WarpJob& j, const WarpScratch& L, void* scratch
     return (WarpJob*)(c + L.job);
 }
 
-// rasterise `njobs` jobs at `dj`, write the optional outputs (ARAPFLOW_OUT_* bits), resolve
+// rasterise `njobs` jobs at `dj`, write the optional outputs (ARAPFLOW_OUT_* bits) and, for jobs with a second field
+// (`step`: arap_mid.h), the flow towards it, resolve
 static void enqueue_warp(hipStream_t stream, const WarpJob* dj, unsigned njobs, int W, int H, int outputs, void* cells,
-                         size_t cell_bytes)
+                         size_t cell_bytes, bool step = false)
 {
     const int N = W * H;
     hipLaunchKernelGGL(k_warp_raster, dim3((W + 63) / 64, (H + 3) / 4, njobs), dim3(64, 4), 0, stream, dj, W, H);
     if (outputs) enqueue_warp_outputs(stream, dj, njobs, W, H, outputs, cells, cell_bytes);
+    if (step) hipLaunchKernelGGL(k_warp_step, dim3((N + 255) / 256, 1, njobs), dim3(256), 0, stream, dj, W, N);
     hipLaunchKernelGGL(k_warp_resolve, dim3((N + 255) / 256, 1, njobs), dim3(256), 0, stream, dj, N);
 }
 
@@ -95,6 +97,31 @@ int ArapFlow_WarpEx(Opt_State* st, unsigned W, unsigned H, const void* rgb, cons
 {
     if (!st || !mask_red || !flow || !out_mask || !scratch || W == 0 || H == 0) return -1;
     return warp_flow(st, W, H, rgb, mask_red, flow, out_rgb, out_mask, out_bwd, out_occ_bwd, out_occ, scratch, WARP_OCC);
+}
+
+int ArapFlow_WarpStep(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* mask_red, const void* flow_a,
+                      const void* flow_b, void* out_rgb, void* out_mask, void* out_step)
+{
+    if (!st || !mask_red || !flow_a || !flow_b || !out_mask || !out_step || W == 0 || H == 0) return -1;
+    if (out_rgb && !rgb) return -1;
+    if ((uint64_t)W * H >= (1ull << 31)) return -1;                              // (the key's triangle index)
+    HC(hipSetDevice(st->device));
+    const size_t N = (size_t)W * H;
+    const WarpScratch L = warp_scratch(W, H, 0);
+    void* scratch = nullptr;                 // the call owns its scratch: it returns when the outputs are written
+    if (hipMalloc(&scratch, L.total) != hipSuccess) return (int)hipErrorOutOfMemory;
+    WarpJob j{};
+    j.flow_in = (const float2*)flow_a; j.flow_b = (const float2*)flow_b;
+    j.rgb = (const uint8_t*)rgb; j.mask = (const uint8_t*)mask_red;
+    j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask; j.step = (float2*)out_step;
+    WarpJob* dj = warp_job_scratch(j, L, scratch);
+    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
+    enqueue_warp(st->stream, dj, 1, (int)W, (int)H, 0, nullptr, 0, true);
+    const int rc = (int)hipGetLastError();
+    HC(hipStreamSynchronize(st->stream));
+    HC(hipFree(scratch));
+    return rc;
 }
 
 uint64_t ArapFlow_WarpLayersScratchBytes(unsigned W, unsigned H, unsigned n)

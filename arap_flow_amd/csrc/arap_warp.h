@@ -34,6 +34,10 @@ struct WarpJob {                    // one frame
     unsigned* cell;                 // [N+1] scratch of the occlusion query: per-cell counts -> starts, zero on entry
     unsigned* rank;                 // [N]   scratch: a vertex's rank inside its cell
     int4* bin;                      // [N]   scratch: binned vertices {P.x, P.y, v, m(v)}
+    // optional output of arap_mid.h (DESIGN.md "In-between frames"): all NULL = not wanted
+    const float2* field_b;          // [N] second state as positions, or NULL when `flow_b` is given
+    const float2* flow_b;           // [N] second state as a flow: position = (x,y) + flow, or NULL
+    float2* step;                   // [N] flow from the warp of `field` to the second state, domain of the warped frame
 };
 
 __device__ __forceinline__ float2 warp_pos(const WarpJob& j, int x, int y, int i)

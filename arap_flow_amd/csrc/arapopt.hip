@@ -34,6 +34,7 @@
 #include "arap_warp.h"
 #include "arap_occ.h"
 #include "arap_layers.h"
+#include "arap_mid.h"
 #include "arap_frame.h"
 
 using namespace arap;

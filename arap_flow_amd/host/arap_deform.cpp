@@ -5,7 +5,10 @@
 //   ./arap_deform --serve                                                (addition: the same lines on stdin, until EOF)
 // A list or --serve line may carry optional tokens after its six paths (addition, DESIGN.md "Backward flow and
 // occlusion"): bwd=PATH.flo (backward flow), occ=PATH.png (forward occlusion), occ_bwd=PATH.png (backward
-// occlusion), 8-bit 0/255.  Other trailing tokens are ignored, as before.
+// occlusion), 8-bit 0/255, and mid=I1,I2,..:PREFIX (DESIGN.md "In-between frames"): the in-between frames after the
+// ramp steps I1 < I2 < .., written as PREFIX_sII.flo, PREFIX_sII.png, PREFIX_sII_mask.png and PREFIX_sII_step.flo (II:
+// the step, two digits) in the formats of the line's own flow, warped RGB and warped mask.  All mid= lines of a batch
+// must name the same steps.  Other trailing tokens are ignored, as before.
 // A line whose first word is `layers` is no solve but the layered warp of one frame (DESIGN.md "Layered warp"):
 //   layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P]      (at least one output)
 // It runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
@@ -49,6 +52,8 @@ extern "C" {
 struct SolvePaths {
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
+    std::vector<unsigned> mid_steps;       // mid= token: snapshot steps (empty: not wanted) and the files' path prefix
+    std::string mid_prefix;
     int outputs() const
     {
         return (bwd.empty() && occ_bwd.empty() ? 0 : ARAPFLOW_OUT_BACKWARD) | (occ.empty() ? 0 : ARAPFLOW_OUT_OCCLUSION);
@@ -129,16 +134,44 @@ static bool load_frame(const SolvePaths& paths, Frame& f)
     return true;
 }
 
-static bool parse_line(const std::string& line, SolvePaths& q)
+// the value of a mid= token: I1,I2,..:PREFIX with 1 <= I1 < I2 < .., at most ARAPFLOW_MAX_SNAPSHOTS indices
+static bool parse_mid(const std::string& v, std::vector<unsigned>& steps, std::string& prefix)
+{
+    const size_t colon = v.find(':');
+    if (colon == std::string::npos || colon == 0 || colon + 1 >= v.size()) return false;
+    steps.clear();
+    size_t a = 0;
+    while (a < colon) {
+        size_t b = v.find(',', a);
+        if (b == std::string::npos || b > colon) b = colon;
+        if (b == a || b - a > 6) return false;
+        unsigned x = 0;
+        for (size_t k = a; k < b; ++k) {
+            if (v[k] < '0' || v[k] > '9') return false;
+            x = 10 * x + (unsigned)(v[k] - '0');
+        }
+        if (x < 1 || (!steps.empty() && x <= steps.back())) return false;
+        steps.push_back(x);
+        if (b == colon && v[b - 1] == ',') return false;
+        a = b + 1;
+    }
+    if (v[colon - 1] == ',' || steps.empty() || steps.size() > ARAPFLOW_MAX_SNAPSHOTS) return false;
+    prefix = v.substr(colon + 1);
+    return true;
+}
+
+// -1: not a solve line (too few paths), 0: a solve line with a malformed mid= token, 1: good
+static int parse_line(const std::string& line, SolvePaths& q)
 {
     std::istringstream tok(line);
-    if (!(tok >> q.rgb >> q.mask >> q.constraints >> q.flow >> q.warped_rgb >> q.warped_mask)) return false;
+    if (!(tok >> q.rgb >> q.mask >> q.constraints >> q.flow >> q.warped_rgb >> q.warped_mask)) return -1;
     for (std::string t; tok >> t;) {
         if (t.compare(0, 4, "bwd=") == 0) q.bwd = t.substr(4);
         else if (t.compare(0, 4, "occ=") == 0) q.occ = t.substr(4);
         else if (t.compare(0, 8, "occ_bwd=") == 0) q.occ_bwd = t.substr(8);
+        else if (t.compare(0, 4, "mid=") == 0 && t.size() > 4 && !parse_mid(t.substr(4), q.mid_steps, q.mid_prefix)) return 0;
     }
-    return true;
+    return 1;
 }
 
 static bool is_layers_line(const std::string& line)
@@ -231,19 +264,27 @@ static bool run_layers(Opt_State* state, const LayersSpec& q)
 // ---- where the lines come from: a finished list, or stdin as it arrives (--serve) ------------------------------------
 struct Loaded { bool ok = false; Frame f; bool is_layers = false; LayersSpec layers; };
 
-struct Item { bool is_layers = false; SolvePaths solve; LayersSpec layers; };
+struct Item { bool is_layers = false, bad = false; SolvePaths solve; LayersSpec layers; };
 
-// a list / --serve line -> item; false for a line that is neither (a bad `layers` line is reported)
+// a list / --serve line -> item; false for a line that is neither (a bad `layers` line and a bad mid= token are
+// reported, and `bad` is set)
 static bool parse_item(const std::string& line, Item& it)
 {
     if (is_layers_line(line)) {
         it.is_layers = true;
         if (parse_layers(line, it.layers)) return true;
+        it.bad = true;
         printf("Invalid layers line: %s\n", line.c_str());
         fflush(stdout);
         return false;
     }
-    return parse_line(line, it.solve);
+    const int rc = parse_line(line, it.solve);
+    if (rc == 0) {
+        it.bad = true;
+        printf("Invalid mid= token: %s\n", line.c_str());
+        fflush(stdout);
+    }
+    return rc == 1;
 }
 
 class FrameSource {
@@ -316,7 +357,13 @@ class FrameSource {
 };
 
 // ---- results: read back from the solver's pinned buffers, encoded and written by worker threads ---------------------
-struct Result { SolvePaths paths; std::vector<float> flow, bwd; std::vector<uint8_t> wrgb, wmsk, occ_bwd, occ; };
+struct MidResult { std::vector<float> flow, step; std::vector<uint8_t> rgb, mask; };
+struct Result {
+    SolvePaths paths;
+    std::vector<float> flow, bwd;
+    std::vector<uint8_t> wrgb, wmsk, occ_bwd, occ;
+    std::vector<MidResult> mid;            // one per snapshot step of the line's mid= token
+};
 
 class Writer {
   public:
@@ -336,6 +383,16 @@ class Writer {
                 printf("%s\n", err.c_str());
             if (!r->paths.occ.empty() && !arapio::write_png_gray8(r->paths.occ, w, h, r->occ.data(), err))
                 printf("%s\n", err.c_str());
+            for (size_t k = 0; k < r->mid.size(); ++k) {
+                char tag[16];
+                snprintf(tag, sizeof(tag), "_s%02u", r->paths.mid_steps[k]);
+                const std::string stem = r->paths.mid_prefix + tag;
+                const MidResult& m = r->mid[k];
+                arapio::write_flo(stem + ".flo", m.flow.data(), w, h);
+                if (!arapio::write_png_rgb(stem + ".png", w, h, m.rgb.data(), err)) printf("%s\n", err.c_str());
+                if (!arapio::write_png_mask1(stem + "_mask.png", w, h, m.mask.data(), err)) printf("%s\n", err.c_str());
+                arapio::write_flo(stem + "_step.flo", m.step.data(), w, h);
+            }
             std::lock_guard<std::mutex> g(*pm);
             if (report) printf("Done %s\n", r->paths.flow.c_str());     // --serve: one line per finished solve
             else printf("Saved\n");
@@ -378,7 +435,7 @@ int main(int argc, const char* argv[])
         for (std::string line; std::getline(list, line);) {
             Item q;
             if (parse_item(line, q)) lines.push_back(q);
-            else if (q.is_layers) return 1;
+            else if (q.bad) return 1;
         }
         if (lines.empty()) {
             printf("No file to be processed");
@@ -460,6 +517,17 @@ int main(int argc, const char* argv[])
                 if (bwd) { r->bwd.assign(bwd, bwd + 2 * n); r->occ_bwd.assign(obwd, obwd + n); }
                 if (occ) r->occ.assign(occ, occ + n);
             }
+            for (unsigned k = 0; k < r->paths.mid_steps.size(); ++k) {
+                const float *mf, *ms; const uint8_t *mr, *mm;
+                if (ArapFlow_SolverHostSnapshot(L.solver, (unsigned)b, k, &mf, &mr, &mm, &ms) != 0 || !mr) {
+                    printf("ARAP snapshots unavailable\n");
+                    return false;
+                }
+                MidResult m;
+                m.flow.assign(mf, mf + 2 * n); m.step.assign(ms, ms + 2 * n);
+                m.rgb.assign(mr, mr + 3 * n); m.mask.assign(mm, mm + n);
+                r->mid.push_back(std::move(m));
+            }
             writer.submit(r, sw, sh);
         }
         L.batch.clear();
@@ -472,6 +540,20 @@ int main(int argc, const char* argv[])
         for (const SolvePaths& q : L.batch) outputs |= q.outputs();
         if (ArapFlow_SolverSetOutputs(L.solver, outputs) != 0) {
             printf("ARAP outputs could not be set\n");
+            return false;
+        }
+        // snapshots are on iff a line of the batch asks (plain batches run nothing new); its mid= lines name the same steps
+        const std::vector<unsigned>* steps = nullptr;
+        for (const SolvePaths& q : L.batch) {
+            if (q.mid_steps.empty()) continue;
+            if (steps && *steps != q.mid_steps) {
+                printf("mid= steps differ from those of the batch: %s\n", q.flow.c_str());
+                return false;
+            }
+            steps = &q.mid_steps;
+        }
+        if (ArapFlow_SolverSetSnapshots(L.solver, steps ? steps->data() : nullptr, steps ? (unsigned)steps->size() : 0) != 0) {
+            printf("ARAP snapshots could not be set\n");
             return false;
         }
         if (ArapFlow_SolverSolveAsync(L.solver, (unsigned)L.batch.size(), numIter, nonLinearIter, linearIter, 1, 1) != 0) {

@@ -7,6 +7,7 @@
   FrameSolver      the device-resident batched counterpart (ArapFlow_Solver*, include/arap_opt.h part 2)
   warp_image       ARAP/warping/src/main.cpp:145-225 through ArapFlow_Warp
   warp_image_ex    the same, plus backward flow and occlusion maps (ArapFlow_WarpEx)
+  warp_step        the warp of one deformation state and the flow from it to a second one (ArapFlow_WarpStep)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -300,6 +301,42 @@ class FrameSolver:
             raise RuntimeError("ArapFlow_SolverSetOutputs failed")
         self.outputs = which
 
+    def set_snapshots(self, steps):
+        """in-between frames (ArapFlow_SolverSetSnapshots, DESIGN.md "In-between frames"): strictly increasing ramp-step
+        indices 1 <= i <= num_iter, at most capi.MAX_SNAPSHOTS; () switches them off.  Every later solve keeps the
+        state after those ramp steps and every warp after it writes their outputs: snapshot() / host_snapshot()."""
+        steps = [int(v) for v in steps]
+        if any(v < 0 for v in steps):
+            raise ValueError("ArapFlow_SolverSetSnapshots: bad arguments")
+        arr = (C.c_uint * max(1, len(steps)))(*steps)
+        if self.lib.ArapFlow_SolverSetSnapshots(self.h, arr, len(steps)) != 0:
+            raise ValueError("ArapFlow_SolverSetSnapshots: bad arguments")
+
+    def snapshot(self, slot, k, want_rgb=True):
+        """snapshot k (0-based) of a slot after the last warp: dict(flow, rgb, mask, step)"""
+        H, W = self.H, self.W
+        flow, step = np.empty((H, W, 2), np.float32), np.empty((H, W, 2), np.float32)
+        rgb = np.empty((H, W, 3), np.uint8) if want_rgb else None
+        mask = np.empty((H, W), np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        if self.lib.ArapFlow_SolverGetSnapshot(self.h, slot, k, p(flow), p(rgb), p(mask), p(step)) != 0:
+            raise ValueError("ArapFlow_SolverGetSnapshot: no snapshot %d for slot %d" % (k, slot))
+        return dict(flow=flow, rgb=rgb, mask=mask, step=step)
+
+    def host_snapshot(self, slot, k):
+        """views (no copy) of the pinned buffers of snapshot k of a `download` solve: valid until this solver's next
+        solve"""
+        H, W = self.H, self.W
+        pf, pr, pm, ps = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.ArapFlow_SolverHostSnapshot(self.h, slot, k, C.byref(pf), C.byref(pr), C.byref(pm), C.byref(ps))
+        if rc != 0:
+            raise ValueError("ArapFlow_SolverHostSnapshot: no downloaded snapshot %d for slot %d" % (k, slot))
+        def view(ptr, ctype, shape):
+            n = int(np.prod(shape))
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).reshape(shape)
+        return dict(flow=view(pf, C.c_float, (H, W, 2)), rgb=view(pr, C.c_uint8, (H, W, 3)) if pr.value else None,
+                    mask=view(pm, C.c_uint8, (H, W)), step=view(ps, C.c_float, (H, W, 2)))
+
     def set_frame(self, slot, mask_red, constraints, rgb=None, border_pins=True):
         mask_red = np.ascontiguousarray(mask_red, np.uint8)
         assert mask_red.shape == (self.H, self.W)
@@ -455,6 +492,32 @@ def warp_image_ex(state, rgb, mask_red, flow, backward=True, occlusion=True):
     if occlusion:
         out.update(occlusion=o_occ.cpu().numpy())
     return out
+
+
+def warp_step(state, rgb, mask_red, flow_a, flow_b):
+    """the warp of flow_a and the flow from that warped frame to the state flow_b (ArapFlow_WarpStep, DESIGN.md
+    "In-between frames").  rgb u8[H,W,3] or None, mask_red u8[H,W], flow_a / flow_b f32[H,W,2] (numpy) -> a dict of
+    warped_rgb (None without rgb), warped_mask and step f32[H,W,2]."""
+    lib = state.lib
+    H, W = mask_red.shape
+    if tuple(np.shape(flow_a)) != (H, W, 2) or tuple(np.shape(flow_b)) != (H, W, 2):
+        raise ValueError("warp_step: flows [H,W,2] expected")
+    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
+    d_msk = torch.from_numpy(np.ascontiguousarray(mask_red, np.uint8)).cuda()
+    d_a = torch.from_numpy(np.ascontiguousarray(flow_a, np.float32)).cuda()
+    d_b = torch.from_numpy(np.ascontiguousarray(flow_b, np.float32)).cuda()
+    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
+    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
+    o_step = torch.empty(H, W, 2, dtype=torch.float32, device="cuda")
+    p = lambda t: _dev_ptr(t) if t is not None else None
+    torch.cuda.synchronize()
+    rc = lib.ArapFlow_WarpStep(state.handle, W, H, p(d_rgb), p(d_msk), p(d_a), p(d_b), p(o_rgb), p(o_msk), p(o_step))
+    if rc != 0:
+        raise (ValueError("ArapFlow_WarpStep: bad arguments") if rc == -1 else
+               RuntimeError("ArapFlow_WarpStep failed: %d" % rc))
+    torch.cuda.synchronize()
+    return dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy(),
+                step=o_step.cpu().numpy())
 
 
 def warp_layers(state, rgb, masks, flows, bwd=False, occ_bwd=False, occ=True):

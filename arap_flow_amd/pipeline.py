@@ -4,7 +4,8 @@ What the reference's Python 2 scripts and C++ drivers do AROUND the hot path (SU
 behaviour (the contract each function states in its docstring), with the size / selection arithmetic as pure
 functions that tests/golden/host/ pins with hand-computed cases:
   SolveLine, parse_line, format_line, done_token, read_list_items    the list line: a solve (6 paths, optional output
-                            tokens bwd= occ= occ_bwd=) or the `layers` line, the layered warp of one frame (addition)
+                            tokens bwd= occ= occ_bwd= mid=) or the `layers` line, the layered warp of one frame (addition)
+  parse_mid, mid_token, mid_files, mid_steps    the mid= token: in-between frames from the constraint ramp (addition)
   deform_list, run_layers   ARAP/deformation/src/main.cpp:162-241  (arap_deform over a list)
   warp_files                ARAP/warping/src/main.cpp:302-336      (warp_image)
   cover_scale, fit_bg, add_bg            para_gen.py:36-61      (background compositing)
@@ -36,15 +37,17 @@ _ANTIALIAS = getattr(Image, "LANCZOS", None) or Image.ANTIALIAS   # Image.ANTIAL
 # A list line is the unit of work between para_gen.py, arap_deform.py and `arap_deform --serve` (C++ twin: parse_item in
 # host/arap_deform.cpp).  It is a solve line, SolveLine, or a `layers` line, the dict of parse_layers; parse_line reads
 # either from text, format_line writes it back, done_token is the path a worker reports it done by.
-EXTRA_KEYS = ("bwd", "occ", "occ_bwd")
+EXTRA_KEYS = ("bwd", "occ", "occ_bwd", "mid")
+MAX_SNAPSHOTS = 8            # ARAPFLOW_MAX_SNAPSHOTS of include/arap_opt.h
 LAYERS_WORD = "layers"
 LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2")
 
 
 class SolveLine(NamedTuple):
     """main.cpp:183-191: one solve per line, six whitespace-separated paths
-        rgb mask constraints out_flow out_rgb out_mask [bwd=PATH.flo] [occ=PATH.png] [occ_bwd=PATH.png]
-    `extra`: the optional outputs the line asks for, {key: path} (parse_extra)"""
+        rgb mask constraints out_flow out_rgb out_mask [bwd=PATH.flo] [occ=PATH.png] [occ_bwd=PATH.png] [mid=I1,I2,..:PREFIX]
+    `extra`: the optional outputs the line asks for, {key: path} (parse_extra); the value of `mid` is the token's text
+    after the `=` (parse_mid)"""
     rgb: str
     mask: str
     constraints: str
@@ -54,13 +57,52 @@ class SolveLine(NamedTuple):
     extra: dict
 
 
+def parse_mid(value):
+    """the value of a mid= token, I1,I2,..:PREFIX (DESIGN.md "In-between frames") -> (steps, prefix): 1 to MAX_SNAPSHOTS
+    strictly increasing ramp-step indices >= 1 and the path prefix of the files of mid_files"""
+    idx, colon, prefix = value.partition(":")
+    try:
+        steps = tuple(int(t) for t in idx.split(","))
+    except ValueError:
+        steps = ()
+    if not (colon and prefix and 1 <= len(steps) <= MAX_SNAPSHOTS and steps[0] >= 1 and
+            all(a < b for a, b in zip(steps, steps[1:]))):
+        raise ValueError("bad mid= token %r: mid=I1,I2,..:PREFIX with 1 <= I1 < I2 < .., at most %d" % (value, MAX_SNAPSHOTS))
+    return steps, prefix
+
+
+def mid_token(steps, prefix):
+    """the inverse of parse_mid"""
+    return "%s:%s" % (",".join("%d" % i for i in steps), prefix)
+
+
+def mid_files(prefix, step):
+    """the four files of the snapshot after ramp step `step`: its flow from frame 1, the in-between frame and its mask
+    (formats of a line's own flow, warped RGB and warped mask) and the flow from it to the next state"""
+    stem = "%s_s%02d" % (prefix, step)
+    return dict(flow=stem + ".flo", rgb=stem + ".png", mask=stem + "_mask.png", step=stem + "_step.flo")
+
+
+def mid_steps(K, num_iter):
+    """para_gen --mid K: K ramp steps spread evenly over the ramp, (i * num_iter) // (K + 1) for i = 1 .. K; they must be
+    distinct and >= 1 (19 and K = 3: 4, 9, 14)"""
+    K, num_iter = int(K), int(num_iter)
+    steps = [(i * num_iter) // (K + 1) for i in range(1, K + 1)]
+    if not 1 <= K <= MAX_SNAPSHOTS or min(steps) < 1 or len(set(steps)) != K:
+        raise ValueError("--mid %d: 1 .. %d distinct steps of a ramp of %d are needed" % (K, MAX_SNAPSHOTS, num_iter))
+    return steps
+
+
 def parse_extra(tokens):
-    """optional tokens after a line's paths: bwd=PATH.flo, occ=PATH.png, occ_bwd=PATH.png -> {key: path}.  Any other
-    token is ignored (a line's tokens after the sixth always were)."""
+    """optional tokens after a line's paths: bwd=PATH.flo, occ=PATH.png, occ_bwd=PATH.png, mid=I1,I2,..:PREFIX ->
+    {key: value}.  Any other token is ignored (a line's tokens after the sixth always were); a malformed mid= token is
+    an error (parse_mid)."""
     out = {}
     for t in tokens:
         k, eq, v = t.partition("=")
         if eq and k in EXTRA_KEYS and v:
+            if k == "mid":
+                parse_mid(v)
             out[k] = v
     return out
 
@@ -193,6 +235,27 @@ def _save_result(ln, r):
         save_occ(r["occlusion_bwd"], extra["occ_bwd"])
     if "occ" in extra:
         save_occ(r["occlusion"], extra["occ"])
+    if "mid" in extra:
+        steps, prefix = parse_mid(extra["mid"])
+        for i, m in zip(steps, r["mid"]):
+            f = mid_files(prefix, i)
+            flo.flow_write(f["flow"], m["flow"])
+            Image.fromarray(m["rgb"]).save(f["rgb"])
+            save_mask(m["mask"], f["mask"])
+            flo.flow_write(f["step"], m["step"])
+
+
+def batch_snapshots(batch):
+    """the snapshot steps of a batch of SolveLines: those of its mid= lines, which must all name the same; () if none
+    asks"""
+    steps = ()
+    for ln in batch:
+        if "mid" in ln.extra:
+            own = parse_mid(ln.extra["mid"])[0]
+            if steps and own != steps:
+                raise ValueError("mid= steps %s differ from the batch's %s: %s" % (own, steps, ln.flow))
+            steps = own
+    return steps
 
 
 class _Lane:
@@ -201,6 +264,7 @@ class _Lane:
 
     def __init__(self):
         self.solver, self.batch = None, []
+        self.snaps = ()                # the snapshot steps in effect in `solver` (batch_snapshots)
 
 
 def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, max_batch=FILL_MAX, verbose=True):
@@ -236,6 +300,9 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
             for b, ln in enumerate(lane.batch):
                 r = lane.solver.host_results(b)
                 res = {k: v.copy() for k, v in r.items() if v is not None}
+                if "mid" in ln.extra:
+                    res["mid"] = [{k: v.copy() for k, v in lane.solver.host_snapshot(b, q).items()}
+                                  for q in range(len(parse_mid(ln.extra["mid"])[0]))]
                 writing.append(pool.submit(_save_result, ln, res))
                 if verbose:
                     print("Saved")                                          # main.cpp:159
@@ -258,6 +325,7 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
                           "same list.\nStarting to re-build plan...")      # CombinedSolver.h:151-153
                 for lane in lanes:
                     lane.solver = opt.FrameSolver(state, W, H, batch=max_batch)
+                    lane.snaps = ()
                 size = (W, H)
             lane, other = lanes[cur], lanes[cur ^ 1]
             solver, batch = lane.solver, lane.batch                     # (empty: drained a round ago)
@@ -280,6 +348,10 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
                 j += 1
             want = set().union(*[ln.extra for ln in batch])
             solver.set_outputs(backward=bool(want & {"bwd", "occ_bwd"}), occlusion="occ" in want)
+            steps = batch_snapshots(batch)                      # on iff a line asks: plain batches run nothing new
+            if steps != lane.snaps:
+                solver.set_snapshots(steps)
+                lane.snaps = steps
             solver.solve_async(len(batch), num_iter, non_linear_iter, linear_iter, warp=True, download=True)
             drain(other)                                               # the previous batch, while this one is being solved
             cur ^= 1
@@ -445,7 +517,10 @@ EXTRA_OF = dict(bwd_gen="bwd", occbwd_gen="occ_bwd", occ_gen="occ")   # para_gen
 def make_arap_path(p):
     """para_gen.py:331-339: the list-file line of one solve, from para_gen's path table of the pair (or segment)"""
     six = [osp.abspath(p[k]) for k in ("rgb1_gen", "msk1_gen", "cstr_tmp", "flow_gen", "rgb2_gen", "msk2_gen")]
-    return SolveLine(*six, extra={t: p[k] for k, t in EXTRA_OF.items() if k in p})
+    extra = {t: p[k] for k, t in EXTRA_OF.items() if k in p}
+    if "mid_gen" in p:                          # --mid: the prefix of the pair's in-between files, steps in "_mid"
+        extra["mid"] = mid_token(p["_mid"], p["mid_gen"])
+    return SolveLine(*six, extra=extra)
 
 
 def replace_ext(dict_path, seg_num, keep_orgs=()):

@@ -201,6 +201,31 @@ int ArapFlow_SolverGetExtraResults(ArapFlow_Solver* s, unsigned slot, float* bwd
 int ArapFlow_SolverHostExtraResults(ArapFlow_Solver* s, unsigned slot, const float** bwd, const uint8_t** occ_bwd,
                                     const uint8_t** occ);
 
+/* In-between frames from the constraint ramp (DESIGN.md "In-between frames"; off by default, and then nothing is
+ * allocated, copied or launched).  After ramp step i (1 <= i <= numIter) the slot's Offset is the state S_i: a converged
+ * deformation towards the fraction i / numIter of every handle's displacement; S_numIter is the final result.
+ * ArapFlow_SolverSetSnapshots(s, steps, n) selects n <= ARAPFLOW_MAX_SNAPSHOTS strictly increasing step indices >= 1
+ * for every later solve (n = 0: off); -1 on bad arguments.  A solve whose numIter is below the largest index returns
+ * -1 before anything is enqueued.  Every later solve copies the states S_{i_k} of its slots as the ramp passes them,
+ * and every warp after it (ArapFlow_SolverWarp, SolveAsync(.., warp = 1, ..)) then writes per snapshot k and slot
+ *   flow  float[H][W][2]   S_{i_k} - grid (frame-1 domain), the expression of the final flow
+ *   rgb   uint8[H][W][3], mask uint8[H][W]   the rasteriser on the field S_{i_k}: the in-between frame t_k
+ *   step  float[H][W][2]   flow from t_k to the next state (S_{i_(k+1)}; the final one after the last snapshot), in the
+ *                          domain of t_k; 0 where nothing is drawn
+ * so flow_1, step_1 .. step_n chain frame 1 -> t_1 -> .. -> t_n -> frame 2.  The optional outputs of
+ * ArapFlow_SolverSetOutputs apply to the final warp only.  Device memory (28 bytes per vertex, snapshot and slot) is
+ * allocated by the first solve that needs it.
+ * ArapFlow_SolverGetSnapshot: synchronise and copy snapshot k (0-based, in the order given) of one slot to HOST
+ * buffers, any may be NULL; -1 if the last warp wrote no such snapshot (or rgb is asked of a slot without RGB).
+ * ArapFlow_SolverHostSnapshot: pointers into the solver's pinned buffers filled by a `download` solve (valid until the
+ * next solve of this solver; rgb NULL if the slot has no RGB); -1 if that solve downloaded no such snapshot. */
+#define ARAPFLOW_MAX_SNAPSHOTS 8
+int ArapFlow_SolverSetSnapshots(ArapFlow_Solver* s, const unsigned* steps, unsigned n);
+int ArapFlow_SolverGetSnapshot(ArapFlow_Solver* s, unsigned slot, unsigned k, float* flow, uint8_t* rgb, uint8_t* mask,
+                               float* step);
+int ArapFlow_SolverHostSnapshot(ArapFlow_Solver* s, unsigned slot, unsigned k, const float** flow, const uint8_t** rgb,
+                                const uint8_t** mask, const float** step);
+
 /* copyResultToCPU + warpField (CombinedSolver.h:280-366) on the device for slots [0, nframes):
  * flow = Offset - grid, and the forward triangle rasterisation of rgb and mask with the solved
  * Offset as warp field.  Asynchronous. */
@@ -288,6 +313,16 @@ uint64_t ArapFlow_WarpExScratchBytes(unsigned W, unsigned H);
 int ArapFlow_WarpEx(Opt_State* state, unsigned W, unsigned H, const void* rgb, const void* mask_red,
                     const void* flow, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ,
                     void* scratch);
+
+/* The warp of flow_a plus the flow from that warped frame to a second state (DESIGN.md "In-between frames"), on
+ * DEVICE buffers: flow_a, flow_b float[H][W][2] are two deformations of the same frame as flows (positions
+ * (float)x + flow.x, (float)y + flow.y, as in ArapFlow_Warp).  out_rgb / out_mask: ArapFlow_Warp's of flow_a (out_rgb
+ * and rgb may be NULL).  out_step float[H][W][2]: per pixel q of the warped frame, with the triangle drawn there, the
+ * point of state b interpolated with the rasteriser's barycentrics of state a, minus q; 0 where nothing is drawn.  With
+ * flow_b = 0 it is ArapFlow_WarpEx's backward flow bit for bit.  The call allocates its own scratch and returns when
+ * the outputs are written.  Returns 0, -1 on bad arguments, or a HIP error code. */
+int ArapFlow_WarpStep(Opt_State* state, unsigned W, unsigned H, const void* rgb, const void* mask_red,
+                      const void* flow_a, const void* flow_b, void* out_rgb, void* out_mask, void* out_step);
 
 /* Layered warp (DESIGN.md "Layered warp"): ONE rasteriser pass over the n layers of a frame -- the --multseg segments in
  * list order, the higher index on top -- on DEVICE buffers: rgb uint8[H][W][3] shared by all layers (or NULL: no

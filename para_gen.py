@@ -2,7 +2,7 @@
 """para_gen -- Python 3 twin of the reference's dataset generator CLI (para_gen.py:341-653), same flags.
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
-                     [--bwd_flow] [--occ | --multseg --occ_layers]
+                     [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -54,9 +54,18 @@ orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
+mid_dir = "Mid"                    # --mid K: in-between frames from the constraint ramp (addition)
+NUM_ITER = 19                      # the ramp length of the ARAP drivers (main.cpp:215-221): what --mid K spreads over
 LAYERS_OCC = "occl_gen"            # --multseg --occ_layers: the frame's forward occlusion, made by a `layers` line
 EXT_KEYS = list(pipeline.EXTRA_OF) + [LAYERS_OCC]                     # every optional output of a frame
 CPP_BIN = osp.join(HERE, "arap_flow_amd", "bin", "arap_deform")
+
+
+def mid_paths(p):
+    """--mid: every in-between file of a pair's path table, step by step (flow, frame, mask, step flow); [] without"""
+    if "mid_gen" not in p:
+        return []
+    return [pipeline.mid_files(p["mid_gen"], i)[k] for i in p["_mid"] for k in ("flow", "rgb", "mask", "step")]
 
 
 def _pair_id(seq, stem):
@@ -141,6 +150,7 @@ def prepare_pair(args):
     p = dict(p)
     seq, stem = p.pop("_seq"), p.pop("_stem")
     line = pipeline.make_arap_path(p)
+    p.pop("_mid", None)
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
     im1, mk1, im2, mk2 = preprocess(p, flags.size)
@@ -195,6 +205,11 @@ def finish_frame(rec):
         im = np.array(Image.open(rec.line.out_rgb).convert("RGB"))
         m = np.array(Image.open(rec.line.out_mask))
         Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(rec.line.out_rgb)
+        if "mid" in rec.line.extra:                         # the in-between frames get the pair's background too
+            steps, prefix = pipeline.parse_mid(rec.line.extra["mid"])
+            for f in (pipeline.mid_files(prefix, i) for i in steps):
+                im, m = np.array(Image.open(f["rgb"]).convert("RGB")), np.array(Image.open(f["mask"]))
+                Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(f["rgb"])
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -366,7 +381,7 @@ def scan(flags, input_root, output_root):
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
-                                                           obw=occ_bwd_dir, occ=occ_dir).items()}
+                                                           obw=occ_bwd_dir, occ=occ_dir, mid=mid_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
     all_paths = []
     for root, dirs, _ in os.walk(rgb_org):
@@ -393,9 +408,13 @@ def scan(flags, input_root, output_root):
                     e.update(occ_gen=osp.join(roots["occ"], seq, f + ".png"))
                 if getattr(flags, "occ_layers", False):
                     e[LAYERS_OCC] = osp.join(roots["occ"], seq, f + ".png")
+                if getattr(flags, "mid", 0):
+                    e["mid_gen"] = osp.join(roots["mid"], seq, f)
                 e = {k: osp.abspath(v) for k, v in e.items()}
                 e["_seq"], e["_stem"] = seq, f
-                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e]    # every requested output
+                if "mid_gen" in e:
+                    e["_mid"] = tuple(flags.mid_steps)
+                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e)    # every requested output
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -444,7 +463,7 @@ def main(flags):
     for p in all_paths:
         ln = pipeline.make_arap_path(p)
         lmdb_paths.append([ln.rgb, ln.out_rgb, ln.flow])
-        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p])
+        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p))
 
     # backgrounds: drawn without replacement until the list is used up, then refilled (para_gen.py:484-499)
     tmp_paths, picks = [], []
@@ -524,7 +543,8 @@ def main(flags):
                 p.kill()
     out_paths = [" ".join(ln) for ln in lmdb_paths if all(osp.exists(q) for q in ln)]    # :588-603
     open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
-    if getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False):     # all_files.list stays as it is; the extra outputs get their own list
+    if (getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False) or
+            getattr(flags, "mid", 0)):                      # all_files.list stays as it is; the extra outputs get their own list
         ext = [" ".join(ln) for ln in ext_paths if all(osp.exists(q) for q in ln)]
         open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     dt = time.time() - t_start
@@ -595,6 +615,10 @@ def parse(argv=None):
     parser.add_argument("--occ_layers", action="store_true", default=False,
                         help="with --multseg: also write the forward occlusion across segments OUT/Occ/<seq>/<frame>.png, "
                              "from one layered warp per frame (DESIGN.md \"Layered warp\")")
+    parser.add_argument("--mid", type=int, default=0, metavar="K",
+                        help="also write K in-between frames per pair, from K ramp steps spread evenly over the solve's "
+                             "constraint ramp: OUT/Mid/<seq>/<frame>_sII{.flo,.png,_mask.png,_step.flo} (DESIGN.md "
+                             "\"In-between frames\")")
     parser.add_argument("--keep_segments", action="store_true", default=False,
                         help="with --multseg: keep the per-segment files after they are merged (for inspection)")
     flags = parser.parse_args(argv)
@@ -610,6 +634,18 @@ def parse(argv=None):
     if (flags.bwd_flow or flags.occ) and not own_arap_bin(flags.arap_bin):
         parser.error("--bwd_flow / --occ need this repository's arap_deform (C++ or arap_deform.py): a foreign "
                      "--arap_bin does not write the extra outputs")
+    flags.mid_steps = []
+    if flags.mid:
+        if flags.multseg:
+            parser.error("--mid cannot be combined with --multseg: merging the segments' in-between states is a "
+                         "separate piece of work")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--mid needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
+                         "not know the mid= token")
+        try:
+            flags.mid_steps = pipeline.mid_steps(flags.mid, NUM_ITER)
+        except ValueError as e:
+            parser.error(str(e))
     if flags.size is not None:
         flags.size = tuple(int(s) for s in flags.size)
     assert 0 < flags.fd < 20, "Invalid fd number!"
