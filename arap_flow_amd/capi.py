@@ -75,6 +75,8 @@ SYMBOLS = [
     ("ArapFlow_WarpStep", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ArapFlow_WarpLayersScratchBytes", C.c_uint64, [_U, _U, _U]),
     ("ArapFlow_WarpLayers", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("ArapFlow_WarpLayersStepScratchBytes", C.c_uint64, [_U, _U, _U]),
+    ("ArapFlow_WarpLayersStep", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 ]
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h

@@ -1,6 +1,6 @@
-// abi_warp.h -- the warp entry points on caller-owned images (ArapFlow_Warp / WarpEx / WarpLayers): the layout of their
-// scratch buffer, stated once for the size functions and for the code that carves it up, and the one enqueue of
-// rasterise -> optional outputs -> resolve that the frame solver's warp shares.
+// abi_warp.h -- the warp entry points on caller-owned images (ArapFlow_Warp / WarpEx / WarpStep / WarpLayers /
+// WarpLayersStep): the layout of their scratch buffer, stated once for the size functions and for the code that carves
+// it up, and the one enqueue of rasterise -> optional outputs -> resolve that the frame solver's warp shares.
 #pragma once
 
 // the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
@@ -20,20 +20,22 @@ static void enqueue_warp_outputs(hipStream_t stream, const WarpJob* dj, unsigned
 }
 
 // Scratch of one warp job: the key image, then -- for the occlusion map (WARP_OCC) -- cell counts, ranks and bins, then
-// the layered warp's owner image (WARP_OWNER), each aligned to 256 bytes, and the WarpJob itself in a last 256 bytes.
+// the layered warp's owner image (WARP_OWNER), then the layered step's query points (WARP_PTS), each aligned to 256
+// bytes, and the WarpJob itself in a last 256 bytes.
 // Offsets from the start of the buffer; a part that is absent has zero bytes (its offset equals the next one's).
-enum { WARP_OCC = 1, WARP_OWNER = 2 };
-struct WarpScratch { size_t key, cell, rank, bin, owner, job, total; };
+enum { WARP_OCC = 1, WARP_OWNER = 2, WARP_PTS = 4 };
+struct WarpScratch { size_t key, cell, rank, bin, owner, pts, job, total; };
 static WarpScratch warp_scratch(uint64_t W, uint64_t H, int parts)
 {
     const uint64_t N = W * H;
-    const bool occ = parts & WARP_OCC, own = parts & WARP_OWNER;
+    const bool occ = parts & WARP_OCC, own = parts & WARP_OWNER, pts = parts & WARP_PTS;
     WarpScratch L{};
     L.cell = L.key + align_up(N * 8, 256);
     L.rank = L.cell + (occ ? align_up(4 * (N + 1), 256) : 0);
     L.bin = L.rank + (occ ? align_up(4 * N, 256) : 0);
     L.owner = L.bin + (occ ? align_up(16 * N, 256) : 0);
-    L.job = L.owner + (own ? align_up(N, 256) : 0);
+    L.pts = L.owner + (own ? align_up(N, 256) : 0);
+    L.job = L.pts + (pts ? align_up(16 * N, 256) : 0);
     L.total = L.job + 256;
     return L;
 }
@@ -161,6 +163,49 @@ int ArapFlow_WarpLayers(Opt_State* st, unsigned W, unsigned H, unsigned n, const
         hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, 1), dim3(1024), 0, st->stream, dj, (int)N);
         hipLaunchKernelGGL(k_layers_scatter, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)H, (int)N);
         hipLaunchKernelGGL(k_layers_tri, g2, dim3(64, 4), 0, st->stream, dj, ls, (int)W, (int)H);
+    }
+    hipLaunchKernelGGL(k_layers_resolve, g1, dim3(256), 0, st->stream, dj, (int)N);
+    return (int)hipGetLastError();
+}
+
+// per pixel: 8 (key) + 4 (cell) + 4 (rank) + 16 (bin) + 16 (query point) = 48 bytes, however many layers
+uint64_t ArapFlow_WarpLayersStepScratchBytes(unsigned W, unsigned H, unsigned n)
+{
+    (void)n;
+    return warp_scratch(W, H, WARP_OCC | WARP_PTS).total;
+}
+
+int ArapFlow_WarpLayersStep(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                            const void* flows_a, const void* flows_b, void* out_rgb, void* out_mask, void* out_step,
+                            void* out_occ, void* scratch)
+{
+    if (!st || !masks_red || !flows_a || !flows_b || !scratch || W == 0 || H == 0 || n == 0 || n > 255) return -1;
+    if (!out_rgb && !out_mask && !out_step && !out_occ) return -1;
+    if (out_rgb && !rgb) return -1;
+    const uint64_t N64 = (uint64_t)W * H;
+    if (N64 >= (1ull << 31) || (out_occ && N64 > (1ull << 24))) return -1;      // key / query point field widths
+    const size_t N = (size_t)N64;
+    const WarpScratch L = warp_scratch(W, H, WARP_OCC | WARP_PTS);
+    WarpJob j{};
+    j.rgb = (const uint8_t*)rgb;
+    j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
+    j.step = (float2*)out_step; j.occ = (uint8_t*)out_occ;
+    WarpJob* dj = warp_job_scratch(j, L, scratch);
+    int4* pts = (int4*)((char*)scratch + L.pts);
+    LayerSet la{}, lb{};                     // the layers placed by a and by b: the same masks
+    la.masks = lb.masks = (const uint8_t*)masks_red; la.n = lb.n = (int)n;
+    la.flows = (const float2*)flows_a; lb.flows = (const float2*)flows_b;
+    const dim3 g1((unsigned)((N + 255) / 256)), g2((W + 63) / 64, (H + 3) / 4, n);
+    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
+    if (out_occ) HC(hipMemsetAsync(j.cell, 0, 4 * (N + 1), st->stream));
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
+    hipLaunchKernelGGL(k_layers_raster, g2, dim3(64, 4), 0, st->stream, dj, la, (int)W, (int)H);
+    if (out_step || out_occ)
+        hipLaunchKernelGGL(k_lstep_step, g1, dim3(256), 0, st->stream, dj, la, lb.flows, pts, (int)W, (int)H, (int)N);
+    if (out_occ) {
+        hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, 1), dim3(1024), 0, st->stream, dj, (int)N);
+        hipLaunchKernelGGL(k_lstep_scatter, g1, dim3(256), 0, st->stream, dj, pts, (int)W, (int)H, (int)N);
+        hipLaunchKernelGGL(k_layers_tri, g2, dim3(64, 4), 0, st->stream, dj, lb, (int)W, (int)H);
     }
     hipLaunchKernelGGL(k_layers_resolve, g1, dim3(256), 0, st->stream, dj, (int)N);
     return (int)hipGetLastError();

@@ -19,10 +19,11 @@ __device__ __forceinline__ float2 warp_pos_b(const WarpJob& j, int x, int y, int
     return make_float2((float)x + f.x, (float)y + f.y);
 }
 
-// step(q) of a covered pixel q = (qx, qy) whose winner under the job's first field a is triangle t: d - q, with d the
-// point of state b interpolated at q with the rasteriser's barycentrics of a(c0), a(c1), a(c2).  With b = the pixel
-// grid this is tri_backward's B(q) (arap_occ.h), expression for expression.
-__device__ __forceinline__ float2 tri_transfer(const WarpJob& j, int W, unsigned t, int qx, int qy)
+// d(q) of a covered pixel q = (qx, qy) whose winner under the job's first field a is triangle t: the point of state b
+// interpolated at q with the rasteriser's barycentrics of a(c0), a(c1), a(c2).  The one copy: tri_transfer and the
+// layered step pass (arap_layers_step.h) call it.  False, and d untouched, where the rasteriser's test fails at q
+// (never: it passed there)
+__device__ __forceinline__ bool tri_transfer_point(const WarpJob& j, int W, unsigned t, int qx, int qy, float2& d)
 {
     const int u = (int)(t >> 1);
     const int uy = u / W, ux = u - uy * W;
@@ -31,13 +32,26 @@ __device__ __forceinline__ float2 tri_transfer(const WarpJob& j, int W, unsigned
     const int ax = ux, ay = uy + odd, bx = ux + 1, by = uy, cx = ux + odd, cy = uy + 1;
     const int i0 = ax + W * ay, i1 = bx + W * by, i2 = cx + W * cy;
     const float2 p0 = warp_pos(j, ax, ay, i0), p1 = warp_pos(j, bx, by, i1), p2 = warp_pos(j, cx, cy, i2);
-    const float sx = (float)qx, sy = (float)qy;
     float b0, b1, b2;
-    if (!tri_bary(p0, p1, p2, sx, sy, b0, b1, b2)) return make_float2(0.f, 0.f);     // (never: the raster passed this test at q)
+    if (!tri_bary(p0, p1, p2, (float)qx, (float)qy, b0, b1, b2)) return false;
     const float2 d0 = warp_pos_b(j, ax, ay, i0), d1 = warp_pos_b(j, bx, by, i1), d2 = warp_pos_b(j, cx, cy, i2);
-    const float dx = (d0.x * b0 + d1.x * b1) + d2.x * b2;
-    const float dy = (d0.y * b0 + d1.y * b1) + d2.y * b2;
-    return make_float2(dx - sx, dy - sy);
+    d.x = (d0.x * b0 + d1.x * b1) + d2.x * b2;
+    d.y = (d0.y * b0 + d1.y * b1) + d2.y * b2;
+    return true;
+}
+
+// the step from pixel q to the point d: the one statement of the subtraction (tri_transfer, k_lstep_step)
+__device__ __forceinline__ float2 step_of(float2 d, int qx, int qy)
+{
+    return make_float2(d.x - (float)qx, d.y - (float)qy);
+}
+
+// step(q) = d(q) - q.  With b = the pixel grid this is tri_backward's B(q) (arap_occ.h), expression for expression.
+__device__ __forceinline__ float2 tri_transfer(const WarpJob& j, int W, unsigned t, int qx, int qy)
+{
+    float2 d;
+    if (!tri_transfer_point(j, W, t, qx, qy, d)) return make_float2(0.f, 0.f);
+    return step_of(d, qx, qy);
 }
 
 // Per pixel q of the in-between frame (the warp of field a): step(q) towards state b, (0, 0) where nothing is drawn

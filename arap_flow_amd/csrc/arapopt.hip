@@ -35,6 +35,7 @@
 #include "arap_occ.h"
 #include "arap_layers.h"
 #include "arap_mid.h"
+#include "arap_layers_step.h"
 #include "arap_frame.h"
 
 using namespace arap;

@@ -10,7 +10,11 @@
 // the step, two digits) in the formats of the line's own flow, warped RGB and warped mask.  All mid= lines of a batch
 // must name the same steps.  Other trailing tokens are ignored, as before.
 // A line whose first word is `layers` is no solve but the layered warp of one frame (DESIGN.md "Layered warp"):
-//   layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P]      (at least one output)
+//   layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P] [mid=I1,I2,..:PREFIX]
+// (at least one output).  Its mid= token (DESIGN.md "Layered in-between frames") reads every layer's snapshot flows
+// STEM_l_sII.flo, STEM_l = FLO_l without `.flo`, and writes per snapshot the composite PREFIX_sII.flo, PREFIX_sII.png,
+// PREFIX_sII_mask.png, PREFIX_sII_step.flo and, with occ= on the line, the link occlusions PREFIX_s00_occ.png (frame 1
+// -> first snapshot) and PREFIX_sII_occ.png (snapshot -> next state).
 // It runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -22,6 +26,7 @@
 // batch's results are read back and encoded (worker threads).  --serve is what para_gen.py starts once per GPU: a
 // persistent worker that is fed list-file lines over a pipe as the front end produces them and reports
 // "Done <flow path>" per finished solve, instead of one child process (HIP start-up, plan, graph capture) per hand-out.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -65,6 +70,8 @@ struct LayersSpec {
     std::string rgb;
     std::vector<std::string> masks, flows;
     std::string occ, bwd, occ_bwd, rgb2, mask2;
+    std::vector<unsigned> mid_steps;       // mid= token (empty: not wanted) and the composite files' path prefix
+    std::string mid_prefix;
     std::string first_out;                 // the first output token's path: what --serve reports
 };
 
@@ -199,11 +206,111 @@ static bool parse_layers(const std::string& line, LayersSpec& q)
         const std::string k = t.substr(0, eq), v = t.substr(eq + 1);
         std::string* dst = k == "occ" ? &q.occ : k == "bwd" ? &q.bwd : k == "occ_bwd" ? &q.occ_bwd
                          : k == "rgb2" ? &q.rgb2 : k == "mask2" ? &q.mask2 : nullptr;
-        if (!dst) return false;
-        *dst = v;
+        if (k == "mid") {
+            if (!parse_mid(v, q.mid_steps, q.mid_prefix)) return false;
+        } else if (!dst) return false;
+        else *dst = v;
         if (q.first_out.empty()) q.first_out = v;
     }
     return !q.first_out.empty();
+}
+
+// PREFIX_sII: the stem of the files of the state after ramp step II (pipeline.mid_files)
+static std::string mid_stem(const std::string& prefix, unsigned step)
+{
+    char tag[16];
+    snprintf(tag, sizeof(tag), "_s%02u", step);
+    return prefix + tag;
+}
+
+// the mid= token of a layers line (pipeline.run_layers_mid): `masks` [n][N] and `flows` [n][N][2] are the line's
+// layers, already read.  One ArapFlow_WarpLayersStep per snapshot on the state's stream, synchronously.
+static bool run_layers_mid(Opt_State* state, const LayersSpec& q, const arapio::Image& rgb,
+                           const std::vector<uint8_t>& masks, const std::vector<float>& flows)
+{
+    const int w = rgb.w, h = rgb.h;
+    const size_t N = (size_t)w * h, n = q.masks.size(), ns = q.mid_steps.size();
+    // states[k]: the layers' flows after snapshot k; states[ns]: the final flows
+    std::vector<std::vector<float>> states(ns);
+    for (size_t k = 0; k < ns; ++k) {
+        states[k].resize(n * N * 2);
+        for (size_t l = 0; l < n; ++l) {
+            const std::string& f = q.flows[l];
+            if (f.size() < 4 || f.compare(f.size() - 4, 4, ".flo") != 0) {
+                printf("layers: mid= needs flows named *.flo, got %s\n", f.c_str());
+                return false;
+            }
+            const std::string snap = mid_stem(f.substr(0, f.size() - 4), q.mid_steps[k]) + ".flo";
+            std::vector<float> fl;
+            int fw = 0, fh = 0;
+            if (!arapio::read_flo(snap, fl, fw, fh)) {
+                printf("layers: snapshot %s is missing\n", snap.c_str());
+                return false;
+            }
+            if (fw != w || fh != h) {
+                printf("layers: %s differs in size from %s\n", snap.c_str(), q.rgb.c_str());
+                return false;
+            }
+            memcpy(states[k].data() + l * N * 2, fl.data(), N * 8);
+        }
+    }
+    const bool occ = !q.occ.empty();
+    const uint64_t scr = std::max(ArapFlow_WarpLayersStepScratchBytes((unsigned)w, (unsigned)h, (unsigned)n),
+                                  ArapFlow_WarpLayersScratchBytes((unsigned)w, (unsigned)h, (unsigned)n));
+    const size_t off_msk = 3 * N, off_a = (off_msk + n * N + 255) / 256 * 256, off_b = off_a + n * N * 8;
+    const size_t off_out = off_b + n * N * 8, out_bytes = 8 * N + 3 * N + N + N;        // step, rgb, mask, occ
+    const size_t off_scr = (off_out + out_bytes + 255) / 256 * 256;
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, off_scr + scr) != hipSuccess) { printf("layers: out of device memory\n"); return false; }
+    char* o = d + off_out;
+    std::vector<uint8_t> host(out_bytes);
+    std::string err;
+    auto png = [&](bool written) { if (!written) printf("%s\n", err.c_str()); return written; };
+    // ok: the device work went through; wrote: so did the files (a file that did not has said so itself)
+    bool wrote = true;
+    bool ok = hipMemcpy(d, rgb.rgb.data(), 3 * N, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + off_msk, masks.data(), n * N, hipMemcpyHostToDevice) == hipSuccess;
+    auto upload = [&](size_t off, size_t k) {
+        const float* src = k < ns ? states[k].data() : flows.data();
+        return hipMemcpy(d + off, src, n * N * 8, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (ok && occ) {                          // frame 1 -> first snapshot: the layered warp's occlusion of that state
+        ok = upload(off_a, 0) &&
+             ArapFlow_WarpLayers(state, (unsigned)w, (unsigned)h, (unsigned)n, nullptr, d + off_msk, d + off_a, nullptr,
+                                 nullptr, nullptr, nullptr, o + 12 * N, d + off_scr) == 0 &&
+             hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(host.data(), o + 12 * N, N, hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok) wrote = png(arapio::write_png_gray8(mid_stem(q.mid_prefix, 0) + "_occ.png", w, h, host.data(), err));
+    }
+    std::vector<float> own(N * 2);
+    for (size_t k = 0; ok && wrote && k < ns; ++k) {
+        ok = upload(off_a, k) && upload(off_b, k + 1) &&
+             ArapFlow_WarpLayersStep(state, (unsigned)w, (unsigned)h, (unsigned)n, d, d + off_msk, d + off_a, d + off_b,
+                                     o + 8 * N, o + 11 * N, o, occ ? o + 12 * N : nullptr, d + off_scr) == 0 &&
+             hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(host.data(), o, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        if (!ok) break;
+        // the composite frame-1 flow: per pixel the snapshot flow of its owner, the largest l with mask_l == 0
+        for (size_t i = 0; i < N; ++i) {
+            own[2 * i] = own[2 * i + 1] = 0.f;
+            for (size_t l = n; l-- > 0;)
+                if (masks[l * N + i] == 0) {
+                    own[2 * i] = states[k][(l * N + i) * 2];
+                    own[2 * i + 1] = states[k][(l * N + i) * 2 + 1];
+                    break;
+                }
+        }
+        const std::string stem = mid_stem(q.mid_prefix, q.mid_steps[k]);
+        const uint8_t* hp = host.data();
+        wrote = arapio::write_flo(stem + ".flo", own.data(), w, h) &&
+                arapio::write_flo(stem + "_step.flo", (const float*)hp, w, h) &&
+                png(arapio::write_png_rgb(stem + ".png", w, h, hp + 8 * N, err)) &&
+                png(arapio::write_png_mask1(stem + "_mask.png", w, h, hp + 11 * N, err)) &&
+                (!occ || png(arapio::write_png_gray8(stem + "_occ.png", w, h, hp + 12 * N, err)));
+    }
+    (void)hipFree(d);
+    if (!ok) printf("ArapFlow_WarpLayersStep failed\n");
+    return ok && wrote;
 }
 
 // the layered warp of one frame, synchronously: read the layers' files, one ArapFlow_WarpLayers on the state's stream
@@ -230,6 +337,8 @@ static bool run_layers(Opt_State* state, const LayersSpec& q)
         for (size_t i = 0; i < N; ++i) masks[l * N + i] = msk.rgb[3 * i];      // red channel
         memcpy(flows.data() + l * N * 2, fl.data(), N * 8);
     }
+    if (!q.mid_steps.empty() && !run_layers_mid(state, q, rgb, masks, flows)) return false;
+    if (q.occ.empty() && q.bwd.empty() && q.occ_bwd.empty() && q.rgb2.empty() && q.mask2.empty()) return true;
     const uint64_t scr = ArapFlow_WarpLayersScratchBytes((unsigned)w, (unsigned)h, (unsigned)n);
     const size_t off_msk = 3 * N, off_flow = (off_msk + n * N + 255) / 256 * 256, off_out = off_flow + n * N * 8;
     const size_t out_bytes = 3 * N + N + 8 * N + N + N;
@@ -384,9 +493,7 @@ class Writer {
             if (!r->paths.occ.empty() && !arapio::write_png_gray8(r->paths.occ, w, h, r->occ.data(), err))
                 printf("%s\n", err.c_str());
             for (size_t k = 0; k < r->mid.size(); ++k) {
-                char tag[16];
-                snprintf(tag, sizeof(tag), "_s%02u", r->paths.mid_steps[k]);
-                const std::string stem = r->paths.mid_prefix + tag;
+                const std::string stem = mid_stem(r->paths.mid_prefix, r->paths.mid_steps[k]);
                 const MidResult& m = r->mid[k];
                 arapio::write_flo(stem + ".flo", m.flow.data(), w, h);
                 if (!arapio::write_png_rgb(stem + ".png", w, h, m.rgb.data(), err)) printf("%s\n", err.c_str());

@@ -558,3 +558,41 @@ def warp_layers(state, rgb, masks, flows, bwd=False, occ_bwd=False, occ=True):
     if occ:
         out.update(occlusion=o_occ.cpu().numpy())
     return out
+
+
+def warp_layers_step(state, rgb, masks, flows_a, flows_b, step=True, occ=True):
+    """layered in-between frames (ArapFlow_WarpLayersStep, DESIGN.md "Layered in-between frames"): the layered warp of
+    state a of the n layers, the flow from that composite to state b and the forward occlusion of that link.  rgb
+    u8[H,W,3] or None, masks u8[n,H,W] (red channels, 0 = object), flows_a / flows_b f32[n,H,W,2] (numpy) -> a dict of
+    warped_rgb (None without rgb), warped_mask and, as asked for, step f32[H,W,2], occlusion_step u8[H,W]."""
+    lib = state.lib
+    masks = np.ascontiguousarray(masks, np.uint8)
+    flows_a = np.ascontiguousarray(flows_a, np.float32)
+    flows_b = np.ascontiguousarray(flows_b, np.float32)
+    if masks.ndim != 3 or flows_a.shape != masks.shape + (2,) or flows_b.shape != flows_a.shape:
+        raise ValueError("warp_layers_step: masks [n,H,W] and flows [n,H,W,2] expected")
+    n, H, W = masks.shape
+    if rgb is not None and tuple(np.shape(rgb)) != (H, W, 3):
+        raise ValueError("warp_layers_step: rgb [H,W,3] expected")
+    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
+    d_msk = torch.from_numpy(masks).cuda()
+    d_a, d_b = torch.from_numpy(flows_a).cuda(), torch.from_numpy(flows_b).cuda()
+    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
+    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
+    o_step = torch.empty(H, W, 2, dtype=torch.float32, device="cuda") if step else None
+    o_occ = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occ else None
+    scratch = torch.empty(int(lib.ArapFlow_WarpLayersStepScratchBytes(W, H, n)), dtype=torch.uint8, device="cuda")
+    p = lambda t: _dev_ptr(t) if t is not None else None
+    torch.cuda.synchronize()
+    rc = lib.ArapFlow_WarpLayersStep(state.handle, W, H, n, p(d_rgb), p(d_msk), p(d_a), p(d_b), p(o_rgb), p(o_msk),
+                                     p(o_step), p(o_occ), p(scratch))
+    if rc != 0:
+        raise (ValueError("ArapFlow_WarpLayersStep: bad arguments") if rc == -1 else
+               RuntimeError("ArapFlow_WarpLayersStep failed: %d" % rc))
+    torch.cuda.synchronize()
+    out = dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy())
+    if step:
+        out.update(step=o_step.cpu().numpy())
+    if occ:
+        out.update(occlusion_step=o_occ.cpu().numpy())
+    return out

@@ -6,6 +6,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   SolveLine, parse_line, format_line, done_token, read_list_items    the list line: a solve (6 paths, optional output
                             tokens bwd= occ= occ_bwd= mid=) or the `layers` line, the layered warp of one frame (addition)
   parse_mid, mid_token, mid_files, mid_steps    the mid= token: in-between frames from the constraint ramp (addition)
+  mid_layer_files, owner_flow, run_layers_mid   a layers line's mid= token: layered in-between frames (addition)
   deform_list, run_layers   ARAP/deformation/src/main.cpp:162-241  (arap_deform over a list)
   warp_files                ARAP/warping/src/main.cpp:302-336      (warp_image)
   cover_scale, fit_bg, add_bg            para_gen.py:36-61      (background compositing)
@@ -40,7 +41,7 @@ _ANTIALIAS = getattr(Image, "LANCZOS", None) or Image.ANTIALIAS   # Image.ANTIAL
 EXTRA_KEYS = ("bwd", "occ", "occ_bwd", "mid")
 MAX_SNAPSHOTS = 8            # ARAPFLOW_MAX_SNAPSHOTS of include/arap_opt.h
 LAYERS_WORD = "layers"
-LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2")
+LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2", "mid")
 
 
 class SolveLine(NamedTuple):
@@ -83,6 +84,13 @@ def mid_files(prefix, step):
     return dict(flow=stem + ".flo", rgb=stem + ".png", mask=stem + "_mask.png", step=stem + "_step.flo")
 
 
+def mid_layer_files(prefix, step):
+    """the files a `layers` line's mid= token writes BESIDE mid_files' four: `occ`, the occlusion of the link that
+    starts at the snapshot after ramp step `step` (DESIGN.md "Layered in-between frames"); step 0 is frame 1 itself,
+    the link frame 1 -> first snapshot"""
+    return dict(occ="%s_s%02d_occ.png" % (prefix, step))
+
+
 def mid_steps(K, num_iter):
     """para_gen --mid K: K ramp steps spread evenly over the ramp, (i * num_iter) // (K + 1) for i = 1 .. K; they must be
     distinct and >= 1 (19 and K = 3: 4, 9, 14)"""
@@ -114,7 +122,7 @@ def extra_tokens(extra):
 
 def parse_layers(tokens):
     """a `layers` line (DESIGN.md "Layered warp"), recognised by its first word:
-        layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P]
+        layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P] [mid=I1,I2,..:PREFIX]
     -> dict(rgb, layers=[(mask, flo)] in layer order (the later on top), out={key: path} in line order).  At least one
     output; anything else after the layers is an error (a new line form has no old meaning to keep)."""
     if len(tokens) < 3 or tokens[0] != LAYERS_WORD:
@@ -130,6 +138,8 @@ def parse_layers(tokens):
         k, eq, v = t.partition("=")
         if not (eq and k in LAYER_KEYS and v):
             raise ValueError("layers line: bad output token %r" % t)
+        if k == "mid":
+            parse_mid(v)
         out[k] = v
     if not out:
         raise ValueError("layers line without an output: %r" % " ".join(tokens))
@@ -172,7 +182,8 @@ def read_list_items(path):
 
 def run_layers(state, spec):
     """one `layers` line: read the frame's RGB and every layer's mask / flow, one opt.warp_layers, write what the line
-    asks for (occ / occ_bwd: 8-bit L PNG; bwd: .flo; rgb2: RGB PNG; mask2: 1-bit PNG as a solve's warped mask)"""
+    asks for (occ / occ_bwd: 8-bit L PNG; bwd: .flo; rgb2: RGB PNG; mask2: 1-bit PNG as a solve's warped mask; mid:
+    run_layers_mid)"""
     from . import opt
     rgb = load_rgb(spec["rgb"])
     masks = [load_mask_red(m) for m, _ in spec["layers"]]
@@ -181,6 +192,10 @@ def run_layers(state, spec):
         if m.shape != rgb.shape[:2] or f.shape[:2] != rgb.shape[:2]:
             raise ValueError("layers line: image, mask and flow sizes differ")
     out = spec["out"]
+    if "mid" in out:
+        run_layers_mid(state, spec, rgb, np.stack(masks), np.stack(flows))
+    if not set(out) - {"mid"}:
+        return
     r = opt.warp_layers(state, rgb, np.stack(masks), np.stack(flows), bwd="bwd" in out, occ_bwd="occ_bwd" in out,
                         occ="occ" in out)
     if "rgb2" in out:
@@ -193,6 +208,55 @@ def run_layers(state, spec):
         save_occ(r["occlusion_bwd"], out["occ_bwd"])
     if "occ" in out:
         save_occ(r["occlusion"], out["occ"])
+
+
+def owner_flow(masks, flows):
+    """the composite frame-1 flow of n layers, masks (n, H, W) red channels and flows (n, H, W, 2): per frame-1 pixel v
+    the flow of owner(v), the largest l with masks[l][v] == 0, and (0, 0) where no layer owns v.  The owner rule of
+    the layered warp -- not the warped-mask selection merge_segments keeps for a frame's final .flo."""
+    obj = np.asarray(masks) == 0
+    n = obj.shape[0]
+    top = (n - 1) - np.argmax(obj[::-1], axis=0)
+    flow = np.take_along_axis(np.asarray(flows, np.float32), top[None, ..., None], axis=0)[0]
+    flow[~obj.any(0)] = 0
+    return flow
+
+
+def run_layers_mid(state, spec, rgb, masks, flows):
+    """the mid= token of a `layers` line (DESIGN.md "Layered in-between frames").  Layer l's state after ramp step i is
+    the file mid_files(stem_l, i)["flow"], stem_l = FLO_l without its `.flo`; after the last snapshot comes the layers'
+    final flow.  Per snapshot one opt.warp_layers_step, written as mid_files(PREFIX, i): the owner_flow of the snapshot,
+    the composite in-between frame and mask, the step flow; with occ= on the line also the link occlusions of
+    mid_layer_files, steps 0 (frame 1 -> first snapshot, opt.warp_layers' occlusion) and i."""
+    from . import opt
+    out = spec["out"]
+    steps, prefix = parse_mid(out["mid"])
+    states = []
+    for i in steps:
+        per = []
+        for _, f in spec["layers"]:
+            if not f.endswith(".flo"):
+                raise ValueError("layers line: mid= needs flows named *.flo, got %s" % f)
+            snap = mid_files(f[:-4], i)["flow"]
+            if not osp.exists(snap):
+                raise ValueError("layers line: snapshot %s is missing" % snap)
+            per.append(flo.flow_read(snap))
+            if per[-1].shape != flows[0].shape:
+                raise ValueError("layers line: %s differs in size from %s" % (snap, spec["rgb"]))
+        states.append(np.stack(per))
+    states.append(flows)
+    occ = "occ" in out
+    if occ:
+        save_occ(opt.warp_layers(state, None, masks, states[0])["occlusion"], mid_layer_files(prefix, 0)["occ"])
+    for k, i in enumerate(steps):
+        r = opt.warp_layers_step(state, rgb, masks, states[k], states[k + 1], step=True, occ=occ)
+        f = mid_files(prefix, i)
+        flo.flow_write(f["flow"], owner_flow(masks, states[k]))
+        Image.fromarray(r["warped_rgb"]).save(f["rgb"])
+        save_mask(r["warped_mask"], f["mask"])
+        flo.flow_write(f["step"], r["step"])
+        if occ:
+            save_occ(r["occlusion_step"], mid_layer_files(prefix, i)["occ"])
 
 
 def save_occ(occ, path):

@@ -340,6 +340,25 @@ int ArapFlow_WarpLayers(Opt_State* state, unsigned W, unsigned H, unsigned n, co
                         const void* flows, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd,
                         void* out_occ, void* scratch);
 
+/* Layered in-between frames (DESIGN.md "Layered in-between frames"): the layered warp of a state a of all n layers, the
+ * flow from that composite frame to a second state b and the forward occlusion of that link, on DEVICE buffers laid out
+ * as in ArapFlow_WarpLayers; flows_a, flows_b float[n][H][W][2] are the layers' two states as flows.  Outputs, each
+ * NULL when not wanted: out_rgb / out_mask, ArapFlow_WarpLayers' of flows_a; out_step float[H][W][2], per covered pixel
+ * q of the composite the point d(q) of state b of the winner's layer, interpolated with the rasteriser's barycentrics
+ * of state a, minus q, and 0 where nothing is drawn (n = 1: ArapFlow_WarpStep's out_step; flows_b = 0:
+ * ArapFlow_WarpLayers' out_bwd); out_occ uint8[H][W], 255 where what pixel q shows is hidden in the next frame: d(q)
+ * leaves the frame, or a triangle of a higher layer, or a triangle of the same layer later than every triangle that
+ * shares a corner with the winner, is drawn over d(q) in state b; for an uncovered q, where state b draws anything at
+ * q.  Lower layers never occlude.  With out_step == out_occ == NULL the call does ArapFlow_WarpLayers' work for RGB
+ * and mask.
+ * `scratch`: 256-byte aligned device buffer of ArapFlow_WarpLayersStepScratchBytes(W, H, n) bytes (48 per pixel).
+ * Asynchronous on the state's stream.  Returns 0; -1 on bad arguments: n = 0, n > 255, no output at all, out_rgb
+ * without rgb, W * H >= 2^31, or out_occ with W * H > 2^24; else a HIP error code. */
+uint64_t ArapFlow_WarpLayersStepScratchBytes(unsigned W, unsigned H, unsigned n);
+int ArapFlow_WarpLayersStep(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* rgb,
+                            const void* masks_red, const void* flows_a, const void* flows_b, void* out_rgb,
+                            void* out_mask, void* out_step, void* out_occ, void* scratch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 """para_gen -- Python 3 twin of the reference's dataset generator CLI (para_gen.py:341-653), same flags.
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
-                     [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K]
+                     [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -66,6 +66,17 @@ def mid_paths(p):
     if "mid_gen" not in p:
         return []
     return [pipeline.mid_files(p["mid_gen"], i)[k] for i in p["_mid"] for k in ("flow", "rgb", "mask", "step")]
+
+
+def mid_layer_paths(p):
+    """--mid_layers: every layered in-between file of a pair's path table: per step mid_files' four, then -- with
+    --occ_layers -- the link occlusions of pipeline.mid_layer_files, step 0 first; [] without"""
+    if "midl_gen" not in p:
+        return []
+    out = [pipeline.mid_files(p["midl_gen"], i)[k] for i in p["_midl"] for k in ("flow", "rgb", "mask", "step")]
+    if LAYERS_OCC in p:
+        out += [pipeline.mid_layer_files(p["midl_gen"], i)["occ"] for i in (0,) + tuple(p["_midl"])]
+    return out
 
 
 def _pair_id(seq, stem):
@@ -151,6 +162,7 @@ def prepare_pair(args):
     seq, stem = p.pop("_seq"), p.pop("_stem")
     line = pipeline.make_arap_path(p)
     p.pop("_mid", None)
+    midl = p.pop("_midl", None)                 # --mid_layers: the snapshot steps of every segment's solve
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
     im1, mk1, im2, mk2 = preprocess(p, flags.size)
@@ -189,14 +201,31 @@ def prepare_pair(args):
             p_ = pipeline.replace_ext(p, s, keep_orgs=["rgb1_gen", "cstr_tmp"])
             Image.fromarray(mask).save(p_["msk1_gen"])
             segs.append(pipeline.make_arap_path(p_))
+            if midl:                            # the segment's snapshots lie beside its flow: <flow without .flo>_sII*
+                segs[-1].extra["mid"] = pipeline.mid_token(midl, segs[-1].flow[:-len(".flo")])
     layers = None
-    if segs and LAYERS_OCC in p:            # the frame's layers line: segments in list order = ascending label, later on top
-        layers = dict(rgb=line.rgb, layers=[(sg.mask, sg.flow) for sg in segs], out=dict(occ=p[LAYERS_OCC]))
+    if segs and (LAYERS_OCC in p or midl):  # the frame's layers line: segments in list order (ascending label, later on top)
+        out = dict(occ=p[LAYERS_OCC]) if LAYERS_OCC in p else {}
+        if midl:
+            out["mid"] = pipeline.mid_token(midl, p["midl_gen"])
+        layers = dict(rgb=line.rgb, layers=[(sg.mask, sg.flow) for sg in segs], out=out)
     return Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
 
 
 def finish_frame(rec):
     """para_gen.py:202-212 for one Frame whose solve(s) are done: flatten the segments, composite the background"""
+    if rec.layers is not None and "mid" in rec.layers["out"]:       # --mid_layers: the layers line is done
+        steps, prefix = pipeline.parse_mid(rec.layers["out"]["mid"])
+        if rec.bg is not None:                              # the in-between frames get the pair's background too
+            for f in (pipeline.mid_files(prefix, i) for i in steps):
+                im, m = np.array(Image.open(f["rgb"]).convert("RGB")), np.array(Image.open(f["mask"]))
+                Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(f["rgb"])
+        if rec.remove:                                      # the segments' snapshot files have been merged
+            for sg in rec.segs:
+                for i in steps:
+                    for q in pipeline.mid_files(sg.flow[:-len(".flo")], i).values():
+                        if osp.exists(q):
+                            os.remove(q)
     if rec.segs is not None:
         if rec.line.extra:                                  # (before flatten removes the segments' warped masks)
             pipeline.flatten_backward(rec.line, rec.segs, remove=rec.remove)
@@ -412,9 +441,14 @@ def scan(flags, input_root, output_root):
                     e["mid_gen"] = osp.join(roots["mid"], seq, f)
                 e = {k: osp.abspath(v) for k, v in e.items()}
                 e["_seq"], e["_stem"] = seq, f
+                if getattr(flags, "mid_layers", 0):
+                    e["midl_gen"] = osp.abspath(osp.join(roots["mid"], seq, f))
                 if "mid_gen" in e:
                     e["_mid"] = tuple(flags.mid_steps)
-                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e)    # every requested output
+                if "midl_gen" in e:
+                    e["_midl"] = tuple(flags.mid_layers_steps)
+                # every requested output
+                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e)
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -463,7 +497,7 @@ def main(flags):
     for p in all_paths:
         ln = pipeline.make_arap_path(p)
         lmdb_paths.append([ln.rgb, ln.out_rgb, ln.flow])
-        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p))
+        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p))
 
     # backgrounds: drawn without replacement until the list is used up, then refilled (para_gen.py:484-499)
     tmp_paths, picks = [], []
@@ -543,8 +577,9 @@ def main(flags):
                 p.kill()
     out_paths = [" ".join(ln) for ln in lmdb_paths if all(osp.exists(q) for q in ln)]    # :588-603
     open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
+    # all_files.list stays as it is; the extra outputs get their own list
     if (getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False) or
-            getattr(flags, "mid", 0)):                      # all_files.list stays as it is; the extra outputs get their own list
+            getattr(flags, "mid", 0) or getattr(flags, "mid_layers", 0)):
         ext = [" ".join(ln) for ln in ext_paths if all(osp.exists(q) for q in ln)]
         open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     dt = time.time() - t_start
@@ -619,6 +654,11 @@ def parse(argv=None):
                         help="also write K in-between frames per pair, from K ramp steps spread evenly over the solve's "
                              "constraint ramp: OUT/Mid/<seq>/<frame>_sII{.flo,.png,_mask.png,_step.flo} (DESIGN.md "
                              "\"In-between frames\")")
+    parser.add_argument("--mid_layers", type=int, default=0, metavar="K",
+                        help="with --multseg: also write K layered in-between frames per pair, merged from every "
+                             "segment's ramp snapshots by one layered pass per snapshot: OUT/Mid/<seq>/<frame>_sII"
+                             "{.flo,.png,_mask.png,_step.flo}; with --occ_layers also the link occlusions "
+                             "<frame>_s00_occ.png, <frame>_sII_occ.png (DESIGN.md \"Layered in-between frames\")")
     parser.add_argument("--keep_segments", action="store_true", default=False,
                         help="with --multseg: keep the per-segment files after they are merged (for inspection)")
     flags = parser.parse_args(argv)
@@ -638,12 +678,23 @@ def parse(argv=None):
     if flags.mid:
         if flags.multseg:
             parser.error("--mid cannot be combined with --multseg: merging the segments' in-between states is a "
-                         "separate piece of work")
+                         "separate piece of work, which --multseg --mid_layers K does")
         if not own_arap_bin(flags.arap_bin):
             parser.error("--mid needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
                          "not know the mid= token")
         try:
             flags.mid_steps = pipeline.mid_steps(flags.mid, NUM_ITER)
+        except ValueError as e:
+            parser.error(str(e))
+    flags.mid_layers_steps = []
+    if flags.mid_layers:
+        if not flags.multseg:
+            parser.error("--mid_layers needs --multseg (a single-object run takes --mid)")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--mid_layers needs this repository's arap_deform (C++ or arap_deform.py): a foreign "
+                         "--arap_bin does not know the layers line")
+        try:
+            flags.mid_layers_steps = pipeline.mid_steps(flags.mid_layers, NUM_ITER)
         except ValueError as e:
             parser.error(str(e))
     if flags.size is not None:
