@@ -40,13 +40,21 @@ static WarpScratch warp_scratch(uint64_t W, uint64_t H, int parts)
     return L;
 }
 
-// point a job at its scratch; returns where the job itself goes on the device
-static WarpJob* warp_job_scratch(WarpJob& j, const WarpScratch& L, void* scratch)
+// The start of every call on caller-owned images: point the job (inputs and outputs filled in by the caller) at its
+// scratch, clear the key image and -- `clear_cells`: the layered calls, when the occlusion map is asked; the
+// single-layer chain clears them itself, in enqueue_warp_outputs, as it does for the frame solver -- the cell counts,
+// upload the job.  Returns where the job is on the device.
+static WarpJob* warp_job_begin(hipStream_t stream, WarpJob& j, const WarpScratch& L, void* scratch, size_t N,
+                               bool clear_cells)
 {
     char* c = (char*)scratch;
     j.key = (unsigned long long*)(c + L.key);
     if (L.rank != L.cell) { j.cell = (unsigned*)(c + L.cell); j.rank = (unsigned*)(c + L.rank); j.bin = (int4*)(c + L.bin); }
-    return (WarpJob*)(c + L.job);
+    WarpJob* dj = (WarpJob*)(c + L.job);
+    HC(hipMemsetAsync(j.key, 0, N * 8, stream));
+    if (clear_cells) HC(hipMemsetAsync(j.cell, 0, 4 * (N + 1), stream));
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, stream));
+    return dj;
 }
 
 // rasterise `njobs` jobs at `dj`, write the optional outputs (ARAPFLOW_OUT_* bits) and, for jobs with a second field
@@ -61,24 +69,55 @@ static void enqueue_warp(hipStream_t stream, const WarpJob* dj, unsigned njobs, 
     hipLaunchKernelGGL(k_warp_resolve, dim3((N + 255) / 256, 1, njobs), dim3(256), 0, stream, dj, N);
 }
 
-// one flow-field warp with a scratch buffer of warp_scratch(W, H, parts) bytes
+// one single-layer warp of a flow field (and, with `flow_b`, the step towards a second one) with a scratch buffer of
+// `L` bytes: the body of ArapFlow_Warp / WarpEx / WarpStep
 static int warp_flow(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* mask_red, const void* flow,
-                     void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ, void* scratch,
-                     int parts)
+                     const void* flow_b, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ,
+                     void* out_step, void* scratch, const WarpScratch& L)
 {
-    const size_t N = (size_t)W * H;
     WarpJob j{};
-    j.field = nullptr; j.flow_in = (const float2*)flow;
+    j.flow_in = (const float2*)flow; j.flow_b = (const float2*)flow_b;
     j.rgb = (const uint8_t*)rgb; j.mask = (const uint8_t*)mask_red;
-    j.flow_out = nullptr;
     j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
     j.bwd = (float2*)out_bwd; j.occ_bwd = (uint8_t*)out_occ_bwd; j.occ = (uint8_t*)out_occ;
-    WarpJob* dj = warp_job_scratch(j, warp_scratch(W, H, parts), scratch);
+    j.step = (float2*)out_step;
+    const size_t N = (size_t)W * H;
+    const WarpJob* dj = warp_job_begin(st->stream, j, L, scratch, N, false);
     const int outputs = (out_bwd || out_occ_bwd ? ARAPFLOW_OUT_BACKWARD : 0) | (out_occ ? ARAPFLOW_OUT_OCCLUSION : 0);
-    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
-    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
-    enqueue_warp(st->stream, dj, 1, (int)W, (int)H, outputs, j.cell, 4 * (N + 1));
+    enqueue_warp(st->stream, dj, 1, (int)W, (int)H, outputs, j.cell, 4 * (N + 1), out_step != nullptr);
     return (int)hipGetLastError();
+}
+
+// The layered chain, stated once:  k_layers_raster (layers placed by `raster`) -> `pixel_pass`, the call's own passes per
+// pixel of the key image -> [k_occ_scan -> `scatter` -> k_layers_tri (layers placed by `query`)] -> k_warp_resolve.
+// The bracket runs when the occlusion map is asked; by then the pixel pass has counted the query points into the cells.
+// pixel_pass and scatter are called with the per-pixel grid.
+template <class PixelPass, class Scatter>
+static int enqueue_layers(hipStream_t stream, const WarpJob* dj, const LayerSet& raster, const LayerSet& query, unsigned W,
+                          unsigned H, bool occ, PixelPass pixel_pass, Scatter scatter)
+{
+    const int N = (int)(W * H);
+    const dim3 g1((unsigned)((N + 255) / 256)), g2((W + 63) / 64, (H + 3) / 4, (unsigned)raster.n);
+    hipLaunchKernelGGL(k_layers_raster, g2, dim3(64, 4), 0, stream, dj, raster, (int)W, (int)H);
+    pixel_pass(g1);
+    if (occ) {
+        hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, 1), dim3(1024), 0, stream, dj, N);
+        scatter(g1);
+        hipLaunchKernelGGL(k_layers_tri, g2, dim3(64, 4), 0, stream, dj, query, (int)W, (int)H);
+    }
+    hipLaunchKernelGGL(k_warp_resolve, g1, dim3(256), 0, stream, dj, N);
+    return (int)hipGetLastError();
+}
+
+// what the two layered calls ask of their arguments alike; the limits are the key's and the bin's field widths
+// (arap_warp.h, arap_occ.h)
+static bool layers_args_ok(const Opt_State* st, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                           const void* flows, const void* out_rgb, const void* out_occ, const void* scratch)
+{
+    if (!st || !masks_red || !flows || !scratch || W == 0 || H == 0 || n == 0 || n > 255) return false;
+    if (out_rgb && !rgb) return false;
+    const uint64_t N = (uint64_t)W * H;
+    return N < (1ull << 31) && !(out_occ && N > (1ull << 24));
 }
 
 extern "C" {
@@ -89,7 +128,8 @@ int ArapFlow_Warp(Opt_State* st, unsigned W, unsigned H, const void* rgb, const 
                   void* out_rgb, void* out_mask, void* scratch)
 {
     if (!st || !mask_red || !flow || !out_mask || !scratch) return -1;
-    return warp_flow(st, W, H, rgb, mask_red, flow, out_rgb, out_mask, nullptr, nullptr, nullptr, scratch, 0);
+    return warp_flow(st, W, H, rgb, mask_red, flow, nullptr, out_rgb, out_mask, nullptr, nullptr, nullptr, nullptr, scratch,
+                     warp_scratch(W, H, 0));
 }
 
 uint64_t ArapFlow_WarpExScratchBytes(unsigned W, unsigned H) { return warp_scratch(W, H, WARP_OCC).total; }
@@ -98,7 +138,8 @@ int ArapFlow_WarpEx(Opt_State* st, unsigned W, unsigned H, const void* rgb, cons
                     void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd, void* out_occ, void* scratch)
 {
     if (!st || !mask_red || !flow || !out_mask || !scratch || W == 0 || H == 0) return -1;
-    return warp_flow(st, W, H, rgb, mask_red, flow, out_rgb, out_mask, out_bwd, out_occ_bwd, out_occ, scratch, WARP_OCC);
+    return warp_flow(st, W, H, rgb, mask_red, flow, nullptr, out_rgb, out_mask, out_bwd, out_occ_bwd, out_occ, nullptr,
+                     scratch, warp_scratch(W, H, WARP_OCC));
 }
 
 int ArapFlow_WarpStep(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* mask_red, const void* flow_a,
@@ -108,19 +149,11 @@ int ArapFlow_WarpStep(Opt_State* st, unsigned W, unsigned H, const void* rgb, co
     if (out_rgb && !rgb) return -1;
     if ((uint64_t)W * H >= (1ull << 31)) return -1;                              // (the key's triangle index)
     HC(hipSetDevice(st->device));
-    const size_t N = (size_t)W * H;
     const WarpScratch L = warp_scratch(W, H, 0);
     void* scratch = nullptr;                 // the call owns its scratch: it returns when the outputs are written
     if (hipMalloc(&scratch, L.total) != hipSuccess) return (int)hipErrorOutOfMemory;
-    WarpJob j{};
-    j.flow_in = (const float2*)flow_a; j.flow_b = (const float2*)flow_b;
-    j.rgb = (const uint8_t*)rgb; j.mask = (const uint8_t*)mask_red;
-    j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask; j.step = (float2*)out_step;
-    WarpJob* dj = warp_job_scratch(j, L, scratch);
-    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
-    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
-    enqueue_warp(st->stream, dj, 1, (int)W, (int)H, 0, nullptr, 0, true);
-    const int rc = (int)hipGetLastError();
+    const int rc = warp_flow(st, W, H, rgb, mask_red, flow_a, flow_b, out_rgb, out_mask, nullptr, nullptr, nullptr,
+                             out_step, scratch, L);
     HC(hipStreamSynchronize(st->stream));
     HC(hipFree(scratch));
     return rc;
@@ -136,36 +169,25 @@ int ArapFlow_WarpLayers(Opt_State* st, unsigned W, unsigned H, unsigned n, const
                         const void* flows, void* out_rgb, void* out_mask, void* out_bwd, void* out_occ_bwd,
                         void* out_occ, void* scratch)
 {
-    if (!st || !masks_red || !flows || !scratch || W == 0 || H == 0 || n == 0 || n > 255) return -1;
+    if (!layers_args_ok(st, W, H, n, rgb, masks_red, flows, out_rgb, out_occ, scratch)) return -1;
     if (!out_rgb && !out_mask && !out_bwd && !out_occ_bwd && !out_occ) return -1;
-    if (out_rgb && !rgb) return -1;
-    const uint64_t N64 = (uint64_t)W * H;
-    if (N64 >= (1ull << 31) || (out_occ && N64 > (1ull << 24))) return -1;      // key / bin field widths (arap_layers.h)
-    const size_t N = (size_t)N64;
     const WarpScratch L = warp_scratch(W, H, WARP_OCC | WARP_OWNER);
     WarpJob j{};
     j.rgb = (const uint8_t*)rgb;
     j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
     j.bwd = (float2*)out_bwd; j.occ_bwd = (uint8_t*)out_occ_bwd; j.occ = (uint8_t*)out_occ;
-    WarpJob* dj = warp_job_scratch(j, L, scratch);
     LayerSet ls{};
     ls.masks = (const uint8_t*)masks_red; ls.flows = (const float2*)flows; ls.n = (int)n;
     ls.owner = (uint8_t*)scratch + L.owner;
-    const dim3 g1((unsigned)((N + 255) / 256)), g2((W + 63) / 64, (H + 3) / 4, n);
-    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
-    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
-    hipLaunchKernelGGL(k_layers_raster, g2, dim3(64, 4), 0, st->stream, dj, ls, (int)W, (int)H);
-    if (out_bwd || out_occ_bwd || out_occ)
-        hipLaunchKernelGGL(k_layers_keys, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)N);
-    if (out_occ) {
-        HC(hipMemsetAsync(j.cell, 0, 4 * (N + 1), st->stream));
-        hipLaunchKernelGGL(k_layers_count, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)H, (int)N);
-        hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, 1), dim3(1024), 0, st->stream, dj, (int)N);
-        hipLaunchKernelGGL(k_layers_scatter, g1, dim3(256), 0, st->stream, dj, ls, (int)W, (int)H, (int)N);
-        hipLaunchKernelGGL(k_layers_tri, g2, dim3(64, 4), 0, st->stream, dj, ls, (int)W, (int)H);
-    }
-    hipLaunchKernelGGL(k_layers_resolve, g1, dim3(256), 0, st->stream, dj, (int)N);
-    return (int)hipGetLastError();
+    hipStream_t stream = st->stream;
+    const int iW = (int)W, iH = (int)H, N = iW * iH;
+    const WarpJob* dj = warp_job_begin(stream, j, L, scratch, (size_t)N, out_occ != nullptr);
+    return enqueue_layers(stream, dj, ls, ls, W, H, out_occ != nullptr,
+        [&](dim3 g1) {
+            if (out_bwd || out_occ_bwd || out_occ) hipLaunchKernelGGL(k_layers_keys, g1, dim3(256), 0, stream, dj, ls, iW, N);
+            if (out_occ) hipLaunchKernelGGL(k_layers_count, g1, dim3(256), 0, stream, dj, ls, iW, iH, N);
+        },
+        [&](dim3 g1) { hipLaunchKernelGGL(k_layers_scatter, g1, dim3(256), 0, stream, dj, ls, iW, iH, N); });
 }
 
 // per pixel: 8 (key) + 4 (cell) + 4 (rank) + 16 (bin) + 16 (query point) = 48 bytes, however many layers
@@ -179,36 +201,26 @@ int ArapFlow_WarpLayersStep(Opt_State* st, unsigned W, unsigned H, unsigned n, c
                             const void* flows_a, const void* flows_b, void* out_rgb, void* out_mask, void* out_step,
                             void* out_occ, void* scratch)
 {
-    if (!st || !masks_red || !flows_a || !flows_b || !scratch || W == 0 || H == 0 || n == 0 || n > 255) return -1;
+    if (!layers_args_ok(st, W, H, n, rgb, masks_red, flows_a, out_rgb, out_occ, scratch) || !flows_b) return -1;
     if (!out_rgb && !out_mask && !out_step && !out_occ) return -1;
-    if (out_rgb && !rgb) return -1;
-    const uint64_t N64 = (uint64_t)W * H;
-    if (N64 >= (1ull << 31) || (out_occ && N64 > (1ull << 24))) return -1;      // key / query point field widths
-    const size_t N = (size_t)N64;
     const WarpScratch L = warp_scratch(W, H, WARP_OCC | WARP_PTS);
     WarpJob j{};
     j.rgb = (const uint8_t*)rgb;
     j.out_rgb = (uint8_t*)out_rgb; j.out_mask = (uint8_t*)out_mask;
     j.step = (float2*)out_step; j.occ = (uint8_t*)out_occ;
-    WarpJob* dj = warp_job_scratch(j, L, scratch);
     int4* pts = (int4*)((char*)scratch + L.pts);
     LayerSet la{}, lb{};                     // the layers placed by a and by b: the same masks
     la.masks = lb.masks = (const uint8_t*)masks_red; la.n = lb.n = (int)n;
     la.flows = (const float2*)flows_a; lb.flows = (const float2*)flows_b;
-    const dim3 g1((unsigned)((N + 255) / 256)), g2((W + 63) / 64, (H + 3) / 4, n);
-    HC(hipMemsetAsync(j.key, 0, N * 8, st->stream));
-    if (out_occ) HC(hipMemsetAsync(j.cell, 0, 4 * (N + 1), st->stream));
-    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));
-    hipLaunchKernelGGL(k_layers_raster, g2, dim3(64, 4), 0, st->stream, dj, la, (int)W, (int)H);
-    if (out_step || out_occ)
-        hipLaunchKernelGGL(k_lstep_step, g1, dim3(256), 0, st->stream, dj, la, lb.flows, pts, (int)W, (int)H, (int)N);
-    if (out_occ) {
-        hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, 1), dim3(1024), 0, st->stream, dj, (int)N);
-        hipLaunchKernelGGL(k_lstep_scatter, g1, dim3(256), 0, st->stream, dj, pts, (int)W, (int)H, (int)N);
-        hipLaunchKernelGGL(k_layers_tri, g2, dim3(64, 4), 0, st->stream, dj, lb, (int)W, (int)H);
-    }
-    hipLaunchKernelGGL(k_layers_resolve, g1, dim3(256), 0, st->stream, dj, (int)N);
-    return (int)hipGetLastError();
+    hipStream_t stream = st->stream;
+    const int iW = (int)W, iH = (int)H, N = iW * iH;
+    const WarpJob* dj = warp_job_begin(stream, j, L, scratch, (size_t)N, out_occ != nullptr);
+    return enqueue_layers(stream, dj, la, lb, W, H, out_occ != nullptr,
+        [&](dim3 g1) {
+            if (out_step || out_occ)
+                hipLaunchKernelGGL(k_lstep_step, g1, dim3(256), 0, stream, dj, la, lb.flows, pts, iW, iH, N);
+        },
+        [&](dim3 g1) { hipLaunchKernelGGL(k_lstep_scatter, g1, dim3(256), 0, stream, dj, pts, iW, iH, N); });
 }
 
 }  // extern "C"

@@ -25,18 +25,13 @@ __device__ __forceinline__ float2 warp_pos_b(const WarpJob& j, int x, int y, int
 // (never: it passed there)
 __device__ __forceinline__ bool tri_transfer_point(const WarpJob& j, int W, unsigned t, int qx, int qy, float2& d)
 {
-    const int u = (int)(t >> 1);
-    const int uy = u / W, ux = u - uy * W;
-    // corners of triangle t and their grid coordinates: 2u = (p00, p01, p10), 2u+1 = (p10, p01, p11)
-    const int odd = (int)(t & 1u);
-    const int ax = ux, ay = uy + odd, bx = ux + 1, by = uy, cx = ux + odd, cy = uy + 1;
-    const int i0 = ax + W * ay, i1 = bx + W * by, i2 = cx + W * cy;
-    const float2 p0 = warp_pos(j, ax, ay, i0), p1 = warp_pos(j, bx, by, i1), p2 = warp_pos(j, cx, cy, i2);
+    const TriCorners c = tri_corners(t, W);
     float b0, b1, b2;
-    if (!tri_bary(p0, p1, p2, (float)qx, (float)qy, b0, b1, b2)) return false;
-    const float2 d0 = warp_pos_b(j, ax, ay, i0), d1 = warp_pos_b(j, bx, by, i1), d2 = warp_pos_b(j, cx, cy, i2);
-    d.x = (d0.x * b0 + d1.x * b1) + d2.x * b2;
-    d.y = (d0.y * b0 + d1.y * b1) + d2.y * b2;
+    if (!tri_bary_at(j, c, (float)qx, (float)qy, b0, b1, b2)) return false;
+    const float2 d0 = warp_pos_b(j, c.x[0], c.y[0], c.i[0]), d1 = warp_pos_b(j, c.x[1], c.y[1], c.i[1]);
+    const float2 d2 = warp_pos_b(j, c.x[2], c.y[2], c.i[2]);
+    d.x = bary_mix(d0.x, d1.x, d2.x, b0, b1, b2);
+    d.y = bary_mix(d0.y, d1.y, d2.y, b0, b1, b2);
     return true;
 }
 
@@ -64,7 +59,7 @@ __global__ __launch_bounds__(256) void k_warp_step(const WarpJob* jobs, int W, i
     if (i >= N || !j.step) return;
     const unsigned long long k = j.key[i];
     const int qy = i / W, qx = i - qy * W;
-    j.step[i] = k ? tri_transfer(j, W, (unsigned)(k >> 32) - 1u, qx, qy) : make_float2(0.f, 0.f);
+    j.step[i] = k ? tri_transfer(j, W, key_winner(k).tri, qx, qy) : make_float2(0.f, 0.f);
 }
 
 }  // namespace arap

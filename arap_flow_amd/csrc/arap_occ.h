@@ -6,18 +6,13 @@
 //
 // Order on the stream:  k_warp_raster -> k_warp_keys -> [k_occ_count -> k_occ_scan -> k_occ_scatter -> k_occ_tri]
 //                       -> k_warp_resolve (which clears the keys k_warp_keys reads).
+// Limits: N < 2^31 (a binned vertex carries its index in a full int); the layered query (arap_layers.h) packs
+// v | l << 24 into the same field and so has N <= 2^24.  Both packings and both "does this triangle test this point"
+// rules are stated once here, in bin_payload / bin_index / bin_tested.
 #pragma once
 #include "arap_warp.h"
 
 namespace arap {
-
-// quad (qx, qy) is rasterised iff it lies in the grid and its four corners are object (k_warp_raster)
-__device__ __forceinline__ bool quad_on(const uint8_t* mask, int W, int H, int qx, int qy)
-{
-    if (qx < 0 || qy < 0 || qx + 1 >= W || qy + 1 >= H) return false;
-    const size_t i = qx + (size_t)W * qy;
-    return mask[i] == 0 && mask[i + 1] == 0 && mask[i + W] == 0 && mask[i + W + 1] == 0;
-}
 
 // m(v): the largest index of a rasterised triangle with vertex (x, y) as a corner, or -1.  The vertex is p00 of quad
 // (x,y) (triangle 2u only), p01 of quad (x-1,y) and p10 of quad (x,y-1) (both triangles), p11 of quad (x-1,y-1)
@@ -37,22 +32,25 @@ __device__ __forceinline__ bool in_frame(float2 P, int W, int H)
     return P.x >= 0.f && P.x <= (float)(W - 1) && P.y >= 0.f && P.y <= (float)(H - 1);     // false on NaN
 }
 
+// tri_bary of the triangle with corners c, placed by the job's (first) field, at the point (sx, sy)
+__device__ __forceinline__ bool tri_bary_at(const WarpJob& j, const TriCorners& c, float sx, float sy, float& b0, float& b1,
+                                            float& b2)
+{
+    const float2 p0 = warp_pos(j, c.x[0], c.y[0], c.i[0]), p1 = warp_pos(j, c.x[1], c.y[1], c.i[1]);
+    const float2 p2 = warp_pos(j, c.x[2], c.y[2], c.i[2]);
+    return tri_bary(p0, p1, p2, sx, sy, b0, b1, b2);
+}
+
 // B(q) of a covered pixel q = (qx, qy) whose winner is triangle t of job j: s - q with s the source point interpolated
 // at q with the rasteriser's barycentrics.  The one copy: k_warp_keys and the layered key pass (arap_layers.h) call it.
 __device__ __forceinline__ float2 tri_backward(const WarpJob& j, int W, unsigned t, int qx, int qy)
 {
-    const int u = (int)(t >> 1);
-    const int uy = u / W, ux = u - uy * W;
-    // corners of triangle t and their grid coordinates: 2u = (p00, p01, p10), 2u+1 = (p10, p01, p11)
-    const int odd = (int)(t & 1u);
-    const int ax = ux, ay = uy + odd, bx = ux + 1, by = uy, cx = ux + odd, cy = uy + 1;
-    const float2 p0 = warp_pos(j, ax, ay, ax + W * ay), p1 = warp_pos(j, bx, by, bx + W * by);
-    const float2 p2 = warp_pos(j, cx, cy, cx + W * cy);
+    const TriCorners c = tri_corners(t, W);
     const float sx = (float)qx, sy = (float)qy;
     float b0, b1, b2;
-    if (!tri_bary(p0, p1, p2, sx, sy, b0, b1, b2)) return make_float2(0.f, 0.f);     // (never: the raster passed this test at q)
-    const float srcx = ((float)ax * b0 + (float)bx * b1) + (float)cx * b2;
-    const float srcy = ((float)ay * b0 + (float)by * b1) + (float)cy * b2;
+    if (!tri_bary_at(j, c, sx, sy, b0, b1, b2)) return make_float2(0.f, 0.f);       // (never: the raster passed this test at q)
+    const float srcx = bary_mix((float)c.x[0], (float)c.x[1], (float)c.x[2], b0, b1, b2);
+    const float srcy = bary_mix((float)c.y[0], (float)c.y[1], (float)c.y[2], b0, b1, b2);
     return make_float2(srcx - sx, srcy - sy);
 }
 
@@ -70,13 +68,56 @@ __global__ __launch_bounds__(256) void k_warp_keys(const WarpJob* jobs, int W, i
     if (j.occ && j.mask[i] != 0) j.occ[i] = k ? 255 : 0;
     if (j.occ_bwd) j.occ_bwd[i] = (!k && j.mask[i] == 0) ? 255 : 0;
     if (!j.bwd) return;
-    j.bwd[i] = k ? tri_backward(j, W, (unsigned)(k >> 32) - 1u, qx, qy) : make_float2(0.f, 0.f);
+    j.bwd[i] = k ? tri_backward(j, W, key_winner(k).tri, qx, qy) : make_float2(0.f, 0.f);
 }
 
-// Forward occlusion, pass 1: per object vertex v, P(v) out of frame -> Occ = 255; else Occ = 0 and v is counted in
-// cell (floor P.x, floor P.y).  The returned old count is v's rank in the cell, so the scatter needs no atomics.  (Under
-// a smooth warp a cell holds about one vertex: the counts hardly collide, and the compiler's per-wave aggregation of
-// same-address atomics has nothing to merge.)
+// the cell of an in-frame point
+__device__ __forceinline__ int occ_cell(float2 P, int W) { return (int)floorf(P.x) + W * (int)floorf(P.y); }
+
+// The count tail of every query, for point i at P: out of frame -> Occ = 255; else Occ = 0 and one count in the cell
+// of P.  The returned old count is the point's rank in the cell, so the scatter needs no atomics.  (Under a smooth warp
+// a cell holds about one point: the counts hardly collide, and the compiler's per-wave aggregation of same-address
+// atomics has nothing to merge.)
+__device__ __forceinline__ void occ_count_point(const WarpJob& j, int i, float2 P, int W, int H)
+{
+    const bool in = in_frame(P, W, H);
+    j.occ[i] = in ? 0 : 255;
+    if (!in) return;
+    j.rank[i] = atomicAdd(j.cell + occ_cell(P, W), 1u);
+}
+
+// The scatter tail, after the scan: a counted point to its slot, bin[start(cell) + rank] = {P.x, P.y, payload, m}
+__device__ __forceinline__ void occ_bin_point(const WarpJob& j, int i, float2 P, int W, int H, int payload, int m)
+{
+    if (!in_frame(P, W, H)) return;
+    j.bin[j.cell[occ_cell(P, W)] + j.rank[i]] = make_int4(__float_as_int(P.x), __float_as_int(P.y), payload, m);
+}
+
+// The payload of a binned point: its index i, full width (N < 2^31) -- or, LAYERED, i | l << 24 with l its layer
+// (N <= 2^24).  bin_index reads the index back; bin_tested is the rule by which triangle `tri` of layer `layer` tests
+// the point v = {P.x, P.y, payload, m}:  tri > m  (not one of the point's own triangles, nor an earlier one) -- or,
+// LAYERED,  layer > l || (layer == l && tri > m).
+template <bool LAYERED>
+__device__ __forceinline__ int bin_payload(int i, unsigned l)
+{
+    return LAYERED ? (int)((unsigned)i | (l << 24)) : i;
+}
+
+template <bool LAYERED>
+__device__ __forceinline__ int bin_index(int4 v)
+{
+    return LAYERED ? v.z & 0xffffff : v.z;
+}
+
+template <bool LAYERED>
+__device__ __forceinline__ bool bin_tested(int4 v, unsigned layer, int tri)
+{
+    if (!LAYERED) return tri > v.w;
+    const unsigned l = (unsigned)v.z >> 24;
+    return layer > l || (layer == l && tri > v.w);
+}
+
+// Forward occlusion, pass 1: every object vertex v at P(v) through the count tail
 // grid = (ceil(N/256), 1, njobs), block = 256
 __global__ __launch_bounds__(256) void k_occ_count(const WarpJob* jobs, int W, int H, int N)
 {
@@ -84,12 +125,7 @@ __global__ __launch_bounds__(256) void k_occ_count(const WarpJob* jobs, int W, i
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N || j.mask[i] != 0) return;
     const int y = i / W, x = i - y * W;
-    const float2 P = warp_pos(j, x, y, i);
-    const bool in = in_frame(P, W, H);
-    j.occ[i] = in ? 0 : 255;
-    if (!in) return;
-    const int c = (int)floorf(P.x) + W * (int)floorf(P.y);
-    j.rank[i] = atomicAdd(j.cell + c, 1u);
+    occ_count_point(j, i, warp_pos(j, x, y, i), W, H);
 }
 
 // pass 2: exclusive scan of the N cell counts in place (cell[N] = total).  One workgroup per frame walks the frame in
@@ -153,13 +189,14 @@ __global__ __launch_bounds__(256) void k_occ_scatter(const WarpJob* jobs, int W,
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N || j.mask[i] != 0) return;
     const int y = i / W, x = i - y * W;
-    const float2 P = warp_pos(j, x, y, i);
-    if (!in_frame(P, W, H)) return;
-    const int c = (int)floorf(P.x) + W * (int)floorf(P.y);
-    j.bin[j.cell[c] + j.rank[i]] = make_int4(__float_as_int(P.x), __float_as_int(P.y), i, own_max_tri(j.mask, W, H, x, y));
+    occ_bin_point(j, i, warp_pos(j, x, y, i), W, H, bin_payload<false>(i, 0u), own_max_tri(j.mask, W, H, x, y));
 }
 
-__device__ __forceinline__ void occ_tri(const WarpJob& j, int W, int H, int tri, float2 p0, float2 p1, float2 p2)
+// The querying triangle walk: triangle `tri` of layer `layer` tests, by bin_tested, the points binned in the cells
+// raster_tri visits for it, and flags those at which the rasteriser would show it
+template <bool LAYERED>
+__device__ __forceinline__ void occ_tri(const WarpJob& j, int W, int H, unsigned layer, int tri, float2 p0, float2 p1,
+                                        float2 p2)
 {
     int xa, ya;
     float maxx, maxy;
@@ -170,11 +207,20 @@ __device__ __forceinline__ void occ_tri(const WarpJob& j, int W, int H, int tri,
             const unsigned e = j.cell[c + 1];
             for (unsigned k = j.cell[c]; k < e; ++k) {
                 const int4 v = j.bin[k];
-                if (tri <= v.w) continue;              // one of v's own triangles, or an earlier one
+                if (!bin_tested<LAYERED>(v, layer, tri)) continue;
                 float b0, b1, b2;
-                if (tri_bary(p0, p1, p2, __int_as_float(v.x), __int_as_float(v.y), b0, b1, b2)) j.occ[v.z] = 255;
+                if (tri_bary(p0, p1, p2, __int_as_float(v.x), __int_as_float(v.y), b0, b1, b2))
+                    j.occ[bin_index<LAYERED>(v)] = 255;
             }
         }
+}
+
+// warp_quad with occ_tri as the action, for the job seen as layer `layer`
+template <bool LAYERED>
+__device__ __forceinline__ void occ_quad(const WarpJob& j, int W, int H, int x, int y, unsigned layer)
+{
+    warp_quad<false>(j, W, H, x, y, [&](unsigned t, float2 p0, float2 p1, float2 p2, const float*, const float*,
+                                        const float*) { occ_tri<LAYERED>(j, W, H, layer, (int)t, p0, p1, p2); });
 }
 
 // pass 4: every rasterised triangle t tests the vertices binned in the cells raster_tri visits for t: a later
@@ -183,14 +229,7 @@ __device__ __forceinline__ void occ_tri(const WarpJob& j, int W, int H, int tri,
 __global__ __launch_bounds__(256) void k_occ_tri(const WarpJob* jobs, int W, int H)
 {
     const WarpJob j = jobs[blockIdx.z];
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x + 1 >= W || y + 1 >= H) return;
-    if (!quad_on(j.mask, W, H, x, y)) return;
-    const int i = x + W * y;
-    const float2 p00 = warp_pos(j, x, y, i), p01 = warp_pos(j, x + 1, y, i + 1);
-    const float2 p10 = warp_pos(j, x, y + 1, i + W), p11 = warp_pos(j, x + 1, y + 1, i + W + 1);
-    occ_tri(j, W, H, 2 * i, p00, p01, p10);
-    occ_tri(j, W, H, 2 * i + 1, p10, p01, p11);
+    occ_quad<false>(j, W, H, blockIdx.x * 64 + threadIdx.x, blockIdx.y * 4 + threadIdx.y, 0u);
 }
 
 }  // namespace arap

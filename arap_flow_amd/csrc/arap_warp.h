@@ -7,11 +7,18 @@
 // The reference rasterises quads sequentially (y outer, x inner; triangle (00,01,10) then
 // (10,01,11)) and later writes overwrite earlier ones.  Here every mesh vertex owns the quad to its
 // lower right and rasterises both triangles concurrently; the sequential order is restored with a
-// 64-bit atomicMax per covered pixel on the key  (triangle_index + 1) << 32 | r << 16 | g << 8 | b :
-// the largest triangle index wins, which is exactly the last writer of the sequential loop, and the
-// colour rides along in the low bits.  A second kernel unpacks the keys (and clears them for the
-// next frame).  Per-pixel arithmetic is the reference's float expression, operation for operation
+// 64-bit atomicMax per covered pixel on a key (warp_key below) with the triangle index above the
+// colour: the largest triangle index wins, which is exactly the last writer of the sequential loop,
+// and the colour rides along in the low bits.  A second kernel unpacks the keys (and clears them for
+// the next frame).  Per-pixel arithmetic is the reference's float expression, operation for operation
 // (-ffp-contract=off), so the output is bit exact against the CPU code.
+//
+// This file holds what every member of the warp family shares (arap_occ.h, arap_mid.h, arap_layers.h,
+// arap_layers_step.h): the job, the key, the inside test, the cell walk, the quad body, the corner
+// numbering of a triangle and the barycentric mix, each stated once.
+//
+// Order on the stream:  k_warp_raster -> [passes of the other headers, which read the keys] -> k_warp_resolve.
+// Limits: 2N < 2^32 (32 bits of triangle + 1 in the key).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,20 +90,41 @@ __device__ __forceinline__ bool tri_cells(int W, int H, float2 p0, float2 p1, fl
     return true;
 }
 
+// the one barycentric mix of three corner values (main.cpp:131-137): colours, source points, points of a second state
+__device__ __forceinline__ float bary_mix(float a, float b, float c, float b0, float b1, float b2)
+{
+    return (a * b0 + b * b1) + c * b2;
+}
+
 // the interpolated colour r << 16 | g << 8 | b of a covered pixel (main.cpp:131-137); the one copy, as tri_bary
 __device__ __forceinline__ unsigned tri_rgb(const float c0[3], const float c1[3], const float c2[3], float b0, float b1,
                                             float b2)
 {
     unsigned rgbv = 0;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float v = (c0[k] * b0 + c1[k] * b1) + c2[k] * b2;
-        rgbv = (rgbv << 8) | (unsigned)(unsigned char)v;
-    }
+    for (int k = 0; k < 3; ++k) rgbv = (rgbv << 8) | (unsigned)(unsigned char)bary_mix(c0[k], c1[k], c2[k], b0, b1, b2);
     return rgbv;
 }
 
-__device__ __forceinline__ void raster_tri(const WarpJob& j, int W, int H, unsigned tri, float2 p0, float2 p1,
+// The key of a covered pixel, one format for the whole family:
+//     (l + 1) << 56 | (t + 1) << 24 | r << 16 | g << 8 | b        0 = not covered
+// with t the triangle and l its layer (arap_layers.h; 0 on the single-layer paths).  atomicMax keeps the
+// lexicographically largest (layer, triangle); 8 bits of l + 1 and 32 bits of t + 1 give the limits n <= 255, 2N < 2^32.
+// warp_key states the bits above the colour, key_winner reads them back: no kernel shifts a key by hand.
+__device__ __forceinline__ unsigned long long warp_key(unsigned layer, unsigned tri)
+{
+    return ((unsigned long long)(layer + 1u) << 56) | ((unsigned long long)(tri + 1u) << 24);
+}
+
+struct KeyWinner { bool covered; unsigned layer, tri; };        // layer and tri mean nothing where !covered
+
+__device__ __forceinline__ KeyWinner key_winner(unsigned long long k)
+{
+    return KeyWinner{k != 0ull, (unsigned)(k >> 56) - 1u, (unsigned)(k >> 24) - 1u};
+}
+
+// rasterise triangle (p0, p1, p2) under the key bits `hi` = warp_key(layer, triangle)
+__device__ __forceinline__ void raster_tri(const WarpJob& j, int W, int H, unsigned long long hi, float2 p0, float2 p1,
                                            float2 p2, const float c0[3], const float c1[3], const float c2[3])
 {
     int xa, ya;
@@ -107,29 +135,30 @@ __device__ __forceinline__ void raster_tri(const WarpJob& j, int W, int H, unsig
             float b0, b1, b2;
             if (!tri_bary(p0, p1, p2, (float)x, (float)y, b0, b1, b2)) continue;
             const unsigned rgbv = j.rgb ? tri_rgb(c0, c1, c2, b0, b1, b2) : 0u;
-            const unsigned long long key = ((unsigned long long)(tri + 1u) << 32) | rgbv;
-            atomicMax(j.key + (x + (size_t)W * y), key);
+            atomicMax(j.key + (x + (size_t)W * y), hi | rgbv);
         }
 }
 
-// grid = (ceil(W/64), ceil(H/4), njobs), block = (64,4)
-__global__ __launch_bounds__(256) void k_warp_raster(const WarpJob* jobs, int W, int H)
+// quad (qx, qy) is rasterised iff it lies in the grid and its four corners are object
+__device__ __forceinline__ bool quad_on(const uint8_t* mask, int W, int H, int qx, int qy)
 {
-    const WarpJob j = jobs[blockIdx.z];
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= W || y >= H) return;
-    const int i = x + W * y;
-    if (j.flow_out) {
-        const float2 o = j.field[i];
-        j.flow_out[i] = make_float2(o.x - (float)x, o.y - (float)y);
-    }
-    if (!(x + 1 < W && y + 1 < H)) return;
-    const int i01 = i + 1, i10 = i + W, i11 = i + W + 1;
-    if (!(j.mask[i] == 0 && j.mask[i10] == 0 && j.mask[i01] == 0 && j.mask[i11] == 0)) return;
+    if (qx < 0 || qy < 0 || qx + 1 >= W || qy + 1 >= H) return false;
+    const size_t i = qx + (size_t)W * qy;
+    return mask[i] == 0 && mask[i + 1] == 0 && mask[i + W] == 0 && mask[i + W + 1] == 0;
+}
+
+// The work of vertex (x, y) on the quad to its lower right, the one copy: if the quad is rasterised, its four corner
+// positions, their colours when COLOUR (zeros without an image) and  act(t, p0, p1, p2, c0, c1, c2)  for its two
+// triangles in the reference's order, 2i = (00,01,10) then 2i+1 = (10,01,11).  `act` rasterises or queries.
+template <bool COLOUR, class Act>
+__device__ __forceinline__ void warp_quad(const WarpJob& j, int W, int H, int x, int y, Act act)
+{
+    if (!quad_on(j.mask, W, H, x, y)) return;
+    const int i = x + W * y, i01 = i + 1, i10 = i + W, i11 = i + W + 1;
     const float2 p00 = warp_pos(j, x, y, i), p01 = warp_pos(j, x + 1, y, i01);
     const float2 p10 = warp_pos(j, x, y + 1, i10), p11 = warp_pos(j, x + 1, y + 1, i11);
     float v00[3] = {0, 0, 0}, v01[3] = {0, 0, 0}, v10[3] = {0, 0, 0}, v11[3] = {0, 0, 0};
-    if (j.rgb) {
+    if (COLOUR && j.rgb) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             v00[k] = (float)j.rgb[3 * (size_t)i + k];
@@ -138,10 +167,47 @@ __global__ __launch_bounds__(256) void k_warp_raster(const WarpJob* jobs, int W,
             v11[k] = (float)j.rgb[3 * (size_t)i11 + k];
         }
     }
-    raster_tri(j, W, H, 2u * (unsigned)i, p00, p01, p10, v00, v01, v10);
-    raster_tri(j, W, H, 2u * (unsigned)i + 1u, p10, p01, p11, v10, v01, v11);
+    act(2u * (unsigned)i, p00, p01, p10, v00, v01, v10);
+    act(2u * (unsigned)i + 1u, p10, p01, p11, v10, v01, v11);
 }
 
+// warp_quad with raster_tri as the action, for the job seen as layer `layer`
+__device__ __forceinline__ void raster_quad(const WarpJob& j, int W, int H, int x, int y, unsigned layer)
+{
+    warp_quad<true>(j, W, H, x, y, [&](unsigned t, float2 p0, float2 p1, float2 p2, const float* c0, const float* c1,
+                                       const float* c2) { raster_tri(j, W, H, warp_key(layer, t), p0, p1, p2, c0, c1, c2); });
+}
+
+// warp_quad's numbering read back: the grid coordinates and indices of the three corners of triangle t,
+// 2u = (p00, p01, p10), 2u+1 = (p10, p01, p11) of the quad of vertex u
+struct TriCorners { int x[3], y[3], i[3]; };
+
+__device__ __forceinline__ TriCorners tri_corners(unsigned t, int W)
+{
+    const int u = (int)(t >> 1);
+    const int uy = u / W, ux = u - uy * W;
+    const int odd = (int)(t & 1u);
+    TriCorners c = {{ux, ux + 1, ux + odd}, {uy + odd, uy, uy + 1}, {0, 0, 0}};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c.i[k] = c.x[k] + W * c.y[k];
+    return c;
+}
+
+// grid = (ceil(W/64), ceil(H/4), njobs), block = (64,4)
+__global__ __launch_bounds__(256) void k_warp_raster(const WarpJob* jobs, int W, int H)
+{
+    const WarpJob j = jobs[blockIdx.z];
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= W || y >= H) return;
+    if (j.flow_out) {
+        const int i = x + W * y;
+        const float2 o = j.field[i];
+        j.flow_out[i] = make_float2(o.x - (float)x, o.y - (float)y);
+    }
+    raster_quad(j, W, H, x, y, 0u);
+}
+
+// unpack RGB and mask, each if its pointer is set, and clear the keys
 // grid = (ceil(N/256), 1, njobs), block = 256
 __global__ __launch_bounds__(256) void k_warp_resolve(const WarpJob* jobs, int N)
 {
@@ -155,7 +221,7 @@ __global__ __launch_bounds__(256) void k_warp_resolve(const WarpJob* jobs, int N
         j.out_rgb[3 * (size_t)i + 1] = (uint8_t)((k >> 8) & 0xffu);
         j.out_rgb[3 * (size_t)i + 2] = (uint8_t)(k & 0xffu);
     }
-    j.out_mask[i] = k ? 255 : 0;
+    if (j.out_mask) j.out_mask[i] = k ? 255 : 0;
 }
 
 }  // namespace arap

@@ -445,79 +445,61 @@ class FrameSolver:
             self.h = None
 
 
+def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True):
+    """One ArapFlow_<name> call on host arrays.  `dims`: (W, H) or (W, H, n); `inputs`: (array or None, dtype) and
+    `outputs`: (dict key, shape or None = not asked, torch dtype), both in the library's argument order; `scratch`: the
+    name of the *ScratchBytes function of a call that takes a scratch buffer.  Uploads, allocates, synchronises, calls,
+    and downloads {key: array} of the outputs asked.  A return code of -1 is a ValueError where `bad_args`, every other
+    non-zero code a RuntimeError."""
+    lib = state.lib
+    args = [torch.from_numpy(np.ascontiguousarray(a, dt)).cuda() if a is not None else None for a, dt in inputs]
+    outs = {k: torch.empty(*shape, dtype=dt, device="cuda") for k, shape, dt in outputs if shape is not None}
+    args += [outs.get(k) for k, _, _ in outputs]
+    if scratch:
+        args.append(torch.empty(int(getattr(lib, "ArapFlow_" + scratch)(*dims)), dtype=torch.uint8, device="cuda"))
+    torch.cuda.synchronize()
+    rc = getattr(lib, "ArapFlow_" + name)(state.handle, *dims, *[_dev_ptr(t) if t is not None else None for t in args])
+    if rc == -1 and bad_args:
+        raise ValueError("ArapFlow_%s: bad arguments" % name)
+    if rc != 0:
+        raise RuntimeError("ArapFlow_%s failed: %d" % (name, rc))
+    torch.cuda.synchronize()
+    return {k: t.cpu().numpy() for k, t in outs.items()}
+
+
 def warp_image(state, rgb, mask_red, flow):
     """warp_image (ARAP/warping/src/main.cpp:302-336 minus file I/O) on the GPU.
     rgb u8[H,W,3], mask_red u8[H,W], flow f32[H,W,2] (numpy) -> (warped_rgb, warped_mask)."""
-    lib = state.lib
     H, W = mask_red.shape
-    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda()
-    d_msk = torch.from_numpy(np.ascontiguousarray(mask_red, np.uint8)).cuda()
-    d_flow = torch.from_numpy(np.ascontiguousarray(flow, np.float32)).cuda()
-    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda")
-    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
-    scratch = torch.empty(int(lib.ArapFlow_WarpScratchBytes(W, H)), dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    rc = lib.ArapFlow_Warp(state.handle, W, H, _dev_ptr(d_rgb), _dev_ptr(d_msk), _dev_ptr(d_flow), _dev_ptr(o_rgb),
-                           _dev_ptr(o_msk), _dev_ptr(scratch))
-    if rc != 0:
-        raise RuntimeError("ArapFlow_Warp failed: %d" % rc)
-    torch.cuda.synchronize()
-    return o_rgb.cpu().numpy(), o_msk.cpu().numpy()
+    r = _warp_call(state, "Warp", (W, H), [(rgb, np.uint8), (mask_red, np.uint8), (flow, np.float32)],
+                   [("warped_rgb", (H, W, 3), torch.uint8), ("warped_mask", (H, W), torch.uint8)], "WarpScratchBytes", bad_args=False)
+    return r["warped_rgb"], r["warped_mask"]
 
 
 def warp_image_ex(state, rgb, mask_red, flow, backward=True, occlusion=True):
     """warp_image plus the optional outputs (ArapFlow_WarpEx): a dict of warped_rgb, warped_mask and, as asked for,
     backward_flow f32[H,W,2] + occlusion_bwd u8[H,W], occlusion u8[H,W].  rgb may be None."""
-    lib = state.lib
     H, W = mask_red.shape
-    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
-    d_msk = torch.from_numpy(np.ascontiguousarray(mask_red, np.uint8)).cuda()
-    d_flow = torch.from_numpy(np.ascontiguousarray(flow, np.float32)).cuda()
-    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
-    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
-    o_bwd = torch.empty(H, W, 2, dtype=torch.float32, device="cuda") if backward else None
-    o_obwd = torch.empty(H, W, dtype=torch.uint8, device="cuda") if backward else None
-    o_occ = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occlusion else None
-    scratch = torch.empty(int(lib.ArapFlow_WarpExScratchBytes(W, H)), dtype=torch.uint8, device="cuda")
-    p = lambda t: _dev_ptr(t) if t is not None else None
-    torch.cuda.synchronize()
-    rc = lib.ArapFlow_WarpEx(state.handle, W, H, p(d_rgb), p(d_msk), p(d_flow), p(o_rgb), p(o_msk), p(o_bwd),
-                             p(o_obwd), p(o_occ), p(scratch))
-    if rc != 0:
-        raise RuntimeError("ArapFlow_WarpEx failed: %d" % rc)
-    torch.cuda.synchronize()
-    out = dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy())
-    if backward:
-        out.update(backward_flow=o_bwd.cpu().numpy(), occlusion_bwd=o_obwd.cpu().numpy())
-    if occlusion:
-        out.update(occlusion=o_occ.cpu().numpy())
-    return out
+    r = _warp_call(state, "WarpEx", (W, H), [(rgb, np.uint8), (mask_red, np.uint8), (flow, np.float32)],
+                   [("warped_rgb", (H, W, 3) if rgb is not None else None, torch.uint8), ("warped_mask", (H, W), torch.uint8),
+                    ("backward_flow", (H, W, 2) if backward else None, torch.float32),
+                    ("occlusion_bwd", (H, W) if backward else None, torch.uint8),
+                    ("occlusion", (H, W) if occlusion else None, torch.uint8)], "WarpExScratchBytes", bad_args=False)
+    return {"warped_rgb": None, **r}
 
 
 def warp_step(state, rgb, mask_red, flow_a, flow_b):
     """the warp of flow_a and the flow from that warped frame to the state flow_b (ArapFlow_WarpStep, DESIGN.md
     "In-between frames").  rgb u8[H,W,3] or None, mask_red u8[H,W], flow_a / flow_b f32[H,W,2] (numpy) -> a dict of
     warped_rgb (None without rgb), warped_mask and step f32[H,W,2]."""
-    lib = state.lib
     H, W = mask_red.shape
     if tuple(np.shape(flow_a)) != (H, W, 2) or tuple(np.shape(flow_b)) != (H, W, 2):
         raise ValueError("warp_step: flows [H,W,2] expected")
-    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
-    d_msk = torch.from_numpy(np.ascontiguousarray(mask_red, np.uint8)).cuda()
-    d_a = torch.from_numpy(np.ascontiguousarray(flow_a, np.float32)).cuda()
-    d_b = torch.from_numpy(np.ascontiguousarray(flow_b, np.float32)).cuda()
-    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
-    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
-    o_step = torch.empty(H, W, 2, dtype=torch.float32, device="cuda")
-    p = lambda t: _dev_ptr(t) if t is not None else None
-    torch.cuda.synchronize()
-    rc = lib.ArapFlow_WarpStep(state.handle, W, H, p(d_rgb), p(d_msk), p(d_a), p(d_b), p(o_rgb), p(o_msk), p(o_step))
-    if rc != 0:
-        raise (ValueError("ArapFlow_WarpStep: bad arguments") if rc == -1 else
-               RuntimeError("ArapFlow_WarpStep failed: %d" % rc))
-    torch.cuda.synchronize()
-    return dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy(),
-                step=o_step.cpu().numpy())
+    r = _warp_call(state, "WarpStep", (W, H),
+                   [(rgb, np.uint8), (mask_red, np.uint8), (flow_a, np.float32), (flow_b, np.float32)],
+                   [("warped_rgb", (H, W, 3) if rgb is not None else None, torch.uint8), ("warped_mask", (H, W), torch.uint8),
+                    ("step", (H, W, 2), torch.float32)])
+    return {"warped_rgb": None, **r}
 
 
 def warp_layers(state, rgb, masks, flows, bwd=False, occ_bwd=False, occ=True):
@@ -525,7 +507,6 @@ def warp_layers(state, rgb, masks, flows, bwd=False, occ_bwd=False, occ=True):
     higher index on top.  rgb u8[H,W,3] or None, masks u8[n,H,W] (red channels, 0 = object), flows f32[n,H,W,2] (numpy)
     -> a dict of the composite warped_rgb (None without rgb), warped_mask and, as asked for, backward_flow f32[H,W,2],
     occlusion_bwd u8[H,W], occlusion u8[H,W] (the forward occlusion across layers)."""
-    lib = state.lib
     masks = np.ascontiguousarray(masks, np.uint8)
     flows = np.ascontiguousarray(flows, np.float32)
     if masks.ndim != 3 or flows.shape != masks.shape + (2,):
@@ -533,31 +514,11 @@ def warp_layers(state, rgb, masks, flows, bwd=False, occ_bwd=False, occ=True):
     n, H, W = masks.shape
     if rgb is not None and tuple(np.shape(rgb)) != (H, W, 3):
         raise ValueError("warp_layers: rgb [H,W,3] expected")
-    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
-    d_msk = torch.from_numpy(masks).cuda()
-    d_flow = torch.from_numpy(flows).cuda()
-    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
-    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
-    o_bwd = torch.empty(H, W, 2, dtype=torch.float32, device="cuda") if bwd else None
-    o_obwd = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occ_bwd else None
-    o_occ = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occ else None
-    scratch = torch.empty(int(lib.ArapFlow_WarpLayersScratchBytes(W, H, n)), dtype=torch.uint8, device="cuda")
-    p = lambda t: _dev_ptr(t) if t is not None else None
-    torch.cuda.synchronize()
-    rc = lib.ArapFlow_WarpLayers(state.handle, W, H, n, p(d_rgb), p(d_msk), p(d_flow), p(o_rgb), p(o_msk), p(o_bwd),
-                                 p(o_obwd), p(o_occ), p(scratch))
-    if rc != 0:
-        raise (ValueError("ArapFlow_WarpLayers: bad arguments") if rc == -1 else
-               RuntimeError("ArapFlow_WarpLayers failed: %d" % rc))
-    torch.cuda.synchronize()
-    out = dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy())
-    if bwd:
-        out.update(backward_flow=o_bwd.cpu().numpy())
-    if occ_bwd:
-        out.update(occlusion_bwd=o_obwd.cpu().numpy())
-    if occ:
-        out.update(occlusion=o_occ.cpu().numpy())
-    return out
+    r = _warp_call(state, "WarpLayers", (W, H, n), [(rgb, np.uint8), (masks, np.uint8), (flows, np.float32)],
+                   [("warped_rgb", (H, W, 3) if rgb is not None else None, torch.uint8), ("warped_mask", (H, W), torch.uint8),
+                    ("backward_flow", (H, W, 2) if bwd else None, torch.float32), ("occlusion_bwd", (H, W) if occ_bwd else None, torch.uint8),
+                    ("occlusion", (H, W) if occ else None, torch.uint8)], "WarpLayersScratchBytes")
+    return {"warped_rgb": None, **r}
 
 
 def warp_layers_step(state, rgb, masks, flows_a, flows_b, step=True, occ=True):
@@ -565,7 +526,6 @@ def warp_layers_step(state, rgb, masks, flows_a, flows_b, step=True, occ=True):
     state a of the n layers, the flow from that composite to state b and the forward occlusion of that link.  rgb
     u8[H,W,3] or None, masks u8[n,H,W] (red channels, 0 = object), flows_a / flows_b f32[n,H,W,2] (numpy) -> a dict of
     warped_rgb (None without rgb), warped_mask and, as asked for, step f32[H,W,2], occlusion_step u8[H,W]."""
-    lib = state.lib
     masks = np.ascontiguousarray(masks, np.uint8)
     flows_a = np.ascontiguousarray(flows_a, np.float32)
     flows_b = np.ascontiguousarray(flows_b, np.float32)
@@ -574,25 +534,9 @@ def warp_layers_step(state, rgb, masks, flows_a, flows_b, step=True, occ=True):
     n, H, W = masks.shape
     if rgb is not None and tuple(np.shape(rgb)) != (H, W, 3):
         raise ValueError("warp_layers_step: rgb [H,W,3] expected")
-    d_rgb = torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).cuda() if rgb is not None else None
-    d_msk = torch.from_numpy(masks).cuda()
-    d_a, d_b = torch.from_numpy(flows_a).cuda(), torch.from_numpy(flows_b).cuda()
-    o_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda") if rgb is not None else None
-    o_msk = torch.empty(H, W, dtype=torch.uint8, device="cuda")
-    o_step = torch.empty(H, W, 2, dtype=torch.float32, device="cuda") if step else None
-    o_occ = torch.empty(H, W, dtype=torch.uint8, device="cuda") if occ else None
-    scratch = torch.empty(int(lib.ArapFlow_WarpLayersStepScratchBytes(W, H, n)), dtype=torch.uint8, device="cuda")
-    p = lambda t: _dev_ptr(t) if t is not None else None
-    torch.cuda.synchronize()
-    rc = lib.ArapFlow_WarpLayersStep(state.handle, W, H, n, p(d_rgb), p(d_msk), p(d_a), p(d_b), p(o_rgb), p(o_msk),
-                                     p(o_step), p(o_occ), p(scratch))
-    if rc != 0:
-        raise (ValueError("ArapFlow_WarpLayersStep: bad arguments") if rc == -1 else
-               RuntimeError("ArapFlow_WarpLayersStep failed: %d" % rc))
-    torch.cuda.synchronize()
-    out = dict(warped_rgb=o_rgb.cpu().numpy() if o_rgb is not None else None, warped_mask=o_msk.cpu().numpy())
-    if step:
-        out.update(step=o_step.cpu().numpy())
-    if occ:
-        out.update(occlusion_step=o_occ.cpu().numpy())
-    return out
+    r = _warp_call(state, "WarpLayersStep", (W, H, n),
+                   [(rgb, np.uint8), (masks, np.uint8), (flows_a, np.float32), (flows_b, np.float32)],
+                   [("warped_rgb", (H, W, 3) if rgb is not None else None, torch.uint8), ("warped_mask", (H, W), torch.uint8),
+                    ("step", (H, W, 2) if step else None, torch.float32), ("occlusion_step", (H, W) if occ else None, torch.uint8)],
+                   "WarpLayersStepScratchBytes")
+    return {"warped_rgb": None, **r}

@@ -123,6 +123,27 @@ def test_mirror_fold_closed_form(gpu_state):
     assert np.array_equal(r["warped_mask"] == 255, strip & (xs <= c))
 
 
+def test_mirror_fold_closed_form_above_2_24_vertices(gpu_state):
+    """test_mirror_fold_closed_form with the strip in the last rows of a 4096 x 4104 grid: N = 2^24 + 32768 and every
+    object vertex has an index >= 2^24.  The single-layer query carries a vertex's index at full width; cut to the 24
+    bits of the layered query's, its flags would land 4096 rows higher, in rows 1..6.  The whole image is compared."""
+    W, H = 4096, 4104
+    y0, y1, x0, x1, c = 4097, 4102, 10, 50, 36
+    assert W * H == (1 << 24) + 32768 and y0 * W + x0 >= 1 << 24
+    ys, xs = np.arange(H)[:, None], np.arange(W)[None, :]
+    strip = (ys >= y0) & (ys <= y1) & (xs >= x0) & (xs <= x1)
+    assert np.flatnonzero(strip).min() >= 1 << 24
+    mask = np.where(strip, 0, 255).astype(np.uint8)
+    fl = np.zeros((H, W, 2), np.float32)
+    fl[..., 0] = np.where(strip & (xs > c), 2 * c - 2 * xs, 0)
+    r = opt.warp_image_ex(gpu_state, None, mask, fl)
+    want = strip & (xs >= 2 * c - x1) & (xs <= c - 1)
+    assert want.sum() == 6 * (c - (2 * c - x1))
+    assert np.array_equal(r["occlusion"] == 255, want)
+    assert np.array_equal(r["occlusion_bwd"] == 255, strip & (xs > c))
+    assert np.array_equal(r["warped_mask"] == 255, strip & (xs <= c))
+
+
 def test_outputs_change_nothing_else_and_repeat_bit_identical(gpu_state):
     W, H, batch = 160, 96, 2
     frames = _frames(W, H, batch, 7)
