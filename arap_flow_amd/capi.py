@@ -77,6 +77,8 @@ SYMBOLS = [
     ("ArapFlow_WarpLayers", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ArapFlow_WarpLayersStepScratchBytes", C.c_uint64, [_U, _U, _U]),
     ("ArapFlow_WarpLayersStep", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("ArapFlow_BackgroundMaps", _I, [C.POINTER(C.c_float)] * 4),
+    ("ArapFlow_Background", _I, [_VP, _U, _U, _VP, _U, _U, C.POINTER(C.c_float), C.POINTER(C.c_float)] + [_VP] * 14),
 ]
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h

@@ -1,6 +1,7 @@
 // abi_warp.h -- the warp entry points on caller-owned images (ArapFlow_Warp / WarpEx / WarpStep / WarpLayers /
 // WarpLayersStep): the layout of their scratch buffer, stated once for the size functions and for the code that carves
 // it up, and the one enqueue of rasterise -> optional outputs -> resolve that the frame solver's warp shares.
+// Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background, arap_bg.h), which needs no scratch.
 #pragma once
 
 // the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
@@ -120,6 +121,21 @@ static bool layers_args_ok(const Opt_State* st, unsigned W, unsigned H, unsigned
     return N < (1ull << 31) && !(out_occ && N > (1ull << 24));
 }
 
+// G = B^-1 o A of two affine maps, in double, rounded once to float; false when B's linear part has det == 0
+static bool bg_compose(const float A[6], const float B[6], float G[6])
+{
+    const double a = B[0], b = B[1], d = B[3], e = B[4];
+    const double det = a * e - b * d;
+    if (det == 0.0) return false;
+    const double ia = e / det, ib = -b / det, id = -d / det, ie = a / det;          // B^-1, linear part
+    const double tx = (double)A[2] - (double)B[2], ty = (double)A[5] - (double)B[5];
+    G[0] = (float)(ia * A[0] + ib * A[3]); G[1] = (float)(ia * A[1] + ib * A[4]); G[2] = (float)(ia * tx + ib * ty);
+    G[3] = (float)(id * A[0] + ie * A[3]); G[4] = (float)(id * A[1] + ie * A[4]); G[5] = (float)(id * tx + ie * ty);
+    return true;
+}
+
+static BgMap bg_map(const float m[6]) { return BgMap{m[0], m[1], m[2], m[3], m[4], m[5]}; }
+
 extern "C" {
 
 uint64_t ArapFlow_WarpScratchBytes(unsigned W, unsigned H) { return warp_scratch(W, H, 0).total; }
@@ -221,6 +237,52 @@ int ArapFlow_WarpLayersStep(Opt_State* st, unsigned W, unsigned H, unsigned n, c
                 hipLaunchKernelGGL(k_lstep_step, g1, dim3(256), 0, stream, dj, la, lb.flows, pts, iW, iH, N);
         },
         [&](dim3 g1) { hipLaunchKernelGGL(k_lstep_scatter, g1, dim3(256), 0, stream, dj, pts, iW, iH, N); });
+}
+
+int ArapFlow_BackgroundMaps(const float M1[6], const float M2[6], float G[6], float Ginv[6])
+{
+    if (!M1 || !M2 || !G || !Ginv) return -1;
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(M1[k]) || !std::isfinite(M2[k])) return -1;
+    const double d1 = (double)M1[0] * M1[4] - (double)M1[1] * M1[3], d2 = (double)M2[0] * M2[4] - (double)M2[1] * M2[3];
+    if (d1 == 0.0 || d2 == 0.0) return -1;
+    if (memcmp(M1, M2, 6 * sizeof(float)) == 0) {            // the same camera: the exact identity, nothing inverted
+        const float I[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+        memcpy(G, I, sizeof(I));
+        memcpy(Ginv, I, sizeof(I));
+        return 0;
+    }
+    return bg_compose(M1, M2, G) && bg_compose(M2, M1, Ginv) ? 0 : -1;
+}
+
+int ArapFlow_Background(Opt_State* st, unsigned W, unsigned H, const void* bg, unsigned bgW, unsigned bgH, const float M1[6],
+                        const float M2[6], const void* rgb1, const void* mask_red, const void* rgb2, const void* cover2,
+                        const void* flow, const void* occ, const void* bwd, const void* occ_bwd, void* out_rgb1,
+                        void* out_rgb2, void* flow_full, void* occ_full, void* bwd_full, void* occ_bwd_full)
+{
+    if (!st || !bg || !mask_red || !cover2 || W == 0 || H == 0 || bgW == 0 || bgH == 0) return -1;
+    if ((uint64_t)W * H >= (1ull << 31) || bgW >= (1u << 31) || bgH >= (1u << 31)) return -1;
+    if ((out_rgb1 && !rgb1) || (out_rgb2 && !rgb2) || (flow_full && !flow) || (occ_full && !occ) || (bwd_full && !bwd) ||
+        (occ_bwd_full && !occ_bwd))
+        return -1;
+    const bool one = out_rgb1 || flow_full || occ_full, two = out_rgb2 || bwd_full || occ_bwd_full;
+    if (!one && !two) return -1;
+    float G[6], Ginv[6];
+    if (ArapFlow_BackgroundMaps(M1, M2, G, Ginv) != 0) return -1;
+    const BgPicture pic{(const uint8_t*)bg, (int)bgW, (int)bgH};
+    const dim3 grid((W + 63) / 64, (H + 3) / 4), block(64, 4);
+    if (one) {
+        const BgSide s{(const uint8_t*)mask_red, (const uint8_t*)cover2, (const uint8_t*)rgb1, (const float2*)flow,
+                       (const uint8_t*)occ, (uint8_t*)out_rgb1, (float2*)flow_full, (uint8_t*)occ_full, bg_map(M1), bg_map(G)};
+        hipLaunchKernelGGL(k_bg_frame1, grid, block, 0, st->stream, s, pic, (int)W, (int)H);
+    }
+    if (two) {
+        const BgSide s{(const uint8_t*)cover2, (const uint8_t*)mask_red, (const uint8_t*)rgb2, (const float2*)bwd,
+                       (const uint8_t*)occ_bwd, (uint8_t*)out_rgb2, (float2*)bwd_full, (uint8_t*)occ_bwd_full, bg_map(M2),
+                       bg_map(Ginv)};
+        hipLaunchKernelGGL(k_bg_frame2, grid, block, 0, st->stream, s, pic, (int)W, (int)H);
+    }
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

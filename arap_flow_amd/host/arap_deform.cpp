@@ -15,7 +15,12 @@
 // STEM_l_sII.flo, STEM_l = FLO_l without `.flo`, and writes per snapshot the composite PREFIX_sII.flo, PREFIX_sII.png,
 // PREFIX_sII_mask.png, PREFIX_sII_step.flo and, with occ= on the line, the link occlusions PREFIX_s00_occ.png (frame 1
 // -> first snapshot) and PREFIX_sII_occ.png (snapshot -> next state).
-// It runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
+// A line whose first word is `bg` is the moving-background pass of one pair (DESIGN.md "Moving background"):
+//   bg BG.png RGB1.png MASK1.png RGB2.png MASK2.png FLOW.flo m=<12 numbers, M1 then M2, comma separated>
+//      [occ=IN] [bwd=IN] [occ_bwd=IN] out=RGB1_OUT.png,RGB2_OUT.png,FLOW_OUT.flo [occ_out=P] [bwd_out=P] [occ_bwd_out=P]
+// (MASK1: red 0 = object; MASK2: a warped mask, non-zero = object; a place of out= may be empty; at least one output).
+// It answers "Done <first output: the places of out=, then occ_out, bwd_out, occ_bwd_out>".
+// Either runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
 // here consecutive frames of equal size are handed to the device-resident batched solver, as many as fit one launch
@@ -73,6 +78,20 @@ struct LayersSpec {
     std::vector<unsigned> mid_steps;       // mid= token (empty: not wanted) and the composite files' path prefix
     std::string mid_prefix;
     std::string first_out;                 // the first output token's path: what --serve reports
+};
+
+// one `bg` line (pipeline.BgLine)
+struct BgSpec {
+    std::string bg, rgb1, mask1, rgb2, mask2, flow;
+    float m[12];                           // M1, M2
+    std::string occ, bwd, occ_bwd;         // optional object-side inputs
+    std::string out_rgb1, out_rgb2, out_flow, out_occ, out_bwd, out_occ_bwd;      // outputs (empty: not wanted)
+    std::string first_out() const
+    {
+        for (const std::string* q : {&out_rgb1, &out_rgb2, &out_flow, &out_occ, &out_bwd, &out_occ_bwd})
+            if (!q->empty()) return *q;
+        return std::string();
+    }
 };
 
 // the usage text of the reference's executable (main.cpp:13-24), verbatim: it is part of the CLI contract
@@ -370,15 +389,142 @@ static bool run_layers(Opt_State* state, const LayersSpec& q)
     return true;
 }
 
+static bool first_word_is(const std::string& line, const char* word)
+{
+    std::istringstream tok(line);
+    std::string w;
+    return (tok >> w) && w == word;
+}
+
+// pipeline.parse_bg
+static bool parse_bg(const std::string& line, BgSpec& q)
+{
+    std::istringstream tok(line);
+    std::string w;
+    if (!(tok >> w >> q.bg >> q.rgb1 >> q.mask1 >> q.rgb2 >> q.mask2 >> q.flow) || w != "bg") return false;
+    bool have_m = false;
+    for (std::string t; tok >> t;) {
+        const size_t eq = t.find('=');
+        if (eq == std::string::npos || eq + 1 >= t.size()) return false;
+        const std::string k = t.substr(0, eq), v = t.substr(eq + 1);
+        if (k == "m") {
+            size_t a = 0;
+            for (int n = 0; n < 12; ++n) {
+                size_t b = v.find(',', a);
+                if (b == std::string::npos) b = v.size();
+                if ((n < 11) != (b < v.size()) || b == a) return false;
+                const std::string num = v.substr(a, b - a);
+                char* end = nullptr;
+                q.m[n] = strtof(num.c_str(), &end);
+                if (end != num.c_str() + num.size()) return false;
+                a = b + 1;
+            }
+            have_m = true;
+        } else if (k == "out") {
+            const size_t c1 = v.find(','), c2 = c1 == std::string::npos ? c1 : v.find(',', c1 + 1);
+            if (c2 == std::string::npos || v.find(',', c2 + 1) != std::string::npos) return false;
+            q.out_rgb1 = v.substr(0, c1); q.out_rgb2 = v.substr(c1 + 1, c2 - c1 - 1); q.out_flow = v.substr(c2 + 1);
+        } else {
+            std::string* dst = k == "occ" ? &q.occ : k == "bwd" ? &q.bwd : k == "occ_bwd" ? &q.occ_bwd
+                             : k == "occ_out" ? &q.out_occ : k == "bwd_out" ? &q.out_bwd
+                             : k == "occ_bwd_out" ? &q.out_occ_bwd : nullptr;
+            if (!dst) return false;
+            *dst = v;
+        }
+    }
+    if ((!q.out_occ.empty() && q.occ.empty()) || (!q.out_bwd.empty() && q.bwd.empty()) ||
+        (!q.out_occ_bwd.empty() && q.occ_bwd.empty()))
+        return false;
+    return have_m && !q.first_out().empty();
+}
+
+// the moving-background pass of one pair, synchronously (pipeline.run_background): read the line's files, one
+// ArapFlow_Background on the state's stream, write the outputs asked for
+static bool run_background(Opt_State* state, const BgSpec& q)
+{
+    std::string err;
+    arapio::Image bg, rgb1, rgb2, m1, m2, occ, occ_bwd;
+    auto png = [&](const std::string& path, arapio::Image& im) {
+        if (arapio::read_png_rgb(path, im, err)) return true;
+        printf("%s\n", err.c_str());
+        return false;
+    };
+    if (!png(q.bg, bg) || !png(q.rgb1, rgb1) || !png(q.mask1, m1) || !png(q.rgb2, rgb2) || !png(q.mask2, m2)) return false;
+    if (!q.occ.empty() && !png(q.occ, occ)) return false;
+    if (!q.occ_bwd.empty() && !png(q.occ_bwd, occ_bwd)) return false;
+    const int w = rgb1.w, h = rgb1.h;
+    std::vector<float> flow, bwd;
+    int fw = 0, fh = 0, bw = w, bh = h;
+    if (!arapio::read_flo(q.flow, flow, fw, fh)) return false;
+    if (!q.bwd.empty() && !arapio::read_flo(q.bwd, bwd, bw, bh)) return false;
+    auto same = [&](const arapio::Image& im) { return im.w == w && im.h == h; };
+    if (!same(m1) || !same(rgb2) || !same(m2) || fw != w || fh != h || bw != w || bh != h ||
+        (!q.occ.empty() && !same(occ)) || (!q.occ_bwd.empty() && !same(occ_bwd))) {
+        printf("bg: image, mask and flow sizes differ: %s\n", q.rgb1.c_str());
+        return false;
+    }
+    const size_t N = (size_t)w * h, B = (size_t)bg.w * bg.h * 3;
+    // host staging: the red channels of the masks (cover2 as it is read: non-zero = object) and of the occlusion maps
+    std::vector<uint8_t> planes(4 * N, 0);
+    for (size_t i = 0; i < N; ++i) {
+        planes[i] = m1.rgb[3 * i];
+        planes[N + i] = m2.rgb[3 * i] ? 255 : 0;
+        if (!q.occ.empty()) planes[2 * N + i] = occ.rgb[3 * i];
+        if (!q.occ_bwd.empty()) planes[3 * N + i] = occ_bwd.rgb[3 * i];
+    }
+    // device: flows first (8-byte aligned), then bytes.  in: flow, bwd, rgb1, rgb2, 4 planes, bg; out: flow_full,
+    // bwd_full, rgb1, rgb2, occ_full, occ_bwd_full
+    const size_t in_bytes = 16 * N + 6 * N + 4 * N, off_bg = in_bytes, off_out = (off_bg + B + 255) / 256 * 256;
+    const size_t out_bytes = 16 * N + 6 * N + 2 * N;
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, off_out + out_bytes) != hipSuccess) { printf("bg: out of device memory\n"); return false; }
+    char* o = d + off_out;
+    bool ok = hipMemcpy(d, flow.data(), 8 * N, hipMemcpyHostToDevice) == hipSuccess &&
+              (bwd.empty() || hipMemcpy(d + 8 * N, bwd.data(), 8 * N, hipMemcpyHostToDevice) == hipSuccess) &&
+              hipMemcpy(d + 16 * N, rgb1.rgb.data(), 3 * N, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + 19 * N, rgb2.rgb.data(), 3 * N, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + 22 * N, planes.data(), 4 * N, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + off_bg, bg.rgb.data(), B, hipMemcpyHostToDevice) == hipSuccess;
+    auto want = [](const std::string& path, char* p) -> void* { return path.empty() ? nullptr : p; };
+    ok = ok && ArapFlow_Background(state, (unsigned)w, (unsigned)h, d + off_bg, (unsigned)bg.w, (unsigned)bg.h, q.m, q.m + 6,
+                                   d + 16 * N, d + 22 * N, d + 19 * N, d + 23 * N, d, q.occ.empty() ? nullptr : d + 24 * N,
+                                   q.bwd.empty() ? nullptr : d + 8 * N, q.occ_bwd.empty() ? nullptr : d + 25 * N,
+                                   want(q.out_rgb1, o + 16 * N), want(q.out_rgb2, o + 19 * N), want(q.out_flow, o),
+                                   want(q.out_occ, o + 22 * N), want(q.out_bwd, o + 8 * N),
+                                   want(q.out_occ_bwd, o + 23 * N)) == 0;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    std::vector<uint8_t> host(out_bytes);
+    ok = ok && hipMemcpy(host.data(), o, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d);
+    if (!ok) { printf("ArapFlow_Background failed\n"); return false; }
+    const uint8_t* hp = host.data();
+    auto say = [&](bool written) { if (!written) printf("%s\n", err.c_str()); return written; };
+    if (!q.out_rgb1.empty() && !say(arapio::write_png_rgb(q.out_rgb1, w, h, hp + 16 * N, err))) return false;
+    if (!q.out_rgb2.empty() && !say(arapio::write_png_rgb(q.out_rgb2, w, h, hp + 19 * N, err))) return false;
+    if (!q.out_flow.empty() && !arapio::write_flo(q.out_flow, (const float*)hp, w, h)) return false;
+    if (!q.out_bwd.empty() && !arapio::write_flo(q.out_bwd, (const float*)(hp + 8 * N), w, h)) return false;
+    if (!q.out_occ.empty() && !say(arapio::write_png_gray8(q.out_occ, w, h, hp + 22 * N, err))) return false;
+    if (!q.out_occ_bwd.empty() && !say(arapio::write_png_gray8(q.out_occ_bwd, w, h, hp + 23 * N, err))) return false;
+    return true;
+}
+
 // ---- where the lines come from: a finished list, or stdin as it arrives (--serve) ------------------------------------
-struct Loaded { bool ok = false; Frame f; bool is_layers = false; LayersSpec layers; };
+struct Loaded { bool ok = false; Frame f; bool is_layers = false, is_bg = false; LayersSpec layers; BgSpec bg; };
 
-struct Item { bool is_layers = false, bad = false; SolvePaths solve; LayersSpec layers; };
+struct Item { bool is_layers = false, is_bg = false, bad = false; SolvePaths solve; LayersSpec layers; BgSpec bg; };
 
-// a list / --serve line -> item; false for a line that is neither (a bad `layers` line and a bad mid= token are
-// reported, and `bad` is set)
+// a list / --serve line -> item; false for a line that is none of the forms (a bad `layers` or `bg` line and a bad mid=
+// token are reported, and `bad` is set)
 static bool parse_item(const std::string& line, Item& it)
 {
+    if (first_word_is(line, "bg")) {
+        it.is_bg = true;
+        if (parse_bg(line, it.bg)) return true;
+        it.bad = true;
+        printf("Invalid bg line: %s\n", line.c_str());
+        fflush(stdout);
+        return false;
+    }
     if (is_layers_line(line)) {
         it.is_layers = true;
         if (parse_layers(line, it.layers)) return true;
@@ -448,9 +594,10 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            if (q->is_layers) {              // read when its turn comes: in a list its inputs may not exist yet
+            if (q->is_layers || q->is_bg) {  // read when its turn comes: in a list its inputs may not exist yet
                 loading_.push_back(std::async(std::launch::deferred, [q]() {
-                    Loaded l; l.ok = true; l.is_layers = true; l.layers = q->layers; return l; }));
+                    Loaded l; l.ok = true; l.is_layers = q->is_layers; l.is_bg = q->is_bg;
+                    l.layers = q->layers; l.bg = q->bg; return l; }));
                 continue;
             }
             loading_.push_back(std::async(std::launch::async, [q]() { Loaded l; l.ok = load_frame(q->solve, l.f); return l; }));
@@ -694,15 +841,15 @@ int main(int argc, const char* argv[])
             }
             if (got < 0) exhausted = true;
         }
-        if (fr && fr->is_layers) {
+        if (fr && (fr->is_layers || fr->is_bg)) {
             // A list: every earlier line is solved and written first (this line's inputs may be their outputs).  --serve:
             // the sender names only files that exist, so nothing is flushed; the call queues behind the solve in flight.
             if (!serve) {
                 if (!launch(L) || !drain(other) || !drain(L)) { rc = 1; break; }
                 writer.finish();
             }
-            if (!run_layers(state, fr->layers)) { rc = 1; break; }
-            writer.say(serve ? "Done " + fr->layers.first_out : std::string("Saved"));
+            if (!(fr->is_bg ? run_background(state, fr->bg) : run_layers(state, fr->layers))) { rc = 1; break; }
+            writer.say(serve ? "Done " + (fr->is_bg ? fr->bg.first_out() : fr->layers.first_out) : std::string("Saved"));
             continue;
         }
         if (fr) {

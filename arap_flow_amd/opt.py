@@ -8,6 +8,7 @@
   warp_image       ARAP/warping/src/main.cpp:145-225 through ArapFlow_Warp
   warp_image_ex    the same, plus backward flow and occlusion maps (ArapFlow_WarpEx)
   warp_step        the warp of one deformation state and the flow from it to a second one (ArapFlow_WarpStep)
+  background       full-frame RGB, flow and occlusion behind a warped pair's objects (ArapFlow_Background)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -445,20 +446,24 @@ class FrameSolver:
             self.h = None
 
 
-def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True):
+def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, lead=()):
     """One ArapFlow_<name> call on host arrays.  `dims`: (W, H) or (W, H, n); `inputs`: (array or None, dtype) and
     `outputs`: (dict key, shape or None = not asked, torch dtype), both in the library's argument order; `scratch`: the
-    name of the *ScratchBytes function of a call that takes a scratch buffer.  Uploads, allocates, synchronises, calls,
+    name of the *ScratchBytes function of a call that takes a scratch buffer; `lead`: arguments between the dims and
+    the inputs, an (array, dtype) to upload or a value passed as it is.  Uploads, allocates, synchronises, calls,
     and downloads {key: array} of the outputs asked.  A return code of -1 is a ValueError where `bad_args`, every other
     non-zero code a RuntimeError."""
     lib = state.lib
-    args = [torch.from_numpy(np.ascontiguousarray(a, dt)).cuda() if a is not None else None for a, dt in inputs]
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
+    lead = [up(*a) if isinstance(a, tuple) else a for a in lead]
+    args = [up(a, dt) if a is not None else None for a, dt in inputs]
     outs = {k: torch.empty(*shape, dtype=dt, device="cuda") for k, shape, dt in outputs if shape is not None}
     args += [outs.get(k) for k, _, _ in outputs]
     if scratch:
         args.append(torch.empty(int(getattr(lib, "ArapFlow_" + scratch)(*dims)), dtype=torch.uint8, device="cuda"))
     torch.cuda.synchronize()
-    rc = getattr(lib, "ArapFlow_" + name)(state.handle, *dims, *[_dev_ptr(t) if t is not None else None for t in args])
+    ptr = lambda t: _dev_ptr(t) if isinstance(t, torch.Tensor) else t
+    rc = getattr(lib, "ArapFlow_" + name)(state.handle, *dims, *[ptr(t) for t in lead], *[ptr(t) for t in args])
     if rc == -1 and bad_args:
         raise ValueError("ArapFlow_%s: bad arguments" % name)
     if rc != 0:
@@ -540,3 +545,49 @@ def warp_layers_step(state, rgb, masks, flows_a, flows_b, step=True, occ=True):
                     ("step", (H, W, 2) if step else None, torch.float32), ("occlusion_step", (H, W) if occ else None, torch.uint8)],
                    "WarpLayersStepScratchBytes")
     return {"warped_rgb": None, **r}
+
+
+BG_OUTPUTS = ("out_rgb1", "out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")
+
+
+def _map6(m):
+    m = np.ascontiguousarray(m, np.float32).reshape(-1)
+    if m.shape != (6,):
+        raise ValueError("an affine map is six numbers (a, b, c, d, e, f)")
+    return (C.c_float * 6)(*m.tolist())
+
+
+def background_maps(M1, M2, lib=None):
+    """the point maps of two sampling maps (ArapFlow_BackgroundMaps, DESIGN.md "Moving background"): (G, Ginv), float32
+    [6] each, G = M2^-1 o M1 from frame 1 to frame 2 and Ginv back; the library's own bits.  Host only (no GPU, no
+    state)."""
+    lib = lib or capi.load()
+    g, gi = (C.c_float * 6)(), (C.c_float * 6)()
+    if lib.ArapFlow_BackgroundMaps(_map6(M1), _map6(M2), g, gi) != 0:
+        raise ValueError("ArapFlow_BackgroundMaps: non-finite or singular maps")
+    return np.array(g[:], np.float32), np.array(gi[:], np.float32)
+
+
+def background(state, bg, M1, M2, rgb1, mask_red, rgb2, cover2, flow, occ=None, bwd=None, occ_bwd=None, want=None):
+    """the moving background of a warped pair (ArapFlow_Background, DESIGN.md "Moving background").  bg u8[bgH,bgW,3];
+    M1, M2 six floats each; rgb1 / rgb2 u8[H,W,3], mask_red / cover2 u8[H,W] (frame-1 object: mask_red == 0, frame-2
+    object: cover2 != 0), flow / bwd f32[H,W,2], occ / occ_bwd u8[H,W] (numpy; any input but bg and the masks may be
+    None).  `want`: which of BG_OUTPUTS to compute; by default every one whose input is given.  Returns {name: array}."""
+    mask_red = np.ascontiguousarray(mask_red, np.uint8)
+    H, W = mask_red.shape
+    bg = np.ascontiguousarray(bg, np.uint8)
+    if bg.ndim != 3 or bg.shape[2] != 3:
+        raise ValueError("background: bg [bgH,bgW,3] expected")
+    given = dict(out_rgb1=rgb1, out_rgb2=rgb2, flow_full=flow, occ_full=occ, bwd_full=bwd, occ_bwd_full=occ_bwd)
+    if want is None:
+        want = [k for k in BG_OUTPUTS if given[k] is not None]
+    if set(want) - set(BG_OUTPUTS):
+        raise ValueError("background: unknown output in %r" % (want,))
+    shape = dict(out_rgb1=(H, W, 3), out_rgb2=(H, W, 3), flow_full=(H, W, 2), occ_full=(H, W), bwd_full=(H, W, 2),
+                 occ_bwd_full=(H, W))
+    dt = dict(flow_full=torch.float32, bwd_full=torch.float32)
+    return _warp_call(state, "Background", (W, H),
+                      [(rgb1, np.uint8), (mask_red, np.uint8), (rgb2, np.uint8), (cover2, np.uint8), (flow, np.float32),
+                       (occ, np.uint8), (bwd, np.float32), (occ_bwd, np.uint8)],
+                      [(k, shape[k] if k in want else None, dt.get(k, torch.uint8)) for k in BG_OUTPUTS],
+                      lead=[(bg, np.uint8), bg.shape[1], bg.shape[0], _map6(M1), _map6(M2)])

@@ -10,6 +10,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   deform_list, run_layers   ARAP/deformation/src/main.cpp:162-241  (arap_deform over a list)
   warp_files                ARAP/warping/src/main.cpp:302-336      (warp_image)
   cover_scale, fit_bg, add_bg            para_gen.py:36-61      (background compositing)
+  BgLine, parse_bg, bg_line, run_background, fit_bg_window, bg_maps    the `bg` line: moving background (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
@@ -36,12 +37,15 @@ _ANTIALIAS = getattr(Image, "LANCZOS", None) or Image.ANTIALIAS   # Image.ANTIAL
 # arap_deform
 # ------------------------------------------------------------------------------------------------------
 # A list line is the unit of work between para_gen.py, arap_deform.py and `arap_deform --serve` (C++ twin: parse_item in
-# host/arap_deform.cpp).  It is a solve line, SolveLine, or a `layers` line, the dict of parse_layers; parse_line reads
-# either from text, format_line writes it back, done_token is the path a worker reports it done by.
+# host/arap_deform.cpp).  It is a solve line, SolveLine, a `layers` line, the dict of parse_layers, or a `bg` line, BgLine;
+# parse_line reads any of them from text, format_line writes it back, done_token is the path a worker reports it done by.
 EXTRA_KEYS = ("bwd", "occ", "occ_bwd", "mid")
 MAX_SNAPSHOTS = 8            # ARAPFLOW_MAX_SNAPSHOTS of include/arap_opt.h
 LAYERS_WORD = "layers"
 LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2", "mid")
+BG_WORD = "bg"
+BG_IN_KEYS = ("occ", "bwd", "occ_bwd")                               # optional object-side inputs of a bg line
+BG_OUT_KEYS = ("occ_out", "bwd_out", "occ_bwd_out")                  # the full maps made from them
 
 
 class SolveLine(NamedTuple):
@@ -152,11 +156,82 @@ def layers_line(rgb, layers, out):
     return " ".join(tok + ["%s=%s" % (k, out[k]) for k in LAYER_KEYS if out.get(k)])
 
 
+class BgLine(NamedTuple):
+    """a `bg` line (DESIGN.md "Moving background"), recognised by its first word: the full-frame pass of one pair
+        bg BG.png RGB1.png MASK1.png RGB2.png MASK2.png FLOW.flo m=<12 numbers> [occ=IN] [bwd=IN] [occ_bwd=IN]
+           out=RGB1_OUT.png,RGB2_OUT.png,FLOW_OUT.flo [occ_out=..] [bwd_out=..] [occ_bwd_out=..]
+    MASK1: the solver's mask (red 0 = object); MASK2: a warped mask (non-zero = object).  `m`: M1 then M2, twelve
+    float32 written with %.9g, comma separated.  `out`: three paths, any of them empty (not wanted).  `inputs` / `outs`:
+    {key: path} over BG_IN_KEYS / BG_OUT_KEYS; an output needs its input.  At least one output."""
+    bg: str
+    rgb1: str
+    mask1: str
+    rgb2: str
+    mask2: str
+    flow: str
+    m: tuple
+    inputs: dict
+    out: tuple
+    outs: dict
+
+
+def parse_bg(tokens):
+    if len(tokens) < 7 or tokens[0] != BG_WORD:
+        raise ValueError("not a bg line: %r" % " ".join(tokens))
+    m, out, inputs, outs = None, ("", "", ""), {}, {}
+    for t in tokens[7:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v):
+            raise ValueError("bg line: bad token %r" % t)
+        if k == "m":
+            try:
+                m = tuple(float(np.float32(float(q))) for q in v.split(","))
+            except ValueError:
+                m = ()
+            if len(m) != 12:
+                raise ValueError("bg line: m= takes 12 numbers, M1 then M2: %r" % t)
+        elif k == "out":
+            out = tuple(v.split(","))
+            if len(out) != 3:
+                raise ValueError("bg line: out= takes RGB1_OUT,RGB2_OUT,FLOW_OUT (a place may be empty): %r" % t)
+        elif k in BG_IN_KEYS:
+            inputs[k] = v
+        elif k in BG_OUT_KEYS:
+            outs[k] = v
+        else:
+            raise ValueError("bg line: bad token %r" % t)
+    if m is None:
+        raise ValueError("bg line without m=: %r" % " ".join(tokens))
+    for k in outs:
+        if k[:-len("_out")] not in inputs:
+            raise ValueError("bg line: %s= needs %s=" % (k, k[:-len("_out")]))
+    if not any(out) and not outs:
+        raise ValueError("bg line without an output: %r" % " ".join(tokens))
+    return BgLine(*tokens[1:7], m=m, inputs=inputs, out=out, outs=outs)
+
+
+def bg_line(item):
+    """the inverse of parse_bg; optional tokens in the order of BG_IN_KEYS, out=, BG_OUT_KEYS"""
+    tok = [BG_WORD] + list(item[:6]) + ["m=" + ",".join("%.9g" % v for v in item.m)]
+    tok += ["%s=%s" % (k, item.inputs[k]) for k in BG_IN_KEYS if item.inputs.get(k)]
+    if any(item.out):
+        tok.append("out=" + ",".join(item.out))
+    return " ".join(tok + ["%s=%s" % (k, item.outs[k]) for k in BG_OUT_KEYS if item.outs.get(k)])
+
+
+def bg_outputs(item):
+    """every file a bg line writes, in the fixed order out= (three places), then BG_OUT_KEYS"""
+    return [q for q in item.out if q] + [item.outs[k] for k in BG_OUT_KEYS if item.outs.get(k)]
+
+
 def parse_line(line):
-    """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`"""
+    """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, or a
+    BgLine when it is `bg`"""
     tok = line.split() if isinstance(line, str) else list(line)
     if tok and tok[0] == LAYERS_WORD:
         return parse_layers(tok)
+    if tok and tok[0] == BG_WORD:
+        return parse_bg(tok)
     if len(tok) < 6:
         raise ValueError("list line needs 6 paths: %r" % line)
     return SolveLine(*tok[:6], extra=parse_extra(tok[6:]))
@@ -166,11 +241,16 @@ def format_line(item):
     """the inverse of parse_line: the text of a list line, optional tokens in the order of extra_tokens / layers_line"""
     if isinstance(item, SolveLine):
         return " ".join(list(item[:6]) + extra_tokens(item.extra))
+    if isinstance(item, BgLine):
+        return bg_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
-    """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token"""
+    """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
+    first of a bg line's bg_outputs"""
+    if isinstance(item, BgLine):
+        return bg_outputs(item)[0]
     return item.flow if isinstance(item, SolveLine) else next(iter(item["out"].values()))
 
 
@@ -208,6 +288,39 @@ def run_layers(state, spec):
         save_occ(r["occlusion_bwd"], out["occ_bwd"])
     if "occ" in out:
         save_occ(r["occlusion"], out["occ"])
+
+
+def run_background(state, spec):
+    """one `bg` line: read the background picture, the pair's frames, masks, flow and the object-side maps the line
+    names, one opt.background, write what the line asks for (RGB: RGB PNG; flows: .flo; occlusions: 8-bit L PNG)"""
+    from . import opt
+    bg, rgb1, rgb2 = load_rgb(spec.bg), load_rgb(spec.rgb1), load_rgb(spec.rgb2)
+    mask_red = load_mask_red(spec.mask1)
+    cover2 = np.where(load_mask_red(spec.mask2) != 0, 255, 0).astype(np.uint8)
+    fl = flo.flow_read(spec.flow)
+    inp = dict(occ=None, bwd=None, occ_bwd=None)
+    if "occ" in spec.inputs:
+        inp["occ"] = np.array(Image.open(spec.inputs["occ"]).convert("L"))
+    if "bwd" in spec.inputs:
+        inp["bwd"] = flo.flow_read(spec.inputs["bwd"])
+    if "occ_bwd" in spec.inputs:
+        inp["occ_bwd"] = np.array(Image.open(spec.inputs["occ_bwd"]).convert("L"))
+    H, W = mask_red.shape
+    for a in (rgb1, rgb2, cover2, fl) + tuple(v for v in inp.values() if v is not None):
+        if a.shape[:2] != (H, W):
+            raise ValueError("bg line: image, mask and flow sizes differ")
+    names = dict(zip(("out_rgb1", "out_rgb2", "flow_full"), spec.out))
+    names.update(occ_full=spec.outs.get("occ_out"), bwd_full=spec.outs.get("bwd_out"),
+                 occ_bwd_full=spec.outs.get("occ_bwd_out"))
+    want = [k for k in opt.BG_OUTPUTS if names.get(k)]
+    r = opt.background(state, bg, spec.m[:6], spec.m[6:], rgb1, mask_red, rgb2, cover2, fl, want=want, **inp)
+    for k in want:
+        if k.startswith("out_rgb"):
+            Image.fromarray(r[k]).save(names[k])
+        elif k in ("flow_full", "bwd_full"):
+            flo.flow_write(names[k], r[k])
+        else:
+            save_occ(r[k], names[k])
 
 
 def owner_flow(masks, flows):
@@ -464,17 +577,63 @@ def cover_scale(bg_hw, im_hw, u):
     return int(bh * (u * cover)), int(bw * (u * cover))
 
 
-def fit_bg(bg, im, rng=rn):
-    """A random window of an enlarged copy of `bg`, as large as `im`.  Three draws from `rng`, in this order (so that a
-    seeded run picks the windows the reference would): the enlargement u = uniform(1, 2), then the window's top row and
-    its left column, each randint over every position that keeps the window inside (both ends included)."""
+def fit_bg_window(bg, im, rng=rn):
+    """The enlarged copy of `bg` and the (left, top) of a random window of it as large as `im`.  Three draws from `rng`,
+    in this order (so that a seeded run picks the windows the reference would): the enlargement u = uniform(1, 2), then
+    the window's top row and its left column, each randint over every position that keeps the window inside (both ends
+    included)."""
     ih, iw = im.shape[:2]
     u = rng.uniform(1, 2)
     nh, nw = cover_scale(bg.shape[:2], (ih, iw), u)
     big = np.asarray(Image.fromarray(bg).resize((nw, nh), _ANTIALIAS))
     top = rng.randint(0, big.shape[0] - ih)
     left = rng.randint(0, big.shape[1] - iw)
+    return big, (left, top)
+
+
+def fit_bg(bg, im, rng=rn):
+    """A random window of an enlarged copy of `bg`, as large as `im` (fit_bg_window's draws)."""
+    ih, iw = im.shape[:2]
+    big, (left, top) = fit_bg_window(bg, im, rng)
     return big[top:top + ih, left:left + iw, :]
+
+
+BG_MOTION_PER_FD = (2.0, 0.01, 3.0)      # degrees, log-scale, pixels per frame of distance: SURVEY 8d's object motion
+
+
+def _affine_compose(A, B):
+    """A o B of two six-number affine maps (first B, then A), in float64"""
+    a, b, c, d, e, f = A
+    g, h, i, j, k, l = B
+    return (a * g + b * j, a * h + b * k, a * i + b * l + c, d * g + e * j, d * h + e * k, d * i + e * l + f)
+
+
+def bg_maps(win_left, win_top, frame_wh, bg_wh, rng, fd=1, strength=1.0):
+    """The sampling maps (M1, M2) of a pair over the enlarged background (DESIGN.md "Moving background"), float32 [6]
+    each.  M1 is the window translation.  M2 = M1 o S with S a similarity about the frame centre: rotation, log-scale
+    and a shift in x and y, drawn from `rng` in this order, uniformly within strength x BG_MOTION_PER_FD x fd.  While a
+    frame corner maps outside [0, bgW - 1] x [0, bgH - 1] the parameters are halved, up to 8 times; then M2 = M1."""
+    W, H = frame_wh
+    bw, bh = bg_wh
+    M1 = (1.0, 0.0, float(win_left), 0.0, 1.0, float(win_top))
+    lim = [strength * fd * v for v in BG_MOTION_PER_FD]
+    rot, lsc = rng.uniform(-lim[0], lim[0]), rng.uniform(-lim[1], lim[1])
+    sx, sy = rng.uniform(-lim[2], lim[2]), rng.uniform(-lim[2], lim[2])
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    M2 = None
+    for _ in range(9):
+        t, sc = np.deg2rad(rot), np.exp(lsc)
+        a, b = sc * np.cos(t), sc * np.sin(t)
+        S = (a, -b, cx - a * cx + b * cy + sx, b, a, cy - b * cx - a * cy + sy)
+        cand = np.asarray(_affine_compose(M1, S), np.float32)
+        m = cand.astype(np.float64)
+        corners = [(m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]) for x in (0, W - 1) for y in (0, H - 1)]
+        if all(0 <= px <= bw - 1 and 0 <= py <= bh - 1 for px, py in corners):
+            M2 = cand
+            break
+        rot, lsc, sx, sy = rot / 2, lsc / 2, sx / 2, sy / 2
+    M1 = np.asarray(M1, np.float32)
+    return M1, (M2 if M2 is not None else M1.copy())
 
 
 def add_bg(im, mk, bgim, bgval=0):

@@ -359,6 +359,34 @@ int ArapFlow_WarpLayersStep(Opt_State* state, unsigned W, unsigned H, unsigned n
                             const void* masks_red, const void* flows_a, const void* flows_b, void* out_rgb,
                             void* out_mask, void* out_step, void* out_occ, void* scratch);
 
+/* Moving background (DESIGN.md "Moving background"): the point maps between two frames whose background is sampled
+ * through the affine maps M1, M2 (six floats (a, b, c, d, e, f): pixel (x, y) shows the background point
+ * (a x + b y + c, d x + e y + f)).  G = M2^-1 o M1 (frame 1 -> frame 2) and Ginv = M1^-1 o M2, derived in double and
+ * rounded once to float; bit-equal M1 and M2 give the exact identity for both.  Host only.  Returns 0, or -1 on a null
+ * pointer, a non-finite coefficient or a linear part with zero determinant. */
+int ArapFlow_BackgroundMaps(const float M1[6], const float M2[6], float G[6], float Ginv[6]);
+
+/* Full-frame RGB, flow and occlusion behind the objects of a warped pair, on DEVICE buffers (M1, M2: host).  bg
+ * uint8[bgH][bgW][3] is the background picture; frame 1 has its object where mask_red uint8[H][W] is 0, frame 2 where
+ * cover2 uint8[H][W] (a warp's out_mask) is not 0.  Outputs, each NULL when not wanted -- an output that is NULL is not
+ * computed and its input not read:
+ *   out_rgb1 / out_rgb2 uint8[H][W][3]   rgb1 / rgb2 on the object, else the bilinear sample (clamp to edge) of bg at
+ *                                        M1 (x, y) / M2 (x, y)
+ *   flow_full float[H][W][2]             `flow` on the frame-1 object, else G (x, y) - (x, y)
+ *   occ_full uint8[H][W]                 `occ` on the frame-1 object, else 255 where G (x, y) leaves the frame or cover2
+ *                                        is set at its nearest pixel
+ *   bwd_full float[H][W][2]              `bwd` on the frame-2 object, else Ginv (x, y) - (x, y)
+ *   occ_bwd_full uint8[H][W]             `occ_bwd` on the frame-2 object, else 255 where Ginv (x, y) leaves the frame or
+ *                                        mask_red is 0 at its nearest pixel
+ * No output may alias an input.  Needs no scratch.  Asynchronous on the state's stream.  Returns 0; -1 on bad arguments:
+ * a null state, bg, mask_red or cover2, a zero size, W * H >= 2^31, an output whose input (rgb1, rgb2, flow, occ, bwd,
+ * occ_bwd in the order above) is NULL, no output at all, or maps ArapFlow_BackgroundMaps refuses; else a HIP error code. */
+int ArapFlow_Background(Opt_State* state, unsigned W, unsigned H, const void* bg, unsigned bgW, unsigned bgH,
+                        const float M1[6], const float M2[6], const void* rgb1, const void* mask_red, const void* rgb2,
+                        const void* cover2, const void* flow, const void* occ, const void* bwd, const void* occ_bwd,
+                        void* out_rgb1, void* out_rgb2, void* flow_full, void* occ_full, void* bwd_full,
+                        void* occ_bwd_full);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
                      [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
+                     [--bg_dir DIR [--bg_motion [STRENGTH]]]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -27,6 +28,10 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     GPU at the same time) or --matches DIR holding precomputed `x1 y1 x2 y2 ...` lines at DIR/<seq>/<frame>.txt.
   * --bg_dir replaces the hard-coded 'data/naturedata' (para_gen.py:16); without it frames keep a black
     background.
+  * --bg_motion (needs --bg_dir) moves the background between the two frames (DESIGN.md "Moving background"): frame 1 is
+    composited as before; the warped frame's background, the full-frame flow OUT/FlowFull and, with --occ / --occ_layers
+    / --bwd_flow, OUT/OccFull, OUT/FlowBwdFull, OUT/OccBwdFull come from one `bg` line per pair, handed to the pair's
+    worker once its solves (and flatten / layers line) are done.
 """
 import argparse
 import json
@@ -40,6 +45,7 @@ import subprocess
 import sys
 import threading
 import time
+import dataclasses
 from dataclasses import dataclass
 from multiprocessing import Pool
 
@@ -57,7 +63,9 @@ bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, -
 mid_dir = "Mid"                    # --mid K: in-between frames from the constraint ramp (addition)
 NUM_ITER = 19                      # the ramp length of the ARAP drivers (main.cpp:215-221): what --mid K spreads over
 LAYERS_OCC = "occl_gen"            # --multseg --occ_layers: the frame's forward occlusion, made by a `layers` line
-EXT_KEYS = list(pipeline.EXTRA_OF) + [LAYERS_OCC]                     # every optional output of a frame
+full_dir, occ_full_dir, bwd_full_dir, occ_bwd_full_dir = "FlowFull", "OccFull", "FlowBwdFull", "OccBwdFull"   # --bg_motion
+FULL_KEYS = ["flowfull_gen", "occfull_gen", "bwdfull_gen", "occbwdfull_gen"]      # --bg_motion: the full-frame maps
+EXT_KEYS = list(pipeline.EXTRA_OF) + [LAYERS_OCC] + FULL_KEYS         # every optional output of a frame
 CPP_BIN = osp.join(HERE, "arap_flow_amd", "bin", "arap_deform")
 
 
@@ -145,9 +153,13 @@ class Frame:
     line: pipeline.SolveLine       # the pair's list line; its outputs are the frame's outputs
     segs: list                     # --multseg: the per-segment lines that are solved in its place, else None
     layers: dict                   # --occ_layers: the frame's layers line (pipeline.parse_layers), else None
-    bg: np.ndarray                 # the background fitted to the frame, or None
+    bg: object                     # the background fitted to the frame (an array), or None; --bg_motion: the path of
+                                   # the enlarged background picture
     remove: bool                   # --multseg: delete the segments' files once they are merged
     left: int = 0                  # main: solves of this frame not yet reported done
+    motion: object = None          # --bg_motion: the pair's bg line (pipeline.BgLine), handed out after finish_frame
+    stage: str = "solves"          # main: what the workers hold of this frame: solves -> layers -> bg
+    tmp: tuple = ()                # --bg_motion: the bg line's own input files, deleted when it is done
 
     @property
     def solves(self):
@@ -184,7 +196,15 @@ def prepare_pair(args):
                 bgim = None
         except Exception:
             bgim = None
-    if bgim is not None:
+    big = None
+    if bgim is not None and getattr(flags, "bg_motion", None) is not None:
+        rng = rn.Random(_pair_id(seq, stem))
+        big, (left, top) = pipeline.fit_bg_window(bgim, im1, rng=rng)          # the window and frame 1 of a run without
+        H, W = im1.shape[:2]
+        maps = pipeline.bg_maps(left, top, (W, H), (big.shape[1], big.shape[0]), rng, flags.fd, flags.bg_motion)
+        out1 = pipeline.add_bg(im1, mk1, big[top:top + H, left:left + W, :])
+        bgim = None
+    elif bgim is not None:
         bgim = pipeline.fit_bg(bgim, im1, rng=rn.Random(_pair_id(seq, stem)))
         out1 = pipeline.add_bg(im1, mk1, bgim)
     else:
@@ -209,11 +229,35 @@ def prepare_pair(args):
         if midl:
             out["mid"] = pipeline.mid_token(midl, p["midl_gen"])
         layers = dict(rgb=line.rgb, layers=[(sg.mask, sg.flow) for sg in segs], out=out)
-    return Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
+    rec = Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
+    if big is not None:
+        # the bg line's own inputs, beside the pair's constraints: the enlarged picture as a PNG (the worker's codec),
+        # with --multseg the union mask (object where any solved segment is object), and the line itself
+        stem_tmp = osp.splitext(p["cstr_tmp"])[0]
+        rec.bg = stem_tmp + "_bg.png"
+        Image.fromarray(big).save(rec.bg)
+        mask1 = line.mask
+        if segs is not None:
+            mask1 = stem_tmp + "_bgmask.png"
+            masks = [np.array(Image.open(sg.mask)) for sg in segs]
+            Image.fromarray(np.minimum.reduce(masks) if masks else np.full_like(mk1, pipeline.ARAP_BG, np.uint8)).save(mask1)
+        occ_in = p.get("occ_gen", p.get(LAYERS_OCC))
+        inputs = {k: v for k, v in dict(occ=occ_in, bwd=p.get("bwd_gen"), occ_bwd=p.get("occbwd_gen")).items() if v}
+        outs = {k + "_out": p[g] for k, g in dict(occ="occfull_gen", bwd="bwdfull_gen", occ_bwd="occbwdfull_gen").items()
+                if k in inputs and g in p}
+        rec.motion = pipeline.BgLine(rec.bg, line.rgb, mask1, line.out_rgb, line.out_mask, line.flow,
+                                     m=tuple(float(v) for v in np.concatenate(maps)), inputs=inputs,
+                                     out=("", line.out_rgb, p["flowfull_gen"]), outs=outs)
+        open(stem_tmp + "_bg.txt", "w").write(pipeline.format_line(rec.motion))
+        rec.tmp = tuple(q for q in (rec.bg, mask1 if segs is not None else None, stem_tmp + "_bg.txt") if q)
+    return rec
 
 
 def finish_frame(rec):
-    """para_gen.py:202-212 for one Frame whose solve(s) are done: flatten the segments, composite the background"""
+    """para_gen.py:202-212 for one Frame whose solve(s) are done: flatten the segments, composite the background (a
+    --bg_motion pair's comes from its bg line afterwards: rec.bg is then a path, not the fitted array)"""
+    if not isinstance(rec.bg, np.ndarray):
+        rec = dataclasses.replace(rec, bg=None)
     if rec.layers is not None and "mid" in rec.layers["out"]:       # --mid_layers: the layers line is done
         steps, prefix = pipeline.parse_mid(rec.layers["out"]["mid"])
         if rec.bg is not None:                              # the in-between frames get the pair's background too
@@ -410,7 +454,8 @@ def scan(flags, input_root, output_root):
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
-                                                           obw=occ_bwd_dir, occ=occ_dir, mid=mid_dir).items()}
+                                                           obw=occ_bwd_dir, occ=occ_dir, mid=mid_dir, ful=full_dir,
+                                                           ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
     all_paths = []
     for root, dirs, _ in os.walk(rgb_org):
@@ -439,6 +484,13 @@ def scan(flags, input_root, output_root):
                     e[LAYERS_OCC] = osp.join(roots["occ"], seq, f + ".png")
                 if getattr(flags, "mid", 0):
                     e["mid_gen"] = osp.join(roots["mid"], seq, f)
+                if getattr(flags, "bg_motion", None) is not None:       # the full-frame maps of what the run asks for
+                    e["flowfull_gen"] = osp.join(roots["ful"], seq, f + ".flo")
+                    if "occ_gen" in e or LAYERS_OCC in e:
+                        e["occfull_gen"] = osp.join(roots["ofu"], seq, f + ".png")
+                    if "bwd_gen" in e:
+                        e.update(bwdfull_gen=osp.join(roots["bfu"], seq, f + ".flo"),
+                                 occbwdfull_gen=osp.join(roots["obf"], seq, f + ".png"))
                 e = {k: osp.abspath(v) for k, v in e.items()}
                 e["_seq"], e["_stem"] = seq, f
                 if getattr(flags, "mid_layers", 0):
@@ -490,6 +542,8 @@ def main(flags):
     if flags.bg_dir:
         for root, _, files in os.walk(flags.bg_dir):
             bg_paths += [osp.join(root, f) for f in files if f.upper().endswith((".PNG", ".JPG", ".JPEG"))]
+    if getattr(flags, "bg_motion", None) is not None and not bg_paths:
+        raise AssertionError("--bg_motion: no background picture (.png, .jpg) under %s" % flags.bg_dir)
     all_paths = scan(flags, input_root, output_root)
     print("Scanning data to be processed\t\t%d files [Done]" % len(all_paths))
     os.makedirs(output_root, exist_ok=True)
@@ -515,16 +569,28 @@ def main(flags):
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
     frames = {}                                        # done token of a line a worker holds -> its Frame
     posts, lock = [], threading.Lock()
-    counts = dict(solves_done=0, frames_done=0, layers_done=0)
+    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0)
 
     def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
         frames[pipeline.done_token(item)] = rec
         put(pipeline.format_line(item))
 
-    def on_done(path):                                 # a worker thread: one solve (or one layers line) finished
+    def bg_ready(rec):                                 # the pool's result thread: finish_frame of a --bg_motion pair is done
+        with lock:
+            rec.stage = "bg"
+            hand_out(rec, rec.motion, workers.put_owed)
+
+    def on_done(path):                                 # a worker thread: one solve (or one layers / bg line) finished
         with lock:
             rec = frames.pop(path)
-            if rec.left == 0:                          # its layers line: the segment files may go now
+            if rec.stage == "bg":                      # its bg line: the frame is complete
+                counts["bg_done"] += 1
+                if rec.remove:
+                    for q in rec.tmp:
+                        if osp.exists(q):
+                            os.remove(q)
+                return
+            if rec.stage == "layers":                  # its layers line: the segment files may go now
                 counts["layers_done"] += 1
             else:
                 counts["solves_done"] += 1
@@ -532,10 +598,15 @@ def main(flags):
                 if rec.left > 0:
                     return
                 if rec.layers is not None:             # last segment done: the frame's layers line, then finish_frame
+                    rec.stage = "layers"
                     hand_out(rec, rec.layers, workers.put_owed)
                     return
             counts["frames_done"] += 1
-            posts.append(pool.apply_async(finish_frame, (rec,)))
+            if rec.motion is None:
+                posts.append(pool.apply_async(finish_frame, (rec,)))
+            else:                                      # then the pair's bg line, over the flattened files
+                posts.append(pool.apply_async(finish_frame, (rec,), callback=lambda _, rec=rec: bg_ready(rec),
+                                              error_callback=lambda e: workers._fail("finish_frame failed: %r" % (e,))))
 
     # --dm_bin builtin: the matcher and the solver must not share a GPU at the same time (the solver's resident kernel
     # needs the whole chip: arap_resident.h), so the run has two phases -- every pair is prepared and matched first
@@ -561,6 +632,8 @@ def main(flags):
             rec.left = len(rec.solves)
             if rec.layers is not None:
                 workers.owe()
+            if rec.motion is not None:
+                workers.owe()
             with lock:
                 for ln in rec.solves:
                     hand_out(rec, ln, workers.put)
@@ -579,12 +652,12 @@ def main(flags):
     open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
     # all_files.list stays as it is; the extra outputs get their own list
     if (getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False) or
-            getattr(flags, "mid", 0) or getattr(flags, "mid_layers", 0)):
+            getattr(flags, "mid", 0) or getattr(flags, "mid_layers", 0) or getattr(flags, "bg_motion", None) is not None):
         ext = [" ".join(ln) for ln in ext_paths if all(osp.exists(q) for q in ln)]
         open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
-                 layers_done=counts["layers_done"],
+                 layers_done=counts["layers_done"], bg_done=counts["bg_done"],
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -642,6 +715,11 @@ def parse(argv=None):
                         help="Path to the deep matching binary, or 'builtin': this repo's GPU matcher (libarapmatch.so)")
     parser.add_argument("--matches", default=None, help="directory of precomputed matches (instead of --dm_bin)")
     parser.add_argument("--bg_dir", default=None, help="directory of background images")
+    parser.add_argument("--bg_motion", type=float, nargs="?", const=1.0, default=None, metavar="STRENGTH",
+                        help="with --bg_dir: move the background between the two frames (a random similarity, STRENGTH "
+                             "times 2 degrees, 1 %% scale and 3 px per frame of --fd; 1.0 when given bare) and write the "
+                             "full-frame flow OUT/FlowFull/<seq>/<frame>.flo and, with --occ / --occ_layers / --bwd_flow, "
+                             "OUT/OccFull, OUT/FlowBwdFull, OUT/OccBwdFull (DESIGN.md \"Moving background\")")
     parser.add_argument("--bwd_flow", action="store_true", default=False,
                         help="also write the backward flow OUT/FlowBwd/<seq>/<frame>.flo and the backward occlusion "
                              "OUT/OccBwd/<seq>/<frame>.png (DESIGN.md)")
@@ -674,6 +752,17 @@ def parse(argv=None):
     if (flags.bwd_flow or flags.occ) and not own_arap_bin(flags.arap_bin):
         parser.error("--bwd_flow / --occ need this repository's arap_deform (C++ or arap_deform.py): a foreign "
                      "--arap_bin does not write the extra outputs")
+    if flags.bg_motion is not None:
+        if not flags.bg_dir:
+            parser.error("--bg_motion needs --bg_dir: there is no background to move")
+        if flags.mid or flags.mid_layers:
+            parser.error("--bg_motion cannot be combined with --mid / --mid_layers: the background motion of an "
+                         "in-between frame needs the motion interpolated per snapshot, which is not built")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--bg_motion needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin "
+                         "does not know the bg line")
+        if not (flags.bg_motion >= 0 and np.isfinite(flags.bg_motion)):
+            parser.error("--bg_motion STRENGTH must be a finite number >= 0")
     flags.mid_steps = []
     if flags.mid:
         if flags.multseg:
