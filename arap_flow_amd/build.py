@@ -63,19 +63,21 @@ def build_match(force=False, verbose=False):
 HOST_DIR = os.path.join(HERE, "host")
 BIN_DIR = os.path.join(HERE, "bin")
 HOST_PROGRAMS = {"arap_deform": ["arap_deform.cpp", "png_io.cpp"], "warp_image": ["warp_image.cpp", "png_io.cpp"],
-                 "png_tool": ["png_tool.cpp", "png_io.cpp"]}
+                 "png_tool": ["png_tool.cpp", "png_io.cpp"], "line_tool": ["line_tool.cpp"]}
+HOST_DEPS = sorted(os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR))        # any header may be included
+HOST_DEPS += [os.path.join(HERE, "..", "include", "arap_opt.h"), OUT]
 
 
 def build_host(force=False, verbose=False):
     """C++ host programs (the reference's drivers are C++: ARAP/deformation/src/main.cpp, ARAP/warping/src/main.cpp)
-    linked against libarapopt.so: arap_flow_amd/bin/arap_deform, arap_flow_amd/bin/warp_image."""
+    linked against libarapopt.so: arap_flow_amd/bin/arap_deform, arap_flow_amd/bin/warp_image, and the two test helpers
+    png_tool and line_tool.  A program is re-built when any file of host/, the library or its header is newer."""
     build(force=False)
     os.makedirs(BIN_DIR, exist_ok=True)
     outs = []
     for name, srcs in HOST_PROGRAMS.items():
         out = os.path.join(BIN_DIR, name)
-        deps = [os.path.join(HOST_DIR, f) for f in srcs + ["png_io.h", "flo_io.h"]] + [OUT]
-        if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
+        if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in HOST_DEPS):
             outs.append(out)
             continue
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"] + \

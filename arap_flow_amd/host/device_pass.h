@@ -1,0 +1,109 @@
+// device_pass.h -- what the synchronous passes of the host programs share (warp_image; the layers and bg lines of
+// arap_deform): one device allocation laid out part by part, one table of the outputs a pass may write, one file writer.
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime_api.h>
+
+#include "flo_io.h"
+#include "png_io.h"
+
+enum class FileKind { flo, rgb, mask1, gray8 };      // .flo float2; RGB PNG; 1-bit PNG of a 0/255 mask; 8-bit L PNG
+
+inline size_t bytes_per_pixel(FileKind kind) { return kind == FileKind::flo ? 8 : kind == FileKind::rgb ? 3 : 1; }
+
+// one output file of [h][w] pixels; a failure is reported here, in the codec's words
+inline bool save(FileKind kind, const std::string& path, int w, int h, const void* data)
+{
+    if (kind == FileKind::flo) return arapio::write_flo(path, (const float*)data, w, h);      // (says so itself)
+    const uint8_t* px = (const uint8_t*)data;
+    std::string err;
+    const bool ok = kind == FileKind::rgb     ? arapio::write_png_rgb(path, w, h, px, err)
+                    : kind == FileKind::mask1 ? arapio::write_png_mask1(path, w, h, px, err)
+                                              : arapio::write_png_gray8(path, w, h, px, err);
+    if (!ok) printf("%s\n", err.c_str());
+    return ok;
+}
+
+// One hipMalloc per pass.  Lay the parts out first -- take(), or stage() for an input that is there already; each part
+// starts 256-byte aligned, the library's rule for scratch and enough for float2 -- then alloc(), then upload().  A part
+// is named by what take() returned; kNone names no part and has the address NULL.  Freed with the object.
+class DeviceArena {
+  public:
+    static constexpr size_t kNone = ~(size_t)0;
+    DeviceArena() = default;
+    DeviceArena(const DeviceArena&) = delete;
+    DeviceArena& operator=(const DeviceArena&) = delete;
+    ~DeviceArena() { if (base_) (void)hipFree(base_); }
+    size_t take(size_t bytes)
+    {
+        const size_t part = size_;
+        size_ = (size_ + bytes + 255) / 256 * 256;
+        return part;
+    }
+    size_t stage(const void* src, size_t bytes)
+    {
+        staged_.push_back(Staged{take(bytes), src, bytes});
+        return staged_.back().part;
+    }
+    hipError_t alloc() { return hipMalloc((void**)&base_, size_ ? size_ : 256); }
+    hipError_t upload() const                              // every staged input
+    {
+        hipError_t e = hipSuccess;
+        for (const Staged& s : staged_)
+            if (e == hipSuccess) e = copy_in(s.part, s.src, s.bytes);
+        return e;
+    }
+    hipError_t copy_in(size_t part, const void* src, size_t bytes) const
+    {
+        return hipMemcpy(at(part), src, bytes, hipMemcpyHostToDevice);
+    }
+    char* at(size_t part) const { return part == kNone ? nullptr : base_ + part; }
+
+  private:
+    struct Staged { size_t part; const void* src; size_t bytes; };
+    char* base_ = nullptr;
+    size_t size_ = 0;
+    std::vector<Staged> staged_;
+};
+
+// The outputs a pass may write, one row each, in the order their files are written.  The row gives the library call its
+// "pointer or NULL", then downloads and writes that same part, so an output cannot end in another one's file.
+class OutputTable {
+  public:
+    OutputTable(DeviceArena& arena, int w, int h) : arena_(arena), w_(w), h_(h) {}
+    // a row; an empty path (not wanted) takes no device memory unless `keep` (set_path names it later, per call)
+    size_t add(FileKind kind, const std::string& path, bool keep = false)
+    {
+        rows_.push_back(Row{kind, path, path.empty() && !keep ? DeviceArena::kNone : arena_.take(bytes(kind)), {}});
+        return rows_.size() - 1;
+    }
+    void set_path(size_t row, const std::string& path) { if (rows_[row].part != DeviceArena::kNone) rows_[row].path = path; }
+    void* dev(size_t row) const { return rows_[row].path.empty() ? nullptr : arena_.at(rows_[row].part); }
+    hipError_t download()                                  // every wanted row, once the call has been waited for
+    {
+        hipError_t e = hipSuccess;
+        for (Row& r : rows_) {
+            if (r.path.empty() || e != hipSuccess) continue;
+            r.data.resize(bytes(r.kind));
+            e = hipMemcpy(r.data.data(), arena_.at(r.part), r.data.size(), hipMemcpyDeviceToHost);
+        }
+        return e;
+    }
+    bool write() const                                     // stops at the first file that could not be written
+    {
+        for (const Row& r : rows_)
+            if (!r.path.empty() && !save(r.kind, r.path, w_, h_, r.data.data())) return false;
+        return true;
+    }
+
+  private:
+    struct Row { FileKind kind; std::string path; size_t part; std::vector<uint8_t> data; };
+    size_t bytes(FileKind kind) const { return bytes_per_pixel(kind) * (size_t)w_ * (size_t)h_; }
+    DeviceArena& arena_;
+    const int w_, h_;
+    std::vector<Row> rows_;
+};

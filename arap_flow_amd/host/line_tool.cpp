@@ -1,0 +1,57 @@
+// line_tool -- test helper for the list-line grammar (list_line.h): reads lines on stdin and prints, per line,
+//   SKIP                      the line is none of the forms
+//   BAD                       a form, refused (after parse_item's own "Invalid ..." line)
+//   <canonical> done=<path>   what was read, written as pipeline.format_line writes it, and the path the line is
+//                             reported done by (pipeline.done_token)
+#include <iostream>
+
+#include "list_line.h"
+
+struct Canon {
+    std::string text;
+    void word(const std::string& s) { text += (text.empty() ? "" : " ") + s; }
+    void token(const char* key, const std::string& value)              // left out when empty, as format_line does
+    {
+        if (!value.empty()) word(std::string(key) + "=" + value);
+    }
+};
+
+static std::string canonical(const Item& it)
+{
+    Canon c;
+    if (it.kind == Item::Kind::Solve) {
+        const SolvePaths& q = it.solve;
+        for (const std::string* s : {&q.rgb, &q.mask, &q.constraints, &q.flow, &q.warped_rgb, &q.warped_mask}) c.word(*s);
+        c.token("bwd", q.bwd); c.token("occ", q.occ); c.token("occ_bwd", q.occ_bwd); c.token("mid", q.mid.text);
+    } else if (it.kind == Item::Kind::Layers) {
+        const LayersSpec& q = it.layers;
+        c.word("layers"); c.word(q.rgb); c.word(std::to_string(q.masks.size()));
+        for (size_t l = 0; l < q.masks.size(); ++l) { c.word(q.masks[l]); c.word(q.flows[l]); }
+        c.token("occ", q.occ); c.token("bwd", q.bwd); c.token("occ_bwd", q.occ_bwd); c.token("rgb2", q.rgb2);
+        c.token("mask2", q.mask2); c.token("mid", q.mid.text);
+    } else {
+        const BgSpec& q = it.bg;
+        c.word("bg");
+        for (const std::string* s : {&q.bg, &q.rgb1, &q.mask1, &q.rgb2, &q.mask2, &q.flow}) c.word(*s);
+        std::string m;
+        for (int n = 0; n < 12; ++n) {
+            char num[32];
+            snprintf(num, sizeof(num), "%s%.9g", n ? "," : "", q.m[n]);
+            m += num;
+        }
+        c.token("m", m); c.token("occ", q.occ); c.token("bwd", q.bwd); c.token("occ_bwd", q.occ_bwd);
+        if (!(q.out_rgb1 + q.out_rgb2 + q.out_flow).empty()) c.word("out=" + q.out_rgb1 + "," + q.out_rgb2 + "," + q.out_flow);
+        c.token("occ_out", q.out_occ); c.token("bwd_out", q.out_bwd); c.token("occ_bwd_out", q.out_occ_bwd);
+    }
+    return c.text + " done=" + done_path(it);
+}
+
+int main()
+{
+    for (std::string line; std::getline(std::cin, line);) {
+        Item it;
+        const Parsed p = parse_item(line, it);
+        printf("%s\n", p == Parsed::Skip ? "SKIP" : p == Parsed::Bad ? "BAD" : canonical(it).c_str());
+    }
+    return 0;
+}

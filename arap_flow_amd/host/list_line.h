@@ -1,0 +1,219 @@
+// list_line.h -- the grammar of one list / --serve line of arap_deform, and nothing else: no HIP, no files.  The C++ twin of
+// pipeline.parse_line / done_token; line_tool.cpp prints what it reads so that a test can hold the two side by side.
+//   solve line:   RGB MASK CONSTRAINTS FLOW WARPED_RGB WARPED_MASK [bwd=P] [occ=P] [occ_bwd=P] [mid=I1,I2,..:PREFIX]
+//                 other trailing tokens are ignored (a line's words after the sixth always were); a malformed mid= is
+//                 the only error
+//   layers line:  layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P] [mid=..:PREFIX]
+//   bg line:      bg BG RGB1 MASK1 RGB2 MASK2 FLOW m=<12 numbers> [occ=IN] [bwd=IN] [occ_bwd=IN]
+//                 out=RGB1_OUT,RGB2_OUT,FLOW_OUT [occ_out=P] [bwd_out=P] [occ_bwd_out=P]
+//                 on these two any unknown key, missing `=` or empty value is an error, and so is a line without output
+#pragma once
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+#include <sstream>
+#include <string>
+#include <vector>
+
+extern "C" {
+#include "../../include/arap_opt.h"
+}
+
+// ---- the one tokeniser: KEY=VALUE (the value may be empty; the first `=` splits) and the table a form looks KEY up in
+inline bool split_token(const std::string& t, std::string& key, std::string& value)
+{
+    const size_t eq = t.find('=');
+    if (eq == std::string::npos) return false;
+    key = t.substr(0, eq);
+    value = t.substr(eq + 1);
+    return true;
+}
+
+struct TokenField { const char* key; std::string* dst; };
+
+inline std::string* field_of(std::initializer_list<TokenField> fields, const std::string& key)
+{
+    for (const TokenField& f : fields)
+        if (key == f.key) return f.dst;
+    return nullptr;
+}
+
+// ---- mid=I1,I2,..:PREFIX with 1 <= I1 < I2 < .., at most ARAPFLOW_MAX_SNAPSHOTS indices (DESIGN.md "In-between frames")
+struct Mid {
+    std::string text;                      // as written after `mid=` (empty: not wanted)
+    std::vector<unsigned> steps;
+    std::string prefix;
+};
+
+inline bool parse_mid(const std::string& v, Mid& mid)
+{
+    const size_t colon = v.find(':');
+    if (colon == std::string::npos || colon + 1 >= v.size()) return false;
+    mid.steps.clear();
+    unsigned x = 0, digits = 0;
+    for (size_t k = 0; k <= colon; ++k) {                  // an index of at most six digits, ended by `,` or the `:`
+        if (v[k] >= '0' && v[k] <= '9' && digits < 6) {
+            x = 10 * x + (unsigned)(v[k] - '0');
+            ++digits;
+            continue;
+        }
+        if ((v[k] != ',' && v[k] != ':') || digits == 0 || x < 1 || (!mid.steps.empty() && x <= mid.steps.back())) return false;
+        mid.steps.push_back(x);
+        x = digits = 0;
+    }
+    if (mid.steps.size() > ARAPFLOW_MAX_SNAPSHOTS) return false;
+    mid.prefix = v.substr(colon + 1);
+    mid.text = v;
+    return true;
+}
+
+// PREFIX_sII: the stem of the files of the state after ramp step II (pipeline.mid_files)
+inline std::string mid_stem(const std::string& prefix, unsigned step)
+{
+    char tag[16];
+    snprintf(tag, sizeof(tag), "_s%02u", step);
+    return prefix + tag;
+}
+
+// ---- the three forms
+struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
+    std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
+    std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
+    Mid mid;
+    int outputs() const
+    {
+        return (bwd.empty() && occ_bwd.empty() ? 0 : ARAPFLOW_OUT_BACKWARD) | (occ.empty() ? 0 : ARAPFLOW_OUT_OCCLUSION);
+    }
+};
+
+struct LayersSpec {
+    std::string rgb;
+    std::vector<std::string> masks, flows;
+    std::string occ, bwd, occ_bwd, rgb2, mask2;
+    Mid mid;                               // its prefix: that of the composite files
+    std::string first_out;                 // the value of the first output token in line order: what --serve reports
+};
+
+struct BgSpec {                            // pipeline.BgLine
+    std::string bg, rgb1, mask1, rgb2, mask2, flow;
+    float m[12];                           // M1, M2
+    std::string occ, bwd, occ_bwd;         // optional object-side inputs
+    std::string out_rgb1, out_rgb2, out_flow, out_occ, out_bwd, out_occ_bwd;      // outputs (empty: not wanted)
+    std::string first_out() const          // in the order of pipeline.bg_outputs
+    {
+        for (const std::string* q : {&out_rgb1, &out_rgb2, &out_flow, &out_occ, &out_bwd, &out_occ_bwd})
+            if (!q->empty()) return *q;
+        return std::string();
+    }
+};
+
+struct Item {
+    enum class Kind { Solve, Layers, Bg } kind = Kind::Solve;
+    SolvePaths solve;
+    LayersSpec layers;
+    BgSpec bg;
+};
+
+// the path `arap_deform --serve` reports a line done by (pipeline.done_token)
+inline std::string done_path(const Item& it)
+{
+    return it.kind == Item::Kind::Solve ? it.solve.flow : it.kind == Item::Kind::Layers ? it.layers.first_out : it.bg.first_out();
+}
+
+enum class Parsed { Skip, Bad, Good };     // Skip: none of the forms; Bad: a form, refused
+
+inline Parsed parse_solve(std::istringstream& tok, SolvePaths& q)
+{
+    if (!(tok >> q.mask >> q.constraints >> q.flow >> q.warped_rgb >> q.warped_mask)) return Parsed::Skip;
+    std::string k, v;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v)) continue;
+        if (k == "mid") {
+            if (!v.empty() && !parse_mid(v, q.mid)) return Parsed::Bad;
+        } else if (std::string* dst = field_of({{"bwd", &q.bwd}, {"occ", &q.occ}, {"occ_bwd", &q.occ_bwd}}, k))
+            *dst = v;
+    }
+    return Parsed::Good;
+}
+
+inline bool parse_layers(std::istringstream& tok, LayersSpec& q)
+{
+    long n = 0;
+    if (!(tok >> q.rgb >> n) || n < 1 || n > 255) return false;
+    for (long l = 0; l < n; ++l) {
+        std::string m, f;
+        if (!(tok >> m >> f)) return false;
+        q.masks.push_back(m);
+        q.flows.push_back(f);
+    }
+    std::string k, v;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "mid") {
+            if (!parse_mid(v, q.mid)) return false;
+        } else if (std::string* dst = field_of({{"occ", &q.occ}, {"bwd", &q.bwd}, {"occ_bwd", &q.occ_bwd}, {"rgb2", &q.rgb2},
+                                                {"mask2", &q.mask2}}, k))
+            *dst = v;
+        else return false;
+        if (q.first_out.empty()) q.first_out = v;
+    }
+    return !q.first_out.empty();
+}
+
+// twelve numbers, comma separated, nothing else
+inline bool parse_bg_maps(const std::string& v, float m[12])
+{
+    const char* p = v.c_str();
+    for (int n = 0; n < 12; ++n) {
+        char* end = nullptr;
+        m[n] = strtof(p, &end);
+        if (end == p || *end != (n < 11 ? ',' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
+}
+
+inline bool parse_bg(std::istringstream& tok, BgSpec& q)
+{
+    if (!(tok >> q.bg >> q.rgb1 >> q.mask1 >> q.rgb2 >> q.mask2 >> q.flow)) return false;
+    bool have_m = false;
+    std::string k, v;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "m") {
+            if (!parse_bg_maps(v, q.m)) return false;
+            have_m = true;
+        } else if (k == "out") {           // three places, each may be empty
+            const size_t c1 = v.find(','), c2 = c1 == std::string::npos ? c1 : v.find(',', c1 + 1);
+            if (c2 == std::string::npos || v.find(',', c2 + 1) != std::string::npos) return false;
+            q.out_rgb1 = v.substr(0, c1); q.out_rgb2 = v.substr(c1 + 1, c2 - c1 - 1); q.out_flow = v.substr(c2 + 1);
+        } else if (std::string* dst = field_of({{"occ", &q.occ}, {"bwd", &q.bwd}, {"occ_bwd", &q.occ_bwd},
+                                                {"occ_out", &q.out_occ}, {"bwd_out", &q.out_bwd},
+                                                {"occ_bwd_out", &q.out_occ_bwd}}, k))
+            *dst = v;
+        else return false;
+    }
+    if ((!q.out_occ.empty() && q.occ.empty()) || (!q.out_bwd.empty() && q.bwd.empty()) ||
+        (!q.out_occ_bwd.empty() && q.occ_bwd.empty()))
+        return false;                      // an output needs its input
+    return have_m && !q.first_out().empty();
+}
+
+// a list / --serve line -> item.  A refused form is reported here, on stdout.
+inline Parsed parse_item(const std::string& line, Item& it)
+{
+    std::istringstream tok(line);
+    std::string first;
+    if (!(tok >> first)) return Parsed::Skip;
+    it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : Item::Kind::Solve;
+    it.solve.rgb = first;
+    Parsed p;
+    if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
+    else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
+    if (p == Parsed::Bad) {
+        const char* const what[] = {"mid= token", "layers line", "bg line"};      // by Item::Kind
+        printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
+        fflush(stdout);
+    }
+    return p;
+}

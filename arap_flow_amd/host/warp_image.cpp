@@ -3,17 +3,12 @@
 // The rasterisation runs on the GPU (ArapFlow_Warp); output is bit exact against the reference's executable.
 // Optional tokens after the five arguments (addition, DESIGN.md "Backward flow and occlusion"): bwd=PATH.flo,
 // occ=PATH.png, occ_bwd=PATH.png; then ArapFlow_WarpEx also writes those maps.
-#include <hip/hip_runtime_api.h>
-
 #include <cstdio>
 #include <string>
 #include <vector>
 
-extern "C" {
-#include "../../include/arap_opt.h"
-}
-#include "flo_io.h"
-#include "png_io.h"
+#include "device_pass.h"
+#include "list_line.h"
 
 static void usage()
 {
@@ -36,10 +31,10 @@ int main(int argc, const char* argv[])
     std::string bwd_path, occ_path, occ_bwd_path;
     bool extra_ok = argc >= 6;
     for (int a = 6; a < argc && extra_ok; ++a) {
-        const std::string t = argv[a];
-        if (t.compare(0, 4, "bwd=") == 0) bwd_path = t.substr(4);
-        else if (t.compare(0, 4, "occ=") == 0) occ_path = t.substr(4);
-        else if (t.compare(0, 8, "occ_bwd=") == 0) occ_bwd_path = t.substr(8);
+        std::string k, v;
+        std::string* dst = split_token(argv[a], k, v)
+                               ? field_of({{"bwd", &bwd_path}, {"occ", &occ_path}, {"occ_bwd", &occ_bwd_path}}, k) : nullptr;
+        if (dst) *dst = v;
         else extra_ok = false;
     }
     if (!extra_ok) {
@@ -61,41 +56,27 @@ int main(int argc, const char* argv[])
     Opt_InitializationParameters ip = {0, 0, 0, 0};
     Opt_State* state = Opt_NewState(ip);
     if (!state) return 1;
-    void *d_rgb, *d_msk, *d_flow, *d_orgb, *d_omsk, *d_scr;
-    HCHECK(hipMalloc(&d_rgb, 3 * N)); HCHECK(hipMalloc(&d_msk, N)); HCHECK(hipMalloc(&d_flow, 8 * N));
-    HCHECK(hipMalloc(&d_orgb, 3 * N)); HCHECK(hipMalloc(&d_omsk, N));
     const bool ex = !bwd_path.empty() || !occ_path.empty() || !occ_bwd_path.empty();
-    void *d_bwd = nullptr, *d_obwd = nullptr, *d_occ = nullptr;
-    if (!bwd_path.empty()) HCHECK(hipMalloc(&d_bwd, 8 * N));
-    if (!occ_bwd_path.empty()) HCHECK(hipMalloc(&d_obwd, N));
-    if (!occ_path.empty()) HCHECK(hipMalloc(&d_occ, N));
-    HCHECK(hipMalloc(&d_scr, ex ? ArapFlow_WarpExScratchBytes((unsigned)w, (unsigned)h)
-                                : ArapFlow_WarpScratchBytes((unsigned)w, (unsigned)h)));
-    HCHECK(hipMemcpy(d_rgb, rgb.rgb.data(), 3 * N, hipMemcpyHostToDevice));
-    HCHECK(hipMemcpy(d_msk, mred.data(), N, hipMemcpyHostToDevice));
-    HCHECK(hipMemcpy(d_flow, flow.data(), 8 * N, hipMemcpyHostToDevice));
-    if (!ex && ArapFlow_Warp(state, (unsigned)w, (unsigned)h, d_rgb, d_msk, d_flow, d_orgb, d_omsk, d_scr) != 0) { printf("ArapFlow_Warp failed\n"); return 1; }
-    if (ex && ArapFlow_WarpEx(state, (unsigned)w, (unsigned)h, d_rgb, d_msk, d_flow, d_orgb, d_omsk, d_bwd, d_obwd, d_occ,
-                              d_scr) != 0) { printf("ArapFlow_WarpEx failed\n"); return 1; }
-    HCHECK(hipDeviceSynchronize());
-    std::vector<uint8_t> orgb(3 * N), omsk(N);
-    HCHECK(hipMemcpy(orgb.data(), d_orgb, 3 * N, hipMemcpyDeviceToHost));
-    HCHECK(hipMemcpy(omsk.data(), d_omsk, N, hipMemcpyDeviceToHost));
-    if (!arapio::write_png_rgb(argv[4], w, h, orgb.data(), err) || !arapio::write_png_mask1(argv[5], w, h, omsk.data(), err)) {
-        printf("%s\n", err.c_str());
+    DeviceArena dev;
+    const size_t d_rgb = dev.stage(rgb.rgb.data(), 3 * N), d_msk = dev.stage(mred.data(), N), d_flow = dev.stage(flow.data(), 8 * N);
+    OutputTable out(dev, w, h);
+    const size_t o_rgb = out.add(FileKind::rgb, argv[4]), o_msk = out.add(FileKind::mask1, argv[5]);
+    const size_t o_bwd = out.add(FileKind::flo, bwd_path), o_obwd = out.add(FileKind::gray8, occ_bwd_path);
+    const size_t o_occ = out.add(FileKind::gray8, occ_path);
+    const size_t d_scr = dev.take(ex ? ArapFlow_WarpExScratchBytes((unsigned)w, (unsigned)h)
+                                     : ArapFlow_WarpScratchBytes((unsigned)w, (unsigned)h));
+    HCHECK(dev.alloc());
+    HCHECK(dev.upload());
+    if (!ex && ArapFlow_Warp(state, (unsigned)w, (unsigned)h, dev.at(d_rgb), dev.at(d_msk), dev.at(d_flow), out.dev(o_rgb),
+                             out.dev(o_msk), dev.at(d_scr)) != 0) { printf("ArapFlow_Warp failed\n"); return 1; }
+    if (ex && ArapFlow_WarpEx(state, (unsigned)w, (unsigned)h, dev.at(d_rgb), dev.at(d_msk), dev.at(d_flow), out.dev(o_rgb),
+                              out.dev(o_msk), out.dev(o_bwd), out.dev(o_obwd), out.dev(o_occ), dev.at(d_scr)) != 0) {
+        printf("ArapFlow_WarpEx failed\n");
         return 1;
     }
-    if (d_bwd) {
-        std::vector<float> bwd(2 * N);
-        HCHECK(hipMemcpy(bwd.data(), d_bwd, 8 * N, hipMemcpyDeviceToHost));
-        if (!arapio::write_flo(bwd_path, bwd.data(), w, h)) return 1;
-    }
-    for (auto po : {std::make_pair(d_obwd, &occ_bwd_path), std::make_pair(d_occ, &occ_path)}) {
-        if (!po.first) continue;
-        std::vector<uint8_t> m(N);
-        HCHECK(hipMemcpy(m.data(), po.first, N, hipMemcpyDeviceToHost));
-        if (!arapio::write_png_gray8(*po.second, w, h, m.data(), err)) { printf("%s\n", err.c_str()); return 1; }
-    }
+    HCHECK(hipDeviceSynchronize());
+    HCHECK(out.download());
+    if (!out.write()) return 1;
     printf("Saved\n");
     return 0;
 }
