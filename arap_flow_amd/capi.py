@@ -79,6 +79,7 @@ SYMBOLS = [
     ("ArapFlow_WarpLayersStep", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ArapFlow_BackgroundMaps", _I, [C.POINTER(C.c_float)] * 4),
     ("ArapFlow_Background", _I, [_VP, _U, _U, _VP, _U, _U, C.POINTER(C.c_float), C.POINTER(C.c_float)] + [_VP] * 14),
+    ("ArapFlow_BackgroundSeq", _I, [_VP, _U, _U, _VP, _U, _U, _U, C.POINTER(C.c_float), _VP] + [C.POINTER(_VP)] * 7),
 ]
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h

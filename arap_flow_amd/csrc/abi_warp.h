@@ -1,7 +1,7 @@
 // abi_warp.h -- the warp entry points on caller-owned images (ArapFlow_Warp / WarpEx / WarpStep / WarpLayers /
 // WarpLayersStep): the layout of their scratch buffer, stated once for the size functions and for the code that carves
 // it up, and the one enqueue of rasterise -> optional outputs -> resolve that the frame solver's warp shares.
-// Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background, arap_bg.h), which needs no scratch.
+// Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background / BackgroundSeq, arap_bg.h), which needs no scratch.
 #pragma once
 
 // the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
@@ -282,6 +282,47 @@ int ArapFlow_Background(Opt_State* st, unsigned W, unsigned H, const void* bg, u
                        bg_map(Ginv)};
         hipLaunchKernelGGL(k_bg_frame2, grid, block, 0, st->stream, s, pic, (int)W, (int)H);
     }
+    return (int)hipGetLastError();
+}
+
+static_assert(BG_SEQ_MAX == ARAPFLOW_MAX_SNAPSHOTS + 2, "frame 1, every snapshot, frame 2");
+
+int ArapFlow_BackgroundSeq(Opt_State* st, unsigned W, unsigned H, const void* bg, unsigned bgW, unsigned bgH, unsigned nframes,
+                           const float* maps, const void* mask_red, const void* const* covers, const void* const* rgbs,
+                           const void* const* flows, const void* const* occs, void* const* out_rgbs, void* const* out_flows,
+                           void* const* out_occs)
+{
+    if (!st || !bg || !mask_red || !maps || !covers || W == 0 || H == 0 || bgW == 0 || bgH == 0) return -1;
+    if (nframes < 2 || nframes > (unsigned)BG_SEQ_MAX) return -1;
+    if ((uint64_t)W * H >= (1ull << 31) || bgW >= (1u << 31) || bgH >= (1u << 31)) return -1;
+    auto at = [](auto* list, unsigned f) { return list ? list[f] : nullptr; };   // a null list: every entry null
+    BgSeq seq{};
+    bool any = false;
+    for (unsigned f = 0; f < nframes; ++f) {
+        const bool link = f + 1 < nframes;
+        BgSide& s = seq.f[f];
+        s.own = (const uint8_t*)(f ? covers[f] : mask_red);
+        if (!s.own) return -1;
+        s.rgb = (const uint8_t*)at(rgbs, f);
+        s.out_rgb = (uint8_t*)at(out_rgbs, f);
+        s.M = bg_map(maps + 6 * f);
+        if (link) {
+            s.other = (const uint8_t*)covers[f + 1];
+            s.flow = (const float2*)at(flows, f);
+            s.occ = (const uint8_t*)at(occs, f);
+            s.out_flow = (float2*)at(out_flows, f);
+            s.out_occ = (uint8_t*)at(out_occs, f);
+            float G[6], Ginv[6];
+            if (!s.other || ArapFlow_BackgroundMaps(maps + 6 * f, maps + 6 * (f + 1), G, Ginv) != 0) return -1;
+            s.G = bg_map(G);
+        }
+        if ((s.out_rgb && !s.rgb) || (s.out_flow && !s.flow) || (s.out_occ && !s.occ)) return -1;
+        any = any || s.out_rgb || s.out_flow || s.out_occ;
+    }
+    if (!any) return -1;
+    const BgPicture pic{(const uint8_t*)bg, (int)bgW, (int)bgH};
+    const dim3 grid((W + 63) / 64, (H + 3) / 4, nframes), block(64, 4);
+    hipLaunchKernelGGL(k_bg_seq, grid, block, 0, st->stream, seq, pic, (int)W, (int)H);
     return (int)hipGetLastError();
 }
 

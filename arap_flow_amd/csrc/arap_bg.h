@@ -1,7 +1,7 @@
 // arap_bg.h -- moving background: full-frame RGB, flow and occlusion behind the warp's objects (gfx950).
 //
-// Definitions: DESIGN.md "Moving background".  A post-pass of the warp family on caller-owned images: two kernels, one
-// per frame domain, one pass per pixel, no atomics, no scratch.  Every output is optional (a null pointer: not computed,
+// Definitions: DESIGN.md "Moving background".  A post-pass of the warp family on caller-owned images: one kernel per
+// frame domain of a pair, and one for a whole sequence of frames (k_bg_seq); one pass per pixel, no atomics, no scratch.  Every output is optional (a null pointer: not computed,
 // its inputs not read) and a function of the inputs alone.  On an object pixel of its domain an output is a copy of the
 // object-side input; on a background pixel it comes from the affine maps: the sampling map M of the domain (pixel ->
 // point of the background picture) and the point map G to the other frame.
@@ -61,15 +61,17 @@ __device__ __forceinline__ void bg_sample(const BgPicture& bg, float2 b, uint8_t
     }
 }
 
-// one pixel of one domain.  FRAME2 only selects the two mask conventions.
-template <bool FRAME2>
+// one pixel of one domain.  The two template flags only select the mask conventions: OWN_COVER, the domain's own mask
+// is a cover (object: != 0) and not a solver mask (object: == 0); OTHER_COVER, the same for the mask of the frame the
+// point map leads to (a cover hides where it is != 0, a solver mask where it is == 0).
+template <bool OWN_COVER, bool OTHER_COVER>
 __device__ __forceinline__ void bg_pixel(const BgSide& s, const BgPicture& bg, int W, int H)
 {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (x >= W || y >= H) return;
     const size_t i = (size_t)y * W + x;
     const uint8_t m = s.own[i];
-    const bool object = FRAME2 ? m != 0 : m == 0;
+    const bool object = OWN_COVER ? m != 0 : m == 0;
     if (s.out_rgb) {
         uint8_t v[3];
         if (object) { v[0] = s.rgb[3 * i]; v[1] = s.rgb[3 * i + 1]; v[2] = s.rgb[3 * i + 2]; }
@@ -89,15 +91,32 @@ __device__ __forceinline__ void bg_pixel(const BgSide& s, const BgPicture& bg, i
     if (!hidden) {
         const int nx = min((int)floorf(p.x + 0.5f), W - 1), ny = min((int)floorf(p.y + 0.5f), H - 1);
         const uint8_t o = s.other[(size_t)ny * W + nx];
-        hidden = FRAME2 ? o == 0 : o != 0;
+        hidden = OTHER_COVER ? o != 0 : o == 0;
     }
     s.out_occ[i] = hidden ? 255 : 0;
 }
 
 // frame-1 domain: out_rgb1, flow_full, occ_full.  grid = (ceil(W/64), ceil(H/4)), block = (64,4)
-__global__ __launch_bounds__(256) void k_bg_frame1(BgSide s, BgPicture bg, int W, int H) { bg_pixel<false>(s, bg, W, H); }
+__global__ __launch_bounds__(256) void k_bg_frame1(BgSide s, BgPicture bg, int W, int H) { bg_pixel<false, true>(s, bg, W, H); }
 
 // frame-2 domain: out_rgb2, bwd_full, occ_bwd_full.  Same launch shape.
-__global__ __launch_bounds__(256) void k_bg_frame2(BgSide s, BgPicture bg, int W, int H) { bg_pixel<true>(s, bg, W, H); }
+__global__ __launch_bounds__(256) void k_bg_frame2(BgSide s, BgPicture bg, int W, int H) { bg_pixel<true, false>(s, bg, W, H); }
+
+// A sequence frame 1 -> t_1 -> .. -> t_n -> frame 2 (DESIGN.md "Moving background over in-between frames"): frame f is a
+// BgSide whose `other` is the cover of frame f + 1 and whose G leads there.  Frame 0 reads its own mask as the solver's,
+// every later frame as a cover; the last frame has no link (out_flow == out_occ == NULL: only out_rgb).  The table
+// travels by value in the kernel arguments (112 bytes a frame), read with scalar loads: blockIdx.z is uniform.
+constexpr int BG_SEQ_MAX = 10;             // ARAPFLOW_MAX_SNAPSHOTS + 2
+
+struct BgSeq { BgSide f[BG_SEQ_MAX]; };
+
+// every frame of a sequence in one launch.  grid = (ceil(W/64), ceil(H/4), frames), block = (64,4)
+__global__ __launch_bounds__(256) void k_bg_seq(BgSeq seq, BgPicture bg, int W, int H)
+{
+    const BgSide& s = seq.f[blockIdx.z];
+    if (!s.out_rgb && !s.out_flow && !s.out_occ) return;
+    if (blockIdx.z == 0) bg_pixel<false, true>(s, bg, W, H);
+    else bg_pixel<true, true>(s, bg, W, H);
+}
 
 }  // namespace arap

@@ -15,11 +15,16 @@
 // STEM_l_sII.flo, STEM_l = FLO_l without `.flo`, and writes per snapshot the composite PREFIX_sII.flo, PREFIX_sII.png,
 // PREFIX_sII_mask.png, PREFIX_sII_step.flo and, with occ= on the line, the link occlusions PREFIX_s00_occ.png (frame 1
 // -> first snapshot) and PREFIX_sII_occ.png (snapshot -> next state).
-// A line whose first word is `bg` is the moving-background pass of one pair (DESIGN.md "Moving background"):
+// A line whose first word is `bg` is the moving-background pass of one pair (DESIGN.md "Moving background"; with mid= also
+// of its in-between frames, "Moving background over in-between frames"):
 //   bg BG.png RGB1.png MASK1.png RGB2.png MASK2.png FLOW.flo m=<12 numbers, M1 then M2, comma separated>
 //      [occ=IN] [bwd=IN] [occ_bwd=IN] out=RGB1_OUT.png,RGB2_OUT.png,FLOW_OUT.flo [occ_out=P] [bwd_out=P] [occ_bwd_out=P]
 // (MASK1: red 0 = object; MASK2: a warped mask, non-zero = object; a place of out= may be empty; at least one output).
-// It answers "Done <first output: the places of out=, then occ_out, bwd_out, occ_bwd_out>".
+// With mid=I1,..,In:PREFIX mm=<6n numbers> mid_out=PREFIX_OUT (all three or none) the line also makes one sequence pass over
+// frame 1, the in-between frames PREFIX_sII{.png,_mask.png,_step.flo} (PREFIX_sI1.flo for the first link; with occ= also
+// PREFIX_s00_occ.png, PREFIX_sII_occ.png) and frame 2, with the cameras mm= gives the in-between frames, and writes
+// PREFIX_OUT_sII.png, PREFIX_OUT_s00_step.flo, PREFIX_OUT_sII_step.flo and, with occ=, PREFIX_OUT_s00_occ.png, _sII_occ.png.
+// It answers "Done <first output: the places of out=, then occ_out, bwd_out, occ_bwd_out, then PREFIX_OUT_sI1.png>".
 // Either runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -245,8 +250,81 @@ static bool run_layers(Opt_State* state, const LayersSpec& q)
     return ok ? out.write() : fail("ArapFlow_WarpLayers failed\n");
 }
 
+// the mid= / mm= / mid_out= tokens of a bg line (pipeline.run_background_seq): frame 1, the snapshots mid= names and
+// frame 2 are the frames of one ArapFlow_BackgroundSeq, which writes every in-between frame, every link's flow and, with
+// occ= on the line, every link's occlusion.  The composites of frame 1 and frame 2 stay with out=.
+static bool run_background_seq(Opt_State* state, const BgSpec& q, const arapio::Image& bg, const std::vector<uint8_t>& mask_red,
+                               const std::vector<uint8_t>& cover2, int w, int h)
+{
+    const size_t N = (size_t)w * h, n = q.mid.steps.size(), m = n + 2;
+    const bool with_occ = !q.occ.empty();
+    std::vector<arapio::Image> rgbs(n);
+    std::vector<std::vector<uint8_t>> covers(n), occs(with_occ ? n + 1 : 0);
+    std::vector<std::vector<float>> flows(n + 1);
+    auto missing = [](const std::string& path) { return fail("bg: snapshot %s is missing\n", path.c_str()); };
+    auto differs = [&](const std::string& path) { return fail("bg: %s differs in size from %s\n", path.c_str(), q.mask1.c_str()); };
+    auto flo = [&](const std::string& path, std::vector<float>& fl) {
+        int fw = 0, fh = 0;
+        if (!arapio::read_flo(path, fl, fw, fh)) return missing(path);
+        return (fw == w && fh == h) || differs(path);
+    };
+    auto png = [&](const std::string& path, arapio::Image& im) {
+        std::string err;
+        if (!arapio::read_png_rgb(path, im, err)) return missing(path);
+        return (im.w == w && im.h == h) || differs(path);
+    };
+    if (!flo(mid_stem(q.mid.prefix, q.mid.steps[0]) + ".flo", flows[0])) return false;
+    for (size_t k = 0; k <= n; ++k) {
+        const std::string stem = mid_stem(q.mid.prefix, k ? q.mid.steps[k - 1] : 0);
+        arapio::Image im;
+        if (with_occ) {
+            if (!png(stem + "_occ.png", im)) return false;
+            occs[k] = red_channel(im);
+        }
+        if (k == 0) continue;
+        if (!png(stem + ".png", rgbs[k - 1]) || !png(stem + "_mask.png", im) || !flo(stem + "_step.flo", flows[k])) return false;
+        covers[k - 1] = red_channel(im);
+        for (uint8_t& c : covers[k - 1]) c = c ? 255 : 0;
+    }
+    DeviceArena dev;
+    const size_t d_bg = dev.stage(bg.rgb.data(), bg.rgb.size()), d_m1 = dev.stage(mask_red.data(), N);
+    std::vector<size_t> d_cover(m, DeviceArena::kNone), d_rgb(m, DeviceArena::kNone), d_flow(m - 1), d_occ(m - 1, DeviceArena::kNone);
+    d_cover[m - 1] = dev.stage(cover2.data(), N);
+    for (size_t k = 0; k < n; ++k) {
+        d_cover[k + 1] = dev.stage(covers[k].data(), N);
+        d_rgb[k + 1] = dev.stage(rgbs[k].rgb.data(), 3 * N);
+    }
+    for (size_t k = 0; k <= n; ++k) {
+        d_flow[k] = dev.stage(flows[k].data(), 8 * N);
+        if (with_occ) d_occ[k] = dev.stage(occs[k].data(), N);
+    }
+    OutputTable out(dev, w, h);            // in the order of pipeline.bg_outputs
+    std::vector<size_t> o_rgb(m, DeviceArena::kNone), o_flow(m - 1), o_occ(m - 1, DeviceArena::kNone);
+    for (size_t k = 1; k <= n; ++k) o_rgb[k] = out.add(FileKind::rgb, mid_stem(q.mid_out, q.mid.steps[k - 1]) + ".png");
+    for (size_t k = 0; k <= n; ++k) o_flow[k] = out.add(FileKind::flo, mid_stem(q.mid_out, k ? q.mid.steps[k - 1] : 0) + "_step.flo");
+    for (size_t k = 0; with_occ && k <= n; ++k)
+        o_occ[k] = out.add(FileKind::gray8, mid_stem(q.mid_out, k ? q.mid.steps[k - 1] : 0) + "_occ.png");
+    if (dev.alloc() != hipSuccess) return fail("bg: out of device memory\n");
+    std::vector<float> maps(q.m, q.m + 6);
+    maps.insert(maps.end(), q.mm.begin(), q.mm.end());
+    maps.insert(maps.end(), q.m + 6, q.m + 12);
+    std::vector<const void*> p_cover(m), p_rgb(m), p_flow(m - 1), p_occ(m - 1);
+    std::vector<void*> p_orgb(m), p_oflow(m - 1), p_oocc(m - 1);
+    auto row = [&](size_t r) { return r == DeviceArena::kNone ? nullptr : out.dev(r); };
+    for (size_t f = 0; f < m; ++f) {
+        p_cover[f] = dev.at(d_cover[f]); p_rgb[f] = dev.at(d_rgb[f]); p_orgb[f] = row(o_rgb[f]);
+        if (f + 1 < m) { p_flow[f] = dev.at(d_flow[f]); p_occ[f] = dev.at(d_occ[f]); p_oflow[f] = row(o_flow[f]); p_oocc[f] = row(o_occ[f]); }
+    }
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_BackgroundSeq(state, (unsigned)w, (unsigned)h, dev.at(d_bg), (unsigned)bg.w, (unsigned)bg.h, (unsigned)m,
+                                           maps.data(), dev.at(d_m1), p_cover.data(), p_rgb.data(), p_flow.data(), p_occ.data(),
+                                           p_orgb.data(), p_oflow.data(), p_oocc.data()) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
+    return ok ? out.write() : fail("ArapFlow_BackgroundSeq failed\n");
+}
+
 // the moving-background pass of one pair, synchronously (pipeline.run_background): read the line's files, one
-// ArapFlow_Background on the state's stream, write the outputs asked for
+// ArapFlow_Background on the state's stream, write the outputs asked for; then, with mid=, the sequence pass
 static bool run_background(Opt_State* state, const BgSpec& q)
 {
     arapio::Image bg, rgb1, rgb2, m1, m2, occ, occ_bwd;
@@ -280,14 +358,17 @@ static bool run_background(Opt_State* state, const BgSpec& q)
     const size_t o_rgb1 = out.add(FileKind::rgb, q.out_rgb1), o_rgb2 = out.add(FileKind::rgb, q.out_rgb2);
     const size_t o_flow = out.add(FileKind::flo, q.out_flow), o_bwd = out.add(FileKind::flo, q.out_bwd);
     const size_t o_occ = out.add(FileKind::gray8, q.out_occ), o_occ_bwd = out.add(FileKind::gray8, q.out_occ_bwd);
+    const bool pair = !(q.out_rgb1 + q.out_rgb2 + q.out_flow + q.out_occ + q.out_bwd + q.out_occ_bwd).empty();
     if (dev.alloc() != hipSuccess) return fail("bg: out of device memory\n");
-    const bool ok = dev.upload() == hipSuccess &&
+    const bool ok = !pair || (dev.upload() == hipSuccess &&
                     ArapFlow_Background(state, (unsigned)w, (unsigned)h, dev.at(d_bg), (unsigned)bg.w, (unsigned)bg.h, q.m, q.m + 6,
                                         dev.at(d_rgb1), dev.at(d_m1), dev.at(d_rgb2), dev.at(d_cover2), dev.at(d_flow),
                                         dev.at(d_occ), dev.at(d_bwd), dev.at(d_occ_bwd), out.dev(o_rgb1), out.dev(o_rgb2),
                                         out.dev(o_flow), out.dev(o_occ), out.dev(o_bwd), out.dev(o_occ_bwd)) == 0 &&
-                    hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
-    return ok ? out.write() : fail("ArapFlow_Background failed\n");
+                    hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess);
+    if (!ok) return fail("ArapFlow_Background failed\n");
+    if (!out.write()) return false;
+    return q.mid_out.empty() || run_background_seq(state, q, bg, mask_red, cover2, w, h);
 }
 
 // ---- where the lines come from: a finished list, or stdin as it arrives (--serve) ------------------------------------

@@ -33,15 +33,20 @@ static std::string canonical(const Item& it)
         const BgSpec& q = it.bg;
         c.word("bg");
         for (const std::string* s : {&q.bg, &q.rgb1, &q.mask1, &q.rgb2, &q.mask2, &q.flow}) c.word(*s);
-        std::string m;
-        for (int n = 0; n < 12; ++n) {
-            char num[32];
-            snprintf(num, sizeof(num), "%s%.9g", n ? "," : "", q.m[n]);
-            m += num;
-        }
-        c.token("m", m); c.token("occ", q.occ); c.token("bwd", q.bwd); c.token("occ_bwd", q.occ_bwd);
+        auto numbers = [](const float* v, size_t count) {
+            std::string m;
+            for (size_t n = 0; n < count; ++n) {
+                char num[32];
+                snprintf(num, sizeof(num), "%s%.9g", n ? "," : "", v[n]);
+                m += num;
+            }
+            return m;
+        };
+        c.token("m", numbers(q.m, 12)); c.token("mid", q.mid.text); c.token("mm", numbers(q.mm.data(), q.mm.size()));
+        c.token("occ", q.occ); c.token("bwd", q.bwd); c.token("occ_bwd", q.occ_bwd);
         if (!(q.out_rgb1 + q.out_rgb2 + q.out_flow).empty()) c.word("out=" + q.out_rgb1 + "," + q.out_rgb2 + "," + q.out_flow);
         c.token("occ_out", q.out_occ); c.token("bwd_out", q.out_bwd); c.token("occ_bwd_out", q.out_occ_bwd);
+        c.token("mid_out", q.mid_out);
     }
     return c.text + " done=" + done_path(it);
 }

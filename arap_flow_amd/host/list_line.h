@@ -4,8 +4,9 @@
 //                 other trailing tokens are ignored (a line's words after the sixth always were); a malformed mid= is
 //                 the only error
 //   layers line:  layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P] [mid=..:PREFIX]
-//   bg line:      bg BG RGB1 MASK1 RGB2 MASK2 FLOW m=<12 numbers> [occ=IN] [bwd=IN] [occ_bwd=IN]
-//                 out=RGB1_OUT,RGB2_OUT,FLOW_OUT [occ_out=P] [bwd_out=P] [occ_bwd_out=P]
+//   bg line:      bg BG RGB1 MASK1 RGB2 MASK2 FLOW m=<12 numbers> [mid=I1,..,In:PREFIX mm=<6n numbers>] [occ=IN] [bwd=IN]
+//                 [occ_bwd=IN] out=RGB1_OUT,RGB2_OUT,FLOW_OUT [occ_out=P] [bwd_out=P] [occ_bwd_out=P] [mid_out=PREFIX_OUT]
+//                 mid=, mm= and mid_out= come together
 //                 on these two any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cstdio>
@@ -99,11 +100,14 @@ struct BgSpec {                            // pipeline.BgLine
     float m[12];                           // M1, M2
     std::string occ, bwd, occ_bwd;         // optional object-side inputs
     std::string out_rgb1, out_rgb2, out_flow, out_occ, out_bwd, out_occ_bwd;      // outputs (empty: not wanted)
+    Mid mid;                               // the pair's in-between files (DESIGN.md "Moving background over in-between frames")
+    std::vector<float> mm;                 // their sampling maps, six numbers each
+    std::string mid_out;                   // the prefix of the sequence's files (pipeline.mid_bg_files)
     std::string first_out() const          // in the order of pipeline.bg_outputs
     {
         for (const std::string* q : {&out_rgb1, &out_rgb2, &out_flow, &out_occ, &out_bwd, &out_occ_bwd})
             if (!q->empty()) return *q;
-        return std::string();
+        return mid_out.empty() ? std::string() : mid_stem(mid_out, mid.steps[0]) + ".png";
     }
 };
 
@@ -160,14 +164,14 @@ inline bool parse_layers(std::istringstream& tok, LayersSpec& q)
     return !q.first_out.empty();
 }
 
-// twelve numbers, comma separated, nothing else
-inline bool parse_bg_maps(const std::string& v, float m[12])
+// `count` numbers, comma separated, nothing else
+inline bool parse_bg_maps(const std::string& v, float* m, size_t count)
 {
     const char* p = v.c_str();
-    for (int n = 0; n < 12; ++n) {
+    for (size_t n = 0; n < count; ++n) {
         char* end = nullptr;
         m[n] = strtof(p, &end);
-        if (end == p || *end != (n < 11 ? ',' : '\0')) return false;
+        if (end == p || *end != (n + 1 < count ? ',' : '\0')) return false;
         p = end + 1;
     }
     return true;
@@ -176,26 +180,36 @@ inline bool parse_bg_maps(const std::string& v, float m[12])
 inline bool parse_bg(std::istringstream& tok, BgSpec& q)
 {
     if (!(tok >> q.bg >> q.rgb1 >> q.mask1 >> q.rgb2 >> q.mask2 >> q.flow)) return false;
-    bool have_m = false;
-    std::string k, v;
+    bool have_m = false, have_mm = false;
+    std::string k, v, mm;
     for (std::string t; tok >> t;) {
         if (!split_token(t, k, v) || v.empty()) return false;
         if (k == "m") {
-            if (!parse_bg_maps(v, q.m)) return false;
+            if (!parse_bg_maps(v, q.m, 12)) return false;
             have_m = true;
+        } else if (k == "mid") {
+            if (!parse_mid(v, q.mid)) return false;
+        } else if (k == "mm") {            // (counted once the line is read: mid= may come after it)
+            mm = v;
+            have_mm = true;
         } else if (k == "out") {           // three places, each may be empty
             const size_t c1 = v.find(','), c2 = c1 == std::string::npos ? c1 : v.find(',', c1 + 1);
             if (c2 == std::string::npos || v.find(',', c2 + 1) != std::string::npos) return false;
             q.out_rgb1 = v.substr(0, c1); q.out_rgb2 = v.substr(c1 + 1, c2 - c1 - 1); q.out_flow = v.substr(c2 + 1);
         } else if (std::string* dst = field_of({{"occ", &q.occ}, {"bwd", &q.bwd}, {"occ_bwd", &q.occ_bwd},
                                                 {"occ_out", &q.out_occ}, {"bwd_out", &q.out_bwd},
-                                                {"occ_bwd_out", &q.out_occ_bwd}}, k))
+                                                {"occ_bwd_out", &q.out_occ_bwd}, {"mid_out", &q.mid_out}}, k))
             *dst = v;
         else return false;
     }
     if ((!q.out_occ.empty() && q.occ.empty()) || (!q.out_bwd.empty() && q.bwd.empty()) ||
         (!q.out_occ_bwd.empty() && q.occ_bwd.empty()))
         return false;                      // an output needs its input
+    if (!q.mid.text.empty() || have_mm || !q.mid_out.empty()) {                    // all three or none
+        if (q.mid.text.empty() || !have_mm || q.mid_out.empty()) return false;
+        q.mm.resize(6 * q.mid.steps.size());
+        if (!parse_bg_maps(mm, q.mm.data(), q.mm.size())) return false;
+    }
     return have_m && !q.first_out().empty();
 }
 

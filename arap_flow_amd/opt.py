@@ -9,6 +9,7 @@
   warp_image_ex    the same, plus backward flow and occlusion maps (ArapFlow_WarpEx)
   warp_step        the warp of one deformation state and the flow from it to a second one (ArapFlow_WarpStep)
   background       full-frame RGB, flow and occlusion behind a warped pair's objects (ArapFlow_Background)
+  background_seq   the same over frame 1, a pair's in-between frames and frame 2 in one call (ArapFlow_BackgroundSeq)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -450,26 +451,34 @@ def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, 
     """One ArapFlow_<name> call on host arrays.  `dims`: (W, H) or (W, H, n); `inputs`: (array or None, dtype) and
     `outputs`: (dict key, shape or None = not asked, torch dtype), both in the library's argument order; `scratch`: the
     name of the *ScratchBytes function of a call that takes a scratch buffer; `lead`: arguments between the dims and
-    the inputs, an (array, dtype) to upload or a value passed as it is.  Uploads, allocates, synchronises, calls,
-    and downloads {key: array} of the outputs asked.  A return code of -1 is a ValueError where `bad_args`, every other
-    non-zero code a RuntimeError."""
+    the inputs, an (array, dtype) to upload or a value passed as it is.  An input that is a list of arrays, or an
+    output whose shape is a list of shapes, is passed as a host array of device pointers and comes back as a list.
+    Uploads, allocates, synchronises, calls, and downloads {key: array} of the outputs asked.  A return code of -1 is a
+    ValueError where `bad_args`, every other non-zero code a RuntimeError."""
     lib = state.lib
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
+    up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
+    new = lambda shape, dt: None if shape is None else torch.empty(*shape, dtype=dt, device="cuda")
     lead = [up(*a) if isinstance(a, tuple) else a for a in lead]
-    args = [up(a, dt) if a is not None else None for a, dt in inputs]
-    outs = {k: torch.empty(*shape, dtype=dt, device="cuda") for k, shape, dt in outputs if shape is not None}
+    args = [[up(x, dt) for x in a] if isinstance(a, list) else up(a, dt) for a, dt in inputs]
+    outs = {k: [new(q, dt) for q in shape] if isinstance(shape, list) else new(shape, dt) for k, shape, dt in outputs}
+    outs = {k: t for k, t in outs.items() if t is not None}
     args += [outs.get(k) for k, _, _ in outputs]
     if scratch:
         args.append(torch.empty(int(getattr(lib, "ArapFlow_" + scratch)(*dims)), dtype=torch.uint8, device="cuda"))
     torch.cuda.synchronize()
-    ptr = lambda t: _dev_ptr(t) if isinstance(t, torch.Tensor) else t
+
+    def ptr(t):
+        if isinstance(t, list):
+            return (C.c_void_p * len(t))(*[None if x is None else x.data_ptr() for x in t])
+        return _dev_ptr(t) if isinstance(t, torch.Tensor) else t
     rc = getattr(lib, "ArapFlow_" + name)(state.handle, *dims, *[ptr(t) for t in lead], *[ptr(t) for t in args])
     if rc == -1 and bad_args:
         raise ValueError("ArapFlow_%s: bad arguments" % name)
     if rc != 0:
         raise RuntimeError("ArapFlow_%s failed: %d" % (name, rc))
     torch.cuda.synchronize()
-    return {k: t.cpu().numpy() for k, t in outs.items()}
+    down = lambda t: None if t is None else t.cpu().numpy()
+    return {k: [down(x) for x in t] if isinstance(t, list) else down(t) for k, t in outs.items()}
 
 
 def warp_image(state, rgb, mask_red, flow):
@@ -591,3 +600,42 @@ def background(state, bg, M1, M2, rgb1, mask_red, rgb2, cover2, flow, occ=None, 
                        (occ, np.uint8), (bwd, np.float32), (occ_bwd, np.uint8)],
                       [(k, shape[k] if k in want else None, dt.get(k, torch.uint8)) for k in BG_OUTPUTS],
                       lead=[(bg, np.uint8), bg.shape[1], bg.shape[0], _map6(M1), _map6(M2)])
+
+
+BG_SEQ_OUTPUTS = ("out_rgb", "flow_full", "occ_full")
+
+
+def background_seq(state, bg, maps, mask_red, covers, rgbs, flows, occs=None, want=None):
+    """the moving background of a sequence of m frames, frame 1 -> in-between frames -> frame 2 (ArapFlow_BackgroundSeq,
+    DESIGN.md "Moving background over in-between frames").  bg u8[bgH,bgW,3]; maps [m,6], the frames' sampling maps;
+    mask_red u8[H,W], frame 1's own mask (object: == 0); covers: m masks u8[H,W] (object: != 0; entry 0 is not used and may
+    be None); rgbs: m frames u8[H,W,3]; flows: m - 1 object-side flows f32[H,W,2], flows[f] in the domain of frame f;
+    occs: m - 1 object-side occlusions u8[H,W] (numpy; any entry of rgbs / flows / occs may be None, and so may the
+    lists).  `want`: {name: one flag per frame (out_rgb) or per link (flow_full, occ_full)} over BG_SEQ_OUTPUTS, a name
+    left out: none of it; by default every output whose input is given.  Returns {name: list}, out_rgb per frame,
+    flow_full and occ_full per link, None where an entry was not computed."""
+    mask_red = np.ascontiguousarray(mask_red, np.uint8)
+    H, W = mask_red.shape
+    bg = np.ascontiguousarray(bg, np.uint8)
+    if bg.ndim != 3 or bg.shape[2] != 3:
+        raise ValueError("background_seq: bg [bgH,bgW,3] expected")
+    maps = np.ascontiguousarray(maps, np.float32)
+    if maps.ndim != 2 or maps.shape[1] != 6 or len(maps) < 2:
+        raise ValueError("background_seq: maps [m,6] with m >= 2 expected")
+    m = len(maps)
+    fill = lambda a, n: [None] * n if a is None else list(a)
+    covers, rgbs, flows, occs = fill(covers, m), fill(rgbs, m), fill(flows, m - 1), fill(occs, m - 1)
+    if (len(covers), len(rgbs), len(flows), len(occs)) != (m, m, m - 1, m - 1):
+        raise ValueError("background_seq: %d covers and rgbs, %d flows and occs expected" % (m, m - 1))
+    given = dict(out_rgb=rgbs, flow_full=flows, occ_full=occs)
+    if want is None:
+        want = {k: [a is not None for a in given[k]] for k in BG_SEQ_OUTPUTS}
+    if set(want) - set(BG_SEQ_OUTPUTS) or any(len(want[k]) != len(given[k]) for k in want):
+        raise ValueError("background_seq: bad `want` %r" % (want,))
+    shape = dict(out_rgb=(H, W, 3), flow_full=(H, W, 2), occ_full=(H, W))
+    outputs = [(k, [shape[k] if w else None for w in want.get(k, [False] * len(given[k]))],
+                torch.float32 if k == "flow_full" else torch.uint8) for k in BG_SEQ_OUTPUTS]
+    return _warp_call(state, "BackgroundSeq", (W, H),
+                      [(mask_red, np.uint8), (covers, np.uint8), (rgbs, np.uint8), (flows, np.float32), (occs, np.uint8)],
+                      outputs, lead=[(bg, np.uint8), bg.shape[1], bg.shape[0], m,
+                                     maps.ctypes.data_as(C.POINTER(C.c_float))])

@@ -11,6 +11,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   warp_files                ARAP/warping/src/main.cpp:302-336      (warp_image)
   cover_scale, fit_bg, add_bg            para_gen.py:36-61      (background compositing)
   BgLine, parse_bg, bg_line, run_background, fit_bg_window, bg_maps    the `bg` line: moving background (addition)
+  mid_bg_files, bg_maps_seq, run_background_seq    its mid= / mm= / mid_out= tokens: the camera per in-between frame (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
@@ -95,6 +96,14 @@ def mid_layer_files(prefix, step):
     return dict(occ="%s_s%02d_occ.png" % (prefix, step))
 
 
+def mid_bg_files(prefix, step):
+    """the files a `bg` line's mid_out= token writes (DESIGN.md "Moving background over in-between frames"): `rgb`, the
+    in-between frame after ramp step `step` with the moving background behind it (steps >= 1); `step`, the full-frame
+    flow of the link that starts at that frame, and `occ`, that link's full-frame occlusion (step 0 is frame 1 itself)"""
+    stem = "%s_s%02d" % (prefix, step)
+    return dict(rgb=stem + ".png", step=stem + "_step.flo", occ=stem + "_occ.png")
+
+
 def mid_steps(K, num_iter):
     """para_gen --mid K: K ramp steps spread evenly over the ramp, (i * num_iter) // (K + 1) for i = 1 .. K; they must be
     distinct and >= 1 (19 and K = 3: 4, 9, 14)"""
@@ -158,11 +167,16 @@ def layers_line(rgb, layers, out):
 
 class BgLine(NamedTuple):
     """a `bg` line (DESIGN.md "Moving background"), recognised by its first word: the full-frame pass of one pair
-        bg BG.png RGB1.png MASK1.png RGB2.png MASK2.png FLOW.flo m=<12 numbers> [occ=IN] [bwd=IN] [occ_bwd=IN]
-           out=RGB1_OUT.png,RGB2_OUT.png,FLOW_OUT.flo [occ_out=..] [bwd_out=..] [occ_bwd_out=..]
+        bg BG.png RGB1.png MASK1.png RGB2.png MASK2.png FLOW.flo m=<12 numbers> [mid=I1,..,In:PREFIX mm=<6n numbers>]
+           [occ=IN] [bwd=IN] [occ_bwd=IN] out=RGB1_OUT.png,RGB2_OUT.png,FLOW_OUT.flo [occ_out=..] [bwd_out=..]
+           [occ_bwd_out=..] [mid_out=PREFIX_OUT]
     MASK1: the solver's mask (red 0 = object); MASK2: a warped mask (non-zero = object).  `m`: M1 then M2, twelve
     float32 written with %.9g, comma separated.  `out`: three paths, any of them empty (not wanted).  `inputs` / `outs`:
-    {key: path} over BG_IN_KEYS / BG_OUT_KEYS; an output needs its input.  At least one output."""
+    {key: path} over BG_IN_KEYS / BG_OUT_KEYS; an output needs its input.  At least one output.
+    `mid`, `mm`, `mid_out` (DESIGN.md "Moving background over in-between frames"), all three or none: the text of a mid=
+    token (parse_mid) naming the pair's in-between files (mid_files, and with occ= the link occlusions of
+    mid_layer_files), the sampling maps of the n in-between frames (6n float32, as `m`), and the prefix of the files of
+    mid_bg_files that the sequence pass writes."""
     bg: str
     rgb1: str
     mask1: str
@@ -173,23 +187,38 @@ class BgLine(NamedTuple):
     inputs: dict
     out: tuple
     outs: dict
+    mid: str = ""
+    mm: tuple = ()
+    mid_out: str = ""
+
+
+def _bg_numbers(text):
+    try:
+        return tuple(float(np.float32(float(q))) for q in text.split(","))
+    except ValueError:
+        return ()
 
 
 def parse_bg(tokens):
     if len(tokens) < 7 or tokens[0] != BG_WORD:
         raise ValueError("not a bg line: %r" % " ".join(tokens))
     m, out, inputs, outs = None, ("", "", ""), {}, {}
+    mid, mm, mid_out = "", None, ""
     for t in tokens[7:]:
         k, eq, v = t.partition("=")
         if not (eq and v):
             raise ValueError("bg line: bad token %r" % t)
         if k == "m":
-            try:
-                m = tuple(float(np.float32(float(q))) for q in v.split(","))
-            except ValueError:
-                m = ()
+            m = _bg_numbers(v)
             if len(m) != 12:
                 raise ValueError("bg line: m= takes 12 numbers, M1 then M2: %r" % t)
+        elif k == "mid":
+            parse_mid(v)
+            mid = v
+        elif k == "mm":
+            mm = _bg_numbers(v)
+        elif k == "mid_out":
+            mid_out = v
         elif k == "out":
             out = tuple(v.split(","))
             if len(out) != 3:
@@ -205,23 +234,39 @@ def parse_bg(tokens):
     for k in outs:
         if k[:-len("_out")] not in inputs:
             raise ValueError("bg line: %s= needs %s=" % (k, k[:-len("_out")]))
-    if not any(out) and not outs:
+    if mid or mm is not None or mid_out:
+        if not (mid and mm is not None and mid_out):
+            raise ValueError("bg line: mid=, mm= and mid_out= come together: %r" % " ".join(tokens))
+        if len(mm) != 6 * len(parse_mid(mid)[0]):
+            raise ValueError("bg line: mm= takes six numbers per index of mid=: %r" % " ".join(tokens))
+    if not any(out) and not outs and not mid_out:
         raise ValueError("bg line without an output: %r" % " ".join(tokens))
-    return BgLine(*tokens[1:7], m=m, inputs=inputs, out=out, outs=outs)
+    return BgLine(*tokens[1:7], m=m, inputs=inputs, out=out, outs=outs, mid=mid, mm=mm or (), mid_out=mid_out)
 
 
 def bg_line(item):
-    """the inverse of parse_bg; optional tokens in the order of BG_IN_KEYS, out=, BG_OUT_KEYS"""
+    """the inverse of parse_bg; optional tokens in the order mid=, mm=, BG_IN_KEYS, out=, BG_OUT_KEYS, mid_out="""
     tok = [BG_WORD] + list(item[:6]) + ["m=" + ",".join("%.9g" % v for v in item.m)]
+    if item.mid:
+        tok += ["mid=" + item.mid, "mm=" + ",".join("%.9g" % v for v in item.mm)]
     tok += ["%s=%s" % (k, item.inputs[k]) for k in BG_IN_KEYS if item.inputs.get(k)]
     if any(item.out):
         tok.append("out=" + ",".join(item.out))
-    return " ".join(tok + ["%s=%s" % (k, item.outs[k]) for k in BG_OUT_KEYS if item.outs.get(k)])
+    tok += ["%s=%s" % (k, item.outs[k]) for k in BG_OUT_KEYS if item.outs.get(k)]
+    return " ".join(tok + (["mid_out=" + item.mid_out] if item.mid_out else []))
 
 
 def bg_outputs(item):
-    """every file a bg line writes, in the fixed order out= (three places), then BG_OUT_KEYS"""
-    return [q for q in item.out if q] + [item.outs[k] for k in BG_OUT_KEYS if item.outs.get(k)]
+    """every file a bg line writes, in the fixed order out= (three places), then BG_OUT_KEYS, then those of mid_out=:
+    the in-between frames, the link flows (frame 1's first), and with occ= the link occlusions"""
+    files = [q for q in item.out if q] + [item.outs[k] for k in BG_OUT_KEYS if item.outs.get(k)]
+    if item.mid_out:
+        steps = parse_mid(item.mid)[0]
+        files += [mid_bg_files(item.mid_out, i)["rgb"] for i in steps]
+        files += [mid_bg_files(item.mid_out, i)["step"] for i in (0,) + steps]
+        if "occ" in item.inputs:
+            files += [mid_bg_files(item.mid_out, i)["occ"] for i in (0,) + steps]
+    return files
 
 
 def parse_line(line):
@@ -292,7 +337,8 @@ def run_layers(state, spec):
 
 def run_background(state, spec):
     """one `bg` line: read the background picture, the pair's frames, masks, flow and the object-side maps the line
-    names, one opt.background, write what the line asks for (RGB: RGB PNG; flows: .flo; occlusions: 8-bit L PNG)"""
+    names, one opt.background, write what the line asks for (RGB: RGB PNG; flows: .flo; occlusions: 8-bit L PNG); then,
+    with mid=, the sequence pass run_background_seq"""
     from . import opt
     bg, rgb1, rgb2 = load_rgb(spec.bg), load_rgb(spec.rgb1), load_rgb(spec.rgb2)
     mask_red = load_mask_red(spec.mask1)
@@ -313,7 +359,8 @@ def run_background(state, spec):
     names.update(occ_full=spec.outs.get("occ_out"), bwd_full=spec.outs.get("bwd_out"),
                  occ_bwd_full=spec.outs.get("occ_bwd_out"))
     want = [k for k in opt.BG_OUTPUTS if names.get(k)]
-    r = opt.background(state, bg, spec.m[:6], spec.m[6:], rgb1, mask_red, rgb2, cover2, fl, want=want, **inp)
+    if want:
+        r = opt.background(state, bg, spec.m[:6], spec.m[6:], rgb1, mask_red, rgb2, cover2, fl, want=want, **inp)
     for k in want:
         if k.startswith("out_rgb"):
             Image.fromarray(r[k]).save(names[k])
@@ -321,6 +368,43 @@ def run_background(state, spec):
             flo.flow_write(names[k], r[k])
         else:
             save_occ(r[k], names[k])
+    if spec.mid:
+        run_background_seq(state, spec, bg, mask_red, cover2)
+
+
+def run_background_seq(state, spec, bg, mask_red, cover2):
+    """the mid= / mm= / mid_out= tokens of a `bg` line (DESIGN.md "Moving background over in-between frames"): the
+    frames are frame 1, the snapshots of mid= and frame 2; one opt.background_seq over them writes the files of
+    mid_bg_files -- every in-between frame, every link's flow and, with occ= on the line, every link's occlusion.  The
+    composites of frame 1 and frame 2 stay with out=."""
+    from . import opt
+    steps, prefix = parse_mid(spec.mid)
+    H, W = mask_red.shape
+
+    def read(path, load):
+        if not osp.exists(path):
+            raise ValueError("bg line: snapshot %s is missing" % path)
+        a = load(path)
+        if a.shape[:2] != (H, W):
+            raise ValueError("bg line: %s differs in size from %s" % (path, spec.mask1))
+        return a
+    files = [mid_files(prefix, i) for i in steps]
+    covers = [None] + [np.where(read(f["mask"], load_mask_red) != 0, 255, 0).astype(np.uint8) for f in files] + [cover2]
+    rgbs = [None] + [read(f["rgb"], load_rgb) for f in files] + [None]
+    flows = [read(files[0]["flow"], flo.flow_read)] + [read(f["step"], flo.flow_read) for f in files]
+    occs = None
+    if "occ" in spec.inputs:
+        gray = lambda q: np.array(Image.open(q).convert("L"))
+        occs = [read(mid_layer_files(prefix, i)["occ"], gray) for i in (0,) + steps]
+    maps = np.asarray(spec.m[:6] + spec.mm + spec.m[6:], np.float32).reshape(-1, 6)
+    r = opt.background_seq(state, bg, maps, mask_red, covers, rgbs, flows, occs)
+    for k, i in enumerate((0,) + steps):
+        out = mid_bg_files(spec.mid_out, i)
+        if k:
+            Image.fromarray(r["out_rgb"][k]).save(out["rgb"])
+        flo.flow_write(out["step"], r["flow_full"][k])
+        if occs is not None:
+            save_occ(r["occ_full"][k], out["occ"])
 
 
 def owner_flow(masks, flows):
@@ -608,11 +692,14 @@ def _affine_compose(A, B):
     return (a * g + b * j, a * h + b * k, a * i + b * l + c, d * g + e * j, d * h + e * k, d * i + e * l + f)
 
 
-def bg_maps(win_left, win_top, frame_wh, bg_wh, rng, fd=1, strength=1.0):
-    """The sampling maps (M1, M2) of a pair over the enlarged background (DESIGN.md "Moving background"), float32 [6]
-    each.  M1 is the window translation.  M2 = M1 o S with S a similarity about the frame centre: rotation, log-scale
-    and a shift in x and y, drawn from `rng` in this order, uniformly within strength x BG_MOTION_PER_FD x fd.  While a
-    frame corner maps outside [0, bgW - 1] x [0, bgH - 1] the parameters are halved, up to 8 times; then M2 = M1."""
+def bg_maps_seq(win_left, win_top, frame_wh, bg_wh, rng, fractions, fd=1, strength=1.0):
+    """The sampling maps of a pair and of its in-between frames over the enlarged background (DESIGN.md "Moving
+    background", "Moving background over in-between frames"): (M1, [M at each fraction], M2), float32 [6] each.  M1 is
+    the window translation.  With S(tau) the similarity about the frame centre with rotation tau x rot, log-scale tau x
+    lsc and shift tau x (sx, sy), the frame at fraction tau gets M1 o S(tau) and M2 = M1 o S(1); rot, lsc, sx, sy are
+    drawn from `rng` in this order, uniformly within strength x BG_MOTION_PER_FD x fd.  While a frame corner maps outside
+    [0, bgW - 1] x [0, bgH - 1] under any map of the sequence the parameters are halved, up to 8 times; then every map
+    is M1."""
     W, H = frame_wh
     bw, bh = bg_wh
     M1 = (1.0, 0.0, float(win_left), 0.0, 1.0, float(win_top))
@@ -620,20 +707,38 @@ def bg_maps(win_left, win_top, frame_wh, bg_wh, rng, fd=1, strength=1.0):
     rot, lsc = rng.uniform(-lim[0], lim[0]), rng.uniform(-lim[1], lim[1])
     sx, sy = rng.uniform(-lim[2], lim[2]), rng.uniform(-lim[2], lim[2])
     cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
-    M2 = None
-    for _ in range(9):
-        t, sc = np.deg2rad(rot), np.exp(lsc)
-        a, b = sc * np.cos(t), sc * np.sin(t)
-        S = (a, -b, cx - a * cx + b * cy + sx, b, a, cy - b * cx - a * cy + sy)
-        cand = np.asarray(_affine_compose(M1, S), np.float32)
+    taus = [float(t) for t in fractions] + [1.0]
+
+    def inside(cand):
         m = cand.astype(np.float64)
         corners = [(m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]) for x in (0, W - 1) for y in (0, H - 1)]
-        if all(0 <= px <= bw - 1 and 0 <= py <= bh - 1 for px, py in corners):
-            M2 = cand
+        return all(0 <= px <= bw - 1 and 0 <= py <= bh - 1 for px, py in corners)
+    found = None
+    for _ in range(9):
+        cands = []
+        for tau in taus:
+            t, sc = np.deg2rad(tau * rot), np.exp(tau * lsc)
+            a, b = sc * np.cos(t), sc * np.sin(t)
+            S = (a, -b, cx - a * cx + b * cy + tau * sx, b, a, cy - b * cx - a * cy + tau * sy)
+            cands.append(np.asarray(_affine_compose(M1, S), np.float32))
+        if all(inside(c) for c in cands):
+            found = cands
             break
         rot, lsc, sx, sy = rot / 2, lsc / 2, sx / 2, sy / 2
     M1 = np.asarray(M1, np.float32)
-    return M1, (M2 if M2 is not None else M1.copy())
+    if found is None:
+        found = [M1.copy() for _ in taus]
+    return M1, found[:-1], found[-1]
+
+
+def bg_maps(win_left, win_top, frame_wh, bg_wh, rng, fd=1, strength=1.0):
+    """The sampling maps (M1, M2) of a pair over the enlarged background (DESIGN.md "Moving background"), float32 [6]
+    each: bg_maps_seq without an in-between frame.  M1 is the window translation.  M2 = M1 o S with S a similarity about
+    the frame centre: rotation, log-scale and a shift in x and y, drawn from `rng` in this order, uniformly within
+    strength x BG_MOTION_PER_FD x fd.  While a frame corner maps outside [0, bgW - 1] x [0, bgH - 1] the parameters are
+    halved, up to 8 times; then M2 = M1."""
+    M1, _, M2 = bg_maps_seq(win_left, win_top, frame_wh, bg_wh, rng, (), fd, strength)
+    return M1, M2
 
 
 def add_bg(im, mk, bgim, bgval=0):

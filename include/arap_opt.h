@@ -387,6 +387,32 @@ int ArapFlow_Background(Opt_State* state, unsigned W, unsigned H, const void* bg
                         void* out_rgb1, void* out_rgb2, void* flow_full, void* occ_full, void* bwd_full,
                         void* occ_bwd_full);
 
+/* Moving background over a sequence of frames (DESIGN.md "Moving background over in-between frames"): frame 1, the
+ * in-between frames t_1 .. t_n of a pair and frame 2 are nframes = n + 2 frames F_0 .. F_{nframes-1}, joined by
+ * nframes - 1 links F_f -> F_{f+1}; one launch does ArapFlow_Background's frame-1 work for every link.  maps
+ * float[nframes][6] (host) are the sampling maps of the frames; the point map of link f is the G of
+ * ArapFlow_BackgroundMaps(maps[f], maps[f+1]).  F_0 has its object where mask_red is 0, F_f (f >= 1) where covers[f]
+ * (a warp's out_mask) is not 0.  The other arguments are HOST arrays of DEVICE pointers (a NULL array: every entry
+ * NULL), buffers as in ArapFlow_Background:
+ *   covers[nframes]       entry 0 unused
+ *   rgbs[nframes]         the frames' object-side RGB
+ *   flows[nframes-1]      the object-side flow of link f, in the domain of F_f
+ *   occs[nframes-1]       the object-side occlusion of link f
+ *   out_rgbs[nframes]     rgbs[f] on the object of F_f, else the bilinear sample of bg at maps[f] (x, y)
+ *   out_flows[nframes-1]  flows[f] on the object of F_f, else G_f (x, y) - (x, y)
+ *   out_occs[nframes-1]   occs[f] on the object of F_f, else 255 where G_f (x, y) leaves the frame or covers[f+1] is
+ *                         set at its nearest pixel
+ * An output entry that is NULL is not computed and its input not read.  With nframes = 2 the outputs are
+ * ArapFlow_Background's out_rgb1, flow_full, occ_full and out_rgb2, bit for bit.  No output may alias an input.  Needs
+ * no scratch.  Asynchronous on the state's stream.  Returns 0; -1, and nothing is launched, on bad arguments: a null
+ * state, bg, maps, mask_red, covers or covers[f] for f >= 1, nframes outside 2 .. ARAPFLOW_MAX_SNAPSHOTS + 2, a zero
+ * size, W * H >= 2^31, an output whose object-side input is NULL, no output at all, or two consecutive maps that
+ * ArapFlow_BackgroundMaps refuses; else a HIP error code. */
+int ArapFlow_BackgroundSeq(Opt_State* state, unsigned W, unsigned H, const void* bg, unsigned bgW, unsigned bgH,
+                           unsigned nframes, const float* maps, const void* mask_red, const void* const* covers,
+                           const void* const* rgbs, const void* const* flows, const void* const* occs,
+                           void* const* out_rgbs, void* const* out_flows, void* const* out_occs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
                      [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
-                     [--bg_dir DIR [--bg_motion [STRENGTH]]]
+                     [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -32,6 +32,12 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     composited as before; the warped frame's background, the full-frame flow OUT/FlowFull and, with --occ / --occ_layers
     / --bwd_flow, OUT/OccFull, OUT/FlowBwdFull, OUT/OccBwdFull come from one `bg` line per pair, handed to the pair's
     worker once its solves (and flatten / layers line) are done.
+  * --mid_bg (needs --bg_motion and --mid K or --multseg --mid_layers K) moves the camera through the in-between frames
+    too (DESIGN.md "Moving background over in-between frames"): the frame after ramp step i gets the camera at the
+    fraction i / 19 of the pair's motion, the pair's bg line names the snapshots (mid=), their cameras (mm=) and
+    OUT/MidFull/<seq>/<frame> (mid_out=), and one sequence pass of the worker writes there every in-between frame over
+    the moving background and every link's full-frame flow (with --mid_layers K --occ_layers: and occlusion).  OUT/Mid
+    keeps the object-side files.
 """
 import argparse
 import json
@@ -60,6 +66,7 @@ orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
+mid_full_dir = "MidFull"           # --mid_bg: the in-between frames and links with the moving background (addition)
 mid_dir = "Mid"                    # --mid K: in-between frames from the constraint ramp (addition)
 NUM_ITER = 19                      # the ramp length of the ARAP drivers (main.cpp:215-221): what --mid K spreads over
 LAYERS_OCC = "occl_gen"            # --multseg --occ_layers: the frame's forward occlusion, made by a `layers` line
@@ -84,6 +91,19 @@ def mid_layer_paths(p):
     out = [pipeline.mid_files(p["midl_gen"], i)[k] for i in p["_midl"] for k in ("flow", "rgb", "mask", "step")]
     if LAYERS_OCC in p:
         out += [pipeline.mid_layer_files(p["midl_gen"], i)["occ"] for i in (0,) + tuple(p["_midl"])]
+    return out
+
+
+def mid_bg_paths(p):
+    """--mid_bg: every file of a pair's bg line's mid_out= token (pipeline.bg_outputs' order: the in-between frames, the
+    link flows from frame 1's on, then -- with --occ_layers -- the link occlusions); [] without"""
+    if "midbg_gen" not in p:
+        return []
+    steps = tuple(p["_midbg"])
+    out = [pipeline.mid_bg_files(p["midbg_gen"], i)["rgb"] for i in steps]
+    out += [pipeline.mid_bg_files(p["midbg_gen"], i)["step"] for i in (0,) + steps]
+    if LAYERS_OCC in p:
+        out += [pipeline.mid_bg_files(p["midbg_gen"], i)["occ"] for i in (0,) + steps]
     return out
 
 
@@ -174,6 +194,7 @@ def prepare_pair(args):
     seq, stem = p.pop("_seq"), p.pop("_stem")
     line = pipeline.make_arap_path(p)
     p.pop("_mid", None)
+    midbg, midbg_out = p.pop("_midbg", None), p.pop("midbg_gen", None)      # --mid_bg: the snapshot steps, the output prefix
     midl = p.pop("_midl", None)                 # --mid_layers: the snapshot steps of every segment's solve
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
@@ -201,7 +222,9 @@ def prepare_pair(args):
         rng = rn.Random(_pair_id(seq, stem))
         big, (left, top) = pipeline.fit_bg_window(bgim, im1, rng=rng)          # the window and frame 1 of a run without
         H, W = im1.shape[:2]
-        maps = pipeline.bg_maps(left, top, (W, H), (big.shape[1], big.shape[0]), rng, flags.fd, flags.bg_motion)
+        # camera and objects move in step: after ramp step i every handle has covered i / NUM_ITER of its displacement
+        M1, mids, M2 = pipeline.bg_maps_seq(left, top, (W, H), (big.shape[1], big.shape[0]), rng,
+                                            [i / float(NUM_ITER) for i in midbg or ()], flags.fd, flags.bg_motion)
         out1 = pipeline.add_bg(im1, mk1, big[top:top + H, left:left + W, :])
         bgim = None
     elif bgim is not None:
@@ -245,9 +268,14 @@ def prepare_pair(args):
         inputs = {k: v for k, v in dict(occ=occ_in, bwd=p.get("bwd_gen"), occ_bwd=p.get("occbwd_gen")).items() if v}
         outs = {k + "_out": p[g] for k, g in dict(occ="occfull_gen", bwd="bwdfull_gen", occ_bwd="occbwdfull_gen").items()
                 if k in inputs and g in p}
+        tokens = {}
+        if midbg:                               # the snapshots' files exist when the line is handed out: after the solve / layers line
+            os.makedirs(osp.dirname(midbg_out), exist_ok=True)
+            tokens = dict(mid=pipeline.mid_token(midbg, p.get("mid_gen", p.get("midl_gen"))),
+                       mm=tuple(float(v) for v in np.concatenate(mids)), mid_out=midbg_out)
         rec.motion = pipeline.BgLine(rec.bg, line.rgb, mask1, line.out_rgb, line.out_mask, line.flow,
-                                     m=tuple(float(v) for v in np.concatenate(maps)), inputs=inputs,
-                                     out=("", line.out_rgb, p["flowfull_gen"]), outs=outs)
+                                     m=tuple(float(v) for v in np.concatenate([M1, M2])), inputs=inputs,
+                                     out=("", line.out_rgb, p["flowfull_gen"]), outs=outs, **tokens)
         open(stem_tmp + "_bg.txt", "w").write(pipeline.format_line(rec.motion))
         rec.tmp = tuple(q for q in (rec.bg, mask1 if segs is not None else None, stem_tmp + "_bg.txt") if q)
     return rec
@@ -454,7 +482,7 @@ def scan(flags, input_root, output_root):
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
-                                                           obw=occ_bwd_dir, occ=occ_dir, mid=mid_dir, ful=full_dir,
+                                                           obw=occ_bwd_dir, occ=occ_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
                                                            ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
     all_paths = []
@@ -499,8 +527,11 @@ def scan(flags, input_root, output_root):
                     e["_mid"] = tuple(flags.mid_steps)
                 if "midl_gen" in e:
                     e["_midl"] = tuple(flags.mid_layers_steps)
+                if getattr(flags, "mid_bg", False):
+                    e["midbg_gen"] = osp.abspath(osp.join(roots["mfu"], seq, f))
+                    e["_midbg"] = tuple(flags.mid_steps or flags.mid_layers_steps)
                 # every requested output
-                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e)
+                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e) + mid_bg_paths(e)
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -551,7 +582,8 @@ def main(flags):
     for p in all_paths:
         ln = pipeline.make_arap_path(p)
         lmdb_paths.append([ln.rgb, ln.out_rgb, ln.flow])
-        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p))
+        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p) +
+                         mid_bg_paths(p))
 
     # backgrounds: drawn without replacement until the list is used up, then refilled (para_gen.py:484-499)
     tmp_paths, picks = [], []
@@ -739,7 +771,22 @@ def parse(argv=None):
                              "<frame>_s00_occ.png, <frame>_sII_occ.png (DESIGN.md \"Layered in-between frames\")")
     parser.add_argument("--keep_segments", action="store_true", default=False,
                         help="with --multseg: keep the per-segment files after they are merged (for inspection)")
+    parser.add_argument("--mid_bg", action="store_true", default=False,
+                        help="with --bg_motion and --mid K or --multseg --mid_layers K: move the camera through the "
+                             "in-between frames too and write OUT/MidFull/<seq>/<frame>_sII.png (the in-between frame over "
+                             "the moving background) and _s00_step.flo, _sII_step.flo (the full-frame flow of every link); "
+                             "with --mid_layers K --occ_layers also the links' full-frame occlusions _s00_occ.png, "
+                             "_sII_occ.png.  A plain --mid K run has no object-side link occlusion, so it writes none and "
+                             "cannot be combined with --occ here (DESIGN.md \"Moving background over in-between frames\")")
     flags = parser.parse_args(argv)
+    if flags.mid_bg:
+        if flags.bg_motion is None:
+            parser.error("--mid_bg needs --bg_motion: it moves that camera through the in-between frames")
+        if not (flags.mid or flags.mid_layers):
+            parser.error("--mid_bg needs --mid K or --multseg --mid_layers K: there is no in-between frame")
+        if flags.mid and flags.occ:
+            parser.error("--mid_bg with --mid K cannot be combined with --occ: the pair's occlusion would ask for link "
+                         "occlusions, which a --mid K run does not make; use --multseg --mid_layers K --occ_layers")
     if flags.occ and flags.multseg:
         parser.error("--occ cannot be combined with --multseg: forward occlusion across segments needs one query over "
                      "every segment's solve, which --occ does not do; use --multseg --occ_layers (--bwd_flow --multseg "
@@ -755,9 +802,10 @@ def parse(argv=None):
     if flags.bg_motion is not None:
         if not flags.bg_dir:
             parser.error("--bg_motion needs --bg_dir: there is no background to move")
-        if flags.mid or flags.mid_layers:
+        if (flags.mid or flags.mid_layers) and not flags.mid_bg:
             parser.error("--bg_motion cannot be combined with --mid / --mid_layers: the background motion of an "
-                         "in-between frame needs the motion interpolated per snapshot, which is not built")
+                         "in-between frame needs the motion interpolated per snapshot, which is not built without "
+                         "--mid_bg")
         if not own_arap_bin(flags.arap_bin):
             parser.error("--bg_motion needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin "
                          "does not know the bg line")

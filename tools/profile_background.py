@@ -7,6 +7,12 @@ the library's device events (ArapFlow_TimerBegin / End).  Prints one JSON line: 
 streams (inputs read and outputs written once, the picture's gathers not counted) and the rate that makes.  For the
 kernel table run it under the profiler, in a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/profile_background.py
+
+--seq (profiles/bg_seq/README.md): the sequence pass instead.  Frame 1, n = 3 in-between frames and frame 2 at 854x480
+over the same picture, the camera at the fractions 4/19, 9/19, 14/19 and 1 of that similarity: ITER ArapFlow_BackgroundSeq
+calls with every output on (one k_bg_seq launch each), ITER with the last frame's RGB left out, and as the yardstick ITER
+rounds of n + 1 ArapFlow_Background calls for out_rgb1, flow_full and occ_full of the same links (one k_bg_frame1 launch
+each, a later frame's cover handed over as a solver mask).  One JSON line with the three times.
 """
 import ctypes as C
 import json
@@ -65,5 +71,82 @@ def main():
     st.close()
 
 
+def similarity(tau):
+    """the camera at the fraction tau of main()'s similarity, as six floats"""
+    t, sc = np.deg2rad(1.5 * tau), 1.01 ** tau
+    a, b, cx, cy = sc * np.cos(t), sc * np.sin(t), (W - 1) / 2.0, (H - 1) / 2.0
+    return [a, -b, 170 + cx - a * cx + b * cy + 4 * tau, b, a, 110 + cy - b * cx - a * cy - 2 * tau]
+
+
+def main_seq():
+    import torch
+    from arap_flow_amd import opt
+    rng = np.random.default_rng(0)
+    n = 3
+    m = n + 2
+    ys, xs = np.mgrid[0:H, 0:W]
+    ellipse = lambda f: ((xs - 0.45 * W - 3 * f) / (0.22 * W)) ** 2 + ((ys - 0.5 * H) / (0.3 * H)) ** 2 <= 1
+    mask = np.where(ellipse(0), 0, 255).astype(np.uint8)
+    covers = [None] + [np.where(ellipse(f), 255, 0).astype(np.uint8) for f in range(1, m)]
+    flow = np.stack([3.0 + 0.01 * (ys - H / 2), -1.0 + 0.01 * (xs - W / 2)], -1).astype(np.float32)
+    flows = [np.where(ellipse(f)[..., None], flow, np.float32(0)) for f in range(m - 1)]
+    rgbs = [rng.integers(0, 256, (H, W, 3)).astype(np.uint8) for _ in range(m)]
+    occs = [np.where(rng.integers(0, 2, (H, W)) != 0, 255, 0).astype(np.uint8) for _ in range(m - 1)]
+    bg = rng.integers(0, 256, (BH, BW, 3)).astype(np.uint8)
+    maps = np.asarray([similarity(t) for t in (0.0, 4 / 19.0, 9 / 19.0, 14 / 19.0, 1.0)], np.float32)
+    st = opt.State()
+    up = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    d_bg, d_mask = up(bg), up(mask)
+    d_cov, d_rgb, d_flow, d_occ = [[up(x) for x in v] for v in (covers, rgbs, flows, occs)]
+    d_own = [d_mask] + [up(np.where(c != 0, 0, 255).astype(np.uint8)) for c in covers[1:-1]]     # the yardstick's own masks
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device="cuda")
+    o_rgb = [new((H, W, 3), torch.uint8) for _ in range(m)]
+    o_flow = [new((H, W, 2), torch.float32) for _ in range(m - 1)]
+    o_occ = [new((H, W), torch.uint8) for _ in range(m - 1)]
+    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    arr = lambda ts: (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+    mp = maps.ctypes.data_as(C.POINTER(C.c_float))
+    m6 = lambda f: (C.c_float * 6)(*maps[f].tolist())
+
+    def seq(out_rgb):
+        rc = st.lib.ArapFlow_BackgroundSeq(st.handle, W, H, p(d_bg), BW, BH, m, mp, p(d_mask), arr(d_cov), arr(d_rgb), arr(d_flow),
+                                           arr(d_occ), arr(out_rgb), arr(o_flow), arr(o_occ))
+        assert rc == 0, rc
+
+    def pairs():
+        for f in range(m - 1):
+            rc = st.lib.ArapFlow_Background(st.handle, W, H, p(d_bg), BW, BH, m6(f), m6(f + 1), p(d_rgb[f]), p(d_own[f]), None,
+                                            p(d_cov[f + 1]), p(d_flow[f]), p(d_occ[f]), None, None, p(o_rgb[f]), None,
+                                            p(o_flow[f]), p(o_occ[f]), None, None)
+            assert rc == 0, rc
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        for _ in range(WARM):
+            fn()
+        torch.cuda.synchronize()
+        st.timer_begin()
+        for _ in range(ITER):
+            fn()
+        return 1e3 * st.timer_end() / ITER
+
+    pairs()
+    torch.cuda.synchronize()
+    ref = [t.clone() for t in o_rgb[:-1] + o_flow + o_occ]
+    for t in o_rgb + o_flow + o_occ:
+        t.zero_()
+    seq(o_rgb)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(ref, o_rgb[:-1] + o_flow + o_occ)), \
+        "the sequence pass and the pair passes differ"
+    N = W * H
+    print(json.dumps(dict(what="ArapFlow_BackgroundSeq, n = 3", W=W, H=H, bg=[BW, BH], frames=m, calls=ITER,
+                          us_seq_every_output=timed(lambda: seq(o_rgb)),
+                          us_seq_without_last_rgb=timed(lambda: seq(o_rgb[:-1] + [None])),
+                          us_pair_passes=timed(pairs), pair_passes_per_round=m - 1,
+                          streamed_bytes_seq=N * ((m - 1) * (3 + 1 + 8 + 1 + 3 + 8 + 1) + (3 + 1 + 3)))))
+    st.close()
+
+
 if __name__ == "__main__":
-    main()
+    main_seq() if "--seq" in sys.argv[1:] else main()
