@@ -16,6 +16,16 @@ class Opt_InitializationParameters(C.Structure):
                 ("collectPerKernelTimingInfo", C.c_int), ("threadsPerBlock", C.c_int)]
 
 
+class MeshStats(C.Structure):
+    """ArapFlow_MeshStats (DESIGN.md "Fold diagnostics")"""
+    _fields_ = [("vertices", C.c_uint32), ("outside", C.c_uint32), ("triangles", C.c_uint32), ("folded", C.c_uint32),
+                ("nonfinite", C.c_uint32), ("reserved", C.c_uint32), ("det_min", C.c_float), ("det_max", C.c_float),
+                ("disp2_max", C.c_float)]
+
+
+MESH_STATS_KEYS = tuple(k for k, _ in MeshStats._fields_ if k != "reserved")     # the order of a diag file's lines
+
+
 # every symbol include/arap_opt.h declares: (name, restype, argtypes)
 _VP, _U, _I = C.c_void_p, C.c_uint, C.c_int
 SYMBOLS = [
@@ -80,6 +90,10 @@ SYMBOLS = [
     ("ArapFlow_BackgroundMaps", _I, [C.POINTER(C.c_float)] * 4),
     ("ArapFlow_Background", _I, [_VP, _U, _U, _VP, _U, _U, C.POINTER(C.c_float), C.POINTER(C.c_float)] + [_VP] * 14),
     ("ArapFlow_BackgroundSeq", _I, [_VP, _U, _U, _VP, _U, _U, _U, C.POINTER(C.c_float), _VP] + [C.POINTER(_VP)] * 7),
+    ("ArapFlow_WarpDiag", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP]),
+    ("ArapFlow_SolverSetDiag", _I, [_VP, _I]),
+    ("ArapFlow_SolverGetDiag", _I, [_VP, _U, C.POINTER(MeshStats), _VP]),
+    ("ArapFlow_SolverHostDiag", _I, [_VP, _U, C.POINTER(C.POINTER(MeshStats)), C.POINTER(_VP)]),
 ]
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h

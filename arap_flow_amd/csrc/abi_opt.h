@@ -111,6 +111,7 @@ void ArapFlow_FreeState(Opt_State* st)
     (void)hipEventDestroy(st->t0);
     (void)hipEventDestroy(st->t1);
     st->ktimer.clear();
+    if (st->diag) (void)hipFree(st->diag);
     delete st;
 }
 

@@ -72,6 +72,16 @@ struct ArapFlow_Solver {
     WarpJob* pin_mid_jobs = nullptr;
     char* pin_mid = nullptr;         // [mid_cap][batch] x {flow float2[N], step float2[N], rgb u8[3N], mask u8[N]}
     size_t pin_mid_slot = 0;
+    // fold diagnostics (ArapFlow_SolverSetDiag, DESIGN.md "Fold diagnostics"); nothing is allocated while off
+    int diag = 0;                    // on for the next warps
+    int warp_diag = 0;               // ... in effect at the last warp
+    int dl_diag = 0;                 // ... downloaded by the last solve call
+    void* dgn = nullptr;             // device: [batch] fold maps u8[N], then [batch] DiagAcc, then [batch] ArapFlow_MeshStats
+    size_t dgn_fold_slot = 0;
+    DiagAcc* dgn_acc = nullptr;
+    ArapFlow_MeshStats* dgn_stats = nullptr;
+    char* pin_diag = nullptr;        // [batch] x {ArapFlow_MeshStats (256 bytes), fold u8[N]}   (allocated on first download)
+    size_t pin_diag_slot = 0;
 };
 
 // pinned staging of the snapshot downloads (as solver_pin_out: when first needed)
@@ -128,10 +138,15 @@ static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
         j.occ_bwd = (o & ARAPFLOW_OUT_BACKWARD) ? e->occ_bwd : nullptr;
         j.occ = (o & ARAPFLOW_OUT_OCCLUSION) ? e->occ : nullptr;
         j.cell = e ? e->cell : nullptr; j.rank = e ? e->rank : nullptr; j.bin = e ? e->bin : nullptr;
+        j.fold = s->diag ? (uint8_t*)s->dgn + s->dgn_fold_slot * b : nullptr;
+        j.acc = s->diag ? s->dgn_acc + b : nullptr;
+        j.stats = s->diag ? s->dgn_stats + b : nullptr;
     }
     HC(hipMemcpyAsync(s->djobs, jobs, sizeof(WarpJob) * nframes, hipMemcpyHostToDevice, st->stream));
     enqueue_warp(st->stream, s->djobs, nframes, s->W, s->H, s->outputs, s->ext_cells, s->ext_cell_slot * nframes);
     s->warp_outputs = s->outputs;
+    if (s->diag) enqueue_warp_diag(st->stream, s->djobs, nframes, s->W, s->H, s->dgn_acc, sizeof(DiagAcc) * nframes);
+    s->warp_diag = s->diag;
     // the in-between frames of the last solve: one warp pass per snapshot over the slots, on the field S_{i_k}, with the
     // step towards the next state; the slot's key image serves every pass (k_warp_resolve left it cleared)
     const unsigned n = s->taken_n;
@@ -170,6 +185,13 @@ static void solver_pin_ext(ArapFlow_Solver* s)
     if (s->pin_ext) return;
     s->pin_ext_slot = align_up(10 * (size_t)s->N, 256);
     HC(hipHostMalloc((void**)&s->pin_ext, s->pin_ext_slot * s->batch, hipHostMallocDefault));
+}
+
+static void solver_pin_diag(ArapFlow_Solver* s)
+{
+    if (s->pin_diag) return;
+    s->pin_diag_slot = 256 + align_up((size_t)s->N, 256);
+    HC(hipHostMalloc((void**)&s->pin_diag, s->pin_diag_slot * s->batch, hipHostMallocDefault));
 }
 
 // the whole schedule of slots [0, a_n) on the compute stream (+ warp, + download on the copy stream), no waiting
@@ -235,6 +257,15 @@ static void solver_enqueue(ArapFlow_Solver* s)
                 }
                 if (s->dl_outputs & ARAPFLOW_OUT_OCCLUSION)
                     HC(hipMemcpyAsync(o + 9 * N, e.occ, N, hipMemcpyDeviceToHost, s->copy));
+            }
+        }
+        s->dl_diag = s->a_warp ? s->diag : 0;
+        if (s->dl_diag) {
+            solver_pin_diag(s);
+            for (unsigned b = 0; b < nframes; ++b) {
+                char* o = s->pin_diag + s->pin_diag_slot * b;
+                HC(hipMemcpyAsync(o, s->dgn_stats + b, sizeof(ArapFlow_MeshStats), hipMemcpyDeviceToHost, s->copy));
+                HC(hipMemcpyAsync(o + 256, (uint8_t*)s->dgn + s->dgn_fold_slot * b, N, hipMemcpyDeviceToHost, s->copy));
             }
         }
         s->dl_snap_n = s->a_warp ? s->taken_n : 0;
@@ -342,6 +373,8 @@ void ArapFlow_SolverFree(ArapFlow_Solver* s)
     if (s->mid) (void)hipFree(s->mid);
     if (s->pin_mid_jobs) (void)hipHostFree(s->pin_mid_jobs);
     if (s->pin_mid) (void)hipHostFree(s->pin_mid);
+    if (s->dgn) (void)hipFree(s->dgn);
+    if (s->pin_diag) (void)hipHostFree(s->pin_diag);
     (void)hipFree(s->block);
     delete s;
 }
@@ -585,6 +618,48 @@ int ArapFlow_SolverHostExtraResults(ArapFlow_Solver* s, unsigned slot, const flo
     if (bwd) *bwd = b ? (const float*)o : nullptr;
     if (occ_bwd) *occ_bwd = b ? (const uint8_t*)(o + 8 * N) : nullptr;
     if (occ) *occ = c ? (const uint8_t*)(o + 9 * N) : nullptr;
+    return 0;
+}
+
+int ArapFlow_SolverSetDiag(ArapFlow_Solver* s, int on)
+{
+    if (!s) return -1;
+    if (const int rc = ArapFlow_SolverWait(s)) return rc;
+    if (on && !s->dgn) {
+        HC(hipSetDevice(s->st->device));
+        const size_t B = s->batch;
+        s->dgn_fold_slot = align_up((size_t)s->N, 256);
+        const size_t accs = align_up(sizeof(DiagAcc) * B, 256), stats = align_up(sizeof(ArapFlow_MeshStats) * B, 256);
+        HC(hipMalloc(&s->dgn, s->dgn_fold_slot * B + accs + stats));
+        s->dgn_acc = (DiagAcc*)((char*)s->dgn + s->dgn_fold_slot * B);
+        s->dgn_stats = (ArapFlow_MeshStats*)((char*)s->dgn_acc + accs);
+        if (s->st->own_stream) solver_pin_diag(s);   // (as pin_out: downloads will be asked for)
+    }
+    s->diag = on ? 1 : 0;
+    return 0;
+}
+
+int ArapFlow_SolverGetDiag(ArapFlow_Solver* s, unsigned slot, ArapFlow_MeshStats* stats, uint8_t* fold)
+{
+    if (!s || slot >= (unsigned)s->batch) return -1;
+    if (ArapFlow_SolverWait(s) != 0) return -1;
+    if (!s->warp_diag) return -1;
+    HC(hipStreamSynchronize(s->st->stream));
+    hipStream_t cs = s->copy;
+    if (stats) HC(hipMemcpyAsync(stats, s->dgn_stats + slot, sizeof(ArapFlow_MeshStats), hipMemcpyDeviceToHost, cs));
+    if (fold) HC(hipMemcpyAsync(fold, (uint8_t*)s->dgn + s->dgn_fold_slot * slot, (size_t)s->N, hipMemcpyDeviceToHost, cs));
+    HC(hipStreamSynchronize(cs));
+    return 0;
+}
+
+int ArapFlow_SolverHostDiag(ArapFlow_Solver* s, unsigned slot, const ArapFlow_MeshStats** stats, const uint8_t** fold)
+{
+    if (!s || slot >= (unsigned)s->batch || !s->a_download || slot >= s->a_n) return -1;
+    if (ArapFlow_SolverWait(s) != 0) return -1;
+    if (!s->dl_diag || !s->pin_diag) return -1;
+    const char* o = s->pin_diag + s->pin_diag_slot * slot;
+    if (stats) *stats = (const ArapFlow_MeshStats*)o;
+    if (fold) *fold = (const uint8_t*)(o + 256);
     return 0;
 }
 

@@ -20,6 +20,16 @@ static void enqueue_warp_outputs(hipStream_t stream, const WarpJob* dj, unsigned
     hipLaunchKernelGGL(k_occ_tri, dim3((W + 63) / 64, (H + 3) / 4, njobs), dim3(64, 4), 0, stream, dj, W, H);
 }
 
+// the fold diagnostics (arap_diag.h) of `njobs` jobs at `dj`, anywhere after their fields are final.  `accs`: the jobs'
+// accumulators, `acc_bytes` contiguous bytes, zeroed here; NULL when the jobs ask for the fold map alone
+static void enqueue_warp_diag(hipStream_t stream, const WarpJob* dj, unsigned njobs, int W, int H, void* accs,
+                              size_t acc_bytes)
+{
+    if (accs) HC(hipMemsetAsync(accs, 0, acc_bytes, stream));
+    hipLaunchKernelGGL(k_warp_diag, dim3((W + 63) / 64, (H + 3) / 4, njobs), dim3(64, 4), 0, stream, dj, W, H);
+    if (accs) hipLaunchKernelGGL(k_diag_finish, dim3((njobs + 63) / 64), dim3(64), 0, stream, dj, (int)njobs);
+}
+
 // Scratch of one warp job: the key image, then -- for the occlusion map (WARP_OCC) -- cell counts, ranks and bins, then
 // the layered warp's owner image (WARP_OWNER), then the layered step's query points (WARP_PTS), each aligned to 256
 // bytes, and the WarpJob itself in a last 256 bytes.
@@ -173,6 +183,23 @@ int ArapFlow_WarpStep(Opt_State* st, unsigned W, unsigned H, const void* rgb, co
     HC(hipStreamSynchronize(st->stream));
     HC(hipFree(scratch));
     return rc;
+}
+
+int ArapFlow_WarpDiag(Opt_State* st, unsigned W, unsigned H, const void* mask_red, const void* flow, void* out_fold,
+                      ArapFlow_MeshStats* out_stats)
+{
+    if (!st || !mask_red || !flow || (!out_fold && !out_stats) || W == 0 || H == 0) return -1;
+    if ((uint64_t)W * H >= (1ull << 31)) return -1;                              // (a vertex index in an int)
+    HC(hipSetDevice(st->device));
+    if (!st->diag && hipMalloc(&st->diag, 512) != hipSuccess) return (int)hipErrorOutOfMemory;
+    WarpJob j{};
+    j.flow_in = (const float2*)flow; j.mask = (const uint8_t*)mask_red;
+    j.fold = (uint8_t*)out_fold;
+    if (out_stats) { j.acc = (DiagAcc*)((char*)st->diag + 256); j.stats = out_stats; }
+    WarpJob* dj = (WarpJob*)st->diag;
+    HC(hipMemcpyAsync(dj, &j, sizeof(j), hipMemcpyHostToDevice, st->stream));     // (pageable: staged before the call returns)
+    enqueue_warp_diag(st->stream, dj, 1, (int)W, (int)H, j.acc, sizeof(DiagAcc));
+    return (int)hipGetLastError();
 }
 
 uint64_t ArapFlow_WarpLayersScratchBytes(unsigned W, unsigned H, unsigned n)

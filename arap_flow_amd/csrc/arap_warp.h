@@ -23,7 +23,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct ArapFlow_MeshStats;          // include/arap_opt.h
+
 namespace arap {
+
+struct DiagAcc;                     // arap_diag.h
 
 struct WarpJob {                    // one frame
     const float2* field;            // warp field [N] (Offset), or NULL when `flow_in` is given
@@ -45,6 +49,10 @@ struct WarpJob {                    // one frame
     const float2* field_b;          // [N] second state as positions, or NULL when `flow_b` is given
     const float2* flow_b;           // [N] second state as a flow: position = (x,y) + flow, or NULL
     float2* step;                   // [N] flow from the warp of `field` to the second state, domain of the warped frame
+    // optional outputs of arap_diag.h (DESIGN.md "Fold diagnostics"): NULL = not wanted; `acc` and `stats` go together
+    uint8_t* fold;                  // [N] 255 = object vertex with a folded or non-finite triangle at it
+    DiagAcc* acc;                   // the job's accumulator, all zero on entry
+    ArapFlow_MeshStats* stats;      // the statistics decoded from `acc`
 };
 
 __device__ __forceinline__ float2 warp_pos(const WarpJob& j, int x, int y, int i)

@@ -115,6 +115,7 @@ struct Opt_State {
     int tile = -1;              // ArapFlow_SetTile: phase-A variant of the two-kernel path; -1 = choose per solve
     bool force_b8 = false;      // ARAPOPT_B8=1 (counter calibration): the 8-byte-per-lane form of phase B
     int stream_a = 0;           // ARAPOPT_STREAM_A=1 (experiments): the tiled k_pcg_a_grid instead of the marching kernel
+    void* diag = nullptr;       // ArapFlow_WarpDiag: device, the call's WarpJob (256 bytes) and its accumulator; at first use
 };
 
 struct Opt_Problem {

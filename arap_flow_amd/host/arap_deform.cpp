@@ -8,7 +8,9 @@
 // occlusion), 8-bit 0/255, and mid=I1,I2,..:PREFIX (DESIGN.md "In-between frames"): the in-between frames after the
 // ramp steps I1 < I2 < .., written as PREFIX_sII.flo, PREFIX_sII.png, PREFIX_sII_mask.png and PREFIX_sII_step.flo (II:
 // the step, two digits) in the formats of the line's own flow, warped RGB and warped mask.  All mid= lines of a batch
-// must name the same steps.  Other trailing tokens are ignored, as before.
+// must name the same steps.  diag=PATH.txt and fold=PATH.png (DESIGN.md "Fold diagnostics"): the mesh statistics of the
+// solve as text (pipeline.format_diag) and its fold map, 8-bit 0/255; a batch computes them iff one of its lines asks.
+// Other trailing tokens are ignored, as before.
 // A line whose first word is `layers` is no solve but the layered warp of one frame (DESIGN.md "Layered warp"):
 //   layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P] [mid=I1,I2,..:PREFIX]
 // (at least one output).  Its mid= token (DESIGN.md "Layered in-between frames") reads every layer's snapshot flows
@@ -441,7 +443,7 @@ class FrameSource {
 };
 
 // ---- results: read back from the solver's pinned buffers, encoded and written by worker threads ---------------------
-struct OutFile { FileKind kind; std::string path; std::vector<uint8_t> data; };
+struct OutFile { FileKind kind; std::string path; std::vector<uint8_t> data; bool text = false; };   // text: written as it is
 struct Result { std::string flow; std::vector<OutFile> files; };       // a line's flow path and its files in writing order
 
 class Writer {
@@ -451,7 +453,10 @@ class Writer {
     {
         while (tasks_.size() >= 24) { tasks_.front().get(); tasks_.pop_front(); }
         tasks_.push_back(std::async(std::launch::async, [this, r, w, h]() {
-            for (const OutFile& f : r->files) save(f.kind, f.path, w, h, f.data.data());
+            for (const OutFile& f : r->files) {
+                if (f.text) save_text(f.path, f.data.data(), f.data.size());
+                else save(f.kind, f.path, w, h, f.data.data());
+            }
             say(report_ ? "Done " + r->flow : std::string("Saved"));    // --serve: one line per finished solve
         }));
     }
@@ -476,6 +481,7 @@ struct Lane {
     ArapFlow_Solver* solver = nullptr;
     std::vector<SolvePaths> batch;         // frames set into the slots, in slot order
     bool inflight = false;
+    bool diag = false;                     // fold diagnostics in effect in `solver`
 };
 
 struct Lanes {
@@ -503,7 +509,7 @@ struct Lanes {
         const double rel = (double)nw * nh / (854.0 * 480.0);
         const int m = (int)(32.0 / (rel < 1.0 ? 1.0 : rel));
         maxBatch = (unsigned)(m < 8 ? 8 : m);
-        for (Lane& L : lane) L.solver = ArapFlow_SolverCreate(state, (unsigned)nw, (unsigned)nh, maxBatch);
+        for (Lane& L : lane) { L.solver = ArapFlow_SolverCreate(state, (unsigned)nw, (unsigned)nh, maxBatch); L.diag = false; }
         w = nw; h = nh;
         return lane[0].solver && lane[1].solver;
     }
@@ -549,6 +555,16 @@ struct Lanes {
                 keep(FileKind::gray8, q.occ_bwd, bwd ? obwd : nullptr);
                 keep(FileKind::gray8, q.occ, occ);
             }
+            if (q.wants_diag()) {
+                const ArapFlow_MeshStats* stats; const uint8_t* fold;
+                if (ArapFlow_SolverHostDiag(L.solver, (unsigned)b, &stats, &fold) != 0)
+                    return fail("ARAP diagnostics unavailable\n");
+                if (!q.diag.empty()) {
+                    const std::string text = format_diag(*stats);
+                    r->files.push_back(OutFile{FileKind::gray8, q.diag, std::vector<uint8_t>(text.begin(), text.end()), true});
+                }
+                keep(FileKind::gray8, q.fold, fold);
+            }
             for (unsigned k = 0; k < q.mid.steps.size(); ++k) {
                 const float *mf, *ms; const uint8_t *mr, *mm;
                 if (ArapFlow_SolverHostSnapshot(L.solver, (unsigned)b, k, &mf, &mr, &mm, &ms) != 0 || !mr)
@@ -581,6 +597,12 @@ struct Lanes {
         }
         if (ArapFlow_SolverSetSnapshots(L.solver, steps ? steps->data() : nullptr, steps ? (unsigned)steps->size() : 0) != 0)
             return fail("ARAP snapshots could not be set\n");
+        bool diag = false;                   // likewise: set only to turn the diagnostics on, or off again
+        for (const SolvePaths& q : L.batch) diag = diag || q.wants_diag();
+        if (diag != L.diag) {
+            if (ArapFlow_SolverSetDiag(L.solver, diag) != 0) return fail("ARAP diagnostics could not be set\n");
+            L.diag = diag;
+        }
         if (ArapFlow_SolverSolveAsync(L.solver, (unsigned)L.batch.size(), numIter, nonLinearIter, linearIter, 1, 1) != 0)
             return fail("ARAP solve could not be started\n");
         if (serve) { printf("Batch %zu\n", L.batch.size()); fflush(stdout); }    // (para_gen.py keeps statistics)

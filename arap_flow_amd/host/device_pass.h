@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "../../include/arap_opt.h"
 #include "flo_io.h"
 #include "png_io.h"
 
@@ -25,6 +26,27 @@ inline bool save(FileKind kind, const std::string& path, int w, int h, const voi
                     : kind == FileKind::mask1 ? arapio::write_png_mask1(path, w, h, px, err)
                                               : arapio::write_png_gray8(path, w, h, px, err);
     if (!ok) printf("%s\n", err.c_str());
+    return ok;
+}
+
+// the text of a diag file (pipeline.format_diag): the struct's fields in order, without `reserved`
+inline std::string format_diag(const ArapFlow_MeshStats& s)
+{
+    char text[512];
+    snprintf(text, sizeof(text),
+             "vertices %u\noutside %u\ntriangles %u\nfolded %u\nnonfinite %u\ndet_min %.9g\ndet_max %.9g\ndisp2_max %.9g\n",
+             s.vertices, s.outside, s.triangles, s.folded, s.nonfinite, (double)s.det_min, (double)s.det_max,
+             (double)s.disp2_max);
+    return text;
+}
+
+// a text file, as it is; says why not
+inline bool save_text(const std::string& path, const void* data, size_t bytes)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    const bool ok = f && fwrite(data, 1, bytes, f) == bytes;
+    if (f && fclose(f) != 0) return printf("Could not write %s\n", path.c_str()), false;
+    if (!ok) printf("Could not write %s\n", path.c_str());
     return ok;
 }
 

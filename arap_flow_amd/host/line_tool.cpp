@@ -23,6 +23,7 @@ static std::string canonical(const Item& it)
         const SolvePaths& q = it.solve;
         for (const std::string* s : {&q.rgb, &q.mask, &q.constraints, &q.flow, &q.warped_rgb, &q.warped_mask}) c.word(*s);
         c.token("bwd", q.bwd); c.token("occ", q.occ); c.token("occ_bwd", q.occ_bwd); c.token("mid", q.mid.text);
+        c.token("diag", q.diag); c.token("fold", q.fold);
     } else if (it.kind == Item::Kind::Layers) {
         const LayersSpec& q = it.layers;
         c.word("layers"); c.word(q.rgb); c.word(std::to_string(q.masks.size()));

@@ -1,6 +1,7 @@
 // list_line.h -- the grammar of one list / --serve line of arap_deform, and nothing else: no HIP, no files.  The C++ twin of
 // pipeline.parse_line / done_token; line_tool.cpp prints what it reads so that a test can hold the two side by side.
 //   solve line:   RGB MASK CONSTRAINTS FLOW WARPED_RGB WARPED_MASK [bwd=P] [occ=P] [occ_bwd=P] [mid=I1,I2,..:PREFIX]
+//                 [diag=P.txt] [fold=P.png]
 //                 other trailing tokens are ignored (a line's words after the sixth always were); a malformed mid= is
 //                 the only error
 //   layers line:  layers RGB n MASK_1 FLO_1 ... MASK_n FLO_n [occ=P] [bwd=P] [occ_bwd=P] [rgb2=P] [mask2=P] [mid=..:PREFIX]
@@ -81,6 +82,8 @@ struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
     Mid mid;
+    std::string diag, fold;                // fold diagnostics (DESIGN.md "Fold diagnostics"; empty: not wanted)
+    bool wants_diag() const { return !diag.empty() || !fold.empty(); }
     int outputs() const
     {
         return (bwd.empty() && occ_bwd.empty() ? 0 : ARAPFLOW_OUT_BACKWARD) | (occ.empty() ? 0 : ARAPFLOW_OUT_OCCLUSION);
@@ -134,7 +137,8 @@ inline Parsed parse_solve(std::istringstream& tok, SolvePaths& q)
         if (!split_token(t, k, v)) continue;
         if (k == "mid") {
             if (!v.empty() && !parse_mid(v, q.mid)) return Parsed::Bad;
-        } else if (std::string* dst = field_of({{"bwd", &q.bwd}, {"occ", &q.occ}, {"occ_bwd", &q.occ_bwd}}, k))
+        } else if (std::string* dst = field_of({{"bwd", &q.bwd}, {"occ", &q.occ}, {"occ_bwd", &q.occ_bwd},
+                                                {"diag", &q.diag}, {"fold", &q.fold}}, k))
             *dst = v;
     }
     return Parsed::Good;

@@ -2,7 +2,8 @@
 //   ./warp_image image mask flow warped_image warped_mask
 // The rasterisation runs on the GPU (ArapFlow_Warp); output is bit exact against the reference's executable.
 // Optional tokens after the five arguments (addition, DESIGN.md "Backward flow and occlusion"): bwd=PATH.flo,
-// occ=PATH.png, occ_bwd=PATH.png; then ArapFlow_WarpEx also writes those maps.
+// occ=PATH.png, occ_bwd=PATH.png; then ArapFlow_WarpEx also writes those maps.  diag=PATH.txt, fold=PATH.png (DESIGN.md
+// "Fold diagnostics"): the mesh statistics and the fold map of the flow, through ArapFlow_WarpDiag.
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -28,12 +29,13 @@ static void usage()
 
 int main(int argc, const char* argv[])
 {
-    std::string bwd_path, occ_path, occ_bwd_path;
+    std::string bwd_path, occ_path, occ_bwd_path, diag_path, fold_path;
     bool extra_ok = argc >= 6;
     for (int a = 6; a < argc && extra_ok; ++a) {
         std::string k, v;
         std::string* dst = split_token(argv[a], k, v)
-                               ? field_of({{"bwd", &bwd_path}, {"occ", &occ_path}, {"occ_bwd", &occ_bwd_path}}, k) : nullptr;
+                               ? field_of({{"bwd", &bwd_path}, {"occ", &occ_path}, {"occ_bwd", &occ_bwd_path},
+                                           {"diag", &diag_path}, {"fold", &fold_path}}, k) : nullptr;
         if (dst) *dst = v;
         else extra_ok = false;
     }
@@ -62,7 +64,8 @@ int main(int argc, const char* argv[])
     OutputTable out(dev, w, h);
     const size_t o_rgb = out.add(FileKind::rgb, argv[4]), o_msk = out.add(FileKind::mask1, argv[5]);
     const size_t o_bwd = out.add(FileKind::flo, bwd_path), o_obwd = out.add(FileKind::gray8, occ_bwd_path);
-    const size_t o_occ = out.add(FileKind::gray8, occ_path);
+    const size_t o_occ = out.add(FileKind::gray8, occ_path), o_fold = out.add(FileKind::gray8, fold_path);
+    const size_t d_stats = diag_path.empty() ? DeviceArena::kNone : dev.take(sizeof(ArapFlow_MeshStats));
     const size_t d_scr = dev.take(ex ? ArapFlow_WarpExScratchBytes((unsigned)w, (unsigned)h)
                                      : ArapFlow_WarpScratchBytes((unsigned)w, (unsigned)h));
     HCHECK(dev.alloc());
@@ -74,9 +77,18 @@ int main(int argc, const char* argv[])
         printf("ArapFlow_WarpEx failed\n");
         return 1;
     }
+    if ((!diag_path.empty() || !fold_path.empty()) &&
+        ArapFlow_WarpDiag(state, (unsigned)w, (unsigned)h, dev.at(d_msk), dev.at(d_flow), out.dev(o_fold),
+                          (ArapFlow_MeshStats*)dev.at(d_stats)) != 0) { printf("ArapFlow_WarpDiag failed\n"); return 1; }
     HCHECK(hipDeviceSynchronize());
     HCHECK(out.download());
     if (!out.write()) return 1;
+    if (!diag_path.empty()) {
+        ArapFlow_MeshStats stats;
+        HCHECK(hipMemcpy(&stats, dev.at(d_stats), sizeof(stats), hipMemcpyDeviceToHost));
+        const std::string text = format_diag(stats);
+        if (!save_text(diag_path, text.data(), text.size())) return 1;
+    }
     printf("Saved\n");
     return 0;
 }

@@ -10,6 +10,7 @@
   warp_step        the warp of one deformation state and the flow from it to a second one (ArapFlow_WarpStep)
   background       full-frame RGB, flow and occlusion behind a warped pair's objects (ArapFlow_Background)
   background_seq   the same over frame 1, a pair's in-between frames and frame 2 in one call (ArapFlow_BackgroundSeq)
+  warp_diag        fold diagnostics of a flow: mesh statistics and the fold map (ArapFlow_WarpDiag)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -283,6 +284,12 @@ class CombinedSolver:
         self.solver.close()
 
 
+def _stats_dict(s):
+    """an ArapFlow_MeshStats as a dict in the struct's order, without `reserved`; the floats as numpy float32"""
+    return {k: (np.float32(getattr(s, k)) if k.startswith(("det", "disp")) else int(getattr(s, k)))
+            for k in capi.MESH_STATS_KEYS}
+
+
 class FrameSolver:
     """Batched, device-resident CombinedSolver (ArapFlow_Solver)."""
 
@@ -293,6 +300,15 @@ class FrameSolver:
         if not self.h:
             raise RuntimeError("ArapFlow_SolverCreate failed")
         self.outputs = 0
+        self.diag = False
+
+    def set_diag(self, on):
+        """fold diagnostics of every later warp (ArapFlow_SolverSetDiag, DESIGN.md "Fold diagnostics"): results() /
+        host_results() then carry mesh_stats (a dict over capi.MESH_STATS_KEYS) and fold u8[H,W] -- when the last warp
+        (or download) computed them."""
+        if self.lib.ArapFlow_SolverSetDiag(self.h, int(bool(on))) != 0:
+            raise RuntimeError("ArapFlow_SolverSetDiag failed")
+        self.diag = bool(on)
 
     def set_outputs(self, backward=False, occlusion=False):
         """optional outputs of every later warp (ArapFlow_SolverSetOutputs): backward flow + backward occlusion,
@@ -397,6 +413,10 @@ class FrameSolver:
                 out.update(backward_flow=view(pb, C.c_float, (H, W, 2)), occlusion_bwd=view(pob, C.c_uint8, (H, W)))
             if po.value:
                 out.update(occlusion=view(po, C.c_uint8, (H, W)))
+        if self.diag:
+            ps, pf = C.POINTER(capi.MeshStats)(), C.c_void_p()
+            if self.lib.ArapFlow_SolverHostDiag(self.h, slot, C.byref(ps), C.byref(pf)) == 0:
+                out.update(mesh_stats=_stats_dict(ps.contents), fold=view(pf, C.c_uint8, (H, W)))
         return out
 
     def warp(self, nframes=None):
@@ -419,6 +439,10 @@ class FrameSolver:
         if rc != 0:
             raise ValueError("ArapFlow_SolverGetResults: bad arguments")
         out = dict(flow=flow, warped_rgb=wrgb, warped_mask=wmsk, offset=off, angle=ang, cost=cost.value)
+        if self.diag:
+            st, fold = capi.MeshStats(), np.empty((H, W), np.uint8)
+            if self.lib.ArapFlow_SolverGetDiag(self.h, slot, C.byref(st), p(fold)) == 0:
+                out.update(mesh_stats=_stats_dict(st), fold=fold)
         if self.outputs:
             bwd = np.empty((H, W, 2), np.float32) if self.outputs & capi.OUT_BACKWARD else None
             obwd = np.empty((H, W), np.uint8) if self.outputs & capi.OUT_BACKWARD else None
@@ -554,6 +578,19 @@ def warp_layers_step(state, rgb, masks, flows_a, flows_b, step=True, occ=True):
                     ("step", (H, W, 2) if step else None, torch.float32), ("occlusion_step", (H, W) if occ else None, torch.uint8)],
                    "WarpLayersStepScratchBytes")
     return {"warped_rgb": None, **r}
+
+
+def warp_diag(state, mask_red, flow, fold=True):
+    """fold diagnostics of a flow (ArapFlow_WarpDiag, DESIGN.md "Fold diagnostics"): mask_red u8[H,W], flow f32[H,W,2]
+    (numpy) -> dict(stats: a dict over capi.MESH_STATS_KEYS, fold: u8[H,W], 255 = no valid correspondence; None when
+    not asked)."""
+    mask_red = np.ascontiguousarray(mask_red, np.uint8)
+    H, W = mask_red.shape
+    if tuple(np.shape(flow)) != (H, W, 2):
+        raise ValueError("warp_diag: flow [H,W,2] expected")
+    r = _warp_call(state, "WarpDiag", (W, H), [(mask_red, np.uint8), (flow, np.float32)],
+                   [("fold", (H, W) if fold else None, torch.uint8), ("stats", (C.sizeof(capi.MeshStats),), torch.uint8)])
+    return dict(stats=_stats_dict(capi.MeshStats.from_buffer_copy(r["stats"].tobytes())), fold=r.get("fold"))
 
 
 BG_OUTPUTS = ("out_rgb1", "out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")

@@ -4,7 +4,8 @@ What the reference's Python 2 scripts and C++ drivers do AROUND the hot path (SU
 behaviour (the contract each function states in its docstring), with the size / selection arithmetic as pure
 functions that tests/golden/host/ pins with hand-computed cases:
   SolveLine, parse_line, format_line, done_token, read_list_items    the list line: a solve (6 paths, optional output
-                            tokens bwd= occ= occ_bwd= mid=) or the `layers` line, the layered warp of one frame (addition)
+                            tokens bwd= occ= occ_bwd= mid= diag= fold=) or the `layers` line, the layered warp of one frame (addition)
+  format_diag, parse_diag, merge_diag, pair_rejected    the diag= / fold= tokens: fold diagnostics (addition)
   parse_mid, mid_token, mid_files, mid_steps    the mid= token: in-between frames from the constraint ramp (addition)
   mid_layer_files, owner_flow, run_layers_mid   a layers line's mid= token: layered in-between frames (addition)
   deform_list, run_layers   ARAP/deformation/src/main.cpp:162-241  (arap_deform over a list)
@@ -40,7 +41,7 @@ _ANTIALIAS = getattr(Image, "LANCZOS", None) or Image.ANTIALIAS   # Image.ANTIAL
 # A list line is the unit of work between para_gen.py, arap_deform.py and `arap_deform --serve` (C++ twin: parse_item in
 # host/arap_deform.cpp).  It is a solve line, SolveLine, a `layers` line, the dict of parse_layers, or a `bg` line, BgLine;
 # parse_line reads any of them from text, format_line writes it back, done_token is the path a worker reports it done by.
-EXTRA_KEYS = ("bwd", "occ", "occ_bwd", "mid")
+EXTRA_KEYS = ("bwd", "occ", "occ_bwd", "mid", "diag", "fold")
 MAX_SNAPSHOTS = 8            # ARAPFLOW_MAX_SNAPSHOTS of include/arap_opt.h
 LAYERS_WORD = "layers"
 LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2", "mid")
@@ -52,6 +53,7 @@ BG_OUT_KEYS = ("occ_out", "bwd_out", "occ_bwd_out")                  # the full 
 class SolveLine(NamedTuple):
     """main.cpp:183-191: one solve per line, six whitespace-separated paths
         rgb mask constraints out_flow out_rgb out_mask [bwd=PATH.flo] [occ=PATH.png] [occ_bwd=PATH.png] [mid=I1,I2,..:PREFIX]
+                                                       [diag=PATH.txt] [fold=PATH.png]
     `extra`: the optional outputs the line asks for, {key: path} (parse_extra); the value of `mid` is the token's text
     after the `=` (parse_mid)"""
     rgb: str
@@ -115,8 +117,8 @@ def mid_steps(K, num_iter):
 
 
 def parse_extra(tokens):
-    """optional tokens after a line's paths: bwd=PATH.flo, occ=PATH.png, occ_bwd=PATH.png, mid=I1,I2,..:PREFIX ->
-    {key: value}.  Any other token is ignored (a line's tokens after the sixth always were); a malformed mid= token is
+    """optional tokens after a line's paths: bwd=PATH.flo, occ=PATH.png, occ_bwd=PATH.png, mid=I1,I2,..:PREFIX,
+    diag=PATH.txt, fold=PATH.png (DESIGN.md "Fold diagnostics") -> {key: value}.  Any other token is ignored (a line's tokens after the sixth always were); a malformed mid= token is
     an error (parse_mid)."""
     out = {}
     for t in tokens:
@@ -465,6 +467,71 @@ def load_rgb(path):
     return np.array(Image.open(path).convert("RGB"))
 
 
+# the lines of a diag file: ArapFlow_MeshStats in the struct's order, without `reserved` (DESIGN.md "Fold diagnostics")
+DIAG_COUNTS = ("vertices", "outside", "triangles", "folded", "nonfinite")
+DIAG_FLOATS = ("det_min", "det_max", "disp2_max")
+
+
+def format_diag(stats):
+    """the text of a diag file: eight lines `name value`, counts in decimal, floats as printf's %.9g of the float32
+    (inf, -inf as printf writes them); the C++ worker writes the same bytes"""
+    return "".join(["%s %d\n" % (k, int(stats[k])) for k in DIAG_COUNTS] +
+                   ["%s %.9g\n" % (k, float(np.float32(stats[k]))) for k in DIAG_FLOATS])
+
+
+def parse_diag(text):
+    """the inverse of format_diag: {name: int or numpy float32}; anything but its eight lines is an error"""
+    rows = [ln.split() for ln in text.splitlines()]
+    if [r[0] if len(r) == 2 else None for r in rows] != list(DIAG_COUNTS + DIAG_FLOATS):
+        raise ValueError("not a diag file: %r" % text)
+    out = {k: int(v) for k, v in rows[:len(DIAG_COUNTS)]}
+    out.update({k: np.float32(float(v)) for k, v in rows[len(DIAG_COUNTS):]})
+    return out
+
+
+def _bit_order(v):
+    """a float32's place in the total order of the IEEE bit patterns (-0 < +0): the order of the statistics' extrema"""
+    u = int(np.float32(v).view(np.uint32))
+    return (u ^ 0xffffffff) if u >> 31 else (u | 0x80000000)
+
+
+def merge_diag(stats, folds=None):
+    """--multseg: the diagnostics of a frame's segments become the frame's: the counts are summed, the extrema combined
+    in the order of the bit patterns (a segment without a value holds the identity: +inf, -inf, 0), and the fold maps
+    OR-ed -- the segments' masks are disjoint.  Returns (stats, fold or None)."""
+    stats = list(stats)
+    out = {k: sum(int(q[k]) for q in stats) for k in DIAG_COUNTS}
+    out["det_min"] = min([np.float32(q["det_min"]) for q in stats] + [np.float32(np.inf)], key=_bit_order)
+    out["det_max"] = max([np.float32(q["det_max"]) for q in stats] + [np.float32(-np.inf)], key=_bit_order)
+    out["disp2_max"] = max([np.float32(q["disp2_max"]) for q in stats] + [np.float32(0)], key=_bit_order)
+    fold = None
+    if folds is not None:
+        fold = np.where(np.any([np.asarray(f) != 0 for f in folds], axis=0), 255, 0).astype(np.uint8)
+    return out, fold
+
+
+def pair_rejected(stats, max_fold):
+    """para_gen --max_fold FRAC: a pair is rejected iff a triangle went non-finite or more than FRAC of them folded"""
+    return stats["nonfinite"] > 0 or stats["folded"] > max_fold * stats["triangles"]
+
+
+def flatten_diag(frame_line, seg_lines, remove=True):
+    """merge_diag at file level: reads every segment's diag and fold files, writes the frame's, deletes the segments'"""
+    ex = [ln.extra for ln in seg_lines]
+    stats = [parse_diag(open(e["diag"]).read()) for e in ex]
+    folds = [np.array(Image.open(e["fold"]).convert("L")) for e in ex] if "fold" in frame_line.extra else None
+    merged, fold = merge_diag(stats, folds)
+    with open(frame_line.extra["diag"], "w") as f:
+        f.write(format_diag(merged))
+    if fold is not None:
+        save_occ(fold, frame_line.extra["fold"])
+    if remove:
+        for e in ex:
+            for k in ("diag", "fold"):
+                if k in e and osp.exists(e[k]):
+                    os.remove(e[k])
+
+
 def load_mask_red(path):
     """red channel of the mask PNG (CombinedSolver.h:213,234): 0 = deformable object"""
     return np.array(Image.open(path).convert("RGB"))[..., 0]
@@ -496,6 +563,11 @@ def _save_result(ln, r):
         save_occ(r["occlusion_bwd"], extra["occ_bwd"])
     if "occ" in extra:
         save_occ(r["occlusion"], extra["occ"])
+    if "diag" in extra:
+        with open(extra["diag"], "w") as f:
+            f.write(format_diag(r["mesh_stats"]))
+    if "fold" in extra:
+        save_occ(r["fold"], extra["fold"])
     if "mid" in extra:
         steps, prefix = parse_mid(extra["mid"])
         for i, m in zip(steps, r["mid"]):
@@ -526,6 +598,7 @@ class _Lane:
     def __init__(self):
         self.solver, self.batch = None, []
         self.snaps = ()                # the snapshot steps in effect in `solver` (batch_snapshots)
+        self.diag = False              # fold diagnostics in effect in `solver`
 
 
 def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, max_batch=FILL_MAX, verbose=True):
@@ -586,7 +659,7 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
                           "same list.\nStarting to re-build plan...")      # CombinedSolver.h:151-153
                 for lane in lanes:
                     lane.solver = opt.FrameSolver(state, W, H, batch=max_batch)
-                    lane.snaps = ()
+                    lane.snaps, lane.diag = (), False
                 size = (W, H)
             lane, other = lanes[cur], lanes[cur ^ 1]
             solver, batch = lane.solver, lane.batch                     # (empty: drained a round ago)
@@ -613,6 +686,10 @@ def deform_list(state, lines, num_iter=19, non_linear_iter=8, linear_iter=400, m
             if steps != lane.snaps:
                 solver.set_snapshots(steps)
                 lane.snaps = steps
+            diag = bool(want & {"diag", "fold"})                # likewise: set only to turn it on, or off again
+            if diag != lane.diag:
+                solver.set_diag(diag)
+                lane.diag = diag
             solver.solve_async(len(batch), num_iter, non_linear_iter, linear_iter, warp=True, download=True)
             drain(other)                                               # the previous batch, while this one is being solved
             cur ^= 1
@@ -632,7 +709,14 @@ def warp_files(state, rgb_path, mask_path, flo_path, out_rgb_path, out_mask_path
     rgb, mask, fl = load_rgb(rgb_path), load_mask_red(mask_path), flo.flow_read(flo_path)
     if fl.shape[:2] != mask.shape or rgb.shape[:2] != mask.shape:
         raise ValueError("image, mask and flow sizes differ")
-    if extra:
+    if extra and {"diag", "fold"} & set(extra):
+        d = opt.warp_diag(state, mask, fl, fold="fold" in extra)
+        if "diag" in extra:
+            with open(extra["diag"], "w") as f:
+                f.write(format_diag(d["stats"]))
+        if "fold" in extra:
+            save_occ(d["fold"], extra["fold"])
+    if extra and set(extra) - {"diag", "fold"}:
         r = opt.warp_image_ex(state, rgb, mask, fl, backward=bool({"bwd", "occ_bwd"} & set(extra)),
                               occlusion="occ" in extra)
         Image.fromarray(r["warped_rgb"]).save(out_rgb_path)
@@ -839,7 +923,8 @@ def scale_rotate(im_path, mk_path, size=None):
     return changed, im, mk
 
 
-EXTRA_OF = dict(bwd_gen="bwd", occbwd_gen="occ_bwd", occ_gen="occ")   # para_gen's path key -> list-line token
+EXTRA_OF = dict(bwd_gen="bwd", occbwd_gen="occ_bwd", occ_gen="occ",   # para_gen's path key -> list-line token
+                diag_gen="diag", fold_gen="fold")
 
 
 def make_arap_path(p):

@@ -413,6 +413,44 @@ int ArapFlow_BackgroundSeq(Opt_State* state, unsigned W, unsigned H, const void*
                            const void* const* rgbs, const void* const* flows, const void* const* occs,
                            void* const* out_rgbs, void* const* out_flows, void* const* out_occs);
 
+/* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
+ * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
+ * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised
+ * triangles t = 2u (p00, p01, p10), t = 2u + 1 (p10, p01, p11) of every quad whose four corners are object,
+ *   det(t) = (e1.x * e2.y) - (e1.y * e2.x),  e1 = P(c1) - P(c0),  e2 = P(c2) - P(c0)      (float32, uncontracted)
+ * is +1 on the pixel grid.  A triangle is non-finite iff det is not finite, folded iff det is finite and <= 0.
+ *   vertices, outside   object vertices; those of them whose P is not inside [0, W-1] x [0, H-1] (NaN counts)
+ *   triangles           rasterised triangles;  folded, nonfinite: as above;  reserved: 0
+ *   det_min, det_max    over the finite dets, in the total order of the IEEE bit patterns (-0 < +0); +inf / -inf when
+ *                       there is none
+ *   disp2_max           max of (dx * dx) + (dy * dy), dx = P.x - (float)x, dy = P.y - (float)y, over the object
+ *                       vertices whose P has two finite coordinates; 0 when there is none
+ * The fold map uint8[H][W] (frame-1 domain) is 255 where the vertex is object and a corner of a folded or non-finite
+ * rasterised triangle, else 0.  Counts, flags and order-independent extrema only: two runs give identical bytes. */
+typedef struct ArapFlow_MeshStats {
+    uint32_t vertices, outside, triangles, folded, nonfinite, reserved;
+    float det_min, det_max, disp2_max;
+} ArapFlow_MeshStats;
+
+/* The diagnostics of a flow on DEVICE buffers: mask_red uint8[H][W], flow float[H][W][2] -> out_fold uint8[H][W],
+ * out_stats one ArapFlow_MeshStats (a DEVICE pointer too), each NULL when not wanted.  Needs no scratch beyond a few
+ * hundred bytes the state allocates at the first call.  Asynchronous on the state's stream.  Returns 0; -1 on bad
+ * arguments: a null state, mask_red or flow, both outputs NULL, a zero size or W * H >= 2^31; else a HIP error code. */
+int ArapFlow_WarpDiag(Opt_State* state, unsigned W, unsigned H, const void* mask_red, const void* flow, void* out_fold,
+                      ArapFlow_MeshStats* out_stats);
+
+/* The same for the frame solver: ArapFlow_SolverSetDiag(s, on) makes every later warp (ArapFlow_SolverWarp,
+ * SolveAsync(.., warp = 1, ..)) compute the statistics and the fold map of its slots' solved fields; the redo after a
+ * resident time-out re-runs them with the warp.  Device memory (one byte per vertex and slot, plus the statistics) is
+ * allocated by the first call that turns them on.  Returns 0, -1 on a null solver.
+ * ArapFlow_SolverGetDiag: synchronise and copy one slot's diagnostics of the last warp to HOST buffers (either may be
+ * NULL); -1 if that warp computed none.
+ * ArapFlow_SolverHostDiag: pointers into the solver's pinned buffers filled by a `download` solve (valid until the next
+ * solve of this solver); -1 if that solve downloaded none. */
+int ArapFlow_SolverSetDiag(ArapFlow_Solver* s, int on);
+int ArapFlow_SolverGetDiag(ArapFlow_Solver* s, unsigned slot, ArapFlow_MeshStats* stats, uint8_t* fold);
+int ArapFlow_SolverHostDiag(ArapFlow_Solver* s, unsigned slot, const ArapFlow_MeshStats** stats, const uint8_t** fold);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
                      [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
-                     [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]]
+                     [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]] [--diag] [--max_fold FRAC]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -38,6 +38,12 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     OUT/MidFull/<seq>/<frame> (mid_out=), and one sequence pass of the worker writes there every in-between frame over
     the moving background and every link's full-frame flow (with --mid_layers K --occ_layers: and occlusion).  OUT/Mid
     keeps the object-side files.
+  * --diag writes the fold diagnostics of every pair (DESIGN.md "Fold diagnostics"): OUT/Diag/<seq>/<frame>.txt, the mesh
+    statistics of the solve, and OUT/Fold/<seq>/<frame>.png, 255 where the frame-1 flow value is no valid correspondence;
+    with --multseg the segments' files are merged.  --max_fold FRAC (implies --diag) keeps a pair out of all_files.list
+    and all_files_ext.list when a triangle went non-finite or more than FRAC of them folded, and names it in
+    OUT/rejected.list instead (`rgb1 rgb2 flow folded triangles nonfinite`); its files stay.  The lists are decided from
+    the Diag files on disk (write_lists), so a --resume run writes the same ones.
 """
 import argparse
 import json
@@ -66,6 +72,7 @@ orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
+diag_dir, fold_dir = "Diag", "Fold"     # --diag: fold diagnostics (addition)
 mid_full_dir = "MidFull"           # --mid_bg: the in-between frames and links with the moving background (addition)
 mid_dir = "Mid"                    # --mid K: in-between frames from the constraint ramp (addition)
 NUM_ITER = 19                      # the ramp length of the ARAP drivers (main.cpp:215-221): what --mid K spreads over
@@ -299,7 +306,9 @@ def finish_frame(rec):
                         if osp.exists(q):
                             os.remove(q)
     if rec.segs is not None:
-        if rec.line.extra:                                  # (before flatten removes the segments' warped masks)
+        if "diag" in rec.line.extra:                        # (before flatten_backward removes the segments' extra files)
+            pipeline.flatten_diag(rec.line, rec.segs, remove=rec.remove)
+        if {"bwd", "occ_bwd"} & set(rec.line.extra):        # (before flatten removes the segments' warped masks)
             pipeline.flatten_backward(rec.line, rec.segs, remove=rec.remove)
         pipeline.flatten([(rec.line, rec.segs)], remove=rec.remove)
     if rec.bg is not None:
@@ -482,7 +491,7 @@ def scan(flags, input_root, output_root):
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
-                                                           obw=occ_bwd_dir, occ=occ_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
+                                                           obw=occ_bwd_dir, occ=occ_dir, dia=diag_dir, fol=fold_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
                                                            ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
     all_paths = []
@@ -508,6 +517,8 @@ def scan(flags, input_root, output_root):
                     e.update(bwd_gen=osp.join(roots["bwd"], seq, f + ".flo"), occbwd_gen=osp.join(roots["obw"], seq, f + ".png"))
                 if getattr(flags, "occ", False):
                     e.update(occ_gen=osp.join(roots["occ"], seq, f + ".png"))
+                if getattr(flags, "diag", False):
+                    e.update(diag_gen=osp.join(roots["dia"], seq, f + ".txt"), fold_gen=osp.join(roots["fol"], seq, f + ".png"))
                 if getattr(flags, "occ_layers", False):
                     e[LAYERS_OCC] = osp.join(roots["occ"], seq, f + ".png")
                 if getattr(flags, "mid", 0):
@@ -566,6 +577,39 @@ def stop_matchers(flags, procs):
             pr.kill()
 
 
+def write_lists(flags, output_root, all_paths):
+    """para_gen.py:588-603 and the additions' own list, from what is on disk: OUT/all_files.list (`rgb1 rgb2 flow` of every
+    pair whose three files exist) and, when the run asks for any optional output, OUT/all_files_ext.list (the same plus
+    every optional file, for the pairs that have them all).  With --max_fold a pair whose Diag file says
+    pipeline.pair_rejected goes to neither but to OUT/rejected.list as `rgb1 rgb2 flow folded triangles nonfinite`.
+    `all_paths`: scan's path tables.  Returns (the lines of all_files.list, those of rejected.list)."""
+    max_fold = getattr(flags, "max_fold", None)
+    out_paths, ext, rejected = [], [], []
+    for p in all_paths:
+        ln = pipeline.make_arap_path(p)
+        trio = [ln.rgb, ln.out_rgb, ln.flow]
+        full = trio + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p) + mid_bg_paths(p)
+        if not all(osp.exists(q) for q in trio):
+            continue
+        if max_fold is not None and osp.exists(p.get("diag_gen", "")):
+            st = pipeline.parse_diag(open(p["diag_gen"]).read())
+            if pipeline.pair_rejected(st, max_fold):
+                rejected.append(" ".join(trio + ["%d" % st[k] for k in ("folded", "triangles", "nonfinite")]))
+                continue
+        out_paths.append(" ".join(trio))
+        if all(osp.exists(q) for q in full):
+            ext.append(" ".join(full))
+    open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
+    # all_files.list stays as it is; the extra outputs get their own list
+    if (getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False) or
+            getattr(flags, "mid", 0) or getattr(flags, "mid_layers", 0) or getattr(flags, "bg_motion", None) is not None or
+            getattr(flags, "diag", False)):
+        open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
+    if max_fold is not None:
+        open(osp.join(output_root, "rejected.list"), "w").write("\n".join(rejected))
+    return out_paths, rejected
+
+
 def main(flags):
     t_start = time.time()
     input_root, output_root = flags.input.rstrip(osp.sep), flags.output.rstrip(osp.sep)
@@ -578,12 +622,6 @@ def main(flags):
     all_paths = scan(flags, input_root, output_root)
     print("Scanning data to be processed\t\t%d files [Done]" % len(all_paths))
     os.makedirs(output_root, exist_ok=True)
-    lmdb_paths, ext_paths = [], []
-    for p in all_paths:
-        ln = pipeline.make_arap_path(p)
-        lmdb_paths.append([ln.rgb, ln.out_rgb, ln.flow])
-        ext_paths.append(lmdb_paths[-1] + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p) +
-                         mid_bg_paths(p))
 
     # backgrounds: drawn without replacement until the list is used up, then refilled (para_gen.py:484-499)
     tmp_paths, picks = [], []
@@ -680,13 +718,10 @@ def main(flags):
         for p in workers.procs:
             if p.poll() is None:
                 p.kill()
-    out_paths = [" ".join(ln) for ln in lmdb_paths if all(osp.exists(q) for q in ln)]    # :588-603
-    open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
-    # all_files.list stays as it is; the extra outputs get their own list
-    if (getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False) or
-            getattr(flags, "mid", 0) or getattr(flags, "mid_layers", 0) or getattr(flags, "bg_motion", None) is not None):
-        ext = [" ".join(ln) for ln in ext_paths if all(osp.exists(q) for q in ln)]
-        open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
+    listed = all_paths
+    if flags.resume and getattr(flags, "diag", False):     # the verdicts are on disk: list the pairs finished earlier too
+        listed = scan(argparse.Namespace(**dict(vars(flags), resume=False)), input_root, output_root)
+    out_paths, rejected = write_lists(flags, output_root, listed)
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
                  layers_done=counts["layers_done"], bg_done=counts["bg_done"],
@@ -694,6 +729,8 @@ def main(flags):
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
                  mean_batch=(float(np.mean(workers.batches)) if workers.batches else 0.0))
+    if getattr(flags, "max_fold", None) is not None:
+        stats["rejected"] = len(rejected)
     open(osp.join(output_root, "arap_stats.json"), "w").write(json.dumps(stats))
     print("Finished: %d frames (%d solves) in %.2f s, mean batch %.1f" % (n_frames, n_solves, dt, stats["mean_batch"]))
     return out_paths
@@ -778,7 +815,22 @@ def parse(argv=None):
                              "with --mid_layers K --occ_layers also the links' full-frame occlusions _s00_occ.png, "
                              "_sII_occ.png.  A plain --mid K run has no object-side link occlusion, so it writes none and "
                              "cannot be combined with --occ here (DESIGN.md \"Moving background over in-between frames\")")
+    parser.add_argument("--diag", action="store_true", default=False,
+                        help="also write the fold diagnostics of every pair: the mesh statistics OUT/Diag/<seq>/<frame>.txt "
+                             "and the fold map OUT/Fold/<seq>/<frame>.png, 255 where the flow value is no valid "
+                             "correspondence (DESIGN.md \"Fold diagnostics\")")
+    parser.add_argument("--max_fold", type=float, default=None, metavar="FRAC",
+                        help="implies --diag: leave a pair out of all_files.list and all_files_ext.list, and name it in "
+                             "OUT/rejected.list, when a triangle of its mesh went non-finite or more than FRAC (0 .. 1) of "
+                             "them folded; its files stay on disk")
     flags = parser.parse_args(argv)
+    if flags.max_fold is not None:
+        if not 0 <= flags.max_fold <= 1:                   # (false on NaN)
+            parser.error("--max_fold FRAC must lie in 0 .. 1")
+        flags.diag = True
+    if flags.diag and not own_arap_bin(flags.arap_bin):
+        parser.error("--diag / --max_fold need this repository's arap_deform (C++ or arap_deform.py): a foreign "
+                     "--arap_bin does not write the diagnostics")
     if flags.mid_bg:
         if flags.bg_motion is None:
             parser.error("--mid_bg needs --bg_motion: it moves that camera through the in-between frames")
