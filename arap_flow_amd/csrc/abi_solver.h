@@ -20,6 +20,30 @@ struct MidDev {                // per snapshot and slot (ArapFlow_SolverSetSnaps
 // ArapFlow_SolverWait returns 0 at once when there is none.
 extern "C" int ArapFlow_SolverWait(ArapFlow_Solver* s);
 
+// ---- the result groups ---------------------------------------------------------------------------------------------------
+// What a solver hands out comes in four groups, each described once below: its planes in the order they have in the
+// pinned staging of a `download` solve.  A plane's pinned offset is the sum of the planes before it, a slot's stride
+// that sum rounded up to 256; the downloads, the Get* copies and the Host* pointers all read this table.
+enum { G_BASE, G_EXTRA, G_MID, G_DIAG, G_COUNT, MAX_PLANES = 5 };
+// what selects a plane: a positive value is an ARAPFLOW_OUT_* bit of the group's state
+enum { SEL_ALWAYS = 0, SEL_RGB = -1 /* the slot has RGB */, SEL_DEVICE = -2 /* Get* only: never staged */ };
+struct Plane {
+    size_t per_vertex, fixed;       // bytes per vertex, or a fixed size (staged in the next multiple of 256)
+    int sel;
+    const void* (*dev)(const ArapFlow_Solver* s, unsigned slot, unsigned k);   // its device home
+};
+// A group's state is one number, kept three times (ResultGroup): the ARAPFLOW_OUT_* bits (extra), the number of
+// snapshots (mid), 1 or 0 (base: always 1; diag).  group_items: how many sets of planes per slot that makes.
+static unsigned group_items(int g, unsigned state) { return g == G_MID ? state : state != 0; }
+struct ResultGroup {
+    unsigned want = 0;              // for the next warps (mid: the snapshots of the next solves)
+    unsigned at_warp = 0;           // ... in effect at the last warp (written by solver_enqueue_warp alone)
+    unsigned at_dl = 0;             // ... carried by the last solve call's download (written by solver_download alone)
+                                    // (solver_mid_alloc zeroes both when it remakes the snapshot buffers)
+    char* pin = nullptr;            // pinned staging: [items][batch] slots of `stride` bytes (solver_pin)
+    size_t stride = 0, off[MAX_PLANES] = {};
+};
+
 struct ArapFlow_Solver {
     Opt_State* st = nullptr;
     int W = 0, H = 0, N = 0, batch = 0;
@@ -41,89 +65,125 @@ struct ArapFlow_Solver {
     hipStream_t copy = nullptr;
     hipEvent_t ev_up = nullptr, ev_done = nullptr, ev_dl = nullptr;
     char* pin_in = nullptr;          // [batch] x {T float2[N], mask u8[N], rgb u8[3N]}
-    char* pin_out = nullptr;         // [batch] x {flow float2[N], rgb u8[3N], mask u8[N]}   (allocated on first download)
-    size_t pin_in_slot = 0, pin_out_slot = 0;
+    size_t pin_in_slot = 0;
     bool uploads_pending = false;    // SetFrame since the last solve: the solve waits for ev_up
     bool inflight = false;           // a solve has been enqueued and not waited for
     bool retried = false;            // the last wait redid the schedule on the two-kernel path
     unsigned launches_at_enqueue = 0; // plan->res_launches when the pending solve call was enqueued
     unsigned a_n = 0, a_numIter = 0, a_nIt = 0, a_lIt = 0;
     int a_warp = 0, a_download = 0;
+    ResultGroup res[G_COUNT];        // (the staging of a group is allocated on first download, or earlier: solver_pin)
     // optional warp outputs (ArapFlow_SolverSetOutputs); every buffer is allocated when first asked for
-    int outputs = 0;                 // ARAPFLOW_OUT_* bits for the next warps
-    int warp_outputs = 0;            // ... in effect at the last warp
-    int dl_outputs = 0;              // ... downloaded by the last solve call
     void* ext = nullptr;             // device: [batch] x FrameExt buffers, then the [batch] cell arrays
     std::vector<FrameExt> hext;
     unsigned* ext_cells = nullptr;
     size_t ext_cell_slot = 0;
-    char* pin_ext = nullptr;         // [batch] x {bwd float2[N], occ_bwd u8[N], occ u8[N]}   (allocated on first download)
-    size_t pin_ext_slot = 0;
     // in-between frames (ArapFlow_SolverSetSnapshots, DESIGN.md "In-between frames"); nothing is allocated while off
-    unsigned snap_n = 0, snap_steps[ARAPFLOW_MAX_SNAPSHOTS] = {};   // the set for the next solves
+    unsigned snap_steps[ARAPFLOW_MAX_SNAPSHOTS] = {};   // the steps of the res[G_MID].want snapshots of the next solves
     unsigned a_snap_n = 0, a_snap_steps[ARAPFLOW_MAX_SNAPSHOTS] = {};   // ... of the solve call pending or last done
     unsigned taken_n = 0;            // states the last solve call copied (they stay valid until the next one)
-    unsigned warp_snap_n = 0;        // snapshots the last warp wrote outputs for
-    unsigned dl_snap_n = 0;          // ... the last solve call downloaded
     void* mid = nullptr;             // device: [mid_cap][batch] x MidDev buffers, then [mid_cap][batch] WarpJobs
-    unsigned mid_cap = 0;            // snapshots `mid`, `pin_mid_jobs` (and `pin_mid`, once there) are sized for
-    std::vector<MidDev> hmid;        // [k * batch + slot]
+    unsigned mid_cap = 0;            // snapshots `mid`, `pin_mid_jobs` (and the staging, once there) are sized for
+    std::vector<MidDev> hmid;        // [k * batch + slot]  (as the staging; the warp jobs of a solve: [k * nframes + slot])
     WarpJob* dmid_jobs = nullptr;
     WarpJob* pin_mid_jobs = nullptr;
-    char* pin_mid = nullptr;         // [mid_cap][batch] x {flow float2[N], step float2[N], rgb u8[3N], mask u8[N]}
-    size_t pin_mid_slot = 0;
     // fold diagnostics (ArapFlow_SolverSetDiag, DESIGN.md "Fold diagnostics"); nothing is allocated while off
-    int diag = 0;                    // on for the next warps
-    int warp_diag = 0;               // ... in effect at the last warp
-    int dl_diag = 0;                 // ... downloaded by the last solve call
     void* dgn = nullptr;             // device: [batch] fold maps u8[N], then [batch] DiagAcc, then [batch] ArapFlow_MeshStats
     size_t dgn_fold_slot = 0;
     DiagAcc* dgn_acc = nullptr;
     ArapFlow_MeshStats* dgn_stats = nullptr;
-    char* pin_diag = nullptr;        // [batch] x {ArapFlow_MeshStats (256 bytes), fold u8[N]}   (allocated on first download)
-    size_t pin_diag_slot = 0;
 };
 
-// pinned staging of the snapshot downloads (as solver_pin_out: when first needed)
-static void solver_pin_mid(ArapFlow_Solver* s)
+using SolverC = const ArapFlow_Solver*;
+static const MidDev& mid_of(SolverC s, unsigned slot, unsigned k) { return s->hmid[(size_t)k * s->batch + slot]; }
+static const Plane kPlanes[G_COUNT][MAX_PLANES] = {
+    {   // base: every solve; offset and angle stay on the device
+        {8, 0, SEL_ALWAYS, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hfr[b].flow; }},
+        {3, 0, SEL_RGB, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hfr[b].out_rgb; }},
+        {1, 0, SEL_ALWAYS, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hfr[b].out_mask; }},
+        {8, 0, SEL_DEVICE, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hfr[b].O; }},
+        {4, 0, SEL_DEVICE, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hfr[b].A; }},
+    },
+    {   // extra: bwd, occ_bwd, occ
+        {8, 0, ARAPFLOW_OUT_BACKWARD, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hext[b].bwd; }},
+        {1, 0, ARAPFLOW_OUT_BACKWARD, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hext[b].occ_bwd; }},
+        {1, 0, ARAPFLOW_OUT_OCCLUSION, [](SolverC s, unsigned b, unsigned) -> const void* { return s->hext[b].occ; }},
+    },
+    {   // mid, per snapshot k: flow, step, rgb, mask
+        {8, 0, SEL_ALWAYS, [](SolverC s, unsigned b, unsigned k) -> const void* { return mid_of(s, b, k).flow; }},
+        {8, 0, SEL_ALWAYS, [](SolverC s, unsigned b, unsigned k) -> const void* { return mid_of(s, b, k).step; }},
+        {3, 0, SEL_RGB, [](SolverC s, unsigned b, unsigned k) -> const void* { return mid_of(s, b, k).rgb; }},
+        {1, 0, SEL_ALWAYS, [](SolverC s, unsigned b, unsigned k) -> const void* { return mid_of(s, b, k).mask; }},
+    },
+    {   // diag: the statistics in a fixed head, fold
+        {0, sizeof(ArapFlow_MeshStats), SEL_ALWAYS, [](SolverC s, unsigned b, unsigned) -> const void* { return s->dgn_stats + b; }},
+        {1, 0, SEL_ALWAYS, [](SolverC s, unsigned b, unsigned) -> const void* { return (const uint8_t*)s->dgn + s->dgn_fold_slot * b; }},
+    },
+};
+static size_t plane_bytes(const Plane& p, size_t N) { return p.fixed ? p.fixed : p.per_vertex * N; }
+static bool plane_pinned(const Plane& p) { return (p.per_vertex || p.fixed) && p.sel != SEL_DEVICE; }   // (an unused entry is all zero)
+// does the staging of a slot carry the plane, the group being in `state`
+static bool plane_staged(SolverC s, const Plane& p, unsigned state, unsigned slot)
 {
-    if (s->pin_mid) return;
-    s->pin_mid_slot = align_up(20 * (size_t)s->N, 256);
-    HC(hipHostMalloc((void**)&s->pin_mid, s->pin_mid_slot * s->mid_cap * s->batch, hipHostMallocDefault));
+    if (!plane_pinned(p)) return false;
+    return p.sel == SEL_ALWAYS || (p.sel == SEL_RGB ? s->has_rgb[slot] != 0 : (state & (unsigned)p.sel) != 0);
 }
+static void solver_layout_results(ArapFlow_Solver* s)
+{
+    for (int g = 0; g < G_COUNT; ++g) {
+        size_t at = 0;
+        for (int i = 0; i < MAX_PLANES; ++i) {
+            const Plane& p = kPlanes[g][i];
+            if (!plane_pinned(p)) continue;
+            s->res[g].off[i] = at;
+            at += p.fixed ? align_up(p.fixed, 256) : p.per_vertex * (size_t)s->N;
+        }
+        s->res[g].stride = align_up(at, 256);
+    }
+    s->res[G_BASE].want = s->res[G_BASE].at_warp = 1;
+}
+
+// pinned staging of a group's downloads, allocated when first needed: in the asynchronous use (`own_stream`) when the
+// group is set up -- at creation, SetOutputs, SetDiag, the first solve with snapshots -- (hipHostMalloc waits for the
+// device, i.e. for another solver object's running solve), else at the first download
+static void solver_pin(ArapFlow_Solver* s, int g)
+{
+    ResultGroup& r = s->res[g];
+    if (r.pin) return;
+    HC(hipHostMalloc((void**)&r.pin, r.stride * s->batch * (g == G_MID ? s->mid_cap : 1), hipHostMallocDefault));
+}
+
 // device buffers of `n` snapshots: 8 B per vertex, snapshot and slot for the state, 20 B for the four outputs
 static void solver_mid_alloc(ArapFlow_Solver* s, unsigned n)
 {
     if (n <= s->mid_cap) return;
     HC(hipSetDevice(s->st->device));
+    ResultGroup& r = s->res[G_MID];
     if (s->mid) HC(hipFree(s->mid));
     if (s->pin_mid_jobs) HC(hipHostFree(s->pin_mid_jobs));
-    if (s->pin_mid) HC(hipHostFree(s->pin_mid));
-    s->pin_mid = nullptr;
+    if (r.pin) HC(hipHostFree(r.pin));
+    r.pin = nullptr;
     const size_t N = s->N, B = s->batch;
-    const size_t sz2 = align_up(8 * N, 256), sz3 = align_up(3 * N, 256), szb = align_up(N, 256);
-    const size_t per = 3 * sz2 + sz3 + szb, jobs = align_up(sizeof(WarpJob) * n * B, 256);
-    HC(hipMalloc(&s->mid, per * n * B + jobs));
-    HC(hipMemsetAsync(s->mid, 0, per * n * B + jobs, s->st->stream));
-    char* c = (char*)s->mid;
-    auto take = [&](size_t b) { char* r = c; c += b; return r; };
     s->hmid.resize(n * B);
-    for (MidDev& m : s->hmid) {
-        m.state = (float2*)take(sz2); m.flow = (float2*)take(sz2); m.step = (float2*)take(sz2);
-        m.rgb = (uint8_t*)take(sz3); m.mask = (uint8_t*)take(szb);
-    }
-    s->dmid_jobs = (WarpJob*)c;
+    s->mid = device_block(s->st, true, [&](Carver& part) {
+        for (MidDev& m : s->hmid) {
+            part(m.state, 8 * N); part(m.flow, 8 * N); part(m.step, 8 * N);
+            part(m.rgb, 3 * N); part(m.mask, N);
+        }
+        part(s->dmid_jobs, sizeof(WarpJob) * n * B);
+    });
     HC(hipHostMalloc((void**)&s->pin_mid_jobs, sizeof(WarpJob) * n * B, hipHostMallocDefault));
     HC(hipStreamSynchronize(s->st->stream));
     s->mid_cap = n;
-    s->taken_n = s->warp_snap_n = s->dl_snap_n = 0;
-    if (s->st->own_stream) solver_pin_mid(s);   // (as pin_out: downloads will be asked for)
+    s->taken_n = r.at_warp = r.at_dl = 0;
+    if (s->st->own_stream) solver_pin(s, G_MID);
 }
 
 static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
 {
     Opt_State* st = s->st;
     WarpJob* jobs = s->pin_jobs;             // (pinned: see plan_gn_step on pageable sources)
+    const bool diag = s->res[G_DIAG].want != 0;
     for (unsigned b = 0; b < nframes; ++b) {
         const FrameDev& f = s->hfr[b];
         WarpJob& j = jobs[b];
@@ -132,38 +192,36 @@ static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
         j.mask = f.mask; j.flow_out = f.flow; j.key = f.key;
         j.out_rgb = s->has_rgb[b] ? f.out_rgb : nullptr;
         j.out_mask = f.out_mask;
-        const int o = s->outputs;
+        const int o = (int)s->res[G_EXTRA].want;
         const FrameExt* e = o ? &s->hext[b] : nullptr;
         j.bwd = (o & ARAPFLOW_OUT_BACKWARD) ? e->bwd : nullptr;
         j.occ_bwd = (o & ARAPFLOW_OUT_BACKWARD) ? e->occ_bwd : nullptr;
         j.occ = (o & ARAPFLOW_OUT_OCCLUSION) ? e->occ : nullptr;
         j.cell = e ? e->cell : nullptr; j.rank = e ? e->rank : nullptr; j.bin = e ? e->bin : nullptr;
-        j.fold = s->diag ? (uint8_t*)s->dgn + s->dgn_fold_slot * b : nullptr;
-        j.acc = s->diag ? s->dgn_acc + b : nullptr;
-        j.stats = s->diag ? s->dgn_stats + b : nullptr;
+        j.fold = diag ? (uint8_t*)s->dgn + s->dgn_fold_slot * b : nullptr;
+        j.acc = diag ? s->dgn_acc + b : nullptr;
+        j.stats = diag ? s->dgn_stats + b : nullptr;
     }
     HC(hipMemcpyAsync(s->djobs, jobs, sizeof(WarpJob) * nframes, hipMemcpyHostToDevice, st->stream));
-    enqueue_warp(st->stream, s->djobs, nframes, s->W, s->H, s->outputs, s->ext_cells, s->ext_cell_slot * nframes);
-    s->warp_outputs = s->outputs;
-    if (s->diag) enqueue_warp_diag(st->stream, s->djobs, nframes, s->W, s->H, s->dgn_acc, sizeof(DiagAcc) * nframes);
-    s->warp_diag = s->diag;
+    enqueue_warp(st->stream, s->djobs, nframes, s->W, s->H, (int)s->res[G_EXTRA].want, s->ext_cells, s->ext_cell_slot * nframes);
+    if (diag) enqueue_warp_diag(st->stream, s->djobs, nframes, s->W, s->H, s->dgn_acc, sizeof(DiagAcc) * nframes);
     // the in-between frames of the last solve: one warp pass per snapshot over the slots, on the field S_{i_k}, with the
     // step towards the next state; the slot's key image serves every pass (k_warp_resolve left it cleared)
     const unsigned n = s->taken_n;
-    s->warp_snap_n = n;
+    for (int g = 0; g < G_COUNT; ++g) s->res[g].at_warp = g == G_MID ? n : s->res[g].want;
     if (n == 0) return;
     WarpJob* mj = s->pin_mid_jobs;
     for (unsigned k = 0; k < n; ++k)
         for (unsigned b = 0; b < nframes; ++b) {
             const FrameDev& f = s->hfr[b];
-            const MidDev& m = s->hmid[(size_t)k * s->batch + b];
+            const MidDev& m = mid_of(s, b, k);
             WarpJob j{};
             j.field = m.state;
             j.rgb = s->has_rgb[b] ? f.rgb : nullptr;
             j.mask = f.mask; j.flow_out = m.flow; j.key = f.key;
             j.out_rgb = s->has_rgb[b] ? m.rgb : nullptr;
             j.out_mask = m.mask;
-            j.field_b = k + 1 < n ? s->hmid[(size_t)(k + 1) * s->batch + b].state : f.O;
+            j.field_b = k + 1 < n ? mid_of(s, b, k + 1).state : f.O;
             j.step = m.step;
             mj[(size_t)k * nframes + b] = j;
         }
@@ -172,26 +230,23 @@ static void solver_enqueue_warp(ArapFlow_Solver* s, unsigned nframes)
         enqueue_warp(st->stream, s->dmid_jobs + (size_t)k * nframes, nframes, s->W, s->H, 0, nullptr, 0, true);
 }
 
-// pinned staging of the downloads, allocated when first needed: at creation / SetOutputs in the asynchronous use
-// (hipHostMalloc waits for the device, i.e. for another solver object's running solve), else at the first download
-static void solver_pin_out(ArapFlow_Solver* s)
+// one group's downloads of a solve call on the copy stream: of every slot (and snapshot) the planes that it has
+static void solver_download(ArapFlow_Solver* s, int g, unsigned nframes, unsigned state)
 {
-    if (s->pin_out) return;
-    s->pin_out_slot = align_up(12 * (size_t)s->N, 256);
-    HC(hipHostMalloc((void**)&s->pin_out, s->pin_out_slot * s->batch, hipHostMallocDefault));
-}
-static void solver_pin_ext(ArapFlow_Solver* s)
-{
-    if (s->pin_ext) return;
-    s->pin_ext_slot = align_up(10 * (size_t)s->N, 256);
-    HC(hipHostMalloc((void**)&s->pin_ext, s->pin_ext_slot * s->batch, hipHostMallocDefault));
-}
-
-static void solver_pin_diag(ArapFlow_Solver* s)
-{
-    if (s->pin_diag) return;
-    s->pin_diag_slot = 256 + align_up((size_t)s->N, 256);
-    HC(hipHostMalloc((void**)&s->pin_diag, s->pin_diag_slot * s->batch, hipHostMallocDefault));
+    ResultGroup& r = s->res[g];
+    r.at_dl = state;
+    const unsigned items = group_items(g, state);
+    if (!items) return;
+    solver_pin(s, g);
+    for (unsigned k = 0; k < items; ++k)
+        for (unsigned b = 0; b < nframes; ++b) {
+            char* o = r.pin + r.stride * ((size_t)k * s->batch + b);
+            for (int i = 0; i < MAX_PLANES; ++i) {
+                const Plane& p = kPlanes[g][i];
+                if (plane_staged(s, p, state, b))
+                    HC(hipMemcpyAsync(o + r.off[i], p.dev(s, b, k), plane_bytes(p, s->N), hipMemcpyDeviceToHost, s->copy));
+            }
+        }
 }
 
 // the whole schedule of slots [0, a_n) on the compute stream (+ warp, + download on the copy stream), no waiting
@@ -224,8 +279,7 @@ static void solver_enqueue(ArapFlow_Solver* s)
         for (unsigned k = 0; k < s->a_snap_n; ++k)
             if (s->a_snap_steps[k] == i + 1)
                 for (unsigned b = 0; b < nframes; ++b)
-                    HC(hipMemcpyAsync(s->hmid[(size_t)k * s->batch + b].state, s->hfr[b].O, sizeof(float2) * s->N,
-                                      hipMemcpyDeviceToDevice, st->stream));
+                    HC(hipMemcpyAsync(mid_of(s, b, k).state, s->hfr[b].O, sizeof(float2) * s->N, hipMemcpyDeviceToDevice, st->stream));
     }
     s->taken_n = s->a_snap_n;
     if (s->a_warp) solver_enqueue_warp(s, nframes);
@@ -235,53 +289,10 @@ static void solver_enqueue(ArapFlow_Solver* s)
     }
     HC(hipEventRecord(s->ev_done, st->stream));
     if (s->a_download) {
-        solver_pin_out(s);
         HC(hipStreamWaitEvent(s->copy, s->ev_done, 0));
-        const size_t N = s->N;
-        for (unsigned b = 0; b < nframes; ++b) {
-            const FrameDev& f = s->hfr[b];
-            char* o = s->pin_out + s->pin_out_slot * b;
-            HC(hipMemcpyAsync(o, f.flow, 8 * N, hipMemcpyDeviceToHost, s->copy));
-            if (s->has_rgb[b]) HC(hipMemcpyAsync(o + 8 * N, f.out_rgb, 3 * N, hipMemcpyDeviceToHost, s->copy));
-            HC(hipMemcpyAsync(o + 11 * N, f.out_mask, N, hipMemcpyDeviceToHost, s->copy));
-        }
-        s->dl_outputs = s->a_warp ? s->outputs : 0;
-        if (s->dl_outputs) {
-            solver_pin_ext(s);
-            for (unsigned b = 0; b < nframes; ++b) {
-                const FrameExt& e = s->hext[b];
-                char* o = s->pin_ext + s->pin_ext_slot * b;
-                if (s->dl_outputs & ARAPFLOW_OUT_BACKWARD) {
-                    HC(hipMemcpyAsync(o, e.bwd, 8 * N, hipMemcpyDeviceToHost, s->copy));
-                    HC(hipMemcpyAsync(o + 8 * N, e.occ_bwd, N, hipMemcpyDeviceToHost, s->copy));
-                }
-                if (s->dl_outputs & ARAPFLOW_OUT_OCCLUSION)
-                    HC(hipMemcpyAsync(o + 9 * N, e.occ, N, hipMemcpyDeviceToHost, s->copy));
-            }
-        }
-        s->dl_diag = s->a_warp ? s->diag : 0;
-        if (s->dl_diag) {
-            solver_pin_diag(s);
-            for (unsigned b = 0; b < nframes; ++b) {
-                char* o = s->pin_diag + s->pin_diag_slot * b;
-                HC(hipMemcpyAsync(o, s->dgn_stats + b, sizeof(ArapFlow_MeshStats), hipMemcpyDeviceToHost, s->copy));
-                HC(hipMemcpyAsync(o + 256, (uint8_t*)s->dgn + s->dgn_fold_slot * b, N, hipMemcpyDeviceToHost, s->copy));
-            }
-        }
-        s->dl_snap_n = s->a_warp ? s->taken_n : 0;
-        if (s->dl_snap_n) {
-            solver_pin_mid(s);
-            for (unsigned k = 0; k < s->dl_snap_n; ++k)
-                for (unsigned b = 0; b < nframes; ++b) {
-                    const size_t kb = (size_t)k * s->batch + b;
-                    const MidDev& m = s->hmid[kb];
-                    char* o = s->pin_mid + s->pin_mid_slot * kb;
-                    HC(hipMemcpyAsync(o, m.flow, 8 * N, hipMemcpyDeviceToHost, s->copy));
-                    HC(hipMemcpyAsync(o + 8 * N, m.step, 8 * N, hipMemcpyDeviceToHost, s->copy));
-                    if (s->has_rgb[b]) HC(hipMemcpyAsync(o + 16 * N, m.rgb, 3 * N, hipMemcpyDeviceToHost, s->copy));
-                    HC(hipMemcpyAsync(o + 19 * N, m.mask, N, hipMemcpyDeviceToHost, s->copy));
-                }
-        }
+        // (without a warp in this call the optional groups are not carried: their buffers are an earlier warp's)
+        for (int g = 0; g < G_COUNT; ++g)
+            solver_download(s, g, nframes, g == G_BASE || s->a_warp ? s->res[g].at_warp : 0u);
         HC(hipEventRecord(s->ev_dl, s->copy));
     }
     s->last_cost_index = p->sp.nIter;
@@ -312,38 +323,31 @@ ArapFlow_Solver* ArapFlow_SolverCreate(Opt_State* st, unsigned W, unsigned H, un
         s->plan->d_t64n = s->plan->d_t64list + batch * T;
     }
     const size_t N = s->N;
-    const size_t sz2 = align_up(N * sizeof(float2), 256), sz1 = align_up(N * sizeof(float), 256);
-    const size_t szb = align_up(N, 256), sz3 = align_up(3 * N, 256), szk = align_up(N * 8, 256);
-    const size_t per = 5 * sz2 + 2 * sz1 + 2 * szb + 2 * sz3 + szk;
-    const size_t tail = align_up(sizeof(FrameDev) * batch, 256) + align_up(sizeof(WarpJob) * batch, 256);
-    HC(hipMalloc(&s->block, per * batch + tail));
-    HC(hipMemsetAsync(s->block, 0, per * batch + tail, st->stream));
-    char* c = (char*)s->block;
-    auto take = [&](size_t b) { char* r = c; c += b; return r; };
     s->hfr.resize(batch);
-    for (unsigned b = 0; b < batch; ++b) {
-        FrameDev& f = s->hfr[b];
-        f.O = (float2*)take(sz2); f.U = (float2*)take(sz2); f.C = (float2*)take(sz2);
-        f.T = (float2*)take(sz2); f.flow = (float2*)take(sz2);
-        f.A = (float*)take(sz1); f.M = (float*)take(sz1);
-        f.mask = (uint8_t*)take(szb); f.out_mask = (uint8_t*)take(szb);
-        f.rgb = (uint8_t*)take(sz3); f.out_rgb = (uint8_t*)take(sz3);
-        f.key = (unsigned long long*)take(szk);
-    }
-    s->dfr = (FrameDev*)take(align_up(sizeof(FrameDev) * batch, 256));
-    s->djobs = (WarpJob*)take(align_up(sizeof(WarpJob) * batch, 256));
+    s->block = device_block(st, true, [&](Carver& part) {
+        for (FrameDev& f : s->hfr) {
+            for (float2** q : {&f.O, &f.U, &f.C, &f.T, &f.flow}) part(*q, N * sizeof(float2));
+            part(f.A, N * sizeof(float)); part(f.M, N * sizeof(float));
+            part(f.mask, N); part(f.out_mask, N);
+            part(f.rgb, 3 * N); part(f.out_rgb, 3 * N);
+            part(f.key, N * 8);
+        }
+        part(s->dfr, sizeof(FrameDev) * batch);
+        part(s->djobs, sizeof(WarpJob) * batch);
+    });
     HC(hipMemcpyAsync(s->dfr, s->hfr.data(), sizeof(FrameDev) * batch, hipMemcpyHostToDevice, st->stream));
     HC(hipStreamSynchronize(st->stream));
     HC(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
     HC(hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming));
     HC(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
     HC(hipEventCreateWithFlags(&s->ev_dl, hipEventDisableTiming));
-    s->pin_in_slot = align_up(12 * N, 256);
+    s->pin_in_slot = align_up((8 + 1 + 3) * N, 256);
     HC(hipHostMalloc((void**)&s->pin_in, s->pin_in_slot * batch, hipHostMallocDefault));
     // (allocated here, not at first use: hipHostMalloc waits for the device, i.e. for another solver object's running solve)
     HC(hipHostMalloc((void**)&s->pin_jobs, sizeof(WarpJob) * batch, hipHostMallocDefault));
     HC(hipHostMalloc((void**)&s->pin_err, 64, hipHostMallocDefault));
-    if (st->own_stream) solver_pin_out(s);   // the asynchronous use (ArapFlow_UseOwnStream first): downloads will be asked for
+    solver_layout_results(s);
+    if (st->own_stream) solver_pin(s, G_BASE);   // the asynchronous use (ArapFlow_UseOwnStream first): downloads will be asked for
     s->has_rgb.assign(batch, 0);
     s->nactive.assign(batch, 0);
     const float wfit = sqrtf(100.0f), wreg = sqrtf(0.01f);   // CombinedSolver.h:173-177
@@ -365,16 +369,14 @@ void ArapFlow_SolverFree(ArapFlow_Solver* s)
     (void)hipStreamDestroy(s->copy);
     (void)hipEventDestroy(s->ev_up); (void)hipEventDestroy(s->ev_done); (void)hipEventDestroy(s->ev_dl);
     if (s->pin_in) (void)hipHostFree(s->pin_in);
-    if (s->pin_out) (void)hipHostFree(s->pin_out);
+    for (ResultGroup& r : s->res)
+        if (r.pin) (void)hipHostFree(r.pin);
     if (s->pin_jobs) (void)hipHostFree(s->pin_jobs);
     if (s->pin_err) (void)hipHostFree(s->pin_err);
-    if (s->pin_ext) (void)hipHostFree(s->pin_ext);
     if (s->ext) (void)hipFree(s->ext);
     if (s->mid) (void)hipFree(s->mid);
     if (s->pin_mid_jobs) (void)hipHostFree(s->pin_mid_jobs);
-    if (s->pin_mid) (void)hipHostFree(s->pin_mid);
     if (s->dgn) (void)hipFree(s->dgn);
-    if (s->pin_diag) (void)hipHostFree(s->pin_diag);
     (void)hipFree(s->block);
     delete s;
 }
@@ -391,8 +393,8 @@ int ArapFlow_SolverSetFrame(ArapFlow_Solver* s, unsigned slot, const uint8_t* rg
     HC(hipStreamSynchronize(s->copy));
     char* stage = s->pin_in + s->pin_in_slot * slot;
     float2* T = (float2*)stage;
-    uint8_t* smask = (uint8_t*)(stage + 8 * N);
-    uint8_t* srgb = (uint8_t*)(stage + 9 * N);
+    uint8_t* smask = (uint8_t*)(T + N);
+    uint8_t* srgb = smask + N;
     // host pre-pass of setConstraintImage's placement loop (CombinedSolver.h:230-240): file
     // constraints first, then border pins (main.cpp:130-136); later entries overwrite earlier ones;
     // only where Mask == 0.
@@ -444,13 +446,14 @@ int ArapFlow_SolverSolveAsync(ArapFlow_Solver* s, unsigned nframes, unsigned num
                               unsigned lIterations, int warp, int download)
 {
     if (!s || nframes == 0 || nframes > (unsigned)s->batch || numIter == 0) return -1;
-    if (s->snap_n && s->snap_steps[s->snap_n - 1] > numIter) return -1;     // (increasing: the last is the largest)
+    const unsigned snaps = s->res[G_MID].want;
+    if (snaps && s->snap_steps[snaps - 1] > numIter) return -1;     // (increasing: the last is the largest)
     if (ArapFlow_SolverWait(s) != 0) return -1;
     Opt_State* st = s->st;
     HC(hipSetDevice(st->device));
-    s->a_snap_n = s->snap_n;
+    s->a_snap_n = snaps;
     memcpy(s->a_snap_steps, s->snap_steps, sizeof(s->snap_steps));
-    solver_mid_alloc(s, s->snap_n);                           // (the first solve that needs it; nothing with none)
+    solver_mid_alloc(s, snaps);                              // (the first solve that needs it; nothing with none)
     const bool paused = st->res_cooldown > 0;                 // this call runs on the two-kernel path: counts as one
     s->a_n = nframes; s->a_numIter = numIter; s->a_nIt = nIterations; s->a_lIt = lIterations;
     s->a_warp = warp; s->a_download = download;
@@ -521,26 +524,20 @@ int ArapFlow_SolverSetOutputs(ArapFlow_Solver* s, int which)
         HC(hipSetDevice(s->st->device));
         const size_t N = s->N;
         const WarpScratch L = warp_scratch(s->W, s->H, WARP_OCC);      // the occlusion scratch of one job
-        const size_t rank_bytes = L.bin - L.rank, bin_bytes = L.owner - L.bin;
-        const size_t per = align_up(8 * N, 256) + 2 * align_up(N, 256) + rank_bytes + bin_bytes;
         s->ext_cell_slot = L.rank - L.cell;
-        HC(hipMalloc(&s->ext, (per + s->ext_cell_slot) * s->batch));
-        HC(hipMemsetAsync(s->ext, 0, (per + s->ext_cell_slot) * s->batch, s->st->stream));
-        char* c = (char*)s->ext;
-        auto take = [&](size_t b) { char* r = c; c += b; return r; };
         s->hext.resize(s->batch);
-        for (int b = 0; b < s->batch; ++b) {
-            FrameExt& e = s->hext[b];
-            e.bwd = (float2*)take(align_up(8 * N, 256));
-            e.occ_bwd = (uint8_t*)take(align_up(N, 256)); e.occ = (uint8_t*)take(align_up(N, 256));
-            e.rank = (unsigned*)take(rank_bytes); e.bin = (int4*)take(bin_bytes);
-        }
-        s->ext_cells = (unsigned*)c;
-        for (int b = 0; b < s->batch; ++b) s->hext[b].cell = (unsigned*)take(s->ext_cell_slot);
+        s->ext = device_block(s->st, true, [&](Carver& part) {
+            for (FrameExt& e : s->hext) {
+                part(e.bwd, 8 * N); part(e.occ_bwd, N); part(e.occ, N);
+                part(e.rank, L.bin - L.rank); part(e.bin, L.owner - L.bin);
+            }
+            for (FrameExt& e : s->hext) part(e.cell, s->ext_cell_slot);
+        });
+        s->ext_cells = s->hext[0].cell;
         HC(hipStreamSynchronize(s->st->stream));
-        if (s->st->own_stream) solver_pin_ext(s);   // (as pin_out: downloads will be asked for)
+        if (s->st->own_stream) solver_pin(s, G_EXTRA);
     }
-    s->outputs = which;
+    s->res[G_EXTRA].want = (unsigned)which;
     return 0;
 }
 
@@ -550,75 +547,65 @@ int ArapFlow_SolverSetSnapshots(ArapFlow_Solver* s, const unsigned* steps, unsig
     for (unsigned k = 0; k < n; ++k)
         if (steps[k] < 1 || (k && steps[k] <= steps[k - 1])) return -1;
     if (const int rc = ArapFlow_SolverWait(s)) return rc;
-    s->snap_n = n;
+    s->res[G_MID].want = n;
     for (unsigned k = 0; k < n; ++k) s->snap_steps[k] = steps[k];
+    return 0;
+}
+
+// What the Get* entry points do: wait, check that the last warp wrote what is asked for, and copy it to the host
+// behind the compute stream.  `dst`: a host buffer per plane in the table's order, nullptr = not asked.
+static int solver_get(ArapFlow_Solver* s, int g, unsigned slot, unsigned k, void* const (&dst)[MAX_PLANES])
+{
+    if (!s || slot >= (unsigned)s->batch) return -1;
+    if (ArapFlow_SolverWait(s) != 0) return -1;
+    const unsigned state = s->res[g].at_warp;
+    if (g != G_EXTRA && k >= group_items(g, state)) return -1;      // (the extra outputs are judged plane by plane)
+    for (int i = 0; i < MAX_PLANES; ++i)
+        if (dst[i] && kPlanes[g][i].sel > 0 && !(state & (unsigned)kPlanes[g][i].sel)) return -1;
+    HC(hipStreamSynchronize(s->st->stream));
+    for (int i = 0; i < MAX_PLANES; ++i)
+        if (dst[i])
+            HC(hipMemcpyAsync(dst[i], kPlanes[g][i].dev(s, slot, k), plane_bytes(kPlanes[g][i], s->N), hipMemcpyDeviceToHost, s->copy));
+    HC(hipStreamSynchronize(s->copy));
+    return 0;
+}
+
+// What the Host* entry points do: pointers into the staging of the last solve call, which must have been a `download`
+// solve of this slot; nullptr for a plane the slot or that solve does not have.  `out`: as `dst` above.
+static int solver_host(ArapFlow_Solver* s, int g, unsigned slot, unsigned k, const void** const (&out)[MAX_PLANES])
+{
+    if (!s || slot >= (unsigned)s->batch || !s->a_download || slot >= s->a_n) return -1;
+    if (ArapFlow_SolverWait(s) != 0) return -1;
+    const ResultGroup& r = s->res[g];
+    if (k >= group_items(g, r.at_dl) || !r.pin) return -1;
+    const char* o = r.pin + r.stride * ((size_t)k * s->batch + slot);
+    for (int i = 0; i < MAX_PLANES; ++i)
+        if (out[i]) *out[i] = plane_staged(s, kPlanes[g][i], r.at_dl, slot) ? o + r.off[i] : nullptr;
     return 0;
 }
 
 int ArapFlow_SolverGetSnapshot(ArapFlow_Solver* s, unsigned slot, unsigned k, float* flow, uint8_t* rgb, uint8_t* mask,
                                float* step)
 {
-    if (!s || slot >= (unsigned)s->batch) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    if (k >= s->warp_snap_n || (rgb && !s->has_rgb[slot])) return -1;
-    HC(hipStreamSynchronize(s->st->stream));
-    const MidDev& m = s->hmid[(size_t)k * s->batch + slot];
-    const size_t N = s->N;
-    hipStream_t cs = s->copy;
-    if (flow) HC(hipMemcpyAsync(flow, m.flow, 8 * N, hipMemcpyDeviceToHost, cs));
-    if (rgb) HC(hipMemcpyAsync(rgb, m.rgb, 3 * N, hipMemcpyDeviceToHost, cs));
-    if (mask) HC(hipMemcpyAsync(mask, m.mask, N, hipMemcpyDeviceToHost, cs));
-    if (step) HC(hipMemcpyAsync(step, m.step, 8 * N, hipMemcpyDeviceToHost, cs));
-    HC(hipStreamSynchronize(cs));
-    return 0;
+    if (s && slot < (unsigned)s->batch && rgb && !s->has_rgb[slot]) return -1;
+    return solver_get(s, G_MID, slot, k, {flow, step, rgb, mask});
 }
 
 int ArapFlow_SolverHostSnapshot(ArapFlow_Solver* s, unsigned slot, unsigned k, const float** flow, const uint8_t** rgb,
                                 const uint8_t** mask, const float** step)
 {
-    if (!s || slot >= (unsigned)s->batch || !s->a_download || slot >= s->a_n) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    if (k >= s->dl_snap_n || !s->pin_mid) return -1;
-    const size_t N = s->N;
-    const char* o = s->pin_mid + s->pin_mid_slot * ((size_t)k * s->batch + slot);
-    if (flow) *flow = (const float*)o;
-    if (step) *step = (const float*)(o + 8 * N);
-    if (rgb) *rgb = s->has_rgb[slot] ? (const uint8_t*)(o + 16 * N) : nullptr;
-    if (mask) *mask = (const uint8_t*)(o + 19 * N);
-    return 0;
+    return solver_host(s, G_MID, slot, k, {(const void**)flow, (const void**)step, (const void**)rgb, (const void**)mask});
 }
 
 int ArapFlow_SolverGetExtraResults(ArapFlow_Solver* s, unsigned slot, float* bwd, uint8_t* occ_bwd, uint8_t* occ)
 {
-    if (!s || slot >= (unsigned)s->batch) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    if (((bwd || occ_bwd) && !(s->warp_outputs & ARAPFLOW_OUT_BACKWARD)) ||
-        (occ && !(s->warp_outputs & ARAPFLOW_OUT_OCCLUSION)))
-        return -1;
-    HC(hipStreamSynchronize(s->st->stream));
-    const FrameExt& e = s->hext[slot];
-    const size_t N = s->N;
-    hipStream_t cs = s->copy;
-    if (bwd) HC(hipMemcpyAsync(bwd, e.bwd, 8 * N, hipMemcpyDeviceToHost, cs));
-    if (occ_bwd) HC(hipMemcpyAsync(occ_bwd, e.occ_bwd, N, hipMemcpyDeviceToHost, cs));
-    if (occ) HC(hipMemcpyAsync(occ, e.occ, N, hipMemcpyDeviceToHost, cs));
-    HC(hipStreamSynchronize(cs));
-    return 0;
+    return solver_get(s, G_EXTRA, slot, 0, {bwd, occ_bwd, occ});
 }
 
 int ArapFlow_SolverHostExtraResults(ArapFlow_Solver* s, unsigned slot, const float** bwd, const uint8_t** occ_bwd,
                                     const uint8_t** occ)
 {
-    if (!s || slot >= (unsigned)s->batch || !s->a_download || slot >= s->a_n) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    if (!s->dl_outputs || !s->pin_ext) return -1;
-    const size_t N = s->N;
-    const char* o = s->pin_ext + s->pin_ext_slot * slot;
-    const bool b = s->dl_outputs & ARAPFLOW_OUT_BACKWARD, c = s->dl_outputs & ARAPFLOW_OUT_OCCLUSION;
-    if (bwd) *bwd = b ? (const float*)o : nullptr;
-    if (occ_bwd) *occ_bwd = b ? (const uint8_t*)(o + 8 * N) : nullptr;
-    if (occ) *occ = c ? (const uint8_t*)(o + 9 * N) : nullptr;
-    return 0;
+    return solver_host(s, G_EXTRA, slot, 0, {(const void**)bwd, (const void**)occ_bwd, (const void**)occ});
 }
 
 int ArapFlow_SolverSetDiag(ArapFlow_Solver* s, int on)
@@ -629,69 +616,39 @@ int ArapFlow_SolverSetDiag(ArapFlow_Solver* s, int on)
         HC(hipSetDevice(s->st->device));
         const size_t B = s->batch;
         s->dgn_fold_slot = align_up((size_t)s->N, 256);
-        const size_t accs = align_up(sizeof(DiagAcc) * B, 256), stats = align_up(sizeof(ArapFlow_MeshStats) * B, 256);
-        HC(hipMalloc(&s->dgn, s->dgn_fold_slot * B + accs + stats));
-        s->dgn_acc = (DiagAcc*)((char*)s->dgn + s->dgn_fold_slot * B);
-        s->dgn_stats = (ArapFlow_MeshStats*)((char*)s->dgn_acc + accs);
-        if (s->st->own_stream) solver_pin_diag(s);   // (as pin_out: downloads will be asked for)
+        uint8_t* folds = nullptr;
+        s->dgn = device_block(s->st, false, [&](Carver& part) {
+            part(folds, s->dgn_fold_slot * B);
+            part(s->dgn_acc, sizeof(DiagAcc) * B);
+            part(s->dgn_stats, sizeof(ArapFlow_MeshStats) * B);
+        });
+        if (s->st->own_stream) solver_pin(s, G_DIAG);
     }
-    s->diag = on ? 1 : 0;
+    s->res[G_DIAG].want = on ? 1 : 0;
     return 0;
 }
 
 int ArapFlow_SolverGetDiag(ArapFlow_Solver* s, unsigned slot, ArapFlow_MeshStats* stats, uint8_t* fold)
 {
-    if (!s || slot >= (unsigned)s->batch) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    if (!s->warp_diag) return -1;
-    HC(hipStreamSynchronize(s->st->stream));
-    hipStream_t cs = s->copy;
-    if (stats) HC(hipMemcpyAsync(stats, s->dgn_stats + slot, sizeof(ArapFlow_MeshStats), hipMemcpyDeviceToHost, cs));
-    if (fold) HC(hipMemcpyAsync(fold, (uint8_t*)s->dgn + s->dgn_fold_slot * slot, (size_t)s->N, hipMemcpyDeviceToHost, cs));
-    HC(hipStreamSynchronize(cs));
-    return 0;
+    return solver_get(s, G_DIAG, slot, 0, {stats, fold});
 }
 
 int ArapFlow_SolverHostDiag(ArapFlow_Solver* s, unsigned slot, const ArapFlow_MeshStats** stats, const uint8_t** fold)
 {
-    if (!s || slot >= (unsigned)s->batch || !s->a_download || slot >= s->a_n) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    if (!s->dl_diag || !s->pin_diag) return -1;
-    const char* o = s->pin_diag + s->pin_diag_slot * slot;
-    if (stats) *stats = (const ArapFlow_MeshStats*)o;
-    if (fold) *fold = (const uint8_t*)(o + 256);
-    return 0;
+    return solver_host(s, G_DIAG, slot, 0, {(const void**)stats, (const void**)fold});
 }
 
 int ArapFlow_SolverHostResults(ArapFlow_Solver* s, unsigned slot, const float** flow, const uint8_t** warped_rgb,
                                const uint8_t** warped_mask)
 {
-    if (!s || slot >= (unsigned)s->batch || !s->pin_out || !s->a_download || slot >= s->a_n) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    const size_t N = s->N;
-    const char* o = s->pin_out + s->pin_out_slot * slot;
-    if (flow) *flow = (const float*)o;
-    if (warped_rgb) *warped_rgb = s->has_rgb[slot] ? (const uint8_t*)(o + 8 * N) : nullptr;
-    if (warped_mask) *warped_mask = (const uint8_t*)(o + 11 * N);
-    return 0;
+    return solver_host(s, G_BASE, slot, 0, {(const void**)flow, (const void**)warped_rgb, (const void**)warped_mask});
 }
 
 int ArapFlow_SolverGetResults(ArapFlow_Solver* s, unsigned slot, float* flow, uint8_t* warped_rgb,
                               uint8_t* warped_mask, float* offset, float* angle, double* final_cost)
 {
-    if (!s || slot >= (unsigned)s->batch) return -1;
-    if (ArapFlow_SolverWait(s) != 0) return -1;
-    HC(hipStreamSynchronize(s->st->stream));
+    if (solver_get(s, G_BASE, slot, 0, {flow, warped_rgb, warped_mask, offset, angle}) != 0) return -1;
     plan_check_resident_error(s->plan);
-    const FrameDev& f = s->hfr[slot];
-    const size_t N = s->N;
-    hipStream_t cs = s->copy;
-    if (flow) HC(hipMemcpyAsync(flow, f.flow, N * sizeof(float2), hipMemcpyDeviceToHost, cs));
-    if (warped_rgb) HC(hipMemcpyAsync(warped_rgb, f.out_rgb, 3 * N, hipMemcpyDeviceToHost, cs));
-    if (warped_mask) HC(hipMemcpyAsync(warped_mask, f.out_mask, N, hipMemcpyDeviceToHost, cs));
-    if (offset) HC(hipMemcpyAsync(offset, f.O, N * sizeof(float2), hipMemcpyDeviceToHost, cs));
-    if (angle) HC(hipMemcpyAsync(angle, f.A, N * sizeof(float), hipMemcpyDeviceToHost, cs));
-    HC(hipStreamSynchronize(cs));
     if (final_cost) *final_cost = plan_read_cost(s->plan, (int)slot, s->last_cost_index);
     return 0;
 }

@@ -10,15 +10,10 @@ static void plan_lm_alloc(Opt_Plan* p)
 {
     if (p->lm_block) return;
     const size_t N = (size_t)p->N;
-    const size_t sz2 = align_up(N * sizeof(float2), 256), sz1 = align_up(N * sizeof(float), 256);
-    HC(hipMalloc(&p->lm_block, 5 * sz2 + 5 * sz1));
-    HC(hipMemsetAsync(p->lm_block, 0, 5 * sz2 + 5 * sz1, p->st->stream));
-    char* c = (char*)p->lm_block;
-    auto take = [&](size_t s) { char* r = c; c += s; return r; };
-    p->pd.bO = (float2*)take(sz2); p->pd.CtCO = (float2*)take(sz2); p->pd.SSqO = (float2*)take(sz2);
-    p->pd.AdO = (float2*)take(sz2); p->prevO = (float2*)take(sz2);
-    p->pd.bA = (float*)take(sz1); p->pd.CtCA = (float*)take(sz1); p->pd.SSqA = (float*)take(sz1);
-    p->pd.AdA = (float*)take(sz1); p->prevA = (float*)take(sz1);
+    p->lm_block = device_block(p->st, true, [&](Carver& part) {
+        for (float2** f : {&p->pd.bO, &p->pd.CtCO, &p->pd.SSqO, &p->pd.AdO, &p->prevO}) part(*f, N * sizeof(float2));
+        for (float** f : {&p->pd.bA, &p->pd.CtCA, &p->pd.SSqA, &p->pd.AdA, &p->prevA}) part(*f, N * sizeof(float));
+    });
 }
 
 static double plan_read_shards(Opt_Plan* p, const double* dev)

@@ -230,6 +230,25 @@ struct Opt_Plan {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// One way to lay out a device block.  `layout` names the block's parts in order through the Carver it is given, each
+// with its size in bytes; every part starts 256-aligned.  It runs twice: over a null base, which gives the block's
+// size, then over the allocation, which gives the pointers.  `zero`: cleared on the state's stream.
+struct Carver {
+    uintptr_t at;
+    template <class T> void operator()(T*& p, size_t bytes) { p = (T*)at; at += align_up(bytes, 256); }
+};
+template <class Layout> static void* device_block(Opt_State* st, bool zero, Layout&& layout)
+{
+    Carver size{0};
+    layout(size);
+    void* block = nullptr;
+    HC(hipMalloc(&block, size.at));
+    if (zero) HC(hipMemsetAsync(block, 0, size.at, st->stream));
+    Carver parts{(uintptr_t)block};
+    layout(parts);
+    return block;
+}
+
 static Opt_Plan* plan_create(Opt_State* st, int W, int H, int batch)
 {
     HC(hipSetDevice(st->device));
@@ -241,33 +260,20 @@ static Opt_Plan* plan_create(Opt_State* st, int W, int H, int batch)
     pd.tilesX = (W + TILE_X - 1) / TILE_X;
     pd.tilesY = (H + TILE_Y - 1) / TILE_Y;
     const size_t BN = (size_t)batch * p->N;
-    // 8 float2 images + 7 float images + flags + tileact + slots, zero initialised (o.t:627-632)
-    const size_t sz2 = align_up(BN * sizeof(float2), 256), sz1 = align_up(BN * sizeof(float), 256);
-    const size_t szf = align_up(BN, 256), szt = align_up((size_t)batch * pd.tilesX * pd.tilesY, 256);
-    const size_t szs = align_up(sizeof(Slot) * batch, 256);
     // order-fixed reductions (arap_device.h: block_reduce_fixed): a slot per workgroup of the largest launch of any
     // kernel of this plan -- every tile shape is at least 16 wide and 4 high -- and the groups' tickets
     pd.maxblk = ((W + 15) / 16) * ((H + 3) / 4) + 16;
-    const size_t szp = align_up((size_t)batch * pd.maxblk * 4 * sizeof(unsigned long long), 256);
-    const size_t szk = align_up((size_t)batch * NSHARD * RED_TICK_STRIDE * sizeof(unsigned), 256);
-    const size_t szg = align_up((size_t)batch * NSHARD * sizeof(unsigned), 256);
-    const size_t total = 8 * sz2 + 7 * sz1 + szf + szt + szs + szp + szk + szg;
-    HC(hipMalloc(&p->block, total));
-    HC(hipMemsetAsync(p->block, 0, total, st->stream));
-    char* c = (char*)p->block;
-    auto take = [&](size_t s) { char* r = c; c += s; return r; };
-    pd.deltaO = (float2*)take(sz2); pd.rO = (float2*)take(sz2); pd.zO = (float2*)take(sz2);
-    pd.pO0 = (float2*)take(sz2); pd.pO1 = (float2*)take(sz2); pd.ApO = (float2*)take(sz2);
-    pd.preO = (float2*)take(sz2); pd.cs = (float2*)take(sz2);
-    pd.deltaA = (float*)take(sz1); pd.rA = (float*)take(sz1); pd.zA = (float*)take(sz1);
-    pd.pA0 = (float*)take(sz1); pd.pA1 = (float*)take(sz1); pd.ApA = (float*)take(sz1);
-    pd.preA = (float*)take(sz1);
-    pd.flags = (uint8_t*)take(szf);
-    pd.tileact = (uint8_t*)take(szt);
-    pd.slots = (Slot*)take(szs);
-    pd.part = (unsigned long long*)take(szp);
-    pd.tick = (unsigned*)take(szk);
-    pd.gen = (unsigned*)take(szg);
+    // 8 float2 images + 7 float images + flags + tileact + slots, zero initialised (o.t:627-632)
+    p->block = device_block(st, true, [&](Carver& part) {
+        for (float2** f : {&pd.deltaO, &pd.rO, &pd.zO, &pd.pO0, &pd.pO1, &pd.ApO, &pd.preO, &pd.cs}) part(*f, BN * sizeof(float2));
+        for (float** f : {&pd.deltaA, &pd.rA, &pd.zA, &pd.pA0, &pd.pA1, &pd.ApA, &pd.preA}) part(*f, BN * sizeof(float));
+        part(pd.flags, BN);
+        part(pd.tileact, (size_t)batch * pd.tilesX * pd.tilesY);
+        part(pd.slots, sizeof(Slot) * batch);
+        part(pd.part, (size_t)batch * pd.maxblk * 4 * sizeof(unsigned long long));
+        part(pd.tick, (size_t)batch * NSHARD * RED_TICK_STRIDE * sizeof(unsigned));
+        part(pd.gen, (size_t)batch * NSHARD * sizeof(unsigned));
+    });
     pd.red = nullptr; pd.costred = nullptr; pd.nslots = 0; pd.ncost = 0;
     p->hslots.assign(batch, Slot{});
     p->h_ntiles.assign(batch, 0);

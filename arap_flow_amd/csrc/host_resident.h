@@ -41,33 +41,27 @@ static void plan_enable_resident(Opt_Plan* p)
             return;
         }
     }
-    const size_t sz_tl = align_up((size_t)p->batch * RES_MAX_TILES * sizeof(int), 256);
-    const size_t sz_nt = align_up((size_t)p->batch * sizeof(int), 256);
-    const size_t sz_gr = align_up((size_t)p->batch * RES_GRAN_PER_LAUNCH * 8, 256);   // one block per launch of a step
-    const size_t sz_map = align_up((size_t)p->batch * RES_WGS * sizeof(ResWg), 256);
+    const size_t B = (size_t)p->batch;
+    const size_t sz_map = align_up(B * RES_WGS * sizeof(ResWg), 256);
     p->rd.rtX = (p->W + RT_X - 1) / RT_X;
     p->rd.rtY = (p->H + RT_Y - 1) / RT_Y;
-    const size_t sz_tp = align_up((size_t)p->batch * p->rd.rtX * p->rd.rtY * sizeof(int), 256);
-    const size_t sz_bx = align_up((size_t)p->batch * p->rd.rtY * sizeof(int), 256);
-    const size_t sz_ra = align_up((size_t)p->rd.rtX * p->rd.rtY, 256);               // drop-in analysis: tile activity
     {
         // border z of every tile (arap_resident.h: ResDev::zx)
-        const size_t nz = (size_t)p->batch * RES_MAX_TILES * RES_ZG * sizeof(unsigned long long);
+        const size_t nz = B * RES_MAX_TILES * RES_ZG * sizeof(unsigned long long);
         HC(hipMalloc((void**)&p->rd.zx, nz));
         HC(hipMemsetAsync(p->rd.zx, 0, nz, st->stream));
     }
     HC(hipHostMalloc((void**)&p->pin_wgmap, sz_map, hipHostMallocDefault));
-    HC(hipMalloc(&p->res_block, sz_gr + sz_tl + sz_nt + 256 + sz_map + sz_tp + sz_bx + sz_ra));
-    HC(hipMemsetAsync(p->res_block, 0, sz_gr + sz_tl + sz_nt + 256 + sz_map + sz_tp + sz_bx + sz_ra, st->stream));
-    char* c = (char*)p->res_block;
-    p->rd.gran = (unsigned long long*)c; c += sz_gr;
-    p->rd.tilelist = (const int*)c; c += sz_tl;
-    p->rd.ntiles = (const int*)c; c += sz_nt;
-    p->rd.err = (unsigned*)c; c += 256;
-    p->d_wgmap = (ResWg*)c; c += sz_map;
-    p->rd.tilepos = (const int*)c; c += sz_tp;
-    p->rd.bandx0 = (const int*)c; c += sz_bx;
-    p->d_resact = (uint8_t*)c;
+    p->res_block = device_block(st, true, [&](Carver& part) {
+        part(p->rd.gran, B * RES_GRAN_PER_LAUNCH * 8);                   // one block per launch of a step
+        part(p->rd.tilelist, B * RES_MAX_TILES * sizeof(int));
+        part(p->rd.ntiles, B * sizeof(int));
+        part(p->rd.err, sizeof(unsigned));
+        part(p->d_wgmap, sz_map);
+        part(p->rd.tilepos, B * p->rd.rtX * p->rd.rtY * sizeof(int));
+        part(p->rd.bandx0, B * p->rd.rtY * sizeof(int));
+        part(p->d_resact, (size_t)p->rd.rtX * p->rd.rtY);                // drop-in analysis: tile activity
+    });
     p->pd.res_err = p->rd.err;
     p->rd.stamps = nullptr;
     p->rd.force_fail = knobs.force_res_fail == 1 ? 1 : 0;   // test hook

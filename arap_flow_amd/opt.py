@@ -30,6 +30,18 @@ def _dev_ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _host_ptr(a):
+    """the pointer of a host array, or NULL for None"""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _view(ptr, ctype, shape):
+    """numpy view (no copy) of the memory a c_void_p points to, None for NULL"""
+    if not ptr.value:
+        return None
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(int(np.prod(shape)),)).reshape(shape)
+
+
 class State:
     """Opt_State (Opt.h:35).  One per process/device; shared by solvers."""
 
@@ -336,7 +348,7 @@ class FrameSolver:
         flow, step = np.empty((H, W, 2), np.float32), np.empty((H, W, 2), np.float32)
         rgb = np.empty((H, W, 3), np.uint8) if want_rgb else None
         mask = np.empty((H, W), np.uint8)
-        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        p = _host_ptr
         if self.lib.ArapFlow_SolverGetSnapshot(self.h, slot, k, p(flow), p(rgb), p(mask), p(step)) != 0:
             raise ValueError("ArapFlow_SolverGetSnapshot: no snapshot %d for slot %d" % (k, slot))
         return dict(flow=flow, rgb=rgb, mask=mask, step=step)
@@ -349,11 +361,8 @@ class FrameSolver:
         rc = self.lib.ArapFlow_SolverHostSnapshot(self.h, slot, k, C.byref(pf), C.byref(pr), C.byref(pm), C.byref(ps))
         if rc != 0:
             raise ValueError("ArapFlow_SolverHostSnapshot: no downloaded snapshot %d for slot %d" % (k, slot))
-        def view(ptr, ctype, shape):
-            n = int(np.prod(shape))
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).reshape(shape)
-        return dict(flow=view(pf, C.c_float, (H, W, 2)), rgb=view(pr, C.c_uint8, (H, W, 3)) if pr.value else None,
-                    mask=view(pm, C.c_uint8, (H, W)), step=view(ps, C.c_float, (H, W, 2)))
+        return dict(flow=_view(pf, C.c_float, (H, W, 2)), rgb=_view(pr, C.c_uint8, (H, W, 3)),
+                    mask=_view(pm, C.c_uint8, (H, W)), step=_view(ps, C.c_float, (H, W, 2)))
 
     def set_frame(self, slot, mask_red, constraints, rgb=None, border_pins=True):
         mask_red = np.ascontiguousarray(mask_red, np.uint8)
@@ -398,25 +407,21 @@ class FrameSolver:
         rc = self.lib.ArapFlow_SolverHostResults(self.h, slot, C.byref(pf), C.byref(pr), C.byref(pm))
         if rc != 0:
             raise ValueError("ArapFlow_SolverHostResults: no downloaded results for slot %d" % slot)
-        def view(ptr, ctype, shape):
-            n = int(np.prod(shape))
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).reshape(shape)
-        out = dict(flow=view(pf, C.c_float, (H, W, 2)),
-                   warped_rgb=view(pr, C.c_uint8, (H, W, 3)) if pr.value else None,
-                   warped_mask=view(pm, C.c_uint8, (H, W)))
+        out = dict(flow=_view(pf, C.c_float, (H, W, 2)), warped_rgb=_view(pr, C.c_uint8, (H, W, 3)),
+                   warped_mask=_view(pm, C.c_uint8, (H, W)))
         if self.outputs:
             pb, pob, po = C.c_void_p(), C.c_void_p(), C.c_void_p()
             rc = self.lib.ArapFlow_SolverHostExtraResults(self.h, slot, C.byref(pb), C.byref(pob), C.byref(po))
             if rc != 0:                 # (that solve computed or downloaded none: the base results only)
                 return out
             if pb.value:
-                out.update(backward_flow=view(pb, C.c_float, (H, W, 2)), occlusion_bwd=view(pob, C.c_uint8, (H, W)))
+                out.update(backward_flow=_view(pb, C.c_float, (H, W, 2)), occlusion_bwd=_view(pob, C.c_uint8, (H, W)))
             if po.value:
-                out.update(occlusion=view(po, C.c_uint8, (H, W)))
+                out.update(occlusion=_view(po, C.c_uint8, (H, W)))
         if self.diag:
             ps, pf = C.POINTER(capi.MeshStats)(), C.c_void_p()
             if self.lib.ArapFlow_SolverHostDiag(self.h, slot, C.byref(ps), C.byref(pf)) == 0:
-                out.update(mesh_stats=_stats_dict(ps.contents), fold=view(pf, C.c_uint8, (H, W)))
+                out.update(mesh_stats=_stats_dict(ps.contents), fold=_view(pf, C.c_uint8, (H, W)))
         return out
 
     def warp(self, nframes=None):
@@ -433,7 +438,7 @@ class FrameSolver:
         off = np.empty((H, W, 2), np.float32)
         ang = np.empty((H, W), np.float32)
         cost = C.c_double(0.0)
-        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        p = _host_ptr
         rc = self.lib.ArapFlow_SolverGetResults(self.h, slot, p(flow), p(wrgb), p(wmsk), p(off), p(ang),
                                                 C.byref(cost))
         if rc != 0:
