@@ -910,6 +910,9 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                           : group_sum(bs, 2u * l + 2u, gran_group, rank, wgs, bcast, rd.err, sigma, fast, nullptr, rd.nowait != 0,
                                       STAMPS ? tm : nullptr, STAMPS ? tarr : nullptr);
         }
+        // (sigma is wanted HERE, with the outcome: else the compiler reads `ok` from the broadcast, branches on it and only
+        //  then fetches the value -- two dependent LDS round trips where the second sum's exit has one 8-byte read)
+        asm volatile("" : "+v"(sigma));
         if (!alive) break;
         RES_STAMP(tS1);
         // ---------------- phase B: alpha, r, z, rho', delta ---------------------------------------------
@@ -973,15 +976,15 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                           : group_sum(bs, 2u * l + 3u, gran_group, rank, wgs, bcast, rd.err, rhoNew, fast, nullptr, rd.nowait != 0,
                                       STAMPS ? tm : nullptr, STAMPS ? tarr + 1 : nullptr);
         }
-        if (!alive) break;
-        RES_STAMP(tS2);
-        float beta = 0.f;
-        if (rho > 0.f) beta = rhoNew / rho;
-        rho = rhoNew;
-        if (l + 1 == L) { alpha_last = alpha; break; }
-        // ---------------- p = z + beta p ---------------------------------------------------------------
-        // (1) issue the loads of the neighbours' border z for this workgroup's halo cells (all in flight)
+        // ---------------- p = z + beta p (its loads first) ----------------------------------------------
+        // (1) issue the loads of the neighbours' border z for this workgroup's halo cells (all in flight): at once, before the
+        //     branches on the sum's outcome -- they depend on none of it (the granules were published before the sum, their
+        //     tags say whether they have arrived), and a launch that leaves the loop here simply never looks at them
+        //     (with nine slots in use the halo entry {granule index, packed LDS offsets} comes from the LDS table, each half
+        //      where it is used: kept from here on, the second half costs the registers the 9-slot loop does not have)
         unsigned long long hg[RES_HALO_PER_THREAD][2];
+        unsigned hpk_[HREG ? 1 : RES_HALO_PER_THREAD];
+#define RES_HPK(U) (HREG ? hreg[U].y : hpk_[HREG ? 0 : (U)])
 #pragma unroll
         for (int u = 0; u < RES_HALO_PER_THREAD; ++u) {
             hg[u][0] = hg[u][1] = (unsigned long long)ztag << 48;
@@ -993,9 +996,21 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 for (int c = 0; c < 2; ++c) hg[u][c] = __hip_atomic_load(q_ + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
+        if (!alive) break;
+        RES_STAMP(tS2);
+        float beta = 0.f;
+        if (rho > 0.f) beta = rhoNew / rho;
+        rho = rhoNew;
+        if (l + 1 == L) { alpha_last = alpha; break; }
         // (2) own cells while those loads fly: delta += alpha p, then p = z + beta p.  Branch free (an excluded lane
         //     computes 0 + beta * 0).  The registers of Ap are free here: every slot's own p is fetched from LDS up front
         //     (one slot ahead, each slot paid an LDS round trip).
+        //     The old p of this thread's halo cells is fetched right behind the own cells (when their registers are free
+        //     again): it does not depend on the loads in flight (a halo cell is never an own cell and stands in the list
+        //     once, so nobody writes it before step (3)), and read in step (3), after the loads have returned, it was up to
+        //     six dependent LDS round trips on the chain.
+        float2 hp2[RES_HALO_PER_THREAD];
+        float hpa[RES_HALO_PER_THREAD];
         {
             float2 Up[NS];
             float Ua[NS];
@@ -1019,6 +1034,26 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 *(float*)(T_ + offA[0] + LPLANE * 16) = fmaf(beta, Ua[j], za);
             }
         }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+#pragma unroll
+            for (int u = 0; u < RES_HALO_PER_THREAD; ++u) {
+                hp2[u] = make_float2(0.f, 0.f); hpa[u] = 0.f;
+                if (!HREG) hpk_[u] = 0u;
+                if (tid + u * RES_THREADS < nh) {
+                    if (!HREG) hpk_[u] = htab[tid + u * RES_THREADS].y;
+                    hp2[u] = *(const float2*)((const char*)lds + (RES_HPK(u) & 0xffffu) * 8u);
+                    hpa[u] = *(const float*)((const char*)lds + (RES_HPK(u) >> 16) * 4u);
+                }
+            }
+        }
+        // delta += alpha p belongs HERE, under the wait for the z granules and these reads: left alone the compiler sinks
+        // its 3 NS FMAs behind the halo stores of step (3), onto the path to the closing barrier (a sched_barrier alone
+        // does not hold them: they cross blocks)
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+            if (HREG) asm volatile("" : "+v"(dx_[j]), "+v"(dy_[j]), "+v"(da_[j]));     // (at nine slots the pin reorders phase B)
+        __builtin_amdgcn_sched_barrier(0);
         // (3) halo cells: p_halo = z_halo + beta p_halo (the owner computes the same expression).  A granule whose tag is
         //     this iteration's holds this iteration's value; the group sum in between took far longer than a store
         //     travels, so the tags all but always match, and a lane whose granule is still the previous iteration's
@@ -1059,12 +1094,10 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                                             __uint_as_float(((unsigned)(hg[u][0] >> 32) & 0xffffu) | ((unsigned)(hg[u][1] >> 32) << 16)));
             const float hz1_ = __uint_as_float((unsigned)hg[u][1]);
             if (tid + u * RES_THREADS < nh) {
-                const unsigned pk = HREG ? hreg[u].y : htab[tid + u * RES_THREADS].y;
-                float2* P = (float2*)((char*)lds + (pk & 0xffffu) * 8u);
-                float* A = (float*)((char*)lds + (pk >> 16) * 4u);
-                const float2 po = *P;
-                *P = make_float2(fmaf(beta, po.x, hz2_.x), fmaf(beta, po.y, hz2_.y));
-                *A = fmaf(beta, *A, hz1_);
+                float2* P = (float2*)((char*)lds + (RES_HPK(u) & 0xffffu) * 8u);
+                float* A = (float*)((char*)lds + (RES_HPK(u) >> 16) * 4u);
+                *P = make_float2(fmaf(beta, hp2[u].x, hz2_.x), fmaf(beta, hp2[u].y, hz2_.y));
+                *A = fmaf(beta, hpa[u], hz1_);
             }
         }
         RES_PRIO_END()
@@ -1140,6 +1173,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 }
 
 #undef RES_STAMP
+#undef RES_HPK
 #undef RES_PRIO
 #undef RES_PRIO_END
 #undef TP2
