@@ -708,6 +708,14 @@ int ArapFlow_SolverResidentLayout(ArapFlow_Solver* s, int* launches_per_step, in
     if (solves_in_flight) *solves_in_flight = res ? s->plan->res_inflight : 0;
     return 0;
 }
+int ArapFlow_SolverResidentSums(ArapFlow_Solver* s, int* sums, unsigned cap)
+{
+    if (!s) return -1;
+    const Opt_Plan* p = s->plan;
+    if (!plan_resident_eligible(p) || p->res_sets <= 0) return 0;
+    for (int k = 0; k < p->res_sets && sums && (unsigned)k < cap; ++k) sums[k] = p->res_sums[k];
+    return p->res_sets;
+}
 int ArapFlow_ResidentFailed(Opt_State* state) { return state && state->resident_failed ? 1 : 0; }
 int ArapFlow_SolverLeanStream(ArapFlow_Solver* s) { return s && plan_lean_stream(s->plan) ? 1 : 0; }
 

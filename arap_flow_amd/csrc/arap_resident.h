@@ -79,6 +79,15 @@ static_assert(2 * ((RES_LDS_BYTES + 1279) / 1280 * 1280) <= 160 * 1024, "two wor
 #ifndef RES_WREG_FIT
 #define RES_WREG_FIT 6        // ... the fit weight too when at most this many slots are in use (else only the four edge weights)
 #endif
+#ifndef RES_WREG_FIT_FLAT
+#define RES_WREG_FIT_FLAT 7   // ... in the flat-sums flavour (RES_SUMS_FLAT below), whose loop leaves 15 VGPRs more
+#endif
+#ifndef RES_WREG_8_FLAT
+#define RES_WREG_8_FLAT 3     // edge weights kept in registers at 8 / 9 slots in the flat-sums flavour (8 slots: 4 spill)
+#endif
+#ifndef RES_WREG_9_FLAT
+#define RES_WREG_9_FLAT RES_WREG_9
+#endif
 // A workgroup's first look at the group's granules comes this long (x 64 clocks) after it has published its own: the
 // others publish at about the same time and a store needs ~300 clocks to become visible, so a look taken at once finds
 // nothing and costs a full L2 round trip before the next one (2.54 -> 2.14 sweeps per sum, 4.62 -> 4.54 us per iteration)
@@ -118,6 +127,15 @@ constexpr int RES_GRAN_PER_LAUNCH = RES_GRAN_X + RES_GRAN_L1;
 #ifndef RES_FLAT_MAX_RUNS
 #define RES_FLAT_MAX_RUNS 2   // groups of up to this many XCD runs sum with group_sum_x (one hop), wider ones in two levels
 #endif
+
+// Group-sum flavours a kernel instantiation carries (template argument SUMS of k_pcg_resident).  The loop inlines every
+// flavour it may need at both sums and chooses by run-time flags; a launch whose groups all have <= 64 workgroups (the
+// host knows when it deals the launch: host_resident.h) only ever runs group_sum, and carrying the other two costs it
+// scalar branches and SGPR reloads on the chain of both sums and ~15 VGPRs in the loop.
+//   RES_SUMS_ANY  : group_sum, group_sum_x and group_sum_h, chosen at run time -- any deal
+//   RES_SUMS_FLAT : group_sum only -- right for any deal (the flat gather sweeps ranks k, k + 64, ...), dealt only to
+//                   launches of groups of <= 64 workgroups, for which it computes the same bits as RES_SUMS_ANY
+constexpr int RES_SUMS_ANY = 0, RES_SUMS_FLAT = 1, RES_SUMS_COUNT = 2;
 
 // One entry per workgroup of a launch, written by the host (host_resident.h: plan_resident_pack): which solve the
 // workgroup works on, its rank in that solve's group, the group's size and where the group's granules start.
@@ -466,14 +484,22 @@ __device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 do
 // starts life as the u16 cell list); tile origins int2[9]; the 10-entry M^-1_O table; broadcast + reduction scratch;
 // the staging area of the border z (9 x 80 float4, 11 520 B).
 // Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), plus the edge weights where they fit
-// (4 per slot up to 7 slots, 2 at 8 and 9): 253 VGPRs at 7 slots, 249 at 9, no scratch.
+// (4 per slot up to 7 slots, 2 at 8 and 9): 253 VGPRs at 7 slots, 249 at 9, no scratch.  (The flat-sums flavour, SUMS
+// below, keeps the fit weight too at 7 slots and 3 edge weights at 8: 251 / 245 / 237 VGPRs at 7 / 8 / 9 slots.)
 // NS = tile slots the loops run over (1 .. RES_SLOTS): the most tiles any workgroup of the LAUNCH holds (the host picks
 // the instantiation per launch, host_step.h: enqueue_gn_step).  The phases are fully unrolled and branch free over the
 // slots, so their length is proportional to NS: a launch whose solves need 7 tiles per workgroup runs the 7-slot kernel.
-template <bool STAMPS, int NS>
+// SUMS = the group-sum flavours the loop carries (RES_SUMS_ANY / RES_SUMS_FLAT above).
+template <bool STAMPS, int NS, int SUMS>
 __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, ResDev rd, int L)
 {
     static_assert(NS >= 1 && NS <= RES_SLOTS, "slots");
+    static_assert(SUMS == RES_SUMS_ANY || SUMS == RES_SUMS_FLAT, "group-sum flavour");
+    constexpr bool FLAT = SUMS == RES_SUMS_FLAT;       // hier, hierx and subfast below are compile-time false
+    // what the flat loop frees goes to weights kept in registers -- not in the instrumented build, whose stamp accumulators
+    // need those registers (with the weights it spills in the update phase and its stamps measure the spills)
+    constexpr bool SPEND = FLAT && !STAMPS;
+    constexpr int WFIT = SPEND ? RES_WREG_FIT_FLAT : RES_WREG_FIT;    // the fit weight lives in registers up to this many slots
     unsigned long long tA = 0, tS1 = 0, tB = 0, tS2 = 0, tU = 0, t0 = 0, t1 = 0;
     unsigned long long tm[6] = {0, 0, 0, 0, 0, 0}, tbs = 0, tzr = 0;     // STAMPS: inside the group sums (shader clocks; wave 0)
     unsigned long long tbp[3] = {0, 0, 0}, tarr[2] = {0, 0};   // STAMPS: parts of the block sums; summed publish times of the two sums
@@ -508,7 +534,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     unsigned* nremote = nbits + 16;                                       // [1] some of them sit on another XCD
     float4* zst = (float4*)((char*)lds + RES_LDS_BYTES - RES_TILES_PER_WG * RES_ZX * 16);     // [9][RES_ZX] border z, staged: (z_x, z_y, z_alpha, z_y)
     unsigned long long* gran_group = rd.gran + me.gran;
-    unsigned long long* granx_group = rd.gran + RES_GRAN_X + me.gran;
+    unsigned long long* granx_group = FLAT ? nullptr : rd.gran + RES_GRAN_X + me.gran;
 
     const int nt = rd.ntiles[b];
     // this workgroup's run of the frame's active-tile list: nt tiles dealt evenly, the first nt % wgs ranks
@@ -544,7 +570,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     // phase A weights an edge by wr^2 or +0 (fit term: wf^2 or +0) according to the vertex's flag bits.  With registers
     // to spare (NS <= RES_WREG_SLOTS) the five weights per slot are formed once, here; otherwise from the flags in
     // every iteration (two bit operations each: 10 of the 51 VALU instructions of a vertex)
-    constexpr int NWR = NS <= RES_WREG_SLOTS ? 4 : (NS == 8 ? RES_WREG_8 : RES_WREG_9);     // edge weights kept per slot
+    constexpr int NWR = NS <= RES_WREG_SLOTS ? 4 : (NS == 8 ? (SPEND ? RES_WREG_8_FLAT : RES_WREG_8)
+                                                            : (SPEND ? RES_WREG_9_FLAT : RES_WREG_9));     // edge weights kept per slot
     constexpr bool WREG = NWR > 0;
     float we[WREG ? NS : 1][5];
     const int loff = lx + W * ly;                      // this lane's vertex inside a tile: index = ibase + loff
@@ -646,7 +673,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             if (NWR > 1) we[j][1] = keep_if<1>(f, wr2);
             if (NWR > 2) we[j][2] = keep_if<2>(f, wr2);
             if (NWR > 3) we[j][3] = keep_if<3>(f, wr2);
-            if (NS <= RES_WREG_FIT) we[j][4] = keep_if<4>(f, wf2);
+            if (NS <= WFIT) we[j][4] = keep_if<4>(f, wf2);
         }
         // (one LDS atomic per wavefront and kind, not one per entry: 560 atomics on one address took 2 us of every launch)
         halo_append(ly == 0 && (f & F_E3), (unsigned short)(j * LPLANE + 0 * LROW + lx + 1), hlist, nhalo);
@@ -731,7 +758,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     bool hierx = false;                                // ... or the one-hop form for a group of few runs (group_sum_x)
     // second-level granules of a group that spans XCDs: it starts at an even bin (blockIdx & 7) - (rank >> 6)
     unsigned long long* const gran2 =
-        rd.gran + RES_GRAN_L1 + ((((int)(blockIdx.x & 7u) - (me.rank >> 6)) >> 1) & 3) * RES_GRAN2_GROUP;
+        FLAT ? nullptr : rd.gran + RES_GRAN_L1 + ((((int)(blockIdx.x & 7u) - (me.rank >> 6)) >> 1) & 3) * RES_GRAN2_GROUP;
     {
         const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15u;     // HW_REG_XCC_ID
         float dummy;
@@ -748,7 +775,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         // granule that a faster workgroup has already reused carries another tag and counts as "elsewhere").
         // (a group of two runs always sums in one hop: its second run may be a short piece, and the second-level granules
         //  of group_sum_h are addressed by whole aligned bins)
-        hier = !fast && wgs > 64;
+        hier = !FLAT && !fast && wgs > 64;
         hierx = hier && (((wgs + 63) >> 6) <= 2 || ((wgs + 63) >> 6) <= rd.flat_runs);
         if (!fast && rd.allow_fast && alive) {
             if (wave == 0) {
@@ -773,7 +800,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             }
             __syncthreads();
             zfast = (*nremote & 1u) == 0u;
-            subfast = hier && (*nremote & 2u) == 0u;
+            subfast = !FLAT && hier && (*nremote & 2u) == 0u;
         } else {
             zfast = fast;
         }
@@ -887,7 +914,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 RES_EDGE(3, 3,      ci,  si,    cn,  sn,   -ci, -si)      // s=( 0,-1): q=(-ci,-si) h=(-cn,-sn)
 #undef RES_EDGE
                 {
-                    const float wf = (WREG && NS <= RES_WREG_FIT) ? we[WREG ? j : 0][4] : keep_if<4>(f, wf2);
+                    const float wf = (WREG && NS <= WFIT) ? we[WREG ? j : 0][4] : keep_if<4>(f, wf2);
                     axy = fma2(make_float2(wf, wf), pv, axy);
                 }
                 const float ax = axy.x, ay = axy.y;
@@ -905,8 +932,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             const unsigned long long cb = STAMPS ? __builtin_amdgcn_s_memtime() : 0ull;
             const double bs = block_sum8(acc, wsum, STAMPS ? tbp : nullptr);
             if (STAMPS) tbs += __builtin_amdgcn_s_memtime() - cb;
-            alive = hierx ? group_sum_x(block_sum_uniform(bs), 2u * l + 2u, gran_group, granx_group, rank, wgs, bcast, rd.err, sigma, subfast)
-                  : hier  ? group_sum_h(block_sum_uniform(bs), 2u * l + 2u, gran_group, gran2, rank, wgs, bcast, rd.err, sigma, subfast)
+            alive = (!FLAT && hierx) ? group_sum_x(block_sum_uniform(bs), 2u * l + 2u, gran_group, granx_group, rank, wgs, bcast, rd.err, sigma, subfast)
+                  : (!FLAT && hier)  ? group_sum_h(block_sum_uniform(bs), 2u * l + 2u, gran_group, gran2, rank, wgs, bcast, rd.err, sigma, subfast)
                           : group_sum(bs, 2u * l + 2u, gran_group, rank, wgs, bcast, rd.err, sigma, fast, nullptr, rd.nowait != 0,
                                       STAMPS ? tm : nullptr, STAMPS ? tarr : nullptr);
         }
@@ -971,8 +998,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                     }
                 }
             }
-            alive = hierx ? group_sum_x(block_sum_uniform(bs), 2u * l + 3u, gran_group, granx_group, rank, wgs, bcast, rd.err, rhoNew, subfast)
-                  : hier  ? group_sum_h(block_sum_uniform(bs), 2u * l + 3u, gran_group, gran2, rank, wgs, bcast, rd.err, rhoNew, subfast)
+            alive = (!FLAT && hierx) ? group_sum_x(block_sum_uniform(bs), 2u * l + 3u, gran_group, granx_group, rank, wgs, bcast, rd.err, rhoNew, subfast)
+                  : (!FLAT && hier)  ? group_sum_h(block_sum_uniform(bs), 2u * l + 3u, gran_group, gran2, rank, wgs, bcast, rd.err, rhoNew, subfast)
                           : group_sum(bs, 2u * l + 3u, gran_group, rank, wgs, bcast, rd.err, rhoNew, fast, nullptr, rd.nowait != 0,
                                       STAMPS ? tm : nullptr, STAMPS ? tarr + 1 : nullptr);
         }

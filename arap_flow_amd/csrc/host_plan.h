@@ -72,6 +72,7 @@ struct Knobs {
     bool stamps = false;        // ARAPOPT_STAMPS=1: diagnostic build of the resident kernel (tools/res_stamps.py)
     int res_groups = 0;         // ARAPOPT_RES_GROUPS=n (experiments only: n equal groups), 0 = the packed deal
     int res_ns = 0;             // ARAPOPT_RES_NS=n (experiments: run at least this many tile slots), 0 = as dealt
+    bool res_sums_any = false;  // ARAPOPT_RES_SUMS=any (tests, A/B): every launch takes the kernel that carries all group-sum flavours
 };
 
 static Knobs read_knobs()
@@ -94,6 +95,7 @@ static Knobs read_knobs()
     k.stamps = is("ARAPOPT_STAMPS", '1');
     k.res_groups = std::max(0, num("ARAPOPT_RES_GROUPS", 0));
     k.res_ns = std::max(0, num("ARAPOPT_RES_NS", 0));
+    k.res_sums_any = is("ARAPOPT_RES_SUMS", 'a');
     return k;
 }
 
@@ -145,6 +147,7 @@ struct StepRecipe {
     int L = -1, nb = 0, nsteps = 0; // lIterations, active slots, Gauss-Newton steps in one graph
     // resident path
     std::vector<int> res_ns;        // per launch of a step: the kernel instantiation (tile slots)
+    std::vector<int> res_sums;      // ... and its group-sum flavour (RES_SUMS_*): the kernel function is baked into the graph node
     bool stamped = false;           // ... of the instrumented build
     int list_blocks = 0;            // > 0: the per-step kernels run over the frames' 64x4 tile lists, with this grid.x
     // kernel-per-phase path
@@ -158,7 +161,7 @@ static bool same_recipe(const StepRecipe& a, const StepRecipe& b)
 {
     auto same3 = [](dim3 x, dim3 y) { return x.x == y.x && x.y == y.y && x.z == y.z; };
     return a.resident == b.resident && a.part == b.part && a.L == b.L && a.nb == b.nb && a.nsteps == b.nsteps &&
-           a.res_ns == b.res_ns && a.stamped == b.stamped && a.list_blocks == b.list_blocks && a.a_kern == b.a_kern &&
+           a.res_ns == b.res_ns && a.res_sums == b.res_sums && a.stamped == b.stamped && a.list_blocks == b.list_blocks && a.a_kern == b.a_kern &&
            a.b_kern == b.b_kern && same3(a.a_grid, b.a_grid) && same3(a.a_block, b.a_block) &&
            std::equal(a.a_arg, a.a_arg + 3, b.a_arg) && a.lag == b.lag;
 }
@@ -206,7 +209,9 @@ struct Opt_Plan {
     std::vector<ResWg> h_wgmap;     // what d_wgmap holds
     int res_sets = 0;               // resident launches per GN step
     std::vector<int> res_ns;        // per launch: tile slots in use = most tiles any of its workgroups holds
+    std::vector<int> res_sums;      // per launch: group-sum flavour (RES_SUMS_FLAT when all its groups have <= 64 workgroups)
     int knob_res_groups = 0, knob_res_ns = 0;   // Knobs::res_groups / res_ns as of this plan's creation
+    bool knob_res_sums_any = false; // Knobs::res_sums_any
     int res_inflight = 0;           // solves of the fullest launch (diagnostic)
     unsigned res_launches = 0;
     // drop-in (Opt_*) plans: result of the Init-time analysis (k_analyse) of the caller's Mask / UrShape

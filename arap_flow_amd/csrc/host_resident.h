@@ -4,21 +4,25 @@
 #pragma once
 
 // The resident kernel is instantiated per number of tile slots its loops run over (arap_resident.h): a launch takes
-// the instantiation for the most tiles any of its workgroups holds.
+// the instantiation for the most tiles any of its workgroups holds -- and per group-sum flavour (RES_SUMS_*): the one
+// that carries only the flat sum when every group dealt to the launch has <= 64 workgroups (resident_launch_sums).
 typedef void (*ResidentKernel)(PlanDev, ResDev, int);
-template <bool STAMPS, int... NS>
+template <bool STAMPS, int SUMS, int... NS>
 static const void* resident_kernel_of(int ns, std::integer_sequence<int, NS...>)
 {
-    static const ResidentKernel table[] = {k_pcg_resident<STAMPS, NS + 1>...};
+    static const ResidentKernel table[] = {k_pcg_resident<STAMPS, NS + 1, SUMS>...};
     return (const void*)table[ns - 1];
 }
-static const void* resident_kernel(bool stamps, int ns)
+static const void* resident_kernel(bool stamps, int ns, int sums)
 {
     if (ns < 1) ns = 1;
     if (ns > RES_SLOTS) ns = RES_SLOTS;
-    return stamps ? resident_kernel_of<true>(ns, std::make_integer_sequence<int, RES_SLOTS>())
-                  : resident_kernel_of<false>(ns, std::make_integer_sequence<int, RES_SLOTS>());
+    const auto slots = std::make_integer_sequence<int, RES_SLOTS>();
+    if (sums == RES_SUMS_FLAT)
+        return stamps ? resident_kernel_of<true, RES_SUMS_FLAT>(ns, slots) : resident_kernel_of<false, RES_SUMS_FLAT>(ns, slots);
+    return stamps ? resident_kernel_of<true, RES_SUMS_ANY>(ns, slots) : resident_kernel_of<false, RES_SUMS_ANY>(ns, slots);
 }
+static const char* resident_sums_name(int sums) { return sums == RES_SUMS_FLAT ? "flat" : "any"; }
 
 // resident-path resources: active-tile lists, granules, error word
 static void plan_enable_resident(Opt_Plan* p)
@@ -27,20 +31,24 @@ static void plan_enable_resident(Opt_Plan* p)
     const Knobs knobs = read_knobs();
     p->knob_res_groups = knobs.res_groups;
     p->knob_res_ns = knobs.res_ns;
+    p->knob_res_sums_any = knobs.res_sums_any;
     if (knobs.no_resident) return;
     hipDeviceProp_t prop;
     HC(hipGetDeviceProperties(&prop, st->device));
     if (prop.multiProcessorCount * 2 < RES_WGS) return;        // two resident workgroups per CU
-    for (int ns = 1; ns <= RES_SLOTS; ++ns) {
-        if (hipFuncSetAttribute(resident_kernel(false, ns), hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES) !=
-            hipSuccess) { (void)hipGetLastError(); return; }
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, resident_kernel(false, ns), RES_THREADS, RES_LDS_BYTES) !=
-                hipSuccess || occ < 2) {
-            (void)hipGetLastError();
-            return;
+    for (int sums = 0; sums < RES_SUMS_COUNT; ++sums)
+        for (int ns = 1; ns <= RES_SLOTS; ++ns) {
+            const void* kern = resident_kernel(false, ns, sums);
+            if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES) != hipSuccess) {
+                (void)hipGetLastError();
+                return;
+            }
+            int occ = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, RES_THREADS, RES_LDS_BYTES) != hipSuccess || occ < 2) {
+                (void)hipGetLastError();
+                return;
+            }
         }
-    }
     const size_t B = (size_t)p->batch;
     const size_t sz_map = align_up(B * RES_WGS * sizeof(ResWg), 256);
     p->rd.rtX = (p->W + RT_X - 1) / RT_X;
@@ -72,8 +80,9 @@ static void plan_enable_resident(Opt_Plan* p)
     p->rd.flat_runs = knobs.flat_runs;
     p->rd.nowait = knobs.res_nowait ? 1 : 0;
     if (knobs.stamps) {
-        for (int ns = 1; ns <= RES_SLOTS; ++ns)
-            HC(hipFuncSetAttribute(resident_kernel(true, ns), hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES));
+        for (int sums = 0; sums < RES_SUMS_COUNT; ++sums)
+            for (int ns = 1; ns <= RES_SLOTS; ++ns)
+                HC(hipFuncSetAttribute(resident_kernel(true, ns, sums), hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES));
         HC(hipMalloc(&p->rd.stamps, 2 * RES_WGS * 16 * sizeof(unsigned long long)));     // two tables (arap_resident.h)
         HC(hipMemset(p->rd.stamps, 0, 2 * RES_WGS * 16 * sizeof(unsigned long long)));
     }
@@ -397,6 +406,16 @@ static int resident_deal(const int* ntiles, int nb, int forced, std::vector<ResW
     return nsets;
 }
 
+// The group-sum flavour of one launch, from its table: the flat-only kernel exactly when every group dealt to it has
+// <= 64 workgroups (the kernel would take group_sum for all of them anyway), else the kernel that carries all three.
+static int resident_launch_sums(const ResWg* map, bool force_any)
+{
+    if (force_any) return RES_SUMS_ANY;
+    for (int i = 0; i < RES_WGS; ++i)
+        if (map[i].slot >= 0 && map[i].wgs > RES_WGS / 8) return RES_SUMS_ANY;
+    return RES_SUMS_FLAT;
+}
+
 // Deal the current batch; true if the tables changed (the caller re-uploads them: plan_upload_wgmap).
 static bool plan_resident_pack(Opt_Plan* p)
 {
@@ -411,18 +430,22 @@ static bool plan_resident_pack(Opt_Plan* p)
         }
     if (p->knob_res_ns > 0)                                      // experiments: run at least this many tile slots
         for (int& m : ns) m = std::max(m, std::min(p->knob_res_ns, (int)RES_SLOTS));
-    const bool same = nsets == p->res_sets && ns == p->res_ns && map.size() == p->h_wgmap.size() &&
+    std::vector<int> sums(nsets, RES_SUMS_ANY);
+    for (int set = 0; set < nsets; ++set)
+        sums[set] = resident_launch_sums(map.data() + (size_t)set * RES_WGS, p->knob_res_sums_any);
+    const bool same = nsets == p->res_sets && ns == p->res_ns && sums == p->res_sums && map.size() == p->h_wgmap.size() &&
                       memcmp(map.data(), p->h_wgmap.data(), map.size() * sizeof(ResWg)) == 0;
     if (same) return false;
     p->h_wgmap.swap(map);
     p->res_ns.swap(ns);
+    p->res_sums.swap(sums);
     p->res_sets = nsets;
     return true;
 }
 
 // A new deal of solves to workgroups (the frames' active-tile counts changed): upload the tables, stream ordered
 // behind earlier launches.  (The captured launches bake in only the number of launches, their slot counts and the list
-// length -- all in the StepRecipe -- so a new deal of the same shape replays the old graph.)
+// length, and through the kernel function the group-sum flavour -- all in the StepRecipe -- so a new deal of the same shape replays the old graph.)
 static void plan_upload_wgmap(Opt_Plan* p)
 {
     Opt_State* st = p->st;

@@ -53,6 +53,7 @@ static StepRecipe plan_step_recipe(Opt_Plan* p, int nsteps)
     if (r.resident) {
         if (plan_resident_pack(p)) plan_upload_wgmap(p);
         r.res_ns = p->res_ns;
+        r.res_sums = p->res_sums;
         r.stamped = p->rd.stamps != nullptr;
         // Frame solver: the resident launch applies the step itself (X += delta, cos/sin of the new Angle:
         // ResDev::fuse_update) and the init kernel zeroes the granules, so a step is [init, resident launches] and a lone
@@ -177,7 +178,7 @@ static void enqueue_gn_step(Opt_Plan* p, hipStream_t s, const StepRecipe& r, int
         for (size_t set = 0; set < r.res_ns.size(); ++set) {
             rd.wgmap = p->d_wgmap + set * RES_WGS;
             rd.gran = p->rd.gran + gran_per_launch * set;
-            const ResidentKernel kern = (ResidentKernel)resident_kernel(r.stamped, r.res_ns[set]);
+            const ResidentKernel kern = (ResidentKernel)resident_kernel(r.stamped, r.res_ns[set], r.res_sums[set]);
             if (r.stamped)
                 hipLaunchKernelGGL(kern, dim3(RES_WGS), dim3(RES_THREADS), RES_LDS_BYTES, s, p->pd, rd, L);
             else

@@ -465,9 +465,15 @@ class FrameSolver:
         self.lib.ArapFlow_SolverStats(self.h, C.byref(a), C.byref(b), C.byref(c))
         ls, fl = C.c_int(0), C.c_int(0)
         self.lib.ArapFlow_SolverResidentLayout(self.h, C.byref(ls), C.byref(fl))
+        # group-sum flavour of the resident kernel per launch of a step ("flat" / "any"; one word when they agree, "" when
+        # the two-kernel path ran)
+        sums = (C.c_int * 64)()
+        n = max(0, min(64, self.lib.ArapFlow_SolverResidentSums(self.h, sums, 64)))
+        names = ["flat" if sums[k] == 1 else "any" for k in range(n)]
         return dict(pcg_iterations_per_frame=a.value, active_vertices=b.value, grid_vertices=c.value,
                     resident_launches=int(self.lib.ArapFlow_SolverResidentLaunches(self.h)),
                     resident_launches_per_step=ls.value, resident_solves_in_flight=fl.value,
+                    resident_sums=names[0] if len(set(names)) == 1 else ",".join(names),
                     lean_stream=bool(self.lib.ArapFlow_SolverLeanStream(self.h)))
 
     def close(self):

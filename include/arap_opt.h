@@ -257,6 +257,11 @@ uint64_t ArapFlow_SolverResidentLaunches(ArapFlow_Solver* s);
  * number of solves in flight in one launch (every solve gets a group of the launch's 512 workgroups sized by its
  * active-tile count; small solves share an XCD).  Both 0 when the two-kernel path ran.  Returns 0, -1 on NULL. */
 int ArapFlow_SolverResidentLayout(ArapFlow_Solver* s, int* launches_per_step, int* solves_in_flight);
+/* Which group-sum flavour of the resident kernel each launch of a Gauss-Newton step of the last solve took: 1 = the
+ * kernel that carries only the flat sum (every group dealt to the launch has <= 64 workgroups), 0 = the kernel that
+ * carries all three (ARAPOPT_RES_SUMS=any, read when the state's plans are created, forces it).  Same arithmetic, identical
+ * results.  Writes min(launches, cap) entries; returns the launches per step (0: the two-kernel path ran), -1 on NULL. */
+int ArapFlow_SolverResidentSums(ArapFlow_Solver* s, int* sums, unsigned cap);
 /* Resident launches per Gauss-Newton step that a solve of slots [0, nframes) would take with the frames set so far
  * (0: the two-kernel path would run, -1: bad arguments).  Every launch costs about the same time however full it
  * is, so a host that wants the best throughput adds frames to a batch while this stays 1 (arap_deform does). */

@@ -1,8 +1,11 @@
 """The PCG loop of the resident kernel as the compiler emitted it (CPU only: hipcc -S cross-compiles).
 
     python tools/loop_diff.py asm OUT.s            device assembly of arap_flow_amd/csrc/arapopt.hip as it is now
-    python tools/loop_diff.py stats A.s [NS]       instruction mix of the main loop of k_pcg_resident<false, NS> (default 7)
-    python tools/loop_diff.py diff A.s B.s [NS]    the two loops side by side with register NAMES normalised
+    python tools/loop_diff.py stats A.s [NS] [SUMS]      instruction mix of the main loop of k_pcg_resident<false, NS, SUMS>
+                                                         (default 7 slots; SUMS: flat (default) or any)
+    python tools/loop_diff.py diff A.s B.s [NS] [SA] [SB]  the two loops side by side with register NAMES normalised (SA / SB:
+                                                         flavour taken from A / B; a file of a build from before the
+                                                         flavours has one kernel per NS, which is taken whatever SA says)
     python tools/loop_diff.py same A.s B.s         every function and kernel descriptor of A against B's of the same name,
                                                    whatever their order in the files; exit status 1 on any difference
 
@@ -28,10 +31,14 @@ def emit_asm(out):
     subprocess.check_call(cmd)
 
 
-def kernel_lines(path, ns):
-    name = "_ZN4arap14k_pcg_residentILb0ELi%dEEEvNS_7PlanDevENS_6ResDevEi" % ns
+SUMS = {"any": 0, "flat": 1}           # arap_resident.h: RES_SUMS_*
+
+
+def kernel_lines(path, ns, sums="flat"):
+    names = ["_ZN4arap14k_pcg_residentILb0ELi%dELi%dEEEvNS_7PlanDevENS_6ResDevEi:" % (ns, SUMS[sums]),
+             "_ZN4arap14k_pcg_residentILb0ELi%dEEEvNS_7PlanDevENS_6ResDevEi:" % ns]       # (builds before the flavours)
     lines = open(path).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith(name + ":"))
+    start = next(i for n in names for i, l in enumerate(lines) if l.startswith(n))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     return lines[start:end]
 
@@ -120,10 +127,11 @@ def main():
     if len(a) >= 2 and a[0] == "asm":
         emit_asm(a[1])
     elif len(a) >= 2 and a[0] == "stats":
-        print(stats(main_loop(kernel_lines(a[1], int(a[2]) if len(a) > 2 else 7))))
+        print(stats(main_loop(kernel_lines(a[1], int(a[2]) if len(a) > 2 else 7, a[3] if len(a) > 3 else "flat"))))
     elif len(a) >= 3 and a[0] == "diff":
         ns = int(a[3]) if len(a) > 3 else 7
-        la, lb = main_loop(kernel_lines(a[1], ns)), main_loop(kernel_lines(a[2], ns))
+        sa = a[4] if len(a) > 4 else "flat"
+        la, lb = main_loop(kernel_lines(a[1], ns, sa)), main_loop(kernel_lines(a[2], ns, a[5] if len(a) > 5 else sa))
         print(a[1], stats(la))
         print(a[2], stats(lb))
         na = [normalise(l) for l in la if normalise(l).strip()]
