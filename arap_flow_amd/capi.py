@@ -23,6 +23,14 @@ class MeshStats(C.Structure):
                 ("disp2_max", C.c_float)]
 
 
+class TexLayer(C.Structure):
+    """ArapFlow_TexLayer (DESIGN.md "Random textures")"""
+    _fields_ = [("kind", C.c_uint32), ("seed", C.c_uint32), ("m", C.c_float * 6), ("p0", C.c_float), ("p1", C.c_float),
+                ("c0", C.c_uint8 * 3), ("c1", C.c_uint8 * 3), ("c2", C.c_uint8 * 3), ("reserved", C.c_uint8 * 3)]
+
+
+TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")      # ARAPFLOW_TEX_*: a kind's number is its index here
+
 MESH_STATS_KEYS = tuple(k for k, _ in MeshStats._fields_ if k != "reserved")     # the order of a diag file's lines
 
 
@@ -91,6 +99,7 @@ SYMBOLS = [
     ("ArapFlow_BackgroundMaps", _I, [C.POINTER(C.c_float)] * 4),
     ("ArapFlow_Background", _I, [_VP, _U, _U, _VP, _U, _U, C.POINTER(C.c_float), C.POINTER(C.c_float)] + [_VP] * 14),
     ("ArapFlow_BackgroundSeq", _I, [_VP, _U, _U, _VP, _U, _U, _U, C.POINTER(C.c_float), _VP] + [C.POINTER(_VP)] * 7),
+    ("ArapFlow_Texture", _I, [_VP, _U, _U, _U, _VP, _VP, C.POINTER(TexLayer), _VP]),
     ("ArapFlow_WarpDiag", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP]),
     ("ArapFlow_SolverSetDiag", _I, [_VP, _I]),
     ("ArapFlow_SolverGetDiag", _I, [_VP, _U, C.POINTER(MeshStats), _VP]),

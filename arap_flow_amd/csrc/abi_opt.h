@@ -112,6 +112,7 @@ void ArapFlow_FreeState(Opt_State* st)
     (void)hipEventDestroy(st->t1);
     st->ktimer.clear();
     if (st->diag) (void)hipFree(st->diag);
+    if (st->tex) (void)hipFree(st->tex);
     delete st;
 }
 

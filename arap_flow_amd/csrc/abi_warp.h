@@ -1,7 +1,8 @@
 // abi_warp.h -- the warp entry points on caller-owned images (ArapFlow_Warp / WarpEx / WarpStep / WarpLayers /
 // WarpLayersStep): the layout of their scratch buffer, stated once for the size functions and for the code that carves
 // it up, and the one enqueue of rasterise -> optional outputs -> resolve that the frame solver's warp shares.
-// Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background / BackgroundSeq, arap_bg.h), which needs no scratch.
+// Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background / BackgroundSeq, arap_bg.h), which needs no
+// scratch, and the random textures of a frame's objects (ArapFlow_Texture, arap_tex.h).
 #pragma once
 
 // the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
@@ -350,6 +351,38 @@ int ArapFlow_BackgroundSeq(Opt_State* st, unsigned W, unsigned H, const void* bg
     const BgPicture pic{(const uint8_t*)bg, (int)bgW, (int)bgH};
     const dim3 grid((W + 63) / 64, (H + 3) / 4, nframes), block(64, 4);
     hipLaunchKernelGGL(k_bg_seq, grid, block, 0, st->stream, seq, pic, (int)W, (int)H);
+    return (int)hipGetLastError();
+}
+
+static_assert(sizeof(TexLayer) == sizeof(ArapFlow_TexLayer) && sizeof(TexLayer) == 52 &&
+              offsetof(TexLayer, m) == offsetof(ArapFlow_TexLayer, m) && offsetof(TexLayer, p0) == offsetof(ArapFlow_TexLayer, p0) &&
+              offsetof(TexLayer, c0) == offsetof(ArapFlow_TexLayer, c0) && offsetof(TexLayer, c2) == offsetof(ArapFlow_TexLayer, c2),
+              "the kernel reads the caller's table as it is");
+static_assert(TEX_CHECKER == ARAPFLOW_TEX_CHECKER && TEX_BRICK == ARAPFLOW_TEX_BRICK && TEX_VORONOI == ARAPFLOW_TEX_VORONOI &&
+              TEX_NOISE == ARAPFLOW_TEX_NOISE && TEX_WAVE == ARAPFLOW_TEX_WAVE && TEX_KINDS == ARAPFLOW_TEX_WAVE + 1, "kinds");
+
+int ArapFlow_Texture(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                     const ArapFlow_TexLayer* layers, void* out_rgb)
+{
+    if (!st || !rgb || !layers || !out_rgb || W == 0 || H == 0 || n == 0 || n > 255) return -1;
+    const uint64_t N = (uint64_t)W * H;
+    if (N >= (1ull << 31)) return -1;
+    for (unsigned l = 0; l < n; ++l) {
+        const ArapFlow_TexLayer& q = layers[l];
+        if (q.kind >= TEX_KINDS || !std::isfinite(q.p0) || !std::isfinite(q.p1)) return -1;
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(q.m[k])) return -1;
+    }
+    auto overlaps = [&](const void* in, uint64_t bytes) {               // [in, in + bytes) and out_rgb's 3 N bytes
+        const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out_rgb;
+        return in && a < o + 3 * N && o < a + bytes;
+    };
+    if (overlaps(rgb, 3 * N) || overlaps(masks_red, n * N)) return -1;
+    HC(hipSetDevice(st->device));
+    if (!st->tex && hipMalloc(&st->tex, 255 * sizeof(TexLayer)) != hipSuccess) return (int)hipErrorOutOfMemory;
+    HC(hipMemcpyAsync(st->tex, layers, n * sizeof(TexLayer), hipMemcpyHostToDevice, st->stream));   // (pageable: staged before the call returns)
+    hipLaunchKernelGGL(k_tex_fill, dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, st->stream, (const uint8_t*)rgb,
+                       (const uint8_t*)masks_red, (const TexLayer*)st->tex, (int)n, (uint8_t*)out_rgb, (int)W, (int)H);
     return (int)hipGetLastError();
 }
 

@@ -37,6 +37,7 @@
 #include "arap_mid.h"
 #include "arap_layers_step.h"
 #include "arap_bg.h"
+#include "arap_tex.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
 

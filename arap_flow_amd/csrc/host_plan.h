@@ -118,6 +118,7 @@ struct Opt_State {
     bool force_b8 = false;      // ARAPOPT_B8=1 (counter calibration): the 8-byte-per-lane form of phase B
     int stream_a = 0;           // ARAPOPT_STREAM_A=1 (experiments): the tiled k_pcg_a_grid instead of the marching kernel
     void* diag = nullptr;       // ArapFlow_WarpDiag: device, the call's WarpJob (256 bytes) and its accumulator; at first use
+    void* tex = nullptr;        // ArapFlow_Texture: device, the call's layer table (255 layers); at first use
 };
 
 struct Opt_Problem {

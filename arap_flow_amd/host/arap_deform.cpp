@@ -27,7 +27,12 @@
 // PREFIX_s00_occ.png, PREFIX_sII_occ.png) and frame 2, with the cameras mm= gives the in-between frames, and writes
 // PREFIX_OUT_sII.png, PREFIX_OUT_s00_step.flo, PREFIX_OUT_sII_step.flo and, with occ=, PREFIX_OUT_s00_occ.png, _sII_occ.png.
 // It answers "Done <first output: the places of out=, then occ_out, bwd_out, occ_bwd_out, then PREFIX_OUT_sI1.png>".
-// Either runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
+// A line whose first word is `tex` is the random-texture twin of one frame (DESIGN.md "Random textures"):
+//   tex RGB n MASK_1 FLO_1 ... MASK_n FLO_n t=<layer 1>;...;<layer n> [rgb1=P] [rgb2=P] [mask2=P]
+// (the layers of the frame's layers line; a layer of t= is 19 numbers, comma separated: kind, seed, the six of the map,
+// p0, p1, nine palette bytes; at least one output).  rgb1: frame 1 with a procedural texture on every layer's object;
+// rgb2 / mask2: its layered warp with the layers' flows, which are read only then.
+// Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
 // here consecutive frames of equal size are handed to the device-resident batched solver, as many as fit one launch
@@ -212,28 +217,73 @@ static bool run_layers_mid(Opt_State* state, const LayersSpec& q, const arapio::
     return ok && wrote;
 }
 
+// the files of a frame's layers, read once: the RGB, every layer's mask (red channel, [n][N]) and -- `with_flows` -- flow
+// ([n][N][2]); `form`: the line's first word, for the messages
+static bool read_layer_files(const char* form, const std::string& rgb_path, const std::vector<std::string>& mask_paths,
+                             const std::vector<std::string>& flow_paths, bool with_flows, arapio::Image& rgb,
+                             std::vector<uint8_t>& masks, std::vector<float>& flows)
+{
+    if (!read_png(rgb_path, rgb)) return false;
+    const int w = rgb.w, h = rgb.h;
+    const size_t N = (size_t)w * h, n = mask_paths.size();
+    masks.resize(n * N);
+    if (with_flows) flows.resize(n * N * 2);
+    for (size_t l = 0; l < n; ++l) {
+        arapio::Image msk;
+        if (!read_png(mask_paths[l], msk)) return false;
+        std::vector<float> fl;
+        int fw = w, fh = h;
+        if (with_flows && !arapio::read_flo(flow_paths[l], fl, fw, fh)) return fail("Could not read %s\n", flow_paths[l].c_str());
+        if (msk.w != w || msk.h != h || fw != w || fh != h)
+            return fail("%s: %s / %s differ in size from %s\n", form, mask_paths[l].c_str(), flow_paths[l].c_str(), rgb_path.c_str());
+        for (size_t i = 0; i < N; ++i) masks[l * N + i] = msk.rgb[3 * i];      // red channel
+        if (with_flows) memcpy(flows.data() + l * N * 2, fl.data(), N * 8);
+    }
+    return true;
+}
+
+// the random-texture twin of one frame, synchronously (pipeline.run_texture): read the layers' files once, one
+// ArapFlow_Texture on the state's stream and, if rgb2 or mask2 is wanted, one ArapFlow_WarpLayers on its result (the
+// retextured frame stays on the device), write the outputs asked for
+static bool run_texture(Opt_State* state, const TexSpec& q)
+{
+    const bool warp = !q.rgb2.empty() || !q.mask2.empty();
+    arapio::Image rgb;
+    std::vector<uint8_t> masks;
+    std::vector<float> flows;
+    if (!read_layer_files("tex", q.rgb, q.masks, q.flows, warp, rgb, masks, flows)) return false;
+    const int w = rgb.w, h = rgb.h;
+    const unsigned W = (unsigned)w, H = (unsigned)h, n = (unsigned)q.masks.size();
+    const size_t N = (size_t)w * h;
+    DeviceArena dev;
+    const size_t d_rgb = dev.stage(rgb.rgb.data(), 3 * N), d_msk = dev.stage(masks.data(), n * N);
+    const size_t d_flow = warp ? dev.stage(flows.data(), n * N * 8) : DeviceArena::kNone;
+    OutputTable out(dev, w, h);
+    const size_t o_rgb1 = out.add(FileKind::rgb, q.rgb1, true);            // the warp's input, written or not
+    const size_t o_rgb2 = out.add(FileKind::rgb, q.rgb2), o_msk2 = out.add(FileKind::mask1, q.mask2);
+    const size_t d_scr = warp ? dev.take(ArapFlow_WarpLayersScratchBytes(W, H, n)) : DeviceArena::kNone;
+    if (dev.alloc() != hipSuccess) return fail("tex: out of device memory\n");
+    void* const rgb1 = out.part(o_rgb1);
+    bool ok = dev.upload() == hipSuccess &&
+              ArapFlow_Texture(state, W, H, n, dev.at(d_rgb), dev.at(d_msk), q.tex.data(), rgb1) == 0;
+    if (ok && warp)
+        ok = ArapFlow_WarpLayers(state, W, H, n, rgb1, dev.at(d_msk), dev.at(d_flow), out.dev(o_rgb2), out.dev(o_msk2), nullptr,
+                                 nullptr, nullptr, dev.at(d_scr)) == 0;
+    ok = ok && hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
+    return ok ? out.write() : fail("ArapFlow_Texture failed\n");
+}
+
 // the layered warp of one frame, synchronously: read the layers' files, one ArapFlow_WarpLayers on the state's stream
 // (behind whatever solve is in flight there, never beside it), write the outputs asked for
 static bool run_layers(Opt_State* state, const LayersSpec& q)
 {
     arapio::Image rgb;
-    if (!read_png(q.rgb, rgb)) return false;
+    std::vector<uint8_t> masks;
+    std::vector<float> flows;
+    if (!read_layer_files("layers", q.rgb, q.masks, q.flows, true, rgb, masks, flows)) return false;
     const int w = rgb.w, h = rgb.h;
     const unsigned W = (unsigned)w, H = (unsigned)h, n = (unsigned)q.masks.size();
     const size_t N = (size_t)w * h;
-    std::vector<uint8_t> masks(n * N);
-    std::vector<float> flows(n * N * 2);
-    for (size_t l = 0; l < n; ++l) {
-        arapio::Image msk;
-        if (!read_png(q.masks[l], msk)) return false;
-        std::vector<float> fl;
-        int fw = 0, fh = 0;
-        if (!arapio::read_flo(q.flows[l], fl, fw, fh)) return fail("Could not read %s\n", q.flows[l].c_str());
-        if (msk.w != w || msk.h != h || fw != w || fh != h)
-            return fail("layers: %s / %s differ in size from %s\n", q.masks[l].c_str(), q.flows[l].c_str(), q.rgb.c_str());
-        for (size_t i = 0; i < N; ++i) masks[l * N + i] = msk.rgb[3 * i];      // red channel
-        memcpy(flows.data() + l * N * 2, fl.data(), N * 8);
-    }
     if (!q.mid.steps.empty() && !run_layers_mid(state, q, rgb, masks, flows)) return false;
     if (q.occ.empty() && q.bwd.empty() && q.occ_bwd.empty() && q.rgb2.empty() && q.mask2.empty()) return true;
     DeviceArena dev;
@@ -423,7 +473,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -698,8 +748,10 @@ int main(int argc, const char* argv[])
                 if (!lanes.flush(L, other)) { rc = 1; break; }
                 writer.finish();
             }
-            const bool is_bg = fr->item.kind == Item::Kind::Bg;
-            if (!(is_bg ? run_background(state, fr->item.bg) : run_layers(state, fr->item.layers))) { rc = 1; break; }
+            const Item::Kind kind = fr->item.kind;
+            if (!(kind == Item::Kind::Bg    ? run_background(state, fr->item.bg)
+                  : kind == Item::Kind::Tex ? run_texture(state, fr->item.tex)
+                                            : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;
         }

@@ -105,6 +105,7 @@ class OutputTable {
     }
     void set_path(size_t row, const std::string& path) { if (rows_[row].part != DeviceArena::kNone) rows_[row].path = path; }
     void* dev(size_t row) const { return rows_[row].path.empty() ? nullptr : arena_.at(rows_[row].part); }
+    void* part(size_t row) const { return arena_.at(rows_[row].part); }       // a kept row's memory, named or not
     hipError_t download()                                  // every wanted row, once the call has been waited for
     {
         hipError_t e = hipSuccess;

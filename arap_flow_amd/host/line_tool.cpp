@@ -30,6 +30,19 @@ static std::string canonical(const Item& it)
         for (size_t l = 0; l < q.masks.size(); ++l) { c.word(q.masks[l]); c.word(q.flows[l]); }
         c.token("occ", q.occ); c.token("bwd", q.bwd); c.token("occ_bwd", q.occ_bwd); c.token("rgb2", q.rgb2);
         c.token("mask2", q.mask2); c.token("mid", q.mid.text);
+    } else if (it.kind == Item::Kind::Tex) {
+        const TexSpec& q = it.tex;
+        c.word("tex"); c.word(q.rgb); c.word(std::to_string(q.masks.size()));
+        for (size_t l = 0; l < q.masks.size(); ++l) { c.word(q.masks[l]); c.word(q.flows[l]); }
+        std::string t;
+        for (const ArapFlow_TexLayer& L : q.tex) {
+            char num[512];
+            snprintf(num, sizeof(num), "%s%u,%u,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%u,%u,%u,%u,%u,%u,%u,%u,%u", t.empty() ? "" : ";",
+                     L.kind, L.seed, L.m[0], L.m[1], L.m[2], L.m[3], L.m[4], L.m[5], L.p0, L.p1, L.c0[0], L.c0[1], L.c0[2],
+                     L.c1[0], L.c1[1], L.c1[2], L.c2[0], L.c2[1], L.c2[2]);
+            t += num;
+        }
+        c.token("t", t); c.token("rgb1", q.rgb1); c.token("rgb2", q.rgb2); c.token("mask2", q.mask2);
     } else {
         const BgSpec& q = it.bg;
         c.word("bg");

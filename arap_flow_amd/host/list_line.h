@@ -8,8 +8,12 @@
 //   bg line:      bg BG RGB1 MASK1 RGB2 MASK2 FLOW m=<12 numbers> [mid=I1,..,In:PREFIX mm=<6n numbers>] [occ=IN] [bwd=IN]
 //                 [occ_bwd=IN] out=RGB1_OUT,RGB2_OUT,FLOW_OUT [occ_out=P] [bwd_out=P] [occ_bwd_out=P] [mid_out=PREFIX_OUT]
 //                 mid=, mm= and mid_out= come together
-//                 on these two any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   tex line:     tex RGB1 n MASK_1 FLO_1 ... MASK_n FLO_n t=<layer 1>;...;<layer n> [rgb1=P] [rgb2=P] [mask2=P]
+//                 a layer: 19 numbers, comma separated: kind, seed, the six of m, p0, p1, nine palette bytes
+//                 (pipeline.TexLine); a repeated key is an error too
+//                 on these three any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
@@ -77,7 +81,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the three forms
+// ---- the four forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -114,17 +118,29 @@ struct BgSpec {                            // pipeline.BgLine
     }
 };
 
+struct TexSpec {                           // pipeline.TexLine
+    std::string rgb;
+    std::vector<std::string> masks, flows;
+    std::vector<ArapFlow_TexLayer> tex;    // one per layer
+    std::string rgb1, rgb2, mask2;         // outputs (empty: not wanted)
+    std::string first_out;                 // the value of the first output token in line order: what --serve reports
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
+    TexSpec tex;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
 inline std::string done_path(const Item& it)
 {
-    return it.kind == Item::Kind::Solve ? it.solve.flow : it.kind == Item::Kind::Layers ? it.layers.first_out : it.bg.first_out();
+    return it.kind == Item::Kind::Solve    ? it.solve.flow
+           : it.kind == Item::Kind::Layers ? it.layers.first_out
+           : it.kind == Item::Kind::Tex    ? it.tex.first_out
+                                           : it.bg.first_out();
 }
 
 enum class Parsed { Skip, Bad, Good };     // Skip: none of the forms; Bad: a form, refused
@@ -217,19 +233,95 @@ inline bool parse_bg(std::istringstream& tok, BgSpec& q)
     return have_m && !q.first_out().empty();
 }
 
+// 1 to 10 decimal digits, nothing else, at most `max`
+inline bool parse_uint(const std::string& v, unsigned long long max, unsigned long long& x)
+{
+    if (v.empty() || v.size() > 10) return false;
+    x = 0;
+    for (char c : v) {
+        if (c < '0' || c > '9') return false;
+        x = 10 * x + (unsigned long long)(c - '0');
+    }
+    return x <= max;
+}
+
+// one layer of t=: 19 numbers, comma separated (pipeline.TexLayer); the floats finite
+inline bool parse_tex_layer(const std::string& v, ArapFlow_TexLayer& q)
+{
+    std::vector<std::string> f(1);
+    for (char c : v) {
+        if (c == ',') f.emplace_back();
+        else f.back() += c;
+    }
+    if (f.size() != 19) return false;
+    unsigned long long x = 0;
+    if (!parse_uint(f[0], ARAPFLOW_TEX_WAVE, x)) return false;
+    q.kind = (uint32_t)x;
+    if (!parse_uint(f[1], 0xffffffffull, x)) return false;
+    q.seed = (uint32_t)x;
+    float fl[8];
+    for (int k = 0; k < 8; ++k)
+        if (!parse_bg_maps(f[2 + k], fl + k, 1) || !std::isfinite(fl[k])) return false;
+    for (int k = 0; k < 6; ++k) q.m[k] = fl[k];
+    q.p0 = fl[6]; q.p1 = fl[7];
+    uint8_t* const cols[3] = {q.c0, q.c1, q.c2};
+    for (int k = 0; k < 9; ++k) {
+        if (!parse_uint(f[10 + k], 255, x)) return false;
+        cols[k / 3][k % 3] = (uint8_t)x;
+    }
+    q.reserved[0] = q.reserved[1] = q.reserved[2] = 0;
+    return true;
+}
+
+inline bool parse_tex(std::istringstream& tok, TexSpec& q)
+{
+    std::string count;
+    unsigned long long n = 0;
+    if (!(tok >> q.rgb >> count) || !parse_uint(count, 255, n) || n < 1) return false;
+    for (unsigned long long l = 0; l < n; ++l) {
+        std::string m, f;
+        if (!(tok >> m >> f)) return false;
+        q.masks.push_back(m);
+        q.flows.push_back(f);
+    }
+    std::string k, v;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "t") {
+            if (!q.tex.empty()) return false;
+            size_t at = 0;
+            for (;;) {                     // layers separated by `;`
+                const size_t semi = v.find(';', at);
+                ArapFlow_TexLayer layer;
+                if (!parse_tex_layer(v.substr(at, semi == std::string::npos ? semi : semi - at), layer)) return false;
+                q.tex.push_back(layer);
+                if (semi == std::string::npos) break;
+                at = semi + 1;
+            }
+            if (q.tex.size() != n) return false;
+        } else if (std::string* dst = field_of({{"rgb1", &q.rgb1}, {"rgb2", &q.rgb2}, {"mask2", &q.mask2}}, k)) {
+            if (!dst->empty()) return false;
+            *dst = v;
+            if (q.first_out.empty()) q.first_out = v;
+        } else return false;
+    }
+    return !q.tex.empty() && !q.first_out.empty();
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
     std::istringstream tok(line);
     std::string first;
     if (!(tok >> first)) return Parsed::Skip;
-    it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : Item::Kind::Solve;
+    it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
+    else if (it.kind == Item::Kind::Tex) p = parse_tex(tok, it.tex) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
-        const char* const what[] = {"mid= token", "layers line", "bg line"};      // by Item::Kind
+        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

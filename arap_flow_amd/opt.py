@@ -486,12 +486,13 @@ def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, 
     """One ArapFlow_<name> call on host arrays.  `dims`: (W, H) or (W, H, n); `inputs`: (array or None, dtype) and
     `outputs`: (dict key, shape or None = not asked, torch dtype), both in the library's argument order; `scratch`: the
     name of the *ScratchBytes function of a call that takes a scratch buffer; `lead`: arguments between the dims and
-    the inputs, an (array, dtype) to upload or a value passed as it is.  An input that is a list of arrays, or an
+    the inputs, an (array, dtype) to upload or a value passed as it is; an input (value, None) is passed as it is too (a
+    host table among the device buffers).  An input that is a list of arrays, or an
     output whose shape is a list of shapes, is passed as a host array of device pointers and comes back as a list.
     Uploads, allocates, synchronises, calls, and downloads {key: array} of the outputs asked.  A return code of -1 is a
     ValueError where `bad_args`, every other non-zero code a RuntimeError."""
     lib = state.lib
-    up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
+    up = lambda a, dt: a if a is None or dt is None else torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
     new = lambda shape, dt: None if shape is None else torch.empty(*shape, dtype=dt, device="cuda")
     lead = [up(*a) if isinstance(a, tuple) else a for a in lead]
     args = [[up(x, dt) for x in a] if isinstance(a, list) else up(a, dt) for a, dt in inputs]
@@ -602,6 +603,48 @@ def warp_diag(state, mask_red, flow, fold=True):
     r = _warp_call(state, "WarpDiag", (W, H), [(mask_red, np.uint8), (flow, np.float32)],
                    [("fold", (H, W) if fold else None, torch.uint8), ("stats", (C.sizeof(capi.MeshStats),), torch.uint8)])
     return dict(stats=_stats_dict(capi.MeshStats.from_buffer_copy(r["stats"].tobytes())), fold=r.get("fold"))
+
+
+def tex_table(layers):
+    """a sequence of layer descriptions (kind, seed, m[6], p0, p1, c0, c1, c2) -- pipeline.TexLayer, the kind a number or a
+    name of capi.TEX_KINDS -- as the ArapFlow_TexLayer array the library reads; floats are rounded to float32 here"""
+    table = (capi.TexLayer * max(1, len(layers)))()
+    for q, (kind, seed, m, p0, p1, c0, c1, c2) in zip(table, layers):
+        q.kind = capi.TEX_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+        q.seed = int(seed) & 0xffffffff
+        q.m = _map6(m)
+        q.p0, q.p1 = float(p0), float(p1)
+        for dst, c in ((q.c0, c0), (q.c1, c1), (q.c2, c2)):
+            dst[:] = [int(v) for v in c]
+    return table
+
+
+def texture(state, rgb, masks, layers):
+    """procedural textures on the objects of a frame (ArapFlow_Texture, DESIGN.md "Random textures").  rgb u8[H,W,3];
+    masks u8[n,H,W] (red channels, 0 = object; the higher index on top) or None: every pixel belongs to layer 0; layers:
+    n descriptions (tex_table) -> the retextured frame u8[H,W,3]: a pixel of a layer shows that layer's texture, every
+    other pixel rgb."""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("texture: rgb [H,W,3] expected")
+    H, W = rgb.shape[:2]
+    if masks is not None:
+        masks = np.ascontiguousarray(masks, np.uint8)
+        if masks.ndim != 3 or masks.shape[1:] != (H, W) or len(masks) != len(layers):
+            raise ValueError("texture: masks [n,H,W] with one layer description each expected")
+    r = _warp_call(state, "Texture", (W, H, len(layers)), [(rgb, np.uint8), (masks, np.uint8), (tex_table(layers), None)],
+                   [("rgb", (H, W, 3), torch.uint8)])
+    return r["rgb"]
+
+
+def retexture_pair(state, rgb, masks, flows, layers):
+    """the random-texture twin of a pair (DESIGN.md "Random textures"): texture() on frame 1, then the layered warp of the
+    retextured frame with the pair's ALREADY SOLVED flows -- no solve, no new rasteriser.  rgb u8[H,W,3], masks u8[n,H,W],
+    flows f32[n,H,W,2], layers: n descriptions -> (rgb1_tex, rgb2_tex, mask2); mask2 is the warped mask of the original
+    pair (same flows, same geometry), and with n = 1 rgb2_tex is warp_image of rgb1_tex."""
+    rgb1 = texture(state, rgb, masks, layers)
+    r = warp_layers(state, rgb1, masks, flows, occ=False)
+    return rgb1, r["warped_rgb"], r["warped_mask"]
 
 
 BG_OUTPUTS = ("out_rgb1", "out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")

@@ -13,6 +13,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   cover_scale, fit_bg, add_bg            para_gen.py:36-61      (background compositing)
   BgLine, parse_bg, bg_line, run_background, fit_bg_window, bg_maps    the `bg` line: moving background (addition)
   mid_bg_files, bg_maps_seq, run_background_seq    its mid= / mm= / mid_out= tokens: the camera per in-between frame (addition)
+  TexLayer, TexLine, parse_tex, tex_line, tex_layers, run_texture    the `tex` line: the random-texture twin (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
@@ -20,9 +21,12 @@ functions that tests/golden/host/ pins with hand-computed cases:
   make_arap_path, replace_ext            para_gen.py:318-339
 No oracle import; the solve and the rasteriser run on the GPU through arap_flow_amd.opt.
 """
+import colorsys
+import math
 import os
 import os.path as osp
 import random as rn
+import re
 from typing import NamedTuple
 
 import numpy as np
@@ -39,7 +43,8 @@ _ANTIALIAS = getattr(Image, "LANCZOS", None) or Image.ANTIALIAS   # Image.ANTIAL
 # arap_deform
 # ------------------------------------------------------------------------------------------------------
 # A list line is the unit of work between para_gen.py, arap_deform.py and `arap_deform --serve` (C++ twin: parse_item in
-# host/arap_deform.cpp).  It is a solve line, SolveLine, a `layers` line, the dict of parse_layers, or a `bg` line, BgLine;
+# host/arap_deform.cpp).  It is a solve line, SolveLine, a `layers` line, the dict of parse_layers, a `bg` line, BgLine, or a
+# `tex` line, TexLine;
 # parse_line reads any of them from text, format_line writes it back, done_token is the path a worker reports it done by.
 EXTRA_KEYS = ("bwd", "occ", "occ_bwd", "mid", "diag", "fold")
 MAX_SNAPSHOTS = 8            # ARAPFLOW_MAX_SNAPSHOTS of include/arap_opt.h
@@ -48,6 +53,9 @@ LAYER_KEYS = ("occ", "bwd", "occ_bwd", "rgb2", "mask2", "mid")
 BG_WORD = "bg"
 BG_IN_KEYS = ("occ", "bwd", "occ_bwd")                               # optional object-side inputs of a bg line
 BG_OUT_KEYS = ("occ_out", "bwd_out", "occ_bwd_out")                  # the full maps made from them
+TEX_WORD = "tex"
+TEX_KEYS = ("rgb1", "rgb2", "mask2")
+TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")         # ARAPFLOW_TEX_*: a kind's number is its index
 
 
 class SolveLine(NamedTuple):
@@ -271,10 +279,157 @@ def bg_outputs(item):
     return files
 
 
+class TexLayer(NamedTuple):
+    """one layer's procedural texture (ArapFlow_TexLayer, DESIGN.md "Random textures"): kind, a number (index of
+    TEX_KINDS); seed, 32 bits; m, six float32 (pixel -> texture point); p0, p1 float32; c0, c1, c2, RGB bytes"""
+    kind: int
+    seed: int
+    m: tuple
+    p0: float
+    p1: float
+    c0: tuple
+    c1: tuple
+    c2: tuple
+
+
+class TexLine(NamedTuple):
+    """a `tex` line (DESIGN.md "Random textures"), recognised by its first word: the random-texture twin of one frame
+        tex RGB1 n MASK_1 FLO_1 ... MASK_n FLO_n t=<layer 1>;...;<layer n> [rgb1=P] [rgb2=P] [mask2=P]
+    The layers are those of the frame's `layers` line (the later on top).  A layer of t= is 19 numbers, comma separated:
+    kind, seed, the six of m, p0, p1 (floats written with %.9g), then the nine palette bytes c0, c1, c2.  rgb1: the
+    retextured frame 1; rgb2 / mask2: its layered warp with the layers' flows.  `out`: {key: path} in line order.  At
+    least one output; anything else -- an unknown or repeated key, a missing `=`, an empty value, a wrong count of numbers
+    -- is an error."""
+    rgb: str
+    layers: list
+    tex: tuple
+    out: dict
+
+
+_UINT = re.compile(r"[0-9]{1,10}$")
+
+
+def _tex_layer(text):
+    q = text.split(",")
+    if len(q) != 19 or not all(_UINT.match(v) for v in q[:2] + q[10:]):
+        return None
+    ints = [int(v) for v in q[:2] + q[10:]]
+    with np.errstate(over="ignore"):            # (a number beyond float32 becomes inf, refused below)
+        fl = _bg_numbers(",".join(q[2:10]))
+    if len(fl) != 8 or not all(math.isfinite(v) for v in fl):
+        return None
+    if ints[0] >= len(TEX_KINDS) or ints[1] > 0xffffffff or max(ints[2:]) > 255:
+        return None
+    return TexLayer(ints[0], ints[1], fl[:6], fl[6], fl[7], tuple(ints[2:5]), tuple(ints[5:8]), tuple(ints[8:11]))
+
+
+def parse_tex(tokens):
+    if len(tokens) < 3 or tokens[0] != TEX_WORD:
+        raise ValueError("not a tex line: %r" % " ".join(tokens))
+    try:
+        n = int(tokens[2]) if _UINT.match(tokens[2]) else 0
+    except ValueError:
+        n = 0
+    if not 1 <= n <= 255 or len(tokens) < 3 + 2 * n:
+        raise ValueError("tex line: 1..255 layers, a mask and a flow each: %r" % " ".join(tokens))
+    out, tex = {}, None
+    for t in tokens[3 + 2 * n:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and (k == "t" or k in TEX_KEYS)) or k in out or (k == "t" and tex is not None):
+            raise ValueError("tex line: bad or repeated token %r" % t)
+        if k == "t":
+            tex = tuple(_tex_layer(q) for q in v.split(";"))
+            if len(tex) != n or None in tex:
+                raise ValueError("tex line: t= takes %d layers of 19 numbers: %r" % (n, t))
+        else:
+            out[k] = v
+    if tex is None:
+        raise ValueError("tex line without t=: %r" % " ".join(tokens))
+    if not out:
+        raise ValueError("tex line without an output: %r" % " ".join(tokens))
+    return TexLine(tokens[1], [(tokens[3 + 2 * l], tokens[4 + 2 * l]) for l in range(n)], tex, out)
+
+
+def tex_line(item):
+    """the inverse of parse_tex: t=, then the outputs in the order of TEX_KEYS"""
+    tok = [TEX_WORD, item.rgb, str(len(item.layers))] + [p for pair in item.layers for p in pair]
+    nums = lambda q: ["%d" % q.kind, "%d" % q.seed] + ["%.9g" % float(np.float32(v)) for v in tuple(q.m) + (q.p0, q.p1)] + \
+        ["%d" % c for c in tuple(q.c0) + tuple(q.c1) + tuple(q.c2)]
+    tok.append("t=" + ";".join(",".join(nums(q)) for q in item.tex))
+    return " ".join(tok + ["%s=%s" % (k, item.out[k]) for k in TEX_KEYS if item.out.get(k)])
+
+
+TEX_CELL_MIN = 4.0           # pixels: a cell this small still survives the warp's resampling
+
+
+def tex_layers(rng, n, frame_wh):
+    """para_gen --retex: one TexLayer per segment, drawn from `rng` (a random.Random; the same state gives the same
+    layers).  Per layer, in this order: the kind, the seed, the cell size in pixels -- log-uniform between TEX_CELL_MIN
+    and a third of the frame's short side (at least TEX_CELL_MIN), so the pattern survives the warp and an object never
+    comes out flat --, the rotation, the aspect ratio (bricks: 2 .. 3 cells wide; drawn for every kind), the offset in
+    cells, the two parameters, and three colours (hue, saturation, value), in the spirit of the reference's random_color;
+    c1 is redrawn while it equals c0.  The map is computed in double and rounded once to float32."""
+    W, H = frame_wh
+    hi = max(TEX_CELL_MIN, min(W, H) / 3.0)
+
+    def colour():
+        r, g, b = colorsys.hsv_to_rgb(rng.uniform(0, 1), rng.uniform(0, 1), rng.uniform(0.5, 1))
+        return (int(r * 255 + 0.5), int(g * 255 + 0.5), int(b * 255 + 0.5))
+    out = []
+    for _ in range(n):
+        kind = rng.randrange(len(TEX_KINDS))
+        seed = rng.getrandbits(32)
+        size = math.exp(rng.uniform(math.log(TEX_CELL_MIN), math.log(hi)))
+        rot = rng.uniform(0, 2 * math.pi)
+        aspect = rng.uniform(2, 3)
+        ou, ov = rng.uniform(-8, 8), rng.uniform(-8, 8)
+        q0, q1 = rng.uniform(0, 1), rng.uniform(0, 1)
+        c0, c1, c2 = colour(), colour(), colour()
+        while c1 == c0:
+            c1 = colour()
+        su = size * aspect if TEX_KINDS[kind] == "brick" else size
+        co, si = math.cos(rot), math.sin(rot)
+        m = (co / su, si / su, ou, -si / size, co / size, ov)
+        p0 = p1 = 0.0
+        if TEX_KINDS[kind] == "brick":
+            p0, p1 = 0.04 + 0.08 * q0, 0.3 + 0.4 * q1       # mortar width, shift of odd rows
+        elif TEX_KINDS[kind] == "wave":
+            p0, p1 = 0.2 + 0.8 * q0, float(q1 >= 0.5)       # amplitude of the bend, triangle or saw
+        f32 = lambda v: float(np.float32(v))
+        out.append(TexLayer(kind, seed, tuple(f32(v) for v in m), f32(p0), f32(p1), c0, c1, c2))
+    return out
+
+
+def run_texture(state, spec):
+    """one `tex` line: read the frame's RGB and every layer's mask (and, for rgb2 / mask2, flow) once, one opt.texture
+    and, if rgb2 or mask2 is wanted, one opt.warp_layers on its result; write what the line asks for (rgb1, rgb2: RGB
+    PNG; mask2: 1-bit PNG as a solve's warped mask)"""
+    from . import opt
+    rgb = load_rgb(spec.rgb)
+    masks = np.stack([load_mask_red(m) for m, _ in spec.layers])
+    if masks.shape[1:] != rgb.shape[:2]:
+        raise ValueError("tex line: image and mask sizes differ")
+    out = spec.out
+    rgb1 = opt.texture(state, rgb, masks, spec.tex)
+    if "rgb1" in out:
+        Image.fromarray(rgb1).save(out["rgb1"])
+    if "rgb2" in out or "mask2" in out:
+        flows = np.stack([flo.flow_read(f) for _, f in spec.layers])
+        if flows.shape[1:3] != rgb.shape[:2]:
+            raise ValueError("tex line: image and flow sizes differ")
+        r = opt.warp_layers(state, rgb1, masks, flows, occ=False)
+        if "rgb2" in out:
+            Image.fromarray(r["warped_rgb"]).save(out["rgb2"])
+        if "mask2" in out:
+            save_mask(r["warped_mask"], out["mask2"])
+
+
 def parse_line(line):
-    """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, or a
-    BgLine when it is `bg`"""
+    """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
+    BgLine when it is `bg`, a TexLine when it is `tex`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == TEX_WORD:
+        return parse_tex(tok)
     if tok and tok[0] == LAYERS_WORD:
         return parse_layers(tok)
     if tok and tok[0] == BG_WORD:
@@ -290,14 +445,18 @@ def format_line(item):
         return " ".join(list(item[:6]) + extra_tokens(item.extra))
     if isinstance(item, BgLine):
         return bg_line(item)
+    if isinstance(item, TexLine):
+        return tex_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
-    first of a bg line's bg_outputs"""
+    first of a bg line's bg_outputs, a tex line's first output token"""
     if isinstance(item, BgLine):
         return bg_outputs(item)[0]
+    if isinstance(item, TexLine):
+        return next(iter(item.out.values()))
     return item.flow if isinstance(item, SolveLine) else next(iter(item["out"].values()))
 
 

@@ -418,6 +418,40 @@ int ArapFlow_BackgroundSeq(Opt_State* state, unsigned W, unsigned H, const void*
                            const void* const* rgbs, const void* const* flows, const void* const* occs,
                            void* const* out_rgbs, void* const* out_flows, void* const* out_occs);
 
+/* Random textures (DESIGN.md "Random textures"): one procedural texture per layer of a frame, for the random-texture twin
+ * of a pair.  A layer's texture is a pure function of the pixel, the layer's seed and these few parameters:
+ *   kind        one of ARAPFLOW_TEX_*
+ *   seed        of the layer's hash; any value
+ *   m           six floats (a, b, c, d, e, f), pixel -> texture point as in ArapFlow_BackgroundMaps: pixel (x, y) shows
+ *               the point (u, v) = (a x + b y + c, d x + e y + f); one texture cell is one unit of (u, v)
+ *   p0, p1      BRICK: the mortar's width as a fraction of a cell, the shift of odd rows in cells; WAVE: the amplitude of
+ *               the noise that bends the bands, in cells, and the profile (p1 < 0.5: saw, else triangle); else unused
+ *   c0, c1, c2  the palette, RGB: CHECKER c0 / c1; BRICK c0 / c1 bricks, c2 mortar; VORONOI and WAVE between c0 and c1;
+ *               NOISE the ramp c0 -> c1 -> c2
+ *   reserved    not read */
+enum { ARAPFLOW_TEX_CHECKER = 0, ARAPFLOW_TEX_BRICK = 1, ARAPFLOW_TEX_VORONOI = 2, ARAPFLOW_TEX_NOISE = 3,
+       ARAPFLOW_TEX_WAVE = 4 };
+typedef struct ArapFlow_TexLayer {
+    uint32_t kind, seed;
+    float m[6];
+    float p0, p1;
+    uint8_t c0[3], c1[3], c2[3], reserved[3];
+} ArapFlow_TexLayer;
+
+/* Retexture the objects of a frame, on DEVICE buffers (layers: HOST, n entries): rgb uint8[H][W][3], masks_red
+ * uint8[n][H][W] (0 = object, the layers of ArapFlow_WarpLayers in the same order; NULL: every pixel belongs to layer 0)
+ * -> out_rgb uint8[H][W][3].  A pixel belongs to the HIGHEST layer index whose mask is 0 there -- the layered warp's
+ * stacking order -- and gets that layer's texture colour; a pixel of no layer gets rgb's bytes.  The result is a function
+ * of the arguments alone: two runs give identical bytes, and a layer's pixels do not depend on the other layers'
+ * descriptions.  Warping out_rgb with the frame's solved flows (ArapFlow_Warp / WarpLayers) gives the twin's second
+ * frame; the flows are shared.  Needs no scratch beyond the layer table (52 bytes a layer), which the state allocates at
+ * the first call and the call copies before it returns.  Asynchronous on the state's stream.  Returns 0; -1, and nothing
+ * is launched or written, on bad arguments: a null state, rgb, layers or out_rgb, n = 0 or n > 255, a zero size,
+ * W * H >= 2^31, an unknown kind, a non-finite map coefficient or parameter, or out_rgb overlapping rgb or masks_red;
+ * else a HIP error code. */
+int ArapFlow_Texture(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                     const ArapFlow_TexLayer* layers, void* out_rgb);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised

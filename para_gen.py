@@ -3,7 +3,7 @@
 
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
                      [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
-                     [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]] [--diag] [--max_fold FRAC]
+                     [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]] [--diag] [--max_fold FRAC] [--retex]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -44,6 +44,13 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     and all_files_ext.list when a triangle went non-finite or more than FRAC of them folded, and names it in
     OUT/rejected.list instead (`rgb1 rgb2 flow folded triangles nonfinite`); its files stay.  The lists are decided from
     the Diag files on disk (write_lists), so a --resume run writes the same ones.
+  * --retex writes the random-texture twin of every kept pair (DESIGN.md "Random textures"; the reference's D15OM beside
+    its D15RM): OUT/inpRGB_tex/<seq>/<frame>.png, frame 1 with a procedural texture on every object (with --multseg one per
+    segment), and OUT/wRGB_tex/<seq>/<frame>.png, its warp with the pair's already solved flows, from one `tex` line per
+    pair, handed to a worker once the pair's solves (and layers line) are done and before the segments are merged.  The
+    twin costs no solve and shares the pair's Flow file: OUT/all_files_tex.list names `inpRGB_tex wRGB_tex Flow`.  With
+    --bg_dir the twin gets the pair's background; with --bg_motion its warped frame goes through a second bg line with the
+    same maps.  The textures are drawn from a random.Random seeded with the pair's id, so a rerun reproduces them.
 """
 import argparse
 import json
@@ -71,6 +78,7 @@ from arap_flow_amd import pipeline          # noqa: E402
 orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen.py:18-26
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
+color_tex_dir, wrgb_tex_dir = "inpRGB_tex", "wRGB_tex"           # --retex: the random-texture twin (addition)
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
 diag_dir, fold_dir = "Diag", "Fold"     # --diag: fold diagnostics (addition)
 mid_full_dir = "MidFull"           # --mid_bg: the in-between frames and links with the moving background (addition)
@@ -187,6 +195,8 @@ class Frame:
     motion: object = None          # --bg_motion: the pair's bg line (pipeline.BgLine), handed out after finish_frame
     stage: str = "solves"          # main: what the workers hold of this frame: solves -> layers -> bg
     tmp: tuple = ()                # --bg_motion: the bg line's own input files, deleted when it is done
+    tex: object = None             # --retex: the pair's tex line (pipeline.TexLine), handed out before finish_frame
+    motion_tex: object = None      # --retex --bg_motion: the twin's bg line, handed out after the pair's
 
     @property
     def solves(self):
@@ -203,6 +213,7 @@ def prepare_pair(args):
     p.pop("_mid", None)
     midbg, midbg_out = p.pop("_midbg", None), p.pop("midbg_gen", None)      # --mid_bg: the snapshot steps, the output prefix
     midl = p.pop("_midl", None)                 # --mid_layers: the snapshot steps of every segment's solve
+    tex1, tex2 = p.pop("rgb1tex_gen", None), p.pop("rgb2tex_gen", None)     # --retex: the twin's two frames
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
     im1, mk1, im2, mk2 = preprocess(p, flags.size)
@@ -260,6 +271,14 @@ def prepare_pair(args):
             out["mid"] = pipeline.mid_token(midl, p["midl_gen"])
         layers = dict(rgb=line.rgb, layers=[(sg.mask, sg.flow) for sg in segs], out=out)
     rec = Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
+    if tex1 is not None:                        # the twin: one texture per solved layer, from the pair's own generator
+        for q in (tex1, tex2):
+            os.makedirs(osp.dirname(q), exist_ok=True)
+        solved = rec.solves
+        H, W = im1.shape[:2]
+        rng_tex = rn.Random(_pair_id(seq, stem))
+        rec.tex = pipeline.TexLine(line.rgb, [(sg.mask, sg.flow) for sg in solved],
+                                   tuple(pipeline.tex_layers(rng_tex, len(solved), (W, H))), dict(rgb1=tex1, rgb2=tex2))
     if big is not None:
         # the bg line's own inputs, beside the pair's constraints: the enlarged picture as a PNG (the worker's codec),
         # with --multseg the union mask (object where any solved segment is object), and the line itself
@@ -284,6 +303,9 @@ def prepare_pair(args):
                                      m=tuple(float(v) for v in np.concatenate([M1, M2])), inputs=inputs,
                                      out=("", line.out_rgb, p["flowfull_gen"]), outs=outs, **tokens)
         open(stem_tmp + "_bg.txt", "w").write(pipeline.format_line(rec.motion))
+        if rec.tex is not None:                 # the twin's warped frame over the same moving background; frame 1 has it
+            rec.motion_tex = pipeline.BgLine(rec.bg, tex1, mask1, tex2, line.out_mask, line.flow, m=rec.motion.m, inputs={},
+                                             out=("", tex2, ""), outs={})
         rec.tmp = tuple(q for q in (rec.bg, mask1 if segs is not None else None, stem_tmp + "_bg.txt") if q)
     return rec
 
@@ -315,6 +337,9 @@ def finish_frame(rec):
         im = np.array(Image.open(rec.line.out_rgb).convert("RGB"))
         m = np.array(Image.open(rec.line.out_mask))
         Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(rec.line.out_rgb)
+        if rec.tex is not None:                             # the twin's warped frame: the same background, the same mask
+            im = np.array(Image.open(rec.tex.out["rgb2"]).convert("RGB"))
+            Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(rec.tex.out["rgb2"])
         if "mid" in rec.line.extra:                         # the in-between frames get the pair's background too
             steps, prefix = pipeline.parse_mid(rec.line.extra["mid"])
             for f in (pipeline.mid_files(prefix, i) for i in steps):
@@ -491,6 +516,7 @@ def scan(flags, input_root, output_root):
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
+                                                           tx1=color_tex_dir, tx2=wrgb_tex_dir,
                                                            obw=occ_bwd_dir, occ=occ_dir, dia=diag_dir, fol=fold_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
                                                            ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
@@ -523,6 +549,8 @@ def scan(flags, input_root, output_root):
                     e[LAYERS_OCC] = osp.join(roots["occ"], seq, f + ".png")
                 if getattr(flags, "mid", 0):
                     e["mid_gen"] = osp.join(roots["mid"], seq, f)
+                if getattr(flags, "retex", False):
+                    e.update(rgb1tex_gen=osp.join(roots["tx1"], seq, f + ".png"), rgb2tex_gen=osp.join(roots["tx2"], seq, f + ".png"))
                 if getattr(flags, "bg_motion", None) is not None:       # the full-frame maps of what the run asks for
                     e["flowfull_gen"] = osp.join(roots["ful"], seq, f + ".flo")
                     if "occ_gen" in e or LAYERS_OCC in e:
@@ -607,6 +635,11 @@ def write_lists(flags, output_root, all_paths):
         open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     if max_fold is not None:
         open(osp.join(output_root, "rejected.list"), "w").write("\n".join(rejected))
+    if getattr(flags, "retex", False):                     # the twins of the listed pairs: their own frames, the SAME flow
+        by_trio = {" ".join(pipeline.make_arap_path(p)[k] for k in (0, 4, 3)): p for p in all_paths}
+        twins = [[by_trio[t]["rgb1tex_gen"], by_trio[t]["rgb2tex_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
+        open(osp.join(output_root, "all_files_tex.list"), "w").write(
+            "\n".join(" ".join(t) for t in twins if all(osp.exists(q) for q in t)))
     return out_paths, rejected
 
 
@@ -639,7 +672,7 @@ def main(flags):
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
     frames = {}                                        # done token of a line a worker holds -> its Frame
     posts, lock = [], threading.Lock()
-    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0)
+    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0)
 
     def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
         frames[pipeline.done_token(item)] = rec
@@ -653,14 +686,21 @@ def main(flags):
     def on_done(path):                                 # a worker thread: one solve (or one layers / bg line) finished
         with lock:
             rec = frames.pop(path)
-            if rec.stage == "bg":                      # its bg line: the frame is complete
+            if rec.stage == "bg" and rec.motion_tex is not None:    # its bg line: now the twin's, over the same inputs
                 counts["bg_done"] += 1
+                rec.stage = "bg_tex"
+                hand_out(rec, rec.motion_tex, workers.put_owed)
+                return
+            if rec.stage in ("bg", "bg_tex"):          # its (last) bg line: the frame is complete
+                counts["bg_done" if rec.stage == "bg" else "tex_done"] += 1
                 if rec.remove:
                     for q in rec.tmp:
                         if osp.exists(q):
                             os.remove(q)
                 return
-            if rec.stage == "layers":                  # its layers line: the segment files may go now
+            if rec.stage == "tex":                     # its tex line: the segment files may go now
+                counts["tex_done"] += 1
+            elif rec.stage == "layers":                # its layers line
                 counts["layers_done"] += 1
             else:
                 counts["solves_done"] += 1
@@ -671,6 +711,10 @@ def main(flags):
                     rec.stage = "layers"
                     hand_out(rec, rec.layers, workers.put_owed)
                     return
+            if rec.tex is not None and rec.stage != "tex":      # the twin reads the segments' flows: before finish_frame
+                rec.stage = "tex"
+                hand_out(rec, rec.tex, workers.put_owed)
+                return
             counts["frames_done"] += 1
             if rec.motion is None:
                 posts.append(pool.apply_async(finish_frame, (rec,)))
@@ -704,6 +748,9 @@ def main(flags):
                 workers.owe()
             if rec.motion is not None:
                 workers.owe()
+            for later in (rec.tex, rec.motion_tex):
+                if later is not None:
+                    workers.owe()
             with lock:
                 for ln in rec.solves:
                     hand_out(rec, ln, workers.put)
@@ -724,7 +771,7 @@ def main(flags):
     out_paths, rejected = write_lists(flags, output_root, listed)
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
-                 layers_done=counts["layers_done"], bg_done=counts["bg_done"],
+                 layers_done=counts["layers_done"], bg_done=counts["bg_done"], tex_done=counts["tex_done"],
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -823,7 +870,19 @@ def parse(argv=None):
                         help="implies --diag: leave a pair out of all_files.list and all_files_ext.list, and name it in "
                              "OUT/rejected.list, when a triangle of its mesh went non-finite or more than FRAC (0 .. 1) of "
                              "them folded; its files stay on disk")
+    parser.add_argument("--retex", action="store_true", default=False,
+                        help="also write the random-texture twin of every pair: OUT/inpRGB_tex/<seq>/<frame>.png, frame 1 "
+                             "with a procedural texture on every object (one per segment with --multseg), OUT/wRGB_tex/"
+                             "<seq>/<frame>.png, its warp with the pair's solved flows, and OUT/all_files_tex.list, whose "
+                             "lines name those two and the pair's own Flow file (DESIGN.md \"Random textures\")")
     flags = parser.parse_args(argv)
+    if flags.retex:
+        if flags.mid or flags.mid_layers or flags.mid_bg:
+            parser.error("--retex cannot be combined with --mid / --mid_layers / --mid_bg: sequences of retextured "
+                         "in-between frames are not built")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--retex needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
+                         "not know the tex line")
     if flags.max_fold is not None:
         if not 0 <= flags.max_fold <= 1:                   # (false on NaN)
             parser.error("--max_fold FRAC must lie in 0 .. 1")
