@@ -96,6 +96,8 @@ SYMBOLS = [
     ("ArapFlow_WarpLayers", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ArapFlow_WarpLayersStepScratchBytes", C.c_uint64, [_U, _U, _U]),
     ("ArapFlow_WarpLayersStep", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("ArapFlow_TrackPointsScratchBytes", C.c_uint64, [_U, _U, _U, _U]),
+    ("ArapFlow_TrackPoints", _I, [_VP, _U, _U, _U, _VP, _U, _VP, _U, _VP, _VP, _VP, _VP]),
     ("ArapFlow_BackgroundMaps", _I, [C.POINTER(C.c_float)] * 4),
     ("ArapFlow_Background", _I, [_VP, _U, _U, _VP, _U, _U, C.POINTER(C.c_float), C.POINTER(C.c_float)] + [_VP] * 14),
     ("ArapFlow_BackgroundSeq", _I, [_VP, _U, _U, _VP, _U, _U, _U, C.POINTER(C.c_float), _VP] + [C.POINTER(_VP)] * 7),

@@ -1,6 +1,7 @@
 // abi_warp.h -- the warp entry points on caller-owned images (ArapFlow_Warp / WarpEx / WarpStep / WarpLayers /
 // WarpLayersStep): the layout of their scratch buffer, stated once for the size functions and for the code that carves
 // it up, and the one enqueue of rasterise -> optional outputs -> resolve that the frame solver's warp shares.
+// Then the point tracks of a sequence (ArapFlow_TrackPoints, arap_track.h), with a scratch layout of their own.
 // Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background / BackgroundSeq, arap_bg.h), which needs no
 // scratch, and the random textures of a frame's objects (ArapFlow_Texture, arap_tex.h).
 #pragma once
@@ -265,6 +266,73 @@ int ArapFlow_WarpLayersStep(Opt_State* st, unsigned W, unsigned H, unsigned n, c
                 hipLaunchKernelGGL(k_lstep_step, g1, dim3(256), 0, stream, dj, la, lb.flows, pts, iW, iH, N);
         },
         [&](dim3 g1) { hipLaunchKernelGGL(k_lstep_scatter, g1, dim3(256), 0, stream, dj, pts, iW, iH, N); });
+}
+
+// Scratch of one track call: per state the cell counts, the ranks, the bins, the query points and a flag array for a
+// caller that wants no occ, each block of T aligned parts contiguous; then the owners and the T WarpJobs.
+struct TrackScratch { size_t cell, rank, bin, pts, occ, own, job, total, cell_stride, rank_stride, bin_stride, occ_stride; };
+static TrackScratch track_scratch(uint64_t W, uint64_t H, uint64_t T, uint64_t P)
+{
+    const uint64_t N = W * H;
+    TrackScratch L{};
+    L.cell_stride = align_up(4 * (N + 1), 256);
+    L.rank_stride = align_up(4 * P, 256);
+    L.bin_stride = align_up(16 * P, 256);
+    L.occ_stride = align_up(P, 256);
+    L.rank = L.cell + T * L.cell_stride;
+    L.bin = L.rank + T * L.rank_stride;
+    L.pts = L.bin + T * L.bin_stride;
+    L.occ = L.pts + align_up(T * 16 * P, 256);
+    L.own = L.occ + T * L.occ_stride;
+    L.job = L.own + align_up(sizeof(TrackOwner) * P, 256);
+    L.total = L.job + align_up(T * sizeof(WarpJob), 256);
+    return L;
+}
+
+// the limits are the bin's field widths (arap_occ.h) and the snapshot count of a sequence
+static bool track_sizes_ok(unsigned W, unsigned H, unsigned T, unsigned P)
+{
+    if (W == 0 || H == 0 || T == 0 || T > ARAPFLOW_MAX_SNAPSHOTS + 1 || P == 0 || P > (1u << 24)) return false;
+    return (uint64_t)W * H < (1ull << 31);
+}
+
+uint64_t ArapFlow_TrackPointsScratchBytes(unsigned W, unsigned H, unsigned T, unsigned P)
+{
+    return track_sizes_ok(W, H, T, P) ? track_scratch(W, H, T, P).total : 0;
+}
+
+int ArapFlow_TrackPoints(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* masks_red, unsigned T,
+                         const void* flows, unsigned P, const void* points, void* out_pos, void* out_occ, void* scratch)
+{
+    if (!st || !masks_red || !flows || !points || !scratch || n == 0 || n > 255 || !track_sizes_ok(W, H, T, P)) return -1;
+    if (!out_pos && !out_occ) return -1;
+    const TrackScratch L = track_scratch(W, H, T, P);
+    char* c = (char*)scratch;
+    WarpJob jobs[ARAPFLOW_MAX_SNAPSHOTS + 1] = {};
+    for (unsigned s = 0; s < T; ++s) {
+        WarpJob& j = jobs[s];
+        j.occ = out_occ ? (uint8_t*)out_occ + (size_t)s * P : (uint8_t*)(c + L.occ + s * L.occ_stride);
+        j.cell = (unsigned*)(c + L.cell + s * L.cell_stride);
+        j.rank = (unsigned*)(c + L.rank + s * L.rank_stride);
+        j.bin = (int4*)(c + L.bin + s * L.bin_stride);
+    }
+    TrackSet ts{};
+    ts.masks = (const uint8_t*)masks_red; ts.flows = (const float2*)flows; ts.points = (const float2*)points;
+    ts.pos = (float2*)out_pos;
+    ts.own = (TrackOwner*)(c + L.own); ts.pts = (int4*)(c + L.pts);
+    ts.n = (int)n; ts.P = (int)P;
+    hipStream_t stream = st->stream;
+    const WarpJob* dj = (const WarpJob*)(c + L.job);
+    HC(hipMemsetAsync(c + L.cell, 0, T * L.cell_stride, stream));
+    HC(hipMemcpyAsync(c + L.job, jobs, T * sizeof(WarpJob), hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
+    const int iW = (int)W, iH = (int)H;
+    const dim3 g1((P + 255) / 256), gT((P + 255) / 256, 1, T);
+    hipLaunchKernelGGL(k_track_locate, g1, dim3(256), 0, stream, ts, iW, iH);
+    hipLaunchKernelGGL(k_track_state, gT, dim3(256), 0, stream, dj, ts, iW, iH);
+    hipLaunchKernelGGL(k_occ_scan, dim3(1, 1, T), dim3(1024), 0, stream, dj, iW * iH);
+    hipLaunchKernelGGL(k_track_scatter, gT, dim3(256), 0, stream, dj, ts, iW, iH);
+    hipLaunchKernelGGL(k_track_tri, dim3((W + 63) / 64, (H + 3) / 4, T * n), dim3(64, 4), 0, stream, dj, ts, iW, iH);
+    return (int)hipGetLastError();
 }
 
 int ArapFlow_BackgroundMaps(const float M1[6], const float M2[6], float G[6], float Ginv[6])

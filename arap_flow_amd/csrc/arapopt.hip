@@ -36,6 +36,7 @@
 #include "arap_layers.h"
 #include "arap_mid.h"
 #include "arap_layers_step.h"
+#include "arap_track.h"
 #include "arap_bg.h"
 #include "arap_tex.h"
 #include "arap_diag.h"

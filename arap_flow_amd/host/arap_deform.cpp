@@ -32,6 +32,9 @@
 // (the layers of the frame's layers line; a layer of t= is 19 numbers, comma separated: kind, seed, the six of the map,
 // p0, p1, nine palette bytes; at least one output).  rgb1: frame 1 with a procedural texture on every layer's object;
 // rgb2 / mask2: its layered warp with the layers' flows, which are read only then.
+// A line whose first word is `trk` is the point tracks of one sequence (DESIGN.md "Point tracks"):
+//   trk PTS.trk n T  MASK_1 FLO_1,1 .. FLO_1,T  ..  MASK_n FLO_n,1 .. FLO_n,T  out=OUT.trk
+// (PTS.trk: a points file, trk_io.h; every state file of every layer is named; OUT.trk has T + 1 frames, the points first).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -61,6 +64,7 @@
 
 #include "device_pass.h"
 #include "list_line.h"
+#include "trk_io.h"
 
 // the usage text of the reference's executable (main.cpp:13-24), verbatim: it is part of the CLI contract
 static const char kUsage[] =
@@ -271,6 +275,59 @@ static bool run_texture(Opt_State* state, const TexSpec& q)
                                  nullptr, nullptr, dev.at(d_scr)) == 0;
     ok = ok && hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
     return ok ? out.write() : fail("ArapFlow_Texture failed\n");
+}
+
+// the point tracks of one sequence, synchronously (pipeline.run_tracks): read the points, every layer's mask and its T
+// state flows, one ArapFlow_TrackPoints on the state's stream, write the track file: the points themselves as frame 0
+// (occ by the frame test), then the T states
+static bool run_tracks(Opt_State* state, const TrkSpec& q)
+{
+    arapio::Tracks trk;
+    if (!arapio::read_trk(q.points, trk)) return false;
+    if (trk.frames != 1) return fail("trk: %s is no points file (%d frames)\n", q.points.c_str(), trk.frames);
+    const int w = trk.w, h = trk.h;
+    const unsigned W = (unsigned)w, H = (unsigned)h, n = (unsigned)q.masks.size(), T = q.states, P = (unsigned)trk.points;
+    const size_t N = (size_t)w * h;
+    std::vector<uint8_t> masks(n * N);
+    std::vector<float> flows((size_t)T * n * N * 2);           // [T][n][N][2]
+    for (size_t l = 0; l < n; ++l) {
+        arapio::Image msk;
+        if (!read_png(q.masks[l], msk)) return false;
+        if (msk.w != w || msk.h != h) return fail("trk: %s differs in size from %s\n", q.masks[l].c_str(), q.points.c_str());
+        for (size_t i = 0; i < N; ++i) masks[l * N + i] = msk.rgb[3 * i];          // red channel
+        for (size_t s = 0; s < T; ++s) {
+            const std::string& path = q.flows[l * T + s];
+            std::vector<float> fl;
+            int fw = 0, fh = 0;
+            if (!arapio::read_flo(path, fl, fw, fh)) return fail("Could not read %s\n", path.c_str());
+            if (fw != w || fh != h) return fail("trk: %s differs in size from %s\n", path.c_str(), q.points.c_str());
+            memcpy(flows.data() + (s * n + l) * N * 2, fl.data(), N * 8);
+        }
+    }
+    const uint64_t scratch = ArapFlow_TrackPointsScratchBytes(W, H, T, P);
+    if (scratch == 0) return fail("trk: %u points, %u states on %d x %d: beyond the limits\n", P, T, w, h);
+    DeviceArena dev;
+    const size_t d_msk = dev.stage(masks.data(), masks.size()), d_flow = dev.stage(flows.data(), flows.size() * 4);
+    const size_t d_pts = dev.stage(trk.pos.data(), (size_t)P * 8);
+    const size_t d_pos = dev.take((size_t)T * P * 8), d_occ = dev.take((size_t)T * P), d_scr = dev.take(scratch);
+    if (dev.alloc() != hipSuccess) return fail("trk: out of device memory\n");
+    arapio::Tracks out;
+    out.w = w; out.h = h; out.frames = (int32_t)T + 1; out.points = (int32_t)P;
+    out.pos.resize((size_t)(T + 1) * P * 2);
+    out.occ.resize((size_t)(T + 1) * P);
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_TrackPoints(state, W, H, n, dev.at(d_msk), T, dev.at(d_flow), P, dev.at(d_pts), dev.at(d_pos),
+                                         dev.at(d_occ), dev.at(d_scr)) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(out.pos.data() + (size_t)P * 2, dev.at(d_pos), (size_t)T * P * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(out.occ.data() + P, dev.at(d_occ), (size_t)T * P, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail("ArapFlow_TrackPoints failed\n");
+    memcpy(out.pos.data(), trk.pos.data(), (size_t)P * 8);
+    for (size_t k = 0; k < P; ++k) {
+        const float x = trk.pos[2 * k], y = trk.pos[2 * k + 1];
+        out.occ[k] = x >= 0.f && x <= (float)(w - 1) && y >= 0.f && y <= (float)(h - 1) ? 0 : 255;     // false on NaN
+    }
+    return arapio::write_trk(q.out, out);
 }
 
 // the layered warp of one frame, synchronously: read the layers' files, one ArapFlow_WarpLayers on the state's stream
@@ -751,6 +808,7 @@ int main(int argc, const char* argv[])
             const Item::Kind kind = fr->item.kind;
             if (!(kind == Item::Kind::Bg    ? run_background(state, fr->item.bg)
                   : kind == Item::Kind::Tex ? run_texture(state, fr->item.tex)
+                  : kind == Item::Kind::Trk ? run_tracks(state, fr->item.trk)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

@@ -43,6 +43,14 @@ static std::string canonical(const Item& it)
             t += num;
         }
         c.token("t", t); c.token("rgb1", q.rgb1); c.token("rgb2", q.rgb2); c.token("mask2", q.mask2);
+    } else if (it.kind == Item::Kind::Trk) {
+        const TrkSpec& q = it.trk;
+        c.word("trk"); c.word(q.points); c.word(std::to_string(q.masks.size())); c.word(std::to_string(q.states));
+        for (size_t l = 0; l < q.masks.size(); ++l) {
+            c.word(q.masks[l]);
+            for (unsigned s = 0; s < q.states; ++s) c.word(q.flows[l * q.states + s]);
+        }
+        c.token("out", q.out);
     } else {
         const BgSpec& q = it.bg;
         c.word("bg");

@@ -11,7 +11,9 @@
 //   tex line:     tex RGB1 n MASK_1 FLO_1 ... MASK_n FLO_n t=<layer 1>;...;<layer n> [rgb1=P] [rgb2=P] [mask2=P]
 //                 a layer: 19 numbers, comma separated: kind, seed, the six of m, p0, p1, nine palette bytes
 //                 (pipeline.TexLine); a repeated key is an error too
-//                 on these three any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   trk line:     trk PTS.trk n T  MASK_1 FLO_1,1 .. FLO_1,T  ..  MASK_n FLO_n,1 .. FLO_n,T  out=OUT.trk
+//                 (pipeline.TrkLine): every state file named, exactly one token, out=, after them
+//                 on these four any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -81,7 +83,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the four forms
+// ---- the five forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -126,12 +128,21 @@ struct TexSpec {                           // pipeline.TexLine
     std::string first_out;                 // the value of the first output token in line order: what --serve reports
 };
 
+struct TrkSpec {                           // pipeline.TrkLine
+    std::string points;
+    std::vector<std::string> masks;        // [n]
+    std::vector<std::string> flows;        // [n][T]: layer l's state s is flows[l * T + s]
+    unsigned states = 0;                   // T
+    std::string out;
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
     TexSpec tex;
+    TrkSpec trk;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -140,6 +151,7 @@ inline std::string done_path(const Item& it)
     return it.kind == Item::Kind::Solve    ? it.solve.flow
            : it.kind == Item::Kind::Layers ? it.layers.first_out
            : it.kind == Item::Kind::Tex    ? it.tex.first_out
+           : it.kind == Item::Kind::Trk    ? it.trk.out
                                            : it.bg.first_out();
 }
 
@@ -308,20 +320,44 @@ inline bool parse_tex(std::istringstream& tok, TexSpec& q)
     return !q.tex.empty() && !q.first_out.empty();
 }
 
+inline bool parse_trk(std::istringstream& tok, TrkSpec& q)
+{
+    std::string count, states;
+    unsigned long long n = 0, T = 0;
+    if (!(tok >> q.points >> count >> states) || !parse_uint(count, 255, n) || n < 1 ||
+        !parse_uint(states, ARAPFLOW_MAX_SNAPSHOTS + 1, T) || T < 1)
+        return false;
+    q.states = (unsigned)T;
+    std::string k, v;
+    if (split_token(q.points, k, v)) return false;
+    for (unsigned long long l = 0; l < n; ++l)
+        for (unsigned long long s = 0; s <= T; ++s) {      // the mask, then the T states
+            std::string path;
+            if (!(tok >> path) || split_token(path, k, v)) return false;
+            (s == 0 ? q.masks : q.flows).push_back(path);
+        }
+    std::string t, more;
+    if (!(tok >> t) || !split_token(t, k, v) || k != "out" || v.empty() || (tok >> more)) return false;
+    q.out = v;
+    return true;
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
     std::istringstream tok(line);
     std::string first;
     if (!(tok >> first)) return Parsed::Skip;
-    it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex : Item::Kind::Solve;
+    it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
+              : first == "trk" ? Item::Kind::Trk : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
     else if (it.kind == Item::Kind::Tex) p = parse_tex(tok, it.tex) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::Trk) p = parse_trk(tok, it.trk) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
-        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line"};      // by Item::Kind
+        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

@@ -485,7 +485,8 @@ class FrameSolver:
 def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, lead=()):
     """One ArapFlow_<name> call on host arrays.  `dims`: (W, H) or (W, H, n); `inputs`: (array or None, dtype) and
     `outputs`: (dict key, shape or None = not asked, torch dtype), both in the library's argument order; `scratch`: the
-    name of the *ScratchBytes function of a call that takes a scratch buffer; `lead`: arguments between the dims and
+    name of the *ScratchBytes function of a call that takes a scratch buffer, or (name, its arguments) where those are
+    not `dims`; `lead`: arguments between the dims and
     the inputs, an (array, dtype) to upload or a value passed as it is; an input (value, None) is passed as it is too (a
     host table among the device buffers).  An input that is a list of arrays, or an
     output whose shape is a list of shapes, is passed as a host array of device pointers and comes back as a list.
@@ -500,7 +501,8 @@ def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, 
     outs = {k: t for k, t in outs.items() if t is not None}
     args += [outs.get(k) for k, _, _ in outputs]
     if scratch:
-        args.append(torch.empty(int(getattr(lib, "ArapFlow_" + scratch)(*dims)), dtype=torch.uint8, device="cuda"))
+        sname, sdims = scratch if isinstance(scratch, tuple) else (scratch, dims)
+        args.append(torch.empty(int(getattr(lib, "ArapFlow_" + sname)(*sdims)), dtype=torch.uint8, device="cuda"))
     torch.cuda.synchronize()
 
     def ptr(t):
@@ -590,6 +592,27 @@ def warp_layers_step(state, rgb, masks, flows_a, flows_b, step=True, occ=True):
                     ("step", (H, W, 2) if step else None, torch.float32), ("occlusion_step", (H, W) if occ else None, torch.uint8)],
                    "WarpLayersStepScratchBytes")
     return {"warped_rgb": None, **r}
+
+
+def track_points(state, masks, flows, points):
+    """point tracks through a sequence (ArapFlow_TrackPoints, DESIGN.md "Point tracks"): masks u8[n,H,W] (red channels,
+    0 = object), flows f32[T,n,H,W,2] the T states of the n layers, points f32[P,2] in frame-1 coordinates (numpy) ->
+    dict(pos f32[T,P,2], occ u8[T,P]): where each point is in each state, and 255 where it is hidden there."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    flows = np.ascontiguousarray(flows, np.float32)
+    points = np.ascontiguousarray(points, np.float32)
+    if masks.ndim != 3 or flows.ndim != 5 or flows.shape[1:] != masks.shape + (2,):
+        raise ValueError("track_points: masks [n,H,W] and flows [T,n,H,W,2] expected")
+    if points.ndim != 2 or points.shape[1] != 2:
+        raise ValueError("track_points: points [P,2] expected")
+    n, H, W = masks.shape
+    T, P = flows.shape[0], points.shape[0]
+    if state.lib.ArapFlow_TrackPointsScratchBytes(W, H, T, P) == 0 or not 1 <= n <= 255:
+        raise ValueError("track_points: 1 <= n <= 255, 1 <= T <= %d, 1 <= P <= 2^24, W * H < 2^31 expected" % (capi.MAX_SNAPSHOTS + 1))
+    return _warp_call(state, "TrackPoints", (W, H, n),
+                      [(masks, np.uint8), (T, None), (flows, np.float32), (P, None), (points, np.float32)],
+                      [("pos", (T, P, 2), torch.float32), ("occ", (T, P), torch.uint8)],
+                      ("TrackPointsScratchBytes", (W, H, T, P)))
 
 
 def warp_diag(state, mask_red, flow, fold=True):

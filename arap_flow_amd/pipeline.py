@@ -14,6 +14,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   BgLine, parse_bg, bg_line, run_background, fit_bg_window, bg_maps    the `bg` line: moving background (addition)
   mid_bg_files, bg_maps_seq, run_background_seq    its mid= / mm= / mid_out= tokens: the camera per in-between frame (addition)
   TexLayer, TexLine, parse_tex, tex_line, tex_layers, run_texture    the `tex` line: the random-texture twin (addition)
+  TrkLine, parse_trk, trk_line, sample_track_points, run_tracks    the `trk` line: point tracks of a sequence (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
@@ -44,7 +45,7 @@ _ANTIALIAS = getattr(Image, "LANCZOS", None) or Image.ANTIALIAS   # Image.ANTIAL
 # ------------------------------------------------------------------------------------------------------
 # A list line is the unit of work between para_gen.py, arap_deform.py and `arap_deform --serve` (C++ twin: parse_item in
 # host/arap_deform.cpp).  It is a solve line, SolveLine, a `layers` line, the dict of parse_layers, a `bg` line, BgLine, or a
-# `tex` line, TexLine;
+# `tex` line, TexLine, or a `trk` line, TrkLine;
 # parse_line reads any of them from text, format_line writes it back, done_token is the path a worker reports it done by.
 EXTRA_KEYS = ("bwd", "occ", "occ_bwd", "mid", "diag", "fold")
 MAX_SNAPSHOTS = 8            # ARAPFLOW_MAX_SNAPSHOTS of include/arap_opt.h
@@ -56,6 +57,7 @@ BG_OUT_KEYS = ("occ_out", "bwd_out", "occ_bwd_out")                  # the full 
 TEX_WORD = "tex"
 TEX_KEYS = ("rgb1", "rgb2", "mask2")
 TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")         # ARAPFLOW_TEX_*: a kind's number is its index
+TRK_WORD = "trk"
 
 
 class SolveLine(NamedTuple):
@@ -424,10 +426,87 @@ def run_texture(state, spec):
             save_mask(r["warped_mask"], out["mask2"])
 
 
+class TrkLine(NamedTuple):
+    """a `trk` line (DESIGN.md "Point tracks"), recognised by its first word: the tracks of the points of one file
+    through the T states of the n layers of a frame
+        trk PTS.trk n T  MASK_1 FLO_1,1 .. FLO_1,T  ..  MASK_n FLO_n,1 .. FLO_n,T  out=OUT.trk
+    PTS.trk: a points file (trk.py, one frame); every state file of every layer is named, in the order of the sequence
+    (the later layer on top); OUT.trk has T + 1 frames, the points first.  `layers`: [(mask, (flo_1, .., flo_T))].  Any
+    other token is an error."""
+    points: str
+    layers: list
+    out: str
+
+
+def parse_trk(tokens):
+    if len(tokens) < 4 or tokens[0] != TRK_WORD:
+        raise ValueError("not a trk line: %r" % " ".join(tokens))
+    n, T = (int(t) if _UINT.match(t) else 0 for t in tokens[2:4])
+    if not (1 <= n <= 255 and 1 <= T <= MAX_SNAPSHOTS + 1):
+        raise ValueError("trk line: 1..255 layers and 1..%d states: %r" % (MAX_SNAPSHOTS + 1, " ".join(tokens)))
+    end = 4 + n * (T + 1)
+    if len(tokens) != end + 1:
+        raise ValueError("trk line: %d layers of a mask and %d flows, then out=: %r" % (n, T, " ".join(tokens)))
+    k, eq, v = tokens[end].partition("=")
+    if not (k == "out" and eq and v):
+        raise ValueError("trk line: bad output token %r" % tokens[end])
+    if any("=" in t for t in tokens[1:end]):
+        raise ValueError("trk line: a path expected where a token is: %r" % " ".join(tokens))
+    at = lambda l: 4 + l * (T + 1)
+    return TrkLine(tokens[1], [(tokens[at(l)], tuple(tokens[at(l) + 1:at(l) + 1 + T])) for l in range(n)], v)
+
+
+def trk_line(item):
+    """the inverse of parse_trk"""
+    tok = [TRK_WORD, item.points, str(len(item.layers)), str(len(item.layers[0][1]))]
+    for mask, flows in item.layers:
+        tok += [mask] + list(flows)
+    return " ".join(tok + ["out=" + item.out])
+
+
+def sample_track_points(rng, P, W, H, masks):
+    """para_gen --tracks P: P query points of a W x H frame 1, float32 [P,2], drawn from `rng` (a random.Random; the same
+    state gives the same points).  The first ceil(P / 2) are uniform over [0, W-1] x [0, H-1]; the rest are a uniformly
+    chosen object pixel (the union of the layers: masks u8[n,H,W], 0 = object) plus a uniform offset in [-0.5, 0.5)^2,
+    clipped to the frame; all are uniform over the frame when there is no object pixel."""
+    obj = np.flatnonzero((np.asarray(masks) == 0).any(0).ravel())
+    out = np.zeros((P, 2), np.float32)
+    for k in range(P):
+        if k < (P + 1) // 2 or not len(obj):
+            x, y = rng.uniform(0, W - 1), rng.uniform(0, H - 1)
+        else:
+            i = int(obj[rng.randrange(len(obj))])
+            x, y = i % W + (rng.random() - 0.5), i // W + (rng.random() - 0.5)
+        out[k] = (min(max(x, 0.0), W - 1.0), min(max(y, 0.0), H - 1.0))      # (rounding to float32 stays in the frame)
+    return out
+
+
+def run_tracks(state, spec):
+    """one `trk` line: read the points, every layer's mask and its T state flows, one opt.track_points, write the track
+    file: frame 0 the points themselves (occ by in_frame), frames 1 .. T the states"""
+    from . import opt, trk
+    pts = trk.read(spec.points)
+    if pts["pos"].shape[0] != 1:
+        raise ValueError("trk line: %s is no points file (%d frames)" % (spec.points, pts["pos"].shape[0]))
+    masks = np.stack([load_mask_red(m) for m, _ in spec.layers])
+    H, W = masks.shape[1:]
+    if (pts["W"], pts["H"]) != (W, H):
+        raise ValueError("trk line: points and mask sizes differ")
+    T = len(spec.layers[0][1])
+    flows = np.stack([np.stack([flo.flow_read(fl[s]) for _, fl in spec.layers]) for s in range(T)])
+    if flows.shape[2:4] != (H, W):
+        raise ValueError("trk line: mask and flow sizes differ")
+    r = opt.track_points(state, masks, flows, pts["pos"][0])
+    first = np.where(trk.in_frame(pts["pos"][0], W, H), 0, 255).astype(np.uint8)
+    trk.write(spec.out, W, H, np.concatenate([pts["pos"], r["pos"]]), np.concatenate([first[None], r["occ"]]))
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
-    BgLine when it is `bg`, a TexLine when it is `tex`"""
+    BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == TRK_WORD:
+        return parse_trk(tok)
     if tok and tok[0] == TEX_WORD:
         return parse_tex(tok)
     if tok and tok[0] == LAYERS_WORD:
@@ -447,12 +526,16 @@ def format_line(item):
         return bg_line(item)
     if isinstance(item, TexLine):
         return tex_line(item)
+    if isinstance(item, TrkLine):
+        return trk_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
-    first of a bg line's bg_outputs, a tex line's first output token"""
+    first of a bg line's bg_outputs, a tex line's first output token, a trk line's track file"""
+    if isinstance(item, TrkLine):
+        return item.out
     if isinstance(item, BgLine):
         return bg_outputs(item)[0]
     if isinstance(item, TexLine):

@@ -364,6 +364,27 @@ int ArapFlow_WarpLayersStep(Opt_State* state, unsigned W, unsigned H, unsigned n
                             const void* masks_red, const void* flows_a, const void* flows_b, void* out_rgb,
                             void* out_mask, void* out_step, void* out_occ, void* scratch);
 
+/* Point tracks through a sequence (DESIGN.md "Point tracks"): where P caller-given sub-pixel points of frame 1 are in
+ * each of T states of the n layers of a frame, and whether they can be seen there, on DEVICE buffers: masks_red as in
+ * ArapFlow_WarpLayers, flows float[T][n][H][W][2] the states of the layers as flows, points float[P][2] in frame-1
+ * coordinates.  A point's owner is the topmost (layer, triangle) of frame 1 that holds it; out_pos float[T][P][2] is
+ * the point carried by its owner into state s with the owner's barycentrics (a point of the background, or outside
+ * the frame, stays where it is); out_occ uint8[T][P] is 255 where the point leaves the frame in state s, or a triangle
+ * of a higher layer, or a triangle of the owner's layer later than every triangle that shares a corner with the owner,
+ * is drawn over it there -- ArapFlow_WarpLayersStep's rule; a point outside the frame (or NaN) is 255 in every state.
+ * With the points the W * H integer pixels in index order, out_occ of state s is the out_occ of
+ * ArapFlow_WarpLayersStep(flows_a = 0, flows_b = flows[s]) and out_pos - pixel its out_step on covered pixels.
+ * Either output may be NULL, not both.  P may exceed W * H.
+ * `scratch`: 256-byte aligned device buffer of ArapFlow_TrackPointsScratchBytes(W, H, T, P) bytes (per state
+ * 4 (W * H + 1) + 37 P, and 32 P once; 0 for sizes the call refuses).  Touches no key image.  Asynchronous on the
+ * state's stream.  Returns 0; -1, and nothing is launched, on bad arguments: a null state, input or scratch, both
+ * outputs NULL, n = 0, n > 255, W * H = 0 or >= 2^31, P = 0 or > 2^24, T = 0 or > ARAPFLOW_MAX_SNAPSHOTS + 1; else a HIP
+ * error code. */
+uint64_t ArapFlow_TrackPointsScratchBytes(unsigned W, unsigned H, unsigned T, unsigned P);
+int ArapFlow_TrackPoints(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* masks_red, unsigned T,
+                         const void* flows, unsigned P, const void* points, void* out_pos, void* out_occ,
+                         void* scratch);
+
 /* Moving background (DESIGN.md "Moving background"): the point maps between two frames whose background is sampled
  * through the affine maps M1, M2 (six floats (a, b, c, d, e, f): pixel (x, y) shows the background point
  * (a x + b y + c, d x + e y + f)).  G = M2^-1 o M1 (frame 1 -> frame 2) and Ginv = M1^-1 o M2, derived in double and

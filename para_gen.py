@@ -4,6 +4,7 @@
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
                      [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
                      [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]] [--diag] [--max_fold FRAC] [--retex]
+                     [--tracks P]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
 Pipeline per frame pair (para_gen.py:384-567): scan IN/orgRGB/**/N.jpg + IN/orgMasks/**/N.png, pair frame n with
@@ -44,6 +45,11 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     and all_files_ext.list when a triangle went non-finite or more than FRAC of them folded, and names it in
     OUT/rejected.list instead (`rgb1 rgb2 flow folded triangles nonfinite`); its files stay.  The lists are decided from
     the Diag files on disk (write_lists), so a --resume run writes the same ones.
+  * --tracks P (needs --mid K or --multseg --mid_layers K) writes long-range point tracks (DESIGN.md "Point tracks"):
+    P query points of frame 1 (pipeline.sample_track_points, from the pair's own generator), their sub-pixel position
+    and an occluded flag in frame 1, the K in-between frames and frame 2, as OUT/Tracks/<seq>/<frame>.trk
+    (arap_flow_amd/trk.py), from one `trk` line per pair once the states' flow files exist.  The background is taken
+    as static, so --bg_motion is refused.
   * --retex writes the random-texture twin of every kept pair (DESIGN.md "Random textures"; the reference's D15OM beside
     its D15RM): OUT/inpRGB_tex/<seq>/<frame>.png, frame 1 with a procedural texture on every object (with --multseg one per
     segment), and OUT/wRGB_tex/<seq>/<frame>.png, its warp with the pair's already solved flows, from one `tex` line per
@@ -85,6 +91,7 @@ mid_full_dir = "MidFull"           # --mid_bg: the in-between frames and links w
 mid_dir = "Mid"                    # --mid K: in-between frames from the constraint ramp (addition)
 NUM_ITER = 19                      # the ramp length of the ARAP drivers (main.cpp:215-221): what --mid K spreads over
 LAYERS_OCC = "occl_gen"            # --multseg --occ_layers: the frame's forward occlusion, made by a `layers` line
+tracks_dir = "Tracks"                                            # --tracks: point tracks (addition)
 full_dir, occ_full_dir, bwd_full_dir, occ_bwd_full_dir = "FlowFull", "OccFull", "FlowBwdFull", "OccBwdFull"   # --bg_motion
 FULL_KEYS = ["flowfull_gen", "occfull_gen", "bwdfull_gen", "occbwdfull_gen"]      # --bg_motion: the full-frame maps
 EXT_KEYS = list(pipeline.EXTRA_OF) + [LAYERS_OCC] + FULL_KEYS         # every optional output of a frame
@@ -120,6 +127,11 @@ def mid_bg_paths(p):
     if LAYERS_OCC in p:
         out += [pipeline.mid_bg_files(p["midbg_gen"], i)["occ"] for i in (0,) + steps]
     return out
+
+
+def track_paths(p):
+    """--tracks: a pair's track file; [] without"""
+    return [p["trk_gen"]] if "trk_gen" in p else []
 
 
 def _pair_id(seq, stem):
@@ -197,6 +209,8 @@ class Frame:
     tmp: tuple = ()                # --bg_motion: the bg line's own input files, deleted when it is done
     tex: object = None             # --retex: the pair's tex line (pipeline.TexLine), handed out before finish_frame
     motion_tex: object = None      # --retex --bg_motion: the twin's bg line, handed out after the pair's
+    tracks: object = None          # --tracks: the pair's trk line (pipeline.TrkLine), handed out once its solves are done
+    pending: int = 0               # main: lines of stage "layers" (the layers line, the trk line) not yet reported done
 
     @property
     def solves(self):
@@ -214,6 +228,8 @@ def prepare_pair(args):
     midbg, midbg_out = p.pop("_midbg", None), p.pop("midbg_gen", None)      # --mid_bg: the snapshot steps, the output prefix
     midl = p.pop("_midl", None)                 # --mid_layers: the snapshot steps of every segment's solve
     tex1, tex2 = p.pop("rgb1tex_gen", None), p.pop("rgb2tex_gen", None)     # --retex: the twin's two frames
+    trk_out, n_tracks = p.pop("trk_gen", None), p.pop("_tracks", 0)         # --tracks: the track file, the number of points
+    layer_masks = []
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
     im1, mk1, im2, mk2 = preprocess(p, flags.size)
@@ -256,11 +272,13 @@ def prepare_pair(args):
         mask = np.zeros_like(mk1, dtype=np.uint8)
         mask[mk1 == 0] = pipeline.ARAP_BG                                      # :514-517
         Image.fromarray(mask).save(p["msk1_gen"])
+        layer_masks.append(mask)
     else:
         segs = []
         for s, mask in pipeline.split_segments(mk1, valids):                   # :518-540
             p_ = pipeline.replace_ext(p, s, keep_orgs=["rgb1_gen", "cstr_tmp"])
             Image.fromarray(mask).save(p_["msk1_gen"])
+            layer_masks.append(mask)
             segs.append(pipeline.make_arap_path(p_))
             if midl:                            # the segment's snapshots lie beside its flow: <flow without .flo>_sII*
                 segs[-1].extra["mid"] = pipeline.mid_token(midl, segs[-1].flow[:-len(".flo")])
@@ -271,6 +289,16 @@ def prepare_pair(args):
             out["mid"] = pipeline.mid_token(midl, p["midl_gen"])
         layers = dict(rgb=line.rgb, layers=[(sg.mask, sg.flow) for sg in segs], out=out)
     rec = Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
+    if trk_out is not None and rec.solves:      # the tracks: the points from the pair's own generator, every state file named
+        from arap_flow_amd import trk
+        os.makedirs(osp.dirname(trk_out), exist_ok=True)
+        H, W = im1.shape[:2]
+        pts_path = osp.splitext(p["cstr_tmp"])[0] + "_pts.trk"
+        trk.write(pts_path, W, H, pipeline.sample_track_points(rn.Random(_pair_id(seq, stem)), n_tracks, W, H,
+                                                               np.stack(layer_masks)))
+        steps = midl or pipeline.parse_mid(line.extra["mid"])[0]
+        states = lambda sg: tuple(pipeline.mid_files(pipeline.parse_mid(sg.extra["mid"])[1], i)["flow"] for i in steps) + (sg.flow,)
+        rec.tracks = pipeline.TrkLine(pts_path, [(sg.mask, states(sg)) for sg in rec.solves], trk_out)
     if tex1 is not None:                        # the twin: one texture per solved layer, from the pair's own generator
         for q in (tex1, tex2):
             os.makedirs(osp.dirname(q), exist_ok=True)
@@ -516,7 +544,7 @@ def scan(flags, input_root, output_root):
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
-                                                           tx1=color_tex_dir, tx2=wrgb_tex_dir,
+                                                           tx1=color_tex_dir, tx2=wrgb_tex_dir, trk=tracks_dir,
                                                            obw=occ_bwd_dir, occ=occ_dir, dia=diag_dir, fol=fold_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
                                                            ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
@@ -566,11 +594,14 @@ def scan(flags, input_root, output_root):
                     e["_mid"] = tuple(flags.mid_steps)
                 if "midl_gen" in e:
                     e["_midl"] = tuple(flags.mid_layers_steps)
+                if getattr(flags, "tracks", 0):
+                    e["trk_gen"], e["_tracks"] = osp.abspath(osp.join(roots["trk"], seq, f + ".trk")), int(flags.tracks)
                 if getattr(flags, "mid_bg", False):
                     e["midbg_gen"] = osp.abspath(osp.join(roots["mfu"], seq, f))
                     e["_midbg"] = tuple(flags.mid_steps or flags.mid_layers_steps)
                 # every requested output
                 done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e) + mid_bg_paths(e)
+                done += track_paths(e)
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -616,7 +647,7 @@ def write_lists(flags, output_root, all_paths):
     for p in all_paths:
         ln = pipeline.make_arap_path(p)
         trio = [ln.rgb, ln.out_rgb, ln.flow]
-        full = trio + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p) + mid_bg_paths(p)
+        full = trio + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p) + mid_bg_paths(p) + track_paths(p)
         if not all(osp.exists(q) for q in trio):
             continue
         if max_fold is not None and osp.exists(p.get("diag_gen", "")):
@@ -672,7 +703,7 @@ def main(flags):
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
     frames = {}                                        # done token of a line a worker holds -> its Frame
     posts, lock = [], threading.Lock()
-    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0)
+    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0, tracks_done=0)
 
     def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
         frames[pipeline.done_token(item)] = rec
@@ -700,16 +731,26 @@ def main(flags):
                 return
             if rec.stage == "tex":                     # its tex line: the segment files may go now
                 counts["tex_done"] += 1
-            elif rec.stage == "layers":                # its layers line
-                counts["layers_done"] += 1
+            elif rec.stage == "layers":                # its layers line or its trk line: both read the segments' snapshots,
+                if rec.tracks is not None and path == rec.tracks.out:          # which go only when both are done
+                    counts["tracks_done"] += 1
+                    if rec.remove and osp.exists(rec.tracks.points):
+                        os.remove(rec.tracks.points)
+                else:
+                    counts["layers_done"] += 1
+                rec.pending -= 1
+                if rec.pending > 0:
+                    return
             else:
                 counts["solves_done"] += 1
                 rec.left -= 1
                 if rec.left > 0:
                     return
-                if rec.layers is not None:             # last segment done: the frame's layers line, then finish_frame
-                    rec.stage = "layers"
-                    hand_out(rec, rec.layers, workers.put_owed)
+                later = [q for q in (rec.layers, rec.tracks) if q is not None]
+                if later:                              # last segment done: the frame's layers and trk lines, then finish_frame
+                    rec.stage, rec.pending = "layers", len(later)
+                    for q in later:
+                        hand_out(rec, q, workers.put_owed)
                     return
             if rec.tex is not None and rec.stage != "tex":      # the twin reads the segments' flows: before finish_frame
                 rec.stage = "tex"
@@ -748,7 +789,7 @@ def main(flags):
                 workers.owe()
             if rec.motion is not None:
                 workers.owe()
-            for later in (rec.tex, rec.motion_tex):
+            for later in (rec.tex, rec.motion_tex, rec.tracks):
                 if later is not None:
                     workers.owe()
             with lock:
@@ -772,6 +813,7 @@ def main(flags):
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
                  layers_done=counts["layers_done"], bg_done=counts["bg_done"], tex_done=counts["tex_done"],
+                 tracks_done=counts["tracks_done"],
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -875,7 +917,22 @@ def parse(argv=None):
                              "with a procedural texture on every object (one per segment with --multseg), OUT/wRGB_tex/"
                              "<seq>/<frame>.png, its warp with the pair's solved flows, and OUT/all_files_tex.list, whose "
                              "lines name those two and the pair's own Flow file (DESIGN.md \"Random textures\")")
+    parser.add_argument("--tracks", type=int, default=0, metavar="P",
+                        help="with --mid K or --multseg --mid_layers K: also write the tracks of P query points of frame 1 "
+                             "through the K in-between frames to frame 2, sub-pixel positions and occluded flags: "
+                             "OUT/Tracks/<seq>/<frame>.trk (DESIGN.md \"Point tracks\")")
     flags = parser.parse_args(argv)
+    if flags.tracks:
+        if not 1 <= flags.tracks <= 1 << 24:
+            parser.error("--tracks P: 1 .. 2^24 points")
+        if not (flags.mid or (flags.multseg and flags.mid_layers)):
+            parser.error("--tracks needs --mid K or --multseg --mid_layers K: the states a point is tracked through")
+        if flags.bg_motion is not None:
+            parser.error("--tracks cannot be combined with --bg_motion: a track of a background point assumes the static "
+                         "background")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--tracks needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
+                         "not know the trk line")
     if flags.retex:
         if flags.mid or flags.mid_layers or flags.mid_bg:
             parser.error("--retex cannot be combined with --mid / --mid_layers / --mid_bg: sequences of retextured "
