@@ -102,6 +102,10 @@ SYMBOLS = [
     ("ArapFlow_Background", _I, [_VP, _U, _U, _VP, _U, _U, C.POINTER(C.c_float), C.POINTER(C.c_float)] + [_VP] * 14),
     ("ArapFlow_BackgroundSeq", _I, [_VP, _U, _U, _VP, _U, _U, _U, C.POINTER(C.c_float), _VP] + [C.POINTER(_VP)] * 7),
     ("ArapFlow_Texture", _I, [_VP, _U, _U, _U, _VP, _VP, C.POINTER(TexLayer), _VP]),
+    ("ArapFlow_BlurSchedule", _I, [C.c_float, C.c_float, _U] + [C.POINTER(C.c_float)] * 4),
+    ("ArapFlow_BlurLayersScratchBytes", C.c_uint64, [_U, _U, _U, _U]),
+    ("ArapFlow_BlurLayers", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _U, _VP, _U, _U,
+                                 C.POINTER(C.c_float), C.POINTER(C.c_float), _VP, _VP, _VP]),
     ("ArapFlow_WarpDiag", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP]),
     ("ArapFlow_SolverSetDiag", _I, [_VP, _I]),
     ("ArapFlow_SolverGetDiag", _I, [_VP, _U, C.POINTER(MeshStats), _VP]),
@@ -110,6 +114,7 @@ SYMBOLS = [
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h
 MAX_SNAPSHOTS = 8                       # ARAPFLOW_MAX_SNAPSHOTS
+MAX_BLUR_SAMPLES, BLUR_CHUNK = 32, 8    # ARAPFLOW_MAX_BLUR_SAMPLES, ARAPFLOW_BLUR_CHUNK
 
 _LIB = None
 

@@ -3,7 +3,8 @@
 // it up, and the one enqueue of rasterise -> optional outputs -> resolve that the frame solver's warp shares.
 // Then the point tracks of a sequence (ArapFlow_TrackPoints, arap_track.h), with a scratch layout of their own.
 // Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background / BackgroundSeq, arap_bg.h), which needs no
-// scratch, and the random textures of a frame's objects (ArapFlow_Texture, arap_tex.h).
+// scratch, the random textures of a frame's objects (ArapFlow_Texture, arap_tex.h) and the motion-blurred frames
+// (ArapFlow_BlurSchedule / BlurLayers, arap_blur.h), with a scratch layout of their own.
 #pragma once
 
 // the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
@@ -451,6 +452,100 @@ int ArapFlow_Texture(Opt_State* st, unsigned W, unsigned H, unsigned n, const vo
     HC(hipMemcpyAsync(st->tex, layers, n * sizeof(TexLayer), hipMemcpyHostToDevice, st->stream));   // (pageable: staged before the call returns)
     hipLaunchKernelGGL(k_tex_fill, dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, st->stream, (const uint8_t*)rgb,
                        (const uint8_t*)masks_red, (const TexLayer*)st->tex, (int)n, (uint8_t*)out_rgb, (int)W, (int)H);
+    return (int)hipGetLastError();
+}
+
+static_assert(BLUR_CHUNK == ARAPFLOW_BLUR_CHUNK && BLUR_MAX_SAMPLES == ARAPFLOW_MAX_BLUR_SAMPLES, "blur limits");
+
+// Scratch of one blur call: min(samples, BLUR_CHUNK) key images, then -- when the samples need more than one chunk -- the
+// carried sums, each aligned to 256 bytes
+struct BlurScratch { size_t key, carry, total; };
+static BlurScratch blur_scratch(uint64_t W, uint64_t H, uint64_t samples)
+{
+    const uint64_t N = W * H, g = samples < (uint64_t)BLUR_CHUNK ? samples : (uint64_t)BLUR_CHUNK;
+    BlurScratch L{};
+    L.carry = L.key + align_up(g * N * 8, 256);
+    L.total = L.carry + (samples > (uint64_t)BLUR_CHUNK ? align_up(N * 8, 256) : 0);
+    return L;
+}
+
+static bool blur_sizes_ok(unsigned W, unsigned H, unsigned n, unsigned samples)
+{
+    if (W == 0 || H == 0 || n == 0 || n > 255 || samples == 0 || samples > (unsigned)BLUR_MAX_SAMPLES) return false;
+    return (uint64_t)W * H < (1ull << 31);
+}
+
+int ArapFlow_BlurSchedule(float centre, float shutter, unsigned samples, const float Ma[6], const float Mb[6], float* times,
+                          float* maps)
+{
+    if (!times || samples == 0 || samples > (unsigned)BLUR_MAX_SAMPLES) return -1;
+    if (!std::isfinite(centre) || !std::isfinite(shutter) || shutter < 0.f) return -1;
+    if (maps) {
+        if (!Ma || !Mb) return -1;
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(Ma[k]) || !std::isfinite(Mb[k])) return -1;
+    }
+    const bool still = maps && memcmp(Ma, Mb, 6 * sizeof(float)) == 0;       // the same camera: every sample uses Ma itself
+    for (unsigned k = 0; k < samples; ++k) {
+        const float t = (float)((double)centre + (double)shutter * (((double)k + 0.5) / (double)samples - 0.5));
+        times[k] = t;
+        if (!maps) continue;
+        const float u = 1.0f - t;
+        for (int i = 0; i < 6; ++i) maps[6 * k + i] = still ? Ma[i] : u * Ma[i] + t * Mb[i];
+    }
+    return 0;
+}
+
+// per pixel: 8 per sample of a chunk (at most 8 * ARAPFLOW_BLUR_CHUNK) + 8 when samples > ARAPFLOW_BLUR_CHUNK
+uint64_t ArapFlow_BlurLayersScratchBytes(unsigned W, unsigned H, unsigned n, unsigned samples)
+{
+    return blur_sizes_ok(W, H, n, samples) ? blur_scratch(W, H, samples).total : 0;
+}
+
+int ArapFlow_BlurLayers(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                        const void* flows_a, const void* flows_b, float centre, float shutter, unsigned samples,
+                        const void* bg, unsigned bgW, unsigned bgH, const float Ma[6], const float Mb[6], void* out_rgb,
+                        void* out_alpha, void* scratch)
+{
+    if (!st || !rgb || !masks_red || !flows_b || !scratch || (!out_rgb && !out_alpha)) return -1;
+    if (!blur_sizes_ok(W, H, n, samples)) return -1;
+    if (bg && (!Ma || !Mb || bgW == 0 || bgH == 0 || bgW >= (1u << 31) || bgH >= (1u << 31))) return -1;
+    float times[BLUR_MAX_SAMPLES], maps[BLUR_MAX_SAMPLES * 6];
+    if (ArapFlow_BlurSchedule(centre, shutter, samples, Ma, Mb, times, bg ? maps : nullptr) != 0) return -1;
+    const uint64_t N = (uint64_t)W * H;
+    const BlurScratch L = blur_scratch(W, H, samples);
+    const std::pair<const void*, uint64_t> ins[] = {{rgb, 3 * N}, {masks_red, n * N}, {flows_a, n * N * 8}, {flows_b, n * N * 8},
+                                                    {bg, 3ull * bgW * bgH}, {scratch, L.total}};
+    const std::pair<const void*, uint64_t> outs[] = {{out_rgb, 3 * N}, {out_alpha, N}};
+    for (const auto& o : outs)
+        for (const auto& in : ins) {
+            const uintptr_t a = (uintptr_t)in.first, b = (uintptr_t)o.first;
+            if (in.first && o.first && a < b + o.second && b < a + in.second) return -1;
+        }
+    char* const c = (char*)scratch;
+    BlurFrame f{};
+    f.rgb = (const uint8_t*)rgb; f.masks = (const uint8_t*)masks_red;
+    f.flows_a = (const float2*)flows_a; f.flows_b = (const float2*)flows_b;
+    f.keys = (unsigned long long*)(c + L.key);
+    f.carry = L.total != L.carry ? (ushort4*)(c + L.carry) : nullptr;
+    f.out_rgb = (uint8_t*)out_rgb; f.out_alpha = (uint8_t*)out_alpha;
+    f.bg = BgPicture{(const uint8_t*)bg, (int)bgW, (int)bgH};
+    f.n = (int)n; f.samples = (int)samples;
+    hipStream_t stream = st->stream;
+    HC(hipMemsetAsync(f.keys, 0, L.carry - L.key, stream));
+    const bool still = bg && memcmp(Ma, Mb, 6 * sizeof(float)) == 0;
+    for (unsigned k0 = 0; k0 < samples; k0 += (unsigned)BLUR_CHUNK) {
+        BlurChunk ch{};
+        ch.g = (int)std::min(samples - k0, (unsigned)BLUR_CHUNK);          // the last chunk: what is left
+        ch.first = k0 == 0; ch.last = k0 + (unsigned)ch.g == samples; ch.same_map = still;
+        for (int s = 0; s < ch.g; ++s) {
+            ch.t[s] = times[k0 + s];
+            if (bg) ch.M[s] = bg_map(maps + 6 * (k0 + s));
+        }
+        hipLaunchKernelGGL(k_blur_raster, dim3((W + 63) / 64, (H + 3) / 4, n * (unsigned)ch.g), dim3(64, 4), 0, stream, f, ch,
+                           (int)W, (int)H);
+        hipLaunchKernelGGL(k_blur_accum, dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, stream, f, ch, (int)W, (int)H);
+    }
     return (int)hipGetLastError();
 }
 

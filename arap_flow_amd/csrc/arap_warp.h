@@ -55,12 +55,23 @@ struct WarpJob {                    // one frame
     ArapFlow_MeshStats* stats;      // the statistics decoded from `acc`
 };
 
+// the position a flow value gives vertex (x, y) (main.cpp:159-166); the one copy
+__device__ __forceinline__ float2 flow_pos(int x, int y, float2 f)
+{
+    return make_float2((float)x + f.x, (float)y + f.y);
+}
+
 __device__ __forceinline__ float2 warp_pos(const WarpJob& j, int x, int y, int i)
 {
     if (j.field) return j.field[i];
-    const float2 f = j.flow_in[i];
-    return make_float2((float)x + f.x, (float)y + f.y);
+    return flow_pos(x, y, j.flow_in[i]);
 }
+
+// where warp_quad takes a vertex's position from: by default the job's field or flow (warp_pos).  arap_blur.h places the
+// vertices by a flow it mixes on the fly; every other caller leaves the default, and its code is what it was.
+struct JobPos {
+    __device__ __forceinline__ float2 operator()(const WarpJob& j, int x, int y, int i) const { return warp_pos(j, x, y, i); }
+};
 
 // The rasteriser's inside test and barycentrics of triangle (p0, p1, p2) at the point (sx, sy) (main.cpp:69-104).  The
 // one copy of this expression: raster_tri, the backward pass and the occlusion query (arap_occ.h) all call it, so their
@@ -157,14 +168,15 @@ __device__ __forceinline__ bool quad_on(const uint8_t* mask, int W, int H, int q
 
 // The work of vertex (x, y) on the quad to its lower right, the one copy: if the quad is rasterised, its four corner
 // positions, their colours when COLOUR (zeros without an image) and  act(t, p0, p1, p2, c0, c1, c2)  for its two
-// triangles in the reference's order, 2i = (00,01,10) then 2i+1 = (10,01,11).  `act` rasterises or queries.
-template <bool COLOUR, class Act>
-__device__ __forceinline__ void warp_quad(const WarpJob& j, int W, int H, int x, int y, Act act)
+// triangles in the reference's order, 2i = (00,01,10) then 2i+1 = (10,01,11).  `act` rasterises or queries; `pos`
+// places the corners (JobPos above).
+template <bool COLOUR, class Act, class Pos = JobPos>
+__device__ __forceinline__ void warp_quad(const WarpJob& j, int W, int H, int x, int y, Act act, Pos pos = Pos())
 {
     if (!quad_on(j.mask, W, H, x, y)) return;
     const int i = x + W * y, i01 = i + 1, i10 = i + W, i11 = i + W + 1;
-    const float2 p00 = warp_pos(j, x, y, i), p01 = warp_pos(j, x + 1, y, i01);
-    const float2 p10 = warp_pos(j, x, y + 1, i10), p11 = warp_pos(j, x + 1, y + 1, i11);
+    const float2 p00 = pos(j, x, y, i), p01 = pos(j, x + 1, y, i01);
+    const float2 p10 = pos(j, x, y + 1, i10), p11 = pos(j, x + 1, y + 1, i11);
     float v00[3] = {0, 0, 0}, v01[3] = {0, 0, 0}, v10[3] = {0, 0, 0}, v11[3] = {0, 0, 0};
     if (COLOUR && j.rgb) {
 #pragma unroll
@@ -180,10 +192,12 @@ __device__ __forceinline__ void warp_quad(const WarpJob& j, int W, int H, int x,
 }
 
 // warp_quad with raster_tri as the action, for the job seen as layer `layer`
-__device__ __forceinline__ void raster_quad(const WarpJob& j, int W, int H, int x, int y, unsigned layer)
+template <class Pos = JobPos>
+__device__ __forceinline__ void raster_quad(const WarpJob& j, int W, int H, int x, int y, unsigned layer, Pos pos = Pos())
 {
     warp_quad<true>(j, W, H, x, y, [&](unsigned t, float2 p0, float2 p1, float2 p2, const float* c0, const float* c1,
-                                       const float* c2) { raster_tri(j, W, H, warp_key(layer, t), p0, p1, p2, c0, c1, c2); });
+                                       const float* c2) { raster_tri(j, W, H, warp_key(layer, t), p0, p1, p2, c0, c1, c2); },
+                    pos);
 }
 
 // warp_quad's numbering read back: the grid coordinates and indices of the three corners of triangle t,

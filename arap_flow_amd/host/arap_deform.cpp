@@ -35,6 +35,11 @@
 // A line whose first word is `trk` is the point tracks of one sequence (DESIGN.md "Point tracks"):
 //   trk PTS.trk n T  MASK_1 FLO_1,1 .. FLO_1,T  ..  MASK_n FLO_n,1 .. FLO_n,T  out=OUT.trk
 // (PTS.trk: a points file, trk_io.h; every state file of every layer is named; OUT.trk has T + 1 frames, the points first).
+// A line whose first word is `blur` is the two motion-blurred frames of one pair (DESIGN.md "Motion blur"):
+//   blur RGB n MASK_1 FLO_1 ... MASK_n FLO_n BG.png b=<shutter>,<samples> [m=<12 numbers: M1 then M2>]
+//        [rgb1=P] [rgb2=P] [alpha1=P] [alpha2=P]
+// (the layers of the frame's layers line; BG.png shows behind them through the cameras of m=, the identity without it; at
+// least one output).  rgb1 / alpha1: the frame exposed around t = 0; rgb2 / alpha2: around t = 1, the same shutter.
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -275,6 +280,38 @@ static bool run_texture(Opt_State* state, const TexSpec& q)
                                  nullptr, nullptr, dev.at(d_scr)) == 0;
     ok = ok && hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
     return ok ? out.write() : fail("ArapFlow_Texture failed\n");
+}
+
+// the motion-blurred frames of one pair, synchronously (pipeline.run_blur): read the layers' files and the background
+// picture once, one ArapFlow_BlurLayers on the state's stream per frame the line asks for (centre 0, centre 1) with one
+// scratch buffer, write the outputs asked for
+static bool run_blur(Opt_State* state, const BlurSpec& q)
+{
+    arapio::Image rgb, bg;
+    std::vector<uint8_t> masks;
+    std::vector<float> flows;
+    if (!read_layer_files("blur", q.rgb, q.masks, q.flows, true, rgb, masks, flows) || !read_png(q.bg, bg)) return false;
+    const int w = rgb.w, h = rgb.h;
+    const unsigned W = (unsigned)w, H = (unsigned)h, n = (unsigned)q.masks.size();
+    const size_t N = (size_t)w * h;
+    const uint64_t scratch = ArapFlow_BlurLayersScratchBytes(W, H, n, q.samples);
+    if (scratch == 0) return fail("blur: %u samples of %u layers on %d x %d: beyond the limits\n", q.samples, n, w, h);
+    DeviceArena dev;
+    const size_t d_rgb = dev.stage(rgb.rgb.data(), 3 * N), d_msk = dev.stage(masks.data(), n * N);
+    const size_t d_flow = dev.stage(flows.data(), n * N * 8), d_bg = dev.stage(bg.rgb.data(), bg.rgb.size());
+    OutputTable out(dev, w, h);
+    const size_t o_rgb[2] = {out.add(FileKind::rgb, q.rgb1), out.add(FileKind::rgb, q.rgb2)};
+    const size_t o_alpha[2] = {out.add(FileKind::gray8, q.alpha1), out.add(FileKind::gray8, q.alpha2)};
+    const size_t d_scr = dev.take(scratch);
+    if (dev.alloc() != hipSuccess) return fail("blur: out of device memory\n");
+    bool ok = dev.upload() == hipSuccess;
+    for (int f = 0; ok && f < 2; ++f)
+        if (out.dev(o_rgb[f]) || out.dev(o_alpha[f]))
+            ok = ArapFlow_BlurLayers(state, W, H, n, dev.at(d_rgb), dev.at(d_msk), nullptr, dev.at(d_flow), (float)f, q.shutter,
+                                     q.samples, dev.at(d_bg), (unsigned)bg.w, (unsigned)bg.h, q.m, q.m + 6, out.dev(o_rgb[f]),
+                                     out.dev(o_alpha[f]), dev.at(d_scr)) == 0;
+    ok = ok && hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
+    return ok ? out.write() : fail("ArapFlow_BlurLayers failed\n");
 }
 
 // the point tracks of one sequence, synchronously (pipeline.run_tracks): read the points, every layer's mask and its T
@@ -530,7 +567,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -809,6 +846,7 @@ int main(int argc, const char* argv[])
             if (!(kind == Item::Kind::Bg    ? run_background(state, fr->item.bg)
                   : kind == Item::Kind::Tex ? run_texture(state, fr->item.tex)
                   : kind == Item::Kind::Trk ? run_tracks(state, fr->item.trk)
+                  : kind == Item::Kind::Blur ? run_blur(state, fr->item.blur)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

@@ -51,6 +51,20 @@ static std::string canonical(const Item& it)
             for (unsigned s = 0; s < q.states; ++s) c.word(q.flows[l * q.states + s]);
         }
         c.token("out", q.out);
+    } else if (it.kind == Item::Kind::Blur) {
+        const BlurSpec& q = it.blur;
+        c.word("blur"); c.word(q.rgb); c.word(std::to_string(q.masks.size()));
+        for (size_t l = 0; l < q.masks.size(); ++l) { c.word(q.masks[l]); c.word(q.flows[l]); }
+        c.word(q.bg);
+        char num[64];
+        snprintf(num, sizeof(num), "%.9g,%u", q.shutter, q.samples);
+        c.token("b", num);
+        std::string m;
+        for (int k = 0; q.have_m && k < 12; ++k) {
+            snprintf(num, sizeof(num), "%s%.9g", k ? "," : "", q.m[k]);
+            m += num;
+        }
+        c.token("m", m); c.token("rgb1", q.rgb1); c.token("rgb2", q.rgb2); c.token("alpha1", q.alpha1); c.token("alpha2", q.alpha2);
     } else {
         const BgSpec& q = it.bg;
         c.word("bg");

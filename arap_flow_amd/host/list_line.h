@@ -13,7 +13,11 @@
 //                 (pipeline.TexLine); a repeated key is an error too
 //   trk line:     trk PTS.trk n T  MASK_1 FLO_1,1 .. FLO_1,T  ..  MASK_n FLO_n,1 .. FLO_n,T  out=OUT.trk
 //                 (pipeline.TrkLine): every state file named, exactly one token, out=, after them
-//                 on these four any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   blur line:    blur RGB1 n MASK_1 FLO_1 ... MASK_n FLO_n BG b=<shutter>,<samples> [m=<12 numbers: M1 then M2>]
+//                 [rgb1=P] [rgb2=P] [alpha1=P] [alpha2=P]
+//                 (pipeline.BlurLine): the shutter a finite number >= 0, 1 .. ARAPFLOW_MAX_BLUR_SAMPLES samples, the maps
+//                 finite; without m= both maps are the identity; a repeated key is an error too
+//                 on these five any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -83,7 +87,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the five forms
+// ---- the six forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -136,13 +140,25 @@ struct TrkSpec {                           // pipeline.TrkLine
     std::string out;
 };
 
+struct BlurSpec {                          // pipeline.BlurLine
+    std::string rgb, bg;
+    std::vector<std::string> masks, flows;
+    float shutter = 0.f;
+    unsigned samples = 0;                  // 0: no b= seen yet
+    bool have_m = false;
+    float m[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f};     // M1, M2; the identity without m=
+    std::string rgb1, rgb2, alpha1, alpha2;        // outputs (empty: not wanted)
+    std::string first_out;                 // the value of the first output token in line order: what --serve reports
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
     TexSpec tex;
     TrkSpec trk;
+    BlurSpec blur;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -152,6 +168,7 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::Layers ? it.layers.first_out
            : it.kind == Item::Kind::Tex    ? it.tex.first_out
            : it.kind == Item::Kind::Trk    ? it.trk.out
+           : it.kind == Item::Kind::Blur   ? it.blur.first_out
                                            : it.bg.first_out();
 }
 
@@ -342,6 +359,41 @@ inline bool parse_trk(std::istringstream& tok, TrkSpec& q)
     return true;
 }
 
+inline bool parse_blur(std::istringstream& tok, BlurSpec& q)
+{
+    std::string count, k, v;
+    unsigned long long n = 0, x = 0;
+    if (!(tok >> q.rgb >> count) || split_token(q.rgb, k, v) || !parse_uint(count, 255, n) || n < 1) return false;
+    for (unsigned long long l = 0; l < n; ++l) {
+        std::string m, f;
+        if (!(tok >> m >> f) || split_token(m, k, v) || split_token(f, k, v)) return false;
+        q.masks.push_back(m);
+        q.flows.push_back(f);
+    }
+    if (!(tok >> q.bg) || split_token(q.bg, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "b") {                    // <shutter>,<samples>
+            const size_t comma = v.find(',');
+            if (q.samples != 0 || comma == std::string::npos) return false;
+            if (!parse_bg_maps(v.substr(0, comma), &q.shutter, 1) || !std::isfinite(q.shutter) || q.shutter < 0.f) return false;
+            if (!parse_uint(v.substr(comma + 1), ARAPFLOW_MAX_BLUR_SAMPLES, x) || x < 1) return false;
+            q.samples = (unsigned)x;
+        } else if (k == "m") {
+            if (q.have_m || !parse_bg_maps(v, q.m, 12)) return false;
+            for (float c : q.m)
+                if (!std::isfinite(c)) return false;
+            q.have_m = true;
+        } else if (std::string* dst = field_of({{"rgb1", &q.rgb1}, {"rgb2", &q.rgb2}, {"alpha1", &q.alpha1},
+                                                {"alpha2", &q.alpha2}}, k)) {
+            if (!dst->empty()) return false;
+            *dst = v;
+            if (q.first_out.empty()) q.first_out = v;
+        } else return false;
+    }
+    return q.samples != 0 && !q.first_out.empty();
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -349,15 +401,16 @@ inline Parsed parse_item(const std::string& line, Item& it)
     std::string first;
     if (!(tok >> first)) return Parsed::Skip;
     it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
-              : first == "trk" ? Item::Kind::Trk : Item::Kind::Solve;
+              : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
     else if (it.kind == Item::Kind::Tex) p = parse_tex(tok, it.tex) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Trk) p = parse_trk(tok, it.trk) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::Blur) p = parse_blur(tok, it.blur) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
-        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line"};      // by Item::Kind
+        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

@@ -670,6 +670,66 @@ def retexture_pair(state, rgb, masks, flows, layers):
     return rgb1, r["warped_rgb"], r["warped_mask"]
 
 
+def blur_schedule(centre, shutter, samples, maps=None, lib=None):
+    """the sample times and, with maps = (Ma, Mb), the per-sample sampling maps of an exposure window
+    (ArapFlow_BlurSchedule, DESIGN.md "Motion blur"): (times f32[samples], maps f32[samples,6] or None), the library's own
+    bits.  Host only (no GPU, no state)."""
+    lib = lib or capi.load()
+    n = max(1, min(int(samples), capi.MAX_BLUR_SAMPLES))
+    times, out = (C.c_float * n)(), (C.c_float * (6 * n))() if maps is not None else None
+    Ma, Mb = (_map6(maps[0]), _map6(maps[1])) if maps is not None else (None, None)
+    if lib.ArapFlow_BlurSchedule(centre, shutter, samples, Ma, Mb, times, out) != 0:
+        raise ValueError("ArapFlow_BlurSchedule: bad arguments")
+    return np.array(times[:], np.float32), None if out is None else np.array(out[:], np.float32).reshape(n, 6)
+
+
+def blur_layers(state, rgb, masks, flows_b, centre, shutter, samples, flows_a=None, bg=None, maps=None, want=("rgb", "alpha")):
+    """a motion-blurred frame (ArapFlow_BlurLayers, DESIGN.md "Motion blur"): the integer mean of `samples` layered warps at
+    the times centre + shutter * ((k + 0.5) / samples - 0.5) of the flows (1 - t) * flows_a + t * flows_b.  rgb u8[H,W,3],
+    masks u8[n,H,W] (red channels, 0 = object), flows_b / flows_a f32[n,H,W,2] (flows_a None: all zero); bg u8[bgH,bgW,3]
+    with maps = (Ma, Mb), six floats each (None: both the identity), shows behind the samples that leave a pixel uncovered
+    (numpy) -> (rgb u8[H,W,3], alpha u8[H,W]), None for one that `want` leaves out."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    flows_b = np.ascontiguousarray(flows_b, np.float32)
+    if masks.ndim != 3 or flows_b.shape != masks.shape + (2,):
+        raise ValueError("blur_layers: masks [n,H,W] and flows [n,H,W,2] expected")
+    if flows_a is not None and np.shape(flows_a) != flows_b.shape:
+        raise ValueError("blur_layers: flows_a [n,H,W,2] expected")
+    n, H, W = masks.shape
+    if tuple(np.shape(rgb)) != (H, W, 3):
+        raise ValueError("blur_layers: rgb [H,W,3] expected")
+    if set(want) - {"rgb", "alpha"} or not want:
+        raise ValueError("blur_layers: want some of rgb, alpha")
+    bgW = bgH = 0
+    Ma = Mb = None
+    if bg is not None:
+        bg = np.ascontiguousarray(bg, np.uint8)
+        if bg.ndim != 3 or bg.shape[2] != 3:
+            raise ValueError("blur_layers: bg [bgH,bgW,3] expected")
+        bgH, bgW = bg.shape[:2]
+        ident = (1, 0, 0, 0, 1, 0)
+        Ma, Mb = (_map6(m) for m in (maps if maps is not None else (ident, ident)))
+    elif maps is not None:
+        raise ValueError("blur_layers: maps without bg")
+    samples = int(samples)
+    if state.lib.ArapFlow_BlurLayersScratchBytes(W, H, n, max(samples, 0)) == 0:
+        raise ValueError("blur_layers: 1 <= n <= 255, 1 <= samples <= %d, W * H < 2^31 expected" % capi.MAX_BLUR_SAMPLES)
+    r = _warp_call(state, "BlurLayers", (W, H, n),
+                   [(rgb, np.uint8), (masks, np.uint8), (flows_a, np.float32), (flows_b, np.float32), (float(centre), None),
+                    (float(shutter), None), (samples, None), (bg, np.uint8), (bgW, None), (bgH, None), (Ma, None), (Mb, None)],
+                   [("rgb", (H, W, 3) if "rgb" in want else None, torch.uint8),
+                    ("alpha", (H, W) if "alpha" in want else None, torch.uint8)],
+                   ("BlurLayersScratchBytes", (W, H, n, samples)))
+    return r.get("rgb"), r.get("alpha")
+
+
+def blur_pair(state, rgb, masks, flows, shutter, samples, bg=None, maps=None, want=("rgb", "alpha")):
+    """the two motion-blurred frames of a pair (DESIGN.md "Motion blur"): frame 1 exposed around t = 0 and frame 2 around
+    t = 1, the same shutter and inputs, so the flow between the exposure centres is the pair's own `flows` ->
+    ((rgb1, alpha1), (rgb2, alpha2))"""
+    return tuple(blur_layers(state, rgb, masks, flows, c, shutter, samples, bg=bg, maps=maps, want=want) for c in (0.0, 1.0))
+
+
 BG_OUTPUTS = ("out_rgb1", "out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")
 
 

@@ -14,6 +14,8 @@ functions that tests/golden/host/ pins with hand-computed cases:
   BgLine, parse_bg, bg_line, run_background, fit_bg_window, bg_maps    the `bg` line: moving background (addition)
   mid_bg_files, bg_maps_seq, run_background_seq    its mid= / mm= / mid_out= tokens: the camera per in-between frame (addition)
   TexLayer, TexLine, parse_tex, tex_line, tex_layers, run_texture    the `tex` line: the random-texture twin (addition)
+  blur_times, blur_maps                  the schedule of a motion-blurred frame (addition)
+  BlurLine, parse_blur, blur_line, run_blur    the `blur` line: the motion-blurred frames of a pair (addition)
   TrkLine, parse_trk, trk_line, sample_track_points, run_tracks    the `trk` line: point tracks of a sequence (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
@@ -58,6 +60,8 @@ TEX_WORD = "tex"
 TEX_KEYS = ("rgb1", "rgb2", "mask2")
 TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")         # ARAPFLOW_TEX_*: a kind's number is its index
 TRK_WORD = "trk"
+BLUR_WORD = "blur"
+BLUR_KEYS = ("rgb1", "rgb2", "alpha1", "alpha2")
 
 
 class SolveLine(NamedTuple):
@@ -501,10 +505,122 @@ def run_tracks(state, spec):
     trk.write(spec.out, W, H, np.concatenate([pts["pos"], r["pos"]]), np.concatenate([first[None], r["occ"]]))
 
 
+MAX_BLUR_SAMPLES = 32        # ARAPFLOW_MAX_BLUR_SAMPLES of include/arap_opt.h
+
+
+def blur_times(centre, shutter, samples):
+    """the sample times of an exposure window (ArapFlow_BlurSchedule, DESIGN.md "Motion blur"), float32 [samples]:
+    t_k = centre + shutter * ((k + 0.5) / samples - 0.5), in double from the float32 values of centre and shutter, rounded
+    once to float32"""
+    c, e = float(np.float32(centre)), float(np.float32(shutter))
+    if not 1 <= samples <= MAX_BLUR_SAMPLES or not (math.isfinite(c) and math.isfinite(e) and e >= 0):
+        raise ValueError("blur: 1 .. %d samples, a finite centre, a finite shutter >= 0 expected" % MAX_BLUR_SAMPLES)
+    return np.array([c + e * ((k + 0.5) / samples - 0.5) for k in range(samples)], np.float64).astype(np.float32)
+
+
+def blur_maps(times, Ma, Mb):
+    """the sampling map of every sample (ArapFlow_BlurSchedule), float32 [samples, 6]: u * Ma + t * Mb per coefficient
+    with u = 1 - t, every operation in float32; Ma itself for every sample when Ma and Mb are bit-equal (a still camera)"""
+    Ma, Mb = (np.ascontiguousarray(m, np.float32).reshape(-1) for m in (Ma, Mb))
+    if Ma.shape != (6,) or Mb.shape != (6,) or not (np.isfinite(Ma).all() and np.isfinite(Mb).all()):
+        raise ValueError("blur: two maps of six finite numbers expected")
+    t = np.asarray(times, np.float32)[:, None]
+    if Ma.tobytes() == Mb.tobytes():
+        return np.repeat(Ma[None], len(t), 0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return ((np.float32(1.0) - t) * Ma[None] + t * Mb[None]).astype(np.float32)
+
+
+class BlurLine(NamedTuple):
+    """a `blur` line (DESIGN.md "Motion blur"), recognised by its first word: the two motion-blurred frames of one pair
+        blur RGB1 n MASK_1 FLO_1 ... MASK_n FLO_n BG.png b=<shutter>,<samples> [m=<12 numbers: M1 then M2>]
+             [rgb1=P] [rgb2=P] [alpha1=P] [alpha2=P]
+    The layers are those of the frame's `layers` line (the later on top); BG.png shows behind them.  b=: the shutter, a
+    finite float32 >= 0 written with %.9g, and the sample count, 1 .. MAX_BLUR_SAMPLES.  m=: the camera at frame 1 and at
+    frame 2 as in a bg line, twelve finite float32 written with %.9g (`m` empty: both the identity).  rgb1 / alpha1: the
+    frame exposed around t = 0; rgb2 / alpha2: around t = 1.  `out`: {key: path} in line order.  At least one output;
+    anything else -- an unknown or repeated key, a missing `=`, an empty value, a wrong count of numbers -- is an error."""
+    rgb: str
+    layers: list
+    bg: str
+    shutter: float
+    samples: int
+    m: tuple
+    out: dict
+
+
+def parse_blur(tokens):
+    if len(tokens) < 3 or tokens[0] != BLUR_WORD:
+        raise ValueError("not a blur line: %r" % " ".join(tokens))
+    n = int(tokens[2]) if _UINT.match(tokens[2]) else 0
+    if not 1 <= n <= 255 or len(tokens) < 4 + 2 * n:
+        raise ValueError("blur line: 1..255 layers, a mask and a flow each, then the background: %r" % " ".join(tokens))
+    if any("=" in t for t in tokens[1:4 + 2 * n]):
+        raise ValueError("blur line: a path expected where a token is: %r" % " ".join(tokens))
+    out, b, m = {}, None, None
+    for t in tokens[4 + 2 * n:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in ("b", "m") + BLUR_KEYS) or k in out or (k == "b" and b is not None) or (k == "m" and m is not None):
+            raise ValueError("blur line: bad or repeated token %r" % t)
+        if k == "b":
+            e, _, count = v.partition(",")
+            with np.errstate(over="ignore"):
+                e = _bg_numbers(e)
+            if len(e) != 1 or not (math.isfinite(e[0]) and e[0] >= 0) or not _UINT.match(count) or not 1 <= int(count) <= MAX_BLUR_SAMPLES:
+                raise ValueError("blur line: b= takes a shutter >= 0 and 1..%d samples: %r" % (MAX_BLUR_SAMPLES, t))
+            b = (e[0], int(count))
+        elif k == "m":
+            with np.errstate(over="ignore"):
+                m = _bg_numbers(v)
+            if len(m) != 12 or not all(math.isfinite(q) for q in m):
+                raise ValueError("blur line: m= takes 12 finite numbers, M1 then M2: %r" % t)
+        else:
+            out[k] = v
+    if b is None:
+        raise ValueError("blur line without b=: %r" % " ".join(tokens))
+    if not out:
+        raise ValueError("blur line without an output: %r" % " ".join(tokens))
+    return BlurLine(tokens[1], [(tokens[3 + 2 * l], tokens[4 + 2 * l]) for l in range(n)], tokens[3 + 2 * n], b[0], b[1],
+                    m or (), out)
+
+
+def blur_line(item):
+    """the inverse of parse_blur: b=, m= if the line has maps, then the outputs in the order of BLUR_KEYS"""
+    tok = [BLUR_WORD, item.rgb, str(len(item.layers))] + [p for pair in item.layers for p in pair] + [item.bg]
+    tok.append("b=%.9g,%d" % (float(np.float32(item.shutter)), item.samples))
+    if len(item.m):
+        tok.append("m=" + ",".join("%.9g" % float(np.float32(v)) for v in item.m))
+    return " ".join(tok + ["%s=%s" % (k, item.out[k]) for k in BLUR_KEYS if item.out.get(k)])
+
+
+def run_blur(state, spec):
+    """one `blur` line: read the frame's RGB, every layer's mask and flow and the background picture once, one
+    opt.blur_layers per frame the line asks for (rgb1 / alpha1: centre 0, rgb2 / alpha2: centre 1), write the outputs (rgb:
+    RGB PNG; alpha: 8-bit L PNG)"""
+    from . import opt
+    rgb, bg = load_rgb(spec.rgb), load_rgb(spec.bg)
+    masks = np.stack([load_mask_red(m) for m, _ in spec.layers])
+    flows = np.stack([flo.flow_read(f) for _, f in spec.layers])
+    if masks.shape[1:] != rgb.shape[:2] or flows.shape[1:3] != rgb.shape[:2]:
+        raise ValueError("blur line: image, mask and flow sizes differ")
+    maps = (spec.m[:6], spec.m[6:]) if len(spec.m) else None
+    for frame, centre in (("1", 0.0), ("2", 1.0)):
+        want = tuple(k for k in ("rgb", "alpha") if k + frame in spec.out)
+        if not want:
+            continue
+        r, a = opt.blur_layers(state, rgb, masks, flows, centre, spec.shutter, spec.samples, bg=bg, maps=maps, want=want)
+        if r is not None:
+            Image.fromarray(r).save(spec.out["rgb" + frame])
+        if a is not None:
+            save_occ(a, spec.out["alpha" + frame])
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
-    BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`"""
+    BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == BLUR_WORD:
+        return parse_blur(tok)
     if tok and tok[0] == TRK_WORD:
         return parse_trk(tok)
     if tok and tok[0] == TEX_WORD:
@@ -528,14 +644,18 @@ def format_line(item):
         return tex_line(item)
     if isinstance(item, TrkLine):
         return trk_line(item)
+    if isinstance(item, BlurLine):
+        return blur_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
-    first of a bg line's bg_outputs, a tex line's first output token, a trk line's track file"""
+    first of a bg line's bg_outputs, a tex or blur line's first output token, a trk line's track file"""
     if isinstance(item, TrkLine):
         return item.out
+    if isinstance(item, BlurLine):
+        return next(iter(item.out.values()))
     if isinstance(item, BgLine):
         return bg_outputs(item)[0]
     if isinstance(item, TexLine):

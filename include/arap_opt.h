@@ -473,6 +473,47 @@ typedef struct ArapFlow_TexLayer {
 int ArapFlow_Texture(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
                      const ArapFlow_TexLayer* layers, void* out_rgb);
 
+/* Motion blur (DESIGN.md "Motion blur"): a frame exposed over a window of time, as the integer mean of `samples` layered
+ * warps of the same mesh at `samples` moments of the window.  The layers are ArapFlow_WarpLayersStep's: masks_red
+ * uint8[n][H][W] (0 = object), two states as flows, flows_a and flows_b float32[n][H][W][2], a shared rgb; flows_a == NULL
+ * means all zero and gives the same bytes as an array of zeros.
+ *   times    t_k = centre + shutter * ((k + 0.5) / samples - 0.5), k = 0 .. samples - 1, computed in double from the float32
+ *            centre and shutter and rounded once to float32; samples = 1 gives t_0 = centre.  t may leave [0, 1]: a frame
+ *            exposed around 0 extrapolates the motion backwards for the first half of its window.
+ *   sample   the flow field f = u * a + t * b with u = 1.0f - t, float32, one IEEE operation per operator; sample k is, by
+ *            definition, what ArapFlow_WarpLayers writes as out_rgb / out_mask for flows = f.
+ *   bg       optional: a picture uint8[bgH][bgW][3] and two sampling maps Ma, Mb (six floats each, as in
+ *            ArapFlow_Background).  Sample k sees the picture through u * Ma[i] + t * Mb[i] per coefficient (float32, on the
+ *            host) -- through Ma itself when Ma and Mb are bit-equal -- and a pixel the sample leaves uncovered contributes
+ *            that sample of the picture (ArapFlow_Background's bilinear sample).  Without bg it contributes 0 (out_rgb is
+ *            then premultiplied colour).
+ *   outputs  with sum the integer sum of a channel over the samples and cnt the number of samples that cover the pixel:
+ *            out_rgb = (2 sum + samples) / (2 samples), out_alpha = (2 * 255 * cnt + samples) / (2 samples), integer
+ *            division (round half up).  Either may be NULL, not both.  No float is added across samples: two runs give
+ *            identical bytes.
+ * ArapFlow_BlurSchedule is the one place the times and maps are derived (host only, needs no device; the device call
+ * uses it): times[samples], maps[samples][6] or NULL (Ma and Mb are then not read).  Returns 0, or -1: times NULL, samples
+ * = 0 or > ARAPFLOW_MAX_BLUR_SAMPLES, a non-finite centre, a non-finite or negative shutter, maps without Ma and Mb or
+ * with a non-finite coefficient.
+ * ArapFlow_BlurLayers works on DEVICE buffers (Ma, Mb: HOST).  Samples are rasterised ARAPFLOW_BLUR_CHUNK at a time, each
+ * into a key image of its own, and summed per pixel in registers; no image per sample exists.  `scratch`: 256-byte aligned
+ * device buffer of ArapFlow_BlurLayersScratchBytes(W, H, n, samples) bytes -- per pixel 8 * min(samples, ARAPFLOW_BLUR_CHUNK)
+ * for the keys and 8 more for the carried sums when samples > ARAPFLOW_BLUR_CHUNK; 0 for sizes the call refuses.  The call
+ * clears what it needs of it.  Asynchronous on the state's stream.  Returns 0; -1, and nothing is launched or written, on
+ * bad arguments: a null state, rgb, masks_red, flows_b or scratch, both outputs NULL, n = 0 or n > 255, W * H = 0 or
+ * >= 2^31, samples = 0 or > ARAPFLOW_MAX_BLUR_SAMPLES, a non-finite or negative shutter, a non-finite centre, bg without
+ * both maps or with a zero picture size or a non-finite coefficient, an output overlapping an input; else a HIP error
+ * code. */
+#define ARAPFLOW_MAX_BLUR_SAMPLES 32
+#define ARAPFLOW_BLUR_CHUNK 8
+int ArapFlow_BlurSchedule(float centre, float shutter, unsigned samples, const float Ma[6], const float Mb[6], float* times,
+                          float* maps);
+uint64_t ArapFlow_BlurLayersScratchBytes(unsigned W, unsigned H, unsigned n, unsigned samples);
+int ArapFlow_BlurLayers(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* rgb, const void* masks_red,
+                        const void* flows_a, const void* flows_b, float centre, float shutter, unsigned samples,
+                        const void* bg, unsigned bgW, unsigned bgH, const float Ma[6], const float Mb[6], void* out_rgb,
+                        void* out_alpha, void* scratch);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised

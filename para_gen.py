@@ -4,6 +4,7 @@
   python para_gen.py --input IN --output OUT --gpu 0 1 .. 7 [--fd k] [--size W H] [--multseg] [--resume]
                      [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
                      [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]] [--diag] [--max_fold FRAC] [--retex]
+                     [--bg_dir DIR --blur SHUTTER [SAMPLES]]
                      [--tracks P]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
@@ -57,6 +58,13 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     twin costs no solve and shares the pair's Flow file: OUT/all_files_tex.list names `inpRGB_tex wRGB_tex Flow`.  With
     --bg_dir the twin gets the pair's background; with --bg_motion its warped frame goes through a second bg line with the
     same maps.  The textures are drawn from a random.Random seeded with the pair's id, so a rerun reproduces them.
+  * --blur SHUTTER [SAMPLES] writes the motion-blurred variant of every kept pair (DESIGN.md "Motion blur"):
+    OUT/inpRGB_blur/<seq>/<frame>.png, frame 1 exposed around t = 0, and OUT/wRGB_blur/<seq>/<frame>.png, frame 2 exposed
+    around t = 1, each the integer mean of SAMPLES (default 9) renders of the pair's solved mesh over a window of SHUTTER
+    (in units of the pair's motion) over the pair's background -- with --bg_motion through the camera of every moment --
+    from one `blur` line per pair, handed to a worker once the pair's solves (and layers line) are done and before the
+    segments are merged.  It costs no solve and shares the pair's Flow file (the exposure windows are centred on the two
+    frame times): OUT/all_files_blur.list names `inpRGB_blur wRGB_blur Flow`.  Needs --bg_dir.
 """
 import argparse
 import json
@@ -84,6 +92,7 @@ from arap_flow_amd import pipeline          # noqa: E402
 orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen.py:18-26
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
+color_blur_dir, wrgb_blur_dir = "inpRGB_blur", "wRGB_blur"       # --blur: the motion-blurred pair (addition)
 color_tex_dir, wrgb_tex_dir = "inpRGB_tex", "wRGB_tex"           # --retex: the random-texture twin (addition)
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
 diag_dir, fold_dir = "Diag", "Fold"     # --diag: fold diagnostics (addition)
@@ -211,6 +220,8 @@ class Frame:
     motion_tex: object = None      # --retex --bg_motion: the twin's bg line, handed out after the pair's
     tracks: object = None          # --tracks: the pair's trk line (pipeline.TrkLine), handed out once its solves are done
     pending: int = 0               # main: lines of stage "layers" (the layers line, the trk line) not yet reported done
+    blur: object = None            # --blur: the pair's blur line (pipeline.BlurLine), handed out where a tex line is
+    blur_tmp: tuple = ()           # --blur: the blur line's own input file, deleted when it is done
 
     @property
     def solves(self):
@@ -229,6 +240,7 @@ def prepare_pair(args):
     midl = p.pop("_midl", None)                 # --mid_layers: the snapshot steps of every segment's solve
     tex1, tex2 = p.pop("rgb1tex_gen", None), p.pop("rgb2tex_gen", None)     # --retex: the twin's two frames
     trk_out, n_tracks = p.pop("trk_gen", None), p.pop("_tracks", 0)         # --tracks: the track file, the number of points
+    blur1, blur2 = p.pop("rgb1blur_gen", None), p.pop("rgb2blur_gen", None)     # --blur: the blurred pair's two frames
     layer_masks = []
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
@@ -307,6 +319,19 @@ def prepare_pair(args):
         rng_tex = rn.Random(_pair_id(seq, stem))
         rec.tex = pipeline.TexLine(line.rgb, [(sg.mask, sg.flow) for sg in solved],
                                    tuple(pipeline.tex_layers(rng_tex, len(solved), (W, H))), dict(rgb1=tex1, rgb2=tex2))
+    if blur1 is not None and (bgim is not None or big is not None):
+        # the blurred pair: the solved layers over the pair's background.  A still background is the fitted picture, written
+        # beside the pair's constraints and seen through the identity; a moving one is the bg line's picture and maps (below)
+        for q in (blur1, blur2):
+            os.makedirs(osp.dirname(q), exist_ok=True)
+        shutter, samples = flags.blur
+        bg_png, maps = osp.splitext(p["cstr_tmp"])[0] + "_bg.png", tuple(float(v) for v in np.concatenate([M1, M2])) if big is not None else ()
+        if big is None:
+            bg_png = osp.splitext(p["cstr_tmp"])[0] + "_blurbg.png"
+            Image.fromarray(bgim).save(bg_png)
+            rec.blur_tmp = (bg_png,)
+        rec.blur = pipeline.BlurLine(line.rgb, [(sg.mask, sg.flow) for sg in rec.solves], bg_png, shutter, samples, maps,
+                                     dict(rgb1=blur1, rgb2=blur2))
     if big is not None:
         # the bg line's own inputs, beside the pair's constraints: the enlarged picture as a PNG (the worker's codec),
         # with --multseg the union mask (object where any solved segment is object), and the line itself
@@ -545,6 +570,7 @@ def scan(flags, input_root, output_root):
     roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
                                                            tx1=color_tex_dir, tx2=wrgb_tex_dir, trk=tracks_dir,
+                                                           bl1=color_blur_dir, bl2=wrgb_blur_dir,
                                                            obw=occ_bwd_dir, occ=occ_dir, dia=diag_dir, fol=fold_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
                                                            ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
@@ -579,6 +605,8 @@ def scan(flags, input_root, output_root):
                     e["mid_gen"] = osp.join(roots["mid"], seq, f)
                 if getattr(flags, "retex", False):
                     e.update(rgb1tex_gen=osp.join(roots["tx1"], seq, f + ".png"), rgb2tex_gen=osp.join(roots["tx2"], seq, f + ".png"))
+                if getattr(flags, "blur", None):
+                    e.update(rgb1blur_gen=osp.join(roots["bl1"], seq, f + ".png"), rgb2blur_gen=osp.join(roots["bl2"], seq, f + ".png"))
                 if getattr(flags, "bg_motion", None) is not None:       # the full-frame maps of what the run asks for
                     e["flowfull_gen"] = osp.join(roots["ful"], seq, f + ".flo")
                     if "occ_gen" in e or LAYERS_OCC in e:
@@ -601,7 +629,7 @@ def scan(flags, input_root, output_root):
                     e["_midbg"] = tuple(flags.mid_steps or flags.mid_layers_steps)
                 # every requested output
                 done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e) + mid_bg_paths(e)
-                done += track_paths(e)
+                done += track_paths(e) + [e[k] for k in ("rgb1blur_gen", "rgb2blur_gen") if k in e]
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -671,6 +699,11 @@ def write_lists(flags, output_root, all_paths):
         twins = [[by_trio[t]["rgb1tex_gen"], by_trio[t]["rgb2tex_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
         open(osp.join(output_root, "all_files_tex.list"), "w").write(
             "\n".join(" ".join(t) for t in twins if all(osp.exists(q) for q in t)))
+    if getattr(flags, "blur", None):                       # the blurred variants of the listed pairs: the SAME flow
+        by_trio = {" ".join(pipeline.make_arap_path(p)[k] for k in (0, 4, 3)): p for p in all_paths}
+        blurred = [[by_trio[t]["rgb1blur_gen"], by_trio[t]["rgb2blur_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
+        open(osp.join(output_root, "all_files_blur.list"), "w").write(
+            "\n".join(" ".join(t) for t in blurred if all(osp.exists(q) for q in t)))
     return out_paths, rejected
 
 
@@ -703,7 +736,7 @@ def main(flags):
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
     frames = {}                                        # done token of a line a worker holds -> its Frame
     posts, lock = [], threading.Lock()
-    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0, tracks_done=0)
+    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0, tracks_done=0, blur_done=0)
 
     def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
         frames[pipeline.done_token(item)] = rec
@@ -729,8 +762,12 @@ def main(flags):
                         if osp.exists(q):
                             os.remove(q)
                 return
-            if rec.stage == "tex":                     # its tex line: the segment files may go now
-                counts["tex_done"] += 1
+            if rec.stage == "tex":                     # its tex (or blur) line: the segment files may go now
+                counts["tex_done" if rec.tex is not None else "blur_done"] += 1
+                if rec.remove:
+                    for q in rec.blur_tmp:
+                        if osp.exists(q):
+                            os.remove(q)
             elif rec.stage == "layers":                # its layers line or its trk line: both read the segments' snapshots,
                 if rec.tracks is not None and path == rec.tracks.out:          # which go only when both are done
                     counts["tracks_done"] += 1
@@ -752,9 +789,10 @@ def main(flags):
                     for q in later:
                         hand_out(rec, q, workers.put_owed)
                     return
-            if rec.tex is not None and rec.stage != "tex":      # the twin reads the segments' flows: before finish_frame
+            twin = rec.tex if rec.tex is not None else rec.blur       # (--retex and --blur exclude each other)
+            if twin is not None and rec.stage != "tex":        # the twin reads the segments' flows: before finish_frame
                 rec.stage = "tex"
-                hand_out(rec, rec.tex, workers.put_owed)
+                hand_out(rec, twin, workers.put_owed)
                 return
             counts["frames_done"] += 1
             if rec.motion is None:
@@ -789,7 +827,7 @@ def main(flags):
                 workers.owe()
             if rec.motion is not None:
                 workers.owe()
-            for later in (rec.tex, rec.motion_tex, rec.tracks):
+            for later in (rec.tex, rec.motion_tex, rec.tracks, rec.blur):
                 if later is not None:
                     workers.owe()
             with lock:
@@ -813,7 +851,7 @@ def main(flags):
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
                  layers_done=counts["layers_done"], bg_done=counts["bg_done"], tex_done=counts["tex_done"],
-                 tracks_done=counts["tracks_done"],
+                 tracks_done=counts["tracks_done"], blur_done=counts["blur_done"],
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -921,7 +959,32 @@ def parse(argv=None):
                         help="with --mid K or --multseg --mid_layers K: also write the tracks of P query points of frame 1 "
                              "through the K in-between frames to frame 2, sub-pixel positions and occluded flags: "
                              "OUT/Tracks/<seq>/<frame>.trk (DESIGN.md \"Point tracks\")")
+    parser.add_argument("--blur", nargs="+", default=None, metavar=("SHUTTER", "SAMPLES"),
+                        help="with --bg_dir: also write the motion-blurred variant of every pair: OUT/inpRGB_blur/<seq>/"
+                             "<frame>.png and OUT/wRGB_blur/<seq>/<frame>.png, frame 1 and frame 2 exposed over a window of "
+                             "SHUTTER (in units of the pair's motion, centred on the frame) as the mean of SAMPLES renders "
+                             "(1 .. 32, default 9), and OUT/all_files_blur.list, whose lines name those two and the pair's own "
+                             "Flow file (DESIGN.md \"Motion blur\")")
     flags = parser.parse_args(argv)
+    if flags.blur is not None:
+        try:
+            if len(flags.blur) > 2:
+                raise ValueError
+            shutter = float(np.float32(float(flags.blur[0])))
+            samples = int(flags.blur[1]) if len(flags.blur) == 2 else 9
+        except (ValueError, OverflowError):
+            parser.error("--blur SHUTTER [SAMPLES]: a number and an optional integer")
+        if not (np.isfinite(shutter) and shutter >= 0) or not 1 <= samples <= pipeline.MAX_BLUR_SAMPLES:
+            parser.error("--blur SHUTTER [SAMPLES]: a finite SHUTTER >= 0 and 1 .. %d SAMPLES" % pipeline.MAX_BLUR_SAMPLES)
+        flags.blur = (shutter, samples)
+        if not flags.bg_dir:
+            parser.error("--blur needs --bg_dir: a blurred object needs a defined background behind it")
+        if flags.mid or flags.mid_layers or flags.mid_bg or flags.retex:
+            parser.error("--blur cannot be combined with --mid / --mid_layers / --mid_bg / --retex: blurred sequences and "
+                         "blurred twins are made with opt.blur_layers, not from this command line")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--blur needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
+                         "not know the blur line")
     if flags.tracks:
         if not 1 <= flags.tracks <= 1 << 24:
             parser.error("--tracks P: 1 .. 2^24 points")
