@@ -7,9 +7,10 @@
 A list line may carry optional output tokens after its six paths (backward flow, forward and backward occlusion), and
 a line whose first word is `layers` is no solve but the layered warp of one frame, one whose first word is `bg` the
 moving-background pass of one pair, one whose first word is `tex` the random-texture twin of one frame, one whose first
-word is `trk` the point tracks of one sequence, one whose first word is `blur` the motion-blurred frames of one pair: the
-forms are defined in arap_flow_amd/pipeline.py (SolveLine, parse_layers, BgLine, TexLine, TrkLine, BlurLine).  A layers, bg,
-tex, trk or blur line runs once every earlier line of the list is solved and written (its inputs may be their outputs).
+word is `trk` the point tracks of one sequence, one whose first word is `blur` the motion-blurred frames of one pair, one
+whose first word is `light` the relit frames of one pair: the forms are defined in arap_flow_amd/pipeline.py (SolveLine,
+parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine).  A layers, bg, tex, trk, blur or light line runs once every
+earlier line of the list is solved and written (its inputs may be their outputs).
 
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
 same border pins, same outputs (.flo + two PNGs).  ARAP_PLAN may name the reference's arap_plan.t; it is then
@@ -63,7 +64,7 @@ def main(argv):
         if not pr:
             return 1
         state.lib.Opt_ProblemDelete(state.handle, pr)
-    # runs of solve lines go to the batched solver; a layers, bg, tex, trk or blur line waits for the run before it
+    # runs of solve lines go to the batched solver; a layers, bg, tex, trk, blur or light line waits for the run before it
     k = 0
     while k < len(lines):
         if not isinstance(lines[k], pipeline.SolveLine):
@@ -75,6 +76,8 @@ def main(argv):
                 pipeline.run_tracks(state, lines[k])
             elif isinstance(lines[k], pipeline.BlurLine):
                 pipeline.run_blur(state, lines[k])
+            elif isinstance(lines[k], pipeline.LightLine):
+                pipeline.run_light(state, lines[k])
             else:
                 pipeline.run_layers(state, lines[k])
             print("Saved")

@@ -29,6 +29,13 @@ class TexLayer(C.Structure):
                 ("c0", C.c_uint8 * 3), ("c1", C.c_uint8 * 3), ("c2", C.c_uint8 * 3), ("reserved", C.c_uint8 * 3)]
 
 
+class LightFrame(C.Structure):
+    """ArapFlow_LightFrame (DESIGN.md "Relit frames")"""
+    _fields_ = [("seed", C.c_uint32), ("m", C.c_float * 6), ("amp", C.c_float), ("vig", C.c_float), ("gain", C.c_float * 3),
+                ("gamma", C.c_float), ("sh_dx", C.c_int32), ("sh_dy", C.c_int32), ("sh_r", C.c_int32), ("sh_g", C.c_int32),
+                ("sigma0", C.c_float), ("sigma1", C.c_float)]
+
+
 TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")      # ARAPFLOW_TEX_*: a kind's number is its index here
 
 MESH_STATS_KEYS = tuple(k for k, _ in MeshStats._fields_ if k != "reserved")     # the order of a diag file's lines
@@ -106,6 +113,8 @@ SYMBOLS = [
     ("ArapFlow_BlurLayersScratchBytes", C.c_uint64, [_U, _U, _U, _U]),
     ("ArapFlow_BlurLayers", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _U, _VP, _U, _U,
                                  C.POINTER(C.c_float), C.POINTER(C.c_float), _VP, _VP, _VP]),
+    ("ArapFlow_LightTables", _I, [C.POINTER(LightFrame), _U, _U, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
+    ("ArapFlow_Relight", _I, [_VP, _U, _U, _VP, _VP, _I, C.POINTER(LightFrame), _VP]),
     ("ArapFlow_WarpDiag", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP]),
     ("ArapFlow_SolverSetDiag", _I, [_VP, _I]),
     ("ArapFlow_SolverGetDiag", _I, [_VP, _U, C.POINTER(MeshStats), _VP]),
@@ -115,6 +124,7 @@ SYMBOLS = [
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h
 MAX_SNAPSHOTS = 8                       # ARAPFLOW_MAX_SNAPSHOTS
 MAX_BLUR_SAMPLES, BLUR_CHUNK = 32, 8    # ARAPFLOW_MAX_BLUR_SAMPLES, ARAPFLOW_BLUR_CHUNK
+LIGHT_MAX_R, LIGHT_MAX_SHIFT = 16, 64   # ARAPFLOW_LIGHT_MAX_R, ARAPFLOW_LIGHT_MAX_SHIFT
 
 _LIB = None
 

@@ -113,6 +113,7 @@ void ArapFlow_FreeState(Opt_State* st)
     st->ktimer.clear();
     if (st->diag) (void)hipFree(st->diag);
     if (st->tex) (void)hipFree(st->tex);
+    if (st->light) (void)hipFree(st->light);
     delete st;
 }
 

@@ -4,7 +4,8 @@
 // Then the point tracks of a sequence (ArapFlow_TrackPoints, arap_track.h), with a scratch layout of their own.
 // Last, the moving-background post-pass (ArapFlow_BackgroundMaps / Background / BackgroundSeq, arap_bg.h), which needs no
 // scratch, the random textures of a frame's objects (ArapFlow_Texture, arap_tex.h) and the motion-blurred frames
-// (ArapFlow_BlurSchedule / BlurLayers, arap_blur.h), with a scratch layout of their own.
+// (ArapFlow_BlurSchedule / BlurLayers, arap_blur.h), with a scratch layout of their own, and the relit frames
+// (ArapFlow_LightTables / Relight, arap_light.h), which need only a 768-byte table.
 #pragma once
 
 // the optional outputs (arap_occ.h) of `njobs` jobs at `dj`, between k_warp_raster and k_warp_resolve.  `cells`:
@@ -546,6 +547,66 @@ int ArapFlow_BlurLayers(Opt_State* st, unsigned W, unsigned H, unsigned n, const
                            (int)W, (int)H);
         hipLaunchKernelGGL(k_blur_accum, dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, stream, f, ch, (int)W, (int)H);
     }
+    return (int)hipGetLastError();
+}
+
+static_assert(LIGHT_MAX_R == ARAPFLOW_LIGHT_MAX_R && LIGHT_MAX_SHIFT == ARAPFLOW_LIGHT_MAX_SHIFT, "light limits");
+
+// the ranges of include/arap_opt.h, one test for ArapFlow_LightTables and ArapFlow_Relight
+static bool light_frame_ok(const ArapFlow_LightFrame& q)
+{
+    for (float c : q.m)
+        if (!std::isfinite(c)) return false;
+    for (float g : q.gain)
+        if (!std::isfinite(g) || !(g > 0.f)) return false;
+    if (!std::isfinite(q.gamma) || !(q.gamma > 0.f)) return false;
+    if (!std::isfinite(q.amp) || !(q.amp >= 0.f) || !(q.vig >= 0.f && q.vig <= 1.f)) return false;
+    if (!std::isfinite(q.sigma0) || !(q.sigma0 >= 0.f) || !std::isfinite(q.sigma1) || !(q.sigma1 >= 0.f)) return false;
+    if (q.sh_dx < -LIGHT_MAX_SHIFT || q.sh_dx > LIGHT_MAX_SHIFT || q.sh_dy < -LIGHT_MAX_SHIFT || q.sh_dy > LIGHT_MAX_SHIFT) return false;
+    return q.sh_r >= 0 && q.sh_r <= LIGHT_MAX_R && q.sh_g >= 0 && q.sh_g <= 256;
+}
+
+int ArapFlow_LightTables(const ArapFlow_LightFrame* frame, unsigned W, unsigned H, uint8_t lut[3][256], float geom[3])
+{
+    if (!frame || !lut || !geom || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31) || !light_frame_ok(*frame)) return -1;
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < 256; ++i) {
+            const double t = (double)frame->gain[c] * pow((double)i / 255.0, (double)frame->gamma);
+            lut[c][i] = (uint8_t)floor(255.0 * fmin(fmax(t, 0.0), 1.0) + 0.5);
+        }
+    const double cx = ((double)W - 1.0) / 2.0, cy = ((double)H - 1.0) / 2.0, r2 = cx * cx + cy * cy;
+    geom[0] = (float)cx; geom[1] = (float)cy; geom[2] = r2 > 0.0 ? (float)(1.0 / r2) : 0.0f;
+    return 0;
+}
+
+int ArapFlow_Relight(Opt_State* st, unsigned W, unsigned H, const void* rgb, const void* cover, int cover_is_mask,
+                     const ArapFlow_LightFrame* frame, void* out_rgb)
+{
+    if (!st || !rgb || !frame || !out_rgb) return -1;
+    uint8_t lut[3][256];
+    float geom[3];
+    if (ArapFlow_LightTables(frame, W, H, lut, geom) != 0) return -1;
+    const bool shadow = frame->sh_g > 0;
+    if (shadow && !cover) return -1;
+    const uint64_t N = (uint64_t)W * H;
+    auto overlaps = [&](const void* in, uint64_t bytes) {               // [in, in + bytes) and out_rgb's 3 N bytes
+        const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out_rgb;
+        return in && a < o + 3 * N && o < a + bytes;
+    };
+    if (overlaps(rgb, 3 * N) || overlaps(cover, N)) return -1;
+    LightParams q{};
+    q.seed = frame->seed; q.m = bg_map(frame->m);
+    q.amp = frame->amp; q.vig = frame->vig;
+    q.cx = geom[0]; q.cy = geom[1]; q.inv_r2 = geom[2];
+    q.sh_dx = frame->sh_dx; q.sh_dy = frame->sh_dy; q.sh_r = frame->sh_r; q.sh_g = frame->sh_g;
+    q.sigma0 = frame->sigma0; q.sigma1 = frame->sigma1;
+    HC(hipSetDevice(st->device));
+    if (!st->light && hipMalloc(&st->light, sizeof(lut)) != hipSuccess) return (int)hipErrorOutOfMemory;
+    HC(hipMemcpyAsync(st->light, lut, sizeof(lut), hipMemcpyHostToDevice, st->stream));   // (pageable: staged before the call returns)
+    const dim3 grid((W + 63) / 64, (H + 3) / 4), block(64, 4);
+    const auto kernel = !shadow ? k_relight<false, false> : cover_is_mask ? k_relight<true, true> : k_relight<true, false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, st->stream, (const uint8_t*)rgb, (const uint8_t*)cover, (const uint8_t*)st->light,
+                       q, (uint8_t*)out_rgb, (int)W, (int)H);
     return (int)hipGetLastError();
 }
 

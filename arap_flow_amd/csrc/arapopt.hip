@@ -40,6 +40,7 @@
 #include "arap_bg.h"
 #include "arap_tex.h"
 #include "arap_blur.h"
+#include "arap_light.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
 

@@ -119,6 +119,7 @@ struct Opt_State {
     int stream_a = 0;           // ARAPOPT_STREAM_A=1 (experiments): the tiled k_pcg_a_grid instead of the marching kernel
     void* diag = nullptr;       // ArapFlow_WarpDiag: device, the call's WarpJob (256 bytes) and its accumulator; at first use
     void* tex = nullptr;        // ArapFlow_Texture: device, the call's layer table (255 layers); at first use
+    void* light = nullptr;      // ArapFlow_Relight: device, the call's tone table (3 x 256 bytes); at first use
 };
 
 struct Opt_Problem {

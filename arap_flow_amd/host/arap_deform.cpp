@@ -40,6 +40,10 @@
 //        [rgb1=P] [rgb2=P] [alpha1=P] [alpha2=P]
 // (the layers of the frame's layers line; BG.png shows behind them through the cameras of m=, the identity without it; at
 // least one output).  rgb1 / alpha1: the frame exposed around t = 0; rgb2 / alpha2: around t = 1, the same shutter.
+// A line whose first word is `light` is the relit variant of one pair (DESIGN.md "Relit frames"):
+//   light RGB1 MASK1 RGB2 COVER2 l=<frame 1>;<frame 2> [rgb1=P] [rgb2=P]
+// (the pair's finished frames; MASK1 in the solver's convention, COVER2 a cover; a frame of l= is the 19 numbers of
+// ArapFlow_LightFrame; at least one output).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -314,6 +318,37 @@ static bool run_blur(Opt_State* state, const BlurSpec& q)
     return ok ? out.write() : fail("ArapFlow_BlurLayers failed\n");
 }
 
+// the relit frames of one pair, synchronously (pipeline.run_light): per frame the line asks for, read the frame and its
+// mask (red channel), one ArapFlow_Relight on the state's stream -- frame 1 with MASK1 in the solver's convention, frame 2
+// with COVER2 as a cover --, write the output
+static bool run_light(Opt_State* state, const LightSpec& q)
+{
+    for (int f = 0; f < 2; ++f) {
+        const std::string& out_path = f ? q.out2 : q.out1;
+        if (out_path.empty()) continue;
+        const std::string &rgb_path = f ? q.rgb2 : q.rgb1, &mask_path = f ? q.cover2 : q.mask1;
+        arapio::Image rgb, msk;
+        if (!read_png(rgb_path, rgb) || !read_png(mask_path, msk)) return false;
+        if (msk.w != rgb.w || msk.h != rgb.h)
+            return fail("light: %s differs in size from %s\n", mask_path.c_str(), rgb_path.c_str());
+        const size_t N = (size_t)rgb.w * rgb.h;
+        std::vector<uint8_t> cover(N);
+        for (size_t i = 0; i < N; ++i) cover[i] = msk.rgb[3 * i];             // red channel
+        DeviceArena dev;
+        const size_t d_rgb = dev.stage(rgb.rgb.data(), 3 * N), d_cov = dev.stage(cover.data(), N);
+        OutputTable out(dev, rgb.w, rgb.h);
+        const size_t o_rgb = out.add(FileKind::rgb, out_path);
+        if (dev.alloc() != hipSuccess) return fail("light: out of device memory\n");
+        const bool ok = dev.upload() == hipSuccess &&
+                        ArapFlow_Relight(state, (unsigned)rgb.w, (unsigned)rgb.h, dev.at(d_rgb), dev.at(d_cov), f == 0, &q.frames[f],
+                                         out.dev(o_rgb)) == 0 &&
+                        hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
+        if (!ok) return fail("ArapFlow_Relight failed\n");
+        if (!out.write()) return false;
+    }
+    return true;
+}
+
 // the point tracks of one sequence, synchronously (pipeline.run_tracks): read the points, every layer's mask and its T
 // state flows, one ArapFlow_TrackPoints on the state's stream, write the track file: the points themselves as frame 0
 // (occ by the frame test), then the T states
@@ -567,7 +602,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex / trk / blur line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur / light line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -847,6 +882,7 @@ int main(int argc, const char* argv[])
                   : kind == Item::Kind::Tex ? run_texture(state, fr->item.tex)
                   : kind == Item::Kind::Trk ? run_tracks(state, fr->item.trk)
                   : kind == Item::Kind::Blur ? run_blur(state, fr->item.blur)
+                  : kind == Item::Kind::Light ? run_light(state, fr->item.light)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

@@ -65,6 +65,21 @@ static std::string canonical(const Item& it)
             m += num;
         }
         c.token("m", m); c.token("rgb1", q.rgb1); c.token("rgb2", q.rgb2); c.token("alpha1", q.alpha1); c.token("alpha2", q.alpha2);
+    } else if (it.kind == Item::Kind::Light) {
+        const LightSpec& q = it.light;
+        c.word("light"); c.word(q.rgb1); c.word(q.mask1); c.word(q.rgb2); c.word(q.cover2);
+        std::string l;
+        char num[64];
+        for (int f = 0; f < 2; ++f) {
+            const ArapFlow_LightFrame& a = q.frames[f];
+            snprintf(num, sizeof(num), "%s%u", f ? ";" : "", a.seed);
+            l += num;
+            const float fl[12] = {a.m[0], a.m[1], a.m[2], a.m[3], a.m[4], a.m[5], a.amp, a.vig, a.gain[0], a.gain[1], a.gain[2], a.gamma};
+            for (float v : fl) { snprintf(num, sizeof(num), ",%.9g", v); l += num; }
+            snprintf(num, sizeof(num), ",%d,%d,%d,%d,%.9g,%.9g", a.sh_dx, a.sh_dy, a.sh_r, a.sh_g, a.sigma0, a.sigma1);
+            l += num;
+        }
+        c.token("l", l); c.token("rgb1", q.out1); c.token("rgb2", q.out2);
     } else {
         const BgSpec& q = it.bg;
         c.word("bg");

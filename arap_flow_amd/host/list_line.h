@@ -17,7 +17,10 @@
 //                 [rgb1=P] [rgb2=P] [alpha1=P] [alpha2=P]
 //                 (pipeline.BlurLine): the shutter a finite number >= 0, 1 .. ARAPFLOW_MAX_BLUR_SAMPLES samples, the maps
 //                 finite; without m= both maps are the identity; a repeated key is an error too
-//                 on these five any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   light line:   light RGB1 MASK1 RGB2 COVER2 l=<frame 1>;<frame 2> [rgb1=P] [rgb2=P]
+//                 (pipeline.LightLine): a frame the 19 numbers of ArapFlow_LightFrame in field order, every one in the
+//                 range ArapFlow_LightTables accepts; a repeated key is an error too
+//                 on these six any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -87,7 +90,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the six forms
+// ---- the seven forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -151,14 +154,23 @@ struct BlurSpec {                          // pipeline.BlurLine
     std::string first_out;                 // the value of the first output token in line order: what --serve reports
 };
 
+struct LightSpec {                         // pipeline.LightLine
+    std::string rgb1, mask1, rgb2, cover2;
+    bool have_l = false;
+    ArapFlow_LightFrame frames[2] = {};
+    std::string out1, out2;                // outputs rgb1=, rgb2= (empty: not wanted)
+    std::string first_out;                 // the value of the first output token in line order: what --serve reports
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
     TexSpec tex;
     TrkSpec trk;
     BlurSpec blur;
+    LightSpec light;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -169,6 +181,7 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::Tex    ? it.tex.first_out
            : it.kind == Item::Kind::Trk    ? it.trk.out
            : it.kind == Item::Kind::Blur   ? it.blur.first_out
+           : it.kind == Item::Kind::Light  ? it.light.first_out
                                            : it.bg.first_out();
 }
 
@@ -394,6 +407,71 @@ inline bool parse_blur(std::istringstream& tok, BlurSpec& q)
     return q.samples != 0 && !q.first_out.empty();
 }
 
+// 1 to 10 decimal digits after an optional `-`, nothing else
+inline bool parse_int(const std::string& v, long long& x)
+{
+    const bool neg = !v.empty() && v[0] == '-';
+    unsigned long long u = 0;
+    if (!parse_uint(neg ? v.substr(1) : v, 9999999999ull, u)) return false;
+    x = neg ? -(long long)u : (long long)u;
+    return true;
+}
+
+// one frame of l=: 19 numbers, comma separated (pipeline.LightFrame), in the ranges ArapFlow_LightTables accepts
+inline bool parse_light_frame(const std::string& v, ArapFlow_LightFrame& q)
+{
+    std::vector<std::string> f(1);
+    for (char c : v) {
+        if (c == ',') f.emplace_back();
+        else f.back() += c;
+    }
+    if (f.size() != 19) return false;
+    unsigned long long x = 0;
+    if (!parse_uint(f[0], 0xffffffffull, x)) return false;
+    q.seed = (uint32_t)x;
+    float fl[14];
+    for (int k = 0; k < 14; ++k)
+        if (!parse_bg_maps(f[k < 12 ? 1 + k : 5 + k], fl + k, 1)) return false;
+    for (int k = 0; k < 6; ++k) q.m[k] = fl[k];
+    q.amp = fl[6]; q.vig = fl[7];
+    for (int k = 0; k < 3; ++k) q.gain[k] = fl[8 + k];
+    q.gamma = fl[11]; q.sigma0 = fl[12]; q.sigma1 = fl[13];
+    long long s[4];
+    if (!parse_int(f[13], s[0]) || !parse_int(f[14], s[1])) return false;
+    for (int k = 2; k < 4; ++k) {
+        if (!parse_uint(f[13 + k], 9999999999ull, x)) return false;
+        s[k] = (long long)x;
+    }
+    for (long long t : s)
+        if (t < -1000000 || t > 1000000) return false;             // (out of range anyway; what is left fits an int32)
+    q.sh_dx = (int32_t)s[0]; q.sh_dy = (int32_t)s[1]; q.sh_r = (int32_t)s[2]; q.sh_g = (int32_t)s[3];
+    uint8_t lut[3][256];
+    float geom[3];
+    return ArapFlow_LightTables(&q, 1, 1, lut, geom) == 0;         // the ranges, stated once (host only)
+}
+
+inline bool parse_light(std::istringstream& tok, LightSpec& q)
+{
+    std::string k, v;
+    if (!(tok >> q.rgb1 >> q.mask1 >> q.rgb2 >> q.cover2)) return false;
+    for (const std::string* p : {&q.rgb1, &q.mask1, &q.rgb2, &q.cover2})
+        if (split_token(*p, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "l") {                    // two frames separated by `;`
+            const size_t semi = v.find(';');
+            if (q.have_l || semi == std::string::npos) return false;
+            if (!parse_light_frame(v.substr(0, semi), q.frames[0]) || !parse_light_frame(v.substr(semi + 1), q.frames[1])) return false;
+            q.have_l = true;
+        } else if (std::string* dst = field_of({{"rgb1", &q.out1}, {"rgb2", &q.out2}}, k)) {
+            if (!dst->empty()) return false;
+            *dst = v;
+            if (q.first_out.empty()) q.first_out = v;
+        } else return false;
+    }
+    return q.have_l && !q.first_out.empty();
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -401,16 +479,18 @@ inline Parsed parse_item(const std::string& line, Item& it)
     std::string first;
     if (!(tok >> first)) return Parsed::Skip;
     it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
-              : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : Item::Kind::Solve;
+              : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : first == "light" ? Item::Kind::Light
+              : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
     else if (it.kind == Item::Kind::Tex) p = parse_tex(tok, it.tex) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Trk) p = parse_trk(tok, it.trk) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Blur) p = parse_blur(tok, it.blur) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::Light) p = parse_light(tok, it.light) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
-        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line"};      // by Item::Kind
+        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

@@ -730,6 +730,59 @@ def blur_pair(state, rgb, masks, flows, shutter, samples, bg=None, maps=None, wa
     return tuple(blur_layers(state, rgb, masks, flows, c, shutter, samples, bg=bg, maps=maps, want=want) for c in (0.0, 1.0))
 
 
+def light_frame(frame):
+    """a frame's light description (seed, m[6], amp, vig, gain[3], gamma, sh_dx, sh_dy, sh_r, sh_g, sigma0, sigma1) --
+    pipeline.LightFrame -- as the ArapFlow_LightFrame the library reads; floats are rounded to float32 here"""
+    seed, m, amp, vig, gain, gamma, sh_dx, sh_dy, sh_r, sh_g, sigma0, sigma1 = frame
+    q = capi.LightFrame()
+    q.seed = int(seed) & 0xffffffff
+    q.m = _map6(m)
+    q.amp, q.vig, q.gamma, q.sigma0, q.sigma1 = float(amp), float(vig), float(gamma), float(sigma0), float(sigma1)
+    if len(gain) != 3:
+        raise ValueError("a tone curve has three gains")
+    q.gain = (C.c_float * 3)(*[float(g) for g in gain])
+    q.sh_dx, q.sh_dy, q.sh_r, q.sh_g = (max(-1 << 31, min(int(v), (1 << 31) - 1)) for v in (sh_dx, sh_dy, sh_r, sh_g))
+    return q
+
+
+def light_tables(frame, W, H, lib=None):
+    """the tone table and the vignette's geometry of a light description on a W x H frame (ArapFlow_LightTables, DESIGN.md
+    "Relit frames"): (lut u8[3,256], geom f32[3] = (cx, cy, inv_r2)), the library's own bits.  Host only (no GPU, no
+    state).  A description outside its ranges is a ValueError."""
+    lib = lib or capi.load()
+    lut, geom = (C.c_uint8 * 768)(), (C.c_float * 3)()
+    if not (0 <= int(W) < 1 << 32 and 0 <= int(H) < 1 << 32) or \
+            lib.ArapFlow_LightTables(C.byref(light_frame(frame)), int(W), int(H), lut, geom) != 0:
+        raise ValueError("ArapFlow_LightTables: bad arguments")
+    return np.array(lut[:], np.uint8).reshape(3, 256), np.array(geom[:], np.float32)
+
+
+def relight(state, rgb, cover, frame, cover_is_mask=False):
+    """a finished frame under one light description (ArapFlow_Relight, DESIGN.md "Relit frames"): the objects' shadow on
+    the background, the tone curve, the illumination field, the vignette and the noise.  rgb u8[H,W,3]; cover u8[H,W]
+    (object: != 0, or == 0 with cover_is_mask, the solver's convention) or None when the description has no shadow;
+    frame: a pipeline.LightFrame (numpy) -> the relit frame u8[H,W,3]."""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("relight: rgb [H,W,3] expected")
+    H, W = rgb.shape[:2]
+    if cover is not None and tuple(np.shape(cover)) != (H, W):
+        raise ValueError("relight: cover [H,W] expected")
+    r = _warp_call(state, "Relight", (W, H),
+                   [(rgb, np.uint8), (cover, np.uint8), (int(bool(cover_is_mask)), None), (C.byref(light_frame(frame)), None)],
+                   [("rgb", (H, W, 3), torch.uint8)])
+    return r["rgb"]
+
+
+def relight_pair(state, rgb1, mask1, rgb2, cover2, frames):
+    """the relit variant of a pair (DESIGN.md "Relit frames"): frame 1 under frames[0] with mask1 read in the solver's
+    convention (object: == 0), frame 2 under frames[1] with cover2 read as a cover (object: != 0) -- the two masks a solve
+    and its warp leave.  The geometry is untouched: the pair's flow is shared -> (rgb1_light, rgb2_light)"""
+    if len(frames) != 2:
+        raise ValueError("relight_pair: two light descriptions expected")
+    return relight(state, rgb1, mask1, frames[0], cover_is_mask=True), relight(state, rgb2, cover2, frames[1])
+
+
 BG_OUTPUTS = ("out_rgb1", "out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")
 
 

@@ -16,6 +16,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   TexLayer, TexLine, parse_tex, tex_line, tex_layers, run_texture    the `tex` line: the random-texture twin (addition)
   blur_times, blur_maps                  the schedule of a motion-blurred frame (addition)
   BlurLine, parse_blur, blur_line, run_blur    the `blur` line: the motion-blurred frames of a pair (addition)
+  LightFrame, LightLine, parse_light, light_line, random_light, run_light    the `light` line: the relit pair (addition)
   TrkLine, parse_trk, trk_line, sample_track_points, run_tracks    the `trk` line: point tracks of a sequence (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
@@ -62,6 +63,8 @@ TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")         # ARAPFLOW_
 TRK_WORD = "trk"
 BLUR_WORD = "blur"
 BLUR_KEYS = ("rgb1", "rgb2", "alpha1", "alpha2")
+LIGHT_WORD = "light"
+LIGHT_KEYS = ("rgb1", "rgb2")
 
 
 class SolveLine(NamedTuple):
@@ -615,10 +618,201 @@ def run_blur(state, spec):
             save_occ(a, spec.out["alpha" + frame])
 
 
+LIGHT_MAX_R, LIGHT_MAX_SHIFT = 16, 64      # ARAPFLOW_LIGHT_MAX_R, ARAPFLOW_LIGHT_MAX_SHIFT of include/arap_opt.h
+
+
+class LightFrame(NamedTuple):
+    """one frame's light (ArapFlow_LightFrame, DESIGN.md "Relit frames"), 19 numbers in this order: seed, 32 bits; m, six
+    float32 (pixel -> field point); amp >= 0; vig, 0 .. 1; gain, three float32 > 0; gamma > 0; sh_dx, sh_dy, integers of
+    magnitude <= LIGHT_MAX_SHIFT; sh_r, 0 .. LIGHT_MAX_R; sh_g, 0 .. 256; sigma0, sigma1 >= 0; every float finite"""
+    seed: int
+    m: tuple
+    amp: float
+    vig: float
+    gain: tuple
+    gamma: float
+    sh_dx: int
+    sh_dy: int
+    sh_r: int
+    sh_g: int
+    sigma0: float
+    sigma1: float
+
+
+LIGHT_NEUTRAL = LightFrame(0, (1.0, 0.0, 0.0, 0.0, 1.0, 0.0), 0.0, 0.0, (1.0, 1.0, 1.0), 1.0, 0, 0, 0, 0, 0.0, 0.0)
+
+
+def light_frame_ok(q):
+    """whether a LightFrame lies in the ranges ArapFlow_LightTables accepts"""
+    fl = tuple(q.m) + (q.amp, q.vig) + tuple(q.gain) + (q.gamma, q.sigma0, q.sigma1)
+    if len(q.m) != 6 or len(q.gain) != 3 or not all(math.isfinite(v) for v in fl):
+        return False
+    if not (0 <= q.seed <= 0xffffffff and q.amp >= 0 and 0 <= q.vig <= 1 and min(q.gain) > 0 and q.gamma > 0):
+        return False
+    if not (q.sigma0 >= 0 and q.sigma1 >= 0 and abs(q.sh_dx) <= LIGHT_MAX_SHIFT and abs(q.sh_dy) <= LIGHT_MAX_SHIFT):
+        return False
+    return 0 <= q.sh_r <= LIGHT_MAX_R and 0 <= q.sh_g <= 256
+
+
+def light_is_neutral(q):
+    """whether a LightFrame returns its input bytes: no field, no vignette, the identity tone curve, no shadow, no noise"""
+    return (q.amp, q.vig, tuple(q.gain), q.gamma, q.sh_g, q.sigma0, q.sigma1) == (0, 0, (1, 1, 1), 1, 0, 0, 0)
+
+
+class LightLine(NamedTuple):
+    """a `light` line (DESIGN.md "Relit frames"), recognised by its first word: the relit variant of one pair
+        light RGB1 MASK1 RGB2 COVER2 l=<frame 1>;<frame 2> [rgb1=P] [rgb2=P]
+    RGB1 / RGB2: the pair's finished frames; MASK1: frame 1's mask in the solver's convention (red channel, object: == 0);
+    COVER2: frame 2's warped mask, read as a cover (red channel, object: != 0).  A frame of l= is the 19 numbers of
+    LightFrame, comma separated: the seed, sh_dx, sh_dy, sh_r and sh_g integers, the floats written with %.9g.  rgb1 /
+    rgb2: the relit frames.  `out`: {key: path} in line order.  At least one output; anything else -- an unknown or
+    repeated key, a missing `=`, an empty value, a wrong count of numbers, a number out of range or non-finite -- is an
+    error."""
+    rgb1: str
+    mask1: str
+    rgb2: str
+    cover2: str
+    frames: tuple
+    out: dict
+
+
+_INT = re.compile(r"-?[0-9]{1,10}$")
+
+
+def _light_frame(text):
+    q = text.split(",")
+    if len(q) != 19 or not _UINT.match(q[0]) or not all(_INT.match(v) for v in q[13:15]) or not all(_UINT.match(v) for v in q[15:17]):
+        return None
+    with np.errstate(over="ignore"):            # (a number beyond float32 becomes inf, refused below)
+        fl = _bg_numbers(",".join(q[1:13] + q[17:]))
+    if len(fl) != 14:
+        return None
+    f = LightFrame(int(q[0]), fl[:6], fl[6], fl[7], fl[8:11], fl[11], int(q[13]), int(q[14]), int(q[15]), int(q[16]), fl[12], fl[13])
+    return f if light_frame_ok(f) else None
+
+
+def parse_light(tokens):
+    if not tokens or tokens[0] != LIGHT_WORD:
+        raise ValueError("not a light line: %r" % " ".join(tokens))
+    if len(tokens) < 5 or any("=" in t for t in tokens[1:5]):
+        raise ValueError("light line: two frames, a mask and a cover, then the tokens: %r" % " ".join(tokens))
+    out, frames = {}, None
+    for t in tokens[5:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and (k == "l" or k in LIGHT_KEYS)) or k in out or (k == "l" and frames is not None):
+            raise ValueError("light line: bad or repeated token %r" % t)
+        if k == "l":
+            frames = tuple(_light_frame(q) for q in v.split(";"))
+            if len(frames) != 2 or None in frames:
+                raise ValueError("light line: l= takes two frames of 19 numbers in their ranges: %r" % t)
+        else:
+            out[k] = v
+    if frames is None:
+        raise ValueError("light line without l=: %r" % " ".join(tokens))
+    if not out:
+        raise ValueError("light line without an output: %r" % " ".join(tokens))
+    return LightLine(tokens[1], tokens[2], tokens[3], tokens[4], frames, out)
+
+
+def light_line(item):
+    """the inverse of parse_light: l=, then the outputs in the order of LIGHT_KEYS"""
+    f32 = lambda v: "%.9g" % float(np.float32(v))
+    nums = lambda q: ["%d" % q.seed] + [f32(v) for v in tuple(q.m) + (q.amp, q.vig) + tuple(q.gain) + (q.gamma,)] + \
+        ["%d" % v for v in (q.sh_dx, q.sh_dy, q.sh_r, q.sh_g)] + [f32(q.sigma0), f32(q.sigma1)]
+    tok = [LIGHT_WORD, item.rgb1, item.mask1, item.rgb2, item.cover2, "l=" + ";".join(",".join(nums(q)) for q in item.frames)]
+    return " ".join(tok + ["%s=%s" % (k, item.out[k]) for k in LIGHT_KEYS if item.out.get(k)])
+
+
+def run_light(state, spec):
+    """one `light` line: read the frame(s) the line asks for with their masks, one opt.relight each (rgb1: frame 1 under
+    the first description, MASK1 in the solver's convention; rgb2: frame 2 under the second, COVER2 as a cover), write the
+    outputs as RGB PNGs"""
+    from . import opt
+    for key, rgb_path, mask_path, frame, is_mask in (("rgb1", spec.rgb1, spec.mask1, spec.frames[0], True),
+                                                     ("rgb2", spec.rgb2, spec.cover2, spec.frames[1], False)):
+        if key not in spec.out:
+            continue
+        rgb, cover = load_rgb(rgb_path), load_mask_red(mask_path)
+        if cover.shape != rgb.shape[:2]:
+            raise ValueError("light line: image and mask sizes differ")
+        Image.fromarray(opt.relight(state, rgb, cover, frame, cover_is_mask=is_mask)).save(spec.out[key])
+
+
+LIGHT_TWIN_SHIFT = 1024      # cells: how far apart the fields of a seed and its twin lie (a power of two)
+
+
+def _tex_mix(x, inverse=False):
+    """the 32-bit mixer of the textures' hash (tex_mix of arap_tex.h), or its inverse: it is a bijection"""
+    M = 0xffffffff
+    if not inverse:
+        x ^= x >> 16; x = x * 0x7feb352d & M; x ^= x >> 15; x = x * 0x846ca68b & M      # noqa: E702
+        return x ^ x >> 16
+    x ^= x >> 16; x = x * pow(0x846ca68b, -1, 1 << 32) & M; x ^= x >> 15 ^ x >> 30      # noqa: E702
+    x = x * pow(0x7feb352d, -1, 1 << 32) & M
+    return x ^ x >> 16
+
+
+def light_twin_seed(seed):
+    """the seed whose illumination field is `seed`'s moved by LIGHT_TWIN_SHIFT cells: the hash of lattice point (i, j),
+    stream 0, is mix(mix(mix(seed) ^ i) ^ j), so with mix(twin) = mix(seed) ^ LIGHT_TWIN_SHIFT the twin's value at (i, j)
+    is the seed's at (i + LIGHT_TWIN_SHIFT, j) for 0 <= i < LIGHT_TWIN_SHIFT.  The noise streams (seed + 1 .. seed + 12)
+    of the two seeds have nothing in common.  A frame description has ONE seed, for its field and its noise: this is how
+    the two frames of a pair see the same drifting light through different noise."""
+    return _tex_mix(_tex_mix(seed & 0xffffffff) ^ LIGHT_TWIN_SHIFT, inverse=True)
+
+
+def random_light(rng, strength, W, H):
+    """para_gen --relight: the two LightFrames of a pair, drawn from `rng` (a random.Random; the same state gives the same
+    pair), every amplitude scaled by `strength` >= 0; strength = 0 gives two neutral descriptions.  In this order: the
+    seed; the field's cell size in pixels (log-uniform between half the frame's short side and twice its long side), its
+    rotation and its drift between the frames in cells (each component within a quarter cell times min(strength, 1)); the
+    field's amplitude; the vignette; per channel the gain of frame 1, then its flicker; the gamma of frame 1 and its flicker;
+    the shadow's direction, distance, penumbra and depth; the two noise deviations.
+    Shared by the two frames: the shadow's geometry and depth, the vignette, the field's amplitude, the noise deviations.
+    Frame 2's seed is frame 1's twin (light_twin_seed) and its map is frame 1's moved by the drift minus LIGHT_TWIN_SHIFT
+    cells: the same field a little further on -- the light drifts, it does not jump -- under different noise.  Frame 1's
+    map puts the frame's centre at (1.5, 0.5) * LIGHT_TWIN_SHIFT, so both frames stay inside the range where the twin
+    relation holds.  Maps are computed in double and rounded once to float32."""
+    s = float(strength)
+    if not (math.isfinite(s) and s >= 0):
+        raise ValueError("random_light: a finite strength >= 0 expected")
+    f32 = lambda v: float(np.float32(v))
+    seed = rng.getrandbits(32)
+    cell = math.exp(rng.uniform(math.log(max(1.0, min(W, H) / 2.0)), math.log(2.0 * max(W, H))))
+    rot = rng.uniform(0, 2 * math.pi)
+    du, dv = (rng.uniform(-0.25, 0.25) * min(s, 1.0) for _ in range(2))
+    amp = min(0.3 * s * rng.uniform(0.3, 1), 0.9)
+    vig = min(s * rng.uniform(0, 0.5), 1.0)
+    gain1, gain2 = [], []
+    for _ in range(3):
+        g = min(max(1 + 0.1 * s * rng.uniform(-1, 1), 0.25), 4.0)
+        gain1.append(f32(g))
+        gain2.append(f32(min(max(g * (1 + 0.03 * s * rng.uniform(-1, 1)), 0.25), 4.0)))
+    gamma1 = math.exp(0.2 * min(s, 4.0) * rng.uniform(-1, 1))
+    gamma2 = gamma1 * min(max(1 + 0.03 * s * rng.uniform(-1, 1), 0.5), 2.0)
+    ang, dist = rng.uniform(0, 2 * math.pi), rng.uniform(4, 24) * max(1.0, min(W, H) / 480.0)
+    lim = lambda v: max(-LIGHT_MAX_SHIFT, min(int(round(v)), LIGHT_MAX_SHIFT))
+    sh_dx, sh_dy = lim(dist * math.cos(ang)), lim(dist * math.sin(ang))
+    sh_r = rng.randint(2, LIGHT_MAX_R)
+    sh_g = min(int(round(s * rng.uniform(64, 160))), 256)
+    sigma0, sigma1 = f32(s * rng.uniform(0.5, 3)), f32(s * rng.uniform(0, 0.02))
+    co, si = math.cos(rot) / cell, math.sin(rot) / cell
+    xc, yc = (W - 1) / 2.0, (H - 1) / 2.0
+    cu, cv = 1.5 * LIGHT_TWIN_SHIFT - (co * xc + si * yc), 0.5 * LIGHT_TWIN_SHIFT - (-si * xc + co * yc)
+    m1 = tuple(f32(v) for v in (co, si, cu, -si, co, cv))
+    m2 = tuple(f32(v) for v in (co, si, cu + du - LIGHT_TWIN_SHIFT, -si, co, cv + dv))
+    shared = (sh_dx, sh_dy, sh_r, sh_g, sigma0, sigma1)
+    return (LightFrame(seed, m1, f32(amp), f32(vig), tuple(gain1), f32(gamma1), *shared),
+            LightFrame(light_twin_seed(seed), m2, f32(amp), f32(vig), tuple(gain2), f32(gamma2), *shared))
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
-    BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`"""
+    BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`, a
+    LightLine when it is `light`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == LIGHT_WORD:
+        return parse_light(tok)
     if tok and tok[0] == BLUR_WORD:
         return parse_blur(tok)
     if tok and tok[0] == TRK_WORD:
@@ -646,15 +840,17 @@ def format_line(item):
         return trk_line(item)
     if isinstance(item, BlurLine):
         return blur_line(item)
+    if isinstance(item, LightLine):
+        return light_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
-    first of a bg line's bg_outputs, a tex or blur line's first output token, a trk line's track file"""
+    first of a bg line's bg_outputs, a tex, blur or light line's first output token, a trk line's track file"""
     if isinstance(item, TrkLine):
         return item.out
-    if isinstance(item, BlurLine):
+    if isinstance(item, (BlurLine, LightLine)):
         return next(iter(item.out.values()))
     if isinstance(item, BgLine):
         return bg_outputs(item)[0]

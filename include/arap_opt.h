@@ -514,6 +514,60 @@ int ArapFlow_BlurLayers(Opt_State* state, unsigned W, unsigned H, unsigned n, co
                         const void* bg, unsigned bgW, unsigned bgH, const float Ma[6], const float Mb[6], void* out_rgb,
                         void* out_alpha, void* scratch);
 
+/* Relit frames (DESIGN.md "Relit frames"): a finished frame (objects over their background) under one soft shadow of the
+ * objects on the background, a tone curve, a smooth illumination field, a vignette and sensor noise.  The geometry is
+ * untouched, so a relit pair shares the clean pair's flow, occlusion and track files.  One frame's description (HOST):
+ *   seed            of the frame's hash (ArapFlow_Texture's h); any value
+ *   m               six floats, pixel -> field point (u, v) = (a x + b y + c, d x + e y + f) as in ArapFlow_TexLayer; one
+ *                   value-noise cell of the illumination field per unit
+ *   amp             >= 0: amplitude of the illumination field
+ *   vig             0 .. 1: depth of the vignette at the frame's corner
+ *   gain[3], gamma  > 0, finite: the tone curve per channel
+ *   sh_dx, sh_dy    |.| <= ARAPFLOW_LIGHT_MAX_SHIFT: where the shadow falls relative to the object, in pixels
+ *   sh_r            0 .. ARAPFLOW_LIGHT_MAX_R: radius of the penumbra (a box of 2 sh_r + 1 pixels a side)
+ *   sh_g            0 .. 256: depth of the shadow in 256ths; 0 = no shadow
+ *   sigma0, sigma1  >= 0: standard deviation of the noise in grey levels, the constant part and the part per grey level
+ * Every float finite.  Derived on the host, in one place (ArapFlow_LightTables, needs no device; the device call uses it):
+ *   lut[c][i] = floor(255 * min(max(gain[c] * pow(i / 255, gamma), 0), 1) + 0.5), in double with the C library's pow;
+ *               gamma = 1, gain = 1 is the identity table
+ *   geom      = (cx, cy, inv_r2) = ((W - 1) / 2, (H - 1) / 2, 1 / (cx^2 + cy^2)), in double, each rounded once to float32;
+ *               inv_r2 = 0 when W = H = 1
+ * Per pixel (x, y), channel c, input byte v0, with obj(p) the cover predicate at pixel p -- cover[p] != 0, or == 0 with
+ * cover_is_mask (the solver's convention); false for every p outside the frame -- and every float operator one IEEE
+ * float32 operation in the order of the parentheses (no fused multiply-add but inside vn, ArapFlow_Texture's value noise):
+ *   shadow   only if sh_g > 0 and !obj(x, y), else v1 = v0:  a = #{(i, j): |i| <= r, |j| <= r, obj(x - sh_dx + i, y - sh_dy
+ *            + j)}, A = (2 r + 1)^2, v1 = (v0 * (256 A - sh_g * a) + 128 A) / (256 A), integer division (below 2^32)
+ *   tone     v2 = lut[c][v1]
+ *   shading  L = 1.0f + amp * (2.0f * vn(seed, u, v, 0) - 1.0f),
+ *            V = 1.0f - vig * min(((fx - cx) * (fx - cx) + (fy - cy) * (fy - cy)) * inv_r2, 1.0f),  fx = (float)x, fy = (float)y
+ *            v3 = (float)v2 * (L * V)
+ *   noise    n = (((r0 + r1) + (r2 + r3)) - 2.0f) * 1.7320508f, r_j = r01(h(seed, x, y, 1 + 4 c + j)): zero mean, unit variance
+ *            v4 = v3 + (sigma0 + sigma1 * v3) * n
+ *   out      (uint8)(min(max(v4, 0.0f), 255.0f) + 0.5f)
+ * The neutral description (amp = vig = 0, gain = gamma = 1, sh_g = 0, sigma0 = sigma1 = 0) returns the input bytes; the
+ * output is a function of the arguments alone; an object pixel does not depend on the cover beyond its own bit.
+ * ArapFlow_LightTables returns 0, or -1: a null pointer, a zero size, W * H >= 2^31, a field outside its range or
+ * non-finite.
+ * ArapFlow_Relight works on DEVICE buffers (frame: HOST): rgb uint8[H][W][3], cover uint8[H][W] (may be NULL when sh_g = 0,
+ * and is then not read) -> out_rgb uint8[H][W][3].  Needs no scratch beyond the 768-byte table, which the state allocates
+ * at the first call and the call copies before it returns.  Asynchronous on the state's stream.  Returns 0; -1, and
+ * nothing is launched or written, on bad arguments: a null state, rgb, frame or out_rgb, a zero size, W * H >= 2^31, a
+ * field outside its range or non-finite, sh_g > 0 without a cover, out_rgb overlapping rgb or cover; else a HIP error
+ * code. */
+#define ARAPFLOW_LIGHT_MAX_R 16
+#define ARAPFLOW_LIGHT_MAX_SHIFT 64
+typedef struct ArapFlow_LightFrame {
+    uint32_t seed;
+    float m[6];
+    float amp, vig;
+    float gain[3], gamma;
+    int32_t sh_dx, sh_dy, sh_r, sh_g;
+    float sigma0, sigma1;
+} ArapFlow_LightFrame;
+int ArapFlow_LightTables(const ArapFlow_LightFrame* frame, unsigned W, unsigned H, uint8_t lut[3][256], float geom[3]);
+int ArapFlow_Relight(Opt_State* state, unsigned W, unsigned H, const void* rgb, const void* cover, int cover_is_mask,
+                     const ArapFlow_LightFrame* frame, void* out_rgb);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised

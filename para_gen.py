@@ -5,6 +5,7 @@
                      [--bwd_flow] [--occ | --multseg --occ_layers] [--mid K | --multseg --mid_layers K]
                      [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]] [--diag] [--max_fold FRAC] [--retex]
                      [--bg_dir DIR --blur SHUTTER [SAMPLES]]
+                     [--bg_dir DIR --relight [STRENGTH]]
                      [--tracks P]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
@@ -65,6 +66,13 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     from one `blur` line per pair, handed to a worker once the pair's solves (and layers line) are done and before the
     segments are merged.  It costs no solve and shares the pair's Flow file (the exposure windows are centred on the two
     frame times): OUT/all_files_blur.list names `inpRGB_blur wRGB_blur Flow`.  Needs --bg_dir.
+  * --relight [STRENGTH] writes the relit variant of every kept pair (DESIGN.md "Relit frames"):
+    OUT/inpRGB_light/<seq>/<frame>.png and OUT/wRGB_light/<seq>/<frame>.png, the pair's two finished frames under a soft
+    shadow of the objects on the background, a drifting illumination field, a flickering tone curve, a vignette and sensor
+    noise (pipeline.random_light, seeded with the pair's id; every amplitude scaled by STRENGTH, default 1), from one `light`
+    line per pair, handed to a worker once both frames are final: after the segments are merged and the background is
+    composited, with --bg_motion after the pair's bg line.  The geometry is untouched, so it costs no solve and shares the
+    pair's Flow file: OUT/all_files_light.list names `inpRGB_light wRGB_light Flow`.  Needs --bg_dir.
 """
 import argparse
 import json
@@ -93,6 +101,7 @@ orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
 color_blur_dir, wrgb_blur_dir = "inpRGB_blur", "wRGB_blur"       # --blur: the motion-blurred pair (addition)
+color_light_dir, wrgb_light_dir = "inpRGB_light", "wRGB_light"   # --relight: the relit pair (addition)
 color_tex_dir, wrgb_tex_dir = "inpRGB_tex", "wRGB_tex"           # --retex: the random-texture twin (addition)
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
 diag_dir, fold_dir = "Diag", "Fold"     # --diag: fold diagnostics (addition)
@@ -214,7 +223,7 @@ class Frame:
     remove: bool                   # --multseg: delete the segments' files once they are merged
     left: int = 0                  # main: solves of this frame not yet reported done
     motion: object = None          # --bg_motion: the pair's bg line (pipeline.BgLine), handed out after finish_frame
-    stage: str = "solves"          # main: what the workers hold of this frame: solves -> layers -> bg
+    stage: str = "solves"          # main: what the workers hold of this frame: solves -> layers -> bg -> light
     tmp: tuple = ()                # --bg_motion: the bg line's own input files, deleted when it is done
     tex: object = None             # --retex: the pair's tex line (pipeline.TexLine), handed out before finish_frame
     motion_tex: object = None      # --retex --bg_motion: the twin's bg line, handed out after the pair's
@@ -222,6 +231,8 @@ class Frame:
     pending: int = 0               # main: lines of stage "layers" (the layers line, the trk line) not yet reported done
     blur: object = None            # --blur: the pair's blur line (pipeline.BlurLine), handed out where a tex line is
     blur_tmp: tuple = ()           # --blur: the blur line's own input file, deleted when it is done
+    light: object = None           # --relight: the pair's light line (pipeline.LightLine), handed out once both frames are final
+    light_tmp: tuple = ()          # --relight: the light line's own input file, deleted when it is done
 
     @property
     def solves(self):
@@ -241,6 +252,7 @@ def prepare_pair(args):
     tex1, tex2 = p.pop("rgb1tex_gen", None), p.pop("rgb2tex_gen", None)     # --retex: the twin's two frames
     trk_out, n_tracks = p.pop("trk_gen", None), p.pop("_tracks", 0)         # --tracks: the track file, the number of points
     blur1, blur2 = p.pop("rgb1blur_gen", None), p.pop("rgb2blur_gen", None)     # --blur: the blurred pair's two frames
+    light1, light2 = p.pop("rgb1light_gen", None), p.pop("rgb2light_gen", None)     # --relight: the relit pair's two frames
     layer_masks = []
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
@@ -360,6 +372,22 @@ def prepare_pair(args):
             rec.motion_tex = pipeline.BgLine(rec.bg, tex1, mask1, tex2, line.out_mask, line.flow, m=rec.motion.m, inputs={},
                                              out=("", tex2, ""), outs={})
         rec.tmp = tuple(q for q in (rec.bg, mask1 if segs is not None else None, stem_tmp + "_bg.txt") if q)
+    if light1 is not None and rec.solves and (bgim is not None or big is not None):
+        # the relit pair: the two finished frames, frame 1's object mask -- with --multseg the union of the segments', the bg
+        # line's where there is one -- and the merged warped mask as frame 2's cover; the light from the pair's own generator
+        for q in (light1, light2):
+            os.makedirs(osp.dirname(q), exist_ok=True)
+        mask1 = line.mask
+        if segs is not None and rec.motion is not None:
+            mask1 = rec.motion.mask1
+        elif segs is not None:
+            mask1 = osp.splitext(p["cstr_tmp"])[0] + "_lightmask.png"
+            Image.fromarray(np.minimum.reduce(layer_masks)).save(mask1)
+            rec.light_tmp = (mask1,)
+        H, W = im1.shape[:2]
+        rec.light = pipeline.LightLine(line.rgb, mask1, line.out_rgb, line.out_mask,
+                                       pipeline.random_light(rn.Random(_pair_id(seq, stem)), flags.relight, W, H),
+                                       dict(rgb1=light1, rgb2=light2))
     return rec
 
 
@@ -571,6 +599,7 @@ def scan(flags, input_root, output_root):
                                                            msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
                                                            tx1=color_tex_dir, tx2=wrgb_tex_dir, trk=tracks_dir,
                                                            bl1=color_blur_dir, bl2=wrgb_blur_dir,
+                                                           lt1=color_light_dir, lt2=wrgb_light_dir,
                                                            obw=occ_bwd_dir, occ=occ_dir, dia=diag_dir, fol=fold_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
                                                            ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
@@ -607,6 +636,8 @@ def scan(flags, input_root, output_root):
                     e.update(rgb1tex_gen=osp.join(roots["tx1"], seq, f + ".png"), rgb2tex_gen=osp.join(roots["tx2"], seq, f + ".png"))
                 if getattr(flags, "blur", None):
                     e.update(rgb1blur_gen=osp.join(roots["bl1"], seq, f + ".png"), rgb2blur_gen=osp.join(roots["bl2"], seq, f + ".png"))
+                if getattr(flags, "relight", None) is not None:
+                    e.update(rgb1light_gen=osp.join(roots["lt1"], seq, f + ".png"), rgb2light_gen=osp.join(roots["lt2"], seq, f + ".png"))
                 if getattr(flags, "bg_motion", None) is not None:       # the full-frame maps of what the run asks for
                     e["flowfull_gen"] = osp.join(roots["ful"], seq, f + ".flo")
                     if "occ_gen" in e or LAYERS_OCC in e:
@@ -629,7 +660,7 @@ def scan(flags, input_root, output_root):
                     e["_midbg"] = tuple(flags.mid_steps or flags.mid_layers_steps)
                 # every requested output
                 done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e) + mid_bg_paths(e)
-                done += track_paths(e) + [e[k] for k in ("rgb1blur_gen", "rgb2blur_gen") if k in e]
+                done += track_paths(e) + [e[k] for k in ("rgb1blur_gen", "rgb2blur_gen", "rgb1light_gen", "rgb2light_gen") if k in e]
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -704,6 +735,11 @@ def write_lists(flags, output_root, all_paths):
         blurred = [[by_trio[t]["rgb1blur_gen"], by_trio[t]["rgb2blur_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
         open(osp.join(output_root, "all_files_blur.list"), "w").write(
             "\n".join(" ".join(t) for t in blurred if all(osp.exists(q) for q in t)))
+    if getattr(flags, "relight", None) is not None:        # the relit variants of the listed pairs: the SAME flow
+        by_trio = {" ".join(pipeline.make_arap_path(p)[k] for k in (0, 4, 3)): p for p in all_paths}
+        relit = [[by_trio[t]["rgb1light_gen"], by_trio[t]["rgb2light_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
+        open(osp.join(output_root, "all_files_light.list"), "w").write(
+            "\n".join(" ".join(t) for t in relit if all(osp.exists(q) for q in t)))
     return out_paths, rejected
 
 
@@ -736,7 +772,8 @@ def main(flags):
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
     frames = {}                                        # done token of a line a worker holds -> its Frame
     posts, lock = [], threading.Lock()
-    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0, tracks_done=0, blur_done=0)
+    counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0, tracks_done=0, blur_done=0,
+                  light_done=0)
 
     def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
         frames[pipeline.done_token(item)] = rec
@@ -747,9 +784,26 @@ def main(flags):
             rec.stage = "bg"
             hand_out(rec, rec.motion, workers.put_owed)
 
+    def light_ready(rec):                              # the pool's result thread: finish_frame of a --relight pair is done
+        with lock:
+            rec.stage = "light"
+            hand_out(rec, rec.light, workers.put_owed)
+
     def on_done(path):                                 # a worker thread: one solve (or one layers / bg line) finished
         with lock:
             rec = frames.pop(path)
+            if rec.stage in ("bg", "light") and rec.light is not None:
+                if rec.stage == "bg":                  # its bg line: both frames are final, now the pair's light line
+                    counts["bg_done"] += 1
+                    rec.stage = "light"
+                    hand_out(rec, rec.light, workers.put_owed)
+                    return
+                counts["light_done"] += 1              # its light line: the frame is complete
+                if rec.remove:
+                    for q in rec.tmp + rec.light_tmp:
+                        if osp.exists(q):
+                            os.remove(q)
+                return
             if rec.stage == "bg" and rec.motion_tex is not None:    # its bg line: now the twin's, over the same inputs
                 counts["bg_done"] += 1
                 rec.stage = "bg_tex"
@@ -795,7 +849,10 @@ def main(flags):
                 hand_out(rec, twin, workers.put_owed)
                 return
             counts["frames_done"] += 1
-            if rec.motion is None:
+            if rec.motion is None and rec.light is not None:       # then the pair's light line, over the finished frames
+                posts.append(pool.apply_async(finish_frame, (rec,), callback=lambda _, rec=rec: light_ready(rec),
+                                              error_callback=lambda e: workers._fail("finish_frame failed: %r" % (e,))))
+            elif rec.motion is None:
                 posts.append(pool.apply_async(finish_frame, (rec,)))
             else:                                      # then the pair's bg line, over the flattened files
                 posts.append(pool.apply_async(finish_frame, (rec,), callback=lambda _, rec=rec: bg_ready(rec),
@@ -827,7 +884,7 @@ def main(flags):
                 workers.owe()
             if rec.motion is not None:
                 workers.owe()
-            for later in (rec.tex, rec.motion_tex, rec.tracks, rec.blur):
+            for later in (rec.tex, rec.motion_tex, rec.tracks, rec.blur, rec.light):
                 if later is not None:
                     workers.owe()
             with lock:
@@ -851,7 +908,7 @@ def main(flags):
     dt = time.time() - t_start
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
                  layers_done=counts["layers_done"], bg_done=counts["bg_done"], tex_done=counts["tex_done"],
-                 tracks_done=counts["tracks_done"], blur_done=counts["blur_done"],
+                 tracks_done=counts["tracks_done"], blur_done=counts["blur_done"], light_done=counts["light_done"],
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -965,7 +1022,24 @@ def parse(argv=None):
                              "SHUTTER (in units of the pair's motion, centred on the frame) as the mean of SAMPLES renders "
                              "(1 .. 32, default 9), and OUT/all_files_blur.list, whose lines name those two and the pair's own "
                              "Flow file (DESIGN.md \"Motion blur\")")
+    parser.add_argument("--relight", nargs="?", type=float, const=1.0, default=None, metavar="STRENGTH",
+                        help="with --bg_dir: also write the relit variant of every pair: OUT/inpRGB_light/<seq>/<frame>.png and "
+                             "OUT/wRGB_light/<seq>/<frame>.png, the pair's two frames under a soft shadow of the objects, a "
+                             "drifting illumination field, a flickering tone curve, a vignette and sensor noise, every "
+                             "amplitude scaled by STRENGTH (default 1), and OUT/all_files_light.list, whose lines name those "
+                             "two and the pair's own Flow file (DESIGN.md \"Relit frames\")")
     flags = parser.parse_args(argv)
+    if flags.relight is not None:
+        if not (np.isfinite(flags.relight) and flags.relight >= 0):
+            parser.error("--relight [STRENGTH]: a finite STRENGTH >= 0")
+        if not flags.bg_dir:
+            parser.error("--relight needs --bg_dir: a shadow needs a background to fall on")
+        if flags.mid or flags.mid_layers or flags.mid_bg or flags.retex or flags.blur is not None:
+            parser.error("--relight cannot be combined with --mid / --mid_layers / --mid_bg / --retex / --blur: relit sequences, "
+                         "twins and blurred frames are made with opt.relight, not from this command line")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--relight needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
+                         "not know the light line")
     if flags.blur is not None:
         try:
             if len(flags.blur) > 2:
