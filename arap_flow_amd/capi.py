@@ -85,6 +85,7 @@ SYMBOLS = [
     ("ArapFlow_SolverResidentLayout", _I, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("ArapFlow_SolverResidentSums", _I, [_VP, C.POINTER(C.c_int), C.c_uint]),
     ("ArapFlow_SolverLeanStream", _I, [_VP]),
+    ("ArapFlow_SolverStepRecipe", _I, [_VP, C.POINTER(C.c_int)]),
     ("ArapFlow_ResidentFailed", _I, [_VP]),
     ("ArapFlow_SolverStamps", _I, [_VP, _VP]),
     ("ArapFlow_SolverStampParts", _I, [_VP, _VP]),

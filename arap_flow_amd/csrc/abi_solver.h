@@ -718,6 +718,19 @@ int ArapFlow_SolverResidentSums(ArapFlow_Solver* s, int* sums, unsigned cap)
 }
 int ArapFlow_ResidentFailed(Opt_State* state) { return state && state->resident_failed ? 1 : 0; }
 int ArapFlow_SolverLeanStream(ArapFlow_Solver* s) { return s && plan_lean_stream(s->plan) ? 1 : 0; }
+// read-only: what plan_step_recipe decided for the step whose graph the plan holds (Opt_Plan::g_recipe)
+int ArapFlow_SolverStepRecipe(ArapFlow_Solver* s, int* out)
+{
+    if (!s || !out) return -1;
+    const Opt_Plan* p = s->plan;
+    const bool have = p->gexec != nullptr;
+    const StepRecipe none;
+    const StepRecipe& r = have ? p->g_recipe : none;
+    out[0] = r.a_kern; out[1] = r.b_kern;
+    for (int k = 0; k < 3; ++k) out[2 + k] = r.a_arg[k];
+    out[5] = r.lag;
+    return have ? 1 : 0;
+}
 
 // diagnostic (ARAPOPT_STAMPS=1): copy the [256][8] phase-time table of the LAST resident launch (table 0)
 // ... or its second [512][16] table: the parts of the on-chip chain of a group sum, arrival times, placement, work

@@ -302,6 +302,11 @@ def _stats_dict(s):
             for k in capi.MESH_STATS_KEYS}
 
 
+# ArapFlow_SolverStepRecipe's kernel numbers (host_plan.h: PhaseA, PhaseB) as FrameSolver.stats() names them
+PHASE_A_NAMES = ("", "direct", "lds16x16", "lds32x8", "lds64x4", "lds32x16", "lds64x8", "march", "march2", "grid")
+PHASE_B_NAMES = ("", "b", "b4", "b4_lean", "b4_r")
+
+
 class FrameSolver:
     """Batched, device-resident CombinedSolver (ArapFlow_Solver)."""
 
@@ -470,11 +475,15 @@ class FrameSolver:
         sums = (C.c_int * 64)()
         n = max(0, min(64, self.lib.ArapFlow_SolverResidentSums(self.h, sums, 64)))
         names = ["flat" if sums[k] == 1 else "any" for k in range(n)]
+        # the kernels of the last Gauss-Newton step enqueued as a graph (ArapFlow_SolverStepRecipe): "" after a resident step
+        rec = (C.c_int * 6)()
+        self.lib.ArapFlow_SolverStepRecipe(self.h, rec)
         return dict(pcg_iterations_per_frame=a.value, active_vertices=b.value, grid_vertices=c.value,
                     resident_launches=int(self.lib.ArapFlow_SolverResidentLaunches(self.h)),
                     resident_launches_per_step=ls.value, resident_solves_in_flight=fl.value,
                     resident_sums=names[0] if len(set(names)) == 1 else ",".join(names),
-                    lean_stream=bool(self.lib.ArapFlow_SolverLeanStream(self.h)))
+                    lean_stream=bool(self.lib.ArapFlow_SolverLeanStream(self.h)),
+                    phase_a=PHASE_A_NAMES[rec[0]], phase_b=PHASE_B_NAMES[rec[1]], a_args=(rec[2], rec[3], rec[4]), lag=rec[5])
 
     def close(self):
         if self.h:

@@ -292,6 +292,15 @@ int ArapFlow_ResidentFailed(Opt_State* state);
  * pause after a timeout), takes the lean streaming schedule (arap_stream.h: k_pcg_a_march2 / k_pcg_b4_r: 85 + 41 bytes
  * per vertex and iteration instead of 57 + 89), which it does when most of its tiles are active. */
 int ArapFlow_SolverLeanStream(ArapFlow_Solver* s);
+/* Which kernels the last Gauss-Newton step this solver enqueued as a graph was made of (read-only; for tests that must
+ * know they reached the kernel pair they were written for).  out[6] = {phase A, phase B, a0, a1, a2, lag}:
+ *   phase A: 0 none (a resident step), 1 k_pcg_a, 2..6 k_pcg_a_lds<16x16, 32x8, 64x4, 32x16, 64x8>, 7 k_pcg_a_march<5>,
+ *            8 k_pcg_a_march2<7>, 9 k_pcg_a_grid<64,8>;   phase B: 0 none, 1 k_pcg_b, 2 k_pcg_b4, 3 k_pcg_b4_lean, 4 k_pcg_b4_r;
+ *   a0, a1, a2: strips (march) or 64x8 tiles (grid) in x, chunks or tiles in y, workgroups per XCD and frame;
+ *   lag: the PCG iteration whose delta += alpha p is left to the update kernel (lean schedule: lIterations - 1), else -1.
+ * Returns 1, 0 when the solver holds no step graph (nothing solved yet, ARAPOPT_NO_GRAPH=1, kernel timing: out is
+ * {0, 0, 0, 0, 0, -1}), -1 on bad arguments. */
+int ArapFlow_SolverStepRecipe(ArapFlow_Solver* s, int* out);
 /* Diagnostic only (env ARAPOPT_STAMPS=1 selects an instrumented build of the resident kernel): copies
  * out[512][16] = per workgroup {phase A, wait 1, phase B, wait 2, update} summed 100 MHz ticks of the
  * last resident launch, tiles per workgroup, halo cells.  Returns -1 when stamps are off. */

@@ -553,11 +553,15 @@ def test_lds_tiled_phase_a_is_bit_identical(gpu_state, oracle, tile):
         fs = opt.FrameSolver(gpu_state, W, H, batch=2)
         fs.set_frame(0, f["mask_red"], f["constraints"]); fs.set_frame(1, np.zeros((H, W), np.uint8), f["constraints"])
         fs.solve(2, 1, 2, 25)
-        r0 = fs.results(0, want_rgb=False)
+        r0, r1 = fs.results(0, want_rgb=False), fs.results(1, want_rgb=False)
         fs.close()
         Of, Af, _ = oracle.frame(f["mask_red"], f["constraints"], numIter=1, nIterations=2, lIterations=25, dtype=np.float32,
                                  mode=1, trig=1)
         assert np.array_equal(r0["offset"], Of) and np.array_equal(r0["angle"], Af)
+        # ... and the all-active frame next to it in the batch
+        O1, A1, c1 = oracle.frame(np.zeros((H, W), np.uint8), f["constraints"], numIter=1, nIterations=2, lIterations=25,
+                                  dtype=np.float32, mode=1, trig=1)
+        assert np.array_equal(r1["offset"], O1) and np.array_equal(r1["angle"], A1) and r1["cost"] == c1[-1]
     finally:
         gpu_state.set_tile(-1, -1)
         gpu_state.set_resident(True)
