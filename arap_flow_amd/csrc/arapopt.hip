@@ -41,6 +41,7 @@
 #include "arap_tex.h"
 #include "arap_blur.h"
 #include "arap_light.h"
+#include "arap_seg.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
 
@@ -54,4 +55,5 @@ using namespace arap;
 #include "host_lm.h"         // "LMGPU" host loop
 #include "abi_opt.h"         // Opt_* drop-in ABI and the small ArapFlow_* entry points
 #include "abi_warp.h"        // warp scratch layout, ArapFlow_Warp*
+#include "abi_seg.h"         // ArapFlow_SegMaps
 #include "abi_solver.h"      // ArapFlow_Solver*

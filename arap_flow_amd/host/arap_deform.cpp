@@ -44,6 +44,11 @@
 //   light RGB1 MASK1 RGB2 COVER2 l=<frame 1>;<frame 2> [rgb1=P] [rgb2=P]
 // (the pair's finished frames; MASK1 in the solver's convention, COVER2 a cover; a frame of l= is the 19 numbers of
 // ArapFlow_LightFrame; at least one output).
+// A line whose first word is `seg` is the segment maps of one pair (DESIGN.md "Segment maps"):
+//   seg n MASK_1 FLO_1 ... MASK_n FLO_n s=<tau>,<radius> [m=<12 numbers: M1 then M2>]
+//       [idx1=P] [idx2=P] [mb1=P] [mb2=P] [dist1=P] [dist2=P]
+// (the layers of the frame's layers line; a static background without m=; 8-bit L PNGs, a distance as its integer square
+// root with 255 for "further than the radius"; at least one output).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -349,6 +354,69 @@ static bool run_light(Opt_State* state, const LightSpec& q)
     return true;
 }
 
+// the segment maps of one pair, synchronously (pipeline.run_seg): read every layer's mask (red channel) and flow, one
+// ArapFlow_SegMaps on the state's stream, write the outputs asked for as 8-bit L PNGs: the labels and the 0 / 255 maps as
+// they are, a distance as the integer square root of the device's squared value, 255 for its sentinel
+static bool run_seg(Opt_State* state, const SegSpec& q)
+{
+    const unsigned n = (unsigned)q.masks.size();
+    std::vector<uint8_t> masks;
+    std::vector<float> flows;
+    int w = 0, h = 0;
+    size_t N = 0;
+    for (unsigned l = 0; l < n; ++l) {
+        arapio::Image msk;
+        std::vector<float> fl;
+        int fw = 0, fh = 0;
+        if (!read_png(q.masks[l], msk)) return false;
+        if (!arapio::read_flo(q.flows[l], fl, fw, fh)) return fail("Could not read %s\n", q.flows[l].c_str());
+        if (l == 0) {
+            w = msk.w; h = msk.h; N = (size_t)w * h;
+            masks.resize(n * N);
+            flows.resize(n * N * 2);
+        }
+        if (msk.w != w || msk.h != h || fw != w || fh != h)
+            return fail("seg: %s / %s differ in size from %s\n", q.masks[l].c_str(), q.flows[l].c_str(), q.masks[0].c_str());
+        for (size_t i = 0; i < N; ++i) masks[l * N + i] = msk.rgb[3 * i];      // red channel
+        memcpy(flows.data() + l * N * 2, fl.data(), N * 8);
+    }
+    const unsigned W = (unsigned)w, H = (unsigned)h;
+    const uint64_t scratch = ArapFlow_SegMapsScratchBytes(W, H, n);
+    if (scratch == 0) return fail("seg: %u layers on %d x %d: beyond the limits\n", n, w, h);
+    DeviceArena dev;
+    const size_t d_msk = dev.stage(masks.data(), n * N), d_flow = dev.stage(flows.data(), n * N * 8);
+    OutputTable out(dev, w, h);
+    const size_t o_idx1 = out.add(FileKind::gray8, q.idx1), o_idx2 = out.add(FileKind::gray8, q.idx2);
+    const size_t o_mb1 = out.add(FileKind::gray8, q.mb1), o_mb2 = out.add(FileKind::gray8, q.mb2);
+    const std::string* const dist_path[2] = {&q.dist1, &q.dist2};
+    size_t d_dist[2];
+    for (int f = 0; f < 2; ++f) d_dist[f] = dist_path[f]->empty() ? DeviceArena::kNone : dev.take(2 * N);
+    const size_t d_scr = dev.take(scratch);
+    if (dev.alloc() != hipSuccess) return fail("seg: out of device memory\n");
+    bool ok = dev.upload() == hipSuccess &&
+              ArapFlow_SegMaps(state, W, H, n, dev.at(d_msk), dev.at(d_flow), q.have_m ? q.m : nullptr, q.have_m ? q.m + 6 : nullptr,
+                               q.tau, q.radius, out.dev(o_idx1), out.dev(o_idx2), out.dev(o_mb1), out.dev(o_mb2),
+                               dev.at(d_dist[0]), dev.at(d_dist[1]), dev.at(d_scr)) == 0 &&
+              hipDeviceSynchronize() == hipSuccess && out.download() == hipSuccess;
+    std::vector<uint16_t> d2(N);
+    std::vector<uint8_t> root[2];
+    for (int f = 0; ok && f < 2; ++f) {
+        if (d_dist[f] == DeviceArena::kNone) continue;
+        ok = hipMemcpy(d2.data(), dev.at(d_dist[f]), 2 * N, hipMemcpyDeviceToHost) == hipSuccess;
+        root[f].resize(N);
+        for (size_t i = 0; i < N; ++i) {
+            unsigned r = 0;
+            while ((r + 1) * (r + 1) <= (unsigned)d2[i]) ++r;                 // (at most 255 steps; the sentinel gives 255)
+            root[f][i] = (uint8_t)r;
+        }
+    }
+    if (!ok) return fail("ArapFlow_SegMaps failed\n");
+    if (!out.write()) return false;
+    for (int f = 0; f < 2; ++f)
+        if (!root[f].empty() && !save(FileKind::gray8, *dist_path[f], w, h, root[f].data())) return false;
+    return true;
+}
+
 // the point tracks of one sequence, synchronously (pipeline.run_tracks): read the points, every layer's mask and its T
 // state flows, one ArapFlow_TrackPoints on the state's stream, write the track file: the points themselves as frame 0
 // (occ by the frame test), then the T states
@@ -602,7 +670,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex / trk / blur / light line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur / light / seg line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -883,6 +951,7 @@ int main(int argc, const char* argv[])
                   : kind == Item::Kind::Trk ? run_tracks(state, fr->item.trk)
                   : kind == Item::Kind::Blur ? run_blur(state, fr->item.blur)
                   : kind == Item::Kind::Light ? run_light(state, fr->item.light)
+                  : kind == Item::Kind::Seg ? run_seg(state, fr->item.seg)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

@@ -65,6 +65,20 @@ static std::string canonical(const Item& it)
             m += num;
         }
         c.token("m", m); c.token("rgb1", q.rgb1); c.token("rgb2", q.rgb2); c.token("alpha1", q.alpha1); c.token("alpha2", q.alpha2);
+    } else if (it.kind == Item::Kind::Seg) {
+        const SegSpec& q = it.seg;
+        c.word("seg"); c.word(std::to_string(q.masks.size()));
+        for (size_t l = 0; l < q.masks.size(); ++l) { c.word(q.masks[l]); c.word(q.flows[l]); }
+        char num[64];
+        snprintf(num, sizeof(num), "%.9g,%u", q.tau, q.radius);
+        c.token("s", num);
+        std::string m;
+        for (int k = 0; q.have_m && k < 12; ++k) {
+            snprintf(num, sizeof(num), "%s%.9g", k ? "," : "", q.m[k]);
+            m += num;
+        }
+        c.token("m", m); c.token("idx1", q.idx1); c.token("idx2", q.idx2); c.token("mb1", q.mb1); c.token("mb2", q.mb2);
+        c.token("dist1", q.dist1); c.token("dist2", q.dist2);
     } else if (it.kind == Item::Kind::Light) {
         const LightSpec& q = it.light;
         c.word("light"); c.word(q.rgb1); c.word(q.mask1); c.word(q.rgb2); c.word(q.cover2);

@@ -20,7 +20,11 @@
 //   light line:   light RGB1 MASK1 RGB2 COVER2 l=<frame 1>;<frame 2> [rgb1=P] [rgb2=P]
 //                 (pipeline.LightLine): a frame the 19 numbers of ArapFlow_LightFrame in field order, every one in the
 //                 range ArapFlow_LightTables accepts; a repeated key is an error too
-//                 on these six any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   seg line:     seg n MASK_1 FLO_1 ... MASK_n FLO_n s=<tau>,<radius> [m=<12 numbers: M1 then M2>]
+//                 [idx1=P] [idx2=P] [mb1=P] [mb2=P] [dist1=P] [dist2=P]
+//                 (pipeline.SegLine): tau a finite number >= 0, the radius 0 .. ARAPFLOW_SEG_MAX_RADIUS, the maps finite;
+//                 without m= the background is static; a repeated key is an error too
+//                 on these seven any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -90,7 +94,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the seven forms
+// ---- the eight forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -162,8 +166,18 @@ struct LightSpec {                         // pipeline.LightLine
     std::string first_out;                 // the value of the first output token in line order: what --serve reports
 };
 
+struct SegSpec {                           // pipeline.SegLine
+    std::vector<std::string> masks, flows;
+    bool have_s = false, have_m = false;
+    float tau = 0.f;
+    unsigned radius = 0;
+    float m[12] = {};                      // M1, M2; read only with have_m
+    std::string idx1, idx2, mb1, mb2, dist1, dist2;        // outputs (empty: not wanted)
+    std::string first_out;                 // the value of the first output token in line order: what --serve reports
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
@@ -171,6 +185,7 @@ struct Item {
     TrkSpec trk;
     BlurSpec blur;
     LightSpec light;
+    SegSpec seg;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -182,6 +197,7 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::Trk    ? it.trk.out
            : it.kind == Item::Kind::Blur   ? it.blur.first_out
            : it.kind == Item::Kind::Light  ? it.light.first_out
+           : it.kind == Item::Kind::Seg    ? it.seg.first_out
                                            : it.bg.first_out();
 }
 
@@ -472,6 +488,41 @@ inline bool parse_light(std::istringstream& tok, LightSpec& q)
     return q.have_l && !q.first_out.empty();
 }
 
+inline bool parse_seg(std::istringstream& tok, SegSpec& q)
+{
+    std::string count, k, v;
+    unsigned long long n = 0, x = 0;
+    if (!(tok >> count) || !parse_uint(count, 255, n) || n < 1) return false;
+    for (unsigned long long l = 0; l < n; ++l) {
+        std::string m, f;
+        if (!(tok >> m >> f) || split_token(m, k, v) || split_token(f, k, v)) return false;
+        q.masks.push_back(m);
+        q.flows.push_back(f);
+    }
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "s") {                    // <tau>,<radius>
+            const size_t comma = v.find(',');
+            if (q.have_s || comma == std::string::npos) return false;
+            if (!parse_bg_maps(v.substr(0, comma), &q.tau, 1) || !std::isfinite(q.tau) || q.tau < 0.f) return false;
+            if (!parse_uint(v.substr(comma + 1), ARAPFLOW_SEG_MAX_RADIUS, x)) return false;
+            q.radius = (unsigned)x;
+            q.have_s = true;
+        } else if (k == "m") {
+            if (q.have_m || !parse_bg_maps(v, q.m, 12)) return false;
+            for (float c : q.m)
+                if (!std::isfinite(c)) return false;
+            q.have_m = true;
+        } else if (std::string* dst = field_of({{"idx1", &q.idx1}, {"idx2", &q.idx2}, {"mb1", &q.mb1}, {"mb2", &q.mb2},
+                                                {"dist1", &q.dist1}, {"dist2", &q.dist2}}, k)) {
+            if (!dst->empty()) return false;
+            *dst = v;
+            if (q.first_out.empty()) q.first_out = v;
+        } else return false;
+    }
+    return q.have_s && !q.first_out.empty();
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -480,7 +531,7 @@ inline Parsed parse_item(const std::string& line, Item& it)
     if (!(tok >> first)) return Parsed::Skip;
     it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
               : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : first == "light" ? Item::Kind::Light
-              : Item::Kind::Solve;
+              : first == "seg" ? Item::Kind::Seg : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
@@ -488,9 +539,10 @@ inline Parsed parse_item(const std::string& line, Item& it)
     else if (it.kind == Item::Kind::Trk) p = parse_trk(tok, it.trk) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Blur) p = parse_blur(tok, it.blur) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Light) p = parse_light(tok, it.light) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::Seg) p = parse_seg(tok, it.seg) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
-        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line"};      // by Item::Kind
+        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

@@ -11,6 +11,7 @@
   background       full-frame RGB, flow and occlusion behind a warped pair's objects (ArapFlow_Background)
   background_seq   the same over frame 1, a pair's in-between frames and frame 2 in one call (ArapFlow_BackgroundSeq)
   warp_diag        fold diagnostics of a flow: mesh statistics and the fold map (ArapFlow_WarpDiag)
+  seg_maps         object index maps, motion boundaries and boundary distance of a pair (ArapFlow_SegMaps)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -491,7 +492,7 @@ class FrameSolver:
             self.h = None
 
 
-def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, lead=()):
+def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, lead=(), view=None):
     """One ArapFlow_<name> call on host arrays.  `dims`: (W, H) or (W, H, n); `inputs`: (array or None, dtype) and
     `outputs`: (dict key, shape or None = not asked, torch dtype), both in the library's argument order; `scratch`: the
     name of the *ScratchBytes function of a call that takes a scratch buffer, or (name, its arguments) where those are
@@ -499,6 +500,7 @@ def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, 
     the inputs, an (array, dtype) to upload or a value passed as it is; an input (value, None) is passed as it is too (a
     host table among the device buffers).  An input that is a list of arrays, or an
     output whose shape is a list of shapes, is passed as a host array of device pointers and comes back as a list.
+    `view`: {key: numpy dtype} of outputs that come back reinterpreted (torch has no unsigned 16-bit tensors to allocate).
     Uploads, allocates, synchronises, calls, and downloads {key: array} of the outputs asked.  A return code of -1 is a
     ValueError where `bad_args`, every other non-zero code a RuntimeError."""
     lib = state.lib
@@ -525,7 +527,8 @@ def _warp_call(state, name, dims, inputs, outputs, scratch=None, bad_args=True, 
         raise RuntimeError("ArapFlow_%s failed: %d" % (name, rc))
     torch.cuda.synchronize()
     down = lambda t: None if t is None else t.cpu().numpy()
-    return {k: [down(x) for x in t] if isinstance(t, list) else down(t) for k, t in outs.items()}
+    res = {k: [down(x) for x in t] if isinstance(t, list) else down(t) for k, t in outs.items()}
+    return {k: a.view(view[k]) if view and k in view else a for k, a in res.items()}
 
 
 def warp_image(state, rgb, mask_red, flow):
@@ -790,6 +793,36 @@ def relight_pair(state, rgb1, mask1, rgb2, cover2, frames):
     if len(frames) != 2:
         raise ValueError("relight_pair: two light descriptions expected")
     return relight(state, rgb1, mask1, frames[0], cover_is_mask=True), relight(state, rgb2, cover2, frames[1])
+
+
+SEG_OUTPUTS = ("idx1", "idx2", "mb1", "mb2", "dist1", "dist2")
+
+
+def seg_maps(state, masks, flows, tau=1.0, radius=140, M1=None, M2=None, which=SEG_OUTPUTS):
+    """the segment maps of a pair (ArapFlow_SegMaps, DESIGN.md "Segment maps").  masks u8[n,H,W] (red channels, 0 =
+    object), flows f32[n,H,W,2], the higher index on top; M1, M2: the cameras of a moving background, six floats each, or
+    both None (numpy) -> {name: array} of the outputs `which` names: idx1 / idx2 u8[H,W], the object index maps of frame
+    1 and frame 2 (0: no object); mb1 / mb2 u8[H,W], 255 where the full forward / backward flow jumps by more than tau
+    against a 4-neighbour; dist1 / dist2 u16[H,W], the squared distance to the nearest such pixel where <= radius^2,
+    else 65535."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    flows = np.ascontiguousarray(flows, np.float32)
+    if masks.ndim != 3 or flows.shape != masks.shape + (2,):
+        raise ValueError("seg_maps: masks [n,H,W] and flows [n,H,W,2] expected")
+    n, H, W = masks.shape
+    which = tuple(which)
+    if not which or set(which) - set(SEG_OUTPUTS):
+        raise ValueError("seg_maps: which: some of %s" % ", ".join(SEG_OUTPUTS))
+    if (M1 is None) != (M2 is None):
+        raise ValueError("seg_maps: both cameras or neither")
+    radius = int(radius)
+    if not 0 <= radius <= capi.SEG_MAX_RADIUS or state.lib.ArapFlow_SegMapsScratchBytes(W, H, n) == 0:
+        raise ValueError("seg_maps: 1 <= n <= 255, 0 <= radius <= %d, 0 < W * H < 2^31 expected" % capi.SEG_MAX_RADIUS)
+    maps = [(None, None), (None, None)] if M1 is None else [(_map6(M1), None), (_map6(M2), None)]
+    return _warp_call(state, "SegMaps", (W, H, n),
+                      [(masks, np.uint8), (flows, np.float32)] + maps + [(float(tau), None), (radius, None)],
+                      [(k, (H, W) if k in which else None, torch.int16 if k.startswith("dist") else torch.uint8)
+                       for k in SEG_OUTPUTS], "SegMapsScratchBytes", view={"dist1": np.uint16, "dist2": np.uint16})
 
 
 BG_OUTPUTS = ("out_rgb1", "out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")

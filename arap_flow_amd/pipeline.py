@@ -17,6 +17,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   blur_times, blur_maps                  the schedule of a motion-blurred frame (addition)
   BlurLine, parse_blur, blur_line, run_blur    the `blur` line: the motion-blurred frames of a pair (addition)
   LightFrame, LightLine, parse_light, light_line, random_light, run_light    the `light` line: the relit pair (addition)
+  SegLine, parse_seg, seg_line, run_seg  the `seg` line: object index maps, motion boundaries, boundary distance (addition)
   TrkLine, parse_trk, trk_line, sample_track_points, run_tracks    the `trk` line: point tracks of a sequence (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
@@ -64,6 +65,9 @@ TRK_WORD = "trk"
 BLUR_WORD = "blur"
 BLUR_KEYS = ("rgb1", "rgb2", "alpha1", "alpha2")
 LIGHT_WORD = "light"
+SEG_WORD = "seg"
+SEG_KEYS = ("idx1", "idx2", "mb1", "mb2", "dist1", "dist2")
+SEG_MAX_RADIUS = 254         # ARAPFLOW_SEG_MAX_RADIUS of include/arap_opt.h
 LIGHT_KEYS = ("rgb1", "rgb2")
 
 
@@ -806,11 +810,95 @@ def random_light(rng, strength, W, H):
             LightFrame(light_twin_seed(seed), m2, f32(amp), f32(vig), tuple(gain2), f32(gamma2), *shared))
 
 
+class SegLine(NamedTuple):
+    """a `seg` line (DESIGN.md "Segment maps"), recognised by its first word: the segment maps of one pair
+        seg n MASK_1 FLO_1 ... MASK_n FLO_n s=<tau>,<radius> [m=<12 numbers: M1 then M2>]
+            [idx1=P] [idx2=P] [mb1=P] [mb2=P] [dist1=P] [dist2=P]
+    The layers are those of the frame's `layers` line (the later on top).  s=: the jump threshold tau, a finite float32
+    >= 0 written with %.9g, and the radius, 0 .. SEG_MAX_RADIUS.  m=: the camera at frame 1 and at frame 2 as in a bg line,
+    twelve finite float32 written with %.9g (`m` empty: a static background).  `out`: {key: path} in line order; every
+    file is an 8-bit L PNG: idx the raw label, mb 0 / 255, dist the integer square root of the squared distance and 255
+    for "further than the radius".  At least one output; anything else -- an unknown or repeated key, a missing `=`, an
+    empty value, a wrong count of numbers, a non-finite number, a negative tau, a radius above SEG_MAX_RADIUS -- is an
+    error."""
+    layers: list
+    tau: float
+    radius: int
+    m: tuple
+    out: dict
+
+
+def parse_seg(tokens):
+    if len(tokens) < 2 or tokens[0] != SEG_WORD:
+        raise ValueError("not a seg line: %r" % " ".join(tokens))
+    n = int(tokens[1]) if _UINT.match(tokens[1]) else 0
+    if not 1 <= n <= 255 or len(tokens) < 2 + 2 * n:
+        raise ValueError("seg line: 1..255 layers, a mask and a flow each: %r" % " ".join(tokens))
+    if any("=" in t for t in tokens[2:2 + 2 * n]):
+        raise ValueError("seg line: a path expected where a token is: %r" % " ".join(tokens))
+    out, s, m = {}, None, None
+    for t in tokens[2 + 2 * n:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in ("s", "m") + SEG_KEYS) or k in out or (k == "s" and s is not None) or (k == "m" and m is not None):
+            raise ValueError("seg line: bad or repeated token %r" % t)
+        if k == "s":
+            tau, _, radius = v.partition(",")
+            with np.errstate(over="ignore"):
+                tau = _bg_numbers(tau)
+            if len(tau) != 1 or not (math.isfinite(tau[0]) and tau[0] >= 0) or not _UINT.match(radius) or int(radius) > SEG_MAX_RADIUS:
+                raise ValueError("seg line: s= takes a tau >= 0 and a radius 0..%d: %r" % (SEG_MAX_RADIUS, t))
+            s = (tau[0], int(radius))
+        elif k == "m":
+            with np.errstate(over="ignore"):
+                m = _bg_numbers(v)
+            if len(m) != 12 or not all(math.isfinite(q) for q in m):
+                raise ValueError("seg line: m= takes 12 finite numbers, M1 then M2: %r" % t)
+        else:
+            out[k] = v
+    if s is None:
+        raise ValueError("seg line without s=: %r" % " ".join(tokens))
+    if not out:
+        raise ValueError("seg line without an output: %r" % " ".join(tokens))
+    return SegLine([(tokens[2 + 2 * l], tokens[3 + 2 * l]) for l in range(n)], s[0], s[1], m or (), out)
+
+
+def seg_line(item):
+    """the inverse of parse_seg: s=, m= if the line has maps, then the outputs in the order of SEG_KEYS"""
+    tok = [SEG_WORD, str(len(item.layers))] + [p for pair in item.layers for p in pair]
+    tok.append("s=%.9g,%d" % (float(np.float32(item.tau)), item.radius))
+    if len(item.m):
+        tok.append("m=" + ",".join("%.9g" % float(np.float32(v)) for v in item.m))
+    return " ".join(tok + ["%s=%s" % (k, item.out[k]) for k in SEG_KEYS if item.out.get(k)])
+
+
+def seg_dist_png(d2):
+    """a distance map as its file shows it: the integer square root of the uint16 squared distance, 255 for the sentinel
+    65535 (isqrt(65535) = 255; every other value is <= 254^2)"""
+    # (exact: the float64 root of an integer below 2^16 is an integer or at least 2^-9 away from one)
+    return np.floor(np.sqrt(np.asarray(d2, np.uint16).astype(np.float64))).astype(np.uint8)
+
+
+def run_seg(state, spec):
+    """one `seg` line: read every layer's mask and flow, one opt.seg_maps for the outputs the line asks for, write them as
+    8-bit L PNGs (SegLine)"""
+    from . import opt
+    masks = np.stack([load_mask_red(m) for m, _ in spec.layers])
+    flows = np.stack([flo.flow_read(f) for _, f in spec.layers])
+    if flows.shape[:3] != masks.shape:
+        raise ValueError("seg line: mask and flow sizes differ")
+    M1, M2 = (spec.m[:6], spec.m[6:]) if len(spec.m) else (None, None)
+    r = opt.seg_maps(state, masks, flows, tau=spec.tau, radius=spec.radius, M1=M1, M2=M2, which=tuple(spec.out))
+    for k, path in spec.out.items():
+        save_occ(seg_dist_png(r[k]) if k.startswith("dist") else r[k], path)
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
     BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`, a
-    LightLine when it is `light`"""
+    LightLine when it is `light`, a SegLine when it is `seg`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == SEG_WORD:
+        return parse_seg(tok)
     if tok and tok[0] == LIGHT_WORD:
         return parse_light(tok)
     if tok and tok[0] == BLUR_WORD:
@@ -842,15 +930,17 @@ def format_line(item):
         return blur_line(item)
     if isinstance(item, LightLine):
         return light_line(item)
+    if isinstance(item, SegLine):
+        return seg_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
-    first of a bg line's bg_outputs, a tex, blur or light line's first output token, a trk line's track file"""
+    first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file"""
     if isinstance(item, TrkLine):
         return item.out
-    if isinstance(item, (BlurLine, LightLine)):
+    if isinstance(item, (BlurLine, LightLine, SegLine)):
         return next(iter(item.out.values()))
     if isinstance(item, BgLine):
         return bg_outputs(item)[0]

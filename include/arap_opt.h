@@ -577,6 +577,36 @@ int ArapFlow_LightTables(const ArapFlow_LightFrame* frame, unsigned W, unsigned 
 int ArapFlow_Relight(Opt_State* state, unsigned W, unsigned H, const void* rgb, const void* cover, int cover_is_mask,
                      const ArapFlow_LightFrame* frame, void* out_rgb);
 
+/* Segment maps (DESIGN.md "Segment maps"): the object index maps of both frames of a pair, the motion boundaries of its
+ * forward and backward flow, and the squared distance to the nearest boundary.  The layers are ArapFlow_WarpLayers':
+ * masks_red uint8[n][H][W] (0 = object), flows float32[n][H][W][2], the higher index on top.
+ *   idx1   uint8[H][W]: the owner of the frame-1 pixel (the largest l with masks_red[l] == 0) + 1; 0: no layer owns it.
+ *   idx2   uint8[H][W]: the layer of the layered rasteriser's winner at the frame-2 pixel + 1; 0: nothing drawn there.
+ *          idx2 != 0 exactly where ArapFlow_WarpLayers' out_mask != 0.
+ *   F1, B2 the full flows, no outputs: F1(p) = flows[owner][p] on an owned pixel, B2(q) = ArapFlow_WarpLayers' out_bwd on
+ *          a covered one; elsewhere the moving background's flow_full / bwd_full expression of ArapFlow_Background for
+ *          the cameras M1, M2 (HOST, six floats each), or exactly (0, 0) when both are NULL.  Bit-equal M1 and M2 give the
+ *          bytes of the static call.
+ *   mb1    uint8[H][W]: 255 where F1 jumps against a 4-neighbour q inside the frame, !(dx * dx + dy * dy <= tau * tau)
+ *          with (dx, dy) = F1(p) - F1(q), every operator one float32 operation, tau * tau formed once; else 0.  A
+ *          non-finite difference is a jump; both sides of a jump are marked.  mb2: the same on B2.
+ *   dist1  uint16[H][W]: the exact squared Euclidean distance in pixels to the nearest pixel with mb1 = 255 if that is
+ *          <= radius^2, else 65535 (also in a frame without boundary).  dist2: the same on mb2.
+ * Any output may be NULL, not all six; a pass no output needs is not launched: without idx2, mb2 and dist2 nothing is
+ * rasterised, without dist1 and dist2 no distance pass runs.  Integer atomics of the rasteriser only, no float
+ * reduction: two runs give identical bytes.  `scratch`: 256-byte aligned device buffer of
+ * ArapFlow_SegMapsScratchBytes(W, H, n) bytes -- per pixel 8 (key image) + 8 (full flow) + 1 (boundary map) + 1 (column
+ * distance) = 18, however many layers, plus a few hundred bytes; 0 for sizes the call refuses.  The call clears what it
+ * needs of it.  Asynchronous on the state's stream.  Returns 0; -1, and nothing is launched or written, on bad arguments:
+ * a null state, masks_red, flows or scratch, all six outputs NULL, n = 0 or n > 255, W * H = 0 or >= 2^31, exactly one of
+ * M1 / M2, maps ArapFlow_BackgroundMaps refuses, a negative or non-finite tau, radius > ARAPFLOW_SEG_MAX_RADIUS, an
+ * output overlapping an input, the scratch or another output; else a HIP error code. */
+#define ARAPFLOW_SEG_MAX_RADIUS 254
+uint64_t ArapFlow_SegMapsScratchBytes(unsigned W, unsigned H, unsigned n);
+int ArapFlow_SegMaps(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* masks_red, const void* flows,
+                     const float M1[6], const float M2[6], float tau, unsigned radius, void* idx1, void* idx2, void* mb1,
+                     void* mb2, void* dist1, void* dist2, void* scratch);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised

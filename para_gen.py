@@ -6,6 +6,7 @@
                      [--bg_dir DIR [--bg_motion [STRENGTH] [--mid_bg]]] [--diag] [--max_fold FRAC] [--retex]
                      [--bg_dir DIR --blur SHUTTER [SAMPLES]]
                      [--bg_dir DIR --relight [STRENGTH]]
+                     [--seg [TAU [RADIUS]]]
                      [--tracks P]
                      [--arap_bin BIN] [--dm_bin BIN | --matches DIR] [--narap N] [--jobs J]
 
@@ -73,6 +74,13 @@ pairs serially and forks one ARAP child per hand-out, which would leave the GPU 
     line per pair, handed to a worker once both frames are final: after the segments are merged and the background is
     composited, with --bg_motion after the pair's bg line.  The geometry is untouched, so it costs no solve and shares the
     pair's Flow file: OUT/all_files_light.list names `inpRGB_light wRGB_light Flow`.  Needs --bg_dir.
+  * --seg [TAU [RADIUS]] writes the segment maps of every kept pair (DESIGN.md "Segment maps"), named like the pair's flow
+    file, as 8-bit PNGs: OUT/Index1 and OUT/Index2, the object index of every pixel of frame 1 and of frame 2 (0: no
+    object; the solved segment in list order + 1); OUT/MB and OUT/MBBwd, 255 where the full forward / backward flow jumps by
+    more than TAU pixels (default 1) against a 4-neighbour; OUT/MBDist and OUT/MBDistBwd, the distance in whole pixels to the
+    nearest such pixel up to RADIUS (default 140, at most 254), 255 beyond -- from one `seg` line per pair over its solved
+    layers, handed to a worker once the pair's solves (and layers line) are done and before the segments are merged.  With
+    --bg_motion the line carries the pair's cameras, so the background's flow counts; without it the background is static.
 """
 import argparse
 import json
@@ -102,6 +110,7 @@ color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
 color_blur_dir, wrgb_blur_dir = "inpRGB_blur", "wRGB_blur"       # --blur: the motion-blurred pair (addition)
 color_light_dir, wrgb_light_dir = "inpRGB_light", "wRGB_light"   # --relight: the relit pair (addition)
+SEG_DIRS = dict(idx1="Index1", idx2="Index2", mb1="MB", mb2="MBBwd", dist1="MBDist", dist2="MBDistBwd")   # --seg (addition)
 color_tex_dir, wrgb_tex_dir = "inpRGB_tex", "wRGB_tex"           # --retex: the random-texture twin (addition)
 bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
 diag_dir, fold_dir = "Diag", "Fold"     # --diag: fold diagnostics (addition)
@@ -233,6 +242,7 @@ class Frame:
     blur_tmp: tuple = ()           # --blur: the blur line's own input file, deleted when it is done
     light: object = None           # --relight: the pair's light line (pipeline.LightLine), handed out once both frames are final
     light_tmp: tuple = ()          # --relight: the light line's own input file, deleted when it is done
+    seg: object = None             # --seg: the pair's seg line (pipeline.SegLine), handed out where a tex line is
 
     @property
     def solves(self):
@@ -253,6 +263,7 @@ def prepare_pair(args):
     trk_out, n_tracks = p.pop("trk_gen", None), p.pop("_tracks", 0)         # --tracks: the track file, the number of points
     blur1, blur2 = p.pop("rgb1blur_gen", None), p.pop("rgb2blur_gen", None)     # --blur: the blurred pair's two frames
     light1, light2 = p.pop("rgb1light_gen", None), p.pop("rgb2light_gen", None)     # --relight: the relit pair's two frames
+    seg_out = {k: p.pop(k + "_seg_gen") for k in SEG_DIRS if k + "_seg_gen" in p}   # --seg: the pair's six maps
     layer_masks = []
     for k in p:
         os.makedirs(osp.dirname(p[k]), exist_ok=True)
@@ -344,6 +355,12 @@ def prepare_pair(args):
             rec.blur_tmp = (bg_png,)
         rec.blur = pipeline.BlurLine(line.rgb, [(sg.mask, sg.flow) for sg in rec.solves], bg_png, shutter, samples, maps,
                                      dict(rgb1=blur1, rgb2=blur2))
+    if seg_out and rec.solves:                  # the segment maps: the solved layers, the bg line's cameras where there is one
+        for q in seg_out.values():
+            os.makedirs(osp.dirname(q), exist_ok=True)
+        tau, radius = flags.seg
+        rec.seg = pipeline.SegLine([(sg.mask, sg.flow) for sg in rec.solves], tau, radius,
+                                   tuple(float(v) for v in np.concatenate([M1, M2])) if big is not None else (), seg_out)
     if big is not None:
         # the bg line's own inputs, beside the pair's constraints: the enlarged picture as a PNG (the worker's codec),
         # with --multseg the union mask (object where any solved segment is object), and the line itself
@@ -600,6 +617,7 @@ def scan(flags, input_root, output_root):
                                                            tx1=color_tex_dir, tx2=wrgb_tex_dir, trk=tracks_dir,
                                                            bl1=color_blur_dir, bl2=wrgb_blur_dir,
                                                            lt1=color_light_dir, lt2=wrgb_light_dir,
+                                                           **{"seg_" + k: v for k, v in SEG_DIRS.items()},
                                                            obw=occ_bwd_dir, occ=occ_dir, dia=diag_dir, fol=fold_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
                                                            ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
@@ -638,6 +656,8 @@ def scan(flags, input_root, output_root):
                     e.update(rgb1blur_gen=osp.join(roots["bl1"], seq, f + ".png"), rgb2blur_gen=osp.join(roots["bl2"], seq, f + ".png"))
                 if getattr(flags, "relight", None) is not None:
                     e.update(rgb1light_gen=osp.join(roots["lt1"], seq, f + ".png"), rgb2light_gen=osp.join(roots["lt2"], seq, f + ".png"))
+                if getattr(flags, "seg", None):
+                    e.update({k + "_seg_gen": osp.join(roots["seg_" + k], seq, f + ".png") for k in SEG_DIRS})
                 if getattr(flags, "bg_motion", None) is not None:       # the full-frame maps of what the run asks for
                     e["flowfull_gen"] = osp.join(roots["ful"], seq, f + ".flo")
                     if "occ_gen" in e or LAYERS_OCC in e:
@@ -661,6 +681,7 @@ def scan(flags, input_root, output_root):
                 # every requested output
                 done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e) + mid_bg_paths(e)
                 done += track_paths(e) + [e[k] for k in ("rgb1blur_gen", "rgb2blur_gen", "rgb1light_gen", "rgb2light_gen") if k in e]
+                done += [e[k + "_seg_gen"] for k in SEG_DIRS if k + "_seg_gen" in e]
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -773,7 +794,7 @@ def main(flags):
     frames = {}                                        # done token of a line a worker holds -> its Frame
     posts, lock = [], threading.Lock()
     counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0, tracks_done=0, blur_done=0,
-                  light_done=0)
+                  light_done=0, seg_done=0)
 
     def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
         frames[pipeline.done_token(item)] = rec
@@ -816,8 +837,8 @@ def main(flags):
                         if osp.exists(q):
                             os.remove(q)
                 return
-            if rec.stage == "tex":                     # its tex (or blur) line: the segment files may go now
-                counts["tex_done" if rec.tex is not None else "blur_done"] += 1
+            if rec.stage == "tex":                     # its tex (or blur, or seg) line: the segment files may go now
+                counts["tex_done" if rec.tex is not None else "blur_done" if rec.blur is not None else "seg_done"] += 1
                 if rec.remove:
                     for q in rec.blur_tmp:
                         if osp.exists(q):
@@ -843,7 +864,7 @@ def main(flags):
                     for q in later:
                         hand_out(rec, q, workers.put_owed)
                     return
-            twin = rec.tex if rec.tex is not None else rec.blur       # (--retex and --blur exclude each other)
+            twin = rec.tex if rec.tex is not None else rec.blur if rec.blur is not None else rec.seg   # (they exclude each other)
             if twin is not None and rec.stage != "tex":        # the twin reads the segments' flows: before finish_frame
                 rec.stage = "tex"
                 hand_out(rec, twin, workers.put_owed)
@@ -884,7 +905,7 @@ def main(flags):
                 workers.owe()
             if rec.motion is not None:
                 workers.owe()
-            for later in (rec.tex, rec.motion_tex, rec.tracks, rec.blur, rec.light):
+            for later in (rec.tex, rec.motion_tex, rec.tracks, rec.blur, rec.light, rec.seg):
                 if later is not None:
                     workers.owe()
             with lock:
@@ -909,6 +930,7 @@ def main(flags):
     stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
                  layers_done=counts["layers_done"], bg_done=counts["bg_done"], tex_done=counts["tex_done"],
                  tracks_done=counts["tracks_done"], blur_done=counts["blur_done"], light_done=counts["light_done"],
+                 seg_done=counts["seg_done"],
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -1028,7 +1050,31 @@ def parse(argv=None):
                              "drifting illumination field, a flickering tone curve, a vignette and sensor noise, every "
                              "amplitude scaled by STRENGTH (default 1), and OUT/all_files_light.list, whose lines name those "
                              "two and the pair's own Flow file (DESIGN.md \"Relit frames\")")
+    parser.add_argument("--seg", nargs="*", default=None, metavar="TAU [RADIUS]",
+                        help="also write the segment maps of every pair, 8-bit PNGs named like its flow file: OUT/Index1 and "
+                             "OUT/Index2 (object index per pixel of frame 1 / frame 2), OUT/MB and OUT/MBBwd (255 where the "
+                             "full forward / backward flow jumps by more than TAU pixels, default 1), OUT/MBDist and "
+                             "OUT/MBDistBwd (whole pixels to the nearest such pixel up to RADIUS, default 140, at most 254; "
+                             "255 beyond) (DESIGN.md \"Segment maps\")")
     flags = parser.parse_args(argv)
+    if flags.seg is not None:
+        try:
+            if len(flags.seg) > 2:
+                raise ValueError
+            tau = float(np.float32(float(flags.seg[0]))) if flags.seg else 1.0
+            radius = int(flags.seg[1]) if len(flags.seg) == 2 else 140
+        except (ValueError, OverflowError):
+            parser.error("--seg [TAU [RADIUS]]: a number and an integer")
+        if not (np.isfinite(tau) and tau >= 0) or not 0 <= radius <= pipeline.SEG_MAX_RADIUS:
+            parser.error("--seg [TAU [RADIUS]]: a finite TAU >= 0 and a RADIUS of 0 .. %d" % pipeline.SEG_MAX_RADIUS)
+        flags.seg = (tau, radius)
+        if flags.mid or flags.mid_layers or flags.mid_bg or flags.retex or flags.blur is not None or flags.relight is not None:
+            parser.error("--seg cannot be combined with --mid / --mid_layers / --mid_bg / --retex / --blur / --relight: the "
+                         "variants share the clean pair's geometry files, and maps of in-between frames are made with "
+                         "opt.seg_maps, not from this command line")
+        if not own_arap_bin(flags.arap_bin):
+            parser.error("--seg needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
+                         "not know the seg line")
     if flags.relight is not None:
         if not (np.isfinite(flags.relight) and flags.relight >= 0):
             parser.error("--relight [STRENGTH]: a finite STRENGTH >= 0")
