@@ -10,7 +10,8 @@
 //     workgroup, one vertex per lane per slot; tiles start at each 8-row band's first active vertex),
 //   * the search direction p and cos/sin(A) live in LDS as 34x10 halo'd tiles (the stencil reads
 //     every neighbour from LDS, one tile slot ahead of the arithmetic; cells that are not active
-//     vertices are zero and invalid edges get a zero weight, so the phases are branch free),
+//     vertices are zero and invalid edges get a zero weight, so the phases are branch free); up to
+//     7 slots a lane's OWN p stays in registers as well and the LDS copy serves its neighbours only,
 //   * per iteration the group exchanges only (a) two 16-byte partial sums per workgroup (all-gather
 //     of data-tagged granules, summed by every workgroup in the same fixed order -> deterministic) and
 //     (b) the preconditioned residual z of tile-border vertices, from which each workgroup rebuilds
@@ -37,7 +38,8 @@ namespace arap {
 
 constexpr int RES_WGS = 512;             // workgroups per launch: TWO per CU of an MI355X (256 CUs), so that one
                                          // workgroup computes while its CU-mate (another frame's group) waits
-constexpr int RES_MAX_GROUPS = 16;       // most equal groups ARAPOPT_RES_GROUPS may force (experiments)
+constexpr int RES_MAX_GROUPS = RES_WGS; // most equal groups ARAPOPT_RES_GROUPS may force (experiments, tests: down to one
+                                         // workgroup per group)
 constexpr int RES_THREADS = 256;         // 4 wavefronts = 4 x 2 rows of a 32x8 tile, one per SIMD
 constexpr int RES_SLOTS = 9;             // tile slots per workgroup (register arrays, fully unrolled)
 constexpr int RES_TILES_PER_WG = RES_SLOTS;
@@ -71,19 +73,31 @@ static_assert(2 * ((RES_LDS_BYTES + 1279) / 1280 * 1280) <= 160 * 1024, "two wor
 #define RES_WREG_SLOTS 7      // keep the per-vertex edge weights in registers when at most this many slots are in use
 #endif
 #ifndef RES_WREG_8
-#define RES_WREG_8 2          // edge weights (of four) kept in registers at 8 slots (3 spill; 2: +1.5 %)
+#define RES_WREG_8 4          // edge weights (of four) kept in registers at 8 slots (all, since a kept weight takes one VGPR: RES_WPIN)
 #endif
 #ifndef RES_WREG_9
-#define RES_WREG_9 2          // ... at 9 slots
+#define RES_WREG_9 4          // ... at 9 slots
 #endif
 #ifndef RES_WREG_FIT
-#define RES_WREG_FIT 6        // ... the fit weight too when at most this many slots are in use (else only the four edge weights)
+#define RES_WREG_FIT 9        // ... the fit weight too when at most this many slots are in use (else only the four edge weights)
 #endif
 #ifndef RES_WREG_FIT_FLAT
-#define RES_WREG_FIT_FLAT 7   // ... in the flat-sums flavour (RES_SUMS_FLAT below), whose loop leaves 15 VGPRs more
+#define RES_WREG_FIT_FLAT 9   // ... in the flat-sums flavour (RES_SUMS_FLAT below)
+#endif
+#ifndef RES_WPIN
+#define RES_WPIN 1            // kept weights take one VGPR each, not two (phase A, the empty asm at the head of the loop)
+#endif
+#ifndef RES_PREG_SLOTS
+#define RES_PREG_SLOTS 7      // the own search direction p stays in registers (3 per slot) when at most this many slots are in use
+#endif
+#ifndef RES_PREG_SLOTS_FLAT
+#define RES_PREG_SLOTS_FLAT 7 // ... in the flat-sums flavour
+#endif
+#ifndef RES_SWEEP1
+#define RES_SWEEP1 1          // the flat flavour's sweep of the group's granules is one straight-line trip
 #endif
 #ifndef RES_WREG_8_FLAT
-#define RES_WREG_8_FLAT 3     // edge weights kept in registers at 8 / 9 slots in the flat-sums flavour (8 slots: 4 spill)
+#define RES_WREG_8_FLAT 4     // edge weights kept in registers at 8 / 9 slots in the flat-sums flavour
 #endif
 #ifndef RES_WREG_9_FLAT
 #define RES_WREG_9_FLAT RES_WREG_9
@@ -133,8 +147,9 @@ constexpr int RES_GRAN_PER_LAUNCH = RES_GRAN_X + RES_GRAN_L1;
 // host knows when it deals the launch: host_resident.h) only ever runs group_sum, and carrying the other two costs it
 // scalar branches and SGPR reloads on the chain of both sums and ~15 VGPRs in the loop.
 //   RES_SUMS_ANY  : group_sum, group_sum_x and group_sum_h, chosen at run time -- any deal
-//   RES_SUMS_FLAT : group_sum only -- right for any deal (the flat gather sweeps ranks k, k + 64, ...), dealt only to
-//                   launches of groups of <= 64 workgroups, for which it computes the same bits as RES_SUMS_ANY
+//   RES_SUMS_FLAT : group_sum only, with a one-trip sweep (lane k reads rank k) -- right ONLY for launches whose groups all
+//                   have <= 64 workgroups, for which it computes the same bits as RES_SUMS_ANY; the host deals it to
+//                   no other launch (host_resident.h: resident_launch_sums, enforced in plan_resident_pack)
 constexpr int RES_SUMS_ANY = 0, RES_SUMS_FLAT = 1, RES_SUMS_COUNT = 2;
 
 // One entry per workgroup of a launch, written by the host (host_resident.h: plan_resident_pack): which solve the
@@ -216,6 +231,10 @@ __device__ __forceinline__ double block_sum_uniform(double t)
 // every tag equals `epoch`; lane k owns workgroups k, k+64, ... and adds their partials in that order,
 // then the fixed DPP tree above adds the lanes, so every workgroup of the group computes the same bits.
 // Returns the sum rounded to float in every thread; false on timeout.
+// ONE: the group has at most 64 workgroups (the flat flavour's host invariant, host_resident.h: plan_resident_pack), so
+// the sweep is one straight-line trip: lane k reads rank k's pair, lanes at or beyond wgs read rank 0's (an address
+// inside the group's granules), add +0.0 and count as arrived.
+template <bool ONE = false>
 __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned long long* gran_group, int rank,
                                           int wgs, float* bcast /* LDS, 2 floats */, unsigned* err, float& out,
                                           bool fast = false, double* out_d = nullptr, bool nowait = false,
@@ -245,8 +264,25 @@ __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned 
         bool ok = false;
         if (tm) { c1 = __builtin_amdgcn_s_memtime(); tm[0] += c1 - c0; c0 = c1; }
         __builtin_amdgcn_s_sleep(RES_FIRST_LOOK);
+        // what does not depend on the granules is formed here, under the first-look sleep: behind the loads' return stand
+        // two compares, one mask operation and the vote, and one select per half of the value
+        const bool own1 = RES_OWN_LOCAL && lane == rank;
+        const bool look = ONE && lane < wgs && !own1;            // this lane's granules count
+        const double idle = own1 ? part : 0.0;                   // (a partial is a sum that started from +0.0: never -0.0,
+                                                                 //  so 0.0 + partial, what the general sweep forms, is the partial)
+        const unsigned long long* const q1 = buf + RES_GS * ((ONE && lane < wgs) ? lane : 0);
         for (unsigned spins = 0; spins < RES_SPIN_LIMIT; ++spins) {
             if (tm) tm[3] += 1;
+            if (ONE) {
+                const unsigned long long lo = __hip_atomic_load(q1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long hi = __hip_atomic_load(q1 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const bool late = look && ((unsigned)(lo >> 32) != epoch || (unsigned)(hi >> 32) != epoch);
+                v = look ? __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull))) : idle;
+                ok = !__any(late) || nowait;
+                if (ok) break;
+                if (RES_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
+                continue;
+            }
             v = 0.0;
             bool mine_ok = true;
             for (int m = lane; m < wgs; m += 64) {
@@ -483,9 +519,10 @@ __device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 do
 // LDS map: 9 halo'd tiles x {px,py,pa,cos,sin} (61 200 B); halo table (uint2 per halo cell, <= 720; it
 // starts life as the u16 cell list); tile origins int2[9]; the 10-entry M^-1_O table; broadcast + reduction scratch;
 // the staging area of the border z (9 x 80 float4, 11 520 B).
-// Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), plus the edge weights where they fit
-// (4 per slot up to 7 slots, 2 at 8 and 9): 253 VGPRs at 7 slots, 249 at 9, no scratch.  (The flat-sums flavour, SUMS
-// below, keeps the fit weight too at 7 slots and 3 edge weights at 8: 251 / 245 / 237 VGPRs at 7 / 8 / 9 slots.)
+// Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), the four edge weights and the fit
+// weight (5 x NS, one VGPR each: RES_WPIN) and, up to 7 slots, the own search direction p (3 x NS; z = M^-1 r of phase B
+// stays in Ap's registers until the update): 230 / 233 / 241 VGPRs at 7 / 8 / 9 slots in the flat-sums flavour (SUMS
+// below), 245 / 247 / 255 in the other, no scratch.
 // NS = tile slots the loops run over (1 .. RES_SLOTS): the most tiles any workgroup of the LAUNCH holds (the host picks
 // the instantiation per launch, host_step.h: enqueue_gn_step).  The phases are fully unrolled and branch free over the
 // slots, so their length is proportional to NS: a launch whose solves need 7 tiles per workgroup runs the 7-slot kernel.
@@ -496,9 +533,12 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     static_assert(NS >= 1 && NS <= RES_SLOTS, "slots");
     static_assert(SUMS == RES_SUMS_ANY || SUMS == RES_SUMS_FLAT, "group-sum flavour");
     constexpr bool FLAT = SUMS == RES_SUMS_FLAT;       // hier, hierx and subfast below are compile-time false
-    // what the flat loop frees goes to weights kept in registers -- not in the instrumented build, whose stamp accumulators
-    // need those registers (with the weights it spills in the update phase and its stamps measure the spills)
+    // (the knobs of the weights once differed between the flat loop and the others, instrumented build included: SPEND
+    //  chooses between two sets of defaults that are now the same)
     constexpr bool SPEND = FLAT && !STAMPS;
+    constexpr bool ONE_TRIP = FLAT && RES_SWEEP1 != 0;         // every group of a flat launch has <= 64 workgroups
+    // own search direction in registers across iterations, z kept from phase B to the update phase (in Ap's registers)
+    constexpr bool PREG = NS <= (FLAT ? RES_PREG_SLOTS_FLAT : RES_PREG_SLOTS);
     constexpr int WFIT = SPEND ? RES_WREG_FIT_FLAT : RES_WREG_FIT;    // the fit weight lives in registers up to this many slots
     unsigned long long tA = 0, tS1 = 0, tB = 0, tS2 = 0, tU = 0, t0 = 0, t1 = 0;
     unsigned long long tm[6] = {0, 0, 0, 0, 0, 0}, tbs = 0, tzr = 0;     // STAMPS: inside the group sums (shader clocks; wave 0)
@@ -565,6 +605,9 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     float dx_[NS], dy_[NS], da_[NS];
     float apx[NS], apy[NS], apa[NS];
     float ma_[NS], mo_[NS];
+    float2 pxy[PREG ? NS : 1];                         // own p (PREG): formed where p0 is, updated where the LDS copy is
+    float pal[PREG ? NS : 1];
+    float zx_[PREG ? NS : 1], zy_[PREG ? NS : 1], za_[PREG ? NS : 1];     // z = M^-1 r from phase B to the update (Ap is dead there)
     unsigned fl[NS];
     int ibase[NS];                                     // SGPRs
     // phase A weights an edge by wr^2 or +0 (fit term: wf^2 or +0) according to the vertex's flag bits.  With registers
@@ -573,6 +616,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     constexpr int NWR = NS <= RES_WREG_SLOTS ? 4 : (NS == 8 ? (SPEND ? RES_WREG_8_FLAT : RES_WREG_8)
                                                             : (SPEND ? RES_WREG_9_FLAT : RES_WREG_9));     // edge weights kept per slot
     constexpr bool WREG = NWR > 0;
+    constexpr bool WPIN = WREG && RES_WPIN != 0;
     float we[WREG ? NS : 1][5];
     const int loff = lx + W * ly;                      // this lane's vertex inside a tile: index = ibase + loff
 
@@ -643,10 +687,16 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         rx[j] = act ? qR[j].x : 0.f; ry[j] = act ? qR[j].y : 0.f; ra[j] = act ? qRa[j] : 0.f;
         ma_[j] = act ? qM[j] : 0.f;
         mo_[j] = moLUT[__popc(qF[j] & 15u) + 5 * (int)((qF[j] >> 4) & 1u)];      // M^-1 of the Offset components
+        const float2 p0 = make_float2(mo_[j] * rx[j], mo_[j] * ry[j]);            // p0 = M^-1 r (k_gn_init)
+        const float pa0 = ma_[j] * ra[j];
         if (act) {
-            TP2(T)[cell] = make_float2(mo_[j] * rx[j], mo_[j] * ry[j]);           // p0 = M^-1 r (k_gn_init)
+            TP2(T)[cell] = p0;
             TCS(T)[cell] = qC[j];
-            TPA(T)[cell] = ma_[j] * ra[j];
+            TPA(T)[cell] = pa0;
+        }
+        if (PREG) {                                    // what the own cell holds: p0, or the zero it was filled with
+            pxy[j] = act ? p0 : make_float2(0.f, 0.f);
+            pal[j] = act ? pa0 : 0.f;
         }
         if (vF[j] & F_ACT) {
             const int hc = vrow * LROW + (lx + 1);
@@ -763,7 +813,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15u;     // HW_REG_XCC_ID
         float dummy;
         const double mine = (double)xcc + 65536.0 * (double)(xcc * xcc);
-        alive = group_sum(mine, 1u, gran_group, rank, wgs, bcast, rd.err, dummy, false, wsum + 8);
+        alive = group_sum<ONE_TRIP>(mine, 1u, gran_group, rank, wgs, bcast, rd.err, dummy, false, wsum + 8);
         const double tot = wsum[8];
         const double s2 = floor(tot / 65536.0), s1 = tot - 65536.0 * s2;
         fast = rd.allow_fast && ((double)wgs * s2 == s1 * s1);
@@ -827,9 +877,22 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     for (int l = 0; l < L && alive; ++l) {
         // ---------------- phase A: Ap = J^T J p, sigma = p.Ap --------------------------------------
         // Software pipelined over the tile slots: the 15 LDS reads of slot j+1 (own cell + 4 neighbours x
-        // {(px,py), (cos,sin), pa}) are issued before the arithmetic of slot j, so that with only two wavefronts
-        // per SIMD the LDS round trip hides behind ~70 VALU instructions instead of stalling every slot.
+        // {(px,py), (cos,sin), pa}; 13 with the own p in registers, PREG) are issued before the arithmetic of slot j,
+        // so that with only two wavefronts per SIMD the LDS round trip hides behind ~70 VALU instructions instead of
+        // stalling every slot.
         static_assert(F_E0 == 1u && F_E1 == 2u && F_E2 == 4u && F_E3 == 8u && F_FIT == 16u && F_ACT == 32u, "bit numbers below");
+        // A kept weight is the first operand of a v_pk_fma_f32 as (w, w).  Loop invariant, the pair is built once in front
+        // of the loop and both halves stay live: two VGPRs per weight.  Passed through an empty asm here, once per
+        // iteration, the weight is a value of this iteration and the broadcast folds into op_sel_hi: one VGPR, the same
+        // instructions (tools/loop_diff.py pairs).  (Pinned at the head of each slot instead, the slots' LDS reads and
+        // sign flips are compiled differently: +40 VALU instructions at 8 and 9 slots.)
+        if (WPIN) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j)
+#pragma unroll
+                for (int e_ = 0; e_ < 5; ++e_)
+                    if (e_ < NWR || (e_ == 4 && NS <= WFIT)) asm volatile("" : "+v"(we[WREG ? j : 0][e_]));
+        }
         double acc = 0.0;
         float2 Lpv[2], Lcs[2], LqO[2][4], Lcn[2][4];
         float Lpa[2], LqA[2][4];
@@ -843,9 +906,9 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         {                                                                                              \
             const int s_ = (J) & 1;                                                                    \
             const char* T_ = (const char*)lds + (J) * (LTILE * 4);                                     \
-            Lpv[s_] = *(const float2*)(T_ + offP[0]);                                                  \
+            if (!PREG) Lpv[s_] = *(const float2*)(T_ + offP[0]);                                       \
             Lcs[s_] = *(const float2*)(T_ + offP[0] + LPLANE * 8);                                     \
-            Lpa[s_] = *(const float*)(T_ + offA[0] + LPLANE * 16);                                     \
+            if (!PREG) Lpa[s_] = *(const float*)(T_ + offA[0] + LPLANE * 16);                          \
             _Pragma("unroll") for (int n_ = 0; n_ < 2; ++n_) {                                         \
                 LqO[s_][n_] = *(const float2*)(T_ + offP[n_ + 1]);                                     \
                 Lcn[s_][n_] = *(const float2*)(T_ + offP[n_ + 1] + LPLANE * 8);                        \
@@ -878,9 +941,9 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 // Branch free: every lane evaluates all four edges (LDS reads stay inside the halo'd tile, whose
                 // never-written cells were zero-filled in the prologue, so every operand is finite) and an edge
                 // whose flag bit is clear gets the weight +0: fma(0, u, a) = a exactly.
-                const float2 pv = Lpv[sj];
+                const float2 pv = PREG ? pxy[PREG ? j : 0] : Lpv[sj];
                 const float2 csv = Lcs[sj];                      // (ci, si)
-                const float pa_ = Lpa[sj];
+                const float pa_ = PREG ? pal[PREG ? j : 0] : Lpa[sj];
                 const float ci = csv.x, si = csv.y;
                 const float2 pa2 = make_float2(pa_, pa_);
                 float2 axy = make_float2(0.f, 0.f);
@@ -934,7 +997,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             if (STAMPS) tbs += __builtin_amdgcn_s_memtime() - cb;
             alive = (!FLAT && hierx) ? group_sum_x(block_sum_uniform(bs), 2u * l + 2u, gran_group, granx_group, rank, wgs, bcast, rd.err, sigma, subfast)
                   : (!FLAT && hier)  ? group_sum_h(block_sum_uniform(bs), 2u * l + 2u, gran_group, gran2, rank, wgs, bcast, rd.err, sigma, subfast)
-                          : group_sum(bs, 2u * l + 2u, gran_group, rank, wgs, bcast, rd.err, sigma, fast, nullptr, rd.nowait != 0,
+                          : group_sum<ONE_TRIP>(bs, 2u * l + 2u, gran_group, rank, wgs, bcast, rd.err, sigma, fast, nullptr, rd.nowait != 0,
                                       STAMPS ? tm : nullptr, STAMPS ? tarr : nullptr);
         }
         // (sigma is wanted HERE, with the outcome: else the compiler reads `ok` from the broadcast, branches on it and only
@@ -958,6 +1021,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             ry[j] = fmaf(-alpha, apy[j], ry[j]);
             ra[j] = fmaf(-alpha, apa[j], ra[j]);
             const float zx = mo * rx[j], zy = mo * ry[j], za = ma * ra[j];
+            if (PREG) { zx_[j] = zx; zy_[j] = zy; za_[j] = za; }
             // Only a tile's border is ever read by another tile (rows 0 and 7, the two end columns): those lanes drop
             // their z into the LDS staging area; waves 1-3 send it out after the block sum below.  (Vector memory stores
             // cost their issue slot whatever the number of active lanes: from here they would be 21 nearly empty store
@@ -968,7 +1032,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             acc += (double)keep_if<5>(f, dot3(zx, zy, za, rx[j], ry[j], ra[j]));
             __builtin_amdgcn_sched_barrier(0);
         }
-        // (delta += alpha p is left to the update phase, which reads the workgroup's own p anyway)
+        // (delta += alpha p is left to the update phase, which has the workgroup's own p at hand)
         float rhoNew;
         RES_PRIO_END()
         RES_STAMP(tB);
@@ -1000,7 +1064,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             }
             alive = (!FLAT && hierx) ? group_sum_x(block_sum_uniform(bs), 2u * l + 3u, gran_group, granx_group, rank, wgs, bcast, rd.err, rhoNew, subfast)
                   : (!FLAT && hier)  ? group_sum_h(block_sum_uniform(bs), 2u * l + 3u, gran_group, gran2, rank, wgs, bcast, rd.err, rhoNew, subfast)
-                          : group_sum(bs, 2u * l + 3u, gran_group, rank, wgs, bcast, rd.err, rhoNew, fast, nullptr, rd.nowait != 0,
+                          : group_sum<ONE_TRIP>(bs, 2u * l + 3u, gran_group, rank, wgs, bcast, rd.err, rhoNew, fast, nullptr, rd.nowait != 0,
                                       STAMPS ? tm : nullptr, STAMPS ? tarr + 1 : nullptr);
         }
         // ---------------- p = z + beta p (its loads first) ----------------------------------------------
@@ -1030,15 +1094,29 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         rho = rhoNew;
         if (l + 1 == L) { alpha_last = alpha; break; }
         // (2) own cells while those loads fly: delta += alpha p, then p = z + beta p.  Branch free (an excluded lane
-        //     computes 0 + beta * 0).  The registers of Ap are free here: every slot's own p is fetched from LDS up front
-        //     (one slot ahead, each slot paid an LDS round trip).
+        //     computes 0 + beta * 0).  Up to 7 slots (PREG) p and z are in registers.  Above, the registers of Ap are free
+        //     here: every slot's own p is fetched from LDS up front (one slot ahead, each slot paid an LDS round trip).
         //     The old p of this thread's halo cells is fetched right behind the own cells (when their registers are free
         //     again): it does not depend on the loads in flight (a halo cell is never an own cell and stands in the list
         //     once, so nobody writes it before step (3)), and read in step (3), after the loads have returned, it was up to
         //     six dependent LDS round trips on the chain.
         float2 hp2[RES_HALO_PER_THREAD];
         float hpa[RES_HALO_PER_THREAD];
-        {
+        if (PREG) {
+            // own p and z are at hand: no LDS round trip between beta and the first FMA, no product formed twice
+#pragma unroll
+            for (int j = 0; j < (PREG ? NS : 0); ++j) {
+                RES_PRIO(j)
+                char* T_ = (char*)lds + j * (LTILE * 4);
+                dx_[j] = fmaf(alpha, pxy[j].x, dx_[j]);
+                dy_[j] = fmaf(alpha, pxy[j].y, dy_[j]);
+                da_[j] = fmaf(alpha, pal[j], da_[j]);
+                pxy[j] = make_float2(fmaf(beta, pxy[j].x, zx_[j]), fmaf(beta, pxy[j].y, zy_[j]));
+                pal[j] = fmaf(beta, pal[j], za_[j]);
+                *(float2*)(T_ + offP[0]) = pxy[j];                     // for the neighbours
+                *(float*)(T_ + offA[0] + LPLANE * 16) = pal[j];
+            }
+        } else {
             float2 Up[NS];
             float Ua[NS];
 #pragma unroll
@@ -1155,8 +1233,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const char* T_ = (const char*)lds + j * (LTILE * 4);
-            const float2 p2 = *(const float2*)(T_ + offP[0]);
-            const float pa1 = *(const float*)(T_ + offA[0] + LPLANE * 16);
+            const float2 p2 = PREG ? pxy[PREG ? j : 0] : *(const float2*)(T_ + offP[0]);
+            const float pa1 = PREG ? pal[PREG ? j : 0] : *(const float*)(T_ + offA[0] + LPLANE * 16);
             dx_[j] = fmaf(alpha_last, p2.x, dx_[j]);
             dy_[j] = fmaf(alpha_last, p2.y, dy_[j]);
             da_[j] = fmaf(alpha_last, pa1, da_[j]);

@@ -408,6 +408,8 @@ static int resident_deal(const int* ntiles, int nb, int forced, std::vector<ResW
 
 // The group-sum flavour of one launch, from its table: the flat-only kernel exactly when every group dealt to it has
 // <= 64 workgroups (the kernel would take group_sum for all of them anyway), else the kernel that carries all three.
+// This is an invariant the flat kernel relies on, not only a choice of speed: its sweep is one trip, lane k reads rank
+// k's granules, and it never looks at a rank beyond 63 (arap_resident.h: group_sum<true>; checked in plan_resident_pack).
 static int resident_launch_sums(const ResWg* map, bool force_any)
 {
     if (force_any) return RES_SUMS_ANY;
@@ -433,6 +435,12 @@ static bool plan_resident_pack(Opt_Plan* p)
     std::vector<int> sums(nsets, RES_SUMS_ANY);
     for (int set = 0; set < nsets; ++set)
         sums[set] = resident_launch_sums(map.data() + (size_t)set * RES_WGS, p->knob_res_sums_any);
+    for (size_t i = 0; i < map.size(); ++i)
+        if (map[i].slot >= 0 && sums[i / RES_WGS] == RES_SUMS_FLAT && map[i].wgs > 64) {
+            fprintf(stderr, "arapopt: a group of %d workgroups was dealt to a launch of the flat group-sum flavour, "
+                            "whose one-trip sweep covers 64\n", map[i].wgs);
+            exit(3);
+        }
     const bool same = nsets == p->res_sets && ns == p->res_ns && sums == p->res_sums && map.size() == p->h_wgmap.size() &&
                       memcmp(map.data(), p->h_wgmap.data(), map.size() * sizeof(ResWg)) == 0;
     if (same) return false;

@@ -178,6 +178,8 @@ static void enqueue_gn_step(Opt_Plan* p, hipStream_t s, const StepRecipe& r, int
         for (size_t set = 0; set < r.res_ns.size(); ++set) {
             rd.wgmap = p->d_wgmap + set * RES_WGS;
             rd.gran = p->rd.gran + gran_per_launch * set;
+            // (the flat flavour only ever gets launches whose groups all have <= 64 workgroups: its sweep of a group's
+            //  granules covers exactly that many -- plan_resident_pack refuses any other pairing)
             const ResidentKernel kern = (ResidentKernel)resident_kernel(r.stamped, r.res_ns[set], r.res_sums[set]);
             if (r.stamped)
                 hipLaunchKernelGGL(kern, dim3(RES_WGS), dim3(RES_THREADS), RES_LDS_BYTES, s, p->pd, rd, L);

@@ -6,6 +6,11 @@
     python tools/loop_diff.py diff A.s B.s [NS] [SA] [SB]  the two loops side by side with register NAMES normalised (SA / SB:
                                                          flavour taken from A / B; a file of a build from before the
                                                          flavours has one kernel per NS, which is taken whatever SA says)
+    python tools/loop_diff.py pairs A.s [NS] [SUMS]      duplicated weight pairs of that loop: loop-invariant first operands of
+                                                         v_pk_fma_f32 whose high half is a copy of the low half made in
+                                                         front of the loop (one VGPR each that an op_sel_hi broadcast
+                                                         would not need), with the kernel's VGPR count and scratch size;
+                                                         without NS: the table of 7, 8, 9 slots x flat, any
     python tools/loop_diff.py same A.s B.s         every function and kernel descriptor of A against B's of the same name,
                                                    whatever their order in the files; exit status 1 on any difference
 
@@ -72,6 +77,47 @@ def stats(body):
     return {"instructions": len(ins), "valu": fam("v_"), "salu": fam("s_"), "lds": fam("ds_"), "global": fam("global_"),
             "scratch": fam("scratch_"), "s_load": fam("s_load"), "v_readlane (SGPR reloads)": c.get("v_readlane_b32", 0),
             "v_writelane": c.get("v_writelane_b32", 0), "s_nop": c.get("s_nop", 0), "s_waitcnt": c.get("s_waitcnt", 0)}
+
+
+def written(l):
+    """registers an instruction line writes (its first operand): {n} or {lo .. hi}"""
+    m = re.match(r"\s+(v_\w+|ds_read\w*|global_load\w*|buffer_load\w*)\s+v(?:\[(\d+):(\d+)\]|(\d+))", l)
+    if not m or m.group(1).startswith(("v_cmp", "v_readlane", "v_readfirstlane")):
+        return set()
+    return set(range(int(m.group(2)), int(m.group(3)) + 1)) if m.group(2) else {int(m.group(4))}
+
+
+def pairs(fn):
+    """duplicated weight pairs of the main loop: v[n:n+1] is the first operand of a v_pk_fma_f32 in the loop, neither half
+    is written in the loop, and the last write of v(n+1) in front of the loop is `v_mov_b32 v(n+1), vn`"""
+    loop = main_loop(fn)
+    hdr = next(i for i in range(len(fn)) if fn[i] is loop[0])
+    live = set()
+    for l in loop:
+        live |= written(l)
+    src0 = set()
+    for l in loop:
+        m = re.match(r"\s+v_pk_fma_f32\s+v\[\d+:\d+\],\s*v\[(\d+):(\d+)\]", l)
+        if m and int(m.group(1)) not in live and int(m.group(2)) not in live:
+            src0.add(int(m.group(1)))
+    last = {}
+    for l in fn[:hdr]:
+        for r in written(l):
+            last[r] = l
+    n = 0
+    for lo in sorted(src0):
+        m = re.match(r"\s+v_mov_b32(?:_e32)?\s+v(\d+),\s*v(\d+)\s*$", re.sub(r";.*", "", last.get(lo + 1, "")).rstrip())
+        n += bool(m and int(m.group(1)) == lo + 1 and int(m.group(2)) == lo)
+    return n
+
+
+def resources(path, ns, sums):
+    """(VGPRs, scratch bytes) of the kernel, from the comment block behind its code"""
+    lines = open(path).read().split("\n")
+    fn = kernel_lines(path, ns, sums)
+    i = next(k for k in range(len(lines)) if lines[k] == fn[0])
+    tail = "\n".join(lines[i + len(fn):i + len(fn) + 400])
+    return int(re.search(r"; NumVgprs: (\d+)", tail).group(1)), int(re.search(r"; ScratchSize: (\d+)", tail).group(1))
 
 
 def functions(path):
@@ -141,6 +187,13 @@ def main():
             print(l)
             n += 1
         print("(%d diff lines)" % n)
+    elif len(a) >= 2 and a[0] == "pairs":
+        for ns, sums in ([(int(a[2]), a[3] if len(a) > 3 else "flat")] if len(a) > 2 else
+                         [(n, f) for n in (7, 8, 9) for f in ("flat", "any")]):
+            st = stats(main_loop(kernel_lines(a[1], ns, sums)))
+            print("%d slots, %-4s: %3d VGPRs, scratch %d, %2d duplicated weight pairs; loop: %d instructions, %d VALU, %d LDS, %d v_readlane" % (
+                (ns, sums) + resources(a[1], ns, sums) + (pairs(kernel_lines(a[1], ns, sums)), st["instructions"], st["valu"],
+                                                          st["lds"], st["v_readlane (SGPR reloads)"])))
     elif len(a) >= 3 and a[0] == "same":
         return same(a[1], a[2])
     else:
