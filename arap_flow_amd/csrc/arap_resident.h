@@ -11,7 +11,7 @@
 //   * the search direction p and cos/sin(A) live in LDS as 34x10 halo'd tiles (the stencil reads
 //     every neighbour from LDS, one tile slot ahead of the arithmetic; cells that are not active
 //     vertices are zero and invalid edges get a zero weight, so the phases are branch free); up to
-//     7 slots a lane's OWN p stays in registers as well and the LDS copy serves its neighbours only,
+//     7 slots a lane's OWN p and (cos, sin) stay in registers as well and the LDS copy serves its neighbours only,
 //   * per iteration the group exchanges only (a) two 16-byte partial sums per workgroup (all-gather
 //     of data-tagged granules, summed by every workgroup in the same fixed order -> deterministic) and
 //     (b) the preconditioned residual z of tile-border vertices, from which each workgroup rebuilds
@@ -92,6 +92,19 @@ static_assert(2 * ((RES_LDS_BYTES + 1279) / 1280 * 1280) <= 160 * 1024, "two wor
 #endif
 #ifndef RES_PREG_SLOTS_FLAT
 #define RES_PREG_SLOTS_FLAT 7 // ... in the flat-sums flavour
+#endif
+#ifndef RES_CSREG_SLOTS
+#define RES_CSREG_SLOTS 7     // the own (cos, sin) stays in registers (2 per slot) when at most this many slots are in use
+#endif
+#ifndef RES_CSREG_SLOTS_FLAT
+#define RES_CSREG_SLOTS_FLAT 7 // ... in the flat-sums flavour
+#endif
+#ifndef RES_HPREG_SLOTS
+#define RES_HPREG_SLOTS 6     // the p of a thread's halo cells stays in registers (9) when at most this many slots are in use
+                              // (7 slots with all three group sums inlined: 36 bytes of scratch)
+#endif
+#ifndef RES_HPREG_SLOTS_FLAT
+#define RES_HPREG_SLOTS_FLAT 7 // ... in the flat-sums flavour
 #endif
 #ifndef RES_SWEEP1
 #define RES_SWEEP1 1          // the flat flavour's sweep of the group's granules is one straight-line trip
@@ -218,6 +231,23 @@ __device__ __forceinline__ float keep_if(unsigned f, float v)
     int m;      // (as asm: the compiler would turn sext(bit) & v back into v_and + v_cmp + v_cndmask)
     asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(f), "n"(BITNO));
     return __uint_as_float(__float_as_uint(v) & (unsigned)m);
+}
+
+// keep_if for a loop-invariant f inside a loop: the volatile asm stays where it stands (hoisted, the mask would take a VGPR
+// per use for the whole loop) and reads f's own register -- no copy of f, as an empty asm on f in front of keep_if costs
+template <int BITNO>
+__device__ __forceinline__ float keep_if_here(unsigned f, float v)
+{
+    int m;
+    asm volatile("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(f), "n"(BITNO));
+    return __uint_as_float(__float_as_uint(v) & (unsigned)m);
+}
+
+// p = fma(b, p, z) written into p's OWN register (three-address v_fma_f32, the same single rounding).  Left to the compiler
+// a loop-carried p becomes v_fmac_f32 into z's register (z dies there) and a v_mov_b32 back into p's at the loop's latch.
+__device__ __forceinline__ void fma_into(float& p, float b, float z)
+{
+    asm("v_fma_f32 %0, %1, %0, %2" : "+v"(p) : "v"(b), "v"(z));
 }
 
 // block_sum8 (below) leaves a workgroup's sum in lanes 2 and 3 of wave 0; the same value in every lane:
@@ -520,9 +550,10 @@ __device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 do
 // starts life as the u16 cell list); tile origins int2[9]; the 10-entry M^-1_O table; broadcast + reduction scratch;
 // the staging area of the border z (9 x 80 float4, 11 520 B).
 // Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), the four edge weights and the fit
-// weight (5 x NS, one VGPR each: RES_WPIN) and, up to 7 slots, the own search direction p (3 x NS; z = M^-1 r of phase B
-// stays in Ap's registers until the update): 230 / 233 / 241 VGPRs at 7 / 8 / 9 slots in the flat-sums flavour (SUMS
-// below), 245 / 247 / 255 in the other, no scratch.
+// weight (5 x NS, one VGPR each: RES_WPIN) and, up to 7 slots, the own search direction p (3 x NS, updated in place; z =
+// M^-1 r of phase B stays in Ap's registers until the update), the own (cos, sin) (2 x NS, RES_CSREG_SLOTS) and the p of
+// the thread's three halo cells (9, RES_HPREG_SLOTS: 7 slots flat, 6 in the other flavour): 246 / 233 / 241 VGPRs at
+// 7 / 8 / 9 slots in the flat-sums flavour (SUMS below), 255 / 247 / 255 in the other, no scratch.
 // NS = tile slots the loops run over (1 .. RES_SLOTS): the most tiles any workgroup of the LAUNCH holds (the host picks
 // the instantiation per launch, host_step.h: enqueue_gn_step).  The phases are fully unrolled and branch free over the
 // slots, so their length is proportional to NS: a launch whose solves need 7 tiles per workgroup runs the 7-slot kernel.
@@ -539,6 +570,9 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     constexpr bool ONE_TRIP = FLAT && RES_SWEEP1 != 0;         // every group of a flat launch has <= 64 workgroups
     // own search direction in registers across iterations, z kept from phase B to the update phase (in Ap's registers)
     constexpr bool PREG = NS <= (FLAT ? RES_PREG_SLOTS_FLAT : RES_PREG_SLOTS);
+    // own (cos, sin) in registers: phase A reads 12 values per slot from LDS, the LDS copy serves the neighbours only
+    // (the instrumented build carries its stamps in VGPRs: one slot less, here and for the halo's p below, or it spills)
+    constexpr bool CSREG = NS <= (FLAT ? RES_CSREG_SLOTS_FLAT : RES_CSREG_SLOTS) - (STAMPS ? 1 : 0);
     constexpr int WFIT = SPEND ? RES_WREG_FIT_FLAT : RES_WREG_FIT;    // the fit weight lives in registers up to this many slots
     unsigned long long tA = 0, tS1 = 0, tB = 0, tS2 = 0, tU = 0, t0 = 0, t1 = 0;
     unsigned long long tm[6] = {0, 0, 0, 0, 0, 0}, tbs = 0, tzr = 0;     // STAMPS: inside the group sums (shader clocks; wave 0)
@@ -607,6 +641,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     float ma_[NS], mo_[NS];
     float2 pxy[PREG ? NS : 1];                         // own p (PREG): formed where p0 is, updated where the LDS copy is
     float pal[PREG ? NS : 1];
+    v2f_t csr[CSREG ? NS : 1];                         // own (cos, sin) (CSREG): what the own cell of the LDS plane holds, an aligned pair
     float zx_[PREG ? NS : 1], zy_[PREG ? NS : 1], za_[PREG ? NS : 1];     // z = M^-1 r from phase B to the update (Ap is dead there)
     unsigned fl[NS];
     int ibase[NS];                                     // SGPRs
@@ -698,6 +733,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             pxy[j] = act ? p0 : make_float2(0.f, 0.f);
             pal[j] = act ? pa0 : 0.f;
         }
+        if (CSREG) csr[j] = act ? (v2f_t){qC[j].x, qC[j].y} : (v2f_t){0.f, 0.f};
         if (vF[j] & F_ACT) {
             const int hc = vrow * LROW + (lx + 1);
             const float mo = moLUT[__popc(vF[j] & 15u) + 5 * (int)((vF[j] >> 4) & 1u)];
@@ -873,11 +909,28 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 #endif
 #define RES_PRIO(J) { if ((J) + RES_PRIO_TAIL >= NS) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(RES_PRIO_HI); }
 #define RES_PRIO_END() __builtin_amdgcn_s_setprio(0);
+    // The p of this thread's halo cells (HPREG: loop-carried in registers).  Other lanes wrote the halo p0 (the prologue's
+    // lane mapping is not the halo table's), so it is read from LDS once, here, behind the prologue's barriers; from then
+    // on each is the value this thread stored the iteration before, and the update phase reads nothing from LDS.
+    constexpr bool HPREG = HREG && NS <= (FLAT ? RES_HPREG_SLOTS_FLAT : RES_HPREG_SLOTS) - (STAMPS ? 1 : 0);
+    float2 hp2[RES_HALO_PER_THREAD];
+    float hpa[RES_HALO_PER_THREAD];
+    if (HPREG) {
+#pragma unroll
+        for (int u = 0; u < RES_HALO_PER_THREAD; ++u) {
+            hp2[u] = make_float2(0.f, 0.f); hpa[u] = 0.f;
+            if (tid + u * RES_THREADS < nh) {
+                hp2[u] = *(const float2*)((const char*)lds + (hreg[u].y & 0xffffu) * 8u);
+                hpa[u] = *(const float*)((const char*)lds + (hreg[u].y >> 16) * 4u);
+            }
+        }
+    }
     if (STAMPS) t0 = __builtin_amdgcn_s_memrealtime();
     for (int l = 0; l < L && alive; ++l) {
         // ---------------- phase A: Ap = J^T J p, sigma = p.Ap --------------------------------------
         // Software pipelined over the tile slots: the 15 LDS reads of slot j+1 (own cell + 4 neighbours x
-        // {(px,py), (cos,sin), pa}; 13 with the own p in registers, PREG) are issued before the arithmetic of slot j,
+        // {(px,py), (cos,sin), pa}; 13 with the own p in registers, PREG, 12 with the own cos/sin too, CSREG) are issued
+        // before the arithmetic of slot j,
         // so that with only two wavefronts per SIMD the LDS round trip hides behind ~70 VALU instructions instead of
         // stalling every slot.
         static_assert(F_E0 == 1u && F_E1 == 2u && F_E2 == 4u && F_E3 == 8u && F_FIT == 16u && F_ACT == 32u, "bit numbers below");
@@ -893,6 +946,12 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 for (int e_ = 0; e_ < 5; ++e_)
                     if (e_ < NWR || (e_ == 4 && NS <= WFIT)) asm volatile("" : "+v"(we[WREG ? j : 0][e_]));
         }
+        // The own (cos, sin) likewise: loop invariant, the swapped pair (sin, cos) that two of the four edges take is built
+        // in front of the loop and kept, two more VGPRs per slot that the loop does not have (scratch at 7 slots).
+        if (CSREG) {
+#pragma unroll
+            for (int j = 0; j < (CSREG ? NS : 0); ++j) asm volatile("" : "+v"(csr[j]));
+        }
         double acc = 0.0;
         float2 Lpv[2], Lcs[2], LqO[2][4], Lcn[2][4];
         float Lpa[2], LqA[2][4];
@@ -907,7 +966,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             const int s_ = (J) & 1;                                                                    \
             const char* T_ = (const char*)lds + (J) * (LTILE * 4);                                     \
             if (!PREG) Lpv[s_] = *(const float2*)(T_ + offP[0]);                                       \
-            Lcs[s_] = *(const float2*)(T_ + offP[0] + LPLANE * 8);                                     \
+            if (!CSREG) Lcs[s_] = *(const float2*)(T_ + offP[0] + LPLANE * 8);                         \
             if (!PREG) Lpa[s_] = *(const float*)(T_ + offA[0] + LPLANE * 16);                          \
             _Pragma("unroll") for (int n_ = 0; n_ < 2; ++n_) {                                         \
                 LqO[s_][n_] = *(const float2*)(T_ + offP[n_ + 1]);                                     \
@@ -933,7 +992,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             unsigned f = fl[j];
             // keep the flag tests inside the loop: hoisted, their 54 lane masks spill out of the SGPR file and
             // come back as two v_readlane per test, more than the two bit operations that make a weight here
-            asm volatile("" : "+v"(f));
+            // (with all five weights kept in registers nothing below reads f: no pin, it would be a v_mov_b32 per slot)
+            if (NWR < 4 || !(WREG && NS <= WFIT)) asm volatile("" : "+v"(f));
             const int sj = j & 1;
             if (j + 1 < NS) RES_LOAD_A(j + 1)
             __builtin_amdgcn_sched_barrier(0);
@@ -942,7 +1002,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 // never-written cells were zero-filled in the prologue, so every operand is finite) and an edge
                 // whose flag bit is clear gets the weight +0: fma(0, u, a) = a exactly.
                 const float2 pv = PREG ? pxy[PREG ? j : 0] : Lpv[sj];
-                const float2 csv = Lcs[sj];                      // (ci, si)
+                const float2 csv = CSREG ? make_float2(csr[CSREG ? j : 0].x, csr[CSREG ? j : 0].y) : Lcs[sj];     // (ci, si)
                 const float pa_ = PREG ? pal[PREG ? j : 0] : Lpa[sj];
                 const float ci = csv.x, si = csv.y;
                 const float2 pa2 = make_float2(pa_, pa_);
@@ -1014,8 +1074,6 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             RES_PRIO(j)
-            unsigned f = fl[j];
-            asm volatile("" : "+v"(f));
             const float mo = mo_[j], ma = ma_[j];
             rx[j] = fmaf(-alpha, apx[j], rx[j]);
             ry[j] = fmaf(-alpha, apy[j], ry[j]);
@@ -1029,7 +1087,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             if (zent >= 0) {
                 zst[j * RES_ZX + zent] = make_float4(zx, zy, za, zy);
             }
-            acc += (double)keep_if<5>(f, dot3(zx, zy, za, rx[j], ry[j], ra[j]));
+            acc += (double)keep_if_here<5>(fl[j], dot3(zx, zy, za, rx[j], ry[j], ra[j]));
             __builtin_amdgcn_sched_barrier(0);
         }
         // (delta += alpha p is left to the update phase, which has the workgroup's own p at hand)
@@ -1100,8 +1158,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         //     again): it does not depend on the loads in flight (a halo cell is never an own cell and stands in the list
         //     once, so nobody writes it before step (3)), and read in step (3), after the loads have returned, it was up to
         //     six dependent LDS round trips on the chain.
-        float2 hp2[RES_HALO_PER_THREAD];
-        float hpa[RES_HALO_PER_THREAD];
+        //     (HPREG: that old p is what this thread stored there the iteration before, kept in registers: no LDS read.)
         if (PREG) {
             // own p and z are at hand: no LDS round trip between beta and the first FMA, no product formed twice
 #pragma unroll
@@ -1111,8 +1168,13 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 dx_[j] = fmaf(alpha, pxy[j].x, dx_[j]);
                 dy_[j] = fmaf(alpha, pxy[j].y, dy_[j]);
                 da_[j] = fmaf(alpha, pal[j], da_[j]);
-                pxy[j] = make_float2(fmaf(beta, pxy[j].x, zx_[j]), fmaf(beta, pxy[j].y, zy_[j]));
-                pal[j] = fmaf(beta, pal[j], za_[j]);
+                // p is updated IN PLACE (fma_into), the slot's delta FMAs held in front of its p update by the empty asm that
+                // both pass through: old and new p are never live together, and no copy of the new p stands behind the
+                // closing barrier (it was 3 NS + 1 v_mov_b32 on the chain of every iteration)
+                asm volatile("" : "+v"(dx_[j]), "+v"(dy_[j]), "+v"(da_[j]), "+v"(pxy[j].x), "+v"(pxy[j].y), "+v"(pal[j]));
+                fma_into(pxy[j].x, beta, zx_[j]);
+                fma_into(pxy[j].y, beta, zy_[j]);
+                fma_into(pal[j], beta, za_[j]);
                 *(float2*)(T_ + offP[0]) = pxy[j];                     // for the neighbours
                 *(float*)(T_ + offA[0] + LPLANE * 16) = pal[j];
             }
@@ -1140,7 +1202,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        {
+        if (!HPREG) {
 #pragma unroll
             for (int u = 0; u < RES_HALO_PER_THREAD; ++u) {
                 hp2[u] = make_float2(0.f, 0.f); hpa[u] = 0.f;
@@ -1157,7 +1219,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         // does not hold them: they cross blocks)
 #pragma unroll
         for (int j = 0; j < NS; ++j)
-            if (HREG) asm volatile("" : "+v"(dx_[j]), "+v"(dy_[j]), "+v"(da_[j]));     // (at nine slots the pin reorders phase B)
+            if (HREG && !PREG) asm volatile("" : "+v"(dx_[j]), "+v"(dy_[j]), "+v"(da_[j]));     // (at nine slots the pin reorders phase B; PREG pins per slot, above)
         __builtin_amdgcn_sched_barrier(0);
         // (3) halo cells: p_halo = z_halo + beta p_halo (the owner computes the same expression).  A granule whose tag is
         //     this iteration's holds this iteration's value; the group sum in between took far longer than a store
@@ -1201,8 +1263,16 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             if (tid + u * RES_THREADS < nh) {
                 float2* P = (float2*)((char*)lds + (RES_HPK(u) & 0xffffu) * 8u);
                 float* A = (float*)((char*)lds + (RES_HPK(u) >> 16) * 4u);
-                *P = make_float2(fmaf(beta, hp2[u].x, hz2_.x), fmaf(beta, hp2[u].y, hz2_.y));
-                *A = fmaf(beta, hpa[u], hz1_);
+                if (HPREG) {                     // in place: the registers now hold what the cell holds
+                    fma_into(hp2[u].x, beta, hz2_.x);
+                    fma_into(hp2[u].y, beta, hz2_.y);
+                    fma_into(hpa[u], beta, hz1_);
+                    *P = hp2[u];
+                    *A = hpa[u];
+                } else {
+                    *P = make_float2(fmaf(beta, hp2[u].x, hz2_.x), fmaf(beta, hp2[u].y, hz2_.y));
+                    *A = fmaf(beta, hpa[u], hz1_);
+                }
             }
         }
         RES_PRIO_END()

@@ -11,7 +11,10 @@
                                                          front of the loop (one VGPR each that an op_sel_hi broadcast
                                                          would not need), with the kernel's VGPR count and scratch size;
                                                          without NS: the table of 7, 8, 9 slots x flat, any
-    python tools/loop_diff.py same A.s B.s         every function and kernel descriptor of A against B's of the same name,
+    python tools/loop_diff.py copies A.s [NS] [SUMS]     the plain register copies (v_mov_b32, DPP forms not counted) of that loop
+                                                         per basic block, the blocks sorted into main / tail (closing
+                                                         barrier to loop header) / exit / spin
+    python tools/loop_diff.py same A.s B.s        every function and kernel descriptor of A against B's of the same name,
                                                    whatever their order in the files; exit status 1 on any difference
 
 Why: the loop runs at 253 of 256 VGPRs and ~100 SGPRs, and any change elsewhere in the kernel can change its register
@@ -111,6 +114,45 @@ def pairs(fn):
     return n
 
 
+def blocks(loop):
+    """[(label, [instruction lines])] of a loop, split at its .LBB labels; the first block is the loop header's"""
+    out = []
+    for l in loop:
+        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        if m or not out:
+            out.append((m.group(1) if m else "<header>", []))
+        if l.startswith("\t") and not l.strip().startswith((".", ";")):
+            out[-1][1].append(re.sub(r"\s*;.*", "", l.strip()))
+    return out
+
+
+def copies(fn):
+    """plain register copies (v_mov_b32 without DPP) of the main loop per basic block: [(label, kind, instructions,
+    copies, the copy lines)].  Kinds: "spin" -- an inner loop (a repeated look at granules: not run in steady state);
+    "exit" -- a block BEHIND the update phase's closing s_barrier (the last of the loop) that is entered by a branch from
+    in front of that barrier: the landing block of `!alive` or `l + 1 == L`, which the compiler lays out next to the
+    latch and which runs once per launch; "tail" -- any other block from that barrier on, the stretch between the closing
+    barrier and the loop header that every iteration runs; "main" -- the rest (blocks under an exec mask or behind a
+    uniform branch included: whether wave 0 alone runs them is not decided here)."""
+    bl = blocks(main_loop(fn))
+    closing = max(k for k, (_, ins) in enumerate(bl) if any(i.startswith("s_barrier") for i in ins))
+    early = {i.split()[-1] for _, ins in bl[:closing] for i in ins if re.match(r"s_c?branch", i)}
+    inner = {re.match(r"^(\.LBB\d+_\d+):", l).group(1) for l in main_loop(fn)
+             if re.match(r"^\.LBB\d+_\d+:", l) and ("Depth=2" in l or "Parent Loop" in l)}
+    rows = []
+    for k, (name, ins) in enumerate(bl):
+        mv = [i for i in ins if re.match(r"v_mov_b32(_e32|_e64)?\s", i)]
+        if k == closing:                                   # only what stands behind the barrier itself is the tail's
+            at = max(n for n, i in enumerate(ins) if i.startswith("s_barrier"))
+            tail_mv = [i for i in ins[at:] if re.match(r"v_mov_b32(_e32|_e64)?\s", i)]
+            rows.append((name, "main", len(ins), len(mv) - len(tail_mv), [i for i in mv if i not in tail_mv]))
+            rows.append((name + " (behind s_barrier)", "tail", len(ins) - at - 1, len(tail_mv), tail_mv))
+            continue
+        kind = "spin" if name in inner else "main" if k < closing else "exit" if name in early else "tail"
+        rows.append((name, kind, len(ins), len(mv), mv))
+    return rows
+
+
 def resources(path, ns, sums):
     """(VGPRs, scratch bytes) of the kernel, from the comment block behind its code"""
     lines = open(path).read().split("\n")
@@ -194,6 +236,13 @@ def main():
             print("%d slots, %-4s: %3d VGPRs, scratch %d, %2d duplicated weight pairs; loop: %d instructions, %d VALU, %d LDS, %d v_readlane" % (
                 (ns, sums) + resources(a[1], ns, sums) + (pairs(kernel_lines(a[1], ns, sums)), st["instructions"], st["valu"],
                                                           st["lds"], st["v_readlane (SGPR reloads)"])))
+    elif len(a) >= 2 and a[0] == "copies":
+        rows = copies(kernel_lines(a[1], int(a[2]) if len(a) > 2 else 7, a[3] if len(a) > 3 else "flat"))
+        for name, kind, n, c, mv in rows:
+            print("%-4s %-36s %4d instructions, %2d v_mov_b32%s" % (kind, name, n, c, (": " + "; ".join(mv)) if mv else ""))
+        tot = lambda k: sum(r[3] for r in rows if r[1] == k)
+        print("v_mov_b32: %d main, %d tail (closing barrier to loop header), %d exit, %d spin" % (
+            tot("main"), tot("tail"), tot("exit"), tot("spin")))
     elif len(a) >= 3 and a[0] == "same":
         return same(a[1], a[2])
     else:
