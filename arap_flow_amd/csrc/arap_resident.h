@@ -115,6 +115,9 @@ static_assert(2 * ((RES_LDS_BYTES + 1279) / 1280 * 1280) <= 160 * 1024, "two wor
 #ifndef RES_WREG_9_FLAT
 #define RES_WREG_9_FLAT RES_WREG_9
 #endif
+#ifndef RES_Z16
+#define RES_Z16 1             // a halo entry's two z granules are fetched with one 16-byte load (0: two 8-byte loads)
+#endif
 // A workgroup's first look at the group's granules comes this long (x 64 clocks) after it has published its own: the
 // others publish at about the same time and a store needs ~300 clocks to become visible, so a look taken at once finds
 // nothing and costs a full L2 round trip before the next one (2.54 -> 2.14 sweeps per sum, 4.62 -> 4.54 us per iteration)
@@ -216,6 +219,27 @@ __device__ __forceinline__ void st_tagged(unsigned long long* p, unsigned hi /* 
     const unsigned long long g = ((unsigned long long)hi << 32) | __float_as_uint(v);
     if (fast) __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     else __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The two granules of one border-z entry (an aligned 16-byte pair: u64 index `gi`, even, of a solve's export `zx_b`), read
+// past the reader's L1 like every granule.  Each half carries its own tag and is checked on its own, so nothing depends on
+// the two halves arriving together: ONE 16-byte load is as safe as two 8-byte ones, and half the requests in the CU's memory
+// queue (3 per thread instead of 6).  It is a buffer_load_dwordx4 sc1 through `zrs`, a raw descriptor of the solve's export
+// (range checked; the same path through the L2 as global_load ... sc1): the builtin leaves the wait counts to the compiler,
+// which inline assembly of a global_load_dwordx4 would not.
+typedef unsigned v4u_t __attribute__((__vector_size__(4 * sizeof(unsigned))));
+__device__ __forceinline__ void ld_zentry(const unsigned long long* zx_b, __amdgpu_buffer_rsrc_t zrs, unsigned gi,
+                                          unsigned long long (&h)[2])
+{
+    if (RES_Z16) {
+        const v4u_t w = __builtin_amdgcn_raw_buffer_load_b128(zrs, (int)(gi * 8u), 0, 16 /* sc1 */);
+        h[0] = ((unsigned long long)w[1] << 32) | w[0];
+        h[1] = ((unsigned long long)w[3] << 32) | w[2];
+    } else {
+        // uniform base + 32-bit byte offset formed here (precomputed 64-bit addresses would spill)
+        const unsigned long long* q_ = (const unsigned long long*)((const char*)zx_b + (size_t)(gi * 8u));
+#pragma unroll
+        for (int c = 0; c < 2; ++c) h[c] = __hip_atomic_load(q_ + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 typedef float v2f_t __attribute__((ext_vector_type(2)));
 // (a.x*b.x + c.x, a.y*b.y + c.y) with one rounding each: v_pk_fma_f32
@@ -552,8 +576,8 @@ __device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 do
 // Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), the four edge weights and the fit
 // weight (5 x NS, one VGPR each: RES_WPIN) and, up to 7 slots, the own search direction p (3 x NS, updated in place; z =
 // M^-1 r of phase B stays in Ap's registers until the update), the own (cos, sin) (2 x NS, RES_CSREG_SLOTS) and the p of
-// the thread's three halo cells (9, RES_HPREG_SLOTS: 7 slots flat, 6 in the other flavour): 246 / 233 / 241 VGPRs at
-// 7 / 8 / 9 slots in the flat-sums flavour (SUMS below), 255 / 247 / 255 in the other, no scratch.
+// the thread's three halo cells (9, RES_HPREG_SLOTS: 7 slots flat, 6 in the other flavour): 244 / 233 / 241 VGPRs at
+// 7 / 8 / 9 slots in the flat-sums flavour (SUMS below), 251 / 245 / 255 in the other, no scratch.
 // NS = tile slots the loops run over (1 .. RES_SLOTS): the most tiles any workgroup of the LAUNCH holds (the host picks
 // the instantiation per launch, host_step.h: enqueue_gn_step).  The phases are fully unrolled and branch free over the
 // slots, so their length is proportional to NS: a launch whose solves need 7 tiles per workgroup runs the 7-slot kernel.
@@ -673,6 +697,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     unsigned long long* const zx_b = rd.zx + (size_t)b * RES_MAX_TILES * RES_ZG;    // this solve's published border z
     for (int c = tid; c < tp * RES_ZG; c += RES_THREADS)
         __hip_atomic_store(zx_b + (size_t)tfirst * RES_ZG + c, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // descriptor of this solve's export for the update phase's 16-byte loads (ld_zentry): raw buffer, range checked
+    const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc((void*)zx_b, 0, RES_MAX_TILES * RES_ZG * 8, 0x00020000);
     float2 qC[NS], qR[NS], vR[NS], vC[NS], hR[NS], hC[NS];
     float qRa[NS], qM[NS], vRa[NS], vM[NS], hRa[NS], hM[NS];
     unsigned qF[NS], vF[NS], hF[NS];                   // flags of the own vertex / of the halo vertices this lane fetches
@@ -1137,13 +1163,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 #pragma unroll
         for (int u = 0; u < RES_HALO_PER_THREAD; ++u) {
             hg[u][0] = hg[u][1] = (unsigned long long)ztag << 48;
-            if (tid + u * RES_THREADS < nh) {
-                // uniform base + 32-bit byte offset formed here (precomputed 64-bit addresses would spill)
-                const unsigned gi = HREG ? hreg[u].x : htab[tid + u * RES_THREADS].x;
-                const unsigned long long* q_ = (const unsigned long long*)((const char*)zx_b + (size_t)(gi * 8u));
-#pragma unroll
-                for (int c = 0; c < 2; ++c) hg[u][c] = __hip_atomic_load(q_ + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (tid + u * RES_THREADS < nh) ld_zentry(zx_b, zrs, HREG ? hreg[u].x : htab[tid + u * RES_THREADS].x, hg[u]);
         }
         if (!alive) break;
         RES_STAMP(tS2);
@@ -1238,13 +1258,9 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 #pragma unroll
                     for (int u = 0; u < RES_HALO_PER_THREAD; ++u) {
                         if (tid + u * RES_THREADS < nh) {
-                            const unsigned gi = HREG ? hreg[u].x : htab[tid + u * RES_THREADS].x;
-                            const unsigned long long* q_ = (const unsigned long long*)((const char*)zx_b + (size_t)(gi * 8u));
+                            ld_zentry(zx_b, zrs, HREG ? hreg[u].x : htab[tid + u * RES_THREADS].x, hg[u]);
 #pragma unroll
-                            for (int c = 0; c < 2; ++c) {
-                                hg[u][c] = __hip_atomic_load(q_ + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                fresh = fresh && (unsigned)(hg[u][c] >> 48) == ztag;
-                            }
+                            for (int c = 0; c < 2; ++c) fresh = fresh && (unsigned)(hg[u][c] >> 48) == ztag;
                         }
                     }
                     if (__all(fresh)) break;
