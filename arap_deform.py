@@ -8,10 +8,10 @@ A list line may carry optional output tokens after its six paths (backward flow,
 a line whose first word is `layers` is no solve but the layered warp of one frame, one whose first word is `bg` the
 moving-background pass of one pair, one whose first word is `tex` the random-texture twin of one frame, one whose first
 word is `trk` the point tracks of one sequence, one whose first word is `blur` the motion-blurred frames of one pair, one
-whose first word is `light` the relit frames of one pair, one whose first word is `seg` the segment maps of one pair: the
-forms are defined in arap_flow_amd/pipeline.py (SolveLine, parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine,
-SegLine).  A layers, bg, tex, trk, blur, light or seg line runs once every earlier line of the list is solved and written
-(its inputs may be their outputs).
+whose first word is `light` the relit frames of one pair, one whose first word is `seg` the segment maps of one pair, one
+whose first word is `score` the error table of one estimated flow: the forms are defined in arap_flow_amd/pipeline.py
+(SolveLine, parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine, SegLine, ScoreLine).  A layers, bg, tex, trk, blur,
+light, seg or score line runs once every earlier line of the list is solved and written (its inputs may be their outputs).
 
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
 same border pins, same outputs (.flo + two PNGs).  ARAP_PLAN may name the reference's arap_plan.t; it is then
@@ -65,7 +65,7 @@ def main(argv):
         if not pr:
             return 1
         state.lib.Opt_ProblemDelete(state.handle, pr)
-    # runs of solve lines go to the batched solver; a layers, bg, tex, trk, blur, light or seg line waits for the run before it
+    # runs of solve lines go to the batched solver; any other line waits for the run before it
     k = 0
     while k < len(lines):
         if not isinstance(lines[k], pipeline.SolveLine):
@@ -81,6 +81,8 @@ def main(argv):
                 pipeline.run_light(state, lines[k])
             elif isinstance(lines[k], pipeline.SegLine):
                 pipeline.run_seg(state, lines[k])
+            elif isinstance(lines[k], pipeline.ScoreLine):
+                pipeline.run_score(state, lines[k])
             else:
                 pipeline.run_layers(state, lines[k])
             print("Saved")

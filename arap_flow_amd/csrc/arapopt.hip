@@ -42,6 +42,7 @@
 #include "arap_blur.h"
 #include "arap_light.h"
 #include "arap_seg.h"
+#include "arap_score.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
 
@@ -56,4 +57,5 @@ using namespace arap;
 #include "abi_opt.h"         // Opt_* drop-in ABI and the small ArapFlow_* entry points
 #include "abi_warp.h"        // warp scratch layout, ArapFlow_Warp*
 #include "abi_seg.h"         // ArapFlow_SegMaps
+#include "abi_score.h"       // ArapFlow_FlowScore
 #include "abi_solver.h"      // ArapFlow_Solver*

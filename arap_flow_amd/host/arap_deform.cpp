@@ -49,6 +49,10 @@
 //       [idx1=P] [idx2=P] [mb1=P] [mb2=P] [dist1=P] [dist2=P]
 // (the layers of the frame's layers line; a static background without m=; 8-bit L PNGs, a distance as its integer square
 // root with 255 for "further than the radius"; at least one output).
+// A line whose first word is `score` is the error table of one estimated flow (DESIGN.md "Flow scoring"):
+//   score GT.flo EST.flo [occ=PNG] [dist=PNG] [skip=PNG] [mask=PNG] out=TXT
+// (occ: non-zero = occluded; dist: the 8-bit distance file of a seg line; skip: non-zero = left out; mask: red != 0 is not
+// object and left out too; out: the table as text, pipeline.format_score).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -417,6 +421,52 @@ static bool run_seg(Opt_State* state, const SegSpec& q)
     return true;
 }
 
+// the error table of one estimate, synchronously (pipeline.run_score): read the two flows and the planes the line names
+// (red channels), the distance file back to squared distances (pipeline.dist_from_png), skip= and mask= OR-ed into the one
+// skip plane, one ArapFlow_FlowScore on the state's stream, write the table as text
+static bool run_score(Opt_State* state, const ScoreSpec& q)
+{
+    std::vector<float> gt, est;
+    int w = 0, h = 0, ew = 0, eh = 0;
+    if (!arapio::read_flo(q.gt, gt, w, h)) return fail("Could not read %s\n", q.gt.c_str());
+    if (!arapio::read_flo(q.est, est, ew, eh)) return fail("Could not read %s\n", q.est.c_str());
+    if (ew != w || eh != h) return fail("score: %s differs in size from %s\n", q.est.c_str(), q.gt.c_str());
+    const size_t N = (size_t)w * h;
+    std::vector<uint8_t> occ, skip;
+    std::vector<uint16_t> dist;
+    const std::string* const paths[4] = {&q.occ, &q.dist, &q.skip, &q.mask};
+    for (int k = 0; k < 4; ++k) {
+        if (paths[k]->empty()) continue;
+        arapio::Image im;
+        if (!read_png(*paths[k], im)) return false;
+        if (im.w != w || im.h != h) return fail("score: %s differs in size from %s\n", paths[k]->c_str(), q.gt.c_str());
+        if (k == 0) occ.resize(N);
+        if (k == 1) dist.resize(N);
+        if (k >= 2) skip.resize(N, 0);
+        for (size_t i = 0; i < N; ++i) {
+            const unsigned v = im.rgb[3 * i];                                   // red channel
+            if (k == 0) occ[i] = (uint8_t)v;
+            else if (k == 1) dist[i] = (uint16_t)(v == 255 ? 65535u : v * v);
+            else skip[i] |= v != 0 ? 1 : 0;
+        }
+    }
+    DeviceArena dev;
+    auto input = [&](const void* src, size_t bytes) { return bytes ? dev.stage(src, bytes) : DeviceArena::kNone; };
+    const size_t d_gt = dev.stage(gt.data(), N * 8), d_est = dev.stage(est.data(), N * 8);
+    const size_t d_occ = input(occ.data(), occ.size()), d_dist = input(dist.data(), dist.size() * 2), d_skip = input(skip.data(), skip.size());
+    uint64_t table[ARAPFLOW_SCORE_ROWS * ARAPFLOW_SCORE_FIELDS];
+    const size_t d_table = dev.take(sizeof(table));
+    if (dev.alloc() != hipSuccess) return fail("score: out of device memory\n");
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_FlowScore(state, (unsigned)w, (unsigned)h, 1, dev.at(d_gt), dev.at(d_est), dev.at(d_occ), dev.at(d_dist),
+                                       dev.at(d_skip), dev.at(d_table), nullptr) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(table, dev.at(d_table), sizeof(table), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail("ArapFlow_FlowScore failed\n");
+    const std::string text = format_score(table);
+    return save_text(q.out, text.data(), text.size());
+}
+
 // the point tracks of one sequence, synchronously (pipeline.run_tracks): read the points, every layer's mask and its T
 // state flows, one ArapFlow_TrackPoints on the state's stream, write the track file: the points themselves as frame 0
 // (occ by the frame test), then the T states
@@ -670,7 +720,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex / trk / blur / light / seg line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur / light / seg / score line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -952,6 +1002,7 @@ int main(int argc, const char* argv[])
                   : kind == Item::Kind::Blur ? run_blur(state, fr->item.blur)
                   : kind == Item::Kind::Light ? run_light(state, fr->item.light)
                   : kind == Item::Kind::Seg ? run_seg(state, fr->item.seg)
+                  : kind == Item::Kind::Score ? run_score(state, fr->item.score)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

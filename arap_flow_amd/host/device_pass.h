@@ -40,6 +40,26 @@ inline std::string format_diag(const ArapFlow_MeshStats& s)
     return text;
 }
 
+// the text of a score file (pipeline.format_score): one line per row of ArapFlow_FlowScore's table, integers only
+inline std::string format_score(const uint64_t* table)
+{
+    static const char* const rows[ARAPFLOW_SCORE_ROWS - 1] = {"all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+"};
+    static const char* const fields[ARAPFLOW_SCORE_FIELDS] = {"count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max"};
+    std::string text;
+    char cell[64];
+    for (int r = 0; r < ARAPFLOW_SCORE_ROWS - 1; ++r) {
+        text += rows[r];
+        for (int f = 0; f < ARAPFLOW_SCORE_FIELDS; ++f) {
+            snprintf(cell, sizeof(cell), " %s=%llu", fields[f], (unsigned long long)table[r * ARAPFLOW_SCORE_FIELDS + f]);
+            text += cell;
+        }
+        text += "\n";
+    }
+    const uint64_t* const left = table + (ARAPFLOW_SCORE_ROWS - 1) * ARAPFLOW_SCORE_FIELDS;
+    snprintf(cell, sizeof(cell), "left_out skipped=%llu gt_nonfinite=%llu\n", (unsigned long long)left[0], (unsigned long long)left[1]);
+    return text + cell;
+}
+
 // a text file, as it is; says why not
 inline bool save_text(const std::string& path, const void* data, size_t bytes)
 {

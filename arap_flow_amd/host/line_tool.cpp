@@ -79,6 +79,10 @@ static std::string canonical(const Item& it)
         }
         c.token("m", m); c.token("idx1", q.idx1); c.token("idx2", q.idx2); c.token("mb1", q.mb1); c.token("mb2", q.mb2);
         c.token("dist1", q.dist1); c.token("dist2", q.dist2);
+    } else if (it.kind == Item::Kind::Score) {
+        const ScoreSpec& q = it.score;
+        c.word("score"); c.word(q.gt); c.word(q.est);
+        c.token("occ", q.occ); c.token("dist", q.dist); c.token("skip", q.skip); c.token("mask", q.mask); c.token("out", q.out);
     } else if (it.kind == Item::Kind::Light) {
         const LightSpec& q = it.light;
         c.word("light"); c.word(q.rgb1); c.word(q.mask1); c.word(q.rgb2); c.word(q.cover2);

@@ -24,7 +24,9 @@
 //                 [idx1=P] [idx2=P] [mb1=P] [mb2=P] [dist1=P] [dist2=P]
 //                 (pipeline.SegLine): tau a finite number >= 0, the radius 0 .. ARAPFLOW_SEG_MAX_RADIUS, the maps finite;
 //                 without m= the background is static; a repeated key is an error too
-//                 on these seven any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   score line:   score GT.flo EST.flo [occ=PNG] [dist=PNG] [skip=PNG] [mask=PNG] out=TXT
+//                 (pipeline.ScoreLine): a repeated key is an error too
+//                 on these eight any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -94,7 +96,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the eight forms
+// ---- the nine forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -176,8 +178,14 @@ struct SegSpec {                           // pipeline.SegLine
     std::string first_out;                 // the value of the first output token in line order: what --serve reports
 };
 
+struct ScoreSpec {                         // pipeline.ScoreLine
+    std::string gt, est;
+    std::string occ, dist, skip, mask;     // optional planes (empty: not given)
+    std::string out;
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
@@ -186,6 +194,7 @@ struct Item {
     BlurSpec blur;
     LightSpec light;
     SegSpec seg;
+    ScoreSpec score;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -198,6 +207,7 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::Blur   ? it.blur.first_out
            : it.kind == Item::Kind::Light  ? it.light.first_out
            : it.kind == Item::Kind::Seg    ? it.seg.first_out
+           : it.kind == Item::Kind::Score  ? it.score.out
                                            : it.bg.first_out();
 }
 
@@ -523,6 +533,19 @@ inline bool parse_seg(std::istringstream& tok, SegSpec& q)
     return q.have_s && !q.first_out.empty();
 }
 
+inline bool parse_score(std::istringstream& tok, ScoreSpec& q)
+{
+    std::string k, v;
+    if (!(tok >> q.gt >> q.est) || split_token(q.gt, k, v) || split_token(q.est, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        std::string* const dst = field_of({{"occ", &q.occ}, {"dist", &q.dist}, {"skip", &q.skip}, {"mask", &q.mask}, {"out", &q.out}}, k);
+        if (!dst || !dst->empty()) return false;
+        *dst = v;
+    }
+    return !q.out.empty();
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -531,7 +554,7 @@ inline Parsed parse_item(const std::string& line, Item& it)
     if (!(tok >> first)) return Parsed::Skip;
     it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
               : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : first == "light" ? Item::Kind::Light
-              : first == "seg" ? Item::Kind::Seg : Item::Kind::Solve;
+              : first == "seg" ? Item::Kind::Seg : first == "score" ? Item::Kind::Score : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
@@ -540,9 +563,10 @@ inline Parsed parse_item(const std::string& line, Item& it)
     else if (it.kind == Item::Kind::Blur) p = parse_blur(tok, it.blur) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Light) p = parse_light(tok, it.light) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Seg) p = parse_seg(tok, it.seg) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::Score) p = parse_score(tok, it.score) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
-        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line"};      // by Item::Kind
+        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line", "score line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

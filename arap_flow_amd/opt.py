@@ -12,6 +12,7 @@
   background_seq   the same over frame 1, a pair's in-between frames and frame 2 in one call (ArapFlow_BackgroundSeq)
   warp_diag        fold diagnostics of a flow: mesh statistics and the fold map (ArapFlow_WarpDiag)
   seg_maps         object index maps, motion boundaries and boundary distance of a pair (ArapFlow_SegMaps)
+  flow_score       the Sintel / KITTI error table of an estimated flow against a pair (ArapFlow_FlowScore)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -825,7 +826,37 @@ def seg_maps(state, masks, flows, tau=1.0, radius=140, M1=None, M2=None, which=S
                        for k in SEG_OUTPUTS], "SegMapsScratchBytes", view={"dist1": np.uint16, "dist2": np.uint16})
 
 
-BG_OUTPUTS = ("out_rgb1", "out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")
+SCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")
+SCORE_FIELDS = ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")
+
+
+def flow_score(state, gt, est, occ=None, dist=None, skip=None, err=False):
+    """the error table of an estimated flow against its ground truth (ArapFlow_FlowScore, DESIGN.md "Flow scoring").
+    gt, est f32[H,W,2] or f32[n,H,W,2]; occ u8 (non-zero: occluded), dist u16 (ArapFlow_SegMaps' squared distance), skip
+    u8 (non-zero: left out), each [H,W] / [n,H,W] or None (numpy) -> {"table": u64[n,10,8]}, rows in the order of
+    SCORE_ROWS and fields in that of SCORE_FIELDS (row 9: skipped, gt_nonfinite), and with `err` also {"err": f32[n,H,W]},
+    the end-point error of a counted pixel and -1 on every other."""
+    gt = np.ascontiguousarray(gt, np.float32)
+    est = np.ascontiguousarray(est, np.float32)
+    if gt.ndim == 3:
+        gt, est = gt[None], est[None] if est.ndim == 3 else est
+    if gt.ndim != 4 or gt.shape[3] != 2 or est.shape != gt.shape:
+        raise ValueError("flow_score: gt and est [H,W,2] or [n,H,W,2] of one shape expected")
+    n, H, W = gt.shape[:3]
+    planes = []
+    for name, a, dt in (("occ", occ, np.uint8), ("dist", dist, np.uint16), ("skip", skip, np.uint8)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dt).reshape((-1,) + np.shape(a)[-2:])
+            if a.shape != (n, H, W):
+                raise ValueError("flow_score: %s of gt's shape without its last axis expected" % name)
+            a = a.view(np.int16) if dt is np.uint16 else a       # (torch uploads no unsigned 16-bit arrays)
+        planes.append((a, np.int16 if dt is np.uint16 else dt))
+    return _warp_call(state, "FlowScore", (W, H, n), [(gt, np.float32), (est, np.float32)] + planes,
+                      [("table", (n, len(SCORE_ROWS), len(SCORE_FIELDS)), torch.int64),
+                       ("err", (n, H, W) if err else None, torch.float32)], view={"table": np.uint64})
+
+
+BG_OUTPUTS = ("out_rgb1","out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")
 
 
 def _map6(m):

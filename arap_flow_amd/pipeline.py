@@ -18,6 +18,8 @@ functions that tests/golden/host/ pins with hand-computed cases:
   BlurLine, parse_blur, blur_line, run_blur    the `blur` line: the motion-blurred frames of a pair (addition)
   LightFrame, LightLine, parse_light, light_line, random_light, run_light    the `light` line: the relit pair (addition)
   SegLine, parse_seg, seg_line, run_seg  the `seg` line: object index maps, motion boundaries, boundary distance (addition)
+  ScoreLine, parse_score, score_line, run_score    the `score` line: the error table of an estimated flow (addition)
+  format_score, parse_score_file, score_summary, add_scores, dist_from_png    a score table as text, as metrics, pooled
   TrkLine, parse_trk, trk_line, sample_track_points, run_tracks    the `trk` line: point tracks of a sequence (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
@@ -68,6 +70,11 @@ LIGHT_WORD = "light"
 SEG_WORD = "seg"
 SEG_KEYS = ("idx1", "idx2", "mb1", "mb2", "dist1", "dist2")
 SEG_MAX_RADIUS = 254         # ARAPFLOW_SEG_MAX_RADIUS of include/arap_opt.h
+SCORE_WORD = "score"
+SCORE_KEYS = ("occ", "dist", "skip", "mask")
+# the rows and the fields of a score table in its order (opt.SCORE_ROWS, opt.SCORE_FIELDS; ArapFlow_FlowScore)
+SCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")
+SCORE_FIELDS = ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")
 LIGHT_KEYS = ("rgb1", "rgb2")
 
 
@@ -892,11 +899,134 @@ def run_seg(state, spec):
         save_occ(seg_dist_png(r[k]) if k.startswith("dist") else r[k], path)
 
 
+class ScoreLine(NamedTuple):
+    """a `score` line (DESIGN.md "Flow scoring"), recognised by its first word: the error table of one estimate
+        score GT.flo EST.flo [occ=PNG] [dist=PNG] [skip=PNG] [mask=PNG] out=TXT
+    occ: an occlusion map, non-zero = occluded; dist: the 8-bit distance file of a seg line (dist_from_png); skip: non-zero
+    = left out (a fold map); mask: a frame-1 object mask in the solver's convention, red != 0 is not object and left out
+    too.  `planes`: {key: path} of those given, `out` the text file (format_score).  Anything else -- an unknown or
+    repeated key, an empty value, no out=, fewer than two paths -- is an error."""
+    gt: str
+    est: str
+    planes: dict
+    out: str
+
+
+def parse_score(tokens):
+    if len(tokens) < 3 or tokens[0] != SCORE_WORD or "=" in tokens[1] or "=" in tokens[2]:
+        raise ValueError("score line: two flow files expected: %r" % " ".join(tokens))
+    planes, out = {}, None
+    for t in tokens[3:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in SCORE_KEYS + ("out",)) or k in planes or (k == "out" and out is not None):
+            raise ValueError("score line: bad or repeated token %r" % t)
+        if k == "out":
+            out = v
+        else:
+            planes[k] = v
+    if out is None:
+        raise ValueError("score line without out=: %r" % " ".join(tokens))
+    return ScoreLine(tokens[1], tokens[2], planes, out)
+
+
+def score_line(item):
+    """the inverse of parse_score: the planes in the order of SCORE_KEYS, then out="""
+    return " ".join([SCORE_WORD, item.gt, item.est] + ["%s=%s" % (k, item.planes[k]) for k in SCORE_KEYS if item.planes.get(k)] +
+                    ["out=" + item.out])
+
+
+def format_score(table):
+    """the text of a score file: one line per row of a table uint64[10][8], `<row name> count=.. sum=.. n1=.. n3=.. n5=..
+    fl=.. nonfinite=.. max=..`, the last `left_out skipped=.. gt_nonfinite=..`; integers only; the C++ worker writes the
+    same bytes"""
+    t = np.asarray(table, np.uint64).reshape(len(SCORE_ROWS), len(SCORE_FIELDS))
+    lines = ["%s %s\n" % (name, " ".join("%s=%d" % (f, int(v)) for f, v in zip(SCORE_FIELDS, row)))
+             for name, row in zip(SCORE_ROWS[:-1], t)]
+    return "".join(lines) + "%s skipped=%d gt_nonfinite=%d\n" % (SCORE_ROWS[-1], int(t[-1, 0]), int(t[-1, 1]))
+
+
+def parse_score_file(text):
+    """the inverse of format_score -> uint64[10][8]"""
+    lines = text.split("\n")
+    if len(lines) != len(SCORE_ROWS) + 1 or lines[-1] != "":
+        raise ValueError("score file: %d lines expected" % len(SCORE_ROWS))
+    t = np.zeros((len(SCORE_ROWS), len(SCORE_FIELDS)), np.uint64)
+    for r, (name, line) in enumerate(zip(SCORE_ROWS, lines)):
+        keys = SCORE_FIELDS if r < len(SCORE_ROWS) - 1 else ("skipped", "gt_nonfinite")
+        tok = line.split(" ")
+        if tok[0] != name or len(tok) != 1 + len(keys):
+            raise ValueError("score file: bad row %r" % line)
+        for f, (key, cell) in enumerate(zip(keys, tok[1:])):
+            k, _, v = cell.partition("=")
+            if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
+                raise ValueError("score file: bad field %r" % cell)
+            t[r, f] = int(v)
+    return t
+
+
+def score_summary(table):
+    """{row name: dict(count, epe, r1, r3, r5, fl)} of a table, float64: the mean end-point error in pixels and the
+    outlier rates as fractions of the row's count (nan for an empty row); `left_out` is dict(skipped, gt_nonfinite)"""
+    t = np.asarray(table, np.uint64).reshape(len(SCORE_ROWS), len(SCORE_FIELDS))
+    res = {}
+    for name, row in zip(SCORE_ROWS[:-1], t):
+        count, total, n1, n3, n5, fl = (float(int(v)) for v in row[:6])
+        over = lambda v: v / count if count else float("nan")
+        res[name] = dict(count=int(row[0]), epe=over(total / 4096.0), r1=over(n1), r3=over(n3), r5=over(n5), fl=over(fl))
+    res[SCORE_ROWS[-1]] = dict(skipped=int(t[-1, 0]), gt_nonfinite=int(t[-1, 1]))
+    return res
+
+
+def add_scores(tables):
+    """the pooled table of several: the integer sum of every field but `max`, which is the maximum -- exactly the table
+    of all their pixels together"""
+    ts = [np.asarray(t, np.uint64).reshape(len(SCORE_ROWS), len(SCORE_FIELDS)) for t in tables]
+    out = np.zeros((len(SCORE_ROWS), len(SCORE_FIELDS)), np.uint64)
+    for t in ts:
+        peak = np.maximum(out[:-1, -1], t[:-1, -1])
+        out += t
+        out[:-1, -1] = peak
+    return out
+
+
+def dist_from_png(u8):
+    """the squared distance a seg line's 8-bit distance file stands for: d * d, 255 -> 65535.  Not seg_dist_png's inverse,
+    but floor(sqrt(d2)) < r is d2 < r * r, so every pixel is in the band of the d2 the file was made from"""
+    d = np.asarray(u8, np.uint8).astype(np.uint16)
+    return np.where(d == 255, np.uint16(65535), d * d).astype(np.uint16)
+
+
+def run_score(state, spec):
+    """one `score` line: read the two flows and the planes given, one opt.flow_score, write the table as text"""
+    from . import opt
+    gt, est = flo.flow_read(spec.gt), flo.flow_read(spec.est)
+    if gt.shape != est.shape:
+        raise ValueError("score line: %s and %s differ in size" % (spec.gt, spec.est))
+    plane = {}
+    for k, path in spec.planes.items():
+        plane[k] = load_mask_red(path)
+        if plane[k].shape != gt.shape[:2]:
+            raise ValueError("score line: %s differs in size from %s" % (path, spec.gt))
+    skip = None
+    if "skip" in plane or "mask" in plane:
+        skip = np.zeros(gt.shape[:2], np.uint8)
+        for k in ("skip", "mask"):
+            if k in plane:
+                skip |= (plane[k] != 0).astype(np.uint8)
+    dist = dist_from_png(plane["dist"]) if "dist" in plane else None
+    table = opt.flow_score(state, gt, est, occ=plane.get("occ"), dist=dist, skip=skip)["table"][0]
+    with open(spec.out, "w") as f:
+        f.write(format_score(table))
+    return table
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
     BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`, a
-    LightLine when it is `light`, a SegLine when it is `seg`"""
+    LightLine when it is `light`, a SegLine when it is `seg`, a ScoreLine when it is `score`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == SCORE_WORD:
+        return parse_score(tok)
     if tok and tok[0] == SEG_WORD:
         return parse_seg(tok)
     if tok and tok[0] == LIGHT_WORD:
@@ -932,13 +1062,16 @@ def format_line(item):
         return light_line(item)
     if isinstance(item, SegLine):
         return seg_line(item)
+    if isinstance(item, ScoreLine):
+        return score_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
-    first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file"""
-    if isinstance(item, TrkLine):
+    first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file, a score
+    line's out= file"""
+    if isinstance(item, (TrkLine, ScoreLine)):
         return item.out
     if isinstance(item, (BlurLine, LightLine, SegLine)):
         return next(iter(item.out.values()))

@@ -607,6 +607,38 @@ int ArapFlow_SegMaps(Opt_State* state, unsigned W, unsigned H, unsigned n, const
                      const float M1[6], const float M2[6], float tau, unsigned radius, void* idx1, void* idx2, void* mb1,
                      void* mb2, void* dist1, void* dist2, void* scratch);
 
+/* Flow scoring (DESIGN.md "Flow scoring"): the error table of an estimated flow against n pairs of one size, on DEVICE
+ * buffers.  gt, est float32[n][H][W][2], the ground truth and the estimate; occ uint8[n][H][W], non-zero = occluded (every
+ * occlusion map here); dist uint16[n][H][W], ArapFlow_SegMaps' squared distance with 65535 = none within the radius;
+ * skip uint8[n][H][W], non-zero = the pixel is left out (a fold map is one); each of the three may be NULL.  Per pixel,
+ * every operator one float32 operation, sqrtf correctly rounded:
+ *   du = est.x - gt.x;  dv = est.y - gt.y;  e2 = du * du + dv * dv;  e = sqrtf(e2);  g2 = gt.x * gt.x + gt.y * gt.y
+ *   ec = (e <= 4096.f) ? e : 4096.f                      (NaN and +inf land on the cap)
+ *   q  = (uint32)(ec * 4096.f + 0.5f)                    (truncation: the end-point error in units of 2^-12 px, <= 2^24)
+ * A pixel with skip != 0 is counted in row 9, field 0, and nowhere else; otherwise one with !(g2 < inf), a non-finite
+ * ground truth, in row 9, field 1, and nowhere else; every other pixel is counted: in row 0 and in at most one row of each
+ * group
+ *   row 0 all
+ *   row 1 noc      occ given and occ == 0             row 2 occ      occ given and occ != 0
+ *   row 3 d0-10    dist given and dist < 100          row 4 d10-60   dist given and 100 <= dist < 3600
+ *   row 5 d60-140  dist given and 3600 <= dist < 19600
+ *   row 6 s0-10    g2 < 100.f       row 7 s10-40   100.f <= g2 < 1600.f       row 8 s40+   g2 >= 1600.f
+ * The fields of a row, each uint64:
+ *   0 count   1 sum: the sum of q   2 n1: !(e2 <= 1.f)   3 n3: !(e2 <= 9.f)   4 n5: !(e2 <= 25.f)
+ *   5 fl: !(e2 <= 9.f) && !(e2 <= 0.0025f * g2), KITTI's Fl outlier   6 nonfinite: !(e2 < inf)   7 max: the largest q
+ * so the mean end-point error of a class is sum / 4096 / count, to 2^-13 px.  A class whose plane is NULL stays zero.
+ *   table  uint64[n][ARAPFLOW_SCORE_ROWS][ARAPFLOW_SCORE_FIELDS]; the call clears it itself.
+ *   err    float32[n][H][W] or NULL: e as computed on a counted pixel, -1.f on every other.
+ * Integer atomics only, no float reduction: two runs give identical bytes.  One launch whatever n; the flows are read 16
+ * bytes at a time where gt, est and err are 16-byte, dist 8-byte, occ and skip 4-byte aligned (a pair whose W * H is odd
+ * included), one pixel at a time otherwise.  Needs no scratch.  Asynchronous on the state's stream.  Returns 0; -1, and
+ * nothing is launched or written, on bad arguments: a null state, gt, est or table, n = 0, W * H = 0, n * W * H >= 2^31,
+ * an output overlapping an input or the other output; else a HIP error code. */
+#define ARAPFLOW_SCORE_ROWS 10
+#define ARAPFLOW_SCORE_FIELDS 8
+int ArapFlow_FlowScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* gt, const void* est,
+                       const void* occ, const void* dist, const void* skip, void* table, void* err);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised
