@@ -9,9 +9,11 @@ a line whose first word is `layers` is no solve but the layered warp of one fram
 moving-background pass of one pair, one whose first word is `tex` the random-texture twin of one frame, one whose first
 word is `trk` the point tracks of one sequence, one whose first word is `blur` the motion-blurred frames of one pair, one
 whose first word is `light` the relit frames of one pair, one whose first word is `seg` the segment maps of one pair, one
-whose first word is `score` the error table of one estimated flow: the forms are defined in arap_flow_amd/pipeline.py
-(SolveLine, parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine, SegLine, ScoreLine).  A layers, bg, tex, trk, blur,
-light, seg or score line runs once every earlier line of the list is solved and written (its inputs may be their outputs).
+whose first word is `score` the error table of one estimated flow, one whose first word is `tscore` the TAP-Vid table of
+one estimated track file, one whose first word is `chain` the track file of chained flow estimates: the forms are defined
+in arap_flow_amd/pipeline.py (SolveLine, parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine, SegLine, ScoreLine,
+TScoreLine, ChainLine).  Any line that is no solve runs once every earlier line of the list is solved and written (its
+inputs may be their outputs).
 
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
 same border pins, same outputs (.flo + two PNGs).  ARAP_PLAN may name the reference's arap_plan.t; it is then
@@ -83,6 +85,10 @@ def main(argv):
                 pipeline.run_seg(state, lines[k])
             elif isinstance(lines[k], pipeline.ScoreLine):
                 pipeline.run_score(state, lines[k])
+            elif isinstance(lines[k], pipeline.TScoreLine):
+                pipeline.run_tscore(state, lines[k])
+            elif isinstance(lines[k], pipeline.ChainLine):
+                pipeline.run_chain(state, lines[k])
             else:
                 pipeline.run_layers(state, lines[k])
             print("Saved")

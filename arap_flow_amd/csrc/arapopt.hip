@@ -43,6 +43,8 @@
 #include "arap_light.h"
 #include "arap_seg.h"
 #include "arap_score.h"
+#include "arap_tscore.h"
+#include "arap_chain.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
 
@@ -58,4 +60,5 @@ using namespace arap;
 #include "abi_warp.h"        // warp scratch layout, ArapFlow_Warp*
 #include "abi_seg.h"         // ArapFlow_SegMaps
 #include "abi_score.h"       // ArapFlow_FlowScore
+#include "abi_tscore.h"      // ArapFlow_TrackScore, ArapFlow_ChainFlows
 #include "abi_solver.h"      // ArapFlow_Solver*

@@ -53,6 +53,12 @@
 //   score GT.flo EST.flo [occ=PNG] [dist=PNG] [skip=PNG] [mask=PNG] out=TXT
 // (occ: non-zero = occluded; dist: the 8-bit distance file of a seg line; skip: non-zero = left out; mask: red != 0 is not
 // object and left out too; out: the table as text, pipeline.format_score).
+// A line whose first word is `tscore` is the TAP-Vid table of one estimated track file (DESIGN.md "Track scoring"):
+//   tscore GT.trk EST.trk [s=SX,SY] out=TXT
+// (the files agree in W, H, F, P; s: the factors the error is taken under; out: the table as text,
+// pipeline.format_track_score), and one whose first word is `chain` the track file of chained flow estimates:
+//   chain PTS.trk L FLO_1 .. FLO_L [bwd=B_1,..,B_L] out=OUT.trk
+// (the query points are frame 0 of PTS.trk; every flow has its W, H; OUT.trk has L + 1 frames).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -467,6 +473,75 @@ static bool run_score(Opt_State* state, const ScoreSpec& q)
     return save_text(q.out, text.data(), text.size());
 }
 
+// the TAP-Vid table of one estimated track file, synchronously (pipeline.run_tscore): read the two track files, one
+// ArapFlow_TrackScore on the state's stream, write the table as text
+static bool run_tscore(Opt_State* state, const TScoreSpec& q)
+{
+    arapio::Tracks gt, est;
+    if (!arapio::read_trk(q.gt, gt) || !arapio::read_trk(q.est, est)) return false;
+    if (gt.w != est.w || gt.h != est.h || gt.frames != est.frames || gt.points != est.points)
+        return fail("tscore: %s and %s differ in W, H, F or P\n", q.gt.c_str(), q.est.c_str());
+    const unsigned F = (unsigned)gt.frames, P = (unsigned)gt.points;
+    if (F < 2 || F > ARAPFLOW_TSCORE_MAX_FRAMES || P > (1u << 24))
+        return fail("tscore: %u frames of %u points: beyond the limits\n", F, P);
+    const size_t n = (size_t)F * P;
+    DeviceArena dev;
+    const size_t d_gp = dev.stage(gt.pos.data(), n * 8), d_go = dev.stage(gt.occ.data(), n);
+    const size_t d_ep = dev.stage(est.pos.data(), n * 8), d_eo = dev.stage(est.occ.data(), n);
+    std::vector<uint64_t> table((size_t)F * ARAPFLOW_TSCORE_CLASSES * ARAPFLOW_TSCORE_FIELDS);
+    const size_t d_table = dev.take(table.size() * 8);
+    if (dev.alloc() != hipSuccess) return fail("tscore: out of device memory\n");
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_TrackScore(state, F, P, dev.at(d_gp), dev.at(d_go), dev.at(d_ep), dev.at(d_eo), q.sx, q.sy,
+                                        dev.at(d_table)) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(table.data(), dev.at(d_table), table.size() * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail("ArapFlow_TrackScore failed\n");
+    const std::string text = format_track_score(table.data(), F);
+    return save_text(q.out, text.data(), text.size());
+}
+
+// the track file of chained flow estimates, synchronously (pipeline.run_chain): read the points and the flows, one
+// ArapFlow_ChainFlows on the state's stream, write the track file
+static bool run_chain(Opt_State* state, const ChainSpec& q)
+{
+    arapio::Tracks pts;
+    if (!arapio::read_trk(q.points, pts)) return false;
+    const int w = pts.w, h = pts.h;
+    const unsigned L = (unsigned)q.flows.size(), P = (unsigned)pts.points;
+    const size_t N = (size_t)w * h;
+    if (P > (1u << 24) || N >= ((size_t)1 << 31)) return fail("chain: %u points on %d x %d: beyond the limits\n", P, w, h);
+    std::vector<float> flows((size_t)L * N * 2), bwd(q.bwd.size() * N * 2);
+    for (int b = 0; b < 2; ++b) {
+        const std::vector<std::string>& paths = b ? q.bwd : q.flows;
+        for (size_t j = 0; j < paths.size(); ++j) {
+            std::vector<float> fl;
+            int fw = 0, fh = 0;
+            if (!arapio::read_flo(paths[j], fl, fw, fh)) return fail("Could not read %s\n", paths[j].c_str());
+            if (fw != w || fh != h) return fail("chain: %s differs in size from %s\n", paths[j].c_str(), q.points.c_str());
+            memcpy((b ? bwd : flows).data() + j * N * 2, fl.data(), N * 8);
+        }
+    }
+    DeviceArena dev;
+    const size_t d_flow = dev.stage(flows.data(), flows.size() * 4);
+    const size_t d_bwd = bwd.empty() ? DeviceArena::kNone : dev.stage(bwd.data(), bwd.size() * 4);
+    const size_t d_pts = dev.stage(pts.pos.data(), (size_t)P * 8);              // frame 0
+    const size_t d_pos = dev.take((size_t)(L + 1) * P * 8), d_occ = dev.take((size_t)(L + 1) * P);
+    if (dev.alloc() != hipSuccess) return fail("chain: out of device memory\n");
+    arapio::Tracks out;
+    out.w = w; out.h = h; out.frames = (int32_t)L + 1; out.points = (int32_t)P;
+    out.pos.resize((size_t)(L + 1) * P * 2);
+    out.occ.resize((size_t)(L + 1) * P);
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_ChainFlows(state, (unsigned)w, (unsigned)h, L, dev.at(d_flow), dev.at(d_bwd), P, dev.at(d_pts),
+                                        dev.at(d_pos), dev.at(d_occ)) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(out.pos.data(), dev.at(d_pos), out.pos.size() * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(out.occ.data(), dev.at(d_occ), out.occ.size(), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail("ArapFlow_ChainFlows failed\n");
+    return arapio::write_trk(q.out, out);
+}
+
 // the point tracks of one sequence, synchronously (pipeline.run_tracks): read the points, every layer's mask and its T
 // state flows, one ArapFlow_TrackPoints on the state's stream, write the track file: the points themselves as frame 0
 // (occ by the frame test), then the T states
@@ -720,7 +795,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex / trk / blur / light / seg / score line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur / light / seg / score / tscore / chain line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -1003,6 +1078,8 @@ int main(int argc, const char* argv[])
                   : kind == Item::Kind::Light ? run_light(state, fr->item.light)
                   : kind == Item::Kind::Seg ? run_seg(state, fr->item.seg)
                   : kind == Item::Kind::Score ? run_score(state, fr->item.score)
+                  : kind == Item::Kind::TScore ? run_tscore(state, fr->item.tscore)
+                  : kind == Item::Kind::Chain ? run_chain(state, fr->item.chain)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

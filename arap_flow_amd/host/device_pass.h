@@ -60,6 +60,29 @@ inline std::string format_score(const uint64_t* table)
     return text + cell;
 }
 
+// the text of a track score file (pipeline.format_track_score): one line per frame and class of ArapFlow_TrackScore's
+// table, integers only
+inline std::string format_track_score(const uint64_t* table, unsigned frames)
+{
+    static const char* const classes[ARAPFLOW_TSCORE_CLASSES] = {"all", "tracked", "reappeared"};
+    static const char* const fields[ARAPFLOW_TSCORE_FIELDS] = {"count", "gt_vis", "est_vis", "agree", "within_1", "within_2", "within_4",
+                                                               "within_8", "within_16", "tp_1", "tp_2", "tp_4", "tp_8", "tp_16", "sum", "max"};
+    std::string text;
+    char cell[64];
+    for (unsigned f = 0; f < frames; ++f)
+        for (int c = 0; c < ARAPFLOW_TSCORE_CLASSES; ++c) {
+            snprintf(cell, sizeof(cell), "%u %s", f, classes[c]);
+            text += cell;
+            for (int k = 0; k < ARAPFLOW_TSCORE_FIELDS; ++k) {
+                snprintf(cell, sizeof(cell), " %s=%llu", fields[k],
+                         (unsigned long long)table[((size_t)f * ARAPFLOW_TSCORE_CLASSES + c) * ARAPFLOW_TSCORE_FIELDS + k]);
+                text += cell;
+            }
+            text += "\n";
+        }
+    return text;
+}
+
 // a text file, as it is; says why not
 inline bool save_text(const std::string& path, const void* data, size_t bytes)
 {

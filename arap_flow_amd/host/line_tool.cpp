@@ -83,6 +83,20 @@ static std::string canonical(const Item& it)
         const ScoreSpec& q = it.score;
         c.word("score"); c.word(q.gt); c.word(q.est);
         c.token("occ", q.occ); c.token("dist", q.dist); c.token("skip", q.skip); c.token("mask", q.mask); c.token("out", q.out);
+    } else if (it.kind == Item::Kind::TScore) {
+        const TScoreSpec& q = it.tscore;
+        c.word("tscore"); c.word(q.gt); c.word(q.est);
+        char num[64];
+        snprintf(num, sizeof(num), "%.9g,%.9g", q.sx, q.sy);
+        if (q.sx != 1.f || q.sy != 1.f) c.token("s", num);
+        c.token("out", q.out);
+    } else if (it.kind == Item::Kind::Chain) {
+        const ChainSpec& q = it.chain;
+        c.word("chain"); c.word(q.points); c.word(std::to_string(q.flows.size()));
+        for (const std::string& f : q.flows) c.word(f);
+        std::string b;
+        for (size_t j = 0; j < q.bwd.size(); ++j) b += (j ? "," : "") + q.bwd[j];
+        c.token("bwd", b); c.token("out", q.out);
     } else if (it.kind == Item::Kind::Light) {
         const LightSpec& q = it.light;
         c.word("light"); c.word(q.rgb1); c.word(q.mask1); c.word(q.rgb2); c.word(q.cover2);

@@ -26,7 +26,11 @@
 //                 without m= the background is static; a repeated key is an error too
 //   score line:   score GT.flo EST.flo [occ=PNG] [dist=PNG] [skip=PNG] [mask=PNG] out=TXT
 //                 (pipeline.ScoreLine): a repeated key is an error too
-//                 on these eight any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   tscore line:  tscore GT.trk EST.trk [s=SX,SY] out=TXT
+//                 (pipeline.TScoreLine): the factors finite and > 0; a repeated key is an error too
+//   chain line:   chain PTS.trk L FLO_1 .. FLO_L [bwd=B_1,..,B_L] out=OUT.trk
+//                 (pipeline.ChainLine): 1 <= L < ARAPFLOW_TSCORE_MAX_FRAMES, bwd= names L files; a repeated key is an error too
+//                 on these ten any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -96,7 +100,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the nine forms
+// ---- the eleven forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -184,8 +188,21 @@ struct ScoreSpec {                         // pipeline.ScoreLine
     std::string out;
 };
 
+struct TScoreSpec {                        // pipeline.TScoreLine
+    std::string gt, est;
+    float sx = 1.f, sy = 1.f;
+    bool have_s = false;
+    std::string out;
+};
+
+struct ChainSpec {                         // pipeline.ChainLine
+    std::string points;
+    std::vector<std::string> flows, bwd;   // L files; bwd L or none
+    std::string out;
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score, TScore, Chain } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
@@ -195,6 +212,8 @@ struct Item {
     LightSpec light;
     SegSpec seg;
     ScoreSpec score;
+    TScoreSpec tscore;
+    ChainSpec chain;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -208,6 +227,8 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::Light  ? it.light.first_out
            : it.kind == Item::Kind::Seg    ? it.seg.first_out
            : it.kind == Item::Kind::Score  ? it.score.out
+           : it.kind == Item::Kind::TScore ? it.tscore.out
+           : it.kind == Item::Kind::Chain  ? it.chain.out
                                            : it.bg.first_out();
 }
 
@@ -546,6 +567,58 @@ inline bool parse_score(std::istringstream& tok, ScoreSpec& q)
     return !q.out.empty();
 }
 
+inline bool parse_tscore(std::istringstream& tok, TScoreSpec& q)
+{
+    std::string k, v;
+    if (!(tok >> q.gt >> q.est) || split_token(q.gt, k, v) || split_token(q.est, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "s") {                    // <sx>,<sy>
+            float s[2];
+            if (q.have_s || !parse_bg_maps(v, s, 2)) return false;
+            for (float c : s)
+                if (!std::isfinite(c) || !(c > 0.f)) return false;
+            q.sx = s[0]; q.sy = s[1];
+            q.have_s = true;
+        } else if (k == "out") {
+            if (!q.out.empty()) return false;
+            q.out = v;
+        } else return false;
+    }
+    return !q.out.empty();
+}
+
+inline bool parse_chain(std::istringstream& tok, ChainSpec& q)
+{
+    std::string count, k, v;
+    unsigned long long L = 0;
+    if (!(tok >> q.points >> count) || split_token(q.points, k, v) || !parse_uint(count, ARAPFLOW_TSCORE_MAX_FRAMES - 1, L) || L < 1)
+        return false;
+    for (unsigned long long j = 0; j < L; ++j) {
+        std::string path;
+        if (!(tok >> path) || split_token(path, k, v)) return false;
+        q.flows.push_back(path);
+    }
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        if (k == "bwd") {                  // L files, comma separated, none empty
+            if (!q.bwd.empty()) return false;
+            q.bwd.emplace_back();
+            for (char c : v) {
+                if (c == ',') q.bwd.emplace_back();
+                else q.bwd.back() += c;
+            }
+            if (q.bwd.size() != L) return false;
+            for (const std::string& b : q.bwd)
+                if (b.empty()) return false;
+        } else if (k == "out") {
+            if (!q.out.empty()) return false;
+            q.out = v;
+        } else return false;
+    }
+    return !q.out.empty();
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -554,7 +627,8 @@ inline Parsed parse_item(const std::string& line, Item& it)
     if (!(tok >> first)) return Parsed::Skip;
     it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
               : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : first == "light" ? Item::Kind::Light
-              : first == "seg" ? Item::Kind::Seg : first == "score" ? Item::Kind::Score : Item::Kind::Solve;
+              : first == "seg" ? Item::Kind::Seg : first == "score" ? Item::Kind::Score : first == "tscore" ? Item::Kind::TScore
+              : first == "chain" ? Item::Kind::Chain : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
@@ -564,9 +638,12 @@ inline Parsed parse_item(const std::string& line, Item& it)
     else if (it.kind == Item::Kind::Light) p = parse_light(tok, it.light) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Seg) p = parse_seg(tok, it.seg) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Score) p = parse_score(tok, it.score) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::TScore) p = parse_tscore(tok, it.tscore) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::Chain) p = parse_chain(tok, it.chain) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
-        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line", "score line"};      // by Item::Kind
+        const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line", "score line",
+                                    "tscore line", "chain line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

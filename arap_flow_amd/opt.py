@@ -13,6 +13,8 @@
   warp_diag        fold diagnostics of a flow: mesh statistics and the fold map (ArapFlow_WarpDiag)
   seg_maps         object index maps, motion boundaries and boundary distance of a pair (ArapFlow_SegMaps)
   flow_score       the Sintel / KITTI error table of an estimated flow against a pair (ArapFlow_FlowScore)
+  track_score      the TAP-Vid table of estimated tracks against a track file's (ArapFlow_TrackScore)
+  chain_flows      estimated tracks from per-link flow estimates (ArapFlow_ChainFlows)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -854,6 +856,53 @@ def flow_score(state, gt, est, occ=None, dist=None, skip=None, err=False):
     return _warp_call(state, "FlowScore", (W, H, n), [(gt, np.float32), (est, np.float32)] + planes,
                       [("table", (n, len(SCORE_ROWS), len(SCORE_FIELDS)), torch.int64),
                        ("err", (n, H, W) if err else None, torch.float32)], view={"table": np.uint64})
+
+
+TSCORE_CLASSES = ("all", "tracked", "reappeared")
+TSCORE_FIELDS = ("count", "gt_vis", "est_vis", "agree", "within_1", "within_2", "within_4", "within_8", "within_16",
+                 "tp_1", "tp_2", "tp_4", "tp_8", "tp_16", "sum", "max")
+
+
+def track_score(state, gt_pos, gt_occ, est_pos, est_occ, scale=(1, 1)):
+    """the TAP-Vid table of estimated tracks against their ground truth (ArapFlow_TrackScore, DESIGN.md "Track scoring").
+    gt_pos, est_pos f32[F,P,2]; gt_occ, est_occ u8[F,P], non-zero = hidden (a track file's planes, numpy); scale: the
+    factors (sx, sy) the error is taken under -> u64[F,3,16], classes in the order of TSCORE_CLASSES and fields in that
+    of TSCORE_FIELDS; frame 0 holds the numbers of valid and invalid points."""
+    gt_pos = np.ascontiguousarray(gt_pos, np.float32)
+    est_pos = np.ascontiguousarray(est_pos, np.float32)
+    gt_occ = np.ascontiguousarray(gt_occ, np.uint8)
+    est_occ = np.ascontiguousarray(est_occ, np.uint8)
+    if gt_pos.ndim != 3 or gt_pos.shape[2] != 2 or est_pos.shape != gt_pos.shape:
+        raise ValueError("track_score: gt_pos and est_pos [F,P,2] of one shape expected")
+    if gt_occ.shape != gt_pos.shape[:2] or est_occ.shape != gt_occ.shape:
+        raise ValueError("track_score: gt_occ and est_occ [F,P] expected")
+    F, P = gt_occ.shape
+    sx, sy = (float(np.float32(v)) for v in scale)
+    return _warp_call(state, "TrackScore", (F, P),
+                      [(gt_pos, np.float32), (gt_occ, np.uint8), (est_pos, np.float32), (est_occ, np.uint8), (sx, None), (sy, None)],
+                      [("table", (F, len(TSCORE_CLASSES), len(TSCORE_FIELDS)), torch.int64)], view={"table": np.uint64})["table"]
+
+
+def chain_flows(state, flows, points, bwd=None):
+    """estimated tracks by chaining per-link flow estimates (ArapFlow_ChainFlows, DESIGN.md "Track scoring"): flows
+    f32[L,H,W,2], link j from sequence frame j to j + 1; bwd the same shape or None, link j from frame j + 1 back to j
+    (the forward-backward check of the visibility); points f32[P,2] in frame 0 (numpy) -> (pos f32[L+1,P,2], occ
+    u8[L+1,P]), the planes of a track file."""
+    flows = np.ascontiguousarray(flows, np.float32)
+    points = np.ascontiguousarray(points, np.float32)
+    if flows.ndim != 4 or flows.shape[3] != 2:
+        raise ValueError("chain_flows: flows [L,H,W,2] expected")
+    if points.ndim != 2 or points.shape[1] != 2:
+        raise ValueError("chain_flows: points [P,2] expected")
+    if bwd is not None:
+        bwd = np.ascontiguousarray(bwd, np.float32)
+        if bwd.shape != flows.shape:
+            raise ValueError("chain_flows: bwd of flows' shape expected")
+    L, H, W = flows.shape[:3]
+    P = points.shape[0]
+    r = _warp_call(state, "ChainFlows", (W, H, L), [(flows, np.float32), (bwd, np.float32), (P, None), (points, np.float32)],
+                   [("pos", (L + 1, P, 2), torch.float32), ("occ", (L + 1, P), torch.uint8)])
+    return r["pos"], r["occ"]
 
 
 BG_OUTPUTS = ("out_rgb1","out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")

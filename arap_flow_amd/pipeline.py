@@ -21,6 +21,9 @@ functions that tests/golden/host/ pins with hand-computed cases:
   ScoreLine, parse_score, score_line, run_score    the `score` line: the error table of an estimated flow (addition)
   format_score, parse_score_file, score_summary, add_scores, dist_from_png    a score table as text, as metrics, pooled
   TrkLine, parse_trk, trk_line, sample_track_points, run_tracks    the `trk` line: point tracks of a sequence (addition)
+  TScoreLine, parse_tscore, tscore_line, run_tscore    the `tscore` line: the TAP-Vid table of an estimated track file (addition)
+  ChainLine, parse_chain, chain_line, run_chain    the `chain` line: an estimated track file from per-link flows (addition)
+  format_track_score, parse_track_score_file, track_score_summary, add_track_scores    a track score table as text, as metrics, pooled
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
@@ -75,6 +78,14 @@ SCORE_KEYS = ("occ", "dist", "skip", "mask")
 # the rows and the fields of a score table in its order (opt.SCORE_ROWS, opt.SCORE_FIELDS; ArapFlow_FlowScore)
 SCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")
 SCORE_FIELDS = ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")
+TSCORE_WORD = "tscore"
+CHAIN_WORD = "chain"
+TSCORE_MAX_FRAMES = 64       # ARAPFLOW_TSCORE_MAX_FRAMES of include/arap_opt.h
+# the classes and the fields of a track score table in its order (opt.TSCORE_CLASSES, opt.TSCORE_FIELDS; ArapFlow_TrackScore)
+TSCORE_CLASSES = ("all", "tracked", "reappeared")
+TSCORE_X = (1, 2, 4, 8, 16)
+TSCORE_FIELDS = ("count", "gt_vis", "est_vis", "agree") + tuple("within_%d" % x for x in TSCORE_X) + \
+                tuple("tp_%d" % x for x in TSCORE_X) + ("sum", "max")
 LIGHT_KEYS = ("rgb1", "rgb2")
 
 
@@ -1020,11 +1031,193 @@ def run_score(state, spec):
     return table
 
 
+class TScoreLine(NamedTuple):
+    """a `tscore` line (DESIGN.md "Track scoring"), recognised by its first word: the TAP-Vid table of one estimated track
+    file against a generated one
+        tscore GT.trk EST.trk [s=SX,SY] out=TXT
+    the two files agree in W, H, F and P; s: the factors the error is taken under, finite and > 0 (float32; (1, 1) without
+    it; written with %.9g); out: the text file (format_track_score).  Anything else -- an unknown or repeated key, an empty
+    value, no out=, fewer than two paths -- is an error."""
+    gt: str
+    est: str
+    scale: tuple
+    out: str
+
+
+def parse_tscore(tokens):
+    if len(tokens) < 3 or tokens[0] != TSCORE_WORD or "=" in tokens[1] or "=" in tokens[2]:
+        raise ValueError("tscore line: two track files expected: %r" % " ".join(tokens))
+    scale, out = None, None
+    for t in tokens[3:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in ("s", "out")) or (k == "s" and scale is not None) or (k == "out" and out is not None):
+            raise ValueError("tscore line: bad or repeated token %r" % t)
+        if k == "out":
+            out = v
+        else:
+            with np.errstate(over="ignore"):
+                scale = _bg_numbers(v)
+            if len(scale) != 2 or not all(math.isfinite(q) and q > 0 for q in scale):
+                raise ValueError("tscore line: s= takes two finite factors > 0: %r" % t)
+    if out is None:
+        raise ValueError("tscore line without out=: %r" % " ".join(tokens))
+    return TScoreLine(tokens[1], tokens[2], scale or (1.0, 1.0), out)
+
+
+def tscore_line(item):
+    """the inverse of parse_tscore: s= unless it is (1, 1), then out="""
+    sx, sy = (float(np.float32(v)) for v in item.scale)
+    return " ".join([TSCORE_WORD, item.gt, item.est] + (["s=%.9g,%.9g" % (sx, sy)] if (sx, sy) != (1.0, 1.0) else []) +
+                    ["out=" + item.out])
+
+
+def format_track_score(table):
+    """the text of a track score file: one line per frame and class of a table uint64[F][3][16], `<frame> <class name>
+    count=.. gt_vis=.. est_vis=.. agree=.. within_1=.. .. tp_16=.. sum=.. max=..`, frame 0 first (its `all` line holds the
+    number of valid points as count and of invalid ones as gt_vis); integers only; the C++ worker writes the same bytes"""
+    t = np.asarray(table, np.uint64).reshape(-1, len(TSCORE_CLASSES), len(TSCORE_FIELDS))
+    return "".join("%d %s %s\n" % (f, name, " ".join("%s=%d" % (k, int(v)) for k, v in zip(TSCORE_FIELDS, row)))
+                   for f, frame in enumerate(t) for name, row in zip(TSCORE_CLASSES, frame))
+
+
+def parse_track_score_file(text):
+    """the inverse of format_track_score -> uint64[F][3][16]"""
+    lines = text.split("\n")
+    nc = len(TSCORE_CLASSES)
+    if len(lines) < 2 * nc + 1 or (len(lines) - 1) % nc or lines[-1] != "" or (len(lines) - 1) // nc > TSCORE_MAX_FRAMES:
+        raise ValueError("track score file: %d lines per frame, 2..%d frames expected" % (nc, TSCORE_MAX_FRAMES))
+    t = np.zeros(((len(lines) - 1) // nc, nc, len(TSCORE_FIELDS)), np.uint64)
+    for r, line in enumerate(lines[:-1]):
+        tok = line.split(" ")
+        if len(tok) != 2 + len(TSCORE_FIELDS) or tok[0] != str(r // nc) or tok[1] != TSCORE_CLASSES[r % nc]:
+            raise ValueError("track score file: bad row %r" % line)
+        for f, (key, cell) in enumerate(zip(TSCORE_FIELDS, tok[2:])):
+            k, _, v = cell.partition("=")
+            if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
+                raise ValueError("track score file: bad field %r" % cell)
+            t[r // nc, r % nc, f] = int(v)
+    return t
+
+
+def add_track_scores(tables):
+    """the pooled table of several: tables of fewer frames are padded with zeros to the longest, every field is summed but
+    `max`, which is the maximum -- exactly the table of all their points together"""
+    ts = [np.asarray(t, np.uint64).reshape(-1, len(TSCORE_CLASSES), len(TSCORE_FIELDS)) for t in tables]
+    out = np.zeros((max(len(t) for t in ts), len(TSCORE_CLASSES), len(TSCORE_FIELDS)), np.uint64)
+    for t in ts:
+        peak = np.maximum(out[:len(t), :, -1], t[:, :, -1])
+        out[:len(t)] += t
+        out[:len(t), :, -1] = peak
+    return out
+
+
+def _tscore_metrics(row):
+    """dict(count, gt_vis, oa, d_1 .. d_16, d_avg, j_1 .. j_16, aj, err) of one row of fields, float64; nan where a
+    denominator is zero"""
+    v = [float(int(x)) for x in row]
+    over = lambda a, b: a / b if b else float("nan")
+    count, gt_vis, est_vis, agree = v[:4]
+    res = dict(count=int(row[0]), gt_vis=int(row[1]), oa=over(agree, count))
+    d = [over(w, gt_vis) for w in v[4:9]]
+    j = [over(tp, gt_vis + est_vis - tp) for tp in v[9:14]]
+    for x, dx, jx in zip(TSCORE_X, d, j):
+        res["d_%d" % x], res["j_%d" % x] = dx, jx
+    res["d_avg"], res["aj"] = sum(d) / len(d), sum(j) / len(j)
+    res["err"] = over(v[14] / 4096.0, gt_vis)
+    return res
+
+
+def track_score_summary(table):
+    """the TAP-Vid numbers of a table: {class name: metrics} over the frames 1 .. F-1 together (integer sums first, the
+    maximum for `max`), then "frames": [metrics of class `all` at frame f, f = 1 .. F-1] -- the drift curve -- and "valid",
+    "invalid": the numbers of query points.  metrics: dict(count, gt_vis, oa = agree / count, d_x = within_x / gt_vis,
+    d_avg, j_x = tp_x / (gt_vis + est_vis - tp_x), aj, err = sum / 4096 / gt_vis), the means over the five x; nan where a
+    denominator is zero.  Pooled counts, not TAP-Vid's mean over videos."""
+    t = np.asarray(table, np.uint64).reshape(-1, len(TSCORE_CLASSES), len(TSCORE_FIELDS))
+    res = {name: _tscore_metrics(t[1:, c].sum(axis=0)) for c, name in enumerate(TSCORE_CLASSES)}
+    res["frames"] = [_tscore_metrics(t[f, 0]) for f in range(1, len(t))]
+    res["valid"], res["invalid"] = int(t[0, 0, 0]), int(t[0, 0, 1])
+    return res
+
+
+def run_tscore(state, spec):
+    """one `tscore` line: read the two track files, one opt.track_score, write the table as text"""
+    from . import opt, trk
+    gt, est = trk.read(spec.gt), trk.read(spec.est)
+    if (gt["W"], gt["H"]) != (est["W"], est["H"]) or gt["pos"].shape != est["pos"].shape:
+        raise ValueError("tscore line: %s and %s differ in W, H, F or P" % (spec.gt, spec.est))
+    table = opt.track_score(state, gt["pos"], gt["occ"], est["pos"], est["occ"], scale=spec.scale)
+    with open(spec.out, "w") as f:
+        f.write(format_track_score(table))
+    return table
+
+
+class ChainLine(NamedTuple):
+    """a `chain` line (DESIGN.md "Track scoring"), recognised by its first word: an estimated track file from per-link
+    flow estimates
+        chain PTS.trk L FLO_1 .. FLO_L [bwd=B_1,..,B_L] out=OUT.trk
+    PTS.trk: the query points are its frame 0 (a points file, or a whole track file); FLO_j: the estimated flow from
+    sequence frame j-1 to j; bwd: the L estimated flows back, for the forward-backward check; OUT.trk has L + 1 frames
+    and PTS.trk's W, H, which every flow must have.  1 <= L < 64.  Anything else -- an unknown or repeated key, an empty
+    value, a wrong count, no out= -- is an error."""
+    points: str
+    flows: tuple
+    bwd: tuple
+    out: str
+
+
+def parse_chain(tokens):
+    if len(tokens) < 3 or tokens[0] != CHAIN_WORD or "=" in tokens[1]:
+        raise ValueError("not a chain line: %r" % " ".join(tokens))
+    L = int(tokens[2]) if _UINT.match(tokens[2]) else 0
+    if not 1 <= L < TSCORE_MAX_FRAMES or len(tokens) < 3 + L or any("=" in t for t in tokens[3:3 + L]):
+        raise ValueError("chain line: 1..%d links, a flow file each: %r" % (TSCORE_MAX_FRAMES - 1, " ".join(tokens)))
+    bwd, out = None, None
+    for t in tokens[3 + L:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in ("bwd", "out")) or (k == "bwd" and bwd is not None) or (k == "out" and out is not None):
+            raise ValueError("chain line: bad or repeated token %r" % t)
+        if k == "out":
+            out = v
+        else:
+            bwd = tuple(v.split(","))
+            if len(bwd) != L or not all(bwd):
+                raise ValueError("chain line: bwd= takes %d files: %r" % (L, t))
+    if out is None:
+        raise ValueError("chain line without out=: %r" % " ".join(tokens))
+    return ChainLine(tokens[1], tuple(tokens[3:3 + L]), bwd or (), out)
+
+
+def chain_line(item):
+    """the inverse of parse_chain"""
+    return " ".join([CHAIN_WORD, item.points, str(len(item.flows))] + list(item.flows) +
+                    (["bwd=" + ",".join(item.bwd)] if item.bwd else []) + ["out=" + item.out])
+
+
+def run_chain(state, spec):
+    """one `chain` line: read the points and the flows, one opt.chain_flows, write the track file"""
+    from . import opt, trk
+    pts = trk.read(spec.points)
+    W, H = pts["W"], pts["H"]
+    flows = [flo.flow_read(p) for p in spec.flows]
+    bwd = [flo.flow_read(p) for p in spec.bwd]
+    for path, a in zip(spec.flows + spec.bwd, flows + bwd):
+        if a.shape[:2] != (H, W):
+            raise ValueError("chain line: %s differs in size from %s" % (path, spec.points))
+    pos, occ = opt.chain_flows(state, np.stack(flows), pts["pos"][0], bwd=np.stack(bwd) if bwd else None)
+    trk.write(spec.out, W, H, pos, occ)
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
     BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`, a
-    LightLine when it is `light`, a SegLine when it is `seg`, a ScoreLine when it is `score`"""
+    LightLine when it is `light`, a SegLine when it is `seg`, a ScoreLine when it is `score`, a TScoreLine when it is
+    `tscore`, a ChainLine when it is `chain`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == TSCORE_WORD:
+        return parse_tscore(tok)
+    if tok and tok[0] == CHAIN_WORD:
+        return parse_chain(tok)
     if tok and tok[0] == SCORE_WORD:
         return parse_score(tok)
     if tok and tok[0] == SEG_WORD:
@@ -1064,14 +1257,18 @@ def format_line(item):
         return seg_line(item)
     if isinstance(item, ScoreLine):
         return score_line(item)
+    if isinstance(item, TScoreLine):
+        return tscore_line(item)
+    if isinstance(item, ChainLine):
+        return chain_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
-    first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file, a score
-    line's out= file"""
-    if isinstance(item, (TrkLine, ScoreLine)):
+    first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file, a score,
+    tscore or chain line's out= file"""
+    if isinstance(item, (TrkLine, ScoreLine, TScoreLine, ChainLine)):
         return item.out
     if isinstance(item, (BlurLine, LightLine, SegLine)):
         return next(iter(item.out.values()))

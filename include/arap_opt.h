@@ -639,6 +639,59 @@ int ArapFlow_SegMaps(Opt_State* state, unsigned W, unsigned H, unsigned n, const
 int ArapFlow_FlowScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* gt, const void* est,
                        const void* occ, const void* dist, const void* skip, void* table, void* err);
 
+/* Track scoring (DESIGN.md "Track scoring"): the TAP-Vid table of estimated point tracks against the tracks of a track
+ * file, on DEVICE buffers in a track file's layout.  gt_pos, est_pos float32[F][P][2]; gt_occ, est_occ uint8[F][P],
+ * non-zero = hidden.  Frame 0 is the query frame and is not scored.  Point k is valid iff gt_occ[0][k] == 0:
+ *   table[0][0][0] = the number of valid points, table[0][0][1] = the number of invalid ones, the rest of frame 0 is zero,
+ * and an invalid point is counted nowhere else.  For a valid point k and a frame f >= 1, every operator one float32
+ * operation, sqrtf correctly rounded:
+ *   dx = (est.x - gt.x) * sx;  dy = (est.y - gt.y) * sy;  e2 = dx * dx + dy * dy;  e = sqrtf(e2)
+ *   ec = (e <= 4096.f) ? e : 4096.f                      (NaN and +inf land on the cap)
+ *   q  = (uint32)(ec * 4096.f + 0.5f)                    (truncation: the error in units of 2^-12 px, <= 2^24)
+ *   gv = gt_occ[f][k] == 0;  ev = est_occ[f][k] == 0;  in_x = gv && (e2 < x * x)   for x = 1, 2, 4, 8, 16
+ * The point-frame is counted in
+ *   class 0 all         always
+ *   class 1 tracked     gv, and the ground truth is visible in every frame 1 .. f-1
+ *   class 2 reappeared  gv, and the ground truth is hidden in some frame 1 .. f-1
+ * The fields of a class, each uint64:
+ *   0 count   1 gt_vis: gv   2 est_vis: ev   3 agree: gv == ev   4..8 within_x: in_x   9..13 tp_x: in_x && ev
+ *   14 sum: the sum of q over gv   15 max: the largest q over gv
+ * so per class and frame OA = agree / count, delta_x = within_x / gt_vis, J_x = tp_x / (gt_vis + est_vis - tp_x), and the
+ * mean error of the visible points is sum / 4096 / gt_vis.
+ *   table  uint64[F][ARAPFLOW_TSCORE_CLASSES][ARAPFLOW_TSCORE_FIELDS]; the call clears it itself.
+ * Integer atomics only, no float reduction: two runs give identical bytes.  One launch, no scratch, asynchronous on the
+ * state's stream.  Returns 0; -1, and nothing is launched or written, on bad arguments: a null state, buffer or table,
+ * P = 0 or P > 2^24, F < 2 or F > ARAPFLOW_TSCORE_MAX_FRAMES, sx or sy not finite or <= 0, the table overlapping an input;
+ * else a HIP error code. */
+#define ARAPFLOW_TSCORE_MAX_FRAMES 64
+#define ARAPFLOW_TSCORE_CLASSES 3
+#define ARAPFLOW_TSCORE_FIELDS 16
+int ArapFlow_TrackScore(Opt_State* state, unsigned F, unsigned P, const void* gt_pos, const void* gt_occ,
+                        const void* est_pos, const void* est_occ, float sx, float sy, void* table);
+
+/* Flow chaining (DESIGN.md "Track scoring"): estimated tracks from per-link flow estimates, on DEVICE buffers.  flows
+ * float32[L][H][W][2], link j the estimated flow from sequence frame j to j + 1 on the integer pixels of frame j; bwd the
+ * same shape or NULL, link j the estimated flow from frame j + 1 back to j; points float32[P][2] in frame 0.  With
+ * in_frame(a): 0 <= a.x <= W - 1 && 0 <= a.y <= H - 1 (false on NaN) and the bilinear sample, per component,
+ *   S(A, a):  x0 = (int)floorf(a.x); y0 = (int)floorf(a.y); x1 = min(x0 + 1, W - 1); y1 = min(y0 + 1, H - 1)
+ *             fx = a.x - (float)x0;  fy = a.y - (float)y0
+ *             top = fmaf(fx, A[y0][x1] - A[y0][x0], A[y0][x0]);  bot = fmaf(fx, A[y1][x1] - A[y1][x0], A[y1][x0])
+ *             v   = fmaf(fy, bot - top, top)
+ * a point p is chained as
+ *   pos[0] = p;  lost = !in_frame(p);  occ[0] = lost ? 255 : 0
+ *   link j, lost:  pos[j+1] = pos[j];  occ[j+1] = 255
+ *   otherwise:     f = S(flows[j], pos[j]);  b = (pos[j].x + f.x, pos[j].y + f.y);  pos[j+1] = b
+ *                  !in_frame(b):  lost = true, occ[j+1] = 255      (for good; decided before any floorf of b)
+ *                  else occ[j+1] = 0, and with bwd:  g = S(bwd[j], b);  s = f + g
+ *                       d2 = s.x * s.x + s.y * s.y;  m2 = (f.x * f.x + f.y * f.y) + (g.x * g.x + g.y * g.y)
+ *                       occ[j+1] = !(d2 <= fmaf(0.01f, m2, 0.5f)) ? 255 : 0      (forward-backward check; per link)
+ *   out_pos float32[L + 1][P][2], out_occ uint8[L + 1][P]: a track file's planes, ArapFlow_TrackScore's est_pos, est_occ.
+ * One launch, no scratch, asynchronous on the state's stream.  Returns 0; -1, and nothing is launched, on bad arguments:
+ * a null state, flows, points or output, L = 0 or L >= ARAPFLOW_TSCORE_MAX_FRAMES, P = 0 or P > 2^24, W * H = 0 or
+ * >= 2^31, an output overlapping an input or the other output; else a HIP error code. */
+int ArapFlow_ChainFlows(Opt_State* state, unsigned W, unsigned H, unsigned L, const void* flows, const void* bwd,
+                        unsigned P, const void* points, void* out_pos, void* out_occ);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised
