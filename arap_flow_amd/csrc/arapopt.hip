@@ -45,6 +45,7 @@
 #include "arap_score.h"
 #include "arap_tscore.h"
 #include "arap_chain.h"
+#include "arap_fscore.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
 
@@ -61,4 +62,5 @@ using namespace arap;
 #include "abi_seg.h"         // ArapFlow_SegMaps
 #include "abi_score.h"       // ArapFlow_FlowScore
 #include "abi_tscore.h"      // ArapFlow_TrackScore, ArapFlow_ChainFlows
+#include "abi_fscore.h"      // ArapFlow_FrameScore
 #include "abi_solver.h"      // ArapFlow_Solver*

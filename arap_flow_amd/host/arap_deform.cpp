@@ -59,6 +59,10 @@
 // pipeline.format_track_score), and one whose first word is `chain` the track file of chained flow estimates:
 //   chain PTS.trk L FLO_1 .. FLO_L [bwd=B_1,..,B_L] out=OUT.trk
 // (the query points are frame 0 of PTS.trk; every flow has its W, H; OUT.trk has L + 1 frames).
+// A line whose first word is `fscore` is the PSNR / SSIM table of one estimated frame (DESIGN.md "Frame scoring"):
+//   fscore REF.png EST.png [occ=PNG] [dist=PNG] [skip=PNG] [obj=PNG] out=TXT
+// (occ: non-zero = occluded; dist: the 8-bit distance file of a seg line; skip: non-zero = left out; obj: red == 0 is
+// object, anything else background; out: the table as text, pipeline.format_frame_score).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -473,6 +477,50 @@ static bool run_score(Opt_State* state, const ScoreSpec& q)
     return save_text(q.out, text.data(), text.size());
 }
 
+// the PSNR / SSIM table of one estimated frame, synchronously (pipeline.run_fscore): read the two frames and the planes
+// the line names (red channels), the distance file back to squared distances (pipeline.dist_from_png), one
+// ArapFlow_FrameScore on the state's stream, write the table as text
+static bool run_fscore(Opt_State* state, const FScoreSpec& q)
+{
+    arapio::Image ref, est;
+    if (!read_png(q.ref, ref) || !read_png(q.est, est)) return false;
+    if (est.w != ref.w || est.h != ref.h) return fail("fscore: %s differs in size from %s\n", q.est.c_str(), q.ref.c_str());
+    const int w = ref.w, h = ref.h;
+    const size_t N = (size_t)w * h;
+    std::vector<uint8_t> plane[4];
+    std::vector<uint16_t> dist;
+    const std::string* const paths[4] = {&q.occ, &q.dist, &q.skip, &q.obj};
+    for (int k = 0; k < 4; ++k) {
+        if (paths[k]->empty()) continue;
+        arapio::Image im;
+        if (!read_png(*paths[k], im)) return false;
+        if (im.w != w || im.h != h) return fail("fscore: %s differs in size from %s\n", paths[k]->c_str(), q.ref.c_str());
+        if (k == 1) dist.resize(N);
+        else plane[k].resize(N);
+        for (size_t i = 0; i < N; ++i) {
+            const unsigned v = im.rgb[3 * i];                                   // red channel
+            if (k == 1) dist[i] = (uint16_t)(v == 255 ? 65535u : v * v);
+            else plane[k][i] = (uint8_t)v;
+        }
+    }
+    DeviceArena dev;
+    auto input = [&](const void* src, size_t bytes) { return bytes ? dev.stage(src, bytes) : DeviceArena::kNone; };
+    const size_t d_ref = dev.stage(ref.rgb.data(), N * 3), d_est = dev.stage(est.rgb.data(), N * 3);
+    const size_t d_occ = input(plane[0].data(), plane[0].size()), d_dist = input(dist.data(), dist.size() * 2);
+    const size_t d_skip = input(plane[2].data(), plane[2].size()), d_obj = input(plane[3].data(), plane[3].size());
+    uint64_t table[ARAPFLOW_FSCORE_ROWS * ARAPFLOW_FSCORE_FIELDS];
+    const size_t d_table = dev.take(sizeof(table));
+    if (dev.alloc() != hipSuccess) return fail("fscore: out of device memory\n");
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_FrameScore(state, (unsigned)w, (unsigned)h, 1, dev.at(d_ref), dev.at(d_est), dev.at(d_occ), dev.at(d_dist),
+                                        dev.at(d_skip), dev.at(d_obj), dev.at(d_table), nullptr) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(table, dev.at(d_table), sizeof(table), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail("ArapFlow_FrameScore failed\n");
+    const std::string text = format_frame_score(table);
+    return save_text(q.out, text.data(), text.size());
+}
+
 // the TAP-Vid table of one estimated track file, synchronously (pipeline.run_tscore): read the two track files, one
 // ArapFlow_TrackScore on the state's stream, write the table as text
 static bool run_tscore(Opt_State* state, const TScoreSpec& q)
@@ -795,7 +843,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex / trk / blur / light / seg / score / tscore / chain line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur / light / seg / score / tscore / chain / fscore line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -1080,6 +1128,7 @@ int main(int argc, const char* argv[])
                   : kind == Item::Kind::Score ? run_score(state, fr->item.score)
                   : kind == Item::Kind::TScore ? run_tscore(state, fr->item.tscore)
                   : kind == Item::Kind::Chain ? run_chain(state, fr->item.chain)
+                  : kind == Item::Kind::FScore ? run_fscore(state, fr->item.fscore)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

@@ -83,6 +83,26 @@ inline std::string format_track_score(const uint64_t* table, unsigned frames)
     return text;
 }
 
+// the text of a frame score file (pipeline.format_frame_score): one line per row of ArapFlow_FrameScore's table, integers only
+inline std::string format_frame_score(const uint64_t* table)
+{
+    static const char* const rows[ARAPFLOW_FSCORE_ROWS - 1] = {"all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg"};
+    static const char* const fields[ARAPFLOW_FSCORE_FIELDS] = {"count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst"};
+    std::string text;
+    char cell[64];
+    for (int r = 0; r < ARAPFLOW_FSCORE_ROWS - 1; ++r) {
+        text += rows[r];
+        for (int f = 0; f < ARAPFLOW_FSCORE_FIELDS; ++f) {
+            snprintf(cell, sizeof(cell), " %s=%llu", fields[f], (unsigned long long)table[r * ARAPFLOW_FSCORE_FIELDS + f]);
+            text += cell;
+        }
+        text += "\n";
+    }
+    const uint64_t* const left = table + (ARAPFLOW_FSCORE_ROWS - 1) * ARAPFLOW_FSCORE_FIELDS;
+    snprintf(cell, sizeof(cell), "left_out pixels=%llu windows=%llu\n", (unsigned long long)left[0], (unsigned long long)left[1]);
+    return text + cell;
+}
+
 // a text file, as it is; says why not
 inline bool save_text(const std::string& path, const void* data, size_t bytes)
 {

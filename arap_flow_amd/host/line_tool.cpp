@@ -97,6 +97,10 @@ static std::string canonical(const Item& it)
         std::string b;
         for (size_t j = 0; j < q.bwd.size(); ++j) b += (j ? "," : "") + q.bwd[j];
         c.token("bwd", b); c.token("out", q.out);
+    } else if (it.kind == Item::Kind::FScore) {
+        const FScoreSpec& q = it.fscore;
+        c.word("fscore"); c.word(q.ref); c.word(q.est);
+        c.token("occ", q.occ); c.token("dist", q.dist); c.token("skip", q.skip); c.token("obj", q.obj); c.token("out", q.out);
     } else if (it.kind == Item::Kind::Light) {
         const LightSpec& q = it.light;
         c.word("light"); c.word(q.rgb1); c.word(q.mask1); c.word(q.rgb2); c.word(q.cover2);

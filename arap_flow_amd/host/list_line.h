@@ -30,7 +30,9 @@
 //                 (pipeline.TScoreLine): the factors finite and > 0; a repeated key is an error too
 //   chain line:   chain PTS.trk L FLO_1 .. FLO_L [bwd=B_1,..,B_L] out=OUT.trk
 //                 (pipeline.ChainLine): 1 <= L < ARAPFLOW_TSCORE_MAX_FRAMES, bwd= names L files; a repeated key is an error too
-//                 on these ten any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   fscore line:  fscore REF.png EST.png [occ=PNG] [dist=PNG] [skip=PNG] [obj=PNG] out=TXT
+//                 (pipeline.FScoreLine): a repeated key is an error too
+//                 on these eleven any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -100,7 +102,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the eleven forms
+// ---- the twelve forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -201,8 +203,14 @@ struct ChainSpec {                         // pipeline.ChainLine
     std::string out;
 };
 
+struct FScoreSpec {                        // pipeline.FScoreLine
+    std::string ref, est;
+    std::string occ, dist, skip, obj;      // optional planes (empty: not given)
+    std::string out;
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score, TScore, Chain } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score, TScore, Chain, FScore } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
@@ -214,6 +222,7 @@ struct Item {
     ScoreSpec score;
     TScoreSpec tscore;
     ChainSpec chain;
+    FScoreSpec fscore;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -229,6 +238,7 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::Score  ? it.score.out
            : it.kind == Item::Kind::TScore ? it.tscore.out
            : it.kind == Item::Kind::Chain  ? it.chain.out
+           : it.kind == Item::Kind::FScore ? it.fscore.out
                                            : it.bg.first_out();
 }
 
@@ -619,6 +629,19 @@ inline bool parse_chain(std::istringstream& tok, ChainSpec& q)
     return !q.out.empty();
 }
 
+inline bool parse_fscore(std::istringstream& tok, FScoreSpec& q)
+{
+    std::string k, v;
+    if (!(tok >> q.ref >> q.est) || split_token(q.ref, k, v) || split_token(q.est, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        std::string* const dst = field_of({{"occ", &q.occ}, {"dist", &q.dist}, {"skip", &q.skip}, {"obj", &q.obj}, {"out", &q.out}}, k);
+        if (!dst || !dst->empty()) return false;
+        *dst = v;
+    }
+    return !q.out.empty();
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -628,7 +651,7 @@ inline Parsed parse_item(const std::string& line, Item& it)
     it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
               : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : first == "light" ? Item::Kind::Light
               : first == "seg" ? Item::Kind::Seg : first == "score" ? Item::Kind::Score : first == "tscore" ? Item::Kind::TScore
-              : first == "chain" ? Item::Kind::Chain : Item::Kind::Solve;
+              : first == "chain" ? Item::Kind::Chain : first == "fscore" ? Item::Kind::FScore : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
@@ -640,10 +663,11 @@ inline Parsed parse_item(const std::string& line, Item& it)
     else if (it.kind == Item::Kind::Score) p = parse_score(tok, it.score) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::TScore) p = parse_tscore(tok, it.tscore) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Chain) p = parse_chain(tok, it.chain) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::FScore) p = parse_fscore(tok, it.fscore) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
         const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line", "score line",
-                                    "tscore line", "chain line"};      // by Item::Kind
+                                    "tscore line", "chain line", "fscore line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

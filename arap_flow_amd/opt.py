@@ -13,6 +13,7 @@
   warp_diag        fold diagnostics of a flow: mesh statistics and the fold map (ArapFlow_WarpDiag)
   seg_maps         object index maps, motion boundaries and boundary distance of a pair (ArapFlow_SegMaps)
   flow_score       the Sintel / KITTI error table of an estimated flow against a pair (ArapFlow_FlowScore)
+  frame_score      the PSNR / integer-SSIM table of estimated frames (ArapFlow_FrameScore)
   track_score      the TAP-Vid table of estimated tracks against a track file's (ArapFlow_TrackScore)
   chain_flows      estimated tracks from per-link flow estimates (ArapFlow_ChainFlows)
 
@@ -903,6 +904,36 @@ def chain_flows(state, flows, points, bwd=None):
     r = _warp_call(state, "ChainFlows", (W, H, L), [(flows, np.float32), (bwd, np.float32), (P, None), (points, np.float32)],
                    [("pos", (L + 1, P, 2), torch.float32), ("occ", (L + 1, P), torch.uint8)])
     return r["pos"], r["occ"]
+
+
+FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")
+FSCORE_FIELDS = ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")
+
+
+def frame_score(state, ref, est, occ=None, dist=None, skip=None, obj=None, ssim=False):
+    """the PSNR / integer-SSIM table of estimated frames against reference frames (ArapFlow_FrameScore, DESIGN.md "Frame
+    scoring").  ref, est u8[H,W,3] or u8[n,H,W,3]; occ u8 (non-zero: occluded), dist u16 (ArapFlow_SegMaps' squared
+    distance), skip u8 (non-zero: left out), obj u8 (0: object, non-zero: background), each [H,W] / [n,H,W] or None
+    (numpy) -> {"table": u64[n,9,7]}, rows in the order of FSCORE_ROWS and fields in that of FSCORE_FIELDS (row 8: pixels,
+    windows), and with `ssim` also {"ssim": f32[n,H,W]}, s at the anchor of a counted window and -2 on every other pixel."""
+    ref = np.ascontiguousarray(ref, np.uint8)
+    est = np.ascontiguousarray(est, np.uint8)
+    if ref.ndim == 3:
+        ref, est = ref[None], est[None] if est.ndim == 3 else est
+    if ref.ndim != 4 or ref.shape[3] != 3 or est.shape != ref.shape:
+        raise ValueError("frame_score: ref and est [H,W,3] or [n,H,W,3] of one shape expected")
+    n, H, W = ref.shape[:3]
+    planes = []
+    for name, a, dt in (("occ", occ, np.uint8), ("dist", dist, np.uint16), ("skip", skip, np.uint8), ("obj", obj, np.uint8)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dt).reshape((-1,) + np.shape(a)[-2:])
+            if a.shape != (n, H, W):
+                raise ValueError("frame_score: %s of ref's shape without its last axis expected" % name)
+            a = a.view(np.int16) if dt is np.uint16 else a       # (torch uploads no unsigned 16-bit arrays)
+        planes.append((a, np.int16 if dt is np.uint16 else dt))
+    return _warp_call(state, "FrameScore", (W, H, n), [(ref, np.uint8), (est, np.uint8)] + planes,
+                      [("table", (n, len(FSCORE_ROWS), len(FSCORE_FIELDS)), torch.int64),
+                       ("ssim", (n, H, W) if ssim else None, torch.float32)], view={"table": np.uint64})
 
 
 BG_OUTPUTS = ("out_rgb1","out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")

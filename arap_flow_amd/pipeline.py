@@ -24,6 +24,8 @@ functions that tests/golden/host/ pins with hand-computed cases:
   TScoreLine, parse_tscore, tscore_line, run_tscore    the `tscore` line: the TAP-Vid table of an estimated track file (addition)
   ChainLine, parse_chain, chain_line, run_chain    the `chain` line: an estimated track file from per-link flows (addition)
   format_track_score, parse_track_score_file, track_score_summary, add_track_scores    a track score table as text, as metrics, pooled
+  FScoreLine, parse_fscore, fscore_line, run_fscore    the `fscore` line: the PSNR / SSIM table of an estimated frame (addition)
+  format_frame_score, parse_frame_score_file, frame_score_summary, add_frame_scores    a frame score table as text, as metrics, pooled
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
@@ -78,6 +80,11 @@ SCORE_KEYS = ("occ", "dist", "skip", "mask")
 # the rows and the fields of a score table in its order (opt.SCORE_ROWS, opt.SCORE_FIELDS; ArapFlow_FlowScore)
 SCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")
 SCORE_FIELDS = ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")
+FSCORE_WORD = "fscore"
+FSCORE_KEYS = ("occ", "dist", "skip", "obj")
+# the rows and the fields of a frame score table in its order (opt.FSCORE_ROWS, opt.FSCORE_FIELDS; ArapFlow_FrameScore)
+FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")
+FSCORE_FIELDS = ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")
 TSCORE_WORD = "tscore"
 CHAIN_WORD = "chain"
 TSCORE_MAX_FRAMES = 64       # ARAPFLOW_TSCORE_MAX_FRAMES of include/arap_opt.h
@@ -1208,12 +1215,126 @@ def run_chain(state, spec):
     trk.write(spec.out, W, H, pos, occ)
 
 
+class FScoreLine(NamedTuple):
+    """an `fscore` line (DESIGN.md "Frame scoring"), recognised by its first word: the PSNR / SSIM table of one estimate
+        fscore REF.png EST.png [occ=PNG] [dist=PNG] [skip=PNG] [obj=PNG] out=TXT
+    occ: an occlusion map, non-zero = occluded; dist: the 8-bit distance file of a seg line (dist_from_png); skip: non-zero
+    = left out; obj: an object mask in the solver's convention, red == 0 is object, anything else background; all in the
+    pixel grid of REF.  `planes`: {key: path} of those given, `out` the text file (format_frame_score).  Anything else --
+    an unknown or repeated key, an empty value, no out=, fewer than two paths -- is an error."""
+    ref: str
+    est: str
+    planes: dict
+    out: str
+
+
+def parse_fscore(tokens):
+    if len(tokens) < 3 or tokens[0] != FSCORE_WORD or "=" in tokens[1] or "=" in tokens[2]:
+        raise ValueError("fscore line: two frame files expected: %r" % " ".join(tokens))
+    planes, out = {}, None
+    for t in tokens[3:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in FSCORE_KEYS + ("out",)) or k in planes or (k == "out" and out is not None):
+            raise ValueError("fscore line: bad or repeated token %r" % t)
+        if k == "out":
+            out = v
+        else:
+            planes[k] = v
+    if out is None:
+        raise ValueError("fscore line without out=: %r" % " ".join(tokens))
+    return FScoreLine(tokens[1], tokens[2], planes, out)
+
+
+def fscore_line(item):
+    """the inverse of parse_fscore: the planes in the order of FSCORE_KEYS, then out="""
+    return " ".join([FSCORE_WORD, item.ref, item.est] + ["%s=%s" % (k, item.planes[k]) for k in FSCORE_KEYS if item.planes.get(k)] +
+                    ["out=" + item.out])
+
+
+def format_frame_score(table):
+    """the text of a frame score file: one line per row of a table uint64[9][7], `<row name> count=.. sse=.. sad=.. max=..
+    windows=.. ssim_sum=.. ssim_worst=..`, the last `left_out pixels=.. windows=..`; integers only; the C++ worker writes
+    the same bytes"""
+    t = np.asarray(table, np.uint64).reshape(len(FSCORE_ROWS), len(FSCORE_FIELDS))
+    lines = ["%s %s\n" % (name, " ".join("%s=%d" % (f, int(v)) for f, v in zip(FSCORE_FIELDS, row)))
+             for name, row in zip(FSCORE_ROWS[:-1], t)]
+    return "".join(lines) + "%s pixels=%d windows=%d\n" % (FSCORE_ROWS[-1], int(t[-1, 0]), int(t[-1, 1]))
+
+
+def parse_frame_score_file(text):
+    """the inverse of format_frame_score -> uint64[9][7]"""
+    lines = text.split("\n")
+    if len(lines) != len(FSCORE_ROWS) + 1 or lines[-1] != "":
+        raise ValueError("frame score file: %d lines expected" % len(FSCORE_ROWS))
+    t = np.zeros((len(FSCORE_ROWS), len(FSCORE_FIELDS)), np.uint64)
+    for r, (name, line) in enumerate(zip(FSCORE_ROWS, lines)):
+        keys = FSCORE_FIELDS if r < len(FSCORE_ROWS) - 1 else ("pixels", "windows")
+        tok = line.split(" ")
+        if tok[0] != name or len(tok) != 1 + len(keys):
+            raise ValueError("frame score file: bad row %r" % line)
+        for f, (key, cell) in enumerate(zip(keys, tok[1:])):
+            k, _, v = cell.partition("=")
+            if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
+                raise ValueError("frame score file: bad field %r" % cell)
+            t[r, f] = int(v)
+    return t
+
+
+def frame_score_summary(table):
+    """{row name: dict(count, psnr, mae, windows, ssim, ssim_min)} of a table, float64: psnr = 10 log10(255^2 * 3 * count /
+    sse) in dB (inf when sse = 0), mae = sad / (3 * count), ssim = ssim_sum / windows / 2^20 - 1, ssim_min = 1 - ssim_worst
+    / 2^20; nan for a row without pixels (psnr, mae) or windows (ssim, ssim_min); `left_out` is dict(pixels, windows)"""
+    t = np.asarray(table, np.uint64).reshape(len(FSCORE_ROWS), len(FSCORE_FIELDS))
+    res, nan = {}, float("nan")
+    for name, row in zip(FSCORE_ROWS[:-1], t):
+        count, sse, sad, _, windows, ssim_sum, worst = (int(v) for v in row)
+        psnr = nan if not count else float("inf") if not sse else 10.0 * math.log10(65025.0 * 3.0 * count / sse)
+        res[name] = dict(count=count, psnr=psnr, mae=sad / (3.0 * count) if count else nan, windows=windows,
+                         ssim=ssim_sum / windows / 1048576.0 - 1.0 if windows else nan,
+                         ssim_min=1.0 - worst / 1048576.0 if windows else nan)
+    res[FSCORE_ROWS[-1]] = dict(pixels=int(t[-1, 0]), windows=int(t[-1, 1]))
+    return res
+
+
+def add_frame_scores(tables):
+    """the pooled table of several: the integer sum of every field but `max` and `ssim_worst`, which take the maximum --
+    exactly the table of all their frames together"""
+    out = np.zeros((len(FSCORE_ROWS), len(FSCORE_FIELDS)), np.uint64)
+    for t in tables:
+        t = np.asarray(t, np.uint64).reshape(out.shape)
+        peak = np.maximum(out[:-1, [3, 6]], t[:-1, [3, 6]])
+        out += t
+        out[:-1, [3, 6]] = peak
+    return out
+
+
+def run_fscore(state, spec):
+    """one `fscore` line: read the two frames and the planes given, one opt.frame_score, write the table as text"""
+    from . import opt
+    ref, est = load_rgb(spec.ref), load_rgb(spec.est)
+    if ref.shape != est.shape:
+        raise ValueError("fscore line: %s and %s differ in size" % (spec.ref, spec.est))
+    plane = {}
+    for k, path in spec.planes.items():
+        plane[k] = load_mask_red(path)
+        if plane[k].shape != ref.shape[:2]:
+            raise ValueError("fscore line: %s differs in size from %s" % (path, spec.ref))
+    if "dist" in plane:
+        plane["dist"] = dist_from_png(plane["dist"])
+    table = opt.frame_score(state, ref, est, **plane)["table"][0]
+    with open(spec.out, "w") as f:
+        f.write(format_frame_score(table))
+    return table
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
     BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`, a
     LightLine when it is `light`, a SegLine when it is `seg`, a ScoreLine when it is `score`, a TScoreLine when it is
-    `tscore`, a ChainLine when it is `chain`"""
+    `tscore`, a ChainLine when it is `chain`, an FScoreLine when it is `fscore`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == FSCORE_WORD:
+        return parse_fscore(tok)
     if tok and tok[0] == TSCORE_WORD:
         return parse_tscore(tok)
     if tok and tok[0] == CHAIN_WORD:
@@ -1261,14 +1382,16 @@ def format_line(item):
         return tscore_line(item)
     if isinstance(item, ChainLine):
         return chain_line(item)
+    if isinstance(item, FScoreLine):
+        return fscore_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
     first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file, a score,
-    tscore or chain line's out= file"""
-    if isinstance(item, (TrkLine, ScoreLine, TScoreLine, ChainLine)):
+    tscore, chain or fscore line's out= file"""
+    if isinstance(item, (TrkLine, ScoreLine, TScoreLine, ChainLine, FScoreLine)):
         return item.out
     if isinstance(item, (BlurLine, LightLine, SegLine)):
         return next(iter(item.out.values()))

@@ -1,0 +1,168 @@
+#!/usr/bin/env python3
+"""Score estimated frames against a generated dataset (DESIGN.md "Frame scoring").
+
+    frame_score_gen.py --data OUT --est EST_ROOT [--full] [--baseline blend] [--gpu 0 1 ..] [--narap N] [--arap_bin CMD]
+                       [--worker auto|serve|batch]
+
+OUT is a tree para_gen.py wrote.  Every ground-truth frame is scored against the file of the same name relative to OUT
+under EST_ROOT (OUT/Mid/a/00003_s09.png against EST_ROOT/Mid/a/00003_s09.png) by one `fscore` line of arap_deform
+(pipeline.FScoreLine) on para_gen.py's workers, one persistent `arap_deform --serve` per GPU.  The ground truth:
+
+  default   every in-between frame OUT/Mid/<seq>/<frame>_sNN.png (--mid, --mid_layers) and every frame 2
+            OUT/wRGB/<seq>/<frame>.png
+  --full    every in-between frame OUT/MidFull/<seq>/<frame>_sNN.png (--mid_bg)
+
+A plane is passed only where a file defined in the scored frame's own pixel grid exists:
+
+  Mid, MidFull  occ=<frame>_sNN_occ.png beside the frame: the occlusion of the link that starts at that snapshot
+  wRGB          occ=OUT/OccBwd/<seq>/<frame>.png, the frame-2 pixels frame 1 does not show, and
+                dist=OUT/MBDistBwd/<seq>/<frame>.png, the distance to a motion boundary in frame 2
+
+Occ, MBDist, Fold and inpMasks live in frame 1's grid and are never passed; the warped masks (wMasks, _sNN_mask.png) are
+in the right grid but non-zero on the object, the opposite of obj=, so the obj and bg rows stay empty here.
+
+  --baseline blend   no estimate is read: for every in-between ground truth the rounded mean (a + b + 1) >> 1 of the
+                     pair's two end frames OUT/inpRGB/<seq>/<frame>.png and OUT/wRGB/<seq>/<frame>.png is written, in
+                     numpy, to OUT/FramesEst/<same relative name>, and that tree is scored: the figure an interpolator has
+                     to beat.  (A frame 2 has no such estimate and is listed as missing.)
+
+Written: OUT/FrameScore/<seq>/<name>.txt per frame (pipeline.format_frame_score), their exact pooled table
+OUT/frame_score.txt (pipeline.add_frame_scores) and OUT/frame_score_missing.list, the ground-truth frames without an
+estimate, which are counted and no error.  Prints the summary (pipeline.frame_score_summary) of the pooled table -- PSNR
+and SSIM over all pixels and windows together --, the mean of the per-frame PSNRs over the frames with sse > 0, which is what
+the interpolation papers report, and the number of exact frames, which have none.
+"""
+import argparse
+import os
+import os.path as osp
+import re
+import sys
+import threading
+
+import numpy as np
+from PIL import Image
+
+HERE = osp.dirname(osp.abspath(__file__))
+sys.path.insert(0, HERE)
+import para_gen                             # noqa: E402
+from arap_flow_amd import pipeline          # noqa: E402
+
+MID_FRAME = re.compile(r"^(.*)_s(\d\d)\.png$")
+EST_DIR = "FramesEst"
+
+
+def ground_truth(data, full):
+    """[(directory under OUT, seq, name without .png, pair stem or None)] of the frames to score; the stem of an
+    in-between frame is its pair's, a frame 2 has None"""
+    found = []
+    for top in ([para_gen.mid_full_dir] if full else [para_gen.mid_dir, para_gen.wrgb_dir]):
+        root = osp.join(data, top)
+        for d, _, fs in sorted(os.walk(root)):
+            for f in sorted(fs):
+                m = MID_FRAME.match(f)
+                if (m is None) != (top == para_gen.wrgb_dir) or not f.endswith(".png"):
+                    continue
+                found.append((top, osp.relpath(d, root), f[:-4], m.group(1) if m else None))
+    return found
+
+
+def planes_of(data, top, seq, name):
+    """{key: path} of the planes defined in the frame's own grid (the module's docstring), those whose file exists"""
+    if top == para_gen.wrgb_dir:
+        planes = dict(occ=osp.join(data, para_gen.occ_bwd_dir, seq, name + ".png"),
+                      dist=osp.join(data, para_gen.SEG_DIRS["dist2"], seq, name + ".png"))
+    else:
+        planes = dict(occ=osp.join(data, top, seq, name + "_occ.png"))
+    return {k: p for k, p in planes.items() if osp.exists(p)}
+
+
+def write_blend(data, full):
+    """--baseline blend: OUT/FramesEst/<relative name> of every in-between ground truth whose two end frames exist"""
+    for top, seq, name, stem in ground_truth(data, full):
+        ends = [osp.join(data, d, seq, "%s.png" % stem) for d in (para_gen.color_dir, para_gen.wrgb_dir)]
+        if stem is None or not all(osp.exists(e) for e in ends):
+            continue
+        a, b = (pipeline.load_rgb(e).astype(np.uint16) for e in ends)
+        out = osp.join(data, EST_DIR, top, seq, name + ".png")
+        os.makedirs(osp.dirname(out), exist_ok=True)
+        Image.fromarray(((a + b + 1) >> 1).astype(np.uint8)).save(out)
+
+
+def score_items(data, est_root, full):
+    """-> ([FScoreLine], [ground-truth files without an estimate])"""
+    items, missing = [], []
+    for top, seq, name, _ in ground_truth(data, full):
+        gt, est = osp.join(data, top, seq, name + ".png"), osp.join(est_root, top, seq, name + ".png")
+        if not osp.exists(est):
+            missing.append(gt)
+            continue
+        out = osp.join(data, "FrameScore", seq, name + ".txt")
+        os.makedirs(osp.dirname(out), exist_ok=True)
+        items.append(pipeline.FScoreLine(gt, est, planes_of(data, top, seq, name), out))
+    return items, missing
+
+
+def summary_text(table):
+    s = pipeline.frame_score_summary(table)
+    text = "%-9s %11s %9s %8s %11s %9s %9s\n" % ("class", "pixels", "PSNR dB", "MAE", "windows", "SSIM", "SSIM min")
+    for name in pipeline.FSCORE_ROWS[:-1]:
+        r = s[name]
+        text += "%-9s %11d %9.4f %8.4f %11d %9.6f %9.6f\n" % (name, r["count"], r["psnr"], r["mae"], r["windows"], r["ssim"], r["ssim_min"])
+    left = s[pipeline.FSCORE_ROWS[-1]]
+    return text + "left out: %d pixels, %d windows\n" % (left["pixels"], left["windows"])
+
+
+def main(flags):
+    data = osp.abspath(flags.data)
+    if flags.baseline:
+        write_blend(data, flags.full)
+    items, missing = score_items(data, osp.join(data, EST_DIR) if flags.baseline else osp.abspath(flags.est), flags.full)
+    done, lock = [], threading.Lock()
+
+    def on_done(path):
+        with lock:
+            done.append(path)
+    if items:
+        serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == para_gen.CPP_BIN)
+        workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, serve, on_done)
+        for it in items:
+            workers.put(pipeline.format_line(it))
+        workers.close()
+        workers.join()
+    assert sorted(done) == sorted(it.out for it in items), "an fscore line was not reported done"
+    tables = [pipeline.parse_frame_score_file(open(it.out).read()) for it in items]
+    pooled = pipeline.add_frame_scores(tables)
+    with open(osp.join(data, "frame_score.txt"), "w") as f:
+        f.write(pipeline.format_frame_score(pooled))
+    with open(osp.join(data, "frame_score_missing.list"), "w") as f:
+        f.write("".join(m + "\n" for m in missing))
+    print("%d frames scored, %d without an estimate" % (len(items), len(missing)))
+    print(summary_text(pooled), end="")
+    psnr = [pipeline.frame_score_summary(t)["all"]["psnr"] for t in tables if int(t[0, 1]) > 0 and int(t[0, 0]) > 0]
+    exact = sum(1 for t in tables if int(t[0, 1]) == 0)
+    print("mean of the per-frame PSNRs: %s over %d frames; %d exact frames" %
+          ("%.4f dB" % (sum(psnr) / len(psnr)) if psnr else "none", len(psnr), exact))
+    return pooled
+
+
+def parse(argv=None):
+    parser = argparse.ArgumentParser(description="PSNR / SSIM tables of estimated frames against a para_gen.py dataset")
+    parser.add_argument("--data", required=True, help="the dataset: para_gen.py's --output")
+    parser.add_argument("--est", help="the estimates: EST/<Mid|wRGB|MidFull>/<seq>/<name>.png, named like the dataset's frames")
+    parser.add_argument("--full", action="store_true", help="score the in-between frames of MidFull instead of Mid and wRGB")
+    parser.add_argument("--baseline", choices=["blend"], help="score the rounded mean of a pair's end frames instead of --est")
+    parser.add_argument("--gpu", nargs="*", type=int, default=[0], help="GPU ids, default 0")
+    parser.add_argument("--narap", type=int, default=64, help="lines one GPU holds at a time")
+    parser.add_argument("--arap_bin", default=para_gen.CPP_BIN if osp.exists(para_gen.CPP_BIN) else
+                        "%s %s" % (sys.executable, osp.join(HERE, "arap_deform.py")), help="this repository's arap_deform")
+    parser.add_argument("--worker", choices=["auto", "serve", "batch"], default="auto", help="as para_gen.py's --worker")
+    flags = parser.parse_args(argv)
+    if (flags.est is None) == (flags.baseline is None):
+        parser.error("one of --est and --baseline is needed")
+    if not para_gen.own_arap_bin(flags.arap_bin):
+        parser.error("--arap_bin: an `fscore` line needs this repository's driver")
+    return flags
+
+
+if __name__ == "__main__":
+    main(parse())

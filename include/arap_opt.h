@@ -692,6 +692,45 @@ int ArapFlow_TrackScore(Opt_State* state, unsigned F, unsigned P, const void* gt
 int ArapFlow_ChainFlows(Opt_State* state, unsigned W, unsigned H, unsigned L, const void* flows, const void* bwd,
                         unsigned P, const void* points, void* out_pos, void* out_occ);
 
+/* Frame scoring (DESIGN.md "Frame scoring"): the PSNR / integer-SSIM table of n estimated frames against n reference
+ * frames of one size, on DEVICE buffers.  ref, est uint8[n][H][W][3]; occ uint8[n][H][W], non-zero = occluded; dist
+ * uint16[n][H][W], ArapFlow_SegMaps' squared distance with 65535 = none; skip uint8[n][H][W], non-zero = left out; obj
+ * uint8[n][H][W], a mask in the solver's convention, 0 = object, non-zero = background; each of the four may be NULL.
+ *   pixel:   d_c = |ref_c - est_c|;  sse = d_0^2 + d_1^2 + d_2^2;  sad = d_0 + d_1 + d_2;  mx = max(d_0, d_1, d_2)
+ *   luma:    Y = (77 R + 150 G + 29 B + 128) >> 8
+ *   window:  every 8 x 8 window wholly in the frame, stride 1: (W - 7)(H - 7) of them, none when W < 8 or H < 8.  With
+ *            a = Y(ref), b = Y(est) over its 64 pixels, in integers (each below 2^31 in magnitude, B signed):
+ *              s1 = sum a;  s2 = sum b;  ss = sum (a * a + b * b);  s12 = sum a * b
+ *              vars = 64 * ss - s1 * s1 - s2 * s2;  covar = 64 * s12 - s1 * s2
+ *              A = 2 * s1 * s2 + 416;  B = 2 * covar + 235963;  C = s1 * s1 + s2 * s2 + 416;  D = vars + 235963
+ *            then, every operator one float32 operation, the division correctly rounded:
+ *              s = ((float)A * (float)B) / ((float)C * (float)D);  t = max(s + 1.0f, 0.0f)
+ *              q = (uint32)(t * 1048576.f + 0.5f)                 (truncation; 2^21 for identical windows, never more)
+ *            The anchor of the window with top-left (x, y) is the pixel (x + 3, y + 3); a window belongs to the rows its
+ *            anchor belongs to.
+ * A pixel with skip != 0 is counted in row 8, field 0, and nowhere else; a window whose anchor has skip != 0 in row 8,
+ * field 1, and nowhere else (its 64 pixels are whatever they are).  Every other pixel or anchor is counted in
+ *   row 0 all
+ *   row 1 noc      occ given and occ == 0             row 2 occ      occ given and occ != 0
+ *   row 3 d0-10    dist given and dist < 100          row 4 d10-60   dist given and 100 <= dist < 3600
+ *   row 5 d60-140  dist given and 3600 <= dist < 19600
+ *   row 6 obj      obj given and obj == 0             row 7 bg       obj given and obj != 0
+ * The fields of a row 0..7, each uint64:
+ *   0 count: pixels   1 sse   2 sad   3 max: the largest mx   4 windows   5 ssim_sum: the sum of q
+ *   6 ssim_worst: the largest 2^21 - q
+ * A row whose plane is NULL stays zero.  Tables pool by adding every field but 3 and 6, which take the maximum.
+ *   table  uint64[n][ARAPFLOW_FSCORE_ROWS][ARAPFLOW_FSCORE_FIELDS]; the call clears it itself.
+ *   ssim   float32[n][H][W] or NULL: s as computed at the anchor of a counted window, -2.f at every other pixel.
+ * Integer atomics only, no float reduction: two runs give identical bytes.  One launch whatever n; the frames are read 16
+ * bytes at a time where ref and est are 16-byte aligned (whatever W * H), byte by byte otherwise.  Needs no scratch.
+ * Asynchronous on the state's stream.  Returns 0; -1, and nothing is launched or written, on bad arguments: a null state,
+ * ref, est or table, n = 0, W * H = 0, n * W * H >= 2^31, an output overlapping an input or the other output; else a HIP
+ * error code. */
+#define ARAPFLOW_FSCORE_ROWS 9
+#define ARAPFLOW_FSCORE_FIELDS 7
+int ArapFlow_FrameScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* ref, const void* est,
+                        const void* occ, const void* dist, const void* skip, const void* obj, void* table, void* ssim);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised
