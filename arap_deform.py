@@ -11,8 +11,9 @@ word is `trk` the point tracks of one sequence, one whose first word is `blur` t
 whose first word is `light` the relit frames of one pair, one whose first word is `seg` the segment maps of one pair, one
 whose first word is `score` the error table of one estimated flow, one whose first word is `tscore` the TAP-Vid table of
 one estimated track file, one whose first word is `chain` the track file of chained flow estimates, one whose first word
-is `fscore` the PSNR / SSIM table of one estimated frame: the forms are defined in arap_flow_amd/pipeline.py (SolveLine,
-parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine, SegLine, ScoreLine, TScoreLine, ChainLine, FScoreLine).  Any line that is no solve runs once every earlier line of the list is solved and written (its
+is `fscore` the PSNR / SSIM table of one estimated frame, one whose first word is `interp` the in-between frames of a
+pair from a flow estimate: the forms are defined in arap_flow_amd/pipeline.py (SolveLine,
+parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine, SegLine, ScoreLine, TScoreLine, ChainLine, FScoreLine, InterpLine).  Any line that is no solve runs once every earlier line of the list is solved and written (its
 inputs may be their outputs).
 
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
@@ -91,6 +92,8 @@ def main(argv):
                 pipeline.run_chain(state, lines[k])
             elif isinstance(lines[k], pipeline.FScoreLine):
                 pipeline.run_fscore(state, lines[k])
+            elif isinstance(lines[k], pipeline.InterpLine):
+                pipeline.run_interp(state, lines[k])
             else:
                 pipeline.run_layers(state, lines[k])
             print("Saved")

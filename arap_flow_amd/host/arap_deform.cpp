@@ -63,6 +63,9 @@
 //   fscore REF.png EST.png [occ=PNG] [dist=PNG] [skip=PNG] [obj=PNG] out=TXT
 // (occ: non-zero = occluded; dist: the 8-bit distance file of a seg line; skip: non-zero = left out; obj: red == 0 is
 // object, anything else background; out: the table as text, pipeline.format_frame_score).
+// A line whose first word is `interp` is the in-between frames of a pair from a flow estimate (DESIGN.md "Frames from flows"):
+//   interp A.png B.png FWD.flo s=I1,I2,.. n=N [bwd=BWD.flo] [src=1] out=PREFIX
+// (the times are (float)I / (float)N; written: PREFIX_sII.png and, with src=1, the source maps PREFIX_sII_src.png).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -521,6 +524,51 @@ static bool run_fscore(Opt_State* state, const FScoreSpec& q)
     return save_text(q.out, text.data(), text.size());
 }
 
+// the in-between frames of one pair from a flow estimate, synchronously (pipeline.run_interp): read the two frames and the
+// flows, one ArapFlow_InterpFrames on the state's stream, write a frame (and with src=1 a source map) per step
+static bool run_interp(Opt_State* state, const InterpSpec& q)
+{
+    arapio::Image a, b;
+    if (!read_png(q.a, a) || !read_png(q.b, b)) return false;
+    if (b.w != a.w || b.h != a.h) return fail("interp: %s differs in size from %s\n", q.b.c_str(), q.a.c_str());
+    const int w = a.w, h = a.h;
+    const size_t N = (size_t)w * h;
+    const unsigned K = (unsigned)q.steps.size();
+    std::vector<float> flow[2];
+    const std::string* const paths[2] = {&q.fwd, &q.bwd};
+    for (int k = 0; k < 2; ++k) {
+        if (paths[k]->empty()) continue;
+        int fw = 0, fh = 0;
+        if (!arapio::read_flo(*paths[k], flow[k], fw, fh)) return fail("Could not read %s\n", paths[k]->c_str());
+        if (fw != w || fh != h) return fail("interp: %s differs in size from %s\n", paths[k]->c_str(), q.a.c_str());
+    }
+    const uint64_t scratch = ArapFlow_InterpScratchBytes((unsigned)w, (unsigned)h, K);
+    if (!scratch) return fail("interp: %u frames of %d x %d: beyond the limits\n", K, w, h);
+    float times[ARAPFLOW_INTERP_MAX_TIMES];
+    for (unsigned k = 0; k < K; ++k) times[k] = (float)q.steps[k] / (float)q.n;
+    DeviceArena dev;
+    const size_t d_a = dev.stage(a.rgb.data(), N * 3), d_b = dev.stage(b.rgb.data(), N * 3);
+    const size_t d_fwd = dev.stage(flow[0].data(), N * 8);
+    const size_t d_bwd = flow[1].empty() ? DeviceArena::kNone : dev.stage(flow[1].data(), N * 8);
+    const size_t d_out = dev.take((size_t)K * N * 3), d_src = q.src ? dev.take((size_t)K * N) : DeviceArena::kNone;
+    const size_t d_scratch = dev.take((size_t)scratch);
+    if (dev.alloc() != hipSuccess) return fail("interp: out of device memory\n");
+    std::vector<uint8_t> out((size_t)K * N * 3), src(q.src ? (size_t)K * N : 0);
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_InterpFrames(state, (unsigned)w, (unsigned)h, dev.at(d_a), dev.at(d_b), dev.at(d_fwd), dev.at(d_bwd), K,
+                                          times, dev.at(d_out), dev.at(d_src), dev.at(d_scratch)) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(out.data(), dev.at(d_out), out.size(), hipMemcpyDeviceToHost) == hipSuccess &&
+                    (!q.src || hipMemcpy(src.data(), dev.at(d_src), src.size(), hipMemcpyDeviceToHost) == hipSuccess);
+    if (!ok) return fail("ArapFlow_InterpFrames failed\n");
+    for (unsigned k = 0; k < K; ++k) {
+        const std::string stem = mid_stem(q.out, q.steps[k]);
+        if (!save(FileKind::rgb, stem + ".png", w, h, out.data() + k * N * 3)) return false;
+        if (q.src && !save(FileKind::gray8, stem + "_src.png", w, h, src.data() + k * N)) return false;
+    }
+    return true;
+}
+
 // the TAP-Vid table of one estimated track file, synchronously (pipeline.run_tscore): read the two track files, one
 // ArapFlow_TrackScore on the state's stream, write the table as text
 static bool run_tscore(Opt_State* state, const TScoreSpec& q)
@@ -843,7 +891,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex / trk / blur / light / seg / score / tscore / chain / fscore line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur / light / seg / score / tscore / chain / fscore / interp line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -1129,6 +1177,7 @@ int main(int argc, const char* argv[])
                   : kind == Item::Kind::TScore ? run_tscore(state, fr->item.tscore)
                   : kind == Item::Kind::Chain ? run_chain(state, fr->item.chain)
                   : kind == Item::Kind::FScore ? run_fscore(state, fr->item.fscore)
+                  : kind == Item::Kind::Interp ? run_interp(state, fr->item.interp)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

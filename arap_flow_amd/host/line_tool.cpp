@@ -101,6 +101,13 @@ static std::string canonical(const Item& it)
         const FScoreSpec& q = it.fscore;
         c.word("fscore"); c.word(q.ref); c.word(q.est);
         c.token("occ", q.occ); c.token("dist", q.dist); c.token("skip", q.skip); c.token("obj", q.obj); c.token("out", q.out);
+    } else if (it.kind == Item::Kind::Interp) {
+        const InterpSpec& q = it.interp;
+        c.word("interp"); c.word(q.a); c.word(q.b); c.word(q.fwd);
+        std::string steps;
+        for (size_t j = 0; j < q.steps.size(); ++j) steps += (j ? "," : "") + std::to_string(q.steps[j]);
+        c.token("s", steps); c.token("n", std::to_string(q.n)); c.token("bwd", q.bwd); c.token("src", q.src ? "1" : "");
+        c.token("out", q.out);
     } else if (it.kind == Item::Kind::Light) {
         const LightSpec& q = it.light;
         c.word("light"); c.word(q.rgb1); c.word(q.mask1); c.word(q.rgb2); c.word(q.cover2);

@@ -32,7 +32,9 @@
 //                 (pipeline.ChainLine): 1 <= L < ARAPFLOW_TSCORE_MAX_FRAMES, bwd= names L files; a repeated key is an error too
 //   fscore line:  fscore REF.png EST.png [occ=PNG] [dist=PNG] [skip=PNG] [obj=PNG] out=TXT
 //                 (pipeline.FScoreLine): a repeated key is an error too
-//                 on these eleven any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   interp line:  interp A.png B.png FWD.flo s=I1,I2,.. n=N [bwd=BWD.flo] [src=1] out=PREFIX
+//                 (pipeline.InterpLine): 1 to ARAPFLOW_INTERP_MAX_TIMES steps, 1 <= I1 < I2 < .. < N; a repeated key is an error too
+//                 on these twelve any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -102,7 +104,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the twelve forms
+// ---- the thirteen forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -209,8 +211,17 @@ struct FScoreSpec {                        // pipeline.FScoreLine
     std::string out;
 };
 
+struct InterpSpec {                        // pipeline.InterpLine
+    std::string a, b, fwd;
+    std::vector<unsigned> steps;           // ramp steps: the times are (float)step / (float)n
+    unsigned n = 0;
+    std::string bwd;                       // optional input (empty: not given)
+    bool src = false;                      // also write the source maps
+    std::string out;                       // the prefix of the files
+};
+
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score, TScore, Chain, FScore } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score, TScore, Chain, FScore, Interp } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
@@ -223,6 +234,7 @@ struct Item {
     TScoreSpec tscore;
     ChainSpec chain;
     FScoreSpec fscore;
+    InterpSpec interp;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -239,6 +251,7 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::TScore ? it.tscore.out
            : it.kind == Item::Kind::Chain  ? it.chain.out
            : it.kind == Item::Kind::FScore ? it.fscore.out
+           : it.kind == Item::Kind::Interp ? it.interp.out
                                            : it.bg.first_out();
 }
 
@@ -642,6 +655,31 @@ inline bool parse_fscore(std::istringstream& tok, FScoreSpec& q)
     return !q.out.empty();
 }
 
+inline bool parse_interp(std::istringstream& tok, InterpSpec& q)
+{
+    std::string k, v, steps, n, src;
+    if (!(tok >> q.a >> q.b >> q.fwd) || split_token(q.a, k, v) || split_token(q.b, k, v) || split_token(q.fwd, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        std::string* const dst = field_of({{"s", &steps}, {"n", &n}, {"bwd", &q.bwd}, {"src", &src}, {"out", &q.out}}, k);
+        if (!dst || !dst->empty()) return false;
+        *dst = v;
+    }
+    unsigned long long x = 0;
+    if (steps.empty() || q.out.empty() || !parse_uint(n, 0xffffffffull, x) || (!src.empty() && src != "1")) return false;
+    q.n = (unsigned)x;
+    q.src = !src.empty();
+    steps += ',';
+    std::string one;
+    for (char c : steps) {                 // decimal steps, comma separated, strictly ascending, 1 <= step < n
+        if (c != ',') { one += c; continue; }
+        if (!parse_uint(one, 0xffffffffull, x) || x < 1 || x >= q.n || (!q.steps.empty() && x <= q.steps.back())) return false;
+        q.steps.push_back((unsigned)x);
+        one.clear();
+    }
+    return q.steps.size() <= ARAPFLOW_INTERP_MAX_TIMES;
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -651,7 +689,8 @@ inline Parsed parse_item(const std::string& line, Item& it)
     it.kind = first == "bg" ? Item::Kind::Bg : first == "layers" ? Item::Kind::Layers : first == "tex" ? Item::Kind::Tex
               : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : first == "light" ? Item::Kind::Light
               : first == "seg" ? Item::Kind::Seg : first == "score" ? Item::Kind::Score : first == "tscore" ? Item::Kind::TScore
-              : first == "chain" ? Item::Kind::Chain : first == "fscore" ? Item::Kind::FScore : Item::Kind::Solve;
+              : first == "chain" ? Item::Kind::Chain : first == "fscore" ? Item::Kind::FScore : first == "interp" ? Item::Kind::Interp
+              : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
@@ -664,10 +703,11 @@ inline Parsed parse_item(const std::string& line, Item& it)
     else if (it.kind == Item::Kind::TScore) p = parse_tscore(tok, it.tscore) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Chain) p = parse_chain(tok, it.chain) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::FScore) p = parse_fscore(tok, it.fscore) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::Interp) p = parse_interp(tok, it.interp) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
         const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line", "score line",
-                                    "tscore line", "chain line", "fscore line"};      // by Item::Kind
+                                    "tscore line", "chain line", "fscore line", "interp line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

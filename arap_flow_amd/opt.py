@@ -16,6 +16,7 @@
   frame_score      the PSNR / integer-SSIM table of estimated frames (ArapFlow_FrameScore)
   track_score      the TAP-Vid table of estimated tracks against a track file's (ArapFlow_TrackScore)
   chain_flows      estimated tracks from per-link flow estimates (ArapFlow_ChainFlows)
+  interp_frames    estimated in-between frames from a flow estimate, by splatting (ArapFlow_InterpFrames)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -904,6 +905,34 @@ def chain_flows(state, flows, points, bwd=None):
     r = _warp_call(state, "ChainFlows", (W, H, L), [(flows, np.float32), (bwd, np.float32), (P, None), (points, np.float32)],
                    [("pos", (L + 1, P, 2), torch.float32), ("occ", (L + 1, P), torch.uint8)])
     return r["pos"], r["occ"]
+
+
+def interp_frames(state, a, b, fwd, times, bwd=None, want_src=False):
+    """estimated in-between frames of a pair from a flow estimate, by flow splatting (ArapFlow_InterpFrames, DESIGN.md
+    "Frames from flows"): a, b u8[H,W,3], frame 1 and frame 2; fwd f32[H,W,2], the flow a -> b on a's pixels; bwd the same
+    shape or None, the flow b -> a on b's pixels; times: K of them, each in (0, 1) (numpy) -> out u8[K,H,W,3], or with
+    `want_src` (out, src u8[K,H,W]): 0 both frames, 1 a only, 2 b only, 3 neither, plus 4 where the flow came from the
+    hole fill, 255 a hole."""
+    a = np.ascontiguousarray(a, np.uint8)
+    b = np.ascontiguousarray(b, np.uint8)
+    fwd = np.ascontiguousarray(fwd, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3 or b.shape != a.shape:
+        raise ValueError("interp_frames: a and b [H,W,3] of one shape expected")
+    H, W = a.shape[:2]
+    if fwd.shape != (H, W, 2):
+        raise ValueError("interp_frames: fwd [H,W,2] of the frames' size expected")
+    if bwd is not None:
+        bwd = np.ascontiguousarray(bwd, np.float32)
+        if bwd.shape != fwd.shape:
+            raise ValueError("interp_frames: bwd of fwd's shape expected")
+    times = np.ascontiguousarray(times, np.float32).reshape(-1)
+    K = times.size
+    r = _warp_call(state, "InterpFrames", (W, H),
+                   [(a, np.uint8), (b, np.uint8), (fwd, np.float32), (bwd, np.float32), (K, None),
+                    (times.ctypes.data_as(C.POINTER(C.c_float)), None)],
+                   [("out", (K, H, W, 3), torch.uint8), ("src", (K, H, W) if want_src else None, torch.uint8)],
+                   ("InterpScratchBytes", (W, H, K)))
+    return (r["out"], r["src"]) if want_src else r["out"]
 
 
 FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")

@@ -26,6 +26,7 @@ functions that tests/golden/host/ pins with hand-computed cases:
   format_track_score, parse_track_score_file, track_score_summary, add_track_scores    a track score table as text, as metrics, pooled
   FScoreLine, parse_fscore, fscore_line, run_fscore    the `fscore` line: the PSNR / SSIM table of an estimated frame (addition)
   format_frame_score, parse_frame_score_file, frame_score_summary, add_frame_scores    a frame score table as text, as metrics, pooled
+  InterpLine, parse_interp, interp_line, run_interp    the `interp` line: in-between frames from a flow estimate (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
   match_ok, valid_cnstr, filter_matches  para_gen.py:216-223,468-482
@@ -85,6 +86,8 @@ FSCORE_KEYS = ("occ", "dist", "skip", "obj")
 # the rows and the fields of a frame score table in its order (opt.FSCORE_ROWS, opt.FSCORE_FIELDS; ArapFlow_FrameScore)
 FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")
 FSCORE_FIELDS = ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")
+INTERP_WORD = "interp"
+INTERP_MAX_TIMES = 32        # ARAPFLOW_INTERP_MAX_TIMES of include/arap_opt.h
 TSCORE_WORD = "tscore"
 CHAIN_WORD = "chain"
 TSCORE_MAX_FRAMES = 64       # ARAPFLOW_TSCORE_MAX_FRAMES of include/arap_opt.h
@@ -1327,12 +1330,88 @@ def run_fscore(state, spec):
     return table
 
 
+class InterpLine(NamedTuple):
+    """an `interp` line (DESIGN.md "Frames from flows"), recognised by its first word: the in-between frames of a pair
+    from a flow estimate
+        interp A.png B.png FWD.flo s=I1,I2,.. n=N [bwd=BWD.flo] [src=1] out=PREFIX
+    A, B: frame 1 and frame 2; FWD: the estimated flow A -> B; bwd: the estimated flow B -> A; the times are (float)I /
+    (float)N, the ramp's own alpha_i: 1 to INTERP_MAX_TIMES steps, distinct and ascending, 1 <= I < N; written:
+    PREFIX_sII.png (mid_files' naming) and, with src=1, PREFIX_sII_src.png, the source map.  Anything else -- an unknown
+    or repeated key, an empty value, no s=, n= or out=, fewer than three paths -- is an error."""
+    a: str
+    b: str
+    fwd: str
+    steps: tuple
+    n: int
+    bwd: str
+    src: bool
+    out: str
+
+
+def parse_interp(tokens):
+    if len(tokens) < 4 or tokens[0] != INTERP_WORD or any("=" in t for t in tokens[1:4]):
+        raise ValueError("interp line: two frame files and a flow file expected: %r" % " ".join(tokens))
+    got = {}
+    for t in tokens[4:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in ("s", "n", "bwd", "src", "out")) or k in got:
+            raise ValueError("interp line: bad or repeated token %r" % t)
+        got[k] = v
+    if "s" not in got or "n" not in got or "out" not in got:
+        raise ValueError("interp line without s=, n= or out=: %r" % " ".join(tokens))
+    n = int(got["n"]) if _UINT.match(got["n"]) and int(got["n"]) < 1 << 32 else 0
+    steps = tuple(int(v) if _UINT.match(v) else 0 for v in got["s"].split(","))
+    if not (1 <= len(steps) <= INTERP_MAX_TIMES and steps[0] >= 1 and steps[-1] < n and all(a < b for a, b in zip(steps, steps[1:]))):
+        raise ValueError("interp line: s=I1,I2,.. n=N with 1 <= I1 < I2 < .. < N, at most %d steps: %r" % (INTERP_MAX_TIMES, " ".join(tokens)))
+    if got.get("src", "1") != "1":
+        raise ValueError("interp line: src=1 or no src=: %r" % " ".join(tokens))
+    return InterpLine(tokens[1], tokens[2], tokens[3], steps, n, got.get("bwd", ""), "src" in got, got["out"])
+
+
+def interp_line(item):
+    """the inverse of parse_interp: s=, n=, bwd=, src=, out= in that order"""
+    return " ".join([INTERP_WORD, item.a, item.b, item.fwd, "s=" + ",".join("%d" % i for i in item.steps), "n=%d" % item.n] +
+                    (["bwd=" + item.bwd] if item.bwd else []) + (["src=1"] if item.src else []) + ["out=" + item.out])
+
+
+def interp_files(prefix, step):
+    """the files of an `interp` line for ramp step `step`: the frame (mid_files' name) and its source map"""
+    return dict(rgb=mid_files(prefix, step)["rgb"], src="%s_s%02d_src.png" % (prefix, step))
+
+
+def interp_times(steps, n):
+    """the times of an interp line, float32: (float)I / (float)N"""
+    return np.array([np.float32(i) / np.float32(n) for i in steps], np.float32)
+
+
+def run_interp(state, spec):
+    """one `interp` line: read the two frames and the flows, one opt.interp_frames, write a frame (and a source map) per step"""
+    from . import opt
+    a, b = load_rgb(spec.a), load_rgb(spec.b)
+    if a.shape != b.shape:
+        raise ValueError("interp line: %s and %s differ in size" % (spec.a, spec.b))
+    fwd = flo.flow_read(spec.fwd)
+    bwd = flo.flow_read(spec.bwd) if spec.bwd else None
+    for path, f in ((spec.fwd, fwd), (spec.bwd, bwd)):
+        if f is not None and f.shape[:2] != a.shape[:2]:
+            raise ValueError("interp line: %s differs in size from %s" % (path, spec.a))
+    out, src = opt.interp_frames(state, a, b, fwd, interp_times(spec.steps, spec.n), bwd=bwd, want_src=True)
+    for k, i in enumerate(spec.steps):
+        names = interp_files(spec.out, i)
+        Image.fromarray(out[k]).save(names["rgb"])
+        if spec.src:
+            Image.fromarray(src[k], "L").save(names["src"])
+    return out, src
+
+
 def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
     BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`, a
     LightLine when it is `light`, a SegLine when it is `seg`, a ScoreLine when it is `score`, a TScoreLine when it is
-    `tscore`, a ChainLine when it is `chain`, an FScoreLine when it is `fscore`"""
+    `tscore`, a ChainLine when it is `chain`, an FScoreLine when it is `fscore`, an InterpLine when it is `interp`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == INTERP_WORD:
+        return parse_interp(tok)
     if tok and tok[0] == FSCORE_WORD:
         return parse_fscore(tok)
     if tok and tok[0] == TSCORE_WORD:
@@ -1384,14 +1463,16 @@ def format_line(item):
         return chain_line(item)
     if isinstance(item, FScoreLine):
         return fscore_line(item)
+    if isinstance(item, InterpLine):
+        return interp_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
 
 
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
     first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file, a score,
-    tscore, chain or fscore line's out= file"""
-    if isinstance(item, (TrkLine, ScoreLine, TScoreLine, ChainLine, FScoreLine)):
+    tscore, chain or fscore line's out= file, an interp line's out= prefix"""
+    if isinstance(item, (TrkLine, ScoreLine, TScoreLine, ChainLine, FScoreLine, InterpLine)):
         return item.out
     if isinstance(item, (BlurLine, LightLine, SegLine)):
         return next(iter(item.out.values()))

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Score estimated frames against a generated dataset (DESIGN.md "Frame scoring").
 
-    frame_score_gen.py --data OUT --est EST_ROOT [--full] [--baseline blend] [--gpu 0 1 ..] [--narap N] [--arap_bin CMD]
-                       [--worker auto|serve|batch]
+    frame_score_gen.py --data OUT --est EST_ROOT [--from_flows] [--full] [--baseline blend] [--gpu 0 1 ..] [--narap N]
+                       [--arap_bin CMD] [--worker auto|serve|batch]
 
 OUT is a tree para_gen.py wrote.  Every ground-truth frame is scored against the file of the same name relative to OUT
 under EST_ROOT (OUT/Mid/a/00003_s09.png against EST_ROOT/Mid/a/00003_s09.png) by one `fscore` line of arap_deform
@@ -25,6 +25,17 @@ in the right grid but non-zero on the object, the opposite of obj=, so the obj a
                      pair's two end frames OUT/inpRGB/<seq>/<frame>.png and OUT/wRGB/<seq>/<frame>.png is written, in
                      numpy, to OUT/FramesEst/<same relative name>, and that tree is scored: the figure an interpolator has
                      to beat.  (A frame 2 has no such estimate and is listed as missing.)
+
+  --from_flows       (with --est, not with --baseline) EST_ROOT holds flow estimates, not frames: for every pair that has
+                     in-between ground truth one `interp` line (pipeline.InterpLine, DESIGN.md "Frames from flows") on the
+                     same workers turns OUT/inpRGB/<seq>/<frame>.png, OUT/wRGB/<seq>/<frame>.png and
+                     EST_ROOT/Flow/<seq>/<frame>.flo -- with bwd=EST_ROOT/FlowBwd/<seq>/<frame>.flo where that file
+                     exists; with --full FlowFull and FlowBwdFull, between the same two frames, which --mid_bg composites
+                     -- into OUT/FramesEst/<Mid|MidFull>/<seq>/<frame>_sNN.png, at the steps of the _sNN names present
+                     with n = para_gen.NUM_ITER, and that tree is scored exactly as --baseline blend's is: the Middlebury
+                     interpolation error of a flow method.  A pair without a flow estimate is listed as missing, and so is
+                     every frame 2.  --est OUT scores the dataset's own flow files: the oracle-flow ceiling, beside the
+                     blend floor.
 
 Written: OUT/FrameScore/<seq>/<name>.txt per frame (pipeline.format_frame_score), their exact pooled table
 OUT/frame_score.txt (pipeline.add_frame_scores) and OUT/frame_score_missing.list, the ground-truth frames without an
@@ -88,12 +99,34 @@ def write_blend(data, full):
         Image.fromarray(((a + b + 1) >> 1).astype(np.uint8)).save(out)
 
 
-def score_items(data, est_root, full):
-    """-> ([FScoreLine], [ground-truth files without an estimate])"""
+def interp_items(data, est_root, full):
+    """--from_flows: {output prefix: InterpLine} of every pair with in-between ground truth, both end frames and a flow
+    estimate; a prefix is OUT/FramesEst/<Mid|MidFull>/<seq>/<frame>"""
+    steps = {}
+    for top, seq, name, stem in ground_truth(data, full):
+        if stem is not None:
+            steps.setdefault((top, seq, stem), []).append(int(name[-2:]))
+    items = {}
+    for (top, seq, stem), idx in sorted(steps.items()):
+        a, b = (osp.join(data, d, seq, stem + ".png") for d in (para_gen.color_dir, para_gen.wrgb_dir))
+        fwd = osp.join(est_root, para_gen.full_dir if full else para_gen.flow_dir, seq, stem + ".flo")
+        bwd = osp.join(est_root, para_gen.bwd_full_dir if full else para_gen.bwd_dir, seq, stem + ".flo")
+        idx = tuple(sorted(set(idx)))
+        if not all(osp.exists(f) for f in (a, b, fwd)) or idx[0] < 1 or idx[-1] >= para_gen.NUM_ITER:
+            continue
+        prefix = osp.join(data, EST_DIR, top, seq, stem)
+        os.makedirs(osp.dirname(prefix), exist_ok=True)
+        items[prefix] = pipeline.InterpLine(a, b, fwd, idx, para_gen.NUM_ITER, bwd if osp.exists(bwd) else "", False, prefix)
+    return items
+
+
+def score_items(data, est_root, full, promised=None):
+    """-> ([FScoreLine], [ground-truth files without an estimate]); `promised`: the estimates an interp line is about to
+    write -- given, only those count as there (--from_flows: a file an earlier run left in OUT/FramesEst is no estimate)"""
     items, missing = [], []
     for top, seq, name, _ in ground_truth(data, full):
         gt, est = osp.join(data, top, seq, name + ".png"), osp.join(est_root, top, seq, name + ".png")
-        if not osp.exists(est):
+        if (est not in promised) if promised is not None else not osp.exists(est):
             missing.append(gt)
             continue
         out = osp.join(data, "FrameScore", seq, name + ".txt")
@@ -116,20 +149,36 @@ def main(flags):
     data = osp.abspath(flags.data)
     if flags.baseline:
         write_blend(data, flags.full)
-    items, missing = score_items(data, osp.join(data, EST_DIR) if flags.baseline else osp.abspath(flags.est), flags.full)
+    interp, promised = {}, None
+    if flags.from_flows:
+        interp = interp_items(data, osp.abspath(flags.est), flags.full)
+        promised = {pipeline.interp_files(prefix, i)["rgb"]: prefix for prefix, it in interp.items() for i in it.steps}
+    items, missing = score_items(data, osp.join(data, EST_DIR) if flags.baseline or flags.from_flows else osp.abspath(flags.est),
+                                 flags.full, promised)
+    after = {}                                  # an interp line's prefix -> the lines that score its frames
+    for it in items:
+        if promised is not None:
+            after.setdefault(promised[it.est], []).append(it)
     done, lock = [], threading.Lock()
+    workers = None
 
     def on_done(path):
         with lock:
             done.append(path)
+        for it in after.get(path, ()):
+            workers.put_owed(pipeline.format_line(it))
     if items:
         serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == para_gen.CPP_BIN)
         workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, serve, on_done)
-        for it in items:
+        for prefix, owed in after.items():
+            for _ in owed:
+                workers.owe()
+            workers.put(pipeline.format_line(interp[prefix]))
+        for it in items if promised is None else ():
             workers.put(pipeline.format_line(it))
         workers.close()
         workers.join()
-    assert sorted(done) == sorted(it.out for it in items), "an fscore line was not reported done"
+    assert sorted(done) == sorted([it.out for it in items] + list(after)), "a line was not reported done"
     tables = [pipeline.parse_frame_score_file(open(it.out).read()) for it in items]
     pooled = pipeline.add_frame_scores(tables)
     with open(osp.join(data, "frame_score.txt"), "w") as f:
@@ -151,6 +200,7 @@ def parse(argv=None):
     parser.add_argument("--est", help="the estimates: EST/<Mid|wRGB|MidFull>/<seq>/<name>.png, named like the dataset's frames")
     parser.add_argument("--full", action="store_true", help="score the in-between frames of MidFull instead of Mid and wRGB")
     parser.add_argument("--baseline", choices=["blend"], help="score the rounded mean of a pair's end frames instead of --est")
+    parser.add_argument("--from_flows", action="store_true", help="--est holds flow estimates: splat them into OUT/FramesEst first")
     parser.add_argument("--gpu", nargs="*", type=int, default=[0], help="GPU ids, default 0")
     parser.add_argument("--narap", type=int, default=64, help="lines one GPU holds at a time")
     parser.add_argument("--arap_bin", default=para_gen.CPP_BIN if osp.exists(para_gen.CPP_BIN) else
@@ -159,6 +209,8 @@ def parse(argv=None):
     flags = parser.parse_args(argv)
     if (flags.est is None) == (flags.baseline is None):
         parser.error("one of --est and --baseline is needed")
+    if flags.from_flows and flags.est is None:
+        parser.error("--from_flows needs --est, the root of the flow estimates, and excludes --baseline")
     if not para_gen.own_arap_bin(flags.arap_bin):
         parser.error("--arap_bin: an `fscore` line needs this repository's driver")
     return flags

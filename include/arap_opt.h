@@ -731,6 +731,58 @@ int ArapFlow_ChainFlows(Opt_State* state, unsigned W, unsigned H, unsigned L, co
 int ArapFlow_FrameScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* ref, const void* est,
                         const void* occ, const void* dist, const void* skip, const void* obj, void* table, void* ssim);
 
+/* Frames from flows (DESIGN.md "Frames from flows"): the in-between frames of a pair at K times from an estimated flow,
+ * by flow splatting (Baker et al., IJCV 2011, section 3.3.2: splat the flow to time t, fill small holes, fetch both frames
+ * along the flow with an occlusion test, blend), in integers wherever a result is stored.  On DEVICE buffers, but for
+ * `times`.
+ *   A, B   uint8[H][W][3], frame 1 and frame 2;  fwd float32[H][W][2], the estimated flow A -> B on A's pixels;
+ *   bwd    the same shape or NULL, the estimated flow B -> A on B's pixels;
+ *   times  float32[K], a HOST array, 1 <= K <= ARAPFLOW_INTERP_MAX_TIMES, each finite and 0 < t < 1.
+ * N = W * H < 2^31.  in_frame(p): 0 <= p.x <= W - 1 and 0 <= p.y <= H - 1, false on NaN; S(F, a): the bilinear flow
+ * sample of ArapFlow_ChainFlows.  A flow value is valid when both components are finite and below 1e9 in magnitude.
+ * s = 1.0f - t; tq = (int)(t * 256.f + 0.5f); every fmaf below is one fused operation, every other operator one float32
+ * operation; nearest(v, hi) = min((int)floorf(v + .5f), hi) (the clamp acts only beyond 2^23).
+ * Step 1, splat.  One 64-bit key per pixel and time, cleared to all ones, updated with a minimum.
+ *   Side A, pixel x = (i, j) with u = fwd[j][i] valid:  e = (i + u.x, j + u.y);  cost = 766 when !in_frame(e), else
+ *   cost = sum_c |A[x][c] - B[q][c]| with q = (nearest(e.x, W - 1), nearest(e.y, H - 1)); the cost does not depend on t.
+ *   For each time: p = (fmaf(t, u.x, (float)i), fmaf(t, u.y, (float)j)); nothing is written when !in_frame(p); else
+ *   r = (nearest(p.x, W - 1), nearest(p.y, H - 1)) and key[k][r] = min(key[k][r], cost << 32 | 0 << 31 | (j * W + i)).
+ *   Side B, only with bwd, pixel y = (i, j) with g = bwd[j][i] valid: the cost the same way, |B[y][c] - A[q][c]| at
+ *   e = y + g;  p = (fmaf(s, g.x, (float)i), fmaf(s, g.y, (float)j));  the key carries a 1 in bit 31 and stands for the
+ *   flow u = -g.
+ *   The winner is the lowest cost; on equal cost side A wins, within a side the lowest source index.
+ * Step 2, hole fill.  A pixel without a key takes the key of the nearest keyed pixel of its own row at distance
+ *   d = 1 .. ARAPFLOW_INTERP_FILL, the left one at equal d; if there is none the pixel is a hole.
+ * Step 3, colour at pixel r = (x, y).  The integer bilinear colour sample C(I, a), a inside the frame:
+ *   x0 = floorf(a.x), x1 = min(x0 + 1, W - 1), wx = (int)((a.x - x0) * 256.f + .5f), the same in y;
+ *   C_c = (256-wx)(256-wy) I[y0][x0][c] + wx (256-wy) I[y0][x1][c] + (256-wx) wy I[y1][x0][c] + wx wy I[y1][x1][c].
+ *   A hole: out_c = ((256 - tq) * A[r][c] + tq * B[r][c] + 128) >> 8, src = 255.
+ *   Any other pixel, u the flow its key stands for (fwd[index], or -bwd[index] with bit 31):
+ *     a0 = (fmaf(-t, u.x, (float)x), fmaf(-t, u.y, (float)y));  b1 = (fmaf(s, u.x, (float)x), fmaf(s, u.y, (float)y))
+ *     okA = in_frame(a0) and, with f0 = S(fwd, a0), d = f0 - u:
+ *           d.x * d.x + d.y * d.y <= fmaf(0.01f, (f0.x * f0.x + f0.y * f0.y) + (u.x * u.x + u.y * u.y), 0.5f)
+ *     okB = in_frame(b1) and, where bwd is given, with g1 = S(bwd, b1), d = u + g1:
+ *           d.x * d.x + d.y * d.y <= fmaf(0.01f, (u.x * u.x + u.y * u.y) + (g1.x * g1.x + g1.y * g1.y), 0.5f)
+ *     (both tests false on NaN)
+ *     both:     out_c = ((256 - tq) * C_c(A, a0) + tq * C_c(B, b1) + 2^23) >> 24        (fits 32 bits)
+ *     one:      out_c = (C_c + 32768) >> 16 of that side
+ *     neither:  the hole formula
+ *     src = 0 both, 1 A only, 2 B only, 3 neither, plus 4 when the key came from the hole fill.
+ *   out      uint8[K][H][W][3]
+ *   src      uint8[K][H][W] or NULL
+ *   scratch  ArapFlow_InterpScratchBytes(W, H, K) bytes, the caller's: the K * N keys, aligned to 256 bytes (0 for sizes
+ *            the call refuses)
+ * Two kernels behind one clear of the keys, each launched once for all K times; the only atomics are the 64-bit integer
+ * minima on the keys, so two runs give identical bytes.  Nothing is launched or allocated unless the call is made.
+ * Asynchronous on the state's stream.  Returns 0; -1, and nothing is launched or written, on bad arguments: a null state,
+ * A, B, fwd, times, out or scratch, K = 0 or K > 32, a time that is not finite or not in (0, 1), W * H = 0 or >= 2^31,
+ * K * W * H >= 2^31, an output or the scratch overlapping an input or each other; else a HIP error code. */
+#define ARAPFLOW_INTERP_MAX_TIMES 32
+#define ARAPFLOW_INTERP_FILL 16
+uint64_t ArapFlow_InterpScratchBytes(unsigned W, unsigned H, unsigned K);
+int ArapFlow_InterpFrames(Opt_State* state, unsigned W, unsigned H, const void* A, const void* B, const void* fwd,
+                          const void* bwd, unsigned K, const float* times, void* out, void* src, void* scratch);
+
 /* Fold diagnostics (DESIGN.md "Fold diagnostics"; off by default, and then nothing is allocated or launched): how much
  * of a warped mesh inverted or went non-finite, and which frame-1 pixels carry a flow value that is no valid
  * correspondence.  With P(v) the warp position of vertex v (the solved Offset, or (x, y) + flow) and the rasterised
