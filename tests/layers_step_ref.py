@@ -127,7 +127,9 @@ def layers_step_brute(masks, fields_a, fields_b):
         xs, ys = [c[0] for c in p], [c[1] for c in p]
         if any(np.isnan(v) for v in xs + ys):
             return False
-        xa, ya = max(0, min(W, int(np.floor(min(xs))))), max(0, min(H, int(np.floor(min(ys)))))
+        mnx, mny = np.floor(min(xs)), np.floor(min(ys))      # clamped as floats first: +-Inf has no int
+        xa = 0 if mnx < 0 else W if mnx > W else int(mnx)
+        ya = 0 if mny < 0 else H if mny > H else int(mny)
         return xa <= x < W and x <= np.ceil(max(xs)) and ya <= y < H and y <= np.ceil(max(ys))
 
     tris = []                                     # (layer, index, [corner (gx, gy)]) in (layer, index) order

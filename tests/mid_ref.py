@@ -71,7 +71,9 @@ def step_brute(mask, field_a, field_b):
         xs, ys = [c[0] for c in p], [c[1] for c in p]
         if any(np.isnan(v) for v in xs + ys):
             return False
-        xa, ya = max(0, min(W, int(np.floor(min(xs))))), max(0, min(H, int(np.floor(min(ys)))))
+        mnx, mny = np.floor(min(xs)), np.floor(min(ys))      # clamped as floats first: +-Inf has no int
+        xa = 0 if mnx < 0 else W if mnx > W else int(mnx)
+        ya = 0 if mny < 0 else H if mny > H else int(mny)
         return xa <= x < W and x <= np.ceil(max(xs)) and ya <= y < H and y <= np.ceil(max(ys))
 
     out = np.zeros((H, W, 2), F)

@@ -125,7 +125,9 @@ def layers_brute(rgb, masks, fields):
         xs, ys = [p[0] for p in (p0, p1, p2)], [p[1] for p in (p0, p1, p2)]
         if any(np.isnan(a) for a in xs + ys):
             return False
-        xa, ya = max(0, min(W, int(np.floor(min(xs))))), max(0, min(H, int(np.floor(min(ys)))))
+        mnx, mny = np.floor(min(xs)), np.floor(min(ys))      # clamped as floats first: +-Inf has no int
+        xa = 0 if mnx < 0 else W if mnx > W else int(mnx)
+        ya = 0 if mny < 0 else H if mny > H else int(mny)
         return xa <= x < W and x <= np.ceil(max(xs)) and ya <= y < H and y <= np.ceil(max(ys))
 
     tris = []                                     # (layer, index, [corner (gx, gy)]) in (layer, index) order
