@@ -174,6 +174,11 @@ void Opt_SetSolverParameter(Opt_State*, Opt_Plan* plan, const char* name, void* 
     SolverParameters& sp = plan->sp;
 #define SETI(f) if (strcmp(name, #f) == 0) { sp.f = *(int*)value; return; }
 #define SETF(f) if (strcmp(name, #f) == 0) { sp.f = *(float*)value; return; }
+    if (strcmp(name, "residual_reset_period") == 0 && *(int*)value < 1) {    // the host loop takes (l + 1) modulo it
+        if (plan->st->verbosity > 0)
+            printf("Warning: residual_reset_period %d is below 1, keeping %d\n", *(int*)value, sp.residual_reset_period);
+        return;
+    }
     SETI(nIterations) SETI(lIterations) SETI(residual_reset_period)
     SETF(min_relative_decrease) SETF(min_trust_region_radius) SETF(max_trust_region_radius)
     SETF(q_tolerance) SETF(function_tolerance) SETF(trust_region_radius) SETF(radius_decrease_factor)
@@ -213,6 +218,16 @@ double Opt_ProblemCurrentCost(Opt_State*, Opt_Plan* plan)
 // C ABI, part 2
 // ---------------------------------------------------------------------------------------------
 const char* ArapFlow_Version(void) { return ARAPOPT_VERSION; }
+
+int ArapFlow_LMState(Opt_Plan* plan, float* radius, float* decrease, int* pcg_iterations_last_step, int* outcome_last_step)
+{
+    if (!plan || plan->kind != 1) return -1;
+    if (radius) *radius = plan->lm_radius;
+    if (decrease) *decrease = plan->lm_decrease;
+    if (pcg_iterations_last_step) *pcg_iterations_last_step = plan->lm_last_pcg;
+    if (outcome_last_step) *outcome_last_step = plan->lm_last_outcome;
+    return 0;
+}
 
 void ArapFlow_SetResident(Opt_State* state, int on)
 {

@@ -4,7 +4,8 @@
 // PCGStep2_2ndHalf :491-535,570-575, computeModelCost :665-678 (o.t:2180-2201).  applyJTJ + CtC*P and the q term of
 // PCGStep2 live in k_pcg_a / k_pcg_b behind PlanDev::lm; the edge term and the raw diagonal are arap_pcg.h's.  The application never selects this kind
 // (CombinedSolverBase.h:75-77) and the reference holds no LM output, so its parity is pinned to the CPU
-// restatement only.  Host loop: host_lm.h:plan_step_lm.
+// restatement, bit for bit per step, and the restatement to an independent float64 twin (DESIGN.md "LM: pins and
+// branches").  Host loop: host_lm.h:plan_step_lm.
 #pragma once
 #include "arap_kernels.h"
 

@@ -43,6 +43,8 @@ static void plan_init_lm(Opt_Plan* p)
     p->lm_radius = p->sp.trust_region_radius;                 // init copies the solver parameters (:996-1001)
     p->lm_decrease = p->sp.radius_decrease_factor;
     p->lm_done = false;
+    p->lm_last_pcg = 0;
+    p->lm_last_outcome = -1;
     HC(hipMemsetAsync(p->pd.costred, 0, (size_t)p->pd.ncost * NSHARD * sizeof(double), p->st->stream));
     hipLaunchKernelGGL(k_cost, p->grid(), p->blk(), 0, p->st->stream, p->pd, 0);
     p->lm_prev_cost = plan_read_cost(p, 0, 0);
@@ -66,6 +68,7 @@ static int plan_step_lm(Opt_Plan* p)
     hipLaunchKernelGGL(k_lm_prepare, g, b, 0, s, p->pd, p->lm_radius, sp.min_lm_diagonal, sp.max_lm_diagonal,
                        sp.nIter == 0 ? 1 : 0);
     float Q0 = (float)plan_read_shards(p, p->pd.lmred);
+    p->lm_last_pcg = 0;
     for (int l = 0; l < L; ++l) {
         hipLaunchKernelGGL(k_pcg_a, g, b, 0, s, p->pd, l);
         if (((l + 1) % sp.residual_reset_period) == 0) {
@@ -78,6 +81,7 @@ static int plan_step_lm(Opt_Plan* p)
         }
         const float Q1 = (float)plan_read_shards(p, p->pd.lmred + (size_t)(l + 1) * NSHARD);
         const float zeta = (float)(l + 1) * (Q1 - Q0) / Q1;
+        p->lm_last_pcg = l + 1;
         if (zeta < sp.q_tolerance) break;
         Q0 = Q1;
     }
@@ -97,6 +101,7 @@ static int plan_step_lm(Opt_Plan* p)
         if (cost_change <= (float)p->lm_prev_cost * sp.function_tolerance) {
             if (st->verbosity > 0) printf("\nFunction tolerance reached, exiting\n");
             p->lm_done = true;
+            p->lm_last_outcome = ARAPFLOW_LM_FUNCTION_TOLERANCE;
             return 0;
         }
         const double step_quality = relative_decrease;
@@ -105,6 +110,7 @@ static int plan_step_lm(Opt_Plan* p)
         p->lm_radius = (float)fmin((double)p->lm_radius, (double)sp.max_trust_region_radius);
         p->lm_decrease = 2.0f;
         p->lm_prev_cost = newCost;
+        p->lm_last_outcome = ARAPFLOW_LM_ACCEPTED;
     } else {
         HC(hipMemcpyAsync(sl.O, p->prevO, N * sizeof(float2), hipMemcpyDeviceToDevice, s));   // revertUpdate
         HC(hipMemcpyAsync(sl.A, p->prevA, N * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -113,8 +119,10 @@ static int plan_step_lm(Opt_Plan* p)
         if (p->lm_radius <= sp.min_trust_region_radius) {
             if (st->verbosity > 0) printf("\nTrust_region_radius is less than the min, exiting\n");
             p->lm_done = true;
+            p->lm_last_outcome = ARAPFLOW_LM_MIN_RADIUS;
             return 0;
         }
+        p->lm_last_outcome = ARAPFLOW_LM_REJECTED;
     }
     if (st->verbosity > 0) printf("cost: %f (trust_region_radius %g)\n", p->lm_prev_cost, p->lm_radius);
     p->sp.nIter += 1;

@@ -230,6 +230,7 @@ struct Opt_Plan {
     float lm_radius = 0.f, lm_decrease = 0.f;      // pd.parameters.trust_region_radius / radius_decrease_factor
     double lm_prev_cost = 0.0;
     bool lm_done = false;
+    int lm_last_pcg = 0, lm_last_outcome = -1;     // of the last step attempted since Init (ArapFlow_LMState)
 
     dim3 grid() const { return dim3(pd.tilesX, pd.tilesY, nb); }
     dim3 blk() const { return dim3(TILE_X, TILE_Y, 1); }

@@ -29,6 +29,7 @@ import torch
 from . import capi
 
 BUILTIN_PLAN = b"builtin:arap"
+LM_OUTCOMES = ("accepted", "rejected", "function_tolerance", "min_radius")      # ARAPFLOW_LM_* of include/arap_opt.h
 
 
 def _dev_ptr(t):
@@ -190,6 +191,15 @@ class OptSolver:
 
     def resident_launches(self):
         return int(self.lib.ArapFlow_PlanResidentLaunches(self.plan))
+
+    def lm_state(self):
+        """ArapFlow_LMState of an "LMGPU" plan: dict(radius, decrease: numpy float32, pcg_iterations: of the last step
+        attempted since Init, outcome: a name of LM_OUTCOMES, None before the first step)"""
+        r, d, n, o = C.c_float(), C.c_float(), C.c_int(), C.c_int()
+        if self.lib.ArapFlow_LMState(self.plan, C.byref(r), C.byref(d), C.byref(n), C.byref(o)) != 0:
+            raise ValueError("ArapFlow_LMState: not an LMGPU plan")
+        return dict(radius=np.float32(r.value), decrease=np.float32(d.value), pcg_iterations=n.value,
+                    outcome=LM_OUTCOMES[o.value] if o.value >= 0 else None)
 
     def close(self):
         if self.plan:

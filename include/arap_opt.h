@@ -70,7 +70,8 @@ void Opt_PlanFree(Opt_State* state, Opt_Plan* plan);
 
 /* Opt.h:51.  `value` points to an int for "nIterations", "lIterations", "residual_reset_period"
  * and to a float for the nine LM parameters (solverGPUGaussNewton.t:148-163), which only "LMGPU" plans read.
- * Unknown names print a warning (:1220). */
+ * Unknown names print a warning (:1220).  A "residual_reset_period" below 1 is not stored (the step takes the PCG
+ * iteration number modulo it): the plan keeps its previous value, with a warning when verbose. */
 void Opt_SetSolverParameter(Opt_State* state, Opt_Plan* plan, const char* name, void* value);
 
 /* Opt.h:56-66.  problemparams is indexed by the plan's declared indices (arap_plan.t:2-8,
@@ -283,6 +284,13 @@ int ArapFlow_ResidentTiles(const uint8_t* mask_red, unsigned W, unsigned H, int 
  * lets the caller change them in between, Opt.h:58-66): new contents or swapped buffers are honoured.  Counts the
  * resident launches executed for this plan. */
 uint64_t ArapFlow_PlanResidentLaunches(Opt_Plan* plan);
+/* Trust-region state of an "LMGPU" plan after the last Init / Step (read-only; any pointer may be NULL): the radius and
+ * the radius decrease factor the next step starts from, the PCG iterations the last step attempted since Init ran
+ * before its zeta break (0 before the first step) and how that step ended (-1 before the first step).  A Step that
+ * returns 0 because nIterations steps have been taken attempts nothing and leaves all four as they were.
+ * Returns 0, or -1 for a NULL or Gauss-Newton plan. */
+enum { ARAPFLOW_LM_ACCEPTED = 0, ARAPFLOW_LM_REJECTED = 1, ARAPFLOW_LM_FUNCTION_TOLERANCE = 2, ARAPFLOW_LM_MIN_RADIUS = 3 };
+int ArapFlow_LMState(Opt_Plan* plan, float* radius, float* decrease, int* pcg_iterations_last_step, int* outcome_last_step);
 /* The resident kernel needs its 512 workgroups co-resident.  If a launch gives up at a bounded group wait (e.g.
  * another process is using the GPU), the step's update is skipped on the device, the work is redone on the
  * two-kernel path (same results) and the resident path pauses for the next 8 solve calls (doubling with every

@@ -441,10 +441,19 @@ double FN(oracle_solve)(int W, int H, REAL *O, REAL *A, const REAL *U, const REA
  * (o.t:2076-2082), PCGStep2 with q :477-482, residual reset :491-535 (PCGStep2_1stHalf, computeAdelta,
  * PCGStep2_2ndHalf), zeta break :1093-1102, model cost (o.t:2180-2201, :665-678), accept/reject and trust
  * region update :1119-1157.  The application never selects it (CombinedSolverBase.h:75-77) and the reference
- * holds no LM output: parity of this branch is pinned to this restatement only ("parity unpinned").
+ * holds no LM output: parity of this branch is pinned to this restatement, and this restatement to the float64 numpy
+ * loop of tests/lm_ref.py, which stands on oracle_evalJTF / oracle_applyJTJ / oracle_cost only (tests/test_lm_host.py).
  * lm[9] = min_relative_decrease, min_trust_region_radius, max_trust_region_radius, q_tolerance,
  *         function_tolerance, trust_region_radius, radius_decrease_factor, min_lm_diagonal, max_lm_diagonal
- * Returns the number of steps taken; costs[0..steps] as for the GN solve; *final_radius out. */
+ * Returns the number of steps taken; costs[0..steps] as for the GN solve; *final_radius out.
+ * trace (may be NULL): ORACLE_LM_TRACE doubles per step attempted (at most nIterations of them), in order
+ *   [0] PCG iterations run   [1] residual resets among them   [2] outcome: 0 accepted, 1 rejected,
+ *   2 function-tolerance exit, 3 minimum-radius exit   [3] radius and [4] decrease factor after the step
+ *   [5] CtC entries clamped low and [6] clamped high in this step's PCGFinalizeDiagonal
+ *   [7] arm of fmax(1/3, tmp_factor) an accepted step took: 1 = 1/3, 2 = tmp_factor, 0 = not accepted */
+#ifndef ORACLE_LM_TRACE
+#define ORACLE_LM_TRACE 8
+#endif
 static REAL FN(clampr)(REAL x, REAL lo, REAL hi) { REAL m = x > lo ? x : lo; return m < hi ? m : hi; }
 
 static void FN(apply_lm_at)(const FN(Prob) * pb, const REAL *cs, const REAL *CtC, const REAL *P, int x, int y, REAL out[3])
@@ -456,7 +465,7 @@ static void FN(apply_lm_at)(const FN(Prob) * pb, const REAL *cs, const REAL *CtC
 
 int FN(oracle_solve_lm)(int W, int H, REAL *O, REAL *A, const REAL *U, const REAL *C, const REAL *M, REAL wf,
                         REAL wr, int nIterations, int lIterations, int residual_reset_period, const REAL *lm,
-                        int trig, double *costs, REAL *final_radius)
+                        int trig, double *costs, REAL *final_radius, double *trace)
 {
     FN(Prob) pbv = {W, H, U, C, M, wf, wr, trig};
     const FN(Prob) *pb = &pbv;
@@ -477,6 +486,9 @@ int FN(oracle_solve_lm)(int W, int H, REAL *O, REAL *A, const REAL *U, const REA
         FN(fill_cs)(pb, A, pl->cs);
         double sd = 0.0, sq = 0.0;
         const REAL inv_radius = (REAL)1 / radius;
+        double *tr = trace ? trace + (size_t)ORACLE_LM_TRACE * nIter : NULL;
+        int pcg_run = 0, resets = 0, outcome, arm = 0;
+        long clamp_lo = 0, clamp_hi = 0;
         for (int y = 0; y < H; ++y)
             for (int x = 0; x < W; ++x) {
                 size_t i = (size_t)(x + W * y);
@@ -491,6 +503,8 @@ int FN(oracle_solve_lm)(int W, int H, REAL *O, REAL *A, const REAL *U, const REA
                     const REAL unclamped = d[k] * inv_radius;                  /* PCGComputeCtC */
                     const REAL mult = ((REAL)1 / SSq[3 * i + k]) / radius;     /* PCGFinalizeDiagonal */
                     const REAL ctc = FN(clampr)(unclamped, min_diag * mult, max_diag * mult);
+                    if (!(unclamped > min_diag * mult)) ++clamp_lo;
+                    else if (!(unclamped < max_diag * mult)) ++clamp_hi;
                     CtC[3 * i + k] = ctc;
                     pl->pre[3 * i + k] = (REAL)1 / FMA(radius, unclamped, ctc);
                     b[3 * i + k] = pl->r[3 * i + k];
@@ -514,7 +528,9 @@ int FN(oracle_solve_lm)(int W, int H, REAL *O, REAL *A, const REAL *U, const REA
             REAL alpha = 0;
             if (sigma > (REAL)0) alpha = rho / sigma;
             sd = 0.0; sq = 0.0;
+            ++pcg_run;
             if (((l + 1) % residual_reset_period) == 0) {
+                ++resets;
                 for (size_t i = 0; i < N; ++i) {                               /* PCGStep2_1stHalf */
                     if (!FN(act)(pb, (int)i)) continue;
                     for (int k = 0; k < 3; ++k) pl->delta[3 * i + k] = FMA(alpha, pl->p[3 * i + k], pl->delta[3 * i + k]);
@@ -599,19 +615,28 @@ int FN(oracle_solve_lm)(int W, int H, REAL *O, REAL *A, const REAL *U, const REA
         const REAL relative_decrease = cost_change / model_cost_change;
         ++steps;
         if (cost_change >= 0 && relative_decrease > min_rel) {
-            if (cost_change <= (REAL)prevCost * f_tol) { costs[steps] = prevCost; --steps; break; }   /* exits, cost stays */
-            const double sqv = (double)relative_decrease, tmp = 1.0 - pow(2.0 * sqv - 1.0, 3.0);
-            radius = (REAL)((double)radius / fmax(1.0 / 3.0, tmp));
-            radius = (REAL)fmin((double)radius, (double)max_rad);
-            dec = (REAL)2;
-            prevCost = newCost;
+            if (cost_change <= (REAL)prevCost * f_tol) outcome = 2;                /* exits, cost stays */
+            else {
+                const double sqv = (double)relative_decrease, tmp = 1.0 - pow(2.0 * sqv - 1.0, 3.0);
+                arm = (1.0 / 3.0 >= tmp) ? 1 : 2;
+                radius = (REAL)((double)radius / fmax(1.0 / 3.0, tmp));
+                radius = (REAL)fmin((double)radius, (double)max_rad);
+                dec = (REAL)2;
+                prevCost = newCost;
+                outcome = 0;
+            }
         } else {
             memcpy(O, pO, 2 * N * sizeof(REAL)); memcpy(A, pA, N * sizeof(REAL)); /* revertUpdate */
             radius = radius / dec;
             dec = (REAL)2 * dec;
-            if (radius <= min_rad) { costs[steps] = prevCost; --steps; break; }
+            outcome = radius <= min_rad ? 3 : 1;
+        }
+        if (tr) {
+            tr[0] = pcg_run; tr[1] = resets; tr[2] = outcome; tr[3] = (double)radius; tr[4] = (double)dec;
+            tr[5] = (double)clamp_lo; tr[6] = (double)clamp_hi; tr[7] = arm;
         }
         costs[steps] = prevCost;
+        if (outcome >= 2) { --steps; break; }
     }
     *final_radius = radius;
     FN(plan_free)(pl);

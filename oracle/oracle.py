@@ -134,9 +134,19 @@ LM_DEFAULTS = dict(min_relative_decrease=1e-3, min_trust_region_radius=1e-32, ma
                    min_lm_diagonal=1e-6, max_lm_diagonal=1e32)      # solverGPUGaussNewton.t:26-39
 
 
+LM_OUTCOMES = ("accepted", "rejected", "function_tolerance", "min_radius")     # codes 0..3 of a trace record
+
+
 def solve_lm(O, A, U, Cn, M, wf, wr, nIterations, lIterations, residual_reset_period=10, dtype=np.float32, trig=1,
-             **lm):
-    """One Opt_ProblemSolve with solver kind "LMGPU".  Returns (O, A, costs[0..steps], steps, final radius)."""
+             trace=None, **lm):
+    """One Opt_ProblemSolve with solver kind "LMGPU".  Returns (O, A, costs[0..steps], steps, final radius).
+    trace: a list that receives one dict per step attempted (pcg_iterations, resets, outcome -- a name of
+    LM_OUTCOMES --, radius and decrease after the step, clamped_low / clamped_high CtC entries, arm of
+    fmax(1/3, tmp_factor): "third", "tmp" or None when the step was not accepted)."""
+    if int(residual_reset_period) < 1:
+        raise ValueError("residual_reset_period must be at least 1")
+    if set(lm) - set(LM_DEFAULTS):
+        raise TypeError("unknown LM parameter(s): %s" % sorted(set(lm) - set(LM_DEFAULTS)))
     H, W = A.shape
     O, A, U, Cn, M = _prep(dtype, O, A, U, Cn, M)
     O, A = O.copy(), A.copy()
@@ -146,11 +156,17 @@ def solve_lm(O, A, U, Cn, M, wf, wr, nIterations, lIterations, residual_reset_pe
     lmv = np.asarray([pars[k] for k in order], dtype)
     costs = np.zeros(nIterations + 2, np.float64)
     rad = np.zeros(1, dtype)
+    rec = np.full((max(nIterations, 0), 8), -1.0, np.float64) if trace is not None else None
     f = getattr(lib(), "oracle_solve_lm" + _suf(dtype))
     f.restype = C.c_int
     steps = f(C.c_int(W), C.c_int(H), _p(O), _p(A), _p(U), _p(Cn), _p(M), _ct(dtype)(wf), _ct(dtype)(wr),
               C.c_int(nIterations), C.c_int(lIterations), C.c_int(residual_reset_period), _p(lmv), C.c_int(trig),
-              _p(costs), _p(rad))
+              _p(costs), _p(rad), _p(rec) if rec is not None else None)
+    if rec is not None:
+        for r in rec[rec[:, 2] >= 0]:
+            trace.append(dict(pcg_iterations=int(r[0]), resets=int(r[1]), outcome=LM_OUTCOMES[int(r[2])],
+                              radius=float(r[3]), decrease=float(r[4]), clamped_low=int(r[5]), clamped_high=int(r[6]),
+                              arm=(None, "third", "tmp")[int(r[7])]))
     return O, A, costs[:steps + 1], steps, float(rad[0])
 
 

@@ -367,7 +367,8 @@ def test_drop_in_api_takes_resident_kernel_only_for_grid_urshape(gpu_state, orac
 def test_LM_solver_kind_vs_oracle(gpu_state, oracle, W, H, nIter, lIter, radius):
     """Solver kind "LMGPU"  through Opt_ProblemSolve vs the CPU restatement of the same branch:
     trust-region bookkeeping (accept / reject / revert), CtC, model cost, zeta break, residual reset every 10th
-    iteration.  The reference holds no LM output, so this parity is pinned to the restatement only."""
+    iteration.  Bit for bit: Offset, Angle and cost.  The reference holds no LM output; the restatement is pinned to an
+    independent float64 twin in tests/test_lm_host.py, and tests/test_gpu_lm.py has the branch-by-branch cases."""
     pb = helpers.random_problem(W, H, seed=W * 3 + H, generic_urshape=(W % 2 == 0), ncons=max(6, W * H // 50))
     dev = {k: torch.from_numpy(pb[k].copy()).cuda() for k in "OAUCM"}
     s = opt.OptSolver(gpu_state, (W, H), opt.BUILTIN_PLAN, b"LMGPU")
@@ -381,13 +382,15 @@ def test_LM_solver_kind_vs_oracle(gpu_state, oracle, W, H, nIter, lIter, radius)
     s.close()
     Or, Ar, costs, steps, rad = oracle.solve_lm(pb["O"], pb["A"], pb["U"], pb["C"], pb["M"], 10.0, 0.1, nIter, lIter,
                                                 trust_region_radius=radius)
-    dO, dOr = dev["O"].cpu().numpy() - pb["O"], Or - pb["O"]
-    assert helpers.rel_l2(dO, dOr) < 1e-4 and helpers.rel_l2(dev["A"].cpu().numpy() - pb["A"], Ar - pb["A"]) < 1e-4
-    assert abs(cost - costs[-1]) <= 1e-4 * abs(costs[-1])
+    Og, Ag = dev["O"].cpu().numpy(), dev["A"].cpu().numpy()
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    nO, nA = int((bits(Og) != bits(Or)).sum()), int((bits(Ag) != bits(Ar)).sum())
+    print("LM %dx%d: %d steps, final radius %g, mismatching floats %d + %d" % (W, H, steps, rad, nO, nA))
+    assert nO == 0 and nA == 0
+    assert cost == costs[-1]
     assert costs[-1] < costs[0]                                       # LM made progress
     ex = pb["M"] != 0
-    assert np.array_equal(dev["O"].cpu().numpy()[ex], pb["O"][ex])
-    print("LM %dx%d: %d steps, final radius %g, mismatching floats %d" % (W, H, steps, rad, int((dO != dOr).sum())))
+    assert np.array_equal(bits(Og[ex]), bits(pb["O"][ex])) and np.array_equal(bits(Ag[ex]), bits(pb["A"][ex]))
 
 
 def test_solver_reuse_across_frames_of_different_tile_counts(gpu_state):
