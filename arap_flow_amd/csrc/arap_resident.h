@@ -115,6 +115,9 @@ static_assert(2 * ((RES_LDS_BYTES + 1279) / 1280 * 1280) <= 160 * 1024, "two wor
 #ifndef RES_WREG_9_FLAT
 #define RES_WREG_9_FLAT RES_WREG_9
 #endif
+#ifndef RES_PUB_MASK
+#define RES_PUB_MASK 1        // flat flavour: the two store flavours of a sum's publish stand under lane masks (0: a branch on `fast`)
+#endif
 #ifndef RES_Z16
 #define RES_Z16 1             // a halo entry's two z granules are fetched with one 16-byte load (0: two 8-byte loads)
 #endif
@@ -241,6 +244,10 @@ __device__ __forceinline__ void ld_zentry(const unsigned long long* zx_b, __amdg
         for (int c = 0; c < 2; ++c) h[c] = __hip_atomic_load(q_ + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+// The buffer-load builtin is an ordinary read to the compiler, which may hoist it out of a spin (its volatile form would
+// pin it, but also raises the load to system scope: sc0 sc1).  An empty asm that clobbers memory, in front of the load
+// inside the spin, has it issued on every trip.  It emits nothing and waits for nothing.
+#define RES_GRANULE_FENCE() asm volatile("" ::: "memory")
 typedef float v2f_t __attribute__((ext_vector_type(2)));
 // (a.x*b.x + c.x, a.y*b.y + c.y) with one rounding each: v_pk_fma_f32
 __device__ __forceinline__ float2 fma2(float2 a, float2 b, float2 c)
@@ -280,20 +287,33 @@ __device__ __forceinline__ double block_sum_uniform(double t)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 3), __builtin_amdgcn_readlane(__double2loint(t), 3));
 }
 
+// Does this lane publish its half of a partial (group_sum: lanes 2 and 3 of wave 0) with the store flavour `flavour`
+// (true: plain, the group shares an L2; false: write-through)?  A per-lane value that the compiler cannot see through, so
+// that each flavour is one store under its own lane mask.
+__device__ __forceinline__ int res_publishes(bool fast, bool flavour)
+{
+    int s_ = (((threadIdx.x & 63) >> 1) == 1 && fast == flavour) ? 1 : 0;
+    asm volatile("" : "+v"(s_));
+    return s_;
+}
+
 // Group-wide sum of one double per workgroup.  `part` is this workgroup's partial (valid in wave 0,
 // lanes 2 and 3: block_sum8).  Wave 0 publishes it as two {tag, 32 bits} granules and sweeps the group's granules until
 // every tag equals `epoch`; lane k owns workgroups k, k+64, ... and adds their partials in that order,
 // then the fixed DPP tree above adds the lanes, so every workgroup of the group computes the same bits.
 // Returns the sum rounded to float in every thread; false on timeout.
 // ONE: the group has at most 64 workgroups (the flat flavour's host invariant, host_resident.h: plan_resident_pack), so
-// the sweep is one straight-line trip: lane k reads rank k's pair, lanes at or beyond wgs read rank 0's (an address
-// inside the group's granules), add +0.0 and count as arrived.
-template <bool ONE = false>
+// the sweep is one straight-line trip: lane k reads rank k's pair with one 16-byte load; lanes at or beyond wgs and the
+// lane of this workgroup's own rank load nothing, add +0.0 / the own partial and count as arrived.
+// PUBMASK: the two store flavours of the publish are predicated by the per-lane `pubf` / `pubs` (res_publishes, formed by the
+// caller in front of its loop) instead of a scalar branch on `fast`.
+template <bool ONE = false, bool PUBMASK = false>
 __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned long long* gran_group, int rank,
                                           int wgs, float* bcast /* LDS, 2 floats */, unsigned* err, float& out,
                                           bool fast = false, double* out_d = nullptr, bool nowait = false,
                                           unsigned long long* tm = nullptr /* diagnostic: publish / poll / tail cycles, ... */,
-                                          unsigned long long* tarr = nullptr /* diagnostic: sum of the publish times (100 MHz) */)
+                                          unsigned long long* tarr = nullptr /* diagnostic: sum of the publish times (100 MHz) */,
+                                          int pubf = 0, int pubs = 0)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned long long c0 = 0ull, c1;
@@ -304,7 +324,15 @@ __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned 
         __builtin_amdgcn_s_setprio(3);
         unsigned long long* buf = gran_group + (size_t)(epoch & 1u) * wgs * RES_GS;
         // lanes 2 and 3 hold the partial (block_sum8) and publish one half each: nothing between the sum and the stores
-        if ((lane >> 1) == 1) {
+        // (the flavour of the store is a per-lane selector: each flavour is one store under its own lane mask, no scalar
+        //  branch on `fast` between the block sum and the store)
+        if (PUBMASK) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(part);
+            const unsigned hw = lane == 2 ? (unsigned)bits : (unsigned)(bits >> 32);
+            const unsigned long long gv = ((unsigned long long)epoch << 32) | hw;
+            if (pubf) __hip_atomic_store(buf + rank * RES_GS + (lane - 2), gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (pubs) __hip_atomic_store(buf + rank * RES_GS + (lane - 2), gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if ((lane >> 1) == 1) {
             const unsigned long long bits = (unsigned long long)__double_as_longlong(part);
             const unsigned hw = lane == 2 ? (unsigned)bits : (unsigned)(bits >> 32);
             const unsigned long long gv = ((unsigned long long)epoch << 32) | hw;
@@ -318,21 +346,30 @@ __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned 
         bool ok = false;
         if (tm) { c1 = __builtin_amdgcn_s_memtime(); tm[0] += c1 - c0; c0 = c1; }
         __builtin_amdgcn_s_sleep(RES_FIRST_LOOK);
-        // what does not depend on the granules is formed here, under the first-look sleep: behind the loads' return stand
-        // two compares, one mask operation and the vote, and one select per half of the value
+        // what does not depend on the granules is formed here, under the first-look sleep.  One trip: the four registers
+        // the sweep loads into are first set to what a lane WITHOUT granules to wait for contributes -- {its addend, the
+        // epoch as tag} in both halves -- and the load runs under the lane mask `look` only: behind the load's return stand
+        // two compares, one mask operation and the branch, and the registers already hold what the lane tree adds.
         const bool own1 = RES_OWN_LOCAL && lane == rank;
         const bool look = ONE && lane < wgs && !own1;            // this lane's granules count
         const double idle = own1 ? part : 0.0;                   // (a partial is a sum that started from +0.0: never -0.0,
                                                                  //  so 0.0 + partial, what the general sweep forms, is the partial)
-        const unsigned long long* const q1 = buf + RES_GS * ((ONE && lane < wgs) ? lane : 0);
-        for (unsigned spins = 0; spins < RES_SPIN_LIMIT; ++spins) {
+        // rank k's pair is 16 bytes, 16-byte aligned (the host deals granules in units of 2 RES_GS): ONE 16-byte load through
+        // a raw descriptor of the group's granules (sc1 like every granule load; each half is judged by its own tag)
+        const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc((void*)gran_group, 0, ONE ? 2 * wgs * RES_GS * 8 : 0, 0x00020000);
+        const int qoff = (int)(((epoch & 1u) * (unsigned)wgs + (unsigned)lane) * (RES_GS * 8u));
+        // (w lives across the trips: a lane that does not look keeps its preset, no copy stands in front of a load)
+        v4u_t w = {(unsigned)__double2loint(idle), epoch, (unsigned)__double2hiint(idle), epoch};
+        // the diagnostic `nowait` is a spin limit of one sweep, not a term of the exit test
+        const unsigned limit = nowait ? 1u : RES_SPIN_LIMIT;
+        for (unsigned spins = 0; spins < limit; ++spins) {
             if (tm) tm[3] += 1;
             if (ONE) {
-                const unsigned long long lo = __hip_atomic_load(q1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long hi = __hip_atomic_load(q1 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const bool late = look && ((unsigned)(lo >> 32) != epoch || (unsigned)(hi >> 32) != epoch);
-                v = look ? __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull))) : idle;
-                ok = !__any(late) || nowait;
+                RES_GRANULE_FENCE();
+                if (look) w = __builtin_amdgcn_raw_buffer_load_b128(grs, qoff, 0, 16 /* sc1 */);
+                const bool late = w[1] != epoch || w[3] != epoch;
+                v = __hiloint2double((int)w[2], (int)w[0]);
+                ok = __builtin_amdgcn_ballot_w64(late) == 0ull;
                 if (ok) break;
                 if (RES_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
                 continue;
@@ -349,10 +386,11 @@ __device__ __forceinline__ bool group_sum(double part, unsigned epoch, unsigned 
                 mine_ok = mine_ok && (own || ((unsigned)(lo >> 32) == epoch && (unsigned)(hi >> 32) == epoch));
                 v += own ? part : __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
             }
-            ok = __all(mine_ok) || nowait;
+            ok = __builtin_amdgcn_ballot_w64(!mine_ok) == 0ull;
             if (ok) break;
             if (RES_POLL_SLEEP) __builtin_amdgcn_s_sleep(1);
         }
+        ok = ok || nowait;
         if (tm) { c1 = __builtin_amdgcn_s_memtime(); tm[1] += c1 - c0; c0 = c1; asm volatile("" : "+v"(v)); }
         v = wave_sum_l63_full(v);
         if (tm) {                                     // (lane tree: a part of the tail; the asm keeps the stamp behind the tree)
@@ -576,7 +614,7 @@ __device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 do
 // Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), the four edge weights and the fit
 // weight (5 x NS, one VGPR each: RES_WPIN) and, up to 7 slots, the own search direction p (3 x NS, updated in place; z =
 // M^-1 r of phase B stays in Ap's registers until the update), the own (cos, sin) (2 x NS, RES_CSREG_SLOTS) and the p of
-// the thread's three halo cells (9, RES_HPREG_SLOTS: 7 slots flat, 6 in the other flavour): 244 / 233 / 241 VGPRs at
+// the thread's three halo cells (9, RES_HPREG_SLOTS: 7 slots flat, 6 in the other flavour): 242 / 233 / 243 VGPRs at
 // 7 / 8 / 9 slots in the flat-sums flavour (SUMS below), 251 / 245 / 255 in the other, no scratch.
 // NS = tile slots the loops run over (1 .. RES_SLOTS): the most tiles any workgroup of the LAUNCH holds (the host picks
 // the instantiation per launch, host_step.h: enqueue_gn_step).  The phases are fully unrolled and branch free over the
@@ -951,6 +989,11 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             }
         }
     }
+    // which store flavour publishes this lane's half of a partial (flat flavour: lane masks instead of a branch on `fast`)
+    // (not the instrumented 9-slot build: it has no VGPR left for the two selectors, 104 more bytes of scratch)
+    constexpr bool PUBMASK = FLAT && RES_PUB_MASK != 0 && !(STAMPS && NS == RES_SLOTS);
+    const int pubf = PUBMASK ? res_publishes(fast, true) : 0, pubs = PUBMASK ? res_publishes(fast, false) : 0;
+    const bool zskip = rd.nowait != 0;                 // (diagnostic: never look again at the z tags)
     if (STAMPS) t0 = __builtin_amdgcn_s_memrealtime();
     for (int l = 0; l < L && alive; ++l) {
         // ---------------- phase A: Ap = J^T J p, sigma = p.Ap --------------------------------------
@@ -1083,8 +1126,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             if (STAMPS) tbs += __builtin_amdgcn_s_memtime() - cb;
             alive = (!FLAT && hierx) ? group_sum_x(block_sum_uniform(bs), 2u * l + 2u, gran_group, granx_group, rank, wgs, bcast, rd.err, sigma, subfast)
                   : (!FLAT && hier)  ? group_sum_h(block_sum_uniform(bs), 2u * l + 2u, gran_group, gran2, rank, wgs, bcast, rd.err, sigma, subfast)
-                          : group_sum<ONE_TRIP>(bs, 2u * l + 2u, gran_group, rank, wgs, bcast, rd.err, sigma, fast, nullptr, rd.nowait != 0,
-                                      STAMPS ? tm : nullptr, STAMPS ? tarr : nullptr);
+                          : group_sum<ONE_TRIP, PUBMASK>(bs, 2u * l + 2u, gran_group, rank, wgs, bcast, rd.err, sigma, fast, nullptr, rd.nowait != 0,
+                                      STAMPS ? tm : nullptr, STAMPS ? tarr : nullptr, pubf, pubs);
         }
         // (sigma is wanted HERE, with the outcome: else the compiler reads `ok` from the broadcast, branches on it and only
         //  then fetches the value -- two dependent LDS round trips where the second sum's exit has one 8-byte read)
@@ -1095,7 +1138,6 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         // Branch free except for the stores: an excluded lane has r = Ap = 0 and M^-1_A = 0, so its r, z stay 0.
         float alpha = 0.f;
         if (sigma > 0.f) alpha = rho / sigma;
-        acc = 0.0;
         const unsigned ztag = 2u * l + 3u;                 // (the epoch of the sum that follows: unique in the launch, never 0)
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
@@ -1113,7 +1155,11 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             if (zent >= 0) {
                 zst[j * RES_ZX + zent] = make_float4(zx, zy, za, zy);
             }
-            acc += (double)keep_if_here<5>(fl[j], dot3(zx, zy, za, rx[j], ry[j], ra[j]));
+            // The first term IS the partial: +0.0 + t = t unless t is -0.0, and z.r is never -0.0 -- z_x r_x = mo r_x^2 and
+            // z_y r_y are products of equal signs (mo > 0), so the inner fma is +0.0 or positive, and a sum rounds to -0.0
+            // only if BOTH addends are -0.0; the mask gives +0.0.  (Phase A keeps its add: p.Ap can be -0.0.)
+            const double t_ = (double)keep_if_here<5>(fl[j], dot3(zx, zy, za, rx[j], ry[j], ra[j]));
+            if (j == 0) acc = t_; else acc += t_;
             __builtin_amdgcn_sched_barrier(0);
         }
         // (delta += alpha p is left to the update phase, which has the workgroup's own p at hand)
@@ -1148,8 +1194,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             }
             alive = (!FLAT && hierx) ? group_sum_x(block_sum_uniform(bs), 2u * l + 3u, gran_group, granx_group, rank, wgs, bcast, rd.err, rhoNew, subfast)
                   : (!FLAT && hier)  ? group_sum_h(block_sum_uniform(bs), 2u * l + 3u, gran_group, gran2, rank, wgs, bcast, rd.err, rhoNew, subfast)
-                          : group_sum<ONE_TRIP>(bs, 2u * l + 3u, gran_group, rank, wgs, bcast, rd.err, rhoNew, fast, nullptr, rd.nowait != 0,
-                                      STAMPS ? tm : nullptr, STAMPS ? tarr + 1 : nullptr);
+                          : group_sum<ONE_TRIP, PUBMASK>(bs, 2u * l + 3u, gran_group, rank, wgs, bcast, rd.err, rhoNew, fast, nullptr, rd.nowait != 0,
+                                      STAMPS ? tm : nullptr, STAMPS ? tarr + 1 : nullptr, pubf, pubs);
         }
         // ---------------- p = z + beta p (its loads first) ----------------------------------------------
         // (1) issue the loads of the neighbours' border z for this workgroup's halo cells (all in flight): at once, before the
@@ -1246,14 +1292,18 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         //     travels, so the tags all but always match, and a lane whose granule is still the previous iteration's
         //     reads it again.
         {
-            bool fresh = true;
+            // branch free: the six tags (the high halves of the granules' second words) against ztag, the differences or-ed
+            const unsigned zt16 = ztag << 16;
+            unsigned bad = 0u;
 #pragma unroll
             for (int u = 0; u < RES_HALO_PER_THREAD; ++u)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) fresh = fresh && (unsigned)(hg[u][c] >> 48) == ztag;
-            if (!__all(fresh) && !rd.nowait) {
+                for (int c = 0; c < 2; ++c) bad |= (unsigned)(hg[u][c] >> 32) ^ zt16;
+            bool fresh = (bad >> 16) == 0u;
+            if (__builtin_amdgcn_ballot_w64(!fresh) != 0ull) if (!zskip) {        // (one scalar test on the usual path)
                 for (unsigned spins = 0; spins < RES_SPIN_LIMIT; ++spins) {
                     if (STAMPS) tzr += 1;
+                    RES_GRANULE_FENCE();
                     fresh = true;
 #pragma unroll
                     for (int u = 0; u < RES_HALO_PER_THREAD; ++u) {
@@ -1263,7 +1313,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                             for (int c = 0; c < 2; ++c) fresh = fresh && (unsigned)(hg[u][c] >> 48) == ztag;
                         }
                     }
-                    if (__all(fresh)) break;
+                    if (__builtin_amdgcn_ballot_w64(!fresh) == 0ull) break;
                     __builtin_amdgcn_s_sleep(1);
                 }
                 // gave up: the host sees the error word and redoes the step on the two-kernel path (the launch runs on
@@ -1364,6 +1414,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 }
 
 #undef RES_STAMP
+#undef RES_GRANULE_FENCE
 #undef RES_HPK
 #undef RES_PRIO
 #undef RES_PRIO_END
