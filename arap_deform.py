@@ -12,8 +12,10 @@ whose first word is `light` the relit frames of one pair, one whose first word i
 whose first word is `score` the error table of one estimated flow, one whose first word is `tscore` the TAP-Vid table of
 one estimated track file, one whose first word is `chain` the track file of chained flow estimates, one whose first word
 is `fscore` the PSNR / SSIM table of one estimated frame, one whose first word is `interp` the in-between frames of a
-pair from a flow estimate: the forms are defined in arap_flow_amd/pipeline.py (SolveLine,
-parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine, SegLine, ScoreLine, TScoreLine, ChainLine, FScoreLine, InterpLine).  Any line that is no solve runs once every earlier line of the list is solved and written (its
+pair from a flow estimate, one whose first word is `lscore` the DAVIS J / F table of one estimated label map, one whose
+first word is `mscore` the precision / recall table of one estimated occlusion or motion-boundary map: the forms are
+defined in arap_flow_amd/pipeline.py (SolveLine, parse_layers, BgLine, TexLine, TrkLine, BlurLine, LightLine, SegLine,
+ScoreLine, TScoreLine, ChainLine, FScoreLine, InterpLine, LScoreLine, MScoreLine).  Any line that is no solve runs once every earlier line of the list is solved and written (its
 inputs may be their outputs).
 
 Same argument contract, same fixed schedule (numIter 19, nonLinearIter 8, linearIter 400, main.cpp:215-221),
@@ -94,6 +96,10 @@ def main(argv):
                 pipeline.run_fscore(state, lines[k])
             elif isinstance(lines[k], pipeline.InterpLine):
                 pipeline.run_interp(state, lines[k])
+            elif isinstance(lines[k], pipeline.LScoreLine):
+                pipeline.run_lscore(state, lines[k])
+            elif isinstance(lines[k], pipeline.MScoreLine):
+                pipeline.run_mscore(state, lines[k])
             else:
                 pipeline.run_layers(state, lines[k])
             print("Saved")

@@ -123,6 +123,9 @@ SYMBOLS = [
     ("ArapFlow_TrackScore", _I, [_VP, _U, _U] + [_VP] * 4 + [C.c_float, C.c_float, _VP]),
     ("ArapFlow_ChainFlows", _I, [_VP, _U, _U, _U, _VP, _VP, _U, _VP, _VP, _VP]),
     ("ArapFlow_FrameScore", _I, [_VP, _U, _U, _U] + [_VP] * 8),
+    ("ArapFlow_MapScoreScratchBytes", C.c_uint64, [_U, _U]),
+    ("ArapFlow_LabelScore", _I, [_VP, _U, _U, _U, _U, _U] + [_VP] * 5),
+    ("ArapFlow_MapScore", _I, [_VP, _U, _U, _U, _VP, _VP, _VP, _U, C.POINTER(C.c_uint), _U, _VP, _VP, _VP]),
     ("ArapFlow_InterpScratchBytes", C.c_uint64, [_U, _U, _U]),
     ("ArapFlow_InterpFrames", _I, [_VP, _U, _U] + [_VP] * 4 + [_U, C.POINTER(C.c_float)] + [_VP] * 3),
     ("ArapFlow_WarpDiag", _I, [_VP, _U, _U, _VP, _VP, _VP, _VP]),
@@ -138,6 +141,7 @@ SEG_MAX_RADIUS = 254                    # ARAPFLOW_SEG_MAX_RADIUS
 SCORE_ROWS, SCORE_FIELDS = 10, 8         # ARAPFLOW_SCORE_ROWS, ARAPFLOW_SCORE_FIELDS
 TSCORE_MAX_FRAMES, TSCORE_CLASSES, TSCORE_FIELDS = 64, 3, 16    # ARAPFLOW_TSCORE_MAX_FRAMES, _CLASSES, _FIELDS
 FSCORE_ROWS, FSCORE_FIELDS = 9, 7         # ARAPFLOW_FSCORE_ROWS, ARAPFLOW_FSCORE_FIELDS
+LSCORE_FIELDS, MSCORE_MAX_THR = 8, 8      # ARAPFLOW_LSCORE_FIELDS, ARAPFLOW_MSCORE_MAX_THR
 INTERP_MAX_TIMES, INTERP_FILL = 32, 16     # ARAPFLOW_INTERP_MAX_TIMES, ARAPFLOW_INTERP_FILL
 LIGHT_MAX_R, LIGHT_MAX_SHIFT = 16, 64   # ARAPFLOW_LIGHT_MAX_R, ARAPFLOW_LIGHT_MAX_SHIFT
 

@@ -100,6 +100,7 @@ Opt_State* Opt_NewState(Opt_InitializationParameters params)
     st->tile = knobs.tile;                 // experiments: phase-A variant
     st->force_b8 = knobs.b8;               // experiments: 8-byte form of phase B
     st->stream_a = knobs.stream_a;
+    st->mscore_plain = knobs.mscore_plain;
     return st;
 }
 

@@ -46,6 +46,7 @@
 #include "arap_tscore.h"
 #include "arap_chain.h"
 #include "arap_fscore.h"
+#include "arap_mscore.h"
 #include "arap_interp.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
@@ -64,5 +65,6 @@ using namespace arap;
 #include "abi_score.h"       // ArapFlow_FlowScore
 #include "abi_tscore.h"      // ArapFlow_TrackScore, ArapFlow_ChainFlows
 #include "abi_fscore.h"      // ArapFlow_FrameScore
+#include "abi_mscore.h"      // ArapFlow_LabelScore, ArapFlow_MapScore
 #include "abi_interp.h"      // ArapFlow_InterpFrames
 #include "abi_solver.h"      // ArapFlow_Solver*

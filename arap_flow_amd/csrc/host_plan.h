@@ -63,6 +63,7 @@ struct Knobs {
     int tile = -1;              // ARAPOPT_TILE=TXxTY: index into kTileShapes, -1 = not given / no such shape
     bool b8 = false;            // ARAPOPT_B8=1: the 8-byte-per-lane form of phase B
     int stream_a = 0;           // ARAPOPT_STREAM_A
+    bool mscore_plain = false;  // ARAPOPT_MSCORE_PLAIN=1 (experiments: k_mscore_hist with one LDS atomic per pixel, no wave aggregation)
     // plan level
     bool no_resident = false;   // ARAPOPT_NO_RESIDENT=1
     int force_res_fail = 0;     // ARAPOPT_FORCE_RES_FAIL=1 / 2 (test hooks)
@@ -87,6 +88,7 @@ static Knobs read_knobs()
     }
     k.b8 = is("ARAPOPT_B8", '1');
     k.stream_a = num("ARAPOPT_STREAM_A", 0);
+    k.mscore_plain = is("ARAPOPT_MSCORE_PLAIN", '1');
     k.no_resident = is("ARAPOPT_NO_RESIDENT", '1');
     k.force_res_fail = is("ARAPOPT_FORCE_RES_FAIL", '1') ? 1 : (is("ARAPOPT_FORCE_RES_FAIL", '2') ? 2 : 0);
     k.no_xcd_fast = is("ARAPOPT_NO_XCD_FAST", '1');
@@ -117,6 +119,7 @@ struct Opt_State {
     int tile = -1;              // ArapFlow_SetTile: phase-A variant of the two-kernel path; -1 = choose per solve
     bool force_b8 = false;      // ARAPOPT_B8=1 (counter calibration): the 8-byte-per-lane form of phase B
     int stream_a = 0;           // ARAPOPT_STREAM_A=1 (experiments): the tiled k_pcg_a_grid instead of the marching kernel
+    bool mscore_plain = false;  // ARAPOPT_MSCORE_PLAIN=1 (experiments): k_mscore_hist without the wave aggregation
     void* diag = nullptr;       // ArapFlow_WarpDiag: device, the call's WarpJob (256 bytes) and its accumulator; at first use
     void* tex = nullptr;        // ArapFlow_Texture: device, the call's layer table (255 layers); at first use
     void* light = nullptr;      // ArapFlow_Relight: device, the call's tone table (3 x 256 bytes); at first use

@@ -66,6 +66,12 @@
 // A line whose first word is `interp` is the in-between frames of a pair from a flow estimate (DESIGN.md "Frames from flows"):
 //   interp A.png B.png FWD.flo s=I1,I2,.. n=N [bwd=BWD.flo] [src=1] out=PREFIX
 // (the times are (float)I / (float)N; written: PREFIX_sII.png and, with src=1, the source maps PREFIX_sII_src.png).
+// A line whose first word is `lscore` is the DAVIS J / F table of one estimated label map, one whose first word is `mscore`
+// the precision / recall table of one estimated occlusion or motion-boundary map (DESIGN.md "Map scoring"):
+//   lscore GT.png EST.png l=<L> r=<radius> [skip=PNG] out=TXT
+//   mscore GT.png EST.png [t=<thr,...> r=<radius>] [skip=PNG] out=TXT
+// (the red channel of every PNG; skip: non-zero = left out; out: the table as text, pipeline.format_label_score /
+// format_map_score).
 // Any of these runs on the solver's own stream between batches; in a list every earlier line is finished and written first (its
 // inputs may be their outputs); --serve answers "Done <path of the first output token on the line>".
 // The reference keeps one CombinedSolver (one Opt plan) and feeds it frame after frame (main.cpp:223-238);
@@ -524,6 +530,75 @@ static bool run_fscore(Opt_State* state, const FScoreSpec& q)
     return save_text(q.out, text.data(), text.size());
 }
 
+// the maps of an lscore / mscore line, red channels: gt, est and, when the line names one, skip, of one size
+static bool read_score_maps(const char* word, const std::string& gt_path, const std::string& est_path, const std::string& skip_path,
+                            int& w, int& h, std::vector<uint8_t> (&plane)[3])
+{
+    const std::string* const paths[3] = {&gt_path, &est_path, &skip_path};
+    for (int k = 0; k < 3; ++k) {
+        if (paths[k]->empty()) continue;
+        arapio::Image im;
+        if (!read_png(*paths[k], im)) return false;
+        if (k == 0) { w = im.w; h = im.h; }
+        if (im.w != w || im.h != h) return fail("%s: %s differs in size from %s\n", word, paths[k]->c_str(), gt_path.c_str());
+        plane[k].resize((size_t)w * h);
+        for (size_t i = 0; i < plane[k].size(); ++i) plane[k][i] = im.rgb[3 * i];
+    }
+    return true;
+}
+
+// the DAVIS J / F table of one estimated label map, synchronously (pipeline.run_lscore): read the maps, one
+// ArapFlow_LabelScore on the state's stream, write the table as text
+static bool run_lscore(Opt_State* state, const LScoreSpec& q)
+{
+    int w = 0, h = 0;
+    std::vector<uint8_t> plane[3];
+    if (!read_score_maps("lscore", q.gt, q.est, q.skip, w, h, plane)) return false;
+    const uint64_t scratch = ArapFlow_MapScoreScratchBytes((unsigned)w, (unsigned)h);
+    if (!scratch) return fail("lscore: maps of %d x %d: beyond the limits\n", w, h);
+    DeviceArena dev;
+    const size_t d_gt = dev.stage(plane[0].data(), plane[0].size()), d_est = dev.stage(plane[1].data(), plane[1].size());
+    const size_t d_skip = plane[2].empty() ? DeviceArena::kNone : dev.stage(plane[2].data(), plane[2].size());
+    std::vector<uint64_t> table((size_t)(q.L + 1) * ARAPFLOW_LSCORE_FIELDS);
+    const size_t d_table = dev.take(table.size() * 8), d_scr = dev.take(scratch);
+    if (dev.alloc() != hipSuccess) return fail("lscore: out of device memory\n");
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_LabelScore(state, (unsigned)w, (unsigned)h, 1, q.L, q.radius, dev.at(d_gt), dev.at(d_est), dev.at(d_skip),
+                                        dev.at(d_table), dev.at(d_scr)) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(table.data(), dev.at(d_table), table.size() * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail("ArapFlow_LabelScore failed\n");
+    const std::string text = format_label_score(table.data(), q.L);
+    return save_text(q.out, text.data(), text.size());
+}
+
+// the precision / recall table of one estimated occlusion or motion-boundary map, synchronously (pipeline.run_mscore)
+static bool run_mscore(Opt_State* state, const MScoreSpec& q)
+{
+    int w = 0, h = 0;
+    std::vector<uint8_t> plane[3];
+    if (!read_score_maps("mscore", q.gt, q.est, q.skip, w, h, plane)) return false;
+    const unsigned m = (unsigned)q.thr.size();
+    const uint64_t scratch = ArapFlow_MapScoreScratchBytes((unsigned)w, (unsigned)h);
+    if (!scratch) return fail("mscore: maps of %d x %d: beyond the limits\n", w, h);
+    DeviceArena dev;
+    const size_t d_gt = dev.stage(plane[0].data(), plane[0].size()), d_est = dev.stage(plane[1].data(), plane[1].size());
+    const size_t d_skip = plane[2].empty() ? DeviceArena::kNone : dev.stage(plane[2].data(), plane[2].size());
+    std::vector<uint64_t> hist(512), match((size_t)m * 4);
+    const size_t d_hist = dev.take(hist.size() * 8);
+    const size_t d_match = m ? dev.take(match.size() * 8) : DeviceArena::kNone, d_scr = m ? dev.take(scratch) : DeviceArena::kNone;
+    if (dev.alloc() != hipSuccess) return fail("mscore: out of device memory\n");
+    const bool ok = dev.upload() == hipSuccess &&
+                    ArapFlow_MapScore(state, (unsigned)w, (unsigned)h, 1, dev.at(d_gt), dev.at(d_est), dev.at(d_skip), m,
+                                      m ? q.thr.data() : nullptr, q.radius, dev.at(d_hist), dev.at(d_match), dev.at(d_scr)) == 0 &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(hist.data(), dev.at(d_hist), hist.size() * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+                    (!m || hipMemcpy(match.data(), dev.at(d_match), match.size() * 8, hipMemcpyDeviceToHost) == hipSuccess);
+    if (!ok) return fail("ArapFlow_MapScore failed\n");
+    const std::string text = format_map_score(hist.data(), q.thr.data(), m, match.data());
+    return save_text(q.out, text.data(), text.size());
+}
+
 // the in-between frames of one pair from a flow estimate, synchronously (pipeline.run_interp): read the two frames and the
 // flows, one ArapFlow_InterpFrames on the state's stream, write a frame (and with src=1 a source map) per step
 static bool run_interp(Opt_State* state, const InterpSpec& q)
@@ -891,7 +966,7 @@ class FrameSource {
         while (!lines_.empty() && loading_.size() < kAhead) {
             auto q = std::make_shared<Item>(std::move(lines_.front()));
             lines_.pop_front();
-            // a layers / bg / tex / trk / blur / light / seg / score / tscore / chain / fscore / interp line is read when its turn comes: in a list its inputs may not exist yet
+            // a layers / bg / tex / trk / blur / light / seg / score / tscore / chain / fscore / interp / lscore / mscore line is read when its turn comes: in a list its inputs may not exist yet
             const bool solve = q->kind == Item::Kind::Solve;
             loading_.push_back(std::async(solve ? std::launch::async : std::launch::deferred, [q, solve]() {
                 Frame f;
@@ -1178,6 +1253,8 @@ int main(int argc, const char* argv[])
                   : kind == Item::Kind::Chain ? run_chain(state, fr->item.chain)
                   : kind == Item::Kind::FScore ? run_fscore(state, fr->item.fscore)
                   : kind == Item::Kind::Interp ? run_interp(state, fr->item.interp)
+                  : kind == Item::Kind::LScore ? run_lscore(state, fr->item.lscore)
+                  : kind == Item::Kind::MScore ? run_mscore(state, fr->item.mscore)
                                             : run_layers(state, fr->item.layers))) { rc = 1; break; }
             writer.say(serve ? "Done " + done_path(fr->item) : std::string("Saved"));
             continue;

@@ -103,6 +103,54 @@ inline std::string format_frame_score(const uint64_t* table)
     return text + cell;
 }
 
+// the text of a label score file (pipeline.format_label_score): the frame's row, then one line per label of
+// ArapFlow_LabelScore's table uint64[L + 1][8], integers only
+inline std::string format_label_score(const uint64_t* table, unsigned L)
+{
+    static const char* const frame[5] = {"counted", "skipped", "equal", "gt_above", "est_above"};
+    static const char* const fields[ARAPFLOW_LSCORE_FIELDS - 1] = {"gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit"};
+    std::string text = "frame";
+    char cell[64];
+    for (int f = 0; f < 5; ++f) {
+        snprintf(cell, sizeof(cell), " %s=%llu", frame[f], (unsigned long long)table[f]);
+        text += cell;
+    }
+    text += "\n";
+    for (unsigned k = 1; k <= L; ++k) {
+        snprintf(cell, sizeof(cell), "label %u", k);
+        text += cell;
+        for (int f = 0; f < ARAPFLOW_LSCORE_FIELDS - 1; ++f) {
+            snprintf(cell, sizeof(cell), " %s=%llu", fields[f], (unsigned long long)table[k * ARAPFLOW_LSCORE_FIELDS + f]);
+            text += cell;
+        }
+        text += "\n";
+    }
+    return text;
+}
+
+// the text of a map score file (pipeline.format_map_score): the two rows of ArapFlow_MapScore's histogram, then one line
+// per threshold of its match table, integers only
+inline std::string format_map_score(const uint64_t* hist, const unsigned* thr, unsigned m, const uint64_t* match)
+{
+    std::string text;
+    char cell[96];
+    for (int c = 0; c < 2; ++c) {
+        text += c ? "pos" : "neg";
+        for (int v = 0; v < 256; ++v) {
+            snprintf(cell, sizeof(cell), " %llu", (unsigned long long)hist[c * 256 + v]);
+            text += cell;
+        }
+        text += "\n";
+    }
+    for (unsigned j = 0; j < m; ++j) {
+        const uint64_t* const q = match + 4 * j;
+        snprintf(cell, sizeof(cell), "match thr=%u a=%llu b=%llu a_hit=%llu b_hit=%llu\n", thr[j], (unsigned long long)q[0],
+                 (unsigned long long)q[1], (unsigned long long)q[2], (unsigned long long)q[3]);
+        text += cell;
+    }
+    return text;
+}
+
 // a text file, as it is; says why not
 inline bool save_text(const std::string& path, const void* data, size_t bytes)
 {

@@ -108,6 +108,16 @@ static std::string canonical(const Item& it)
         for (size_t j = 0; j < q.steps.size(); ++j) steps += (j ? "," : "") + std::to_string(q.steps[j]);
         c.token("s", steps); c.token("n", std::to_string(q.n)); c.token("bwd", q.bwd); c.token("src", q.src ? "1" : "");
         c.token("out", q.out);
+    } else if (it.kind == Item::Kind::LScore) {
+        const LScoreSpec& q = it.lscore;
+        c.word("lscore"); c.word(q.gt); c.word(q.est);
+        c.token("l", std::to_string(q.L)); c.token("r", std::to_string(q.radius)); c.token("skip", q.skip); c.token("out", q.out);
+    } else if (it.kind == Item::Kind::MScore) {
+        const MScoreSpec& q = it.mscore;
+        c.word("mscore"); c.word(q.gt); c.word(q.est);
+        std::string thr;
+        for (size_t j = 0; j < q.thr.size(); ++j) thr += (j ? "," : "") + std::to_string(q.thr[j]);
+        c.token("t", thr); c.token("r", q.thr.empty() ? "" : std::to_string(q.radius)); c.token("skip", q.skip); c.token("out", q.out);
     } else if (it.kind == Item::Kind::Light) {
         const LightSpec& q = it.light;
         c.word("light"); c.word(q.rgb1); c.word(q.mask1); c.word(q.rgb2); c.word(q.cover2);

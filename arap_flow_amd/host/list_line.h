@@ -34,7 +34,12 @@
 //                 (pipeline.FScoreLine): a repeated key is an error too
 //   interp line:  interp A.png B.png FWD.flo s=I1,I2,.. n=N [bwd=BWD.flo] [src=1] out=PREFIX
 //                 (pipeline.InterpLine): 1 to ARAPFLOW_INTERP_MAX_TIMES steps, 1 <= I1 < I2 < .. < N; a repeated key is an error too
-//                 on these twelve any unknown key, missing `=` or empty value is an error, and so is a line without output
+//   lscore line:  lscore GT.png EST.png l=<L> r=<radius> [skip=PNG] out=TXT
+//                 (pipeline.LScoreLine): 1 <= L <= 255, radius 0 .. ARAPFLOW_SEG_MAX_RADIUS; a repeated key is an error too
+//   mscore line:  mscore GT.png EST.png [t=<thr,...> r=<radius>] [skip=PNG] out=TXT
+//                 (pipeline.MScoreLine): 1 to ARAPFLOW_MSCORE_MAX_THR thresholds 1..255; t= and r= both or neither; a
+//                 repeated key is an error too
+//                 on these fourteen any unknown key, missing `=` or empty value is an error, and so is a line without output
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -104,7 +109,7 @@ inline std::string mid_stem(const std::string& prefix, unsigned step)
     return prefix + tag;
 }
 
-// ---- the thirteen forms
+// ---- the fifteen forms
 struct SolvePaths {                        // ARAP/deformation/src/main.cpp:4-11,183-191
     std::string rgb, mask, constraints, flow, warped_rgb, warped_mask;
     std::string bwd, occ, occ_bwd;         // optional outputs (empty: not wanted)
@@ -211,6 +216,21 @@ struct FScoreSpec {                        // pipeline.FScoreLine
     std::string out;
 };
 
+struct LScoreSpec {                        // pipeline.LScoreLine
+    std::string gt, est;
+    unsigned L = 0, radius = 0;
+    std::string skip;                      // optional plane (empty: not given)
+    std::string out;
+};
+
+struct MScoreSpec {                        // pipeline.MScoreLine
+    std::string gt, est;
+    std::vector<unsigned> thr;             // none: the histogram alone
+    unsigned radius = 0;
+    std::string skip;                      // optional plane (empty: not given)
+    std::string out;
+};
+
 struct InterpSpec {                        // pipeline.InterpLine
     std::string a, b, fwd;
     std::vector<unsigned> steps;           // ramp steps: the times are (float)step / (float)n
@@ -221,7 +241,7 @@ struct InterpSpec {                        // pipeline.InterpLine
 };
 
 struct Item {
-    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score, TScore, Chain, FScore, Interp } kind = Kind::Solve;
+    enum class Kind { Solve, Layers, Bg, Tex, Trk, Blur, Light, Seg, Score, TScore, Chain, FScore, Interp, LScore, MScore } kind = Kind::Solve;
     SolvePaths solve;
     LayersSpec layers;
     BgSpec bg;
@@ -235,6 +255,8 @@ struct Item {
     ChainSpec chain;
     FScoreSpec fscore;
     InterpSpec interp;
+    LScoreSpec lscore;
+    MScoreSpec mscore;
 };
 
 // the path `arap_deform --serve` reports a line done by (pipeline.done_token)
@@ -252,6 +274,8 @@ inline std::string done_path(const Item& it)
            : it.kind == Item::Kind::Chain  ? it.chain.out
            : it.kind == Item::Kind::FScore ? it.fscore.out
            : it.kind == Item::Kind::Interp ? it.interp.out
+           : it.kind == Item::Kind::LScore ? it.lscore.out
+           : it.kind == Item::Kind::MScore ? it.mscore.out
                                            : it.bg.first_out();
 }
 
@@ -680,6 +704,49 @@ inline bool parse_interp(std::istringstream& tok, InterpSpec& q)
     return q.steps.size() <= ARAPFLOW_INTERP_MAX_TIMES;
 }
 
+inline bool parse_lscore(std::istringstream& tok, LScoreSpec& q)
+{
+    std::string k, v, l, r;
+    if (!(tok >> q.gt >> q.est) || split_token(q.gt, k, v) || split_token(q.est, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        std::string* const dst = field_of({{"l", &l}, {"r", &r}, {"skip", &q.skip}, {"out", &q.out}}, k);
+        if (!dst || !dst->empty()) return false;
+        *dst = v;
+    }
+    unsigned long long x = 0, y = 0;
+    if (q.out.empty() || !parse_uint(l, 255, x) || x < 1 || !parse_uint(r, ARAPFLOW_SEG_MAX_RADIUS, y)) return false;
+    q.L = (unsigned)x;
+    q.radius = (unsigned)y;
+    return true;
+}
+
+inline bool parse_mscore(std::istringstream& tok, MScoreSpec& q)
+{
+    std::string k, v, thr, r;
+    if (!(tok >> q.gt >> q.est) || split_token(q.gt, k, v) || split_token(q.est, k, v)) return false;
+    for (std::string t; tok >> t;) {
+        if (!split_token(t, k, v) || v.empty()) return false;
+        std::string* const dst = field_of({{"t", &thr}, {"r", &r}, {"skip", &q.skip}, {"out", &q.out}}, k);
+        if (!dst || !dst->empty()) return false;
+        *dst = v;
+    }
+    if (q.out.empty() || thr.empty() != r.empty()) return false;
+    if (thr.empty()) return true;
+    unsigned long long x = 0;
+    if (!parse_uint(r, ARAPFLOW_SEG_MAX_RADIUS, x)) return false;
+    q.radius = (unsigned)x;
+    thr += ',';
+    std::string one;
+    for (char c : thr) {                   // decimal thresholds, comma separated, each 1..255
+        if (c != ',') { one += c; continue; }
+        if (!parse_uint(one, 255, x) || x < 1) return false;
+        q.thr.push_back((unsigned)x);
+        one.clear();
+    }
+    return q.thr.size() <= ARAPFLOW_MSCORE_MAX_THR;
+}
+
 // a list / --serve line -> item.  A refused form is reported here, on stdout.
 inline Parsed parse_item(const std::string& line, Item& it)
 {
@@ -690,7 +757,7 @@ inline Parsed parse_item(const std::string& line, Item& it)
               : first == "trk" ? Item::Kind::Trk : first == "blur" ? Item::Kind::Blur : first == "light" ? Item::Kind::Light
               : first == "seg" ? Item::Kind::Seg : first == "score" ? Item::Kind::Score : first == "tscore" ? Item::Kind::TScore
               : first == "chain" ? Item::Kind::Chain : first == "fscore" ? Item::Kind::FScore : first == "interp" ? Item::Kind::Interp
-              : Item::Kind::Solve;
+              : first == "lscore" ? Item::Kind::LScore : first == "mscore" ? Item::Kind::MScore : Item::Kind::Solve;
     it.solve.rgb = first;
     Parsed p;
     if (it.kind == Item::Kind::Solve) p = parse_solve(tok, it.solve);
@@ -704,10 +771,13 @@ inline Parsed parse_item(const std::string& line, Item& it)
     else if (it.kind == Item::Kind::Chain) p = parse_chain(tok, it.chain) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::FScore) p = parse_fscore(tok, it.fscore) ? Parsed::Good : Parsed::Bad;
     else if (it.kind == Item::Kind::Interp) p = parse_interp(tok, it.interp) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::LScore) p = parse_lscore(tok, it.lscore) ? Parsed::Good : Parsed::Bad;
+    else if (it.kind == Item::Kind::MScore) p = parse_mscore(tok, it.mscore) ? Parsed::Good : Parsed::Bad;
     else p = (it.kind == Item::Kind::Bg ? parse_bg(tok, it.bg) : parse_layers(tok, it.layers)) ? Parsed::Good : Parsed::Bad;
     if (p == Parsed::Bad) {
         const char* const what[] = {"mid= token", "layers line", "bg line", "tex line", "trk line", "blur line", "light line", "seg line", "score line",
-                                    "tscore line", "chain line", "fscore line", "interp line"};      // by Item::Kind
+                                    "tscore line", "chain line", "fscore line", "interp line", "lscore line",
+                                    "mscore line"};      // by Item::Kind
         printf("Invalid %s: %s\n", what[(int)it.kind], line.c_str());
         fflush(stdout);
     }

@@ -14,6 +14,8 @@
   seg_maps         object index maps, motion boundaries and boundary distance of a pair (ArapFlow_SegMaps)
   flow_score       the Sintel / KITTI error table of an estimated flow against a pair (ArapFlow_FlowScore)
   frame_score      the PSNR / integer-SSIM table of estimated frames (ArapFlow_FrameScore)
+  label_score      the DAVIS J / F counts of estimated label maps per object (ArapFlow_LabelScore)
+  map_score        the precision / recall counts of estimated occlusion / boundary maps (ArapFlow_MapScore)
   track_score      the TAP-Vid table of estimated tracks against a track file's (ArapFlow_TrackScore)
   chain_flows      estimated tracks from per-link flow estimates (ArapFlow_ChainFlows)
   interp_frames    estimated in-between frames from a flow estimate, by splatting (ArapFlow_InterpFrames)
@@ -973,6 +975,58 @@ def frame_score(state, ref, est, occ=None, dist=None, skip=None, obj=None, ssim=
     return _warp_call(state, "FrameScore", (W, H, n), [(ref, np.uint8), (est, np.uint8)] + planes,
                       [("table", (n, len(FSCORE_ROWS), len(FSCORE_FIELDS)), torch.int64),
                        ("ssim", (n, H, W) if ssim else None, torch.float32)], view={"table": np.uint64})
+
+
+LSCORE_FIELDS = ("gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit", "zero")
+LSCORE_FRAME_FIELDS = ("counted", "skipped", "equal", "gt_above", "est_above")       # row 0 of a label table
+MSCORE_MAX_THR = 8
+
+
+def _score_maps(name, gt, est, skip):
+    gt = np.ascontiguousarray(gt, np.uint8)
+    est = np.ascontiguousarray(est, np.uint8)
+    if gt.ndim == 2:
+        gt, est = gt[None], est[None] if est.ndim == 2 else est
+    if gt.ndim != 3 or est.shape != gt.shape:
+        raise ValueError("%s: gt and est [H,W] or [n,H,W] of one shape expected" % name)
+    if skip is not None:
+        skip = np.ascontiguousarray(skip, np.uint8).reshape((-1,) + np.shape(skip)[-2:])
+        if skip.shape != gt.shape:
+            raise ValueError("%s: skip of gt's shape expected" % name)
+    return gt, est, skip
+
+
+def label_score(state, gt, est, L, radius, skip=None):
+    """the DAVIS J / F counts of estimated label maps per object (ArapFlow_LabelScore, DESIGN.md "Map scoring").  gt, est
+    u8[H,W] or u8[n,H,W], label maps with 0 = no object; skip u8 of that shape or None, non-zero = left out; 1 <= L <= 255
+    labels scored; radius 0..254, the tolerance of the boundary match (numpy) -> {"table": u64[n,L+1,8]}: row 0 in the
+    order of LSCORE_FRAME_FIELDS, row k of label k in that of LSCORE_FIELDS."""
+    gt, est, skip = _score_maps("label_score", gt, est, skip)
+    n, H, W = gt.shape
+    return _warp_call(state, "LabelScore", (W, H, n), [(gt, np.uint8), (est, np.uint8), (skip, np.uint8)],
+                      [("table", (n, max(int(L), 0) + 1, len(LSCORE_FIELDS)), torch.int64)], ("MapScoreScratchBytes", (W, H)),
+                      lead=(int(L), int(radius)), view={"table": np.uint64})
+
+
+def map_score(state, gt, est, skip=None, thr=(), radius=0):
+    """the precision / recall counts of estimated occlusion or motion-boundary maps (ArapFlow_MapScore, DESIGN.md "Map
+    scoring").  gt u8[H,W] or u8[n,H,W], non-zero = positive; est u8 of that shape, a score 0..255; skip likewise or None;
+    thr up to 8 thresholds 1..255 and radius 0..254 for the tolerant boundary match (numpy) -> {"hist": u64[n,2,256],
+    "match": u64[n,len(thr),4]}: hist[c][v] the counted pixels of class c = (gt != 0) with est == v, match[j] = (a, b,
+    a_hit, b_hit) of A = {gt != 0}, B = {est >= thr[j]}."""
+    gt, est, skip = _score_maps("map_score", gt, est, skip)
+    n, H, W = gt.shape
+    thr = [int(t) for t in thr]
+    if any(t < 0 or t >= 1 << 32 for t in thr):
+        raise ValueError("map_score: bad threshold")
+    m = len(thr)
+    r = _warp_call(state, "MapScore", (W, H, n),
+                   [(gt, np.uint8), (est, np.uint8), (skip, np.uint8), (m, None), ((C.c_uint * m)(*thr) if m else None, None),
+                    (int(radius), None)],
+                   [("hist", (n, 2, 256), torch.int64), ("match", (n, m, 4) if m else None, torch.int64)],
+                   ("MapScoreScratchBytes", (W, H)), view={"hist": np.uint64, "match": np.uint64})
+    r.setdefault("match", np.zeros((n, 0, 4), np.uint64))
+    return r
 
 
 BG_OUTPUTS = ("out_rgb1","out_rgb2", "flow_full", "occ_full", "bwd_full", "occ_bwd_full")

@@ -26,6 +26,10 @@ functions that tests/golden/host/ pins with hand-computed cases:
   format_track_score, parse_track_score_file, track_score_summary, add_track_scores    a track score table as text, as metrics, pooled
   FScoreLine, parse_fscore, fscore_line, run_fscore    the `fscore` line: the PSNR / SSIM table of an estimated frame (addition)
   format_frame_score, parse_frame_score_file, frame_score_summary, add_frame_scores    a frame score table as text, as metrics, pooled
+  LScoreLine, parse_lscore, lscore_line, run_lscore    the `lscore` line: the DAVIS J / F table of an estimated label map (addition)
+  MScoreLine, parse_mscore, mscore_line, run_mscore    the `mscore` line: the precision / recall table of an estimated map (addition)
+  format_label_score, parse_label_score_file, label_score_summary, add_label_scores    a label score table as text, as metrics, pooled
+  format_map_score, parse_map_score_file, map_score_summary, add_map_scores    a map score as text, as metrics, pooled
   InterpLine, parse_interp, interp_line, run_interp    the `interp` line: in-between frames from a flow estimate (addition)
   merge_segments, flatten                para_gen.py:136-175    (--multseg: merge per-segment outputs by the warped masks)
   merge_backward, flatten_backward       --multseg merge of the backward flow / backward occlusion (addition)
@@ -40,7 +44,7 @@ import os
 import os.path as osp
 import random as rn
 import re
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 from PIL import Image
@@ -87,6 +91,14 @@ FSCORE_KEYS = ("occ", "dist", "skip", "obj")
 FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")
 FSCORE_FIELDS = ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")
 INTERP_WORD = "interp"
+LSCORE_WORD = "lscore"
+MSCORE_WORD = "mscore"
+MSCORE_MAX_THR = 8           # ARAPFLOW_MSCORE_MAX_THR of include/arap_opt.h
+# row 0 and a label's row of a label score table in their order (opt.LSCORE_FRAME_FIELDS; opt.LSCORE_FIELDS without its
+# last field, which is zero; ArapFlow_LabelScore), and a row of ArapFlow_MapScore's match table
+LSCORE_FRAME_FIELDS = ("counted", "skipped", "equal", "gt_above", "est_above")
+LSCORE_FIELDS = ("gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit")
+MSCORE_MATCH_FIELDS = ("a", "b", "a_hit", "b_hit")
 INTERP_MAX_TIMES = 32        # ARAPFLOW_INTERP_MAX_TIMES of include/arap_opt.h
 TSCORE_WORD = "tscore"
 CHAIN_WORD = "chain"
@@ -1330,6 +1342,270 @@ def run_fscore(state, spec):
     return table
 
 
+class LScoreLine(NamedTuple):
+    """an `lscore` line (DESIGN.md "Map scoring"), recognised by its first word: the DAVIS J / F table of one estimated
+    label map
+        lscore GT.png EST.png l=<L> r=<radius> [skip=PNG] out=TXT
+    GT, EST: label maps in the format of Index1 / Index2 (the red channel; 0 = no object); l=: the labels scored, 1..255;
+    r=: the tolerance of the boundary match, 0 .. SEG_MAX_RADIUS; skip: non-zero = left out.  `skip` is None when not
+    given, `out` the text file (format_label_score).  Anything else -- an unknown or repeated key, an empty value, no
+    out=, no l= or r=, a number out of range, fewer than two paths -- is an error."""
+    gt: str
+    est: str
+    L: int
+    radius: int
+    skip: Optional[str]
+    out: str
+
+
+class MScoreLine(NamedTuple):
+    """an `mscore` line (DESIGN.md "Map scoring"), recognised by its first word: the precision / recall table of one
+    estimated occlusion or motion-boundary map
+        mscore GT.png EST.png [t=<thr,...> r=<radius>] [skip=PNG] out=TXT
+    GT: non-zero = positive; EST: a score 0..255 (the red channel of both); t=: 1 to MSCORE_MAX_THR thresholds 1..255 for
+    the tolerant boundary match, with r= its radius, 0 .. SEG_MAX_RADIUS -- both or neither; skip: non-zero = left out.
+    `thr` is () and `radius` None without t=; `out` the text file (format_map_score).  Anything else is an error."""
+    gt: str
+    est: str
+    thr: tuple
+    radius: Optional[int]
+    skip: Optional[str]
+    out: str
+
+
+def _score_map_tokens(word, keys, tokens):
+    """the {key: value} of an lscore / mscore line after its two paths"""
+    if len(tokens) < 3 or tokens[0] != word or "=" in tokens[1] or "=" in tokens[2]:
+        raise ValueError("%s line: two map files expected: %r" % (word, " ".join(tokens)))
+    got = {}
+    for t in tokens[3:]:
+        k, eq, v = t.partition("=")
+        if not (eq and v and k in keys) or k in got:
+            raise ValueError("%s line: bad or repeated token %r" % (word, t))
+        got[k] = v
+    if "out" not in got:
+        raise ValueError("%s line without out=: %r" % (word, " ".join(tokens)))
+    return got
+
+
+def _score_uint(word, text, low, high):
+    if text is None or not _UINT.match(text) or not low <= int(text) <= high:
+        raise ValueError("%s line: a number %d..%d expected, not %r" % (word, low, high, text))
+    return int(text)
+
+
+def parse_lscore(tokens):
+    got = _score_map_tokens(LSCORE_WORD, ("l", "r", "skip", "out"), tokens)
+    return LScoreLine(tokens[1], tokens[2], _score_uint(LSCORE_WORD, got.get("l"), 1, 255),
+                      _score_uint(LSCORE_WORD, got.get("r"), 0, SEG_MAX_RADIUS), got.get("skip"), got["out"])
+
+
+def lscore_line(item):
+    """the inverse of parse_lscore: l=, r=, skip= if given, out="""
+    return " ".join([LSCORE_WORD, item.gt, item.est, "l=%d" % item.L, "r=%d" % item.radius] +
+                    (["skip=" + item.skip] if item.skip else []) + ["out=" + item.out])
+
+
+def parse_mscore(tokens):
+    got = _score_map_tokens(MSCORE_WORD, ("t", "r", "skip", "out"), tokens)
+    if ("t" in got) != ("r" in got):
+        raise ValueError("mscore line: t= and r= come together: %r" % " ".join(tokens))
+    thr, radius = (), None
+    if "t" in got:
+        thr = tuple(_score_uint(MSCORE_WORD, v, 1, 255) for v in got["t"].split(","))
+        radius = _score_uint(MSCORE_WORD, got["r"], 0, SEG_MAX_RADIUS)
+        if len(thr) > MSCORE_MAX_THR:
+            raise ValueError("mscore line: at most %d thresholds: %r" % (MSCORE_MAX_THR, got["t"]))
+    return MScoreLine(tokens[1], tokens[2], thr, radius, got.get("skip"), got["out"])
+
+
+def mscore_line(item):
+    """the inverse of parse_mscore: t= and r= if it has thresholds, skip= if given, out="""
+    return " ".join([MSCORE_WORD, item.gt, item.est] +
+                    (["t=" + ",".join("%d" % t for t in item.thr), "r=%d" % item.radius] if item.thr else []) +
+                    (["skip=" + item.skip] if item.skip else []) + ["out=" + item.out])
+
+
+def format_label_score(table):
+    """the text of a label score file, of a table uint64[L+1][8]: `frame counted=.. skipped=.. equal=.. gt_above=..
+    est_above=..`, then per label `label <k> gt=.. est=.. inter=.. gt_b=.. est_b=.. gt_hit=.. est_hit=..`; integers only;
+    the C++ worker writes the same bytes"""
+    t = np.asarray(table, np.uint64).reshape(-1, len(LSCORE_FIELDS) + 1)
+    lines = ["frame " + " ".join("%s=%d" % (f, int(v)) for f, v in zip(LSCORE_FRAME_FIELDS, t[0]))]
+    lines += ["label %d " % k + " ".join("%s=%d" % (f, int(v)) for f, v in zip(LSCORE_FIELDS, t[k])) for k in range(1, len(t))]
+    return "\n".join(lines) + "\n"
+
+
+def _score_cells(what, line, head, keys):
+    """the integers of `<head> key=int ...` in the order of `keys`"""
+    tok = line.split(" ")
+    if tok[:len(head)] != head or len(tok) != len(head) + len(keys):
+        raise ValueError("%s: bad row %r" % (what, line))
+    out = []
+    for key, cell in zip(keys, tok[len(head):]):
+        k, _, v = cell.partition("=")
+        if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
+            raise ValueError("%s: bad field %r" % (what, cell))
+        out.append(int(v))
+    return out
+
+
+def parse_label_score_file(text):
+    """the inverse of format_label_score -> uint64[L+1][8]"""
+    lines = text.split("\n")
+    if not 3 <= len(lines) <= 257 or lines[-1] != "":
+        raise ValueError("label score file: a frame row and 1 to 255 label rows expected")
+    t = np.zeros((len(lines) - 1, len(LSCORE_FIELDS) + 1), np.uint64)
+    t[0, :len(LSCORE_FRAME_FIELDS)] = _score_cells("label score file", lines[0], ["frame"], LSCORE_FRAME_FIELDS)
+    for k in range(1, len(t)):
+        t[k, :len(LSCORE_FIELDS)] = _score_cells("label score file", lines[k], ["label", "%d" % k], LSCORE_FIELDS)
+    return t
+
+
+def add_label_scores(tables):
+    """the pooled table of several: the integer sum field by field, a table of fewer labels padded with zero rows --
+    the table of all their maps together, but that a label above a table's own L stays where that table counted it, in
+    gt_above / est_above"""
+    ts = [np.asarray(t, np.uint64).reshape(-1, len(LSCORE_FIELDS) + 1) for t in tables]
+    out = np.zeros((max([len(t) for t in ts] + [2]), len(LSCORE_FIELDS) + 1), np.uint64)
+    for t in ts:
+        out[:len(t)] += t
+    return out
+
+
+def _pr_f(hit_est, n_est, hit_gt, n_gt):
+    """(P, R, F) of a boundary match by the DAVIS toolkit's conventions for empty sets"""
+    if n_est == 0 and n_gt > 0:
+        P, R = 1.0, 0.0
+    elif n_est > 0 and n_gt == 0:
+        P, R = 0.0, 1.0
+    elif n_est == 0 and n_gt == 0:
+        P, R = 1.0, 1.0
+    else:
+        P, R = hit_est / n_est, hit_gt / n_gt
+    return P, R, 2.0 * P * R / (P + R) if P + R else 0.0
+
+
+def label_score_summary(table):
+    """dict(labels={k: dict(J, P, R, F)}, J, F, JF, frame=dict(...)) of a table, float64: J = inter / (gt + est - inter), 1
+    when the union is empty; P = est_hit / est_b and R = gt_hit / gt_b with the DAVIS toolkit's conventions (est_b = 0 <
+    gt_b: 1, 0; gt_b = 0 < est_b: 0, 1; both 0: 1, 1); F = 2 P R / (P + R), 0 when P + R = 0; J, F the means over the
+    labels and JF their mean"""
+    t = np.asarray(table, np.uint64).reshape(-1, len(LSCORE_FIELDS) + 1)
+    labels = {}
+    for k in range(1, len(t)):
+        gt, est, inter, gt_b, est_b, gt_hit, est_hit = (int(v) for v in t[k, :7])
+        union = gt + est - inter
+        P, R, F = _pr_f(est_hit, est_b, gt_hit, gt_b)
+        labels[k] = dict(J=inter / union if union else 1.0, P=P, R=R, F=F)
+    J = sum(v["J"] for v in labels.values()) / len(labels)
+    F = sum(v["F"] for v in labels.values()) / len(labels)
+    return dict(labels=labels, J=J, F=F, JF=(J + F) / 2.0, frame={f: int(v) for f, v in zip(LSCORE_FRAME_FIELDS, t[0])})
+
+
+def format_map_score(score):
+    """the text of a map score file, of dict(hist uint64[2][256], thr, match uint64[m][4]): `neg` and `pos` followed by
+    the 256 counts of the class, then per threshold `match thr=.. a=.. b=.. a_hit=.. b_hit=..`; integers only; the C++
+    worker writes the same bytes"""
+    h = np.asarray(score["hist"], np.uint64).reshape(2, 256)
+    lines = [name + "".join(" %d" % int(v) for v in row) for name, row in zip(("neg", "pos"), h)]
+    match = np.asarray(score.get("match", ()), np.uint64).reshape(-1, 4)
+    lines += ["match thr=%d " % t + " ".join("%s=%d" % (f, int(v)) for f, v in zip(MSCORE_MATCH_FIELDS, q))
+              for t, q in zip(score.get("thr", ()), match)]
+    return "\n".join(lines) + "\n"
+
+
+def parse_map_score_file(text):
+    """the inverse of format_map_score -> dict(hist, thr, match)"""
+    lines = text.split("\n")
+    if not 3 <= len(lines) <= 3 + MSCORE_MAX_THR or lines[-1] != "":
+        raise ValueError("map score file: two histogram rows and up to %d match rows expected" % MSCORE_MAX_THR)
+    hist = np.zeros((2, 256), np.uint64)
+    for c, name in enumerate(("neg", "pos")):
+        tok = lines[c].split(" ")
+        if tok[0] != name or len(tok) != 257 or not all(re.match(r"[0-9]{1,20}$", v) and int(v) < 1 << 64 for v in tok[1:]):
+            raise ValueError("map score file: bad row %r" % lines[c][:40])
+        hist[c] = [int(v) for v in tok[1:]]
+    thr, match = [], np.zeros((len(lines) - 3, 4), np.uint64)
+    for j, line in enumerate(lines[2:-1]):
+        cells = _score_cells("map score file", line, ["match"], ("thr",) + MSCORE_MATCH_FIELDS)
+        if not 1 <= cells[0] <= 255:
+            raise ValueError("map score file: bad threshold in %r" % line)
+        thr.append(cells[0])
+        match[j] = cells[1:]
+    return dict(hist=hist, thr=tuple(thr), match=match)
+
+
+def add_map_scores(scores):
+    """the pooled score of several: the integer sums of the histograms and, threshold by threshold, of the match rows --
+    exactly the score of all their maps together.  The scores have the same thresholds."""
+    scores = list(scores)
+    thr = tuple(scores[0]["thr"]) if scores else ()
+    hist, match = np.zeros((2, 256), np.uint64), np.zeros((len(thr), 4), np.uint64)
+    for s in scores:
+        if tuple(s["thr"]) != thr:
+            raise ValueError("add_map_scores: thresholds %r and %r" % (thr, tuple(s["thr"])))
+        hist += np.asarray(s["hist"], np.uint64).reshape(2, 256)
+        match += np.asarray(s["match"], np.uint64).reshape(len(thr), 4)
+    return dict(hist=hist, thr=thr, match=match)
+
+
+def map_score_summary(score):
+    """the pixelwise precision / recall curve of a score and what follows from it, float64: with TP(t) the positives and
+    FP(t) the negatives with est >= t, t = 1..255: P(t) = TP / (TP + FP), 1 when nothing is predicted, R(t) = TP / pos
+    (1 without positives) -> dict(pos, neg, P, R (arrays indexed by t, entry 0 unused), f128 = F at t = 128, best_f and
+    best_t (the smallest t of the best F), ap = sum_t (R(t) - R(t + 1)) P(t) with R(256) = 0, match = {thr: dict(P, R, F)}
+    by the conventions of label_score_summary)"""
+    h = np.asarray(score["hist"], np.uint64).reshape(2, 256)
+    neg, pos = [[int(v) for v in row] for row in h]
+    n_pos = sum(pos)
+    P, R, F = [float("nan")] * 256, [float("nan")] * 256, [float("nan")] * 256
+    tp = fp = 0
+    for t in range(255, 0, -1):
+        tp, fp = tp + pos[t], fp + neg[t]
+        P[t] = tp / (tp + fp) if tp + fp else 1.0
+        R[t] = tp / n_pos if n_pos else 1.0
+        F[t] = 2.0 * P[t] * R[t] / (P[t] + R[t]) if P[t] + R[t] else 0.0
+    ap = sum((R[t] - (R[t + 1] if t < 255 else 0.0)) * P[t] for t in range(1, 256))
+    best_t = max(range(1, 256), key=lambda t: (F[t], -t))
+    match = {}
+    for t, q in zip(score.get("thr", ()), np.asarray(score.get("match", ()), np.uint64).reshape(-1, 4)):
+        a, b, a_hit, b_hit = (int(v) for v in q)
+        match[int(t)] = dict(zip("PRF", _pr_f(b_hit, b, a_hit, a)))
+    return dict(pos=n_pos, neg=sum(neg), P=np.asarray(P), R=np.asarray(R), f128=F[128], best_f=F[best_t], best_t=best_t,
+                ap=ap, match=match)
+
+
+def _load_score_maps(word, spec):
+    gt, est = load_mask_red(spec.gt), load_mask_red(spec.est)
+    skip = load_mask_red(spec.skip) if spec.skip else None
+    for path, a in ((spec.est, est), (spec.skip, skip)):
+        if a is not None and a.shape != gt.shape:
+            raise ValueError("%s line: %s differs in size from %s" % (word, path, spec.gt))
+    return gt, est, skip
+
+
+def run_lscore(state, spec):
+    """one `lscore` line: read the maps, one opt.label_score, write the table as text"""
+    from . import opt
+    gt, est, skip = _load_score_maps(LSCORE_WORD, spec)
+    table = opt.label_score(state, gt, est, spec.L, spec.radius, skip=skip)["table"][0]
+    with open(spec.out, "w") as f:
+        f.write(format_label_score(table))
+    return table
+
+
+def run_mscore(state, spec):
+    """one `mscore` line: read the maps, one opt.map_score, write the score as text"""
+    from . import opt
+    gt, est, skip = _load_score_maps(MSCORE_WORD, spec)
+    r = opt.map_score(state, gt, est, skip=skip, thr=spec.thr, radius=spec.radius or 0)
+    score = dict(hist=r["hist"][0], thr=tuple(spec.thr), match=r["match"][0])
+    with open(spec.out, "w") as f:
+        f.write(format_map_score(score))
+    return score
+
+
 class InterpLine(NamedTuple):
     """an `interp` line (DESIGN.md "Frames from flows"), recognised by its first word: the in-between frames of a pair
     from a flow estimate
@@ -1408,8 +1684,13 @@ def parse_line(line):
     """a list line, as text or as its tokens -> SolveLine, or parse_layers' dict when its first word is `layers`, a
     BgLine when it is `bg`, a TexLine when it is `tex`, a TrkLine when it is `trk`, a BlurLine when it is `blur`, a
     LightLine when it is `light`, a SegLine when it is `seg`, a ScoreLine when it is `score`, a TScoreLine when it is
-    `tscore`, a ChainLine when it is `chain`, an FScoreLine when it is `fscore`, an InterpLine when it is `interp`"""
+    `tscore`, a ChainLine when it is `chain`, an FScoreLine when it is `fscore`, an InterpLine when it is `interp`, an
+    LScoreLine when it is `lscore`, an MScoreLine when it is `mscore`"""
     tok = line.split() if isinstance(line, str) else list(line)
+    if tok and tok[0] == LSCORE_WORD:
+        return parse_lscore(tok)
+    if tok and tok[0] == MSCORE_WORD:
+        return parse_mscore(tok)
     if tok and tok[0] == INTERP_WORD:
         return parse_interp(tok)
     if tok and tok[0] == FSCORE_WORD:
@@ -1463,6 +1744,10 @@ def format_line(item):
         return chain_line(item)
     if isinstance(item, FScoreLine):
         return fscore_line(item)
+    if isinstance(item, LScoreLine):
+        return lscore_line(item)
+    if isinstance(item, MScoreLine):
+        return mscore_line(item)
     if isinstance(item, InterpLine):
         return interp_line(item)
     return layers_line(item["rgb"], item["layers"], item["out"])
@@ -1471,8 +1756,8 @@ def format_line(item):
 def done_token(item):
     """the path `arap_deform --serve` reports a line done by: a solve's flow, a layers line's first output token, the
     first of a bg line's bg_outputs, a tex, blur, light or seg line's first output token, a trk line's track file, a score,
-    tscore, chain or fscore line's out= file, an interp line's out= prefix"""
-    if isinstance(item, (TrkLine, ScoreLine, TScoreLine, ChainLine, FScoreLine, InterpLine)):
+    tscore, chain, fscore, lscore or mscore line's out= file, an interp line's out= prefix"""
+    if isinstance(item, (TrkLine, ScoreLine, TScoreLine, ChainLine, FScoreLine, InterpLine, LScoreLine, MScoreLine)):
         return item.out
     if isinstance(item, (BlurLine, LightLine, SegLine)):
         return next(iter(item.out.values()))

@@ -739,6 +739,49 @@ int ArapFlow_ChainFlows(Opt_State* state, unsigned W, unsigned H, unsigned L, co
 int ArapFlow_FrameScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* ref, const void* est,
                         const void* occ, const void* dist, const void* skip, const void* obj, void* table, void* ssim);
 
+/* Map scoring (DESIGN.md "Map scoring"): the scorers of the fourth kind of ground truth, the maps -- DAVIS J (region
+ * similarity) and F (boundary accuracy) per object of estimated label maps, and the precision / recall histogram of
+ * estimated occlusion or motion-boundary maps -- over n maps of one size, on DEVICE buffers, in integers only.
+ *   gt, est  uint8[n][H][W];  skip uint8[n][H][W] or NULL, non-zero = the pixel is left out;  a pixel with skip == 0 (or
+ *            no skip plane) is "counted".  radius 0 .. ARAPFLOW_SEG_MAX_RADIUS.
+ * Boundary match of two pixel sets A (from gt) and B (from est): the skipped pixels are removed from both (they are
+ * neither counted nor targets); a = |A|, b = |B|; a_hit = the number of p in A for which some q in B has
+ * (p.x - q.x)^2 + (p.y - q.y)^2 <= radius^2; b_hit the same with the roles swapped.  With radius 0 a hit is the same
+ * pixel.  (The DAVIS toolkit's f_measure: dilation by disk(radius), then intersection; no thinning.)
+ * bmap(m) of a binary map m, the toolkit's seg2bmap at equal size: for x < W-1, y < H-1:
+ *   b = m[y][x] != m[y][x+1] | m[y][x] != m[y+1][x] | m[y][x] != m[y+1][x+1];  last row, x < W-1: m[y][x] != m[y][x+1];
+ *   last column, y < H-1: m[y][x] != m[y+1][x];  the bottom-right pixel: 0.  It is formed on the whole mask, skipped
+ *   pixels included; the match then removes them (the toolkit's handling of void pixels).
+ *
+ * ArapFlow_LabelScore: gt, est are label maps (ArapFlow_SegMaps' idx1 / idx2: 0 = no object), 1 <= L <= 255 labels are
+ * scored.  table uint64[n][L + 1][ARAPFLOW_LSCORE_FIELDS], cleared by the call:
+ *   row 0:            0 counted pixels  1 skipped pixels  2 counted with gt == est  3 counted with gt > L
+ *                     4 counted with est > L  5..7 zero
+ *   row k, 1..L:      0 gt: counted with gt == k  1 est: counted with est == k  2 inter: counted with both
+ *                     3 gt_b, 4 est_b, 5 gt_hit, 6 est_hit: a, b, a_hit, b_hit of the boundary match of
+ *                     A = bmap(gt == k), B = bmap(est == k)   7 zero
+ * ArapFlow_MapScore: gt is binary (non-zero = positive), est a score 0..255 (a hard map written 0 / 255 is one).
+ *   hist   uint64[n][2][256], cleared by the call: hist[c][v] = the counted pixels with (gt != 0) == c and est == v; the
+ *          skipped pixels are W * H minus its sum.
+ *   m, thr 0 <= m <= ARAPFLOW_MSCORE_MAX_THR thresholds, a HOST array, each 1..255; for threshold j the boundary match
+ *          of A = {gt != 0}, B = {est >= thr[j]} goes to match uint64[n][m][4] as (a, b, a_hit, b_hit), cleared by the
+ *          call.  With m = 0 thr, match and scratch may be NULL and neither a set nor a distance pass is launched.
+ * scratch: ArapFlow_MapScoreScratchBytes(W, H) bytes (7 a pixel, 256-byte aligned, whatever n, L and m; 0 for sizes the
+ * calls refuse), 256-byte aligned; it serves both calls.
+ * Integer atomics only: two runs give identical bytes and tables add exactly.  Asynchronous on the state's stream.
+ * Return 0; -1, and nothing is launched or written, on bad arguments: a null state, gt, est, table or hist, n = 0,
+ * W * H = 0, n * W * H >= 2^31, L = 0 or L > 255, radius > ARAPFLOW_SEG_MAX_RADIUS, m > ARAPFLOW_MSCORE_MAX_THR, a
+ * threshold of 0 or above 255, m > 0 with a null thr, match or scratch, a label call with a null scratch, an output
+ * (the scratch is one) overlapping an input or another output; else a HIP error code. */
+#define ARAPFLOW_LSCORE_FIELDS 8
+#define ARAPFLOW_MSCORE_MAX_THR 8
+uint64_t ArapFlow_MapScoreScratchBytes(unsigned W, unsigned H);
+int ArapFlow_LabelScore(Opt_State* state, unsigned W, unsigned H, unsigned n, unsigned L, unsigned radius, const void* gt,
+                        const void* est, const void* skip, void* table, void* scratch);
+int ArapFlow_MapScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* gt, const void* est,
+                      const void* skip, unsigned m, const unsigned* thr, unsigned radius, void* hist, void* match,
+                      void* scratch);
+
 /* Frames from flows (DESIGN.md "Frames from flows"): the in-between frames of a pair at K times from an estimated flow,
  * by flow splatting (Baker et al., IJCV 2011, section 3.3.2: splat the flow to time t, fill small holes, fetch both frames
  * along the flow with an occlusion test, blend), in integers wherever a result is stored.  On DEVICE buffers, but for
