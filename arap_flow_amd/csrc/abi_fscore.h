@@ -7,18 +7,12 @@ extern "C" {
 int ArapFlow_FrameScore(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* ref, const void* est, const void* occ,
                         const void* dist, const void* skip, const void* obj, void* table, void* ssim)
 {
-    if (!st || !ref || !est || !table || n == 0 || W == 0 || H == 0) return -1;
-    const uint64_t N = (uint64_t)W * H;
-    if (N >= (1ull << 31) || n * N >= (1ull << 31)) return -1;
-    const uint64_t all = n * N;
+    if (!st || !ref || !est || !table || !sizes_ok(W, H, n)) return -1;
+    const uint64_t all = (uint64_t)n * W * H;
     const std::pair<const void*, uint64_t> bufs[] = {{table, (uint64_t)n * FSCORE_ROWS * FSCORE_FIELDS * 8}, {ssim, all * 4},
                                                      {ref, all * 3}, {est, all * 3}, {occ, all}, {dist, all * 2}, {skip, all},
                                                      {obj, all}};
-    for (int o = 0; o < 2; ++o)                          // both outputs against every later buffer of the table
-        for (int k = o + 1; k < 8; ++k) {
-            const uintptr_t a = (uintptr_t)bufs[o].first, b = (uintptr_t)bufs[k].first;
-            if (a && b && a < b + bufs[k].second && b < a + bufs[o].second) return -1;
-        }
+    if (buffers_overlap(bufs, 2, 8)) return -1;
     FScoreJob j{};
     j.ref = (const uint8_t*)ref; j.est = (const uint8_t*)est;
     j.occ = (const uint8_t*)occ; j.dist = (const uint16_t*)dist; j.skip = (const uint8_t*)skip; j.obj = (const uint8_t*)obj;

@@ -28,7 +28,7 @@ int ArapFlow_InterpFrames(Opt_State* st, unsigned W, unsigned H, const void* A, 
     const uint64_t N = (uint64_t)W * H, all = K * N, keys = all * 8;
     const std::pair<const void*, uint64_t> bufs[] = {{out, all * 3}, {src, all}, {scratch, align_up(keys, 256)}, {A, N * 3}, {B, N * 3},
                                                      {fwd, N * 8}, {bwd, N * 8}};
-    if (tscore_overlap(bufs, 3, 7)) return -1;
+    if (buffers_overlap(bufs, 3, 7)) return -1;
     InterpJob j{};
     j.A = (const uint8_t*)A; j.B = (const uint8_t*)B; j.fwd = (const float2*)fwd; j.bwd = (const float2*)bwd;
     j.key = (unsigned long long*)scratch; j.out = (uint8_t*)out; j.src = (uint8_t*)src;

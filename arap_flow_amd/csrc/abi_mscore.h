@@ -16,23 +16,6 @@ static MScoreScratch mscore_scratch(uint64_t N)
     return L;
 }
 
-static bool mscore_sizes_ok(unsigned W, unsigned H, unsigned n)
-{
-    const uint64_t N = (uint64_t)W * H;
-    return n != 0 && N != 0 && N < (1ull << 31) && n * N < (1ull << 31);
-}
-
-// does any of the first `outs` buffers overlap a later one of the table?
-static bool mscore_overlap(const std::pair<const void*, uint64_t>* bufs, int outs, int count)
-{
-    for (int o = 0; o < outs; ++o)
-        for (int k = o + 1; k < count; ++k) {
-            const uintptr_t a = (uintptr_t)bufs[o].first, b = (uintptr_t)bufs[k].first;
-            if (a && b && a < b + bufs[k].second && b < a + bufs[o].second) return true;
-        }
-    return false;
-}
-
 static MScoreJob mscore_job(const void* gt, const void* est, const void* skip, void* out, unsigned W, unsigned H, unsigned n,
                             unsigned L)
 {
@@ -76,18 +59,18 @@ extern "C" {
 // per pixel: 1 + 1 (the two sets) + 1 (column distance) + 2 + 2 (the two squared distances) = 7 bytes, whatever n, L and m
 uint64_t ArapFlow_MapScoreScratchBytes(unsigned W, unsigned H)
 {
-    return mscore_sizes_ok(W, H, 1) ? mscore_scratch((uint64_t)W * H).total : 0;
+    return sizes_ok(W, H, 1) ? mscore_scratch((uint64_t)W * H).total : 0;
 }
 
 int ArapFlow_LabelScore(Opt_State* st, unsigned W, unsigned H, unsigned n, unsigned L, unsigned radius, const void* gt,
                         const void* est, const void* skip, void* table, void* scratch)
 {
-    if (!st || !gt || !est || !table || !scratch || !mscore_sizes_ok(W, H, n)) return -1;
+    if (!st || !gt || !est || !table || !scratch || !sizes_ok(W, H, n)) return -1;
     if (L == 0 || L > 255 || radius > (unsigned)SEG_MAX_RADIUS) return -1;
     const uint64_t all = (uint64_t)n * W * H, bytes = (uint64_t)n * (L + 1) * LSCORE_FIELDS * 8;
     const std::pair<const void*, uint64_t> bufs[] = {{table, bytes}, {scratch, mscore_scratch((uint64_t)W * H).total},
                                                      {gt, all}, {est, all}, {skip, all}};
-    if (mscore_overlap(bufs, 2, 5)) return -1;
+    if (buffers_overlap(bufs, 2, 5)) return -1;
     const MScoreJob j = mscore_job(gt, est, skip, table, W, H, n, L);
     HC(hipMemsetAsync(table, 0, bytes, st->stream));
     SEG_LAUNCH(st, "k_mscore_labels", k_mscore_count<true>, mscore_count_grid(j.N, n), dim3(256), j);
@@ -101,7 +84,7 @@ int ArapFlow_LabelScore(Opt_State* st, unsigned W, unsigned H, unsigned n, unsig
 int ArapFlow_MapScore(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* gt, const void* est, const void* skip,
                       unsigned m, const unsigned* thr, unsigned radius, void* hist, void* match, void* scratch)
 {
-    if (!st || !gt || !est || !hist || !mscore_sizes_ok(W, H, n)) return -1;
+    if (!st || !gt || !est || !hist || !sizes_ok(W, H, n)) return -1;
     if (m > (unsigned)MSCORE_MAX_THR || radius > (unsigned)SEG_MAX_RADIUS) return -1;
     if (m && (!thr || !match || !scratch)) return -1;
     for (unsigned k = 0; k < m; ++k)
@@ -110,7 +93,7 @@ int ArapFlow_MapScore(Opt_State* st, unsigned W, unsigned H, unsigned n, const v
     const std::pair<const void*, uint64_t> bufs[] = {{hist, hbytes}, {m ? match : nullptr, mbytes},
                                                      {m ? scratch : nullptr, mscore_scratch((uint64_t)W * H).total},
                                                      {gt, all}, {est, all}, {skip, all}};
-    if (mscore_overlap(bufs, 3, 6)) return -1;
+    if (buffers_overlap(bufs, 3, 6)) return -1;
     const MScoreJob j = mscore_job(gt, est, skip, hist, W, H, n, 0);
     HC(hipMemsetAsync(hist, 0, hbytes, st->stream));
     if (m) HC(hipMemsetAsync(match, 0, mbytes, st->stream));

@@ -18,17 +18,11 @@ extern "C" {
 int ArapFlow_FlowScore(Opt_State* st, unsigned W, unsigned H, unsigned n, const void* gt, const void* est, const void* occ,
                        const void* dist, const void* skip, void* table, void* err)
 {
-    if (!st || !gt || !est || !table || n == 0 || W == 0 || H == 0) return -1;
-    const uint64_t N = (uint64_t)W * H;
-    if (N >= (1ull << 31) || n * N >= (1ull << 31)) return -1;
-    const uint64_t all = n * N;
+    if (!st || !gt || !est || !table || !sizes_ok(W, H, n)) return -1;
+    const uint64_t N = (uint64_t)W * H, all = n * N;
     const std::pair<const void*, uint64_t> bufs[] = {{table, (uint64_t)n * SCORE_ROWS * SCORE_FIELDS * 8}, {err, all * 4},
                                                      {gt, all * 8}, {est, all * 8}, {occ, all}, {dist, all * 2}, {skip, all}};
-    for (int o = 0; o < 2; ++o)                          // both outputs against every later buffer of the table
-        for (int k = o + 1; k < 7; ++k) {
-            const uintptr_t a = (uintptr_t)bufs[o].first, b = (uintptr_t)bufs[k].first;
-            if (a && b && a < b + bufs[k].second && b < a + bufs[o].second) return -1;
-        }
+    if (buffers_overlap(bufs, 2, 7)) return -1;
     ScoreJob j{};
     j.gt = (const float2*)gt; j.est = (const float2*)est;
     j.occ = (const uint8_t*)occ; j.dist = (const uint16_t*)dist; j.skip = (const uint8_t*)skip;

@@ -76,11 +76,7 @@ int ArapFlow_SegMaps(Opt_State* st, unsigned W, unsigned H, unsigned n, const vo
     const std::pair<const void*, uint64_t> bufs[] = {{idx1, N64}, {idx2, N64}, {mb1, N64}, {mb2, N64}, {dist1, 2 * N64},
                                                      {dist2, 2 * N64}, {masks_red, n * N64}, {flows, n * N64 * 8},
                                                      {scratch, L.total}};
-    for (int o = 0; o < 6; ++o)                          // every output against every later buffer of the table
-        for (int k = o + 1; k < 9; ++k) {
-            const uintptr_t a = (uintptr_t)bufs[o].first, b = (uintptr_t)bufs[k].first;
-            if (a && b && a < b + bufs[k].second && b < a + bufs[o].second) return -1;
-        }
+    if (buffers_overlap(bufs, 6, 9)) return -1;
     char* const c = (char*)scratch;
     float2* const F = (float2*)(c + L.flow);
     uint8_t* const g = (uint8_t*)(c + L.g);

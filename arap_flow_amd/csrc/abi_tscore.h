@@ -2,17 +2,6 @@
 // arap_chain.h): the argument checks and the one launch of each call.
 #pragma once
 
-// true where two of the buffers that are given overlap: the first `outs` of the table against every later one
-static bool tscore_overlap(const std::pair<const void*, uint64_t>* bufs, int outs, int n)
-{
-    for (int o = 0; o < outs; ++o)
-        for (int k = o + 1; k < n; ++k) {
-            const uintptr_t a = (uintptr_t)bufs[o].first, b = (uintptr_t)bufs[k].first;
-            if (a && b && a < b + bufs[k].second && b < a + bufs[o].second) return true;
-        }
-    return false;
-}
-
 extern "C" {
 
 int ArapFlow_TrackScore(Opt_State* st, unsigned F, unsigned P, const void* gt_pos, const void* gt_occ, const void* est_pos,
@@ -24,7 +13,7 @@ int ArapFlow_TrackScore(Opt_State* st, unsigned F, unsigned P, const void* gt_po
     const uint64_t all = (uint64_t)F * P, bytes = (uint64_t)F * TSCORE_CELLS * 8;
     const std::pair<const void*, uint64_t> bufs[] = {{table, bytes}, {gt_pos, all * 8}, {gt_occ, all}, {est_pos, all * 8},
                                                      {est_occ, all}};
-    if (tscore_overlap(bufs, 1, 5)) return -1;
+    if (buffers_overlap(bufs, 1, 5)) return -1;
     TScoreJob j{};
     j.gt_pos = (const float2*)gt_pos; j.est_pos = (const float2*)est_pos;
     j.gt_occ = (const uint8_t*)gt_occ; j.est_occ = (const uint8_t*)est_occ;
@@ -54,7 +43,7 @@ int ArapFlow_ChainFlows(Opt_State* st, unsigned W, unsigned H, unsigned L, const
     const uint64_t all = (uint64_t)(L + 1) * P;
     const std::pair<const void*, uint64_t> bufs[] = {{out_pos, all * 8}, {out_occ, all}, {flows, L * N * 8}, {bwd, L * N * 8},
                                                      {points, (uint64_t)P * 8}};
-    if (tscore_overlap(bufs, 2, 5)) return -1;
+    if (buffers_overlap(bufs, 2, 5)) return -1;
     ChainJob j{};
     j.flows = (const float2*)flows; j.bwd = (const float2*)bwd; j.points = (const float2*)points;
     j.pos = (float2*)out_pos; j.occ = (uint8_t*)out_occ;

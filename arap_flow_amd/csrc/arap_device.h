@@ -198,6 +198,31 @@ __device__ __forceinline__ double wave_sum_full(double v)
                             __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
+// The wave's sum / maximum of an unsigned word in LANE 63, all 64 lanes active: the DPP tree of wave_sum_l63 on
+// integers (the score kernels' tables).  A lane a step leaves without a source takes 0, the identity of both.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned dpp_u32(unsigned v)
+{
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+template <bool MAX>
+__device__ __forceinline__ unsigned wave_reduce_u32_l63(unsigned v)
+{
+#define WAVE_U32_STEP(CTRL, ROW_MASK)                           \
+    {                                                           \
+        const unsigned u = dpp_u32<CTRL, ROW_MASK>(v);          \
+        v = MAX ? max(v, u) : v + u;                            \
+    }
+    WAVE_U32_STEP(0x111, 0xf)             // row_shr:1
+    WAVE_U32_STEP(0x112, 0xf)             // row_shr:2
+    WAVE_U32_STEP(0x114, 0xf)             // row_shr:4
+    WAVE_U32_STEP(0x118, 0xf)             // row_shr:8 -> lane 15 of every row holds the row's
+    WAVE_U32_STEP(0x142, 0xa)             // row_bcast:15 into rows 1 and 3
+    WAVE_U32_STEP(0x143, 0xc)             // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave's
+#undef WAVE_U32_STEP
+    return v;
+}
+
 // ---- order-fixed reduction of one (or two) doubles over all workgroups of a launch ------------------------------
 // The reference adds per-warp partials with red.global.add.f32 in arrival order (solverGPUGaussNewton.t:312-317): its
 // sums differ from run to run.  Here a launch's sum does not depend on the order in which workgroups finish:

@@ -38,7 +38,6 @@
 #pragma once
 #include "../../include/arap_opt.h"
 #include "arap_device.h"
-#include "arap_score.h"
 
 namespace arap {
 
@@ -223,19 +222,19 @@ __global__ __launch_bounds__(256) void k_frame_score(FScoreJob j)
             for (int c = 0; c < NC; ++c) {
                 unsigned w[FSCORE_WORDS] = {0u, 0u, 0u, 0u, 0u, 0u};
                 if (c == 0 || (c < 3 ? has_occ : c < 6 ? has_dist : has_obj)) {
-                    w[0] = score_wave_l63<false>(a.sse[c]);
-                    w[1] = score_wave_l63<false>(a.sad[c]);
-                    w[2] = score_wave_l63<false>(a.cw[c]);
-                    w[3] = score_wave_l63<true>(a.mx[c]);
-                    w[4] = score_wave_l63<false>(a.qs[c]);
-                    w[5] = score_wave_l63<true>(a.worst[c]);
+                    w[0] = wave_reduce_u32_l63<false>(a.sse[c]);
+                    w[1] = wave_reduce_u32_l63<false>(a.sad[c]);
+                    w[2] = wave_reduce_u32_l63<false>(a.cw[c]);
+                    w[3] = wave_reduce_u32_l63<true>(a.mx[c]);
+                    w[4] = wave_reduce_u32_l63<false>(a.qs[c]);
+                    w[5] = wave_reduce_u32_l63<true>(a.worst[c]);
                 }
                 if (lane == 63u)
 #pragma unroll
                     for (int k = 0; k < FSCORE_WORDS; ++k) red[wave][c * FSCORE_WORDS + k] = w[k];
             }
             {
-                const unsigned left = score_wave_l63<false>(a.left);
+                const unsigned left = wave_reduce_u32_l63<false>(a.left);
                 if (lane == 63u) red[wave][FSCORE_RED - 1] = left;
             }
             __syncthreads();

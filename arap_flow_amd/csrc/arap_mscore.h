@@ -20,13 +20,13 @@
 // pixel would serialise a wave on one address.  A wave therefore aggregates before any atomic: for each of the 16 pixel
 // slots of a group it loops over the DISTINCT keys its lanes hold (readlane, ballot of the lanes with that key,
 // popcount) and one lane adds the count to the block's LDS table, one LDS add per distinct key and wave.  The counts of
-// row 0 are kept per lane (fewer than 2^31 pixels) and summed over the wave once per map, by k_flow_score's DPP tree.
+// row 0 are kept per lane (fewer than 2^31 pixels) and summed over the wave once per map, by arap_device.h's integer DPP tree.
 // The LDS table holds full 32-bit words (a block sees fewer than 2^31 pixels of a map: n * W * H < 2^31), and only its
 // non-zero entries reach the 64-bit table, by integer vector atomics.  Every loop that holds a ballot or a barrier has
 // a trip count that is uniform over the wave (block).
 #pragma once
 #include "../../include/arap_opt.h"
-#include "arap_score.h"
+#include "arap_device.h"
 #include "arap_seg.h"
 
 namespace arap {
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_mscore_count(MScoreJob j)
         if (LABELS)
 #pragma unroll
             for (int f = 0; f < MSCORE_FRAME_WORDS; ++f) {
-                const unsigned w = score_wave_l63<false>(fr[f]);             // all 64 lanes are here
+                const unsigned w = wave_reduce_u32_l63<false>(fr[f]);             // all 64 lanes are here
                 if (lane == 63u && w) atomicAdd(&tab[MSCORE_LABEL_WORDS + f], w);
             }
         __syncthreads();

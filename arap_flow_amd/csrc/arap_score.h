@@ -92,31 +92,6 @@ __device__ __forceinline__ float score_pixel(ScoreAcc& a, float2 g, float2 s, un
     return counted ? e : -1.f;
 }
 
-// The wave's sum / maximum of an unsigned word in LANE 63, all 64 lanes active: the DPP tree of wave_sum_l63
-// (arap_device.h) on integers.  A lane a step leaves without a source takes 0, the identity of both.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned score_dpp(unsigned v)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-template <bool MAX>
-__device__ __forceinline__ unsigned score_wave_l63(unsigned v)
-{
-#define SCORE_STEP(CTRL, ROW_MASK)                              \
-    {                                                           \
-        const unsigned u = score_dpp<CTRL, ROW_MASK>(v);        \
-        v = MAX ? max(v, u) : v + u;                            \
-    }
-    SCORE_STEP(0x111, 0xf)                // row_shr:1
-    SCORE_STEP(0x112, 0xf)                // row_shr:2
-    SCORE_STEP(0x114, 0xf)                // row_shr:4
-    SCORE_STEP(0x118, 0xf)                // row_shr:8 -> lane 15 of every row holds the row's
-    SCORE_STEP(0x142, 0xa)                // row_bcast:15 into rows 1 and 3
-    SCORE_STEP(0x143, 0xc)                // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave's
-#undef SCORE_STEP
-    return v;
-}
-
 // field f of class c from the block's totals
 __device__ __forceinline__ unsigned long long score_field(const unsigned* tot, int c, int f)
 {
@@ -186,19 +161,19 @@ __global__ __launch_bounds__(256) void k_flow_score(ScoreJob j)
         for (int c = C0; c < SCORE_CLASSES; ++c) {
             unsigned w[SCORE_WORDS] = {0u, 0u, 0u, 0u, 0u, 0u};
             if (c >= SCORE_FIRST_SPEED || (c < 2 ? has_occ : has_dist)) {
-                w[0] = score_wave_l63<false>(a.cnt[c] & 0x00ff00ffu);
-                w[1] = score_wave_l63<false>((a.cnt[c] >> 8) & 0x00ff00ffu);
-                w[2] = score_wave_l63<false>(a.out[c]);
-                w[3] = score_wave_l63<false>(a.sum[c] & 0xffffu);
-                w[4] = score_wave_l63<false>(a.sum[c] >> 16);
-                w[5] = score_wave_l63<true>(a.mx[c]);
+                w[0] = wave_reduce_u32_l63<false>(a.cnt[c] & 0x00ff00ffu);
+                w[1] = wave_reduce_u32_l63<false>((a.cnt[c] >> 8) & 0x00ff00ffu);
+                w[2] = wave_reduce_u32_l63<false>(a.out[c]);
+                w[3] = wave_reduce_u32_l63<false>(a.sum[c] & 0xffffu);
+                w[4] = wave_reduce_u32_l63<false>(a.sum[c] >> 16);
+                w[5] = wave_reduce_u32_l63<true>(a.mx[c]);
             }
             if (lane == 63u)
 #pragma unroll
                 for (int k = 0; k < SCORE_WORDS; ++k) red[wave][c * SCORE_WORDS + k] = w[k];
         }
         {
-            const unsigned left = score_wave_l63<false>(a.left);
+            const unsigned left = wave_reduce_u32_l63<false>(a.left);
             if (lane == 63u) red[wave][SCORE_RED - 1] = left;
         }
         __syncthreads();

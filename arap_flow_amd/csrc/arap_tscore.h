@@ -22,14 +22,14 @@
 // and est_vis = agree; a point-frame with gv is in exactly one of the classes 1 and 2, so every field of class 0 that
 // implies gv is the sum (max: the maximum) of theirs; class 0's count is the number of valid points in every frame.
 // sum and max of q are kept per lane over the chunks (<= 32 * 2^24) and reduced across the wave once per frame
-// (score_wave_l63 of arap_score.h; the sum as its low 16 bits and the rest, so that 64 lanes fit a word).
+// (wave_reduce_u32_l63 of arap_device.h; the sum as its low 16 bits and the rest, so that 64 lanes fit a word).
 //
 // Once per frame a wave adds what it has into the block's LDS copy of the table (64-bit cells: a block's sum can pass
 // 2^32) with LDS integer atomics, lane 0 the counts and lane 63 the reductions; the block ends by deriving the
 // dependent fields and one 64-bit integer atomic per non-zero cell of the table.
 #pragma once
 #include "../../include/arap_opt.h"
-#include "arap_score.h"
+#include "arap_device.h"
 
 namespace arap {
 
@@ -86,7 +86,7 @@ struct TScoreCounts {
 // the wave's sum of a lane's sum (<= 2^29) in lane 63, as 64 bits
 __device__ __forceinline__ unsigned long long tscore_wave_sum(unsigned s)
 {
-    const unsigned lo = score_wave_l63<false>(s & 0xffffu), hi = score_wave_l63<false>(s >> 16);
+    const unsigned lo = wave_reduce_u32_l63<false>(s & 0xffffu), hi = wave_reduce_u32_l63<false>(s >> 16);
     return ((unsigned long long)hi << 16) + lo;
 }
 
@@ -186,12 +186,12 @@ __global__ __launch_bounds__(THREADS) void k_track_score(TScoreJob j)
         // the wave's frame into the block's table
         unsigned long long* const row = tab + (size_t)f * TSCORE_CELLS;
         const unsigned long long sum1 = tscore_wave_sum(s1);
-        const unsigned max1 = score_wave_l63<true>(x1);
+        const unsigned max1 = wave_reduce_u32_l63<true>(x1);
         unsigned long long sum2 = 0ull;
         unsigned max2 = 0u;
         if (c2.n) {                                                         // (wave-uniform)
             sum2 = tscore_wave_sum(s2);
-            max2 = score_wave_l63<true>(x2);
+            max2 = wave_reduce_u32_l63<true>(x2);
         }
         if (lane == 0u) {
             tscore_add(row + TSCORE_EST_VIS, est0);

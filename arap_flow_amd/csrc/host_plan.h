@@ -241,6 +241,24 @@ struct Opt_Plan {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the argument checks the scoring and map calls share.  buffers_overlap: of a table {pointer, bytes} with the outputs
+// first, does any of the first `outs` overlap a later one?  A null pointer is a buffer not given.  sizes_ok: n maps of
+// W x H pixels that 31-bit indices address, one map and all together
+static bool buffers_overlap(const std::pair<const void*, uint64_t>* bufs, int outs, int count)
+{
+    for (int o = 0; o < outs; ++o)
+        for (int k = o + 1; k < count; ++k) {
+            const uintptr_t a = (uintptr_t)bufs[o].first, b = (uintptr_t)bufs[k].first;
+            if (a && b && a < b + bufs[k].second && b < a + bufs[o].second) return true;
+        }
+    return false;
+}
+static bool sizes_ok(unsigned W, unsigned H, unsigned n)
+{
+    const uint64_t N = (uint64_t)W * H;
+    return n != 0 && N != 0 && N < (1ull << 31) && n * N < (1ull << 31);
+}
+
 // One way to lay out a device block.  `layout` names the block's parts in order through the Carver it is given, each
 // with its size in bytes; every part starts 256-aligned.  It runs twice: over a null base, which gives the block's
 // size, then over the allocation, which gives the pointers.  `zero`: cleared on the state's stream.

@@ -40,24 +40,35 @@ inline std::string format_diag(const ArapFlow_MeshStats& s)
     return text;
 }
 
+// one row of a score file (scores.format_row): `head`, then ` key=value` for each of `count` integers, then the newline
+inline void append_row(std::string& text, const std::string& head, const char* const* keys, const uint64_t* values, int count)
+{
+    text += head;
+    char cell[64];
+    for (int k = 0; k < count; ++k) {
+        snprintf(cell, sizeof(cell), " %s=%llu", keys[k], (unsigned long long)values[k]);
+        text += cell;
+    }
+    text += "\n";
+}
+
+// a fixed table (scores.FixedTable): a row of `nfields` fields per name of `rows`, then `left_out` with its two keys
+inline std::string format_fixed_table(const uint64_t* table, const char* const* rows, int nrows, const char* const* fields, int nfields,
+                                      const char* const* left_keys)
+{
+    std::string text;
+    for (int r = 0; r < nrows; ++r) append_row(text, rows[r], fields, table + r * nfields, nfields);
+    append_row(text, "left_out", left_keys, table + nrows * nfields, 2);
+    return text;
+}
+
 // the text of a score file (pipeline.format_score): one line per row of ArapFlow_FlowScore's table, integers only
 inline std::string format_score(const uint64_t* table)
 {
     static const char* const rows[ARAPFLOW_SCORE_ROWS - 1] = {"all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+"};
     static const char* const fields[ARAPFLOW_SCORE_FIELDS] = {"count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max"};
-    std::string text;
-    char cell[64];
-    for (int r = 0; r < ARAPFLOW_SCORE_ROWS - 1; ++r) {
-        text += rows[r];
-        for (int f = 0; f < ARAPFLOW_SCORE_FIELDS; ++f) {
-            snprintf(cell, sizeof(cell), " %s=%llu", fields[f], (unsigned long long)table[r * ARAPFLOW_SCORE_FIELDS + f]);
-            text += cell;
-        }
-        text += "\n";
-    }
-    const uint64_t* const left = table + (ARAPFLOW_SCORE_ROWS - 1) * ARAPFLOW_SCORE_FIELDS;
-    snprintf(cell, sizeof(cell), "left_out skipped=%llu gt_nonfinite=%llu\n", (unsigned long long)left[0], (unsigned long long)left[1]);
-    return text + cell;
+    static const char* const left[2] = {"skipped", "gt_nonfinite"};
+    return format_fixed_table(table, rows, ARAPFLOW_SCORE_ROWS - 1, fields, ARAPFLOW_SCORE_FIELDS, left);
 }
 
 // the text of a track score file (pipeline.format_track_score): one line per frame and class of ArapFlow_TrackScore's
@@ -68,18 +79,10 @@ inline std::string format_track_score(const uint64_t* table, unsigned frames)
     static const char* const fields[ARAPFLOW_TSCORE_FIELDS] = {"count", "gt_vis", "est_vis", "agree", "within_1", "within_2", "within_4",
                                                                "within_8", "within_16", "tp_1", "tp_2", "tp_4", "tp_8", "tp_16", "sum", "max"};
     std::string text;
-    char cell[64];
     for (unsigned f = 0; f < frames; ++f)
-        for (int c = 0; c < ARAPFLOW_TSCORE_CLASSES; ++c) {
-            snprintf(cell, sizeof(cell), "%u %s", f, classes[c]);
-            text += cell;
-            for (int k = 0; k < ARAPFLOW_TSCORE_FIELDS; ++k) {
-                snprintf(cell, sizeof(cell), " %s=%llu", fields[k],
-                         (unsigned long long)table[((size_t)f * ARAPFLOW_TSCORE_CLASSES + c) * ARAPFLOW_TSCORE_FIELDS + k]);
-                text += cell;
-            }
-            text += "\n";
-        }
+        for (int c = 0; c < ARAPFLOW_TSCORE_CLASSES; ++c)
+            append_row(text, std::to_string(f) + " " + classes[c], fields,
+                       table + ((size_t)f * ARAPFLOW_TSCORE_CLASSES + c) * ARAPFLOW_TSCORE_FIELDS, ARAPFLOW_TSCORE_FIELDS);
     return text;
 }
 
@@ -88,19 +91,8 @@ inline std::string format_frame_score(const uint64_t* table)
 {
     static const char* const rows[ARAPFLOW_FSCORE_ROWS - 1] = {"all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg"};
     static const char* const fields[ARAPFLOW_FSCORE_FIELDS] = {"count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst"};
-    std::string text;
-    char cell[64];
-    for (int r = 0; r < ARAPFLOW_FSCORE_ROWS - 1; ++r) {
-        text += rows[r];
-        for (int f = 0; f < ARAPFLOW_FSCORE_FIELDS; ++f) {
-            snprintf(cell, sizeof(cell), " %s=%llu", fields[f], (unsigned long long)table[r * ARAPFLOW_FSCORE_FIELDS + f]);
-            text += cell;
-        }
-        text += "\n";
-    }
-    const uint64_t* const left = table + (ARAPFLOW_FSCORE_ROWS - 1) * ARAPFLOW_FSCORE_FIELDS;
-    snprintf(cell, sizeof(cell), "left_out pixels=%llu windows=%llu\n", (unsigned long long)left[0], (unsigned long long)left[1]);
-    return text + cell;
+    static const char* const left[2] = {"pixels", "windows"};
+    return format_fixed_table(table, rows, ARAPFLOW_FSCORE_ROWS - 1, fields, ARAPFLOW_FSCORE_FIELDS, left);
 }
 
 // the text of a label score file (pipeline.format_label_score): the frame's row, then one line per label of
@@ -109,45 +101,25 @@ inline std::string format_label_score(const uint64_t* table, unsigned L)
 {
     static const char* const frame[5] = {"counted", "skipped", "equal", "gt_above", "est_above"};
     static const char* const fields[ARAPFLOW_LSCORE_FIELDS - 1] = {"gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit"};
-    std::string text = "frame";
-    char cell[64];
-    for (int f = 0; f < 5; ++f) {
-        snprintf(cell, sizeof(cell), " %s=%llu", frame[f], (unsigned long long)table[f]);
-        text += cell;
-    }
-    text += "\n";
-    for (unsigned k = 1; k <= L; ++k) {
-        snprintf(cell, sizeof(cell), "label %u", k);
-        text += cell;
-        for (int f = 0; f < ARAPFLOW_LSCORE_FIELDS - 1; ++f) {
-            snprintf(cell, sizeof(cell), " %s=%llu", fields[f], (unsigned long long)table[k * ARAPFLOW_LSCORE_FIELDS + f]);
-            text += cell;
-        }
-        text += "\n";
-    }
+    std::string text;
+    append_row(text, "frame", frame, table, 5);
+    for (unsigned k = 1; k <= L; ++k)
+        append_row(text, "label " + std::to_string(k), fields, table + k * ARAPFLOW_LSCORE_FIELDS, ARAPFLOW_LSCORE_FIELDS - 1);
     return text;
 }
 
-// the text of a map score file (pipeline.format_map_score): the two rows of ArapFlow_MapScore's histogram, then one line
-// per threshold of its match table, integers only
+// the text of a map score file (pipeline.format_map_score): the two rows of ArapFlow_MapScore's histogram, which have no
+// keys, then one line per threshold of its match table, integers only
 inline std::string format_map_score(const uint64_t* hist, const unsigned* thr, unsigned m, const uint64_t* match)
 {
+    static const char* const fields[4] = {"a", "b", "a_hit", "b_hit"};
     std::string text;
-    char cell[96];
     for (int c = 0; c < 2; ++c) {
         text += c ? "pos" : "neg";
-        for (int v = 0; v < 256; ++v) {
-            snprintf(cell, sizeof(cell), " %llu", (unsigned long long)hist[c * 256 + v]);
-            text += cell;
-        }
+        for (int v = 0; v < 256; ++v) text += " " + std::to_string(hist[c * 256 + v]);
         text += "\n";
     }
-    for (unsigned j = 0; j < m; ++j) {
-        const uint64_t* const q = match + 4 * j;
-        snprintf(cell, sizeof(cell), "match thr=%u a=%llu b=%llu a_hit=%llu b_hit=%llu\n", thr[j], (unsigned long long)q[0],
-                 (unsigned long long)q[1], (unsigned long long)q[2], (unsigned long long)q[3]);
-        text += cell;
-    }
+    for (unsigned j = 0; j < m; ++j) append_row(text, "match thr=" + std::to_string(thr[j]), fields, match + 4 * j, 4);
     return text;
 }
 

@@ -3,8 +3,13 @@
 //   BAD                       a form, refused (after parse_item's own "Invalid ..." line)
 //   <canonical> done=<path>   what was read, written as pipeline.format_line writes it, and the path the line is
 //                             reported done by (pipeline.done_token)
+// and, as `line_tool format score|fscore|tscore|lscore|mscore [frames|L|thresholds]` with a table's integers on stdin,
+// the text device_pass.h's format_* makes of it.  Neither mode needs a device.
+#include <cstdlib>
 #include <iostream>
+#include <vector>
 
+#include "device_pass.h"
 #include "list_line.h"
 
 struct Canon {
@@ -155,8 +160,32 @@ static std::string canonical(const Item& it)
     return c.text + " done=" + done_path(it);
 }
 
-int main()
+// `line_tool format KIND [SIZE]`: the table's integers on stdin -> the text of its score file; false for a bad call
+static bool print_score_file(const std::string& kind, unsigned size)
 {
+    std::vector<uint64_t> v;
+    for (uint64_t x; std::cin >> x;) v.push_back(x);
+    const size_t want = kind == "score"    ? ARAPFLOW_SCORE_ROWS * ARAPFLOW_SCORE_FIELDS
+                        : kind == "fscore" ? ARAPFLOW_FSCORE_ROWS * ARAPFLOW_FSCORE_FIELDS
+                        : kind == "tscore" ? (size_t)size * ARAPFLOW_TSCORE_CLASSES * ARAPFLOW_TSCORE_FIELDS
+                        : kind == "lscore" ? ((size_t)size + 1) * ARAPFLOW_LSCORE_FIELDS
+                        : kind == "mscore" ? 512 + (size_t)size * 5
+                                           : 0;
+    if (!want || v.size() != want) return false;
+    std::vector<unsigned> thr(v.begin() + (kind == "mscore" ? 512 : 0), v.begin() + (kind == "mscore" ? 512 + size : 0));
+    const std::string text = kind == "score"    ? format_score(v.data())
+                             : kind == "fscore" ? format_frame_score(v.data())
+                             : kind == "tscore" ? format_track_score(v.data(), size)
+                             : kind == "lscore" ? format_label_score(v.data(), size)
+                                                : format_map_score(v.data(), thr.data(), size, v.data() + 512 + size);
+    fputs(text.c_str(), stdout);
+    return true;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1)               // mscore's integers: the histogram, SIZE thresholds, SIZE match rows
+        return argc >= 3 && std::string(argv[1]) == "format" && print_score_file(argv[2], argc > 3 ? (unsigned)atoi(argv[3]) : 0) ? 0 : 2;
     for (std::string line; std::getline(std::cin, line);) {
         Item it;
         const Parsed p = parse_item(line, it);

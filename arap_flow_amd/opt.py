@@ -29,6 +29,9 @@ import numpy as np
 import torch
 
 from . import capi
+# the rows and fields of the score tables, in their order (LSCORE_FIELDS: the 8 of a label row as the table holds it)
+from .scores import (SCORE_ROWS, SCORE_FIELDS, FSCORE_ROWS, FSCORE_FIELDS, TSCORE_CLASSES, TSCORE_FIELDS,        # noqa: F401
+                     LSCORE_TABLE_FIELDS as LSCORE_FIELDS, LSCORE_FRAME_FIELDS, MSCORE_MAX_THR)
 
 BUILTIN_PLAN = b"builtin:arap"
 LM_OUTCOMES = ("accepted", "rejected", "function_tolerance", "min_radius")      # ARAPFLOW_LM_* of include/arap_opt.h
@@ -842,10 +845,6 @@ def seg_maps(state, masks, flows, tau=1.0, radius=140, M1=None, M2=None, which=S
                        for k in SEG_OUTPUTS], "SegMapsScratchBytes", view={"dist1": np.uint16, "dist2": np.uint16})
 
 
-SCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")
-SCORE_FIELDS = ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")
-
-
 def flow_score(state, gt, est, occ=None, dist=None, skip=None, err=False):
     """the error table of an estimated flow against its ground truth (ArapFlow_FlowScore, DESIGN.md "Flow scoring").
     gt, est f32[H,W,2] or f32[n,H,W,2]; occ u8 (non-zero: occluded), dist u16 (ArapFlow_SegMaps' squared distance), skip
@@ -870,11 +869,6 @@ def flow_score(state, gt, est, occ=None, dist=None, skip=None, err=False):
     return _warp_call(state, "FlowScore", (W, H, n), [(gt, np.float32), (est, np.float32)] + planes,
                       [("table", (n, len(SCORE_ROWS), len(SCORE_FIELDS)), torch.int64),
                        ("err", (n, H, W) if err else None, torch.float32)], view={"table": np.uint64})
-
-
-TSCORE_CLASSES = ("all", "tracked", "reappeared")
-TSCORE_FIELDS = ("count", "gt_vis", "est_vis", "agree", "within_1", "within_2", "within_4", "within_8", "within_16",
-                 "tp_1", "tp_2", "tp_4", "tp_8", "tp_16", "sum", "max")
 
 
 def track_score(state, gt_pos, gt_occ, est_pos, est_occ, scale=(1, 1)):
@@ -947,10 +941,6 @@ def interp_frames(state, a, b, fwd, times, bwd=None, want_src=False):
     return (r["out"], r["src"]) if want_src else r["out"]
 
 
-FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")
-FSCORE_FIELDS = ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")
-
-
 def frame_score(state, ref, est, occ=None, dist=None, skip=None, obj=None, ssim=False):
     """the PSNR / integer-SSIM table of estimated frames against reference frames (ArapFlow_FrameScore, DESIGN.md "Frame
     scoring").  ref, est u8[H,W,3] or u8[n,H,W,3]; occ u8 (non-zero: occluded), dist u16 (ArapFlow_SegMaps' squared
@@ -975,11 +965,6 @@ def frame_score(state, ref, est, occ=None, dist=None, skip=None, obj=None, ssim=
     return _warp_call(state, "FrameScore", (W, H, n), [(ref, np.uint8), (est, np.uint8)] + planes,
                       [("table", (n, len(FSCORE_ROWS), len(FSCORE_FIELDS)), torch.int64),
                        ("ssim", (n, H, W) if ssim else None, torch.float32)], view={"table": np.uint64})
-
-
-LSCORE_FIELDS = ("gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit", "zero")
-LSCORE_FRAME_FIELDS = ("counted", "skipped", "equal", "gt_above", "est_above")       # row 0 of a label table
-MSCORE_MAX_THR = 8
 
 
 def _score_maps(name, gt, est, skip):

@@ -50,6 +50,15 @@ import numpy as np
 from PIL import Image
 
 from . import flo
+# a score table's names, its file's text, pooling and metrics: scores.py.  (LSCORE_FIELDS here is a label row as its file
+# writes it, 7 names; opt.LSCORE_FIELDS is the table's 8.)
+from .scores import (SCORE_ROWS, SCORE_FIELDS, FSCORE_ROWS, FSCORE_FIELDS, TSCORE_MAX_FRAMES, TSCORE_CLASSES, TSCORE_X,      # noqa: F401
+                     TSCORE_FIELDS, LSCORE_FRAME_FIELDS, LSCORE_FILE_FIELDS as LSCORE_FIELDS, MSCORE_MAX_THR, MSCORE_MATCH_FIELDS,
+                     format_score, parse_score_file, add_scores, score_summary,
+                     format_track_score, parse_track_score_file, add_track_scores, track_score_summary,
+                     format_frame_score, parse_frame_score_file, add_frame_scores, frame_score_summary,
+                     format_label_score, parse_label_score_file, add_label_scores, label_score_summary,
+                     format_map_score, parse_map_score_file, add_map_scores, map_score_summary)
 
 ARAP_BG = 255        # para_gen.py:30
 
@@ -82,32 +91,14 @@ SEG_KEYS = ("idx1", "idx2", "mb1", "mb2", "dist1", "dist2")
 SEG_MAX_RADIUS = 254         # ARAPFLOW_SEG_MAX_RADIUS of include/arap_opt.h
 SCORE_WORD = "score"
 SCORE_KEYS = ("occ", "dist", "skip", "mask")
-# the rows and the fields of a score table in its order (opt.SCORE_ROWS, opt.SCORE_FIELDS; ArapFlow_FlowScore)
-SCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")
-SCORE_FIELDS = ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")
 FSCORE_WORD = "fscore"
 FSCORE_KEYS = ("occ", "dist", "skip", "obj")
-# the rows and the fields of a frame score table in its order (opt.FSCORE_ROWS, opt.FSCORE_FIELDS; ArapFlow_FrameScore)
-FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")
-FSCORE_FIELDS = ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")
 INTERP_WORD = "interp"
 LSCORE_WORD = "lscore"
 MSCORE_WORD = "mscore"
-MSCORE_MAX_THR = 8           # ARAPFLOW_MSCORE_MAX_THR of include/arap_opt.h
-# row 0 and a label's row of a label score table in their order (opt.LSCORE_FRAME_FIELDS; opt.LSCORE_FIELDS without its
-# last field, which is zero; ArapFlow_LabelScore), and a row of ArapFlow_MapScore's match table
-LSCORE_FRAME_FIELDS = ("counted", "skipped", "equal", "gt_above", "est_above")
-LSCORE_FIELDS = ("gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit")
-MSCORE_MATCH_FIELDS = ("a", "b", "a_hit", "b_hit")
 INTERP_MAX_TIMES = 32        # ARAPFLOW_INTERP_MAX_TIMES of include/arap_opt.h
 TSCORE_WORD = "tscore"
 CHAIN_WORD = "chain"
-TSCORE_MAX_FRAMES = 64       # ARAPFLOW_TSCORE_MAX_FRAMES of include/arap_opt.h
-# the classes and the fields of a track score table in its order (opt.TSCORE_CLASSES, opt.TSCORE_FIELDS; ArapFlow_TrackScore)
-TSCORE_CLASSES = ("all", "tracked", "reappeared")
-TSCORE_X = (1, 2, 4, 8, 16)
-TSCORE_FIELDS = ("count", "gt_vis", "est_vis", "agree") + tuple("within_%d" % x for x in TSCORE_X) + \
-                tuple("tp_%d" % x for x in TSCORE_X) + ("sum", "max")
 LIGHT_KEYS = ("rgb1", "rgb2")
 
 
@@ -945,81 +936,31 @@ class ScoreLine(NamedTuple):
     out: str
 
 
-def parse_score(tokens):
-    if len(tokens) < 3 or tokens[0] != SCORE_WORD or "=" in tokens[1] or "=" in tokens[2]:
-        raise ValueError("score line: two flow files expected: %r" % " ".join(tokens))
-    planes, out = {}, None
+def _score_tokens(word, what, keys, tokens):
+    """the {key: value} of a score, tscore, fscore, lscore or mscore line after its two paths, `what` files"""
+    if len(tokens) < 3 or tokens[0] != word or "=" in tokens[1] or "=" in tokens[2]:
+        raise ValueError("%s line: two %s files expected: %r" % (word, what, " ".join(tokens)))
+    got = {}
     for t in tokens[3:]:
         k, eq, v = t.partition("=")
-        if not (eq and v and k in SCORE_KEYS + ("out",)) or k in planes or (k == "out" and out is not None):
-            raise ValueError("score line: bad or repeated token %r" % t)
-        if k == "out":
-            out = v
-        else:
-            planes[k] = v
-    if out is None:
-        raise ValueError("score line without out=: %r" % " ".join(tokens))
-    return ScoreLine(tokens[1], tokens[2], planes, out)
+        if not (eq and v and k in keys) or k in got:
+            raise ValueError("%s line: bad or repeated token %r" % (word, t))
+        got[k] = v
+    if "out" not in got:
+        raise ValueError("%s line without out=: %r" % (word, " ".join(tokens)))
+    return got
+
+
+def parse_score(tokens):
+    got = _score_tokens(SCORE_WORD, "flow", SCORE_KEYS + ("out",), tokens)
+    out = got.pop("out")
+    return ScoreLine(tokens[1], tokens[2], got, out)
 
 
 def score_line(item):
     """the inverse of parse_score: the planes in the order of SCORE_KEYS, then out="""
     return " ".join([SCORE_WORD, item.gt, item.est] + ["%s=%s" % (k, item.planes[k]) for k in SCORE_KEYS if item.planes.get(k)] +
                     ["out=" + item.out])
-
-
-def format_score(table):
-    """the text of a score file: one line per row of a table uint64[10][8], `<row name> count=.. sum=.. n1=.. n3=.. n5=..
-    fl=.. nonfinite=.. max=..`, the last `left_out skipped=.. gt_nonfinite=..`; integers only; the C++ worker writes the
-    same bytes"""
-    t = np.asarray(table, np.uint64).reshape(len(SCORE_ROWS), len(SCORE_FIELDS))
-    lines = ["%s %s\n" % (name, " ".join("%s=%d" % (f, int(v)) for f, v in zip(SCORE_FIELDS, row)))
-             for name, row in zip(SCORE_ROWS[:-1], t)]
-    return "".join(lines) + "%s skipped=%d gt_nonfinite=%d\n" % (SCORE_ROWS[-1], int(t[-1, 0]), int(t[-1, 1]))
-
-
-def parse_score_file(text):
-    """the inverse of format_score -> uint64[10][8]"""
-    lines = text.split("\n")
-    if len(lines) != len(SCORE_ROWS) + 1 or lines[-1] != "":
-        raise ValueError("score file: %d lines expected" % len(SCORE_ROWS))
-    t = np.zeros((len(SCORE_ROWS), len(SCORE_FIELDS)), np.uint64)
-    for r, (name, line) in enumerate(zip(SCORE_ROWS, lines)):
-        keys = SCORE_FIELDS if r < len(SCORE_ROWS) - 1 else ("skipped", "gt_nonfinite")
-        tok = line.split(" ")
-        if tok[0] != name or len(tok) != 1 + len(keys):
-            raise ValueError("score file: bad row %r" % line)
-        for f, (key, cell) in enumerate(zip(keys, tok[1:])):
-            k, _, v = cell.partition("=")
-            if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
-                raise ValueError("score file: bad field %r" % cell)
-            t[r, f] = int(v)
-    return t
-
-
-def score_summary(table):
-    """{row name: dict(count, epe, r1, r3, r5, fl)} of a table, float64: the mean end-point error in pixels and the
-    outlier rates as fractions of the row's count (nan for an empty row); `left_out` is dict(skipped, gt_nonfinite)"""
-    t = np.asarray(table, np.uint64).reshape(len(SCORE_ROWS), len(SCORE_FIELDS))
-    res = {}
-    for name, row in zip(SCORE_ROWS[:-1], t):
-        count, total, n1, n3, n5, fl = (float(int(v)) for v in row[:6])
-        over = lambda v: v / count if count else float("nan")
-        res[name] = dict(count=int(row[0]), epe=over(total / 4096.0), r1=over(n1), r3=over(n3), r5=over(n5), fl=over(fl))
-    res[SCORE_ROWS[-1]] = dict(skipped=int(t[-1, 0]), gt_nonfinite=int(t[-1, 1]))
-    return res
-
-
-def add_scores(tables):
-    """the pooled table of several: the integer sum of every field but `max`, which is the maximum -- exactly the table
-    of all their pixels together"""
-    ts = [np.asarray(t, np.uint64).reshape(len(SCORE_ROWS), len(SCORE_FIELDS)) for t in tables]
-    out = np.zeros((len(SCORE_ROWS), len(SCORE_FIELDS)), np.uint64)
-    for t in ts:
-        peak = np.maximum(out[:-1, -1], t[:-1, -1])
-        out += t
-        out[:-1, -1] = peak
-    return out
 
 
 def dist_from_png(u8):
@@ -1029,17 +970,28 @@ def dist_from_png(u8):
     return np.where(d == 255, np.uint16(65535), d * d).astype(np.uint16)
 
 
+def _load_score_planes(word, planes, like, like_path):
+    """{key: the red channel of its file} of a line's planes, each of the size of the array `like` read from `like_path`"""
+    plane = {}
+    for k, path in planes.items():
+        plane[k] = load_mask_red(path)
+        if plane[k].shape != like.shape[:2]:
+            raise ValueError("%s line: %s differs in size from %s" % (word, path, like_path))
+    return plane
+
+
+def _write_text(path, text):
+    with open(path, "w") as f:
+        f.write(text)
+
+
 def run_score(state, spec):
     """one `score` line: read the two flows and the planes given, one opt.flow_score, write the table as text"""
     from . import opt
     gt, est = flo.flow_read(spec.gt), flo.flow_read(spec.est)
     if gt.shape != est.shape:
         raise ValueError("score line: %s and %s differ in size" % (spec.gt, spec.est))
-    plane = {}
-    for k, path in spec.planes.items():
-        plane[k] = load_mask_red(path)
-        if plane[k].shape != gt.shape[:2]:
-            raise ValueError("score line: %s differs in size from %s" % (path, spec.gt))
+    plane = _load_score_planes(SCORE_WORD, spec.planes, gt, spec.gt)
     skip = None
     if "skip" in plane or "mask" in plane:
         skip = np.zeros(gt.shape[:2], np.uint8)
@@ -1048,8 +1000,7 @@ def run_score(state, spec):
                 skip |= (plane[k] != 0).astype(np.uint8)
     dist = dist_from_png(plane["dist"]) if "dist" in plane else None
     table = opt.flow_score(state, gt, est, occ=plane.get("occ"), dist=dist, skip=skip)["table"][0]
-    with open(spec.out, "w") as f:
-        f.write(format_score(table))
+    _write_text(spec.out, format_score(table))
     return table
 
 
@@ -1067,23 +1018,14 @@ class TScoreLine(NamedTuple):
 
 
 def parse_tscore(tokens):
-    if len(tokens) < 3 or tokens[0] != TSCORE_WORD or "=" in tokens[1] or "=" in tokens[2]:
-        raise ValueError("tscore line: two track files expected: %r" % " ".join(tokens))
-    scale, out = None, None
-    for t in tokens[3:]:
-        k, eq, v = t.partition("=")
-        if not (eq and v and k in ("s", "out")) or (k == "s" and scale is not None) or (k == "out" and out is not None):
-            raise ValueError("tscore line: bad or repeated token %r" % t)
-        if k == "out":
-            out = v
-        else:
-            with np.errstate(over="ignore"):
-                scale = _bg_numbers(v)
-            if len(scale) != 2 or not all(math.isfinite(q) and q > 0 for q in scale):
-                raise ValueError("tscore line: s= takes two finite factors > 0: %r" % t)
-    if out is None:
-        raise ValueError("tscore line without out=: %r" % " ".join(tokens))
-    return TScoreLine(tokens[1], tokens[2], scale or (1.0, 1.0), out)
+    got = _score_tokens(TSCORE_WORD, "track", ("s", "out"), tokens)
+    scale = (1.0, 1.0)
+    if "s" in got:
+        with np.errstate(over="ignore"):
+            scale = _bg_numbers(got["s"])
+        if len(scale) != 2 or not all(math.isfinite(q) and q > 0 for q in scale):
+            raise ValueError("tscore line: s= takes two finite factors > 0: %r" % ("s=" + got["s"]))
+    return TScoreLine(tokens[1], tokens[2], scale, got["out"])
 
 
 def tscore_line(item):
@@ -1093,75 +1035,6 @@ def tscore_line(item):
                     ["out=" + item.out])
 
 
-def format_track_score(table):
-    """the text of a track score file: one line per frame and class of a table uint64[F][3][16], `<frame> <class name>
-    count=.. gt_vis=.. est_vis=.. agree=.. within_1=.. .. tp_16=.. sum=.. max=..`, frame 0 first (its `all` line holds the
-    number of valid points as count and of invalid ones as gt_vis); integers only; the C++ worker writes the same bytes"""
-    t = np.asarray(table, np.uint64).reshape(-1, len(TSCORE_CLASSES), len(TSCORE_FIELDS))
-    return "".join("%d %s %s\n" % (f, name, " ".join("%s=%d" % (k, int(v)) for k, v in zip(TSCORE_FIELDS, row)))
-                   for f, frame in enumerate(t) for name, row in zip(TSCORE_CLASSES, frame))
-
-
-def parse_track_score_file(text):
-    """the inverse of format_track_score -> uint64[F][3][16]"""
-    lines = text.split("\n")
-    nc = len(TSCORE_CLASSES)
-    if len(lines) < 2 * nc + 1 or (len(lines) - 1) % nc or lines[-1] != "" or (len(lines) - 1) // nc > TSCORE_MAX_FRAMES:
-        raise ValueError("track score file: %d lines per frame, 2..%d frames expected" % (nc, TSCORE_MAX_FRAMES))
-    t = np.zeros(((len(lines) - 1) // nc, nc, len(TSCORE_FIELDS)), np.uint64)
-    for r, line in enumerate(lines[:-1]):
-        tok = line.split(" ")
-        if len(tok) != 2 + len(TSCORE_FIELDS) or tok[0] != str(r // nc) or tok[1] != TSCORE_CLASSES[r % nc]:
-            raise ValueError("track score file: bad row %r" % line)
-        for f, (key, cell) in enumerate(zip(TSCORE_FIELDS, tok[2:])):
-            k, _, v = cell.partition("=")
-            if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
-                raise ValueError("track score file: bad field %r" % cell)
-            t[r // nc, r % nc, f] = int(v)
-    return t
-
-
-def add_track_scores(tables):
-    """the pooled table of several: tables of fewer frames are padded with zeros to the longest, every field is summed but
-    `max`, which is the maximum -- exactly the table of all their points together"""
-    ts = [np.asarray(t, np.uint64).reshape(-1, len(TSCORE_CLASSES), len(TSCORE_FIELDS)) for t in tables]
-    out = np.zeros((max(len(t) for t in ts), len(TSCORE_CLASSES), len(TSCORE_FIELDS)), np.uint64)
-    for t in ts:
-        peak = np.maximum(out[:len(t), :, -1], t[:, :, -1])
-        out[:len(t)] += t
-        out[:len(t), :, -1] = peak
-    return out
-
-
-def _tscore_metrics(row):
-    """dict(count, gt_vis, oa, d_1 .. d_16, d_avg, j_1 .. j_16, aj, err) of one row of fields, float64; nan where a
-    denominator is zero"""
-    v = [float(int(x)) for x in row]
-    over = lambda a, b: a / b if b else float("nan")
-    count, gt_vis, est_vis, agree = v[:4]
-    res = dict(count=int(row[0]), gt_vis=int(row[1]), oa=over(agree, count))
-    d = [over(w, gt_vis) for w in v[4:9]]
-    j = [over(tp, gt_vis + est_vis - tp) for tp in v[9:14]]
-    for x, dx, jx in zip(TSCORE_X, d, j):
-        res["d_%d" % x], res["j_%d" % x] = dx, jx
-    res["d_avg"], res["aj"] = sum(d) / len(d), sum(j) / len(j)
-    res["err"] = over(v[14] / 4096.0, gt_vis)
-    return res
-
-
-def track_score_summary(table):
-    """the TAP-Vid numbers of a table: {class name: metrics} over the frames 1 .. F-1 together (integer sums first, the
-    maximum for `max`), then "frames": [metrics of class `all` at frame f, f = 1 .. F-1] -- the drift curve -- and "valid",
-    "invalid": the numbers of query points.  metrics: dict(count, gt_vis, oa = agree / count, d_x = within_x / gt_vis,
-    d_avg, j_x = tp_x / (gt_vis + est_vis - tp_x), aj, err = sum / 4096 / gt_vis), the means over the five x; nan where a
-    denominator is zero.  Pooled counts, not TAP-Vid's mean over videos."""
-    t = np.asarray(table, np.uint64).reshape(-1, len(TSCORE_CLASSES), len(TSCORE_FIELDS))
-    res = {name: _tscore_metrics(t[1:, c].sum(axis=0)) for c, name in enumerate(TSCORE_CLASSES)}
-    res["frames"] = [_tscore_metrics(t[f, 0]) for f in range(1, len(t))]
-    res["valid"], res["invalid"] = int(t[0, 0, 0]), int(t[0, 0, 1])
-    return res
-
-
 def run_tscore(state, spec):
     """one `tscore` line: read the two track files, one opt.track_score, write the table as text"""
     from . import opt, trk
@@ -1169,8 +1042,7 @@ def run_tscore(state, spec):
     if (gt["W"], gt["H"]) != (est["W"], est["H"]) or gt["pos"].shape != est["pos"].shape:
         raise ValueError("tscore line: %s and %s differ in W, H, F or P" % (spec.gt, spec.est))
     table = opt.track_score(state, gt["pos"], gt["occ"], est["pos"], est["occ"], scale=spec.scale)
-    with open(spec.out, "w") as f:
-        f.write(format_track_score(table))
+    _write_text(spec.out, format_track_score(table))
     return table
 
 
@@ -1244,20 +1116,9 @@ class FScoreLine(NamedTuple):
 
 
 def parse_fscore(tokens):
-    if len(tokens) < 3 or tokens[0] != FSCORE_WORD or "=" in tokens[1] or "=" in tokens[2]:
-        raise ValueError("fscore line: two frame files expected: %r" % " ".join(tokens))
-    planes, out = {}, None
-    for t in tokens[3:]:
-        k, eq, v = t.partition("=")
-        if not (eq and v and k in FSCORE_KEYS + ("out",)) or k in planes or (k == "out" and out is not None):
-            raise ValueError("fscore line: bad or repeated token %r" % t)
-        if k == "out":
-            out = v
-        else:
-            planes[k] = v
-    if out is None:
-        raise ValueError("fscore line without out=: %r" % " ".join(tokens))
-    return FScoreLine(tokens[1], tokens[2], planes, out)
+    got = _score_tokens(FSCORE_WORD, "frame", FSCORE_KEYS + ("out",), tokens)
+    out = got.pop("out")
+    return FScoreLine(tokens[1], tokens[2], got, out)
 
 
 def fscore_line(item):
@@ -1266,79 +1127,17 @@ def fscore_line(item):
                     ["out=" + item.out])
 
 
-def format_frame_score(table):
-    """the text of a frame score file: one line per row of a table uint64[9][7], `<row name> count=.. sse=.. sad=.. max=..
-    windows=.. ssim_sum=.. ssim_worst=..`, the last `left_out pixels=.. windows=..`; integers only; the C++ worker writes
-    the same bytes"""
-    t = np.asarray(table, np.uint64).reshape(len(FSCORE_ROWS), len(FSCORE_FIELDS))
-    lines = ["%s %s\n" % (name, " ".join("%s=%d" % (f, int(v)) for f, v in zip(FSCORE_FIELDS, row)))
-             for name, row in zip(FSCORE_ROWS[:-1], t)]
-    return "".join(lines) + "%s pixels=%d windows=%d\n" % (FSCORE_ROWS[-1], int(t[-1, 0]), int(t[-1, 1]))
-
-
-def parse_frame_score_file(text):
-    """the inverse of format_frame_score -> uint64[9][7]"""
-    lines = text.split("\n")
-    if len(lines) != len(FSCORE_ROWS) + 1 or lines[-1] != "":
-        raise ValueError("frame score file: %d lines expected" % len(FSCORE_ROWS))
-    t = np.zeros((len(FSCORE_ROWS), len(FSCORE_FIELDS)), np.uint64)
-    for r, (name, line) in enumerate(zip(FSCORE_ROWS, lines)):
-        keys = FSCORE_FIELDS if r < len(FSCORE_ROWS) - 1 else ("pixels", "windows")
-        tok = line.split(" ")
-        if tok[0] != name or len(tok) != 1 + len(keys):
-            raise ValueError("frame score file: bad row %r" % line)
-        for f, (key, cell) in enumerate(zip(keys, tok[1:])):
-            k, _, v = cell.partition("=")
-            if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
-                raise ValueError("frame score file: bad field %r" % cell)
-            t[r, f] = int(v)
-    return t
-
-
-def frame_score_summary(table):
-    """{row name: dict(count, psnr, mae, windows, ssim, ssim_min)} of a table, float64: psnr = 10 log10(255^2 * 3 * count /
-    sse) in dB (inf when sse = 0), mae = sad / (3 * count), ssim = ssim_sum / windows / 2^20 - 1, ssim_min = 1 - ssim_worst
-    / 2^20; nan for a row without pixels (psnr, mae) or windows (ssim, ssim_min); `left_out` is dict(pixels, windows)"""
-    t = np.asarray(table, np.uint64).reshape(len(FSCORE_ROWS), len(FSCORE_FIELDS))
-    res, nan = {}, float("nan")
-    for name, row in zip(FSCORE_ROWS[:-1], t):
-        count, sse, sad, _, windows, ssim_sum, worst = (int(v) for v in row)
-        psnr = nan if not count else float("inf") if not sse else 10.0 * math.log10(65025.0 * 3.0 * count / sse)
-        res[name] = dict(count=count, psnr=psnr, mae=sad / (3.0 * count) if count else nan, windows=windows,
-                         ssim=ssim_sum / windows / 1048576.0 - 1.0 if windows else nan,
-                         ssim_min=1.0 - worst / 1048576.0 if windows else nan)
-    res[FSCORE_ROWS[-1]] = dict(pixels=int(t[-1, 0]), windows=int(t[-1, 1]))
-    return res
-
-
-def add_frame_scores(tables):
-    """the pooled table of several: the integer sum of every field but `max` and `ssim_worst`, which take the maximum --
-    exactly the table of all their frames together"""
-    out = np.zeros((len(FSCORE_ROWS), len(FSCORE_FIELDS)), np.uint64)
-    for t in tables:
-        t = np.asarray(t, np.uint64).reshape(out.shape)
-        peak = np.maximum(out[:-1, [3, 6]], t[:-1, [3, 6]])
-        out += t
-        out[:-1, [3, 6]] = peak
-    return out
-
-
 def run_fscore(state, spec):
     """one `fscore` line: read the two frames and the planes given, one opt.frame_score, write the table as text"""
     from . import opt
     ref, est = load_rgb(spec.ref), load_rgb(spec.est)
     if ref.shape != est.shape:
         raise ValueError("fscore line: %s and %s differ in size" % (spec.ref, spec.est))
-    plane = {}
-    for k, path in spec.planes.items():
-        plane[k] = load_mask_red(path)
-        if plane[k].shape != ref.shape[:2]:
-            raise ValueError("fscore line: %s differs in size from %s" % (path, spec.ref))
+    plane = _load_score_planes(FSCORE_WORD, spec.planes, ref, spec.ref)
     if "dist" in plane:
         plane["dist"] = dist_from_png(plane["dist"])
     table = opt.frame_score(state, ref, est, **plane)["table"][0]
-    with open(spec.out, "w") as f:
-        f.write(format_frame_score(table))
+    _write_text(spec.out, format_frame_score(table))
     return table
 
 
@@ -1373,21 +1172,6 @@ class MScoreLine(NamedTuple):
     out: str
 
 
-def _score_map_tokens(word, keys, tokens):
-    """the {key: value} of an lscore / mscore line after its two paths"""
-    if len(tokens) < 3 or tokens[0] != word or "=" in tokens[1] or "=" in tokens[2]:
-        raise ValueError("%s line: two map files expected: %r" % (word, " ".join(tokens)))
-    got = {}
-    for t in tokens[3:]:
-        k, eq, v = t.partition("=")
-        if not (eq and v and k in keys) or k in got:
-            raise ValueError("%s line: bad or repeated token %r" % (word, t))
-        got[k] = v
-    if "out" not in got:
-        raise ValueError("%s line without out=: %r" % (word, " ".join(tokens)))
-    return got
-
-
 def _score_uint(word, text, low, high):
     if text is None or not _UINT.match(text) or not low <= int(text) <= high:
         raise ValueError("%s line: a number %d..%d expected, not %r" % (word, low, high, text))
@@ -1395,7 +1179,7 @@ def _score_uint(word, text, low, high):
 
 
 def parse_lscore(tokens):
-    got = _score_map_tokens(LSCORE_WORD, ("l", "r", "skip", "out"), tokens)
+    got = _score_tokens(LSCORE_WORD, "map", ("l", "r", "skip", "out"), tokens)
     return LScoreLine(tokens[1], tokens[2], _score_uint(LSCORE_WORD, got.get("l"), 1, 255),
                       _score_uint(LSCORE_WORD, got.get("r"), 0, SEG_MAX_RADIUS), got.get("skip"), got["out"])
 
@@ -1407,7 +1191,7 @@ def lscore_line(item):
 
 
 def parse_mscore(tokens):
-    got = _score_map_tokens(MSCORE_WORD, ("t", "r", "skip", "out"), tokens)
+    got = _score_tokens(MSCORE_WORD, "map", ("t", "r", "skip", "out"), tokens)
     if ("t" in got) != ("r" in got):
         raise ValueError("mscore line: t= and r= come together: %r" % " ".join(tokens))
     thr, radius = (), None
@@ -1426,163 +1210,10 @@ def mscore_line(item):
                     (["skip=" + item.skip] if item.skip else []) + ["out=" + item.out])
 
 
-def format_label_score(table):
-    """the text of a label score file, of a table uint64[L+1][8]: `frame counted=.. skipped=.. equal=.. gt_above=..
-    est_above=..`, then per label `label <k> gt=.. est=.. inter=.. gt_b=.. est_b=.. gt_hit=.. est_hit=..`; integers only;
-    the C++ worker writes the same bytes"""
-    t = np.asarray(table, np.uint64).reshape(-1, len(LSCORE_FIELDS) + 1)
-    lines = ["frame " + " ".join("%s=%d" % (f, int(v)) for f, v in zip(LSCORE_FRAME_FIELDS, t[0]))]
-    lines += ["label %d " % k + " ".join("%s=%d" % (f, int(v)) for f, v in zip(LSCORE_FIELDS, t[k])) for k in range(1, len(t))]
-    return "\n".join(lines) + "\n"
-
-
-def _score_cells(what, line, head, keys):
-    """the integers of `<head> key=int ...` in the order of `keys`"""
-    tok = line.split(" ")
-    if tok[:len(head)] != head or len(tok) != len(head) + len(keys):
-        raise ValueError("%s: bad row %r" % (what, line))
-    out = []
-    for key, cell in zip(keys, tok[len(head):]):
-        k, _, v = cell.partition("=")
-        if k != key or not re.match(r"[0-9]{1,20}$", v) or int(v) >= 1 << 64:
-            raise ValueError("%s: bad field %r" % (what, cell))
-        out.append(int(v))
-    return out
-
-
-def parse_label_score_file(text):
-    """the inverse of format_label_score -> uint64[L+1][8]"""
-    lines = text.split("\n")
-    if not 3 <= len(lines) <= 257 or lines[-1] != "":
-        raise ValueError("label score file: a frame row and 1 to 255 label rows expected")
-    t = np.zeros((len(lines) - 1, len(LSCORE_FIELDS) + 1), np.uint64)
-    t[0, :len(LSCORE_FRAME_FIELDS)] = _score_cells("label score file", lines[0], ["frame"], LSCORE_FRAME_FIELDS)
-    for k in range(1, len(t)):
-        t[k, :len(LSCORE_FIELDS)] = _score_cells("label score file", lines[k], ["label", "%d" % k], LSCORE_FIELDS)
-    return t
-
-
-def add_label_scores(tables):
-    """the pooled table of several: the integer sum field by field, a table of fewer labels padded with zero rows --
-    the table of all their maps together, but that a label above a table's own L stays where that table counted it, in
-    gt_above / est_above"""
-    ts = [np.asarray(t, np.uint64).reshape(-1, len(LSCORE_FIELDS) + 1) for t in tables]
-    out = np.zeros((max([len(t) for t in ts] + [2]), len(LSCORE_FIELDS) + 1), np.uint64)
-    for t in ts:
-        out[:len(t)] += t
-    return out
-
-
-def _pr_f(hit_est, n_est, hit_gt, n_gt):
-    """(P, R, F) of a boundary match by the DAVIS toolkit's conventions for empty sets"""
-    if n_est == 0 and n_gt > 0:
-        P, R = 1.0, 0.0
-    elif n_est > 0 and n_gt == 0:
-        P, R = 0.0, 1.0
-    elif n_est == 0 and n_gt == 0:
-        P, R = 1.0, 1.0
-    else:
-        P, R = hit_est / n_est, hit_gt / n_gt
-    return P, R, 2.0 * P * R / (P + R) if P + R else 0.0
-
-
-def label_score_summary(table):
-    """dict(labels={k: dict(J, P, R, F)}, J, F, JF, frame=dict(...)) of a table, float64: J = inter / (gt + est - inter), 1
-    when the union is empty; P = est_hit / est_b and R = gt_hit / gt_b with the DAVIS toolkit's conventions (est_b = 0 <
-    gt_b: 1, 0; gt_b = 0 < est_b: 0, 1; both 0: 1, 1); F = 2 P R / (P + R), 0 when P + R = 0; J, F the means over the
-    labels and JF their mean"""
-    t = np.asarray(table, np.uint64).reshape(-1, len(LSCORE_FIELDS) + 1)
-    labels = {}
-    for k in range(1, len(t)):
-        gt, est, inter, gt_b, est_b, gt_hit, est_hit = (int(v) for v in t[k, :7])
-        union = gt + est - inter
-        P, R, F = _pr_f(est_hit, est_b, gt_hit, gt_b)
-        labels[k] = dict(J=inter / union if union else 1.0, P=P, R=R, F=F)
-    J = sum(v["J"] for v in labels.values()) / len(labels)
-    F = sum(v["F"] for v in labels.values()) / len(labels)
-    return dict(labels=labels, J=J, F=F, JF=(J + F) / 2.0, frame={f: int(v) for f, v in zip(LSCORE_FRAME_FIELDS, t[0])})
-
-
-def format_map_score(score):
-    """the text of a map score file, of dict(hist uint64[2][256], thr, match uint64[m][4]): `neg` and `pos` followed by
-    the 256 counts of the class, then per threshold `match thr=.. a=.. b=.. a_hit=.. b_hit=..`; integers only; the C++
-    worker writes the same bytes"""
-    h = np.asarray(score["hist"], np.uint64).reshape(2, 256)
-    lines = [name + "".join(" %d" % int(v) for v in row) for name, row in zip(("neg", "pos"), h)]
-    match = np.asarray(score.get("match", ()), np.uint64).reshape(-1, 4)
-    lines += ["match thr=%d " % t + " ".join("%s=%d" % (f, int(v)) for f, v in zip(MSCORE_MATCH_FIELDS, q))
-              for t, q in zip(score.get("thr", ()), match)]
-    return "\n".join(lines) + "\n"
-
-
-def parse_map_score_file(text):
-    """the inverse of format_map_score -> dict(hist, thr, match)"""
-    lines = text.split("\n")
-    if not 3 <= len(lines) <= 3 + MSCORE_MAX_THR or lines[-1] != "":
-        raise ValueError("map score file: two histogram rows and up to %d match rows expected" % MSCORE_MAX_THR)
-    hist = np.zeros((2, 256), np.uint64)
-    for c, name in enumerate(("neg", "pos")):
-        tok = lines[c].split(" ")
-        if tok[0] != name or len(tok) != 257 or not all(re.match(r"[0-9]{1,20}$", v) and int(v) < 1 << 64 for v in tok[1:]):
-            raise ValueError("map score file: bad row %r" % lines[c][:40])
-        hist[c] = [int(v) for v in tok[1:]]
-    thr, match = [], np.zeros((len(lines) - 3, 4), np.uint64)
-    for j, line in enumerate(lines[2:-1]):
-        cells = _score_cells("map score file", line, ["match"], ("thr",) + MSCORE_MATCH_FIELDS)
-        if not 1 <= cells[0] <= 255:
-            raise ValueError("map score file: bad threshold in %r" % line)
-        thr.append(cells[0])
-        match[j] = cells[1:]
-    return dict(hist=hist, thr=tuple(thr), match=match)
-
-
-def add_map_scores(scores):
-    """the pooled score of several: the integer sums of the histograms and, threshold by threshold, of the match rows --
-    exactly the score of all their maps together.  The scores have the same thresholds."""
-    scores = list(scores)
-    thr = tuple(scores[0]["thr"]) if scores else ()
-    hist, match = np.zeros((2, 256), np.uint64), np.zeros((len(thr), 4), np.uint64)
-    for s in scores:
-        if tuple(s["thr"]) != thr:
-            raise ValueError("add_map_scores: thresholds %r and %r" % (thr, tuple(s["thr"])))
-        hist += np.asarray(s["hist"], np.uint64).reshape(2, 256)
-        match += np.asarray(s["match"], np.uint64).reshape(len(thr), 4)
-    return dict(hist=hist, thr=thr, match=match)
-
-
-def map_score_summary(score):
-    """the pixelwise precision / recall curve of a score and what follows from it, float64: with TP(t) the positives and
-    FP(t) the negatives with est >= t, t = 1..255: P(t) = TP / (TP + FP), 1 when nothing is predicted, R(t) = TP / pos
-    (1 without positives) -> dict(pos, neg, P, R (arrays indexed by t, entry 0 unused), f128 = F at t = 128, best_f and
-    best_t (the smallest t of the best F), ap = sum_t (R(t) - R(t + 1)) P(t) with R(256) = 0, match = {thr: dict(P, R, F)}
-    by the conventions of label_score_summary)"""
-    h = np.asarray(score["hist"], np.uint64).reshape(2, 256)
-    neg, pos = [[int(v) for v in row] for row in h]
-    n_pos = sum(pos)
-    P, R, F = [float("nan")] * 256, [float("nan")] * 256, [float("nan")] * 256
-    tp = fp = 0
-    for t in range(255, 0, -1):
-        tp, fp = tp + pos[t], fp + neg[t]
-        P[t] = tp / (tp + fp) if tp + fp else 1.0
-        R[t] = tp / n_pos if n_pos else 1.0
-        F[t] = 2.0 * P[t] * R[t] / (P[t] + R[t]) if P[t] + R[t] else 0.0
-    ap = sum((R[t] - (R[t + 1] if t < 255 else 0.0)) * P[t] for t in range(1, 256))
-    best_t = max(range(1, 256), key=lambda t: (F[t], -t))
-    match = {}
-    for t, q in zip(score.get("thr", ()), np.asarray(score.get("match", ()), np.uint64).reshape(-1, 4)):
-        a, b, a_hit, b_hit = (int(v) for v in q)
-        match[int(t)] = dict(zip("PRF", _pr_f(b_hit, b, a_hit, a)))
-    return dict(pos=n_pos, neg=sum(neg), P=np.asarray(P), R=np.asarray(R), f128=F[128], best_f=F[best_t], best_t=best_t,
-                ap=ap, match=match)
-
-
 def _load_score_maps(word, spec):
-    gt, est = load_mask_red(spec.gt), load_mask_red(spec.est)
-    skip = load_mask_red(spec.skip) if spec.skip else None
-    for path, a in ((spec.est, est), (spec.skip, skip)):
-        if a is not None and a.shape != gt.shape:
-            raise ValueError("%s line: %s differs in size from %s" % (word, path, spec.gt))
-    return gt, est, skip
+    gt = load_mask_red(spec.gt)
+    plane = _load_score_planes(word, dict([("est", spec.est)] + ([("skip", spec.skip)] if spec.skip else [])), gt, spec.gt)
+    return gt, plane["est"], plane.get("skip")
 
 
 def run_lscore(state, spec):
@@ -1590,8 +1221,7 @@ def run_lscore(state, spec):
     from . import opt
     gt, est, skip = _load_score_maps(LSCORE_WORD, spec)
     table = opt.label_score(state, gt, est, spec.L, spec.radius, skip=skip)["table"][0]
-    with open(spec.out, "w") as f:
-        f.write(format_label_score(table))
+    _write_text(spec.out, format_label_score(table))
     return table
 
 
@@ -1601,8 +1231,7 @@ def run_mscore(state, spec):
     gt, est, skip = _load_score_maps(MSCORE_WORD, spec)
     r = opt.map_score(state, gt, est, skip=skip, thr=spec.thr, radius=spec.radius or 0)
     score = dict(hist=r["hist"][0], thr=tuple(spec.thr), match=r["match"][0])
-    with open(spec.out, "w") as f:
-        f.write(format_map_score(score))
+    _write_text(spec.out, format_map_score(score))
     return score
 
 

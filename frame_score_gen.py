@@ -48,7 +48,6 @@ import os
 import os.path as osp
 import re
 import sys
-import threading
 
 import numpy as np
 from PIL import Image
@@ -56,6 +55,7 @@ from PIL import Image
 HERE = osp.dirname(osp.abspath(__file__))
 sys.path.insert(0, HERE)
 import para_gen                             # noqa: E402
+import score_cli                            # noqa: E402
 from arap_flow_amd import pipeline          # noqa: E402
 
 MID_FRAME = re.compile(r"^(.*)_s(\d\d)\.png$")
@@ -159,32 +159,10 @@ def main(flags):
     for it in items:
         if promised is not None:
             after.setdefault(promised[it.est], []).append(it)
-    done, lock = [], threading.Lock()
-    workers = None
-
-    def on_done(path):
-        with lock:
-            done.append(path)
-        for it in after.get(path, ()):
-            workers.put_owed(pipeline.format_line(it))
-    if items:
-        serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == para_gen.CPP_BIN)
-        workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, serve, on_done)
-        for prefix, owed in after.items():
-            for _ in owed:
-                workers.owe()
-            workers.put(pipeline.format_line(interp[prefix]))
-        for it in items if promised is None else ():
-            workers.put(pipeline.format_line(it))
-        workers.close()
-        workers.join()
-    assert sorted(done) == sorted([it.out for it in items] + list(after)), "a line was not reported done"
+    score_cli.run_lines(flags, items if promised is None else [interp[prefix] for prefix in after], after)
     tables = [pipeline.parse_frame_score_file(open(it.out).read()) for it in items]
     pooled = pipeline.add_frame_scores(tables)
-    with open(osp.join(data, "frame_score.txt"), "w") as f:
-        f.write(pipeline.format_frame_score(pooled))
-    with open(osp.join(data, "frame_score_missing.list"), "w") as f:
-        f.write("".join(m + "\n" for m in missing))
+    score_cli.write_results(data, "frame_score", pipeline.format_frame_score(pooled), missing)
     print("%d frames scored, %d without an estimate" % (len(items), len(missing)))
     print(summary_text(pooled), end="")
     psnr = [pipeline.frame_score_summary(t)["all"]["psnr"] for t in tables if int(t[0, 1]) > 0 and int(t[0, 0]) > 0]
@@ -201,18 +179,13 @@ def parse(argv=None):
     parser.add_argument("--full", action="store_true", help="score the in-between frames of MidFull instead of Mid and wRGB")
     parser.add_argument("--baseline", choices=["blend"], help="score the rounded mean of a pair's end frames instead of --est")
     parser.add_argument("--from_flows", action="store_true", help="--est holds flow estimates: splat them into OUT/FramesEst first")
-    parser.add_argument("--gpu", nargs="*", type=int, default=[0], help="GPU ids, default 0")
-    parser.add_argument("--narap", type=int, default=64, help="lines one GPU holds at a time")
-    parser.add_argument("--arap_bin", default=para_gen.CPP_BIN if osp.exists(para_gen.CPP_BIN) else
-                        "%s %s" % (sys.executable, osp.join(HERE, "arap_deform.py")), help="this repository's arap_deform")
-    parser.add_argument("--worker", choices=["auto", "serve", "batch"], default="auto", help="as para_gen.py's --worker")
+    score_cli.add_worker_options(parser)
     flags = parser.parse_args(argv)
     if (flags.est is None) == (flags.baseline is None):
         parser.error("one of --est and --baseline is needed")
     if flags.from_flows and flags.est is None:
         parser.error("--from_flows needs --est, the root of the flow estimates, and excludes --baseline")
-    if not para_gen.own_arap_bin(flags.arap_bin):
-        parser.error("--arap_bin: an `fscore` line needs this repository's driver")
+    score_cli.check_driver(parser, flags, "an `fscore` line")
     return flags
 
 

@@ -30,7 +30,6 @@ import math
 import os
 import os.path as osp
 import sys
-import threading
 
 import numpy as np
 from PIL import Image
@@ -38,6 +37,7 @@ from PIL import Image
 HERE = osp.dirname(osp.abspath(__file__))
 sys.path.insert(0, HERE)
 import para_gen                             # noqa: E402
+import score_cli                            # noqa: E402
 from arap_flow_amd import pipeline          # noqa: E402
 
 SCORE_DIR = "MapScore"
@@ -130,19 +130,7 @@ def main(flags):
     data = osp.abspath(flags.data)
     still = flags.baseline == "still"
     items, missing = score_items(data, None if still else osp.abspath(flags.est), flags.full, flags.radius, flags.thr, still)
-    done, lock = [], threading.Lock()
-
-    def on_done(path):
-        with lock:
-            done.append(path)
-    if items:
-        serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == para_gen.CPP_BIN)
-        workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, serve, on_done)
-        for _, it in items:
-            workers.put(pipeline.format_line(it))
-        workers.close()
-        workers.join()
-    assert sorted(done) == sorted(it.out for _, it in items), "a line was not reported done"
+    score_cli.run_lines(flags, [it for _, it in items])
     per_file = {}
     for top, it in items:
         text = open(it.out).read()
@@ -150,10 +138,7 @@ def main(flags):
                                             else pipeline.parse_map_score_file(text))
     pooled = {top: pipeline.add_label_scores(ts) if isinstance(ts[0], np.ndarray) else pipeline.add_map_scores(ts)
               for top, ts in per_file.items()}
-    with open(osp.join(data, "map_score.txt"), "w") as f:
-        f.write(pooled_text(pooled))
-    with open(osp.join(data, "map_score_missing.list"), "w") as f:
-        f.write("".join(m + "\n" for m in missing))
+    score_cli.write_results(data, "map_score", pooled_text(pooled), missing)
     print("%d maps scored, %d without an estimate" % (len(items), len(missing)))
     print(summary_text(pooled, per_file), end="")
     return pooled
@@ -167,11 +152,7 @@ def parse(argv=None):
     parser.add_argument("--radius", type=int, help="the tolerance of the boundary match; default 0.008 of the diagonal, rounded up")
     parser.add_argument("--thr", default=",".join("%d" % t for t in DEFAULT_THR), help="thresholds of the tolerant match of MB and MBBwd")
     parser.add_argument("--baseline", choices=["still"], help="score Index1 as the estimate of Index2 instead of --est")
-    parser.add_argument("--gpu", nargs="*", type=int, default=[0], help="GPU ids, default 0")
-    parser.add_argument("--narap", type=int, default=64, help="lines one GPU holds at a time")
-    parser.add_argument("--arap_bin", default=para_gen.CPP_BIN if osp.exists(para_gen.CPP_BIN) else
-                        "%s %s" % (sys.executable, osp.join(HERE, "arap_deform.py")), help="this repository's arap_deform")
-    parser.add_argument("--worker", choices=["auto", "serve", "batch"], default="auto", help="as para_gen.py's --worker")
+    score_cli.add_worker_options(parser)
     flags = parser.parse_args(argv)
     if (flags.est is None) == (flags.baseline is None):
         parser.error("one of --est and --baseline is needed")
@@ -183,8 +164,7 @@ def parse(argv=None):
         parser.error("--thr: at most %d thresholds, each 1..255" % pipeline.MSCORE_MAX_THR)
     if flags.radius is not None and not 0 <= flags.radius <= pipeline.SEG_MAX_RADIUS:
         parser.error("--radius: 0..%d" % pipeline.SEG_MAX_RADIUS)
-    if not para_gen.own_arap_bin(flags.arap_bin):
-        parser.error("--arap_bin: an `lscore` or `mscore` line needs this repository's driver")
+    score_cli.check_driver(parser, flags, "an `lscore` or `mscore` line")
     return flags
 
 

@@ -20,11 +20,10 @@ import argparse
 import os
 import os.path as osp
 import sys
-import threading
 
 HERE = osp.dirname(osp.abspath(__file__))
 sys.path.insert(0, HERE)
-import para_gen                             # noqa: E402
+import score_cli                            # noqa: E402
 from arap_flow_amd import pipeline          # noqa: E402
 
 
@@ -71,25 +70,9 @@ def summary_text(table):
 def main(flags):
     data = osp.abspath(flags.data)
     items, missing = score_items(data, osp.abspath(flags.est), flags.full)
-    done, lock = [], threading.Lock()
-
-    def on_done(path):
-        with lock:
-            done.append(path)
-    if items:
-        serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == para_gen.CPP_BIN)
-        workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, serve, on_done)
-        for it in items:
-            workers.put(pipeline.format_line(it))
-        workers.close()
-        workers.join()
-    assert sorted(done) == sorted(it.out for it in items), "a score line was not reported done"
-    tables = [pipeline.parse_score_file(open(it.out).read()) for it in items]
-    pooled = pipeline.add_scores(tables)
-    with open(osp.join(data, "score.txt"), "w") as f:
-        f.write(pipeline.format_score(pooled))
-    with open(osp.join(data, "score_missing.list"), "w") as f:
-        f.write("".join(m + "\n" for m in missing))
+    score_cli.run_lines(flags, items)
+    pooled = pipeline.add_scores([pipeline.parse_score_file(open(it.out).read()) for it in items])
+    score_cli.write_results(data, "score", pipeline.format_score(pooled), missing)
     print("%d pairs scored, %d without an estimate" % (len(items), len(missing)))
     print(summary_text(pooled), end="")
     return pooled
@@ -100,14 +83,9 @@ def parse(argv=None):
     parser.add_argument("--data", required=True, help="the dataset: para_gen.py's --output")
     parser.add_argument("--est", required=True, help="the estimates: EST/<seq>/<frame>.flo, named like the dataset's flow files")
     parser.add_argument("--full", action="store_true", help="score against FlowFull / OccFull, every pixel, instead of Flow on the objects")
-    parser.add_argument("--gpu", nargs="*", type=int, default=[0], help="GPU ids, default 0")
-    parser.add_argument("--narap", type=int, default=64, help="lines one GPU holds at a time")
-    parser.add_argument("--arap_bin", default=para_gen.CPP_BIN if osp.exists(para_gen.CPP_BIN) else
-                        "%s %s" % (sys.executable, osp.join(HERE, "arap_deform.py")), help="this repository's arap_deform")
-    parser.add_argument("--worker", choices=["auto", "serve", "batch"], default="auto", help="as para_gen.py's --worker")
+    score_cli.add_worker_options(parser)
     flags = parser.parse_args(argv)
-    if not para_gen.own_arap_bin(flags.arap_bin):
-        parser.error("--arap_bin: a `score` line needs this repository's driver")
+    score_cli.check_driver(parser, flags, "a `score` line")
     return flags
 
 

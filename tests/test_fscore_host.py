@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import fscore_ref
-from arap_flow_amd import capi, pipeline
+from arap_flow_amd import capi, pipeline, scores
 
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 ONE = fscore_ref.ONE
@@ -198,8 +198,9 @@ def test_new_entry_point_exported_and_refusals_without_a_device():
     assert "int ArapFlow_FrameScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* ref, const void* est," in header
     assert (capi.FSCORE_ROWS, capi.FSCORE_FIELDS) == (len(pipeline.FSCORE_ROWS), len(pipeline.FSCORE_FIELDS)) == (9, 7)
     src = open(osp.join(ROOT, "arap_flow_amd", "opt.py")).read()
-    assert 'FSCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")' in src
-    assert 'FSCORE_FIELDS = ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")' in src
+    assert "from .scores import (SCORE_ROWS, SCORE_FIELDS, FSCORE_ROWS, FSCORE_FIELDS," in src          # opt's names are scores.py's
+    assert scores.FSCORE_ROWS == ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "obj", "bg", "left_out")
+    assert scores.FSCORE_FIELDS == ("count", "sse", "sad", "max", "windows", "ssim_sum", "ssim_worst")
     # refused before anything is read or launched: a stand-in for the state and the buffers is never dereferenced
     mem = C.create_string_buffer(4096)
     p = C.c_void_p(C.addressof(mem))

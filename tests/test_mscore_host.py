@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import mscore_ref
-from arap_flow_amd import capi, pipeline
+from arap_flow_amd import capi, pipeline, scores
 
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 U8 = np.uint8
@@ -272,7 +272,8 @@ def test_new_entry_points_exported_and_refusals_without_a_device():
     assert "int ArapFlow_MapScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* gt, const void* est," in header
     assert (capi.LSCORE_FIELDS, capi.MSCORE_MAX_THR) == (8, pipeline.MSCORE_MAX_THR) == (len(pipeline.LSCORE_FIELDS) + 1, 8)
     src = open(osp.join(ROOT, "arap_flow_amd", "opt.py")).read()
-    assert 'LSCORE_FIELDS = ("gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit", "zero")' in src
+    assert "LSCORE_TABLE_FIELDS as LSCORE_FIELDS," in src                                   # opt's name is scores.py's table row
+    assert scores.LSCORE_TABLE_FIELDS == ("gt", "est", "inter", "gt_b", "est_b", "gt_hit", "est_hit", "zero")
     # the scratch: 7 bytes a pixel in five parts of 256-byte steps, whatever n; 0 for sizes the calls refuse
     up = lambda v: (v + 255) // 256 * 256
     for W, H in ((5, 3), (854, 480), (256, 1), (257, 1)):

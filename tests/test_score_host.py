@@ -12,7 +12,7 @@ import pytest
 from PIL import Image
 
 import score_ref
-from arap_flow_amd import capi, flo, pipeline
+from arap_flow_amd import capi, flo, pipeline, scores
 
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 F = np.float32
@@ -262,8 +262,9 @@ def test_new_entry_point_exported_and_refusals_without_a_device():
     assert "int ArapFlow_FlowScore(Opt_State* state, unsigned W, unsigned H, unsigned n, const void* gt, const void* est," in header
     assert (capi.SCORE_ROWS, capi.SCORE_FIELDS) == (len(pipeline.SCORE_ROWS), len(pipeline.SCORE_FIELDS)) == (10, 8)
     src = open(osp.join(ROOT, "arap_flow_amd", "opt.py")).read()
-    assert 'SCORE_ROWS = ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")' in src
-    assert 'SCORE_FIELDS = ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")' in src
+    assert "from .scores import (SCORE_ROWS, SCORE_FIELDS," in src                          # opt's names are scores.py's
+    assert scores.SCORE_ROWS == ("all", "noc", "occ", "d0-10", "d10-60", "d60-140", "s0-10", "s10-40", "s40+", "left_out")
+    assert scores.SCORE_FIELDS == ("count", "sum", "n1", "n3", "n5", "fl", "nonfinite", "max")
     # refused before anything is read or launched: a stand-in for the state and the buffers is never dereferenced
     mem = C.create_string_buffer(4096)
     p = C.c_void_p(C.addressof(mem))

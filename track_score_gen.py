@@ -24,13 +24,12 @@ import os
 import os.path as osp
 import struct
 import sys
-import threading
 
 import numpy as np
 
 HERE = osp.dirname(osp.abspath(__file__))
 sys.path.insert(0, HERE)
-import para_gen                             # noqa: E402
+import score_cli                            # noqa: E402
 from arap_flow_amd import pipeline          # noqa: E402
 
 
@@ -98,34 +97,12 @@ def summary_text(table):
 def main(flags):
     data = osp.abspath(flags.data)
     items, missing = score_items(data, osp.abspath(flags.est), flags.from_flows, flags.tapvid)
-    done, lock = [], threading.Lock()
-    after = {chain.out: ts for chain, ts in items if chain is not None}      # a chain's track file -> the line that scores it
-    workers = None
-
-    def on_done(path):
-        with lock:
-            done.append(path)
-        if path in after:
-            workers.put_owed(pipeline.format_line(after[path]))
-    if items:
-        serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == para_gen.CPP_BIN)
-        workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, serve, on_done)
-        for chain, ts in items:
-            if chain is not None:
-                workers.owe()
-                workers.put(pipeline.format_line(chain))
-            else:
-                workers.put(pipeline.format_line(ts))
-        workers.close()
-        workers.join()
-    assert sorted(done) == sorted([ts.out for _, ts in items] + list(after)), "a line was not reported done"
+    # a chain's track file -> the line that scores it
+    score_cli.run_lines(flags, [chain or ts for chain, ts in items], {chain.out: [ts] for chain, ts in items if chain is not None})
     tables = [pipeline.parse_track_score_file(open(ts.out).read()) for _, ts in items]
     pooled = pipeline.add_track_scores(tables) if tables else \
         np.zeros((2, len(pipeline.TSCORE_CLASSES), len(pipeline.TSCORE_FIELDS)), np.uint64)
-    with open(osp.join(data, "track_score.txt"), "w") as f:
-        f.write(pipeline.format_track_score(pooled))
-    with open(osp.join(data, "track_score_missing.list"), "w") as f:
-        f.write("".join(m + "\n" for m in missing))
+    score_cli.write_results(data, "track_score", pipeline.format_track_score(pooled), missing)
     print("%d track files scored, %d without an estimate" % (len(items), len(missing)))
     print(summary_text(pooled), end="")
     return pooled
@@ -137,14 +114,9 @@ def parse(argv=None):
     parser.add_argument("--est", required=True, help="the estimates: EST/<seq>/<frame>.trk, or with --from_flows EST/<seq>/<frame>_l<j>.flo")
     parser.add_argument("--from_flows", action="store_true", help="chain per-link flow estimates into OUT/TracksEst first")
     parser.add_argument("--tapvid", action="store_true", help="take the error on the benchmark's 256 x 256 raster")
-    parser.add_argument("--gpu", nargs="*", type=int, default=[0], help="GPU ids, default 0")
-    parser.add_argument("--narap", type=int, default=64, help="lines one GPU holds at a time")
-    parser.add_argument("--arap_bin", default=para_gen.CPP_BIN if osp.exists(para_gen.CPP_BIN) else
-                        "%s %s" % (sys.executable, osp.join(HERE, "arap_deform.py")), help="this repository's arap_deform")
-    parser.add_argument("--worker", choices=["auto", "serve", "batch"], default="auto", help="as para_gen.py's --worker")
+    score_cli.add_worker_options(parser)
     flags = parser.parse_args(argv)
-    if not para_gen.own_arap_bin(flags.arap_bin):
-        parser.error("--arap_bin: a `tscore` line needs this repository's driver")
+    score_cli.check_driver(parser, flags, "a `tscore` line")
     return flags
 
 
