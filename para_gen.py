@@ -226,7 +226,7 @@ class Frame:
     """one frame pair on its way from prepare_pair through main to finish_frame"""
     line: pipeline.SolveLine       # the pair's list line; its outputs are the frame's outputs
     segs: list                     # --multseg: the per-segment lines that are solved in its place, else None
-    layers: dict                   # --occ_layers: the frame's layers line (pipeline.parse_layers), else None
+    layers: object                 # --occ_layers: the frame's layers line (pipeline.LayersLine), else None
     bg: object                     # the background fitted to the frame (an array), or None; --bg_motion: the path of
                                    # the enlarged background picture
     remove: bool                   # --multseg: delete the segments' files once they are merged
@@ -322,7 +322,7 @@ def prepare_pair(args):
         out = dict(occ=p[LAYERS_OCC]) if LAYERS_OCC in p else {}
         if midl:
             out["mid"] = pipeline.mid_token(midl, p["midl_gen"])
-        layers = dict(rgb=line.rgb, layers=[(sg.mask, sg.flow) for sg in segs], out=out)
+        layers = pipeline.LayersLine(line.rgb, [(sg.mask, sg.flow) for sg in segs], out)
     rec = Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
     if trk_out is not None and rec.solves:      # the tracks: the points from the pair's own generator, every state file named
         from arap_flow_amd import trk
@@ -413,8 +413,8 @@ def finish_frame(rec):
     --bg_motion pair's comes from its bg line afterwards: rec.bg is then a path, not the fitted array)"""
     if not isinstance(rec.bg, np.ndarray):
         rec = dataclasses.replace(rec, bg=None)
-    if rec.layers is not None and "mid" in rec.layers["out"]:       # --mid_layers: the layers line is done
-        steps, prefix = pipeline.parse_mid(rec.layers["out"]["mid"])
+    if rec.layers is not None and "mid" in rec.layers.out:          # --mid_layers: the layers line is done
+        steps, prefix = pipeline.parse_mid(rec.layers.out["mid"])
         if rec.bg is not None:                              # the in-between frames get the pair's background too
             for f in (pipeline.mid_files(prefix, i) for i in steps):
                 im, m = np.array(Image.open(f["rgb"]).convert("RGB")), np.array(Image.open(f["mask"]))

@@ -187,7 +187,7 @@ def test_bg_line_round_trip():
             pipeline.parse_line(bad)
     # the other forms still parse as themselves
     assert isinstance(pipeline.parse_line("a b c d e f"), pipeline.SolveLine)
-    assert isinstance(pipeline.parse_line("layers r 1 m f occ=o"), dict)
+    assert isinstance(pipeline.parse_line("layers r 1 m f occ=o"), pipeline.LayersLine)
 
 
 def test_bg_maps_window_and_corner_rule():

@@ -179,7 +179,7 @@ def test_tokens_through_both_grammars():
 def test_deform_list_turns_diagnostics_on_only_for_batches_that_ask(monkeypatch):
     """a stand-in solver: plain batches never see set_diag; a batch with a diag= or fold= line turns it on in its lane,
     and the next plain batch of that lane turns it off again"""
-    from arap_flow_amd import opt, pipeline
+    from arap_flow_amd import opt, pipeline, run_lines
     six = "r%d.png m%d.png c%d.txt f%d.flo w%d.png wm%d.png"
     extras = [{}, {}, dict(diag="d2.txt"), {}, {}, {}, {}, dict(fold="f7.png"), {}, {}]
     lines = [pipeline.parse_line(" ".join([six.replace("%d", str(k))] + pipeline.extra_tokens(e))) for k, e in enumerate(extras)]
@@ -215,8 +215,8 @@ def test_deform_list_turns_diagnostics_on_only_for_batches_that_ask(monkeypatch)
             pass
 
     monkeypatch.setattr(opt, "FrameSolver", Solver)
-    monkeypatch.setattr(pipeline, "_load_line", lambda ln: (np.zeros((4, 6, 3), np.uint8), np.zeros((4, 6), np.uint8), lines.index(ln)))
-    monkeypatch.setattr(pipeline, "_save_result", lambda ln, r: None)
+    monkeypatch.setattr(run_lines, "_load_line", lambda ln: (np.zeros((4, 6, 3), np.uint8), np.zeros((4, 6), np.uint8), lines.index(ln)))
+    monkeypatch.setattr(run_lines, "_save_result", lambda ln, r: None)
     pipeline.deform_list(SimpleNamespace(use_own_stream=lambda: None), lines, max_batch=2, verbose=False)
     assert calls == [("solve", 0, [0, 1]), ("set_diag", 1, True), ("solve", 1, [2, 3]), ("solve", 0, [4, 5]),
                      ("solve", 1, [6, 7]), ("solve", 0, [8, 9])]

@@ -233,7 +233,7 @@ def test_layers_mid_line_both_twins_equal_the_api(tmp_path, gpu_state):
     for tag in ("py", "cpp", "serve"):
         prefix = str(tmp_path / (tag + "_mid"))
         out = dict(occ=str(tmp_path / (tag + "_occ.png")), mid=pipeline.mid_token(steps, prefix))
-        line = pipeline.layers_line(str(tmp_path / "r.png"), layers, out)
+        line = pipeline.layers_line(pipeline.LayersLine(str(tmp_path / "r.png"), layers, out))
         if tag == "serve":
             said = _run([cpp, "--serve"], str(tmp_path), stdin=line + "\n")
             assert "Done " + out["occ"] in said.splitlines()
@@ -255,7 +255,7 @@ def test_layers_mid_line_both_twins_equal_the_api(tmp_path, gpu_state):
                 assert _same(g[key], got["py"][k][key]), (tag, key)
     # a flow that is not named *.flo, or a missing snapshot, ends the run with a message
     os.rename(tmp_path / "f1_s12.flo", tmp_path / "gone.flo")
-    bad = pipeline.layers_line(str(tmp_path / "r.png"), layers, dict(mid=pipeline.mid_token(steps, str(tmp_path / "x"))))
+    bad = pipeline.layers_line(pipeline.LayersLine(str(tmp_path / "r.png"), layers, dict(mid=pipeline.mid_token(steps, str(tmp_path / "x")))))
     (tmp_path / "bad.txt").write_text(bad)
     env = dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "0"))
     for prog in ([sys.executable, osp.join(ROOT, "arap_deform.py")], [cpp]):

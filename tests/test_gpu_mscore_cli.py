@@ -54,7 +54,7 @@ def test_lines_all_three_hosts_equal_the_twin_on_a_solved_frame(tmp_path):
                                  p("wm%d.png" % s), extra={}) for s, _ in segs]
     layers = [(ln.mask, ln.flow) for ln in solves]
     seg = pipeline.SegLine(layers, 1.0, 16, (), {k: p(k + ".png") for k in ("idx1", "idx2", "mb1", "mb2")})
-    made = [pipeline.format_line(ln) for ln in solves] + [pipeline.layers_line(p("r.png"), layers, dict(occ=p("occ.png"))),
+    made = [pipeline.format_line(ln) for ln in solves] + [pipeline.layers_line(pipeline.LayersLine(p("r.png"), layers, dict(occ=p("occ.png")))),
                                                           pipeline.format_line(seg)]
     (tmp_path / "make.txt").write_text("\n".join(made) + "\n")
     _run([cpp, p("make.txt")], str(tmp_path))

@@ -56,7 +56,7 @@ def test_solve_seg_and_score_lines_all_three_hosts_equal_the_twin(tmp_path):
                                  p("wm%d.png" % s), extra=dict(fold=p("fold%d.png" % s))) for s, _ in segs]
     layers = [(ln.mask, ln.flow) for ln in solves]
     seg = pipeline.SegLine(layers, 1.0, 140, (), dict(dist1=p("dist.png")))
-    lay = dict(rgb=p("r.png"), layers=layers, out=dict(occ=p("occ.png")))
+    lay = pipeline.LayersLine(p("r.png"), layers, dict(occ=p("occ.png")))
     (tmp_path / "gen.txt").write_text("\n".join(pipeline.format_line(x) for x in solves + [lay, seg]) + "\n")
     _run([cpp, p("gen.txt")], str(tmp_path))
     # the ground truth: segment 0's flow; the "estimate": that flow perturbed, with a few outliers and a hole

@@ -104,12 +104,12 @@ def test_mid_token_round_trip_on_a_layers_line():
     assert pipeline.LAYER_KEYS[-1] == "mid" and pipeline.LAYER_KEYS[0] == "occ"
     text = LAY + " mid=6,12:/o/Mid/f occ=/o/o.png"
     spec = pipeline.parse_line(text)
-    assert spec["out"] == dict(mid="6,12:/o/Mid/f", occ="/o/o.png")
+    assert spec.out == dict(mid="6,12:/o/Mid/f", occ="/o/o.png")
     assert pipeline.done_token(spec) == "6,12:/o/Mid/f"          # the first output token on the line
     canonical = pipeline.format_line(spec)
     assert canonical == LAY + " occ=/o/o.png mid=6,12:/o/Mid/f"  # layers_line still writes occ first, mid last
     again = pipeline.parse_line(canonical)
-    assert again["out"] == spec["out"] and pipeline.done_token(again) == "/o/o.png"
+    assert again.out == spec.out and pipeline.done_token(again) == "/o/o.png"
     assert pipeline.format_line(again) == canonical
     only = pipeline.parse_line(LAY + " mid=3:/o/p")               # mid alone is an output
     assert pipeline.done_token(only) == "3:/o/p"

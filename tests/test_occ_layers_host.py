@@ -84,11 +84,11 @@ def test_layers_line_round_trip_and_old_lines_unchanged(tmp_path):
     assert [ln[:6] for ln in solves] == [tuple(six.split())] * 3
     assert [ln.extra for ln in solves] == [{}, dict(occ="/x.png"), {}]
     spec = items[2]
-    assert spec["rgb"] == "/a/r.png" and spec["layers"] == [("/a/m1.png", "/a/f1.flo"), ("/a/m2.png", "/a/f2.flo")]
-    assert spec["out"] == dict(bwd="/o/b.flo", occ="/o/o.png")
+    assert spec.rgb == "/a/r.png" and spec.layers == [("/a/m1.png", "/a/f1.flo"), ("/a/m2.png", "/a/f2.flo")]
+    assert spec.out == dict(bwd="/o/b.flo", occ="/o/o.png")
     assert pipeline.done_token(spec) == "/o/b.flo"               # the first output token on the line
-    again = pipeline.parse_layers(pipeline.layers_line(spec["rgb"], spec["layers"], spec["out"]).split())
-    assert again["layers"] == spec["layers"] and again["out"] == spec["out"]
+    again = pipeline.parse_layers(pipeline.layers_line(spec).split())
+    assert again.layers == spec.layers and again.out == spec.out
     assert pipeline.done_token(again) == "/o/o.png"              # layers_line writes occ first
     for bad in BAD_LAYERS:
         with pytest.raises(ValueError):

@@ -97,7 +97,7 @@ def test_deform_list_saves_every_result_with_its_own_line(monkeypatch):
     """deform_list's two alternating lanes over 5 frames of one size, two to a batch, with a stand-in solver: the result
     read from slot b of a lane is saved under the line (and so the optional outputs) that was set into that slot, and
     every batch asks the solver for what its own lines want"""
-    from arap_flow_amd import opt, pipeline
+    from arap_flow_amd import opt, pipeline, run_lines
     six = "r%d.png m%d.png c%d.txt f%d.flo w%d.png wm%d.png"
     extras = [{}, dict(bwd="b1.flo"), dict(occ="o2.png"), dict(occ_bwd="ob3.png"), dict(bwd="b4.flo", occ="o4.png")]
     lines = [pipeline.parse_line(" ".join([six.replace("%d", str(k))] + pipeline.extra_tokens(e)))
@@ -137,9 +137,9 @@ def test_deform_list_saves_every_result_with_its_own_line(monkeypatch):
             pass
 
     monkeypatch.setattr(opt, "FrameSolver", Solver)
-    monkeypatch.setattr(pipeline, "_load_line",
+    monkeypatch.setattr(run_lines, "_load_line",
                         lambda ln: (np.zeros((4, 6, 3), np.uint8), np.zeros((4, 6), np.uint8), lines.index(ln)))
-    monkeypatch.setattr(pipeline, "_save_result", lambda ln, r: saved.append((int(r["flow"][0]), ln)))
+    monkeypatch.setattr(run_lines, "_save_result", lambda ln, r: saved.append((int(r["flow"][0]), ln)))
     pipeline.deform_list(State(), lines, max_batch=2, verbose=False)
     assert sorted(k for k, _ in saved) == [0, 1, 2, 3, 4]
     for k, ln in saved:
