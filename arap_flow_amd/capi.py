@@ -36,6 +36,13 @@ class LightFrame(C.Structure):
                 ("sigma0", C.c_float), ("sigma1", C.c_float)]
 
 
+class AugSample(C.Structure):
+    """ArapFlow_AugSample (DESIGN.md "Training batches")"""
+    _fields_ = [("T1", C.c_float * 6), ("T2", C.c_float * 6), ("gain1", C.c_float * 3), ("gamma1", C.c_float),
+                ("gain2", C.c_float * 3), ("gamma2", C.c_float), ("n_erase", C.c_uint32), ("erase", (C.c_int32 * 4) * 4),
+                ("fill", C.c_float * 3)]
+
+
 TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")      # ARAPFLOW_TEX_*: a kind's number is its index here
 
 MESH_STATS_KEYS = tuple(k for k, _ in MeshStats._fields_ if k != "reserved")     # the order of a diag file's lines
@@ -132,6 +139,9 @@ SYMBOLS = [
     ("ArapFlow_SolverSetDiag", _I, [_VP, _I]),
     ("ArapFlow_SolverGetDiag", _I, [_VP, _U, C.POINTER(MeshStats), _VP]),
     ("ArapFlow_SolverHostDiag", _I, [_VP, _U, C.POINTER(C.POINTER(MeshStats)), C.POINTER(_VP)]),
+    ("ArapFlow_AugmentTables", _I, [C.POINTER(AugSample)] + [C.POINTER(C.c_float)] * 4),
+    ("ArapFlow_AugmentPairs", _I, [_VP, _U, _U, _U, _U, _U] + [_VP] * 4 + [C.POINTER(AugSample)] + [C.POINTER(C.c_float)] * 2 +
+     [C.c_float] + [_VP] * 4),
 ]
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h
@@ -144,6 +154,7 @@ FSCORE_ROWS, FSCORE_FIELDS = 9, 7         # ARAPFLOW_FSCORE_ROWS, ARAPFLOW_FSCOR
 LSCORE_FIELDS, MSCORE_MAX_THR = 8, 8      # ARAPFLOW_LSCORE_FIELDS, ARAPFLOW_MSCORE_MAX_THR
 INTERP_MAX_TIMES, INTERP_FILL = 32, 16     # ARAPFLOW_INTERP_MAX_TIMES, ARAPFLOW_INTERP_FILL
 LIGHT_MAX_R, LIGHT_MAX_SHIFT = 16, 64   # ARAPFLOW_LIGHT_MAX_R, ARAPFLOW_LIGHT_MAX_SHIFT
+AUG_MAX_BATCH, AUG_MAX_ERASE = 64, 4    # ARAPFLOW_AUG_MAX_BATCH, ARAPFLOW_AUG_MAX_ERASE
 
 _LIB = None
 

@@ -101,6 +101,7 @@ Opt_State* Opt_NewState(Opt_InitializationParameters params)
     st->force_b8 = knobs.b8;               // experiments: 8-byte form of phase B
     st->stream_a = knobs.stream_a;
     st->mscore_plain = knobs.mscore_plain;
+    st->aug_bytes = knobs.aug_bytes;
     return st;
 }
 
@@ -115,6 +116,7 @@ void ArapFlow_FreeState(Opt_State* st)
     if (st->diag) (void)hipFree(st->diag);
     if (st->tex) (void)hipFree(st->tex);
     if (st->light) (void)hipFree(st->light);
+    if (st->aug) (void)hipFree(st->aug);
     delete st;
 }
 

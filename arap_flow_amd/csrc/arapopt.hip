@@ -50,6 +50,7 @@
 #include "arap_interp.h"
 #include "arap_diag.h"
 #include "arap_frame.h"
+#include "arap_aug.h"
 
 using namespace arap;
 
@@ -68,3 +69,4 @@ using namespace arap;
 #include "abi_mscore.h"      // ArapFlow_LabelScore, ArapFlow_MapScore
 #include "abi_interp.h"      // ArapFlow_InterpFrames
 #include "abi_solver.h"      // ArapFlow_Solver*
+#include "abi_aug.h"         // ArapFlow_AugmentTables, ArapFlow_AugmentPairs

@@ -64,6 +64,7 @@ struct Knobs {
     bool b8 = false;            // ARAPOPT_B8=1: the 8-byte-per-lane form of phase B
     int stream_a = 0;           // ARAPOPT_STREAM_A
     bool mscore_plain = false;  // ARAPOPT_MSCORE_PLAIN=1 (experiments: k_mscore_hist with one LDS atomic per pixel, no wave aggregation)
+    bool aug_bytes = false;     // ARAPOPT_AUG_BYTES=1 (experiments: k_augment reads a tap's three bytes one by one, not as one dword)
     // plan level
     bool no_resident = false;   // ARAPOPT_NO_RESIDENT=1
     int force_res_fail = 0;     // ARAPOPT_FORCE_RES_FAIL=1 / 2 (test hooks)
@@ -89,6 +90,7 @@ static Knobs read_knobs()
     k.b8 = is("ARAPOPT_B8", '1');
     k.stream_a = num("ARAPOPT_STREAM_A", 0);
     k.mscore_plain = is("ARAPOPT_MSCORE_PLAIN", '1');
+    k.aug_bytes = is("ARAPOPT_AUG_BYTES", '1');
     k.no_resident = is("ARAPOPT_NO_RESIDENT", '1');
     k.force_res_fail = is("ARAPOPT_FORCE_RES_FAIL", '1') ? 1 : (is("ARAPOPT_FORCE_RES_FAIL", '2') ? 2 : 0);
     k.no_xcd_fast = is("ARAPOPT_NO_XCD_FAST", '1');
@@ -123,6 +125,9 @@ struct Opt_State {
     void* diag = nullptr;       // ArapFlow_WarpDiag: device, the call's WarpJob (256 bytes) and its accumulator; at first use
     void* tex = nullptr;        // ArapFlow_Texture: device, the call's layer table (255 layers); at first use
     void* light = nullptr;      // ArapFlow_Relight: device, the call's tone table (3 x 256 bytes); at first use
+    void* aug = nullptr;        // ArapFlow_AugmentPairs: device, the call's sample table (aug_cap samples); at first use, grown with B
+    unsigned aug_cap = 0;
+    bool aug_bytes = false;     // ARAPOPT_AUG_BYTES=1 (experiments): k_augment without the dword loads of the taps
 };
 
 struct Opt_Problem {

@@ -19,9 +19,11 @@
   track_score      the TAP-Vid table of estimated tracks against a track file's (ArapFlow_TrackScore)
   chain_flows      estimated tracks from per-link flow estimates (ArapFlow_ChainFlows)
   interp_frames    estimated in-between frames from a flow estimate, by splatting (ArapFlow_InterpFrames)
+  augment_pairs    a training batch: B pairs augmented, cropped and normalised on the device (ArapFlow_AugmentPairs)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
+import collections
 import ctypes as C
 import math
 
@@ -813,6 +815,103 @@ def relight_pair(state, rgb1, mask1, rgb2, cover2, frames):
     if len(frames) != 2:
         raise ValueError("relight_pair: two light descriptions expected")
     return relight(state, rgb1, mask1, frames[0], cover_is_mask=True), relight(state, rgb2, cover2, frames[1])
+
+
+# a sample of a training batch (DESIGN.md "Training batches"): T1, T2 six floats each (output pixel -> source point of
+# frame 1 / frame 2), the tone curves (gain[3], gamma per frame), up to four eraser rectangles (x0, y0, x1, y1) on frame
+# 2 in output pixels, half-open, and their fill colour
+AugSample = collections.namedtuple("AugSample", "T1 T2 gain1 gamma1 gain2 gamma2 erase fill")
+AUG_NEUTRAL = AugSample((1, 0, 0, 0, 1, 0), (1, 0, 0, 0, 1, 0), (1, 1, 1), 1.0, (1, 1, 1), 1.0, (), (0, 0, 0))
+AUG_OUTPUTS = ("img1", "img2", "flow", "valid")
+
+
+def _f3(v, what):
+    if len(v) != 3:
+        raise ValueError("%s: three values expected" % what)
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def aug_sample(sample):
+    """an AugSample as the ArapFlow_AugSample the library reads; floats are rounded to float32 here.  More rectangles than
+    a sample holds are a ValueError (the library would see only a count)."""
+    T1, T2, gain1, gamma1, gain2, gamma2, erase, fill = sample
+    q = capi.AugSample()
+    q.T1, q.T2 = _map6(T1), _map6(T2)
+    q.gain1, q.gain2, q.fill = _f3(gain1, "gain1"), _f3(gain2, "gain2"), _f3(fill, "fill")
+    q.gamma1, q.gamma2 = float(gamma1), float(gamma2)
+    erase = [tuple(r) for r in erase]
+    if len(erase) > capi.AUG_MAX_ERASE or any(len(r) != 4 for r in erase):
+        raise ValueError("a sample has at most %d rectangles (x0, y0, x1, y1)" % capi.AUG_MAX_ERASE)
+    q.n_erase = len(erase)
+    for i, r in enumerate(erase):
+        q.erase[i] = (C.c_int32 * 4)(*[max(-1 << 31, min(int(v), (1 << 31) - 1)) for v in r])
+    return q
+
+
+def augment_tables(sample, scale=(1, 1, 1), bias=(0, 0, 0), lib=None):
+    """what the library derives of a sample (ArapFlow_AugmentTables, DESIGN.md "Training batches"): (P2 f32[6], the
+    inverse of T2; lut f32[2,3,256], the tone table of each frame with the normalisation folded in), the library's own
+    bits.  Host only (no GPU, no state).  A sample outside its ranges is a ValueError."""
+    lib = lib or capi.load()
+    P2, lut = (C.c_float * 6)(), (C.c_float * 1536)()
+    if lib.ArapFlow_AugmentTables(C.byref(aug_sample(sample)), _f3(scale, "scale"), _f3(bias, "bias"), P2, lut) != 0:
+        raise ValueError("ArapFlow_AugmentTables: bad arguments")
+    return np.array(P2[:], np.float32), np.array(lut[:], np.float32).reshape(2, 3, 256)
+
+
+def augment_pairs(state, rgb1, rgb2, flow, samples, size, skip=None, scale=(1, 1, 1), bias=(0, 0, 0), tau=1.0,
+                  want=AUG_OUTPUTS, out=None):
+    """a training batch in one launch (ArapFlow_AugmentPairs, DESIGN.md "Training batches").  rgb1, rgb2 u8[B,H,W,3], flow
+    f32[B,H,W,2], skip u8[B,H,W] or None (non-zero: no ground truth), numpy arrays or CUDA tensors; an input no wanted
+    output needs may be None.  samples: B AugSample; size = (w, h), the crop; scale, bias: the normalisation per channel;
+    tau: the most a pixel's flow taps may differ for its flow to count.  -> {name: CUDA tensor} of the outputs `want`
+    names: img1, img2 f32[B,3,h,w], flow f32[B,2,h,w], valid u8[B,h,w] (0 / 255).  Nothing is downloaded and nothing
+    waited for: the call is enqueued on the state's stream (State.set_stream; by default the null stream, torch's
+    default), where the inputs must be ready and the outputs are.  `out`: {name: tensor} of caller-owned CUDA tensors
+    (contiguous, of the output's shape and type) to write instead of new ones."""
+    want = tuple(want)
+    if not want or set(want) - set(AUG_OUTPUTS) or len(set(want)) != len(want):
+        raise ValueError("augment_pairs: want: some of %s" % ", ".join(AUG_OUTPUTS))
+    w, h = (int(v) for v in size)
+    samples = list(samples)
+    B = len(samples)
+
+    def up(a, dt, tail, what):
+        if a is None:
+            return None
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dt))
+        if t.dtype != getattr(torch, np.dtype(dt).name) or t.dim() != 1 + len(tail) + 2 or t.shape[0] != B or \
+                tuple(t.shape[3:]) != tail:
+            raise ValueError("augment_pairs: %s: %s[B,H,W%s] expected" % (what, np.dtype(dt).name, "".join(",%d" % v for v in tail)))
+        return t.cuda().contiguous()
+    ins = [up(rgb1, np.uint8, (3,), "rgb1"), up(rgb2, np.uint8, (3,), "rgb2"), up(flow, np.float32, (2,), "flow"),
+           up(skip, np.uint8, (), "skip")]
+    shapes = {tuple(t.shape[1:3]) for t in ins if t is not None}
+    if len(shapes) != 1:
+        raise ValueError("augment_pairs: inputs of one size [B,H,W,..] expected")
+    H, W = shapes.pop()
+    if not (0 < w < 1 << 31 and 0 < h < 1 << 31 and 0 < B <= capi.AUG_MAX_BATCH):
+        raise ValueError("augment_pairs: a crop of at least one pixel and 1 .. %d samples expected" % capi.AUG_MAX_BATCH)
+    form = {"img1": ((B, 3, h, w), torch.float32), "img2": ((B, 3, h, w), torch.float32), "flow": ((B, 2, h, w), torch.float32),
+            "valid": ((B, h, w), torch.uint8)}
+    outs = {}
+    for k in want:
+        shape, dt = form[k]
+        t = (out or {}).get(k)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device="cuda")
+        elif not (t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape and t.dtype == dt):
+            raise ValueError("augment_pairs: out[%r]: a contiguous CUDA %s tensor of shape %s expected" % (k, dt, shape))
+        outs[k] = t
+    table = (capi.AugSample * B)(*[aug_sample(s) for s in samples])
+    ptr = lambda t: None if t is None else _dev_ptr(t)
+    rc = state.lib.ArapFlow_AugmentPairs(state.handle, W, H, w, h, B, *[ptr(t) for t in ins], table, _f3(scale, "scale"),
+                                         _f3(bias, "bias"), float(tau), *[ptr(outs.get(k)) for k in AUG_OUTPUTS])
+    if rc == -1:
+        raise ValueError("ArapFlow_AugmentPairs: bad arguments")
+    if rc != 0:
+        raise RuntimeError("ArapFlow_AugmentPairs failed: %d" % rc)
+    return outs
 
 
 SEG_OUTPUTS = ("idx1", "idx2", "mb1", "mb2", "dist1", "dist2")

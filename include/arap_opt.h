@@ -872,6 +872,67 @@ int ArapFlow_SolverSetDiag(ArapFlow_Solver* s, int on);
 int ArapFlow_SolverGetDiag(ArapFlow_Solver* s, unsigned slot, ArapFlow_MeshStats* stats, uint8_t* fold);
 int ArapFlow_SolverHostDiag(ArapFlow_Solver* s, unsigned slot, const ArapFlow_MeshStats** stats, const uint8_t** fold);
 
+/* Training batches (DESIGN.md "Training batches"; the numpy twin is tests/aug_ref.py): B pairs of one source size W x H,
+ * each under its own geometric and photometric augmentation, cropped to w x h, normalised and laid out planar, in one
+ * launch.  DEVICE inputs, stacked like ArapFlow_FlowScore's pairs:
+ *   rgb1, rgb2   uint8[B][H][W][3]
+ *   flow         float[B][H][W][2], on frame 1's pixels
+ *   skip         uint8[B][H][W] or NULL: non-zero = no ground truth at that pixel
+ * DEVICE outputs, each NULL when not wanted (then it is not computed, and inputs only it needs are not read and may be
+ * NULL: img1 needs rgb1, img2 needs rgb2, out_flow and valid need flow):
+ *   img1, img2   float[B][3][h][w]
+ *   out_flow     float[B][2][h][w]
+ *   valid        uint8[B][h][w], 0 or 255
+ * Per sample a HOST ArapFlow_AugSample; per call scale[3], bias[3] (the normalisation) and tau >= 0 or +inf.
+ * Every float operator below is one IEEE float32 operation in the order of the parentheses; there is no fused
+ * multiply-add anywhere.  (float)x, (float)y: the output pixel's coordinates converted first.
+ *   q_k = ((a * x + b * y) + c, (d * x + e * y) + f), (a .. f) = T_k: the source point of frame k that output pixel
+ *         (x, y) shows
+ *   Tables (ArapFlow_AugmentTables, a pure host function; the device call uses the same code):
+ *     P2 = the inverse of T2 as a map, in IEEE double: det = a e - b d,
+ *          P2 = (e / det, -b / det, (b f - e c) / det, -d / det, a / det, (d c - a f) / det), each rounded once to float
+ *     lut[k][c][i] = (float)((255 * min(max(gain_k[c] * pow(i / 255, gamma_k), 0), 1)) * scale[c] + bias[c]), in double
+ *          with the C library's pow, rounded once.  Neutral (gain = gamma = scale = 1, bias = 0): lut[i] == i.
+ *   Taps of a point q in a W x H plane:  inside = q.x >= 0 && q.x <= W-1 && q.y >= 0 && q.y <= H-1 (false on NaN);
+ *     bx = fminf(fmaxf(q.x, 0), (float)(W-1));  x0 = min((int)floorf(bx), W-1);  x1 = min(x0 + 1, W-1);
+ *     fx = bx - (float)x0;  the same in y.  Tap ij is the pixel (x_j, y_i).
+ *   mix(c00, c01, c10, c11) = top + fy * (bot - top),  top = c00 + fx * (c01 - c00),  bot = c10 + fx * (c11 - c10)
+ *   Images:  img_k[c][y][x] = mix of lut[k][c][byte] at the four taps of q_k (not rounded); img2 is then fill[c] where
+ *     (x, y) lies in any of the sample's rectangles erase[i] = (x0, y0, x1, y1), half-open, output pixels.
+ *   Flow, at the taps of q1:  tap 01 is used iff fx > 0, tap 10 iff fy > 0, tap 11 iff both, tap 00 always.  An unused
+ *     tap is replaced by tap 00 (it is not read).  A tap is bad iff its skip byte is non-zero or a flow component is not
+ *     finite; a bad tap's value is (0, 0) in what follows.
+ *       u      = mix of the four values, per component
+ *       spread = max over the taps of max(|f.x - f00.x|, |f.y - f00.y|)
+ *       out.x  = (((P2.a * q1.x + P2.b * q1.y) + P2.c) - (float)x) + (P2.a * u.x + P2.b * u.y);  out.y with d, e, f
+ *       valid  = inside(q1) && no tap bad && spread <= tau && out.x and out.y finite
+ *     Where !valid: out_flow = (0, 0), valid = 0; else valid = 255.  spread <= tau is the motion-boundary guard.
+ * One kernel, one launch (grid.z = B), no atomics, no scratch: two runs give identical bytes.  The per-sample table
+ * lives in device memory the state owns (allocated at the first call, grown with B) and is copied stream-ordered
+ * before the call returns.  Nothing is allocated or launched unless the call is made.
+ * ArapFlow_AugmentTables returns 0; -1 on a null pointer, a non-finite coefficient of T1 or T2, det(T2) == 0 in double,
+ * or a gain or gamma that is not finite and > 0.  (n_erase, the rectangles and fill are not read.)
+ * ArapFlow_AugmentPairs is asynchronous on the state's stream.  Returns 0; -1, and nothing is launched or written, on: a
+ * null state, samples, scale or bias, a null input that an asked output needs, every output NULL, a zero size, W * H >= 2^31 or
+ * B * w * h >= 2^31, B > ARAPFLOW_AUG_MAX_BATCH, a sample that ArapFlow_AugmentTables refuses or whose n_erase exceeds
+ * ARAPFLOW_AUG_MAX_ERASE, tau NaN or negative, an output overlapping an input it reads or another output; else a HIP
+ * error code. */
+#define ARAPFLOW_AUG_MAX_BATCH 64
+#define ARAPFLOW_AUG_MAX_ERASE 4
+typedef struct ArapFlow_AugSample {
+    float T1[6], T2[6];
+    float gain1[3], gamma1, gain2[3], gamma2;
+    uint32_t n_erase;
+    int32_t erase[ARAPFLOW_AUG_MAX_ERASE][4];
+    float fill[3];
+} ArapFlow_AugSample;
+int ArapFlow_AugmentTables(const ArapFlow_AugSample* sample, const float scale[3], const float bias[3], float P2[6],
+                           float lut[2][3][256]);
+int ArapFlow_AugmentPairs(Opt_State* state, unsigned W, unsigned H, unsigned w, unsigned h, unsigned B, const void* rgb1,
+                          const void* rgb2, const void* flow, const void* skip, const ArapFlow_AugSample* samples,
+                          const float scale[3], const float bias[3], float tau, void* img1, void* img2, void* out_flow,
+                          void* valid);
+
 #ifdef __cplusplus
 }
 #endif
