@@ -79,7 +79,10 @@ int ArapFlow_AugmentPairs(Opt_State* st, unsigned W, unsigned H, unsigned w, uns
         if (hipMalloc(&st->aug, B * sizeof(AugSampleDev)) != hipSuccess) return (int)hipErrorOutOfMemory;
         st->aug_cap = B;
     }
-    HC(hipMemcpyAsync(st->aug, tab.data(), B * sizeof(AugSampleDev), hipMemcpyHostToDevice, st->stream));   // (pageable: staged before the call returns)
+    // pageable: the runtime has copied `tab` away when this returns and writes the table in the stream's order; it does not
+    // wait for the stream (tests/test_gpu_aug.py observes that).  One table per state: calls on one stream follow each other,
+    // a caller who moves the state to another stream orders the two streams (data.AugmentLoader does)
+    HC(hipMemcpyAsync(st->aug, tab.data(), B * sizeof(AugSampleDev), hipMemcpyHostToDevice, st->stream));
     AugJob j{};
     j.rgb1 = (const uint8_t*)rgb1; j.rgb2 = (const uint8_t*)rgb2; j.flow = (const float2*)flow; j.skip = (const uint8_t*)skip;
     j.tab = (const AugSampleDev*)st->aug;

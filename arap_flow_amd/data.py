@@ -168,7 +168,22 @@ class AugmentLoader:
     pair's augmentation is draw_sample(cfg, seed, e, its index in the list).  epoch(e) iterates over one epoch; iter()
     over the next one (0, 1, ..).  A batch is a dict(img1, img2, flow, valid) of what `augment` returns: CUDA tensors of
     the current device, ready on torch's current stream.  While the caller works on a batch the files of the next one
-    are decoded.  The last batch of an epoch is shorter when the list's length is no multiple of `batch`."""
+    are decoded.  The last batch of an epoch is shorter when the list's length is no multiple of `batch`.
+
+    Who owns the staging buffers.  There are three sets.  Two belong to the epoch in progress, which fills one while the
+    other is uploaded; the third belongs to batch_at.  epoch(e) (and iter()) takes the two over at the call: the loader
+    has one epoch in progress, the one asked for last.  An older iterator raises RuntimeError at its next step and
+    never yields a batch of anybody else's pixels; one that was simply abandoned costs nothing.  batch_at may be
+    called at any time, also between two next() of an epoch, and does not disturb it.  Nobody decodes into a set before
+    the jobs last started on it have ended and its last upload has been read, whoever started them.  One thread calls
+    the loader.
+
+    Streams.  Every batch is made on the stream that is torch's current one when it is asked for (next() or batch_at),
+    and the loader moves the state there.  The state has a single device table of samples, which a call overwrites, so
+    a batch asked for under another stream than the batch before it makes its stream wait for that batch's call first;
+    batches of one stream are ordered by the stream.  The loader orders only its own calls: whoever else calls
+    augment_pairs on the loader's state from another stream has to order those calls against the loader's."""
+    ALONE = 2                                   # batch_at's buffer set
 
     def __init__(self, pairs, state, batch, size, cfg=AUG_DEFAULT, seed=0, jobs=8, augment=opt.augment_pairs, scale=(1, 1, 1),
                  bias=(0, 0, 0), tau=1.0, shuffle=True):
@@ -180,9 +195,11 @@ class AugmentLoader:
         self.pool = concurrent.futures.ThreadPoolExecutor(self.jobs)
         self.next_epoch = 0
         self.source = None                      # (W, H), known from the first pair decoded
-        self.sets = [None, None]                # two sets of host buffers: one is filled while the other is uploaded
-        self.uploaded = [None, None]            # the event behind a set's last upload
-        self.filling = [(), ()]                 # the decoding jobs last started on a set (an abandoned epoch may leave some)
+        self.generation = 0                     # of the epoch that owns the sets 0 and 1
+        self.sets = [None, None, None]          # host buffers: 0 and 1 of the epoch in progress, ALONE of batch_at
+        self.uploaded = [None, None, None]      # the event behind a set's last upload
+        self.filling = [(), (), ()]             # the decoding jobs last started on a set (an abandoned epoch may leave some)
+        self.called = None                      # (stream, event) of the last call made on the state
 
     def __len__(self):
         return (len(self.pairs) + self.batch - 1) // self.batch
@@ -217,47 +234,61 @@ class AugmentLoader:
         bufs["flow"][slot].numpy()[...] = flow
         bufs["skip"][slot].numpy()[...] = 0 if skip is None else skip
 
-    def _start(self, order, k):
-        """the decoding of batch k into the buffer set k % 2 -> (indices, futures)"""
+    def _start(self, order, k, which):
+        """the decoding of batch k into the buffer set `which` -> (indices, futures)"""
         idx = [int(i) for i in order[k * self.batch:(k + 1) * self.batch]]
         if self.source is None:
             first = self.pairs.load(idx[0])[0]
             self.source = (first.shape[1], first.shape[0])
-        if self.uploaded[k % 2] is not None:
-            self.uploaded[k % 2].synchronize()              # the set's last upload has read it
-            self.uploaded[k % 2] = None
-        concurrent.futures.wait(self.filling[k % 2])
-        bufs = self._buffers(k % 2)
-        self.filling[k % 2] = [self.pool.submit(self._decode_into, bufs, slot, i) for slot, i in enumerate(idx)]
-        return idx, self.filling[k % 2]
+        if self.uploaded[which] is not None:
+            self.uploaded[which].synchronize()              # the set's last upload has read it
+            self.uploaded[which] = None
+        concurrent.futures.wait(self.filling[which])         # (and nobody's job still writes it)
+        bufs = self._buffers(which)
+        self.filling[which] = [self.pool.submit(self._decode_into, bufs, slot, i) for slot, i in enumerate(idx)]
+        return idx, self.filling[which]
 
-    def _make(self, epoch, k, idx, futures):
+    def _make(self, epoch, idx, futures, which):
         for f in futures:
             f.result()
-        B, bufs = len(idx), self.sets[k % 2]
+        B, bufs = len(idx), self.sets[which]
         ins = {name: t[:B] for name, t in bufs.items()}
         if self.state is not None:
+            stream = torch.cuda.current_stream()
             ins = {name: t.cuda(non_blocking=True) for name, t in ins.items()}
-            self.uploaded[k % 2] = torch.cuda.Event()
-            self.uploaded[k % 2].record()
-            self.state.set_stream(torch.cuda.current_stream())
+            self.uploaded[which] = torch.cuda.Event()
+            self.uploaded[which].record()
+            if self.called is not None and self.called[0] != stream:
+                stream.wait_event(self.called[1])           # the state has one sample table, which the last call's kernel reads
+            self.state.set_stream(stream)
         W, H = self.source
         samples = [draw_sample(self.cfg, self.seed, epoch, i, W, H, *self.size) for i in idx]
-        return self.augment(self.state, ins["rgb1"], ins["rgb2"], ins["flow"], samples, self.size, skip=ins["skip"],
-                            scale=self.scale, bias=self.bias, tau=self.tau)
+        out = self.augment(self.state, ins["rgb1"], ins["rgb2"], ins["flow"], samples, self.size, skip=ins["skip"],
+                           scale=self.scale, bias=self.bias, tau=self.tau)
+        if self.state is not None:
+            self.called = (stream, torch.cuda.Event())
+            self.called[1].record()
+        return out
 
     def epoch(self, epoch):
+        """an iterator over the batches of one epoch, which becomes the loader's epoch in progress at this call"""
+        self.generation += 1
+        return self._epoch(epoch, self.generation)
+
+    def _epoch(self, epoch, generation):
         order, n = self.order(epoch), len(self)
-        pending = self._start(order, 0)
+        pending = None
         for k in range(n):
-            idx, futures = pending
+            if generation != self.generation:               # checked after every yield, before a shared set is touched
+                raise RuntimeError("AugmentLoader: epoch %d was replaced by a later epoch() of this loader" % epoch)
+            idx, futures = pending or self._start(order, k, k % 2)
             concurrent.futures.wait(futures)
-            pending = self._start(order, k + 1) if k + 1 < n else None
-            yield self._make(epoch, k, idx, futures)
+            pending = self._start(order, k + 1, (k + 1) % 2) if k + 1 < n else None
+            yield self._make(epoch, idx, futures, k % 2)
 
     def batch_at(self, epoch, k):
-        """batch k of an epoch on its own (nothing is decoded ahead)"""
+        """batch k of an epoch on its own (nothing is decoded ahead), in a buffer set that no epoch uses"""
         if not 0 <= k < len(self):
             raise IndexError(k)
-        idx, futures = self._start(self.order(epoch), k)
-        return self._make(epoch, k, idx, futures)
+        idx, futures = self._start(self.order(epoch), k, self.ALONE)
+        return self._make(epoch, idx, futures, self.ALONE)

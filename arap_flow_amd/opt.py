@@ -867,7 +867,9 @@ def augment_pairs(state, rgb1, rgb2, flow, samples, size, skip=None, scale=(1, 1
     tau: the most a pixel's flow taps may differ for its flow to count.  -> {name: CUDA tensor} of the outputs `want`
     names: img1, img2 f32[B,3,h,w], flow f32[B,2,h,w], valid u8[B,h,w] (0 / 255).  Nothing is downloaded and nothing
     waited for: the call is enqueued on the state's stream (State.set_stream; by default the null stream, torch's
-    default), where the inputs must be ready and the outputs are.  `out`: {name: tensor} of caller-owned CUDA tensors
+    default), where the inputs must be ready and the outputs are.  A state has one device table of samples, written in
+    the stream's order: calls on one stream follow each other; before a call on another stream than the last one's,
+    make that stream wait for the last call (data.AugmentLoader does).  `out`: {name: tensor} of caller-owned CUDA tensors
     (contiguous, of the output's shape and type) to write instead of new ones."""
     want = tuple(want)
     if not want or set(want) - set(AUG_OUTPUTS) or len(set(want)) != len(want):

@@ -1,13 +1,15 @@
 """CPU-only: training batches (DESIGN.md "Training batches") around the kernel.  The numpy twin tests/aug_ref.py against
 plain numpy slicing on the five exact cases of the definition, and its properties (used and unused bad taps, the
 motion-boundary guard, the eraser rectangles); ArapFlow_AugmentTables (host only) through ctypes: the neutral table, the
-inverse, the tone table against numpy's statement, every refusal; the new names."""
+inverse, the tone table against numpy's statement, every refusal; the new names.  The twin's flow under a general map against
+a closed form that does not share its formula (tests/aug_cases.py)."""
 import ctypes as C
 import os.path as osp
 
 import numpy as np
 import pytest
 
+import aug_cases
 import aug_ref
 
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
@@ -149,6 +151,24 @@ def test_rectangles_overwrite_the_second_image_only_and_are_clipped():
     assert np.array_equal(r["img2"][0], want)
     for k in ("img1", "flow", "valid"):
         assert np.array_equal(r[k], plain[k])
+
+
+# ---- the flow under a general map, against a closed form ----------------------------------------------------------------
+def test_flow_of_an_affine_field_is_the_closed_form():
+    """u(q) = G q + g on a dyadic lattice, no skip, tau = inf, under transforms()[5] and 20 draws of AUG_DEFAULT: the
+    twin's flow equals inv(T2)(T1 x + u(T1 x)) - x, evaluated in float64, within the bound aug_cases.affine_bound derives
+    operation by operation, and four misreadings of the definition miss it by more than ten bounds (affine_check).
+    Largest error / bound over the 21 cases: 0.570."""
+    W, H, w, h = aug_cases.AFFINE_SIZES
+    flow = aug_cases.affine_flow(W, H)[None]
+    zeros = np.zeros((1, H, W, 3), np.uint8)
+    cases = aug_cases.affine_cases()
+    assert len(cases) == 21
+    worst = 0.0
+    for name, T1, T2 in cases:
+        r = aug_ref.augment(zeros, zeros, flow, [sample(T1, T2)], (w, h), tau=float("inf"), want=("flow", "valid"))
+        worst = max(worst, aug_cases.affine_check(name, r["flow"][0], r["valid"][0] != 0, T1, T2, W, H))
+    print("affine flow, twin: largest error / bound %.3f" % worst)
 
 
 # ---- ArapFlow_AugmentTables: the library against the Python statement ---------------------------------------------------

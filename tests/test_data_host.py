@@ -1,7 +1,8 @@
 """CPU-only: from a generated tree to training batches (arap_flow_amd/data.py, DESIGN.md "Training batches").  PairList on
 a tree written here: the four lists, missing planes, the OR into one skip plane, a moved tree; draw_sample: a pure function
 within its configuration's ranges whose frame-2 map always inverts; AugmentLoader on the numpy twin: the same bytes for the
-same (seed, epoch, k), other bytes for another epoch, the ragged last batch."""
+same (seed, epoch, k), other bytes for another epoch, the ragged last batch; who owns the loader's buffer sets: batch_at between the
+steps of an epoch, two epochs at once, an abandoned epoch, a pair of another size, one and sixteen decoding threads."""
 import math
 
 import numpy as np
@@ -180,3 +181,102 @@ def test_loader_feeds_the_pairs_it_names(tmp_path):
     ld.close()
     with pytest.raises(ValueError):
         loader(str(tmp_path), batch=65)
+
+
+# ---- who owns the buffer sets -------------------------------------------------------------------------------------------
+# nine pairs, two a batch: five batches, the last one ragged, every shared set used more than once
+@pytest.fixture(scope="module")
+def nine(tmp_path_factory):
+    """(root, the bytes of the epochs 0 and 1 from a loader that nothing disturbs)"""
+    root = str(tmp_path_factory.mktemp("nine"))
+    aug_ref.write_tree(root, 9, W, H)
+    ld = loader(root, batch=2)
+    ref = [[as_bytes(x) for x in ld.epoch(e)] for e in range(2)]
+    ld.close()
+    assert [len(r) for r in ref] == [5, 5] and all(len(set(x[k] for r in ref for x in r)) == 10 for k in ("img1", "img2", "flow"))
+    return root, ref
+
+
+def test_batch_at_between_the_steps_of_an_epoch(nine):
+    """after every next() of epoch 0, an even and an odd batch of either epoch on their own: every batch of the epoch and
+    every batch_at equals the undisturbed loader's"""
+    root, ref = nine
+    ld = loader(root, batch=2)
+    it = ld.epoch(0)
+    for k in range(5):
+        assert as_bytes(next(it)) == ref[0][k], k
+        for e, j in ((0, (k + 2) % 5 // 2 * 2), (0, 3), (1, 4), (1, 1)):
+            assert as_bytes(ld.batch_at(e, j)) == ref[e][j], (k, e, j)
+    with pytest.raises(StopIteration):
+        next(it)
+    ld.close()
+
+
+def test_two_epochs_at_once_the_older_one_raises(nine):
+    """epoch() takes the shared sets over: the iterator asked for last yields the undisturbed batches, the older one raises
+    at its next step, whether it had begun or not, and never yields another batch"""
+    root, ref = nine
+    ld = loader(root, batch=2)
+    i0, i1 = ld.epoch(0), ld.epoch(1)
+    for k in range(5):
+        assert as_bytes(next(i1)) == ref[1][k], k
+        if k < 2:
+            with pytest.raises(RuntimeError if k == 0 else StopIteration):     # (a generator that raised has ended)
+                next(i0)
+    begun = ld.epoch(0)
+    assert as_bytes(next(begun)) == ref[0][0] and as_bytes(next(begun)) == ref[0][1]
+    later = iter(ld)                                                           # epoch 0, by iter()'s count
+    assert as_bytes(next(later)) == ref[0][0]
+    with pytest.raises(RuntimeError):
+        next(begun)
+    assert [as_bytes(x) for x in later] == ref[0][1:]
+    ld.close()
+
+
+def test_an_abandoned_epoch_costs_nothing(nine):
+    root, ref = nine
+    ld = loader(root, batch=2)
+    it = ld.epoch(1)
+    assert as_bytes(next(it)) == ref[1][0] and as_bytes(next(it)) == ref[1][1]      # batch 2 is being decoded into set 0
+    del it
+    assert [as_bytes(x) for x in ld.epoch(0)] == ref[0]
+    assert as_bytes(ld.batch_at(1, 3)) == ref[1][3] and as_bytes(ld.batch_at(0, 4)) == ref[0][4]
+    ld.close()
+
+
+def test_a_pair_of_another_size_is_an_error_that_leaves_the_loader_usable(tmp_path):
+    from PIL import Image
+    from arap_flow_amd import flo
+    root = str(tmp_path)
+    aug_ref.write_tree(root, 9, W, H)
+    ld = loader(root, batch=2, shuffle=False)
+    ref = [as_bytes(x) for x in ld.epoch(0)]
+    ld.close()
+    pl = data.PairList(root, planes=("fold",))
+    rng = np.random.default_rng(5)
+    for f in (pl[5].rgb1, pl[5].rgb2):                                         # pair 5 (batch 2) becomes 71 x 9
+        Image.fromarray(rng.integers(0, 256, (H, W + 1, 3)).astype(np.uint8)).save(f)
+    flo.flow_write(pl[5].flow, np.zeros((H, W + 1, 2), F))
+    ld = loader(root, batch=2, shuffle=False)
+    it = ld.epoch(0)
+    assert as_bytes(next(it)) == ref[0] and as_bytes(next(it)) == ref[1]
+    with pytest.raises(ValueError):
+        next(it)
+    with pytest.raises(StopIteration):
+        next(it)
+    assert as_bytes(ld.batch_at(0, 3)) == ref[3]
+    with pytest.raises(ValueError):
+        ld.batch_at(0, 2)
+    assert as_bytes(ld.batch_at(0, 4)) == ref[4] and as_bytes(ld.batch_at(0, 1)) == ref[1]
+    it = ld.epoch(0)
+    assert as_bytes(next(it)) == ref[0]
+    ld.close()                                                                 # with batch 1 decoded ahead: returns
+
+
+def test_one_and_sixteen_decoding_threads_give_the_same_bytes(nine):
+    root, ref = nine
+    for jobs in (1, 16):
+        ld = loader(root, batch=2, jobs=jobs)
+        assert ld.jobs == jobs and [[as_bytes(x) for x in ld.epoch(e)] for e in range(2)] == ref
+        assert as_bytes(ld.batch_at(1, 2)) == ref[1][2]
+        ld.close()

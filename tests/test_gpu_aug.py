@@ -1,16 +1,20 @@
 """GPU: opt.augment_pairs (ArapFlow_AugmentPairs, DESIGN.md "Training batches") against the numpy twin tests/aug_ref.py,
 equal as numbers (-0 may be +0) and free of NaN, at the shapes the kernel branches on: a block is a 64 x 16 tile and a
 lane four pixels of a row, stored with 16-byte stores when the crop's width is a multiple of four and the bases are
-aligned."""
+aligned; B up to 64 and a table that grows under calls in flight; both tap instantiations; inputs off their natural
+alignment; side streams: the call returns while its stream is busy, and two calls in flight on two streams share no
+table; the flow of an affine field against its closed form (tests/aug_cases.py)."""
 import ctypes as C
 import itertools
-import math
+import time
 
 import numpy as np
 import pytest
 import torch
 
+import aug_cases
 import aug_ref
+from aug_cases import transforms
 from arap_flow_amd import capi, opt
 
 pytestmark = pytest.mark.gpu
@@ -43,30 +47,6 @@ def make_pair(W, H, B, seed):
     return rgb1, rgb2, flow, skip
 
 
-def rot(angle, scale, cx, cy, ox, oy):
-    """output pixel -> source point: a rotation by `angle` and a scale about the output point (ox, oy), which shows the
-    source point (cx, cy); composed in double"""
-    a, b = scale * math.cos(angle), -scale * math.sin(angle)
-    return (a, b, cx - (a * ox + b * oy), -b, a, cy - (-b * ox + a * oy))
-
-
-def transforms(W, H, w, h):
-    """the identity, the exact cases of the definition, a rotation with scale and a relative motion of frame 2, and a map
-    that leaves the source; with tone curves, rectangles and fills of their own"""
-    r1 = rot(0.2, 1.3, (W - 1) / 2, (H - 1) / 2, (w - 1) / 2, (h - 1) / 2)
-    r2 = rot(0.23, 1.25, (W - 1) / 2 + 0.7, (H - 1) / 2 - 0.4, (w - 1) / 2, (h - 1) / 2)
-    out = rot(-0.4, 2.5, -3.0, H + 2.0, 0, 0)
-    S = opt.AugSample
-    return [S(ID, ID, (1, 1, 1), 1.0, (1, 1, 1), 1.0, (), (0, 0, 0)),
-            S((1, 0, 3, 0, 1, 1), (1, 0, 3, 0, 1, 1), (1.1, 0.9, 1.0), 0.8, (0.9, 1.0, 1.2), 1.1, ((1, 0, 3, 2),), (0.5, -1, 2)),
-            S((-1, 0, W - 1, 0, 1, 0), (-1, 0, W - 1, 0, 1, 0), (1, 1, 1), 2.2, (1, 1, 1), 0.45, (), (0, 0, 0)),
-            S((2, 0, 0, 0, 2, 0), (2, 0, 0, 0, 2, 0), (1.5, 1.5, 0.5), 1.0, (1, 1, 1), 1.0, ((-4, -4, 2, 1), (w - 1, h - 1, w + 5, h + 5)), (1, 2, 3)),
-            S(ID, (1, 0, 2, 0, 1, 1), (1, 1, 1), 1.0, (0.8, 0.8, 0.8), 1.3, (), (0, 0, 0)),
-            S(r1, r2, (1.2, 1.0, 0.8), 0.9, (1.0, 1.1, 0.9), 1.2,
-              ((2, 1, 9, 4), (w // 2, 0, w // 2 + 7, h), (-3, h - 2, 4, h + 3), (w + 1, h + 1, w + 9, h + 9)), (0.25, 0.5, 0.75)),
-            S(out, r2, (1, 1, 1), 1.0, (1, 1, 1), 1.0, (), (0, 0, 0))]
-
-
 def same(got, want):
     assert set(got) == set(want)
     for k in want:
@@ -95,6 +75,215 @@ def test_augment_equals_twin(gpu_state, pairs, source, B):
             kw = dict(scale=SCALE, bias=BIAS, tau=1.0)
             want = aug_ref.augment(rgb1, rgb2, flow, samples, (w, h), skip=skip, tables=lib_tables, **kw)
             same(opt.augment_pairs(gpu_state, dev[0], dev[1], dev[2], samples, (w, h), skip=dev[3], **kw), want)
+
+
+@pytest.mark.parametrize("inputs", ["numpy", "device"])
+def test_augment_equals_twin_on_a_side_stream(gpu_state, pairs, inputs):
+    """70x9, B = 3, every crop under every transform, with the state on a side stream that is torch's current stream"""
+    W, H, B = 70, 9, 3
+    host = pairs[W, H, B]
+    side = torch.cuda.Stream()
+    try:
+        gpu_state.set_stream(side)
+        with torch.cuda.stream(side):
+            ins = [torch.from_numpy(a).cuda() for a in host] if inputs == "device" else host
+            for w, h in CROPS:
+                ts = transforms(W, H, w, h)
+                for first in range(0, len(ts), B):
+                    samples = [ts[(first + i) % len(ts)] for i in range(B)]
+                    kw = dict(scale=SCALE, bias=BIAS, tau=1.0)
+                    want = aug_ref.augment(*host[:3], samples, (w, h), skip=host[3], tables=lib_tables, **kw)
+                    got = opt.augment_pairs(gpu_state, ins[0], ins[1], ins[2], samples, (w, h), skip=ins[3], **kw)
+                    side.synchronize()
+                    same(got, want)
+    finally:
+        gpu_state.set_stream(None)
+
+
+# ---- batch sizes up to the limit, and a table that grows while calls are in flight ----------------------------------------
+def cycled(W, H, w, h, B, first=0):
+    ts = transforms(W, H, w, h)
+    return [ts[(first + i) % len(ts)] for i in range(B)]
+
+
+@pytest.fixture(scope="module")
+def big():
+    """{B: (inputs, samples, the twin's outputs)} for 70x9 -> 65x9, the seven transforms cycled over the samples"""
+    W, H, w, h = 70, 9, 65, 9
+    out = {}
+    for B in (1, 3, 33, 64):
+        ins = make_pair(W, H, B, seed=100 + B)
+        samples = cycled(W, H, w, h, B, first=B)
+        out[B] = (ins, samples, aug_ref.augment(*ins[:3], samples, (w, h), skip=ins[3], tables=lib_tables, scale=SCALE, bias=BIAS))
+    return out
+
+
+@pytest.mark.parametrize("B", [33, 64])
+def test_large_batches(gpu_state, big, B):
+    ins, samples, want = big[B]
+    same(opt.augment_pairs(gpu_state, *ins[:3], samples, (65, 9), skip=ins[3], scale=SCALE, bias=BIAS), want)
+
+
+def test_table_grows_under_calls_in_flight(big):
+    """a fresh state: B = 1, then 64, then 3, with nothing waited for in between"""
+    st = opt.State()
+    try:
+        dev = {B: [torch.from_numpy(a).cuda() for a in big[B][0]] for B in (1, 64, 3)}
+        torch.cuda.synchronize()
+        got = {B: opt.augment_pairs(st, *dev[B][:3], big[B][1], (65, 9), skip=dev[B][3], scale=SCALE, bias=BIAS) for B in (1, 64, 3)}
+        torch.cuda.synchronize()
+        for B in (1, 64, 3):
+            same(got[B], big[B][2])
+    finally:
+        st.close()
+
+
+# ---- both instantiations of the taps ------------------------------------------------------------------------------------
+def test_byte_taps_equal_dword_taps(gpu_state, pairs, monkeypatch):
+    """ARAPOPT_AUG_BYTES=1 selects k_augment<false> at any size (a state reads it when it is made)"""
+    monkeypatch.setenv("ARAPOPT_AUG_BYTES", "1")
+    st = opt.State()
+    try:
+        for W, H in SOURCES:
+            rgb1, rgb2, flow, skip = pairs[W, H, 3]
+            samples = transforms(W, H, 65, 17)[4:7]
+            kw = dict(skip=skip, scale=SCALE, bias=BIAS)
+            want = aug_ref.augment(rgb1, rgb2, flow, samples, (65, 17), tables=lib_tables, **kw)
+            a = opt.augment_pairs(st, rgb1, rgb2, flow, samples, (65, 17), **kw)
+            b = opt.augment_pairs(gpu_state, rgb1, rgb2, flow, samples, (65, 17), **kw)
+            same(a, want)
+            same(b, want)
+            assert all(a[k].cpu().numpy().tobytes() == b[k].cpu().numpy().tobytes() for k in want), (W, H)
+    finally:
+        st.close()
+
+
+# ---- inputs off their natural alignment ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(70, 9, 65, 9), (2, 2, 4, 1)], ids=lambda s: "%dx%d-%dx%d" % s)
+def test_misaligned_inputs(gpu_state, pairs, shape):
+    """each input one element into a larger allocation: the frames and skip at odd addresses (the dword taps straddle
+    dwords), the flow at 4 mod 8 (its two-float loads are not 8-byte aligned)"""
+    W, H, w, h = shape
+    host = pairs[W, H, 3]
+    dev = []
+    for a in host:
+        t = torch.from_numpy(a)
+        room = torch.zeros(t.numel() + 1, dtype=t.dtype, device="cuda")
+        room[1:] = t.reshape(-1).cuda()
+        dev.append(room[1:].view(t.shape))
+    assert dev[0].data_ptr() % 2 == 1 and dev[1].data_ptr() % 2 == 1 and dev[3].data_ptr() % 2 == 1 and dev[2].data_ptr() % 8 == 4
+    assert all(t.is_contiguous() for t in dev)
+    samples = transforms(W, H, w, h)[4:7]
+    want = aug_ref.augment(*host[:3], samples, (w, h), skip=host[3], tables=lib_tables, scale=SCALE, bias=BIAS)
+    same(opt.augment_pairs(gpu_state, *dev[:3], samples, (w, h), skip=dev[3], scale=SCALE, bias=BIAS), want)
+    samples = transforms(W, H, w, h)[:3]
+    want = aug_ref.augment(*host[:3], samples, (w, h), skip=host[3], tables=lib_tables)
+    same(opt.augment_pairs(gpu_state, *dev[:3], samples, (w, h), skip=dev[3]), want)
+
+
+# ---- streams ------------------------------------------------------------------------------------------------------------
+def host_time_of_a_call(call, sync):
+    """seconds, the median of five calls that each begin on an idle stream"""
+    ts = []
+    for _ in range(5):
+        sync()
+        t0 = time.perf_counter()
+        call()
+        ts.append(time.perf_counter() - t0)
+    sync()
+    return sorted(ts)[2]
+
+
+@pytest.mark.parametrize("B", [3, 64])
+def test_call_returns_while_the_stream_is_busy(gpu_state, big, B):
+    """device work of D = min(0.4 s, 300 host times of the call) is queued on the state's stream, then the call is made:
+    when it has returned that work has not finished, i.e. the call waited for nothing on its stream -- not for its
+    table either, 19 KB of pageable host memory at B = 3 and 394 KB at B = 64, which the runtime stages itself"""
+    size = (65, 9)
+    host, samples, want = big[B]
+    side = torch.cuda.Stream()
+    try:
+        gpu_state.set_stream(side)
+        with torch.cuda.stream(side):
+            dev = [torch.from_numpy(a).cuda() for a in host]
+            call = lambda: opt.augment_pairs(gpu_state, *dev[:3], samples, size, skip=dev[3], scale=SCALE, bias=BIAS)
+            call()                                                         # (first use: the table is allocated)
+            t_call = host_time_of_a_call(call, side.synchronize)
+            work = aug_cases.BusyWork(side)
+            begin, busy = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            begin.record()
+            work.queue(min(0.4, 300 * t_call))
+            busy.record()
+            t0 = time.perf_counter()
+            got = call()
+            t_busy_call = time.perf_counter() - t0
+            returned_first = not busy.query()
+            side.synchronize()
+            D = begin.elapsed_time(busy) / 1e3
+        print("augment_pairs, B = %d, on a busy stream: D %.1f ms, host time of the call idle %.0f us, busy %.0f us, returned first: %s"
+              % (B, D * 1e3, t_call * 1e6, t_busy_call * 1e6, returned_first))
+        assert D <= 0.5
+        assert returned_first
+        same(got, want)
+    finally:
+        gpu_state.set_stream(None)
+
+
+def test_two_streams_do_not_share_a_table(gpu_state, pairs):
+    """call 1 on stream a behind 0.1 s of work, call 2 with other samples on stream b at once: each equals its twin.  The
+    state has one table, and the library does not order two streams: here call 2's table and kernel run at once, call 1's
+    table is written behind the work on a and read by the kernel that follows it there.  What could go wrong is a copy
+    that lands between another stream's copy and its kernel, a window of microseconds that no test can hold open; a
+    caller who moves a state between streams closes it (data.AugmentLoader does, tests/test_gpu_data.py)."""
+    W, H, B, size = 70, 9, 3, (65, 9)
+    host = pairs[W, H, B]
+    ts = transforms(W, H, *size)
+    S1, S2 = ts[4:7], ts[1:4]
+    kw = dict(scale=SCALE, bias=BIAS)
+    want1 = aug_ref.augment(*host[:3], S1, size, skip=host[3], tables=lib_tables, **kw)
+    want2 = aug_ref.augment(*host[:3], S2, size, skip=host[3], tables=lib_tables, **kw)
+    assert all(not np.array_equal(want1[k], want2[k]) for k in want1)
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    try:
+        dev = [torch.from_numpy(x).cuda() for x in host]
+        opt.augment_pairs(gpu_state, *dev[:3], S2, size, skip=dev[3], **kw)      # (first use: the tables are allocated)
+        torch.cuda.synchronize()
+        work = aug_cases.BusyWork(a)
+        busy = torch.cuda.Event()
+        with torch.cuda.stream(a):
+            work.queue(0.1)
+            busy.record()
+            gpu_state.set_stream(a)
+            got1 = opt.augment_pairs(gpu_state, *dev[:3], S1, size, skip=dev[3], **kw)
+        with torch.cuda.stream(b):
+            gpu_state.set_stream(b)
+            got2 = opt.augment_pairs(gpu_state, *dev[:3], S2, size, skip=dev[3], **kw)
+        in_flight = not busy.query()
+        a.synchronize()
+        b.synchronize()
+        assert in_flight                                                       # call 1 had not run when call 2 was made
+        same(got2, want2)
+        same(got1, want1)
+    finally:
+        gpu_state.set_stream(None)
+
+
+# ---- the flow under a general map, against a closed form ----------------------------------------------------------------
+def test_flow_of_an_affine_field_is_the_closed_form(gpu_state):
+    """as tests/test_aug_host.py states it for the twin, here for the kernel: 21 cases in batches of seven, within the bound
+    aug_cases.affine_bound derives.  Largest error / bound on the MI355X: see DESIGN.md "Training batches"."""
+    W, H, w, h = aug_cases.AFFINE_SIZES
+    cases = aug_cases.affine_cases()
+    flow = aug_cases.affine_flow(W, H)
+    worst = 0.0
+    for first in range(0, len(cases), 7):
+        part = cases[first:first + 7]
+        samples = [opt.AUG_NEUTRAL._replace(T1=T1, T2=T2) for _, T1, T2 in part]
+        got = opt.augment_pairs(gpu_state, None, None, np.stack([flow] * len(part)), samples, (w, h), tau=float("inf"), want=("flow", "valid"))
+        out, valid = got["flow"].cpu().numpy(), got["valid"].cpu().numpy() != 0
+        for i, (name, T1, T2) in enumerate(part):
+            worst = max(worst, aug_cases.affine_check(name, out[i], valid[i], T1, T2, W, H))
+    print("affine flow, kernel: largest error / bound %.3f" % worst)
 
 
 def crafted():
