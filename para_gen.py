@@ -94,9 +94,9 @@ import subprocess
 import sys
 import threading
 import time
-import dataclasses
 from dataclasses import dataclass
 from multiprocessing import Pool
+from typing import Callable, NamedTuple
 
 import numpy as np
 from PIL import Image
@@ -108,37 +108,87 @@ from arap_flow_amd import pipeline          # noqa: E402
 orgcolor, orgmask = "orgRGB", "orgMasks"                              # para_gen.py:18-26
 color_dir, mask_dir, constraints_dir = "inpRGB", "inpMasks", "tmpCnstr"
 flow_dir, wrgb_dir, wMask_dir = "Flow", "wRGB", "wMasks"
-color_blur_dir, wrgb_blur_dir = "inpRGB_blur", "wRGB_blur"       # --blur: the motion-blurred pair (addition)
-color_light_dir, wrgb_light_dir = "inpRGB_light", "wRGB_light"   # --relight: the relit pair (addition)
-SEG_DIRS = dict(idx1="Index1", idx2="Index2", mb1="MB", mb2="MBBwd", dist1="MBDist", dist2="MBDistBwd")   # --seg (addition)
-color_tex_dir, wrgb_tex_dir = "inpRGB_tex", "wRGB_tex"           # --retex: the random-texture twin (addition)
-bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"       # --bwd_flow, --occ (additions)
-diag_dir, fold_dir = "Diag", "Fold"     # --diag: fold diagnostics (addition)
-mid_full_dir = "MidFull"           # --mid_bg: the in-between frames and links with the moving background (addition)
-mid_dir = "Mid"                    # --mid K: in-between frames from the constraint ramp (addition)
+color_blur_dir, wrgb_blur_dir = "inpRGB_blur", "wRGB_blur"
+color_light_dir, wrgb_light_dir = "inpRGB_light", "wRGB_light"
+SEG_DIRS = dict(idx1="Index1", idx2="Index2", mb1="MB", mb2="MBBwd", dist1="MBDist", dist2="MBDistBwd")
+color_tex_dir, wrgb_tex_dir = "inpRGB_tex", "wRGB_tex"
+bwd_dir, occ_bwd_dir, occ_dir = "FlowBwd", "OccBwd", "Occ"
+diag_dir, fold_dir = "Diag", "Fold"
+mid_dir, mid_full_dir = "Mid", "MidFull"
+tracks_dir = "Tracks"
+full_dir, occ_full_dir, bwd_full_dir, occ_bwd_full_dir = "FlowFull", "OccFull", "FlowBwdFull", "OccBwdFull"
 NUM_ITER = 19                      # the ramp length of the ARAP drivers (main.cpp:215-221): what --mid K spreads over
 LAYERS_OCC = "occl_gen"            # --multseg --occ_layers: the frame's forward occlusion, made by a `layers` line
-tracks_dir = "Tracks"                                            # --tracks: point tracks (addition)
-full_dir, occ_full_dir, bwd_full_dir, occ_bwd_full_dir = "FlowFull", "OccFull", "FlowBwdFull", "OccBwdFull"   # --bg_motion
-FULL_KEYS = ["flowfull_gen", "occfull_gen", "bwdfull_gen", "occbwdfull_gen"]      # --bg_motion: the full-frame maps
-EXT_KEYS = list(pipeline.EXTRA_OF) + [LAYERS_OCC] + FULL_KEYS         # every optional output of a frame
 CPP_BIN = osp.join(HERE, "arap_flow_amd", "bin", "arap_deform")
 
 
-def mid_paths(p):
+NONE_IS_OFF = ("bg_motion", "relight", "blur", "seg")      # given iff not None (a strength of 0 counts); the others iff truthy
+
+
+def asked(when, flags):
+    """a condition of the tables OUTPUTS, FOREIGN and EXCLUSIVE: a tuple of alternatives, each the "+"-joined flags that
+    must all be given"""
+    given = lambda n, v: v is not None if n in NONE_IS_OFF else bool(v)
+    return any(all(given(n, getattr(flags, n, None)) for n in alt.split("+")) for alt in when)
+
+
+class Output(NamedTuple):
+    """one optional output of a pair beyond the base six: its key in the path table, its directory under OUT, its extension
+    ("": the prefix of several files, which requested_outputs spells out) and when it is asked for (`asked`).  `use`, in words:
+    "resume" -- --resume skips a pair only if it exists; "ext" -- all_files_ext.list names it; "makes" -- asking for it is a
+    reason to write that list; "late" -- its line's builder makes its directory once the pair is kept (the front end makes
+    the others before it can drop the pair).  `aux`: (private key, flags -> value) that goes into the path table with it."""
+    key: str
+    dir: str
+    ext: str
+    when: tuple
+    use: str = "resume ext makes"
+    aux: tuple = None
+
+
+# A pair's variants: name -> (flag, directory of frame 1, of frame 2, use).  Their pictures, rgb1<name>_gen and
+# rgb2<name>_gen, come late from the variant's own line and are listed with the pair's OWN flow in all_files_<name>.list.
+VARIANTS = dict(blur=("blur", color_blur_dir, wrgb_blur_dir, "resume late"),
+                light=("relight", color_light_dir, wrgb_light_dir, "resume late"),
+                tex=("retex", color_tex_dir, wrgb_tex_dir, "late"))
+# Every optional output, in the order all_files_ext.list names them.  Two asymmetries are INHERITED, not designed, and
+# kept as they are: --resume looks for the blur, light and seg files but not for the two --retex files; and
+# all_files_ext.list names none of the tex / blur / light / seg files (--tracks names its file there but does not cause
+# the list -- it cannot be given without --mid / --mid_layers, which do).
+OUTPUTS = (
+    Output("bwd_gen", bwd_dir, ".flo", ("bwd_flow",)),
+    Output("occbwd_gen", occ_bwd_dir, ".png", ("bwd_flow",)),
+    Output("occ_gen", occ_dir, ".png", ("occ",)),
+    Output("diag_gen", diag_dir, ".txt", ("diag",)),
+    Output("fold_gen", fold_dir, ".png", ("diag",)),
+    Output(LAYERS_OCC, occ_dir, ".png", ("occ_layers",)),
+    Output("flowfull_gen", full_dir, ".flo", ("bg_motion",)),        # --bg_motion: the full-frame maps of what the run asks for
+    Output("occfull_gen", occ_full_dir, ".png", ("bg_motion+occ", "bg_motion+occ_layers")),
+    Output("bwdfull_gen", bwd_full_dir, ".flo", ("bg_motion+bwd_flow",)),
+    Output("occbwdfull_gen", occ_bwd_full_dir, ".png", ("bg_motion+bwd_flow",)),
+    Output("mid_gen", mid_dir, "", ("mid",), aux=("_mid", lambda flags: tuple(flags.mid_steps))),
+    Output("midl_gen", mid_dir, "", ("mid_layers",), aux=("_midl", lambda flags: tuple(flags.mid_layers_steps))),
+    Output("midbg_gen", mid_full_dir, "", ("mid_bg",), "resume ext makes late",
+           aux=("_midbg", lambda flags: tuple(flags.mid_steps or flags.mid_layers_steps))),
+    Output("trk_gen", tracks_dir, ".trk", ("tracks",), "resume ext late", aux=("_tracks", lambda flags: int(flags.tracks))),
+) + tuple(Output("rgb%d%s_gen" % (n, v), d, ".png", (flag,), use)
+          for v, (flag, *dirs, use) in VARIANTS.items() for n, d in enumerate(dirs, 1)
+          ) + tuple(Output(k + "_seg_gen", d, ".png", ("seg",), "resume late") for k, d in SEG_DIRS.items())
+LATE = {o.key for o in OUTPUTS if "late" in o.use}
+
+
+def mid_paths(p, key="mid_gen", steps="_mid"):
     """--mid: every in-between file of a pair's path table, step by step (flow, frame, mask, step flow); [] without"""
-    if "mid_gen" not in p:
+    if key not in p:
         return []
-    return [pipeline.mid_files(p["mid_gen"], i)[k] for i in p["_mid"] for k in ("flow", "rgb", "mask", "step")]
+    return [pipeline.mid_files(p[key], i)[k] for i in p[steps] for k in ("flow", "rgb", "mask", "step")]
 
 
 def mid_layer_paths(p):
     """--mid_layers: every layered in-between file of a pair's path table: per step mid_files' four, then -- with
     --occ_layers -- the link occlusions of pipeline.mid_layer_files, step 0 first; [] without"""
-    if "midl_gen" not in p:
-        return []
-    out = [pipeline.mid_files(p["midl_gen"], i)[k] for i in p["_midl"] for k in ("flow", "rgb", "mask", "step")]
-    if LAYERS_OCC in p:
+    out = mid_paths(p, "midl_gen", "_midl")
+    if out and LAYERS_OCC in p:
         out += [pipeline.mid_layer_files(p["midl_gen"], i)["occ"] for i in (0,) + tuple(p["_midl"])]
     return out
 
@@ -148,17 +198,20 @@ def mid_bg_paths(p):
     link flows from frame 1's on, then -- with --occ_layers -- the link occlusions); [] without"""
     if "midbg_gen" not in p:
         return []
-    steps = tuple(p["_midbg"])
-    out = [pipeline.mid_bg_files(p["midbg_gen"], i)["rgb"] for i in steps]
-    out += [pipeline.mid_bg_files(p["midbg_gen"], i)["step"] for i in (0,) + steps]
-    if LAYERS_OCC in p:
-        out += [pipeline.mid_bg_files(p["midbg_gen"], i)["occ"] for i in (0,) + steps]
+    steps, files = tuple(p["_midbg"]), lambda i: pipeline.mid_bg_files(p["midbg_gen"], i)
+    out = [files(i)["rgb"] for i in steps] + [files(i)["step"] for i in (0,) + steps]
+    return out + ([files(i)["occ"] for i in (0,) + steps] if LAYERS_OCC in p else [])
+
+
+def requested_outputs(p, use):
+    """every optional output a pair's path table asks for, in OUTPUTS' order, that counts for `use`: "resume" (what
+    --resume looks for beside the flow file) or "ext" (what all_files_ext.list names after the pair's trio)"""
+    prefix_files = dict(mid_gen=mid_paths, midl_gen=mid_layer_paths, midbg_gen=mid_bg_paths)
+    out = []
+    for o in OUTPUTS:
+        if o.key in p and use in o.use.split():
+            out += prefix_files[o.key](p) if o.ext == "" else [p[o.key]]
     return out
-
-
-def track_paths(p):
-    """--tracks: a pair's track file; [] without"""
-    return [p["trk_gen"]] if "trk_gen" in p else []
 
 
 def _pair_id(seq, stem):
@@ -221,52 +274,74 @@ def cleanup(p):
 # ----------------------------------------------------------------------------------------------------------------
 # front end / back end of one frame pair: run in the --jobs pool
 # ----------------------------------------------------------------------------------------------------------------
+class Step(NamedTuple):
+    """one list line of a pair's plan: the line (a pipeline *Line), the key of main's `counts` it bumps when a worker
+    reports it done, and the files that go when its stage is done (kept with --keep_segments)"""
+    line: object
+    count: str
+    remove: tuple = ()
+
+
+FINISH = "finish_frame"            # the one stage of a plan that is no list of Steps: finish_frame, run in the pool
+
+
 @dataclass
 class Frame:
     """one frame pair on its way from prepare_pair through main to finish_frame"""
     line: pipeline.SolveLine       # the pair's list line; its outputs are the frame's outputs
     segs: list                     # --multseg: the per-segment lines that are solved in its place, else None
-    layers: object                 # --occ_layers: the frame's layers line (pipeline.LayersLine), else None
-    bg: object                     # the background fitted to the frame (an array), or None; --bg_motion: the path of
-                                   # the enlarged background picture
-    remove: bool                   # --multseg: delete the segments' files once they are merged
-    left: int = 0                  # main: solves of this frame not yet reported done
-    motion: object = None          # --bg_motion: the pair's bg line (pipeline.BgLine), handed out after finish_frame
-    stage: str = "solves"          # main: what the workers hold of this frame: solves -> layers -> bg -> light
-    tmp: tuple = ()                # --bg_motion: the bg line's own input files, deleted when it is done
-    tex: object = None             # --retex: the pair's tex line (pipeline.TexLine), handed out before finish_frame
-    motion_tex: object = None      # --retex --bg_motion: the twin's bg line, handed out after the pair's
-    tracks: object = None          # --tracks: the pair's trk line (pipeline.TrkLine), handed out once its solves are done
-    pending: int = 0               # main: lines of stage "layers" (the layers line, the trk line) not yet reported done
-    blur: object = None            # --blur: the pair's blur line (pipeline.BlurLine), handed out where a tex line is
-    blur_tmp: tuple = ()           # --blur: the blur line's own input file, deleted when it is done
-    light: object = None           # --relight: the pair's light line (pipeline.LightLine), handed out once both frames are final
-    light_tmp: tuple = ()          # --relight: the light line's own input file, deleted when it is done
-    seg: object = None             # --seg: the pair's seg line (pipeline.SegLine), handed out where a tex line is
+    layers: object                 # --occ_layers / --mid_layers: the frame's layers line (pipeline.LayersLine), else None
+    bg: object                     # the still background fitted to the frame (an array), or None (--bg_motion: the bg line's)
+    remove: bool                   # delete the segments' files once they are merged, and every Step's own files
+    plan: list                     # the stages still to do: FINISH, or a list of Steps that may be in flight together
+    left: int = 0                  # main: Steps of the current stage not yet reported done
+    also_bg: tuple = ()            # further warped frames that finish_frame puts the still background behind (the twin's)
 
     @property
     def solves(self):
         return [self.line] if self.segs is None else self.segs
 
 
-def prepare_pair(args):
-    """para_gen.py:447-556 for one pair: everything up to its list-file line(s).  Returns None when the pair is
-    dropped (no mask, no valid constraint), else its Frame."""
-    flags, p, bgpath = args
-    p = dict(p)
-    seq, stem = p.pop("_seq"), p.pop("_stem")
-    line = pipeline.make_arap_path(p)
-    p.pop("_mid", None)
-    midbg, midbg_out = p.pop("_midbg", None), p.pop("midbg_gen", None)      # --mid_bg: the snapshot steps, the output prefix
-    midl = p.pop("_midl", None)                 # --mid_layers: the snapshot steps of every segment's solve
-    tex1, tex2 = p.pop("rgb1tex_gen", None), p.pop("rgb2tex_gen", None)     # --retex: the twin's two frames
-    trk_out, n_tracks = p.pop("trk_gen", None), p.pop("_tracks", 0)         # --tracks: the track file, the number of points
-    blur1, blur2 = p.pop("rgb1blur_gen", None), p.pop("rgb2blur_gen", None)     # --blur: the blurred pair's two frames
-    light1, light2 = p.pop("rgb1light_gen", None), p.pop("rgb2light_gen", None)     # --relight: the relit pair's two frames
-    seg_out = {k: p.pop(k + "_seg_gen") for k in SEG_DIRS if k + "_seg_gen" in p}   # --seg: the pair's six maps
-    layer_masks = []
-    for k in p:
-        os.makedirs(osp.dirname(p[k]), exist_ok=True)
+def follow_up_steps(plan):
+    """every Step of a plan after its first stage: the lines main owes the workers when it hands out the solves"""
+    return [st for stage in plan[1:] if stage != FINISH for st in stage]
+
+
+class Pair(NamedTuple):
+    """what front_end leaves to the builders of a pair's follow-up lines"""
+    rec: Frame                     # the pair's Frame, its plan not yet written: line, segs, solves and the still background
+    id: int                        # _pair_id
+    p: dict                        # the path table without its private and late entries ...
+    own: dict                      # ... and those entries
+    stack: list                    # the solved layers as the layered lines name them: (mask, flow), the later on top
+    masks: list                    # frame 1's mask(s) as written: one, or one per segment
+    wh: tuple                      # (W, H)
+    big: object                    # --bg_motion: the enlarged background (an array), else None
+    mids: tuple                    # --bg_motion: the in-between frames' maps of pipeline.bg_maps_seq
+    m: tuple                       # --bg_motion: M1 then M2 as a line's m= token takes them, else ()
+
+    def rng(self):              # a FRESH generator: the bg window, the textures, the track points and the light each start one
+        return rn.Random(self.id)
+
+    def tmp(self, suffix):      # a file of the lines' own inputs, beside the pair's constraints
+        return osp.splitext(self.p["cstr_tmp"])[0] + suffix
+
+    def union_mask(self, suffix):
+        """the union of the segments' masks (object where any solved segment is object) as a PNG -> its path"""
+        Image.fromarray(np.minimum.reduce(self.masks)).save(self.tmp(suffix))
+        return self.tmp(suffix)
+
+
+def _make_dirs(paths):
+    for q in paths:
+        os.makedirs(osp.dirname(q), exist_ok=True)
+
+
+def front_end(flags, p, bgpath, seq, stem, own):
+    """para_gen.py:447-540 for one pair, up to "frame 1 and its mask(s) are written": preprocess, match, filter, background,
+    masks.  Returns None when the pair is dropped (no mask, no valid constraint), else its Pair."""
+    line, midl, midbg = pipeline.make_arap_path(dict(p, **own)), own.get("_midl"), own.get("_midbg")
+    _make_dirs(p.values())
     im1, mk1, im2, mk2 = preprocess(p, flags.size)
     if not has_mask(p["msk1_org"], p["msk2_org"]):
         cleanup(p)
@@ -286,14 +361,15 @@ def prepare_pair(args):
                 bgim = None
         except Exception:
             bgim = None
-    big = None
+    H, W = im1.shape[:2]
+    big, mids, m = None, (), ()
     if bgim is not None and getattr(flags, "bg_motion", None) is not None:
         rng = rn.Random(_pair_id(seq, stem))
         big, (left, top) = pipeline.fit_bg_window(bgim, im1, rng=rng)          # the window and frame 1 of a run without
-        H, W = im1.shape[:2]
         # camera and objects move in step: after ramp step i every handle has covered i / NUM_ITER of its displacement
         M1, mids, M2 = pipeline.bg_maps_seq(left, top, (W, H), (big.shape[1], big.shape[0]), rng,
                                             [i / float(NUM_ITER) for i in midbg or ()], flags.fd, flags.bg_motion)
+        m = tuple(float(v) for v in np.concatenate([M1, M2]))
         out1 = pipeline.add_bg(im1, mk1, big[top:top + H, left:left + W, :])
         bgim = None
     elif bgim is not None:
@@ -302,147 +378,175 @@ def prepare_pair(args):
     else:
         out1 = im1
     Image.fromarray(out1).save(p["rgb1_gen"])
-    segs = None
+    segs, masks = None, []
     if not flags.multseg:
         mask = np.zeros_like(mk1, dtype=np.uint8)
         mask[mk1 == 0] = pipeline.ARAP_BG                                      # :514-517
         Image.fromarray(mask).save(p["msk1_gen"])
-        layer_masks.append(mask)
+        masks.append(mask)
     else:
         segs = []
-        for s, mask in pipeline.split_segments(mk1, valids):                   # :518-540
-            p_ = pipeline.replace_ext(p, s, keep_orgs=["rgb1_gen", "cstr_tmp"])
+        for s, mask in pipeline.split_segments(mk1, valids):                   # :518-540 (a kept constraint has a label > 0:
+            p_ = pipeline.replace_ext(p, s, keep_orgs=["rgb1_gen", "cstr_tmp"])        # there is at least one segment)
             Image.fromarray(mask).save(p_["msk1_gen"])
-            layer_masks.append(mask)
+            masks.append(mask)
             segs.append(pipeline.make_arap_path(p_))
             if midl:                            # the segment's snapshots lie beside its flow: <flow without .flo>_sII*
                 segs[-1].extra["mid"] = pipeline.mid_token(midl, segs[-1].flow[:-len(".flo")])
-    layers = None
-    if segs and (LAYERS_OCC in p or midl):  # the frame's layers line: segments in list order (ascending label, later on top)
-        out = dict(occ=p[LAYERS_OCC]) if LAYERS_OCC in p else {}
-        if midl:
-            out["mid"] = pipeline.mid_token(midl, p["midl_gen"])
-        layers = pipeline.LayersLine(line.rgb, [(sg.mask, sg.flow) for sg in segs], out)
-    rec = Frame(line=line, segs=segs, layers=layers, bg=bgim, remove=not getattr(flags, "keep_segments", False))
-    if trk_out is not None and rec.solves:      # the tracks: the points from the pair's own generator, every state file named
-        from arap_flow_amd import trk
-        os.makedirs(osp.dirname(trk_out), exist_ok=True)
-        H, W = im1.shape[:2]
-        pts_path = osp.splitext(p["cstr_tmp"])[0] + "_pts.trk"
-        trk.write(pts_path, W, H, pipeline.sample_track_points(rn.Random(_pair_id(seq, stem)), n_tracks, W, H,
-                                                               np.stack(layer_masks)))
-        steps = midl or pipeline.parse_mid(line.extra["mid"])[0]
-        states = lambda sg: tuple(pipeline.mid_files(pipeline.parse_mid(sg.extra["mid"])[1], i)["flow"] for i in steps) + (sg.flow,)
-        rec.tracks = pipeline.TrkLine(pts_path, [(sg.mask, states(sg)) for sg in rec.solves], trk_out)
-    if tex1 is not None:                        # the twin: one texture per solved layer, from the pair's own generator
-        for q in (tex1, tex2):
-            os.makedirs(osp.dirname(q), exist_ok=True)
-        solved = rec.solves
-        H, W = im1.shape[:2]
-        rng_tex = rn.Random(_pair_id(seq, stem))
-        rec.tex = pipeline.TexLine(line.rgb, [(sg.mask, sg.flow) for sg in solved],
-                                   tuple(pipeline.tex_layers(rng_tex, len(solved), (W, H))), dict(rgb1=tex1, rgb2=tex2))
-    if blur1 is not None and (bgim is not None or big is not None):
-        # the blurred pair: the solved layers over the pair's background.  A still background is the fitted picture, written
-        # beside the pair's constraints and seen through the identity; a moving one is the bg line's picture and maps (below)
-        for q in (blur1, blur2):
-            os.makedirs(osp.dirname(q), exist_ok=True)
-        shutter, samples = flags.blur
-        bg_png, maps = osp.splitext(p["cstr_tmp"])[0] + "_bg.png", tuple(float(v) for v in np.concatenate([M1, M2])) if big is not None else ()
-        if big is None:
-            bg_png = osp.splitext(p["cstr_tmp"])[0] + "_blurbg.png"
-            Image.fromarray(bgim).save(bg_png)
-            rec.blur_tmp = (bg_png,)
-        rec.blur = pipeline.BlurLine(line.rgb, [(sg.mask, sg.flow) for sg in rec.solves], bg_png, shutter, samples, maps,
-                                     dict(rgb1=blur1, rgb2=blur2))
-    if seg_out and rec.solves:                  # the segment maps: the solved layers, the bg line's cameras where there is one
-        for q in seg_out.values():
-            os.makedirs(osp.dirname(q), exist_ok=True)
-        tau, radius = flags.seg
-        rec.seg = pipeline.SegLine([(sg.mask, sg.flow) for sg in rec.solves], tau, radius,
-                                   tuple(float(v) for v in np.concatenate([M1, M2])) if big is not None else (), seg_out)
-    if big is not None:
-        # the bg line's own inputs, beside the pair's constraints: the enlarged picture as a PNG (the worker's codec),
-        # with --multseg the union mask (object where any solved segment is object), and the line itself
-        stem_tmp = osp.splitext(p["cstr_tmp"])[0]
-        rec.bg = stem_tmp + "_bg.png"
-        Image.fromarray(big).save(rec.bg)
-        mask1 = line.mask
-        if segs is not None:
-            mask1 = stem_tmp + "_bgmask.png"
-            masks = [np.array(Image.open(sg.mask)) for sg in segs]
-            Image.fromarray(np.minimum.reduce(masks) if masks else np.full_like(mk1, pipeline.ARAP_BG, np.uint8)).save(mask1)
-        occ_in = p.get("occ_gen", p.get(LAYERS_OCC))
-        inputs = {k: v for k, v in dict(occ=occ_in, bwd=p.get("bwd_gen"), occ_bwd=p.get("occbwd_gen")).items() if v}
-        outs = {k + "_out": p[g] for k, g in dict(occ="occfull_gen", bwd="bwdfull_gen", occ_bwd="occbwdfull_gen").items()
-                if k in inputs and g in p}
-        tokens = {}
-        if midbg:                               # the snapshots' files exist when the line is handed out: after the solve / layers line
-            os.makedirs(osp.dirname(midbg_out), exist_ok=True)
-            tokens = dict(mid=pipeline.mid_token(midbg, p.get("mid_gen", p.get("midl_gen"))),
-                       mm=tuple(float(v) for v in np.concatenate(mids)), mid_out=midbg_out)
-        rec.motion = pipeline.BgLine(rec.bg, line.rgb, mask1, line.out_rgb, line.out_mask, line.flow,
-                                     m=tuple(float(v) for v in np.concatenate([M1, M2])), inputs=inputs,
-                                     out=("", line.out_rgb, p["flowfull_gen"]), outs=outs, **tokens)
-        open(stem_tmp + "_bg.txt", "w").write(pipeline.format_line(rec.motion))
-        if rec.tex is not None:                 # the twin's warped frame over the same moving background; frame 1 has it
-            rec.motion_tex = pipeline.BgLine(rec.bg, tex1, mask1, tex2, line.out_mask, line.flow, m=rec.motion.m, inputs={},
-                                             out=("", tex2, ""), outs={})
-        rec.tmp = tuple(q for q in (rec.bg, mask1 if segs is not None else None, stem_tmp + "_bg.txt") if q)
-    if light1 is not None and rec.solves and (bgim is not None or big is not None):
-        # the relit pair: the two finished frames, frame 1's object mask -- with --multseg the union of the segments', the bg
-        # line's where there is one -- and the merged warped mask as frame 2's cover; the light from the pair's own generator
-        for q in (light1, light2):
-            os.makedirs(osp.dirname(q), exist_ok=True)
-        mask1 = line.mask
-        if segs is not None and rec.motion is not None:
-            mask1 = rec.motion.mask1
-        elif segs is not None:
-            mask1 = osp.splitext(p["cstr_tmp"])[0] + "_lightmask.png"
-            Image.fromarray(np.minimum.reduce(layer_masks)).save(mask1)
-            rec.light_tmp = (mask1,)
-        H, W = im1.shape[:2]
-        rec.light = pipeline.LightLine(line.rgb, mask1, line.out_rgb, line.out_mask,
-                                       pipeline.random_light(rn.Random(_pair_id(seq, stem)), flags.relight, W, H),
-                                       dict(rgb1=light1, rgb2=light2))
-    return rec
+    rec = Frame(line, segs, None, bgim, not getattr(flags, "keep_segments", False), plan=[])
+    return Pair(rec, _pair_id(seq, stem), p, own, [(sg.mask, sg.flow) for sg in rec.solves], masks, (W, H), big, mids, m)
+
+
+# -- the builders of a pair's follow-up lines: (the Pair, the flags) -> the line's Step -- the line, its counter, its own
+#    temporary files -- or None when the run or the pair has no such line
+def layers_step(pr, flags):
+    """--occ_layers / --mid_layers: the frame's layers line, segments in list order (ascending label, later on top)"""
+    midl = pr.own.get("_midl")
+    if not pr.rec.segs or not (LAYERS_OCC in pr.p or midl):
+        return None
+    out = dict(occ=pr.p[LAYERS_OCC]) if LAYERS_OCC in pr.p else {}
+    if midl:
+        out["mid"] = pipeline.mid_token(midl, pr.p["midl_gen"])
+    return Step(pipeline.LayersLine(pr.rec.line.rgb, pr.stack, out), "layers_done")
+
+
+def track_step(pr, flags):
+    """--tracks: the points from the pair's own generator, every state file of every layer named"""
+    if "trk_gen" not in pr.own:
+        return None
+    from arap_flow_amd import trk
+    _make_dirs([pr.own["trk_gen"]])
+    (W, H), pts = pr.wh, pr.tmp("_pts.trk")
+    trk.write(pts, W, H, pipeline.sample_track_points(pr.rng(), pr.own["_tracks"], W, H, np.stack(pr.masks)))
+    steps = pr.own.get("_midl") or pipeline.parse_mid(pr.rec.line.extra["mid"])[0]
+    states = lambda sg: tuple(pipeline.mid_files(pipeline.parse_mid(sg.extra["mid"])[1], i)["flow"] for i in steps) + (sg.flow,)
+    return Step(pipeline.TrkLine(pts, [(sg.mask, states(sg)) for sg in pr.rec.solves], pr.own["trk_gen"]), "tracks_done", (pts,))
+
+
+def _two_frames(pr, name, needs_bg=False):
+    """a variant's two pictures (VARIANTS) as its line's `out`, their directories made; None without the variant, or its bg"""
+    if "rgb1%s_gen" % name not in pr.own or (needs_bg and pr.rec.bg is None and pr.big is None):
+        return None
+    out = dict(rgb1=pr.own["rgb1%s_gen" % name], rgb2=pr.own["rgb2%s_gen" % name])
+    _make_dirs(out.values())
+    return out
+
+
+def tex_step(pr, flags):
+    """--retex: the twin, one texture per solved layer, from the pair's own generator"""
+    out = _two_frames(pr, "tex")
+    tex = out and tuple(pipeline.tex_layers(pr.rng(), len(pr.stack), pr.wh))
+    return out and Step(pipeline.TexLine(pr.rec.line.rgb, pr.stack, tex, out), "tex_done")
+
+
+def blur_step(pr, flags):
+    """--blur: the solved layers over the pair's background.  A still background is the fitted picture, written beside the
+    pair's constraints and seen through the identity; a moving one is the bg line's picture and maps (bg_steps)"""
+    out = _two_frames(pr, "blur", needs_bg=True)
+    if out is None:
+        return None
+    bg_png = pr.tmp("_blurbg.png" if pr.big is None else "_bg.png")
+    if pr.big is None:
+        Image.fromarray(pr.rec.bg).save(bg_png)
+    return Step(pipeline.BlurLine(pr.rec.line.rgb, pr.stack, bg_png, *flags.blur, pr.m, out), "blur_done",
+                (bg_png,) if pr.big is None else ())
+
+
+def seg_step(pr, flags):
+    """--seg: the segment maps over the solved layers, with the bg line's cameras where there is one"""
+    out = {k: pr.own[k + "_seg_gen"] for k in SEG_DIRS if k + "_seg_gen" in pr.own}
+    _make_dirs(out.values())
+    return Step(pipeline.SegLine(pr.stack, *flags.seg, pr.m, out), "seg_done") if out else None
+
+
+def bg_steps(pr, flags, tex):
+    """--bg_motion: the pair's bg line, whose Step removes the line's own inputs, beside the pair's constraints: the enlarged
+    picture as a PNG (the worker's codec), with --multseg the union mask, and the line itself as text; after it, with
+    --retex, the twin's warped frame over the same moving background, a second bg line (frame 1 has it)"""
+    if pr.big is None:
+        return []
+    p, line, bg_png, midbg = pr.p, pr.rec.line, pr.tmp("_bg.png"), pr.own.get("_midbg")
+    Image.fromarray(pr.big).save(bg_png)
+    mask1 = line.mask if pr.rec.segs is None else pr.union_mask("_bgmask.png")
+    occ_in = p.get("occ_gen", p.get(LAYERS_OCC))
+    inputs = {k: v for k, v in dict(occ=occ_in, bwd=p.get("bwd_gen"), occ_bwd=p.get("occbwd_gen")).items() if v}
+    outs = {k + "_out": p[g] for k, g in dict(occ="occfull_gen", bwd="bwdfull_gen", occ_bwd="occbwdfull_gen").items()
+            if k in inputs and g in p}
+    tokens = {}
+    if midbg:                                   # the snapshots' files exist when the line is handed out: after the solve / layers line
+        _make_dirs([pr.own["midbg_gen"]])
+        tokens = dict(mid=pipeline.mid_token(midbg, p.get("mid_gen", p.get("midl_gen"))),
+                      mm=tuple(float(v) for v in np.concatenate(pr.mids)), mid_out=pr.own["midbg_gen"])
+    bg = pipeline.BgLine(bg_png, line.rgb, mask1, line.out_rgb, line.out_mask, line.flow, m=pr.m, inputs=inputs,
+                         out=("", line.out_rgb, p["flowfull_gen"]), outs=outs, **tokens)
+    open(pr.tmp("_bg.txt"), "w").write(pipeline.format_line(bg))
+    steps = [Step(bg, "bg_done", (bg_png,) + ((mask1,) if pr.rec.segs is not None else ()) + (pr.tmp("_bg.txt"),))]
+    if tex:
+        rgb1, rgb2 = tex.line.out["rgb1"], tex.line.out["rgb2"]
+        steps.append(Step(bg._replace(rgb1=rgb1, rgb2=rgb2, inputs={}, out=("", rgb2, ""), outs={}, mid="", mm=(), mid_out=""),
+                          "tex_done"))
+    return steps
+
+
+def light_step(pr, flags, bg):
+    """--relight: the two finished frames, frame 1's object mask -- with --multseg the union of the segments', the bg line's
+    where there is one -- and the merged warped mask as frame 2's cover; the light from the pair's own generator"""
+    out = _two_frames(pr, "light", needs_bg=True)
+    if out is None:
+        return None
+    line = pr.rec.line
+    mine = (pr.union_mask("_lightmask.png"),) if pr.rec.segs is not None and not bg else ()
+    mask1 = line.mask if pr.rec.segs is None else bg[0].line.mask1 if bg else mine[0]
+    light = pipeline.random_light(pr.rng(), flags.relight, *pr.wh)
+    return Step(pipeline.LightLine(line.rgb, mask1, line.out_rgb, line.out_mask, light, out), "light_done", mine)
+
+
+def prepare_pair(args):
+    """para_gen.py:447-556 for one pair: everything up to its list-file line(s).  Returns None when the pair is dropped (no
+    mask, no valid constraint), else its Frame, whose plan says what is handed out when:
+      1. every solve;  2. the layers line and the trk line, together;  3. the tex / blur / seg line -- they read the
+      segments' files, so they come before  4. FINISH, which merges and removes them;  5. the pair's bg line;  6. the twin's
+      bg line, or the light line (without --bg_motion right after FINISH)."""
+    flags, p, bgpath = args
+    p = dict(p)
+    seq, stem = p.pop("_seq"), p.pop("_stem")
+    pr = front_end(flags, p, bgpath, seq, stem, {k: p.pop(k) for k in list(p) if k.startswith("_") or k in LATE})
+    if pr is None:
+        return None
+    some = lambda *steps: [st for st in steps if st is not None]
+    merge, tex = layers_step(pr, flags), tex_step(pr, flags)
+    bg = bg_steps(pr, flags, tex)
+    finals = bg + some(light_step(pr, flags, bg))
+    if len(finals) > 1:         # (only after a bg line) the bg line's own inputs go with the pair's LAST line that reads them
+        finals[0], finals[-1] = bg[0]._replace(remove=()), finals[-1]._replace(remove=bg[0].remove + finals[-1].remove)
+    plan = [[Step(ln, "solves_done") for ln in pr.rec.solves], some(merge, track_step(pr, flags)),
+            some(tex, blur_step(pr, flags), seg_step(pr, flags)), FINISH] + [[st] for st in finals]
+    pr.rec.layers, pr.rec.also_bg = merge and merge.line, (tex.line.out["rgb2"],) if tex else ()
+    pr.rec.plan = [stage for stage in plan if stage]
+    return pr.rec
 
 
 def finish_frame(rec):
-    """para_gen.py:202-212 for one Frame whose solve(s) are done: flatten the segments, composite the background (a
-    --bg_motion pair's comes from its bg line afterwards: rec.bg is then a path, not the fitted array)"""
-    if not isinstance(rec.bg, np.ndarray):
-        rec = dataclasses.replace(rec, bg=None)
-    if rec.layers is not None and "mid" in rec.layers.out:          # --mid_layers: the layers line is done
-        steps, prefix = pipeline.parse_mid(rec.layers.out["mid"])
-        if rec.bg is not None:                              # the in-between frames get the pair's background too
-            for f in (pipeline.mid_files(prefix, i) for i in steps):
-                im, m = np.array(Image.open(f["rgb"]).convert("RGB")), np.array(Image.open(f["mask"]))
-                Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(f["rgb"])
-        if rec.remove:                                      # the segments' snapshot files have been merged
-            for sg in rec.segs:
-                for i in steps:
-                    for q in pipeline.mid_files(sg.flow[:-len(".flo")], i).values():
-                        if osp.exists(q):
-                            os.remove(q)
+    """para_gen.py:202-212 for one Frame whose solve(s) are done: flatten the segments, composite the still background (a
+    --bg_motion pair's comes from its bg line afterwards)"""
+    merged = pipeline.parse_mid(rec.layers.out["mid"]) if rec.layers is not None and "mid" in rec.layers.out else None
+    if merged and rec.remove:                               # --mid_layers: the segments' snapshot files have been merged
+        for q in (q for sg in rec.segs for i in merged[0] for q in pipeline.mid_files(sg.flow[:-len(".flo")], i).values()):
+            if osp.exists(q):
+                os.remove(q)
     if rec.segs is not None:
         if "diag" in rec.line.extra:                        # (before flatten_backward removes the segments' extra files)
             pipeline.flatten_diag(rec.line, rec.segs, remove=rec.remove)
         if {"bwd", "occ_bwd"} & set(rec.line.extra):        # (before flatten removes the segments' warped masks)
             pipeline.flatten_backward(rec.line, rec.segs, remove=rec.remove)
         pipeline.flatten([(rec.line, rec.segs)], remove=rec.remove)
-    if rec.bg is not None:
-        im = np.array(Image.open(rec.line.out_rgb).convert("RGB"))
-        m = np.array(Image.open(rec.line.out_mask))
-        Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(rec.line.out_rgb)
-        if rec.tex is not None:                             # the twin's warped frame: the same background, the same mask
-            im = np.array(Image.open(rec.tex.out["rgb2"]).convert("RGB"))
-            Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(rec.tex.out["rgb2"])
-        if "mid" in rec.line.extra:                         # the in-between frames get the pair's background too
-            steps, prefix = pipeline.parse_mid(rec.line.extra["mid"])
-            for f in (pipeline.mid_files(prefix, i) for i in steps):
-                im, m = np.array(Image.open(f["rgb"]).convert("RGB")), np.array(Image.open(f["mask"]))
-                Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(f["rgb"])
+    if rec.bg is not None:      # behind the warped frame, the twin's (the same mask) and every in-between frame
+        own = pipeline.parse_mid(rec.line.extra["mid"]) if "mid" in rec.line.extra else None       # --mid
+        behind = [(q, rec.line.out_mask) for q in (rec.line.out_rgb,) + rec.also_bg]
+        behind += [(f["rgb"], f["mask"]) for mid in (merged, own) if mid for f in (pipeline.mid_files(mid[1], i) for i in mid[0])]
+        for rgb, mask in behind:
+            im, m = np.array(Image.open(rgb).convert("RGB")), np.array(Image.open(mask))
+            Image.fromarray(pipeline.add_bg(im, m, rec.bg)).save(rgb)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -610,16 +714,12 @@ class GpuWorkers:
 
 
 def scan(flags, input_root, output_root):
-    """para_gen.py:384-432"""
+    """para_gen.py:384-432: the path table of every pair to do -- the base six, the four inputs, the OUTPUTS the flags ask
+    for and the private entries `_seq`, `_stem` and those that go with an output (Output.aux)"""
     rgb_org, msk_org = osp.join(input_root, orgcolor), osp.join(input_root, orgmask)
-    roots = {k: osp.join(output_root, v) for k, v in dict(cst=constraints_dir, flo=flow_dir, rgb=color_dir,
-                                                           msk=mask_dir, wco=wrgb_dir, wmk=wMask_dir, bwd=bwd_dir,
-                                                           tx1=color_tex_dir, tx2=wrgb_tex_dir, trk=tracks_dir,
-                                                           bl1=color_blur_dir, bl2=wrgb_blur_dir,
-                                                           lt1=color_light_dir, lt2=wrgb_light_dir,
-                                                           **{"seg_" + k: v for k, v in SEG_DIRS.items()},
-                                                           obw=occ_bwd_dir, occ=occ_dir, dia=diag_dir, fol=fold_dir, mid=mid_dir, mfu=mid_full_dir, ful=full_dir,
-                                                           ofu=occ_full_dir, bfu=bwd_full_dir, obf=occ_bwd_full_dir).items()}
+    base = dict(rgb1_gen=(color_dir, ".png"), msk1_gen=(mask_dir, ".png"), rgb2_gen=(wrgb_dir, ".png"),
+                msk2_gen=(wMask_dir, ".png"), cstr_tmp=(constraints_dir, ".txt"), flow_gen=(flow_dir, ".flo"))
+    wanted = [o for o in OUTPUTS if asked(o.when, flags)]
     reg = re.compile(r"(\d+)\.(jp.?g|png)$", flags=re.IGNORECASE)
     all_paths = []
     for root, dirs, _ in os.walk(rgb_org):
@@ -635,53 +735,14 @@ def scan(flags, input_root, output_root):
                 f2 = f.replace(num.group(1), n.format(int(num.group(1)) + flags.fd))
                 if not osp.exists(osp.join(rgb_org, seq, f2 + ext)) or not osp.exists(osp.join(msk_org, seq, f2 + ".png")):
                     continue
-                e = dict(rgb1_gen=osp.join(roots["rgb"], seq, f + ".png"), msk1_gen=osp.join(roots["msk"], seq, f + ".png"),
-                         rgb2_gen=osp.join(roots["wco"], seq, f + ".png"), msk2_gen=osp.join(roots["wmk"], seq, f + ".png"),
-                         cstr_tmp=osp.join(roots["cst"], seq, f + ".txt"), flow_gen=osp.join(roots["flo"], seq, f + ".flo"),
-                         rgb1_org=osp.join(rgb_org, seq, f1), msk1_org=osp.join(msk_org, seq, f + ".png"),
+                e = {k: osp.join(output_root, d_, seq, f + x) for k, (d_, x) in base.items()}
+                e.update(rgb1_org=osp.join(rgb_org, seq, f1), msk1_org=osp.join(msk_org, seq, f + ".png"),
                          rgb2_org=osp.join(rgb_org, seq, f2 + ext), msk2_org=osp.join(msk_org, seq, f2 + ".png"))
-                if getattr(flags, "bwd_flow", False):
-                    e.update(bwd_gen=osp.join(roots["bwd"], seq, f + ".flo"), occbwd_gen=osp.join(roots["obw"], seq, f + ".png"))
-                if getattr(flags, "occ", False):
-                    e.update(occ_gen=osp.join(roots["occ"], seq, f + ".png"))
-                if getattr(flags, "diag", False):
-                    e.update(diag_gen=osp.join(roots["dia"], seq, f + ".txt"), fold_gen=osp.join(roots["fol"], seq, f + ".png"))
-                if getattr(flags, "occ_layers", False):
-                    e[LAYERS_OCC] = osp.join(roots["occ"], seq, f + ".png")
-                if getattr(flags, "mid", 0):
-                    e["mid_gen"] = osp.join(roots["mid"], seq, f)
-                if getattr(flags, "retex", False):
-                    e.update(rgb1tex_gen=osp.join(roots["tx1"], seq, f + ".png"), rgb2tex_gen=osp.join(roots["tx2"], seq, f + ".png"))
-                if getattr(flags, "blur", None):
-                    e.update(rgb1blur_gen=osp.join(roots["bl1"], seq, f + ".png"), rgb2blur_gen=osp.join(roots["bl2"], seq, f + ".png"))
-                if getattr(flags, "relight", None) is not None:
-                    e.update(rgb1light_gen=osp.join(roots["lt1"], seq, f + ".png"), rgb2light_gen=osp.join(roots["lt2"], seq, f + ".png"))
-                if getattr(flags, "seg", None):
-                    e.update({k + "_seg_gen": osp.join(roots["seg_" + k], seq, f + ".png") for k in SEG_DIRS})
-                if getattr(flags, "bg_motion", None) is not None:       # the full-frame maps of what the run asks for
-                    e["flowfull_gen"] = osp.join(roots["ful"], seq, f + ".flo")
-                    if "occ_gen" in e or LAYERS_OCC in e:
-                        e["occfull_gen"] = osp.join(roots["ofu"], seq, f + ".png")
-                    if "bwd_gen" in e:
-                        e.update(bwdfull_gen=osp.join(roots["bfu"], seq, f + ".flo"),
-                                 occbwdfull_gen=osp.join(roots["obf"], seq, f + ".png"))
+                e.update({o.key: osp.join(output_root, o.dir, seq, f + o.ext) for o in wanted})
                 e = {k: osp.abspath(v) for k, v in e.items()}
                 e["_seq"], e["_stem"] = seq, f
-                if getattr(flags, "mid_layers", 0):
-                    e["midl_gen"] = osp.abspath(osp.join(roots["mid"], seq, f))
-                if "mid_gen" in e:
-                    e["_mid"] = tuple(flags.mid_steps)
-                if "midl_gen" in e:
-                    e["_midl"] = tuple(flags.mid_layers_steps)
-                if getattr(flags, "tracks", 0):
-                    e["trk_gen"], e["_tracks"] = osp.abspath(osp.join(roots["trk"], seq, f + ".trk")), int(flags.tracks)
-                if getattr(flags, "mid_bg", False):
-                    e["midbg_gen"] = osp.abspath(osp.join(roots["mfu"], seq, f))
-                    e["_midbg"] = tuple(flags.mid_steps or flags.mid_layers_steps)
-                # every requested output
-                done = [e["flow_gen"]] + [e[k] for k in EXT_KEYS if k in e] + mid_paths(e) + mid_layer_paths(e) + mid_bg_paths(e)
-                done += track_paths(e) + [e[k] for k in ("rgb1blur_gen", "rgb2blur_gen", "rgb1light_gen", "rgb2light_gen") if k in e]
-                done += [e[k + "_seg_gen"] for k in SEG_DIRS if k + "_seg_gen" in e]
+                e.update({o.aux[0]: o.aux[1](flags) for o in wanted if o.aux})
+                done = [e["flow_gen"]] + requested_outputs(e, "resume")
                 if not flags.resume or not all(osp.exists(q) for q in done):      # --resume (:431)
                     all_paths.append(e)
     return all_paths
@@ -723,11 +784,11 @@ def write_lists(flags, output_root, all_paths):
     pipeline.pair_rejected goes to neither but to OUT/rejected.list as `rgb1 rgb2 flow folded triangles nonfinite`.
     `all_paths`: scan's path tables.  Returns (the lines of all_files.list, those of rejected.list)."""
     max_fold = getattr(flags, "max_fold", None)
-    out_paths, ext, rejected = [], [], []
+    out_paths, ext, rejected, listed = [], [], [], []
     for p in all_paths:
         ln = pipeline.make_arap_path(p)
         trio = [ln.rgb, ln.out_rgb, ln.flow]
-        full = trio + [p[k] for k in EXT_KEYS if k in p] + mid_paths(p) + mid_layer_paths(p) + mid_bg_paths(p) + track_paths(p)
+        full = trio + requested_outputs(p, "ext")
         if not all(osp.exists(q) for q in trio):
             continue
         if max_fold is not None and osp.exists(p.get("diag_gen", "")):
@@ -736,31 +797,20 @@ def write_lists(flags, output_root, all_paths):
                 rejected.append(" ".join(trio + ["%d" % st[k] for k in ("folded", "triangles", "nonfinite")]))
                 continue
         out_paths.append(" ".join(trio))
+        listed.append(p)
         if all(osp.exists(q) for q in full):
             ext.append(" ".join(full))
     open(osp.join(output_root, "all_files.list"), "w").write("\n".join(out_paths))
     # all_files.list stays as it is; the extra outputs get their own list
-    if (getattr(flags, "bwd_flow", False) or getattr(flags, "occ", False) or getattr(flags, "occ_layers", False) or
-            getattr(flags, "mid", 0) or getattr(flags, "mid_layers", 0) or getattr(flags, "bg_motion", None) is not None or
-            getattr(flags, "diag", False)):
+    if any("makes" in o.use and asked(o.when, flags) for o in OUTPUTS):
         open(osp.join(output_root, "all_files_ext.list"), "w").write("\n".join(ext))
     if max_fold is not None:
         open(osp.join(output_root, "rejected.list"), "w").write("\n".join(rejected))
-    if getattr(flags, "retex", False):                     # the twins of the listed pairs: their own frames, the SAME flow
-        by_trio = {" ".join(pipeline.make_arap_path(p)[k] for k in (0, 4, 3)): p for p in all_paths}
-        twins = [[by_trio[t]["rgb1tex_gen"], by_trio[t]["rgb2tex_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
-        open(osp.join(output_root, "all_files_tex.list"), "w").write(
-            "\n".join(" ".join(t) for t in twins if all(osp.exists(q) for q in t)))
-    if getattr(flags, "blur", None):                       # the blurred variants of the listed pairs: the SAME flow
-        by_trio = {" ".join(pipeline.make_arap_path(p)[k] for k in (0, 4, 3)): p for p in all_paths}
-        blurred = [[by_trio[t]["rgb1blur_gen"], by_trio[t]["rgb2blur_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
-        open(osp.join(output_root, "all_files_blur.list"), "w").write(
-            "\n".join(" ".join(t) for t in blurred if all(osp.exists(q) for q in t)))
-    if getattr(flags, "relight", None) is not None:        # the relit variants of the listed pairs: the SAME flow
-        by_trio = {" ".join(pipeline.make_arap_path(p)[k] for k in (0, 4, 3)): p for p in all_paths}
-        relit = [[by_trio[t]["rgb1light_gen"], by_trio[t]["rgb2light_gen"], by_trio[t]["flow_gen"]] for t in out_paths]
-        open(osp.join(output_root, "all_files_light.list"), "w").write(
-            "\n".join(" ".join(t) for t in relit if all(osp.exists(q) for q in t)))
+    for name, (flag, *_) in VARIANTS.items():              # the variants of the listed pairs: their own frames, the SAME flow
+        if asked((flag,), flags):
+            trios = [[p["rgb1%s_gen" % name], p["rgb2%s_gen" % name], p["flow_gen"]] for p in listed]
+            open(osp.join(output_root, "all_files_%s.list" % name), "w").write(
+                "\n".join(" ".join(t) for t in trios if all(osp.exists(q) for q in t)))
     return out_paths, rejected
 
 
@@ -789,95 +839,44 @@ def main(flags):
         tmp_paths.remove(bgpath)
         picks.append(bgpath)
 
-    serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == CPP_BIN)
+    serve = serves(flags)
     pool = Pool(processes=max(1, flags.jobs))          # (forked before any thread exists)
-    frames = {}                                        # done token of a line a worker holds -> its Frame
-    posts, lock = [], threading.Lock()
+    frames = {}                                        # done token of a line a worker holds -> (its Frame, its Step)
+    posts, lock = [], threading.RLock()
     counts = dict(solves_done=0, frames_done=0, layers_done=0, bg_done=0, tex_done=0, tracks_done=0, blur_done=0,
                   light_done=0, seg_done=0)
 
-    def hand_out(rec, item, put):                      # (under `lock`) the one place a line becomes text
-        frames[pipeline.done_token(item)] = rec
-        put(pipeline.format_line(item))
-
-    def bg_ready(rec):                                 # the pool's result thread: finish_frame of a --bg_motion pair is done
-        with lock:
-            rec.stage = "bg"
-            hand_out(rec, rec.motion, workers.put_owed)
-
-    def light_ready(rec):                              # the pool's result thread: finish_frame of a --relight pair is done
-        with lock:
-            rec.stage = "light"
-            hand_out(rec, rec.light, workers.put_owed)
-
-    def on_done(path):                                 # a worker thread: one solve (or one layers / bg line) finished
-        with lock:
-            rec = frames.pop(path)
-            if rec.stage in ("bg", "light") and rec.light is not None:
-                if rec.stage == "bg":                  # its bg line: both frames are final, now the pair's light line
-                    counts["bg_done"] += 1
-                    rec.stage = "light"
-                    hand_out(rec, rec.light, workers.put_owed)
-                    return
-                counts["light_done"] += 1              # its light line: the frame is complete
-                if rec.remove:
-                    for q in rec.tmp + rec.light_tmp:
-                        if osp.exists(q):
-                            os.remove(q)
-                return
-            if rec.stage == "bg" and rec.motion_tex is not None:    # its bg line: now the twin's, over the same inputs
-                counts["bg_done"] += 1
-                rec.stage = "bg_tex"
-                hand_out(rec, rec.motion_tex, workers.put_owed)
-                return
-            if rec.stage in ("bg", "bg_tex"):          # its (last) bg line: the frame is complete
-                counts["bg_done" if rec.stage == "bg" else "tex_done"] += 1
-                if rec.remove:
-                    for q in rec.tmp:
-                        if osp.exists(q):
-                            os.remove(q)
-                return
-            if rec.stage == "tex":                     # its tex (or blur, or seg) line: the segment files may go now
-                counts["tex_done" if rec.tex is not None else "blur_done" if rec.blur is not None else "seg_done"] += 1
-                if rec.remove:
-                    for q in rec.blur_tmp:
-                        if osp.exists(q):
-                            os.remove(q)
-            elif rec.stage == "layers":                # its layers line or its trk line: both read the segments' snapshots,
-                if rec.tracks is not None and path == rec.tracks.out:          # which go only when both are done
-                    counts["tracks_done"] += 1
-                    if rec.remove and osp.exists(rec.tracks.points):
-                        os.remove(rec.tracks.points)
-                else:
-                    counts["layers_done"] += 1
-                rec.pending -= 1
-                if rec.pending > 0:
-                    return
-            else:
-                counts["solves_done"] += 1
-                rec.left -= 1
-                if rec.left > 0:
-                    return
-                later = [q for q in (rec.layers, rec.tracks) if q is not None]
-                if later:                              # last segment done: the frame's layers and trk lines, then finish_frame
-                    rec.stage, rec.pending = "layers", len(later)
-                    for q in later:
-                        hand_out(rec, q, workers.put_owed)
-                    return
-            twin = rec.tex if rec.tex is not None else rec.blur if rec.blur is not None else rec.seg   # (they exclude each other)
-            if twin is not None and rec.stage != "tex":        # the twin reads the segments' flows: before finish_frame
-                rec.stage = "tex"
-                hand_out(rec, twin, workers.put_owed)
-                return
+    # The scheduler: a Frame's plan, stage by stage.  It knows stages and Steps, no variant -- prepare_pair wrote the plan.
+    def start(rec, put):                               # (under `lock`) begin the plan's first stage; none left: the pair is done
+        if rec.plan and rec.plan[0] == FINISH:         # frames_done counts the hand-over to the pool, not its return
             counts["frames_done"] += 1
-            if rec.motion is None and rec.light is not None:       # then the pair's light line, over the finished frames
-                posts.append(pool.apply_async(finish_frame, (rec,), callback=lambda _, rec=rec: light_ready(rec),
-                                              error_callback=lambda e: workers._fail("finish_frame failed: %r" % (e,))))
-            elif rec.motion is None:
-                posts.append(pool.apply_async(finish_frame, (rec,)))
-            else:                                      # then the pair's bg line, over the flattened files
-                posts.append(pool.apply_async(finish_frame, (rec,), callback=lambda _, rec=rec: bg_ready(rec),
-                                              error_callback=lambda e: workers._fail("finish_frame failed: %r" % (e,))))
+            posts.append(pool.apply_async(finish_frame, (rec,), callback=lambda _: advance(rec),
+                                          error_callback=lambda e: workers._fail("finish_frame failed: %r" % (e,))))
+        elif rec.plan:
+            rec.left = len(rec.plan[0])
+            for st in rec.plan[0]:                     # the one place a line becomes text
+                frames[pipeline.done_token(st.line)] = (rec, st)
+                put(pipeline.format_line(st.line))
+
+    def advance(rec):                                  # a worker thread, or the pool's result thread: the current stage is done
+        try:
+            with lock:
+                stage = rec.plan.pop(0)
+                if stage != FINISH and rec.remove:
+                    for q in (q for st in stage for q in st.remove):
+                        if osp.exists(q):
+                            os.remove(q)
+                start(rec, workers.put_owed)
+        except Exception as e:                         # (an exception would end the calling thread, and the run would hang)
+            workers._fail("the plan of %s stopped: %r" % (rec.line.flow, e))
+
+    def on_done(path):                                 # a worker thread: one line finished
+        with lock:
+            rec, st = frames.pop(path)
+            counts[st.count] += 1
+            rec.left -= 1
+            if rec.left == 0:
+                advance(rec)
 
     # --dm_bin builtin: the matcher and the solver must not share a GPU at the same time (the solver's resident kernel
     # needs the whole chip: arap_resident.h), so the run has two phases -- every pair is prepared and matched first
@@ -900,17 +899,10 @@ def main(flags):
             workers.check()
             if rec is None or not rec.solves:
                 continue
-            rec.left = len(rec.solves)
-            if rec.layers is not None:
+            for _ in follow_up_steps(rec.plan):        # the workers stay open for every line the plan puts later
                 workers.owe()
-            if rec.motion is not None:
-                workers.owe()
-            for later in (rec.tex, rec.motion_tex, rec.tracks, rec.blur, rec.light, rec.seg):
-                if later is not None:
-                    workers.owe()
             with lock:
-                for ln in rec.solves:
-                    hand_out(rec, ln, workers.put)
+                start(rec, workers.put)
             n_solves += len(rec.solves)
             n_frames += 1
         workers.close()
@@ -927,10 +919,8 @@ def main(flags):
         listed = scan(argparse.Namespace(**dict(vars(flags), resume=False)), input_root, output_root)
     out_paths, rejected = write_lists(flags, output_root, listed)
     dt = time.time() - t_start
-    stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt, frames_done=counts["frames_done"],
-                 layers_done=counts["layers_done"], bg_done=counts["bg_done"], tex_done=counts["tex_done"],
-                 tracks_done=counts["tracks_done"], blur_done=counts["blur_done"], light_done=counts["light_done"],
-                 seg_done=counts["seg_done"],
+    stats = dict(pairs=len(all_paths), frames=n_frames, solves=n_solves, seconds=dt,
+                 **{k: v for k, v in counts.items() if k != "solves_done"},        # (`solves` above says it)
                  seconds_since_workers_ready=(time.time() - workers.t_ready) if workers.t_ready else None,
                  gpus=list(flags.gpu), worker="serve" if serve else "batch", jobs=flags.jobs, narap=flags.narap,
                  batches=workers.batches,
@@ -942,11 +932,44 @@ def main(flags):
     return out_paths
 
 
+def serves(flags):
+    """are the workers persistent `arap_bin --serve` children?  --worker serve, or auto with this repository's C++ driver"""
+    return flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == CPP_BIN)
+
+
 def own_arap_bin(cmd):
     """is --arap_bin this repository's driver (the C++ arap_deform, or arap_deform.py under an interpreter)?"""
     tok = cmd.split()
     own = {CPP_BIN, osp.join(HERE, "arap_deform.py")}
     return bool(tok) and (osp.abspath(tok[0]) in own or (len(tok) > 1 and osp.abspath(tok[1]) in own))
+
+
+# What needs this repository's arap_deform: (the condition (`asked`), how the refusal names the flags, what a foreign
+# --arap_bin does ...).  parse() says where in its order of checks each refusal stands (refuse).
+FOREIGN = dict(
+    seg=(("seg",), "--seg needs", "not know the seg line"),
+    relight=(("relight",), "--relight needs", "not know the light line"),
+    blur=(("blur",), "--blur needs", "not know the blur line"),
+    tracks=(("tracks",), "--tracks needs", "not know the trk line"),
+    retex=(("retex",), "--retex needs", "not know the tex line"),
+    diag=(("diag",), "--diag / --max_fold need", "not write the diagnostics"),
+    occ_layers=(("occ_layers",), "--occ_layers needs", "not know the layers line"),
+    bwd_occ=(("bwd_flow", "occ"), "--bwd_flow / --occ need", "not write the extra outputs"),
+    bg_motion=(("bg_motion",), "--bg_motion needs", "not know the bg line"),
+    mid=(("mid",), "--mid needs", "not know the mid= token"),
+    mid_layers=(("mid_layers",), "--mid_layers needs", "not know the layers line"))
+# What a flag cannot be combined with: flag -> (the flags it excludes, why)
+_SEQUENCES = ("mid", "mid_layers", "mid_bg")
+EXCLUSIVE = dict(
+    seg=(_SEQUENCES + ("retex", "blur", "relight"),
+         "the variants share the clean pair's geometry files, and maps of in-between frames are made with opt.seg_maps, "
+         "not from this command line"),
+    relight=(_SEQUENCES + ("retex", "blur"),
+             "relit sequences, twins and blurred frames are made with opt.relight, not from this command line"),
+    blur=(_SEQUENCES + ("retex",),
+          "blurred sequences and blurred twins are made with opt.blur_layers, not from this command line"),
+    tracks=(("bg_motion",), "a track of a background point assumes the static background"),
+    retex=(_SEQUENCES, "sequences of retextured in-between frames are not built"))
 
 
 def parse(argv=None):
@@ -1057,6 +1080,15 @@ def parse(argv=None):
                              "OUT/MBDistBwd (whole pixels to the nearest such pixel up to RADIUS, default 140, at most 254; "
                              "255 beyond) (DESIGN.md \"Segment maps\")")
     flags = parser.parse_args(argv)
+
+    def refuse(key):            # the refusals of `key`: EXCLUSIVE's, if it has a row, then FOREIGN's.  A flag counts as given
+        others, reason = EXCLUSIVE.get(key, ((), ""))      # by `asked`, also while --blur / --seg still hold their raw lists
+        if asked(others, flags):
+            parser.error("--%s cannot be combined with %s: %s" % (key, " / ".join("--" + n for n in others), reason))
+        when, subject, lacks = FOREIGN[key]
+        if asked(when, flags) and not own_arap_bin(flags.arap_bin):
+            parser.error("%s this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does %s" % (subject, lacks))
+
     if flags.seg is not None:
         try:
             if len(flags.seg) > 2:
@@ -1068,24 +1100,13 @@ def parse(argv=None):
         if not (np.isfinite(tau) and tau >= 0) or not 0 <= radius <= pipeline.SEG_MAX_RADIUS:
             parser.error("--seg [TAU [RADIUS]]: a finite TAU >= 0 and a RADIUS of 0 .. %d" % pipeline.SEG_MAX_RADIUS)
         flags.seg = (tau, radius)
-        if flags.mid or flags.mid_layers or flags.mid_bg or flags.retex or flags.blur is not None or flags.relight is not None:
-            parser.error("--seg cannot be combined with --mid / --mid_layers / --mid_bg / --retex / --blur / --relight: the "
-                         "variants share the clean pair's geometry files, and maps of in-between frames are made with "
-                         "opt.seg_maps, not from this command line")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--seg needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
-                         "not know the seg line")
+        refuse("seg")
     if flags.relight is not None:
         if not (np.isfinite(flags.relight) and flags.relight >= 0):
             parser.error("--relight [STRENGTH]: a finite STRENGTH >= 0")
         if not flags.bg_dir:
             parser.error("--relight needs --bg_dir: a shadow needs a background to fall on")
-        if flags.mid or flags.mid_layers or flags.mid_bg or flags.retex or flags.blur is not None:
-            parser.error("--relight cannot be combined with --mid / --mid_layers / --mid_bg / --retex / --blur: relit sequences, "
-                         "twins and blurred frames are made with opt.relight, not from this command line")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--relight needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
-                         "not know the light line")
+        refuse("relight")
     if flags.blur is not None:
         try:
             if len(flags.blur) > 2:
@@ -1099,37 +1120,20 @@ def parse(argv=None):
         flags.blur = (shutter, samples)
         if not flags.bg_dir:
             parser.error("--blur needs --bg_dir: a blurred object needs a defined background behind it")
-        if flags.mid or flags.mid_layers or flags.mid_bg or flags.retex:
-            parser.error("--blur cannot be combined with --mid / --mid_layers / --mid_bg / --retex: blurred sequences and "
-                         "blurred twins are made with opt.blur_layers, not from this command line")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--blur needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
-                         "not know the blur line")
+        refuse("blur")
     if flags.tracks:
         if not 1 <= flags.tracks <= 1 << 24:
             parser.error("--tracks P: 1 .. 2^24 points")
         if not (flags.mid or (flags.multseg and flags.mid_layers)):
             parser.error("--tracks needs --mid K or --multseg --mid_layers K: the states a point is tracked through")
-        if flags.bg_motion is not None:
-            parser.error("--tracks cannot be combined with --bg_motion: a track of a background point assumes the static "
-                         "background")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--tracks needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
-                         "not know the trk line")
+        refuse("tracks")
     if flags.retex:
-        if flags.mid or flags.mid_layers or flags.mid_bg:
-            parser.error("--retex cannot be combined with --mid / --mid_layers / --mid_bg: sequences of retextured "
-                         "in-between frames are not built")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--retex needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
-                         "not know the tex line")
+        refuse("retex")
     if flags.max_fold is not None:
         if not 0 <= flags.max_fold <= 1:                   # (false on NaN)
             parser.error("--max_fold FRAC must lie in 0 .. 1")
         flags.diag = True
-    if flags.diag and not own_arap_bin(flags.arap_bin):
-        parser.error("--diag / --max_fold need this repository's arap_deform (C++ or arap_deform.py): a foreign "
-                     "--arap_bin does not write the diagnostics")
+    refuse("diag")
     if flags.mid_bg:
         if flags.bg_motion is None:
             parser.error("--mid_bg needs --bg_motion: it moves that camera through the in-between frames")
@@ -1144,12 +1148,8 @@ def parse(argv=None):
                      "is supported)")
     if flags.occ_layers and not flags.multseg:
         parser.error("--occ_layers needs --multseg (a single-object run takes --occ)")
-    if flags.occ_layers and not own_arap_bin(flags.arap_bin):
-        parser.error("--occ_layers needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin "
-                     "does not know the layers line")
-    if (flags.bwd_flow or flags.occ) and not own_arap_bin(flags.arap_bin):
-        parser.error("--bwd_flow / --occ need this repository's arap_deform (C++ or arap_deform.py): a foreign "
-                     "--arap_bin does not write the extra outputs")
+    refuse("occ_layers")
+    refuse("bwd_occ")
     if flags.bg_motion is not None:
         if not flags.bg_dir:
             parser.error("--bg_motion needs --bg_dir: there is no background to move")
@@ -1157,9 +1157,7 @@ def parse(argv=None):
             parser.error("--bg_motion cannot be combined with --mid / --mid_layers: the background motion of an "
                          "in-between frame needs the motion interpolated per snapshot, which is not built without "
                          "--mid_bg")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--bg_motion needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin "
-                         "does not know the bg line")
+        refuse("bg_motion")
         if not (flags.bg_motion >= 0 and np.isfinite(flags.bg_motion)):
             parser.error("--bg_motion STRENGTH must be a finite number >= 0")
     flags.mid_steps = []
@@ -1167,9 +1165,7 @@ def parse(argv=None):
         if flags.multseg:
             parser.error("--mid cannot be combined with --multseg: merging the segments' in-between states is a "
                          "separate piece of work, which --multseg --mid_layers K does")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--mid needs this repository's arap_deform (C++ or arap_deform.py): a foreign --arap_bin does "
-                         "not know the mid= token")
+        refuse("mid")
         try:
             flags.mid_steps = pipeline.mid_steps(flags.mid, NUM_ITER)
         except ValueError as e:
@@ -1178,9 +1174,7 @@ def parse(argv=None):
     if flags.mid_layers:
         if not flags.multseg:
             parser.error("--mid_layers needs --multseg (a single-object run takes --mid)")
-        if not own_arap_bin(flags.arap_bin):
-            parser.error("--mid_layers needs this repository's arap_deform (C++ or arap_deform.py): a foreign "
-                         "--arap_bin does not know the layers line")
+        refuse("mid_layers")
         try:
             flags.mid_layers_steps = pipeline.mid_steps(flags.mid_layers, NUM_ITER)
         except ValueError as e:

@@ -41,8 +41,7 @@ def run_lines(flags, now, after=None):
         for it in after.get(path, ()):
             workers.put_owed(pipeline.format_line(it))
     if expected:
-        serve = flags.worker == "serve" or (flags.worker == "auto" and osp.abspath(flags.arap_bin.split()[0]) == para_gen.CPP_BIN)
-        workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, serve, on_done)
+        workers = para_gen.GpuWorkers(flags.arap_bin, flags.gpu, flags.narap, para_gen.serves(flags), on_done)
         for _ in expected[len(now):]:
             workers.owe()
         for it in now:

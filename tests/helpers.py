@@ -28,6 +28,122 @@ def para_gen_flags(extra):
     return para_gen.parse(["--input", "in", "--output", "out", "--matches", "m"] + extra)
 
 
+RECORDING_WORKER = r'''
+import os, shutil, sys
+# stand-in for arap_deform (no GPU), for every form of line para_gen hands out: a line is logged, REFUSED (exit 3) when a
+# file it reads is not there yet (or no longer), and answered by a placeholder at every output path it names -- real
+# pictures, flows and diag files where para_gen's back end reads them (tests/helpers.py: recording_worker)
+import numpy as np
+from PIL import Image
+sys.path.insert(0, %r)
+from arap_flow_amd import flo as F, pipeline
+from arap_flow_amd.run_lines import format_diag
+LOG = %r
+
+def layer_files(layers):
+    return [q for mask, flows in layers for q in [mask] + ([flows] if isinstance(flows, str) else list(flows))]
+
+def snapshots(token):
+    steps, prefix = pipeline.parse_mid(token)
+    return steps, [pipeline.mid_files(prefix, i) for i in steps]
+
+def reads(it):
+    if isinstance(it, pipeline.SolveLine):
+        return list(it[:3])
+    if isinstance(it, pipeline.LayersLine):
+        mids = [q for _, flo in it.layers for f in snapshots("%%s:%%s" %% (it.out["mid"].split(":")[0], flo[:-4]))[1]
+                for q in f.values()] if "mid" in it.out else []
+        return [it.rgb] + layer_files(it.layers) + mids
+    if isinstance(it, pipeline.BgLine):
+        mids = []
+        if it.mid:
+            steps, files = snapshots(it.mid)
+            mids = [q for f in files for q in f.values()]
+            if "occ" in it.inputs:
+                prefix = pipeline.parse_mid(it.mid)[1]
+                mids += [pipeline.mid_layer_files(prefix, i)["occ"] for i in (0,) + tuple(steps)]
+        return list(it[:6]) + list(it.inputs.values()) + mids
+    if isinstance(it, pipeline.TrkLine):
+        return [it.points] + layer_files(it.layers)
+    if isinstance(it, pipeline.LightLine):
+        return list(it[:4])
+    if isinstance(it, pipeline.BlurLine):
+        return [it.rgb, it.bg] + layer_files(it.layers)
+    if isinstance(it, pipeline.TexLine):
+        return [it.rgb] + layer_files(it.layers)
+    return layer_files(it.layers)                       # a seg line
+
+def put(path, like, shape):
+    """a placeholder of the kind the path's name asks for; a picture that is there already (a bg line's own frame) stays"""
+    if path.endswith(".flo"):
+        F.flow_write(path, np.zeros(shape + (2,), np.float32))
+    elif path.endswith(".txt"):
+        open(path, "w").write(format_diag(dict(vertices=4, outside=0, triangles=2, folded=0, nonfinite=0,
+                                               det_min=1.0, det_max=1.0, disp2_max=0.0)))
+    elif path.endswith(".png") and like is not None:
+        if not os.path.exists(path):
+            shutil.copy(like, path)
+    else:
+        open(path, "w").write("placeholder\n")
+
+def run(line):
+    it = pipeline.parse_line(line)
+    with open(LOG, "a") as log:
+        log.write(line.rstrip("\n") + "\n")
+    for q in reads(it):
+        if not os.path.exists(q):
+            print("%%s line before (or after) its input %%s" %% (type(it).__name__, q), flush=True)
+            sys.exit(3)
+    if isinstance(it, pipeline.SolveLine):
+        m = np.array(Image.open(it.mask).convert("RGB"))[..., 0]
+        F.flow_write(it.flow, np.zeros(m.shape + (2,), np.float32))
+        shutil.copy(it.rgb, it.out_rgb)
+        Image.fromarray(m == 0).save(it.out_mask)
+        for k, q in it.extra.items():
+            if k == "mid":
+                for f in snapshots(q)[1]:
+                    F.flow_write(f["flow"], np.zeros(m.shape + (2,), np.float32)); F.flow_write(f["step"], np.zeros(m.shape + (2,), np.float32))
+                    shutil.copy(it.rgb, f["rgb"]); Image.fromarray(m == 0).save(f["mask"])
+            elif q.endswith(".png"):
+                Image.fromarray(np.zeros(m.shape, np.uint8)).save(q)
+            else:
+                put(q, None, m.shape)
+        return
+    if isinstance(it, pipeline.BgLine):
+        like, outs = it.rgb2, pipeline.bg_outputs(it)
+    elif isinstance(it, pipeline.TrkLine):
+        like, outs = None, [it.out]
+    else:
+        like = it.rgb1 if isinstance(it, pipeline.LightLine) else getattr(it, "rgb", None) or it.layers[0][0]
+        outs = [q for k, q in it.out.items() if k != "mid"]
+        if "mid" in it.out:                             # a layers line: the merged snapshots and, with occ=, the link occlusions
+            steps, files = snapshots(it.out["mid"])
+            outs += [q for f in files for q in f.values()]
+            if "occ" in it.out:
+                outs += [pipeline.mid_layer_files(pipeline.parse_mid(it.out["mid"])[1], i)["occ"] for i in (0,) + tuple(steps)]
+    shape = np.array(Image.open(like if like else it.layers[0][0])).shape[:2]
+    for q in outs:
+        put(q, like, shape)
+
+if sys.argv[1] == "--serve":
+    print("Ready", flush=True)
+    for line in sys.stdin:
+        run(line)
+        print("Done " + pipeline.done_token(pipeline.parse_line(line)), flush=True)
+else:
+    for l in open(sys.argv[1]).read().splitlines():
+        if l.strip(): run(l)
+'''
+
+
+def recording_worker(path, log, root):
+    """writes RECORDING_WORKER to `path` (its log at `log`, this repository at `root`) -> the --arap_bin that runs it"""
+    import sys
+    with open(str(path), "w") as f:
+        f.write(RECORDING_WORKER % (str(root), str(log)))
+    return "%s %s" % (sys.executable, path)
+
+
 def rel_l2(a, b):
     a = np.asarray(a, np.float64).ravel()
     b = np.asarray(b, np.float64).ravel()
