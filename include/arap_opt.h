@@ -321,8 +321,12 @@ int ArapFlow_SolverStampParts(ArapFlow_Solver* s, uint64_t* out);
 
 /* warp_image (ARAP/warping/src/main.cpp:145-225) on DEVICE buffers: rgb uint8[H][W][3], mask_red
  * uint8[H][W], flow float[H][W][2] -> out_rgb uint8[H][W][3], out_mask uint8[H][W].
- * `scratch` is a device buffer of ArapFlow_WarpScratchBytes(W,H) bytes.  Asynchronous on the state's
- * stream.  Returns 0 or a HIP error code. */
+ * `scratch` is a 256-byte aligned device buffer of ArapFlow_WarpScratchBytes(W,H) bytes (64-bit keys and the job the
+ * kernels read live in it).  Asynchronous on the state's stream.  Returns 0 or a HIP error code.
+ * For every ArapFlow_* call on caller-owned device memory: `scratch` owes 256 bytes of alignment, every other buffer its
+ * element type's (8 for float[..][2] data and the 64-bit tables, 4 for float planes and ArapFlow_MeshStats, 2 for 16-bit
+ * distances, 1 for bytes) unless the call states otherwise; a call writes nothing outside the bytes stated for a buffer,
+ * expects nothing of the contents of `scratch`, and enqueues all of its work on the state's stream. */
 uint64_t ArapFlow_WarpScratchBytes(unsigned W, unsigned H);
 int ArapFlow_Warp(Opt_State* state, unsigned W, unsigned H, const void* rgb, const void* mask_red,
                   const void* flow, void* out_rgb, void* out_mask, void* scratch);
@@ -821,8 +825,8 @@ int ArapFlow_MapScore(Opt_State* state, unsigned W, unsigned H, unsigned n, cons
  *     src = 0 both, 1 A only, 2 B only, 3 neither, plus 4 when the key came from the hole fill.
  *   out      uint8[K][H][W][3]
  *   src      uint8[K][H][W] or NULL
- *   scratch  ArapFlow_InterpScratchBytes(W, H, K) bytes, the caller's: the K * N keys, aligned to 256 bytes (0 for sizes
- *            the call refuses)
+ *   scratch  a 256-byte aligned device buffer of ArapFlow_InterpScratchBytes(W, H, K) bytes, the caller's: the K * N
+ *            64-bit keys, rounded up to 256 bytes (0 for sizes the call refuses)
  * Two kernels behind one clear of the keys, each launched once for all K times; the only atomics are the 64-bit integer
  * minima on the keys, so two runs give identical bytes.  Nothing is launched or allocated unless the call is made.
  * Asynchronous on the state's stream.  Returns 0; -1, and nothing is launched or written, on bad arguments: a null state,
