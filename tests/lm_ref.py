@@ -3,7 +3,8 @@
 Written from the reference's solver, ARAP/API/src/solverGPUGaussNewton.t: the step at :1016-1177 and the kernels at
 :361-397 (PCGInit1), :421-434 (PCGStep1), :446-489 (PCGStep2 with q), :491-535 (the residual reset), :537-557 (PCGStep3,
 PCGLinearUpdate), :616-662 (PCGSaveSSq, PCGComputeCtC, PCGFinalizeDiagonal), guardedInvert :323-332 -- not from the
-oracle's restatement of them (oracle/arap_oracle_impl.h: oracle_solve_lm), which this twin is there to pin.
+oracle's restatement of them (oracle/arap_oracle_impl.h: oracle_solve_lm), which this twin is there to pin.  The loop body
+it shares with the Gauss-Newton kind (PCGStep1, the alpha, delta and r updates of PCGStep2, PCGStep3) is gn_ref.pcg.
 
 It stands on three float64 primitives only, each pinned by finite differences in tests/test_oracle.py:
   oracle.evalJTF   g = J^T F and diag(J^T J)
@@ -16,6 +17,8 @@ so nothing here knows what a residual looks like.  Sums are numpy's pairwise flo
 thing that separates this loop from oracle.solve_lm(dtype=float64).
 """
 import numpy as np
+
+import gn_ref
 
 OUTCOMES = ("accepted", "rejected", "function_tolerance", "min_radius")
 
@@ -63,27 +66,13 @@ def solve_lm(orc, O, A, U, Cn, M, wf, wr, nIterations, lIterations, residual_res
             pre = on(1.0 / (CtC + radius * unclamped))
             b = r.copy()
             p = pre * r
-            rho = dot(r, p)
             Q0 = 0.5 * dot(delta, r + r)
             apply_a = lambda v: on(orc.applyJTJ(A, U, Cn, M, wf, wr, v, dtype=np.float64) + CtC * v)   # o.t:2076-2082
+            reset = lambda l, d: b - apply_a(d) if (l + 1) % residual_reset_period == 0 else None      # :1077-1083
             ran = 0
-            for l in range(lIterations):                                                        # :1056-1103
-                Ap = apply_a(p)                                                                 # PCGStep1
-                sigma = dot(p, Ap)
-                alpha = rho / sigma if sigma > 0.0 else 0.0
-                delta = delta + alpha * p
-                if (l + 1) % residual_reset_period == 0:                                        # :1077-1083
-                    r = b - apply_a(delta)
-                else:
-                    r = r - alpha * Ap                                                          # PCGStep2
-                z = pre * r
-                rho_new = dot(z, r)
-                Q1 = 0.5 * dot(delta, r + b)
-                beta = rho_new / rho if rho > 0.0 else 0.0
-                p = z + beta * p                                                                # PCGStep3
-                rho = rho_new
-                ran = l + 1
-                zeta = np.float64(l + 1) * (np.float64(Q1) - Q0) / np.float64(Q1)              # :1093-1102
+            for ran, delta, r in gn_ref.pcg(apply_a, r, p, pre, lIterations, reset):           # :1056-1103, PCGStep1-3
+                Q1 = 0.5 * dot(delta, r + b)                                                    # PCGStep2 :477-482
+                zeta = np.float64(ran) * (np.float64(Q1) - Q0) / np.float64(Q1)                # :1093-1102
                 if zeta < par["q_tolerance"]:
                     break
                 Q0 = Q1

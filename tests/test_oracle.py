@@ -15,7 +15,31 @@ from PIL import Image
 import helpers
 
 
+def _closed_forms_vs_jacobian(oracle, O, A, U, C, M, wf, wr, J, r0, cols):
+    """evalJTF, applyJTJ and cost at (O, A) against a central-difference Jacobian J[:, cols] of the residuals r0 there
+    (cols: the positions, in a flattened [H, W, 3], of the unknowns J has a column for -- every active one at least)"""
+    H, W = A.shape
+    act = np.repeat(M.reshape(-1) == 0, 3)
+    assert act[cols].sum() == act.sum()
+    sel = act[cols]                                       # columns of active unknowns
+    g, d = oracle.evalJTF(O, A, U, C, M, wf, wr)
+    gfd, dfd = J.T @ r0, (J * J).sum(0)
+    assert np.abs(g.reshape(-1)[cols][sel] - gfd[sel]).max() / np.abs(gfd).max() < 1e-7
+    assert np.abs(d.reshape(-1)[cols][sel] - dfd[sel]).max() / np.abs(dfd).max() < 1e-7
+    assert np.all(g.reshape(-1)[~act] == 0)
+    rng = np.random.default_rng(1)
+    P = rng.normal(size=(H, W, 3))
+    P[M != 0] = 0
+    JP = J.T @ (J @ P.reshape(-1)[cols])
+    out = oracle.applyJTJ(A, U, C, M, wf, wr, P)
+    assert np.abs(out.reshape(-1)[cols][sel] - JP[sel]).max() / np.abs(JP).max() < 1e-7
+    assert abs(oracle.cost(O, A, U, C, M, wf, wr) - 0.5 * (r0 ** 2).sum()) < 1e-9 * (r0 ** 2).sum()
+
+
 def test_closed_forms_match_finite_differences(oracle):
+    """the 9x7 random problem, then every case of tests/gn_cases.py at its start (their Jacobians are the ones the
+    Gauss-Newton pins of tests/test_gn_host.py use: built once per session)"""
+    import gn_cases
     pb = helpers.random_problem(9, 7, seed=0)
     W, H = 9, 7
     U, C, M = (pb[k].astype(np.float64) for k in "UCM")
@@ -40,19 +64,10 @@ def test_closed_forms_match_finite_differences(oracle):
         xp[j] += eps
         xm[j] -= eps
         J[:, j] = (res(xp) - res(xm)) / (2 * eps)
-    act = np.repeat(M.reshape(-1) == 0, 3)
-    g, d = oracle.evalJTF(O, A, U, C, M, wf, wr)
-    gfd, dfd = J.T @ r0, (J * J).sum(0)
-    assert np.abs(g.reshape(-1)[act] - gfd[act]).max() / np.abs(gfd).max() < 1e-7
-    assert np.abs(d.reshape(-1)[act] - dfd[act]).max() / np.abs(dfd).max() < 1e-7
-    assert np.all(g.reshape(-1)[~act] == 0)
-    rng = np.random.default_rng(1)
-    P = rng.normal(size=(H, W, 3))
-    P[M != 0] = 0
-    JP = J.T @ (J @ P.reshape(-1))
-    out = oracle.applyJTJ(A, U, C, M, wf, wr, P)
-    assert np.abs(out.reshape(-1)[act] - JP[act]).max() / np.abs(JP).max() < 1e-7
-    assert abs(oracle.cost(O, A, U, C, M, wf, wr) - 0.5 * (r0 ** 2).sum()) < 1e-9 * (r0 ** 2).sum()
+    _closed_forms_vs_jacobian(oracle, O, A, U, C, M, wf, wr, J, r0, np.arange(3 * N))
+    for case in gn_cases.CASES:
+        d = gn_cases.direct(oracle, case)
+        _closed_forms_vs_jacobian(oracle, *gn_cases.args(case), d.J, d.F, d.idx)
 
 
 def test_sincos_spec_accuracy(oracle):
