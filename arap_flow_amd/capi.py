@@ -43,6 +43,12 @@ class AugSample(C.Structure):
                 ("fill", C.c_float * 3)]
 
 
+class ClipFrame(C.Structure):
+    """ArapFlow_ClipFrame (DESIGN.md "Training clips")"""
+    _fields_ = [("T", C.c_float * 6), ("gain", C.c_float * 3), ("gamma", C.c_float), ("fill", C.c_float * 3),
+                ("n_erase", C.c_uint32), ("erase", (C.c_int32 * 4) * 4)]
+
+
 TEX_KINDS = ("checker", "brick", "voronoi", "noise", "wave")      # ARAPFLOW_TEX_*: a kind's number is its index here
 
 MESH_STATS_KEYS = tuple(k for k, _ in MeshStats._fields_ if k != "reserved")     # the order of a diag file's lines
@@ -142,6 +148,9 @@ SYMBOLS = [
     ("ArapFlow_AugmentTables", _I, [C.POINTER(AugSample)] + [C.POINTER(C.c_float)] * 4),
     ("ArapFlow_AugmentPairs", _I, [_VP, _U, _U, _U, _U, _U] + [_VP] * 4 + [C.POINTER(AugSample)] + [C.POINTER(C.c_float)] * 2 +
      [C.c_float] + [_VP] * 4),
+    ("ArapFlow_ClipTables", _I, [C.POINTER(ClipFrame)] + [C.POINTER(C.c_float)] * 4),
+    ("ArapFlow_AugmentClips", _I, [_VP] + [_U] * 8 + [_VP, C.POINTER(C.c_int32)] + [_VP] * 4 + [C.POINTER(ClipFrame)] +
+     [C.POINTER(C.c_float)] * 2 + [C.c_float] + [_VP] * 5),
 ]
 
 OUT_BACKWARD, OUT_OCCLUSION = 1, 2      # ARAPFLOW_OUT_* of include/arap_opt.h
@@ -155,6 +164,7 @@ LSCORE_FIELDS, MSCORE_MAX_THR = 8, 8      # ARAPFLOW_LSCORE_FIELDS, ARAPFLOW_MSC
 INTERP_MAX_TIMES, INTERP_FILL = 32, 16     # ARAPFLOW_INTERP_MAX_TIMES, ARAPFLOW_INTERP_FILL
 LIGHT_MAX_R, LIGHT_MAX_SHIFT = 16, 64   # ARAPFLOW_LIGHT_MAX_R, ARAPFLOW_LIGHT_MAX_SHIFT
 AUG_MAX_BATCH, AUG_MAX_ERASE = 64, 4    # ARAPFLOW_AUG_MAX_BATCH, ARAPFLOW_AUG_MAX_ERASE
+CLIP_MAX_FRAMES, CLIP_MAX_LINKS, CLIP_MAX_UNITS = 16, 32, 256   # ARAPFLOW_CLIP_MAX_FRAMES, ARAPFLOW_CLIP_MAX_LINKS; B * T <= 256
 
 _LIB = None
 

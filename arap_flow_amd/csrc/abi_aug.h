@@ -6,31 +6,48 @@
 static_assert(AUG_MAX_BATCH == ARAPFLOW_AUG_MAX_BATCH && AUG_MAX_ERASE == ARAPFLOW_AUG_MAX_ERASE, "augmentation limits");
 static_assert(sizeof(ArapFlow_AugSample) == 160, "ArapFlow_AugSample layout");
 
-// P2 and the two tone tables of a sample, in double, each value rounded once; false for a sample outside its ranges
-static bool aug_tables(const ArapFlow_AugSample& s, const float scale[3], const float bias[3], float P2[6], float lut[2][3][256])
+// The per-frame pieces of the tables, shared by ArapFlow_AugmentTables and ArapFlow_ClipTables (abi_clip.h).
+// a frame inside its ranges: a finite map, a finite gain and gamma > 0
+static bool aug_frame_ok(const float T[6], const float gain[3], float gamma)
 {
     for (int i = 0; i < 6; ++i)
-        if (!std::isfinite(s.T1[i]) || !std::isfinite(s.T2[i])) return false;
-    const float* gains[2] = {s.gain1, s.gain2};
-    const float gammas[2] = {s.gamma1, s.gamma2};
-    for (int k = 0; k < 2; ++k) {
-        if (!std::isfinite(gammas[k]) || !(gammas[k] > 0.f)) return false;
-        for (int c = 0; c < 3; ++c)
-            if (!std::isfinite(gains[k][c]) || !(gains[k][c] > 0.f)) return false;
-    }
-    const double a = s.T2[0], b = s.T2[1], c = s.T2[2], d = s.T2[3], e = s.T2[4], f = s.T2[5];
+        if (!std::isfinite(T[i])) return false;
+    if (!std::isfinite(gamma) || !(gamma > 0.f)) return false;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(gain[c]) || !(gain[c] > 0.f)) return false;
+    return true;
+}
+
+// P = the inverse of T as a map, in double, each value rounded once; false (nothing written) where det(T) == 0
+static bool aug_frame_inverse(const float T[6], float P[6])
+{
+    const double a = T[0], b = T[1], c = T[2], d = T[3], e = T[4], f = T[5];
     const double det = a * e - b * d;
     if (det == 0.0) return false;
-    P2[0] = (float)(e / det); P2[1] = (float)(-b / det); P2[2] = (float)((b * f - e * c) / det);
-    P2[3] = (float)(-d / det); P2[4] = (float)(a / det); P2[5] = (float)((d * c - a * f) / det);
-    for (int k = 0; k < 2; ++k)
-        for (int i = 0; i < 256; ++i) {
-            const double p = pow((double)i / 255.0, (double)gammas[k]);          // (one pow for the three channels)
-            for (int ch = 0; ch < 3; ++ch) {
-                const double t = (double)gains[k][ch] * p;
-                lut[k][ch][i] = (float)((255.0 * fmin(fmax(t, 0.0), 1.0)) * (double)scale[ch] + (double)bias[ch]);
-            }
+    P[0] = (float)(e / det); P[1] = (float)(-b / det); P[2] = (float)((b * f - e * c) / det);
+    P[3] = (float)(-d / det); P[4] = (float)(a / det); P[5] = (float)((d * c - a * f) / det);
+    return true;
+}
+
+// a frame's tone table with the normalisation folded in, in double, each value rounded once
+static void aug_frame_lut(const float gain[3], float gamma, const float scale[3], const float bias[3], float lut[3][256])
+{
+    for (int i = 0; i < 256; ++i) {
+        const double p = pow((double)i / 255.0, (double)gamma);                  // (one pow for the three channels)
+        for (int ch = 0; ch < 3; ++ch) {
+            const double t = (double)gain[ch] * p;
+            lut[ch][i] = (float)((255.0 * fmin(fmax(t, 0.0), 1.0)) * (double)scale[ch] + (double)bias[ch]);
         }
+    }
+}
+
+// P2 and the two tone tables of a sample; false for a sample outside its ranges
+static bool aug_tables(const ArapFlow_AugSample& s, const float scale[3], const float bias[3], float P2[6], float lut[2][3][256])
+{
+    if (!aug_frame_ok(s.T1, s.gain1, s.gamma1) || !aug_frame_ok(s.T2, s.gain2, s.gamma2)) return false;
+    if (!aug_frame_inverse(s.T2, P2)) return false;
+    aug_frame_lut(s.gain1, s.gamma1, scale, bias, lut[0]);
+    aug_frame_lut(s.gain2, s.gamma2, scale, bias, lut[1]);
     return true;
 }
 

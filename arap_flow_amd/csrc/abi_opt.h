@@ -117,6 +117,7 @@ void ArapFlow_FreeState(Opt_State* st)
     if (st->tex) (void)hipFree(st->tex);
     if (st->light) (void)hipFree(st->light);
     if (st->aug) (void)hipFree(st->aug);
+    if (st->clip) (void)hipFree(st->clip);
     delete st;
 }
 

@@ -51,6 +51,7 @@
 #include "arap_diag.h"
 #include "arap_frame.h"
 #include "arap_aug.h"
+#include "arap_clip.h"
 
 using namespace arap;
 
@@ -70,3 +71,4 @@ using namespace arap;
 #include "abi_interp.h"      // ArapFlow_InterpFrames
 #include "abi_solver.h"      // ArapFlow_Solver*
 #include "abi_aug.h"         // ArapFlow_AugmentTables, ArapFlow_AugmentPairs
+#include "abi_clip.h"        // ArapFlow_ClipTables, ArapFlow_AugmentClips

@@ -127,7 +127,9 @@ struct Opt_State {
     void* light = nullptr;      // ArapFlow_Relight: device, the call's tone table (3 x 256 bytes); at first use
     void* aug = nullptr;        // ArapFlow_AugmentPairs: device, the call's sample table (aug_cap samples); at first use, grown with B
     unsigned aug_cap = 0;
-    bool aug_bytes = false;     // ARAPOPT_AUG_BYTES=1 (experiments): k_augment without the dword loads of the taps
+    void* clip = nullptr;       // ArapFlow_AugmentClips: device, the call's frame table (clip_cap frames) and link table; at first use, grown with B * T
+    unsigned clip_cap = 0;
+    bool aug_bytes = false;     // ARAPOPT_AUG_BYTES=1 (experiments): k_augment and k_augment_clip without the dword loads of the taps
 };
 
 struct Opt_Problem {

@@ -20,6 +20,7 @@
   chain_flows      estimated tracks from per-link flow estimates (ArapFlow_ChainFlows)
   interp_frames    estimated in-between frames from a flow estimate, by splatting (ArapFlow_InterpFrames)
   augment_pairs    a training batch: B pairs augmented, cropped and normalised on the device (ArapFlow_AugmentPairs)
+  augment_clips    a batch of training clips: T frames, L flow links and P point tracks each (ArapFlow_AugmentClips)
 
 torch is used only to own device memory (tensor.data_ptr()) and streams.
 """
@@ -913,6 +914,113 @@ def augment_pairs(state, rgb1, rgb2, flow, samples, size, skip=None, scale=(1, 1
         raise ValueError("ArapFlow_AugmentPairs: bad arguments")
     if rc != 0:
         raise RuntimeError("ArapFlow_AugmentPairs failed: %d" % rc)
+    return outs
+
+
+# a frame of a training clip (DESIGN.md "Training clips"): T six floats (output pixel -> source point of this frame), its
+# tone curve (gain[3], gamma), up to four eraser rectangles (x0, y0, x1, y1) in output pixels, half-open, and their fill
+ClipFrame = collections.namedtuple("ClipFrame", "T gain gamma erase fill")
+CLIP_NEUTRAL = ClipFrame((1, 0, 0, 0, 1, 0), (1, 1, 1), 1.0, (), (0, 0, 0))
+CLIP_OUTPUTS = ("video", "flows", "valid", "tracks", "vis")
+
+
+def clip_frame(frame):
+    """a ClipFrame as the ArapFlow_ClipFrame the library reads; floats are rounded to float32 here.  More rectangles than
+    a frame holds are a ValueError (the library would see only a count)."""
+    T, gain, gamma, erase, fill = frame
+    q = capi.ClipFrame()
+    q.T, q.gain, q.fill, q.gamma = _map6(T), _f3(gain, "gain"), _f3(fill, "fill"), float(gamma)
+    erase = [tuple(r) for r in erase]
+    if len(erase) > capi.AUG_MAX_ERASE or any(len(r) != 4 for r in erase):
+        raise ValueError("a frame has at most %d rectangles (x0, y0, x1, y1)" % capi.AUG_MAX_ERASE)
+    q.n_erase = len(erase)
+    for i, r in enumerate(erase):
+        q.erase[i] = (C.c_int32 * 4)(*[max(-1 << 31, min(int(v), (1 << 31) - 1)) for v in r])
+    return q
+
+
+def clip_tables(frame, scale=(1, 1, 1), bias=(0, 0, 0), lib=None):
+    """what the library derives of a clip's frame (ArapFlow_ClipTables, DESIGN.md "Training clips"): (P f32[6], the
+    inverse of T; lut f32[3,256], the frame's tone table with the normalisation folded in), the library's own bits.  Host
+    only (no GPU, no state).  A frame outside its ranges is a ValueError."""
+    lib = lib or capi.load()
+    P, lut = (C.c_float * 6)(), (C.c_float * 768)()
+    if lib.ArapFlow_ClipTables(C.byref(clip_frame(frame)), _f3(scale, "scale"), _f3(bias, "bias"), P, lut) != 0:
+        raise ValueError("ArapFlow_ClipTables: bad arguments")
+    return np.array(P[:], np.float32), np.array(lut[:], np.float32).reshape(3, 256)
+
+
+def augment_clips(state, frames, samples, size, links=(), flows=None, skip=None, pos=None, occ=None, scale=(1, 1, 1),
+                  bias=(0, 0, 0), tau=1.0, want=None, out=None):
+    """a batch of training clips in at most two launches (ArapFlow_AugmentClips, DESIGN.md "Training clips").  frames
+    u8[B,T,H,W,3]; links: L pairs (i, j) of frame numbers, one table for the batch; flows f32[B,L,H,W,2], link l on the
+    pixels of frame i towards frame j; skip u8[B,L,H,W] or None (non-zero: no ground truth); pos f32[B,T,P,2] and occ
+    u8[B,T,P] (non-zero: hidden), a point's position in every source frame; numpy arrays or CUDA tensors, and an input no
+    wanted output needs may be None.  samples: B sequences of T ClipFrame; size = (w, h), the crop; scale, bias, tau as in
+    augment_pairs.  -> {name: CUDA tensor} of the outputs `want` names (by default every one whose inputs are given):
+    video f32[B,T,3,h,w], flows f32[B,L,2,h,w], valid u8[B,L,h,w] (0 / 255), tracks f32[B,T,P,2], vis u8[B,T,P]
+    (0 / 255).  Nothing is downloaded and nothing waited for: the call is enqueued on the state's stream, under
+    augment_pairs' rules (one device table per state; data.ClipLoader orders its calls).  `out`: {name: tensor} of
+    caller-owned CUDA tensors (contiguous, of the output's shape and type) to write instead of new ones."""
+    given = {"video": frames is not None, "flows": flows is not None, "valid": flows is not None, "tracks": pos is not None,
+             "vis": pos is not None and occ is not None}
+    want = tuple(k for k in CLIP_OUTPUTS if given[k]) if want is None else tuple(want)
+    if not want or set(want) - set(CLIP_OUTPUTS) or len(set(want)) != len(want):
+        raise ValueError("augment_clips: want: some of %s" % ", ".join(CLIP_OUTPUTS))
+    w, h = (int(v) for v in size)
+    samples = [list(s) for s in samples]
+    B = len(samples)
+    T = len(samples[0]) if B else 0
+    if not (0 < B <= capi.AUG_MAX_BATCH and 0 < T <= capi.CLIP_MAX_FRAMES and B * T <= capi.CLIP_MAX_UNITS) or \
+            any(len(s) != T for s in samples):
+        raise ValueError("augment_clips: samples: 1 .. %d clips of one length 1 .. %d, at most %d frames in all expected"
+                         % (capi.AUG_MAX_BATCH, capi.CLIP_MAX_FRAMES, capi.CLIP_MAX_UNITS))
+    links = [tuple(int(v) for v in l) for l in links]
+    L = len(links)
+    if L > capi.CLIP_MAX_LINKS or any(len(l) != 2 for l in links):
+        raise ValueError("augment_clips: links: at most %d pairs (i, j) expected" % capi.CLIP_MAX_LINKS)
+
+    def up(a, dt, lead, tail, what):
+        if a is None:
+            return None
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dt))
+        if t.dtype != getattr(torch, np.dtype(dt).name) or t.dim() != 2 + len(tail) or tuple(t.shape[:2]) != (B, lead) or \
+                any(v is not None and t.shape[2 + i] != v for i, v in enumerate(tail)):
+            raise ValueError("augment_clips: %s: %s[%d,%d,%s] expected" % (what, np.dtype(dt).name, B, lead, ",".join(
+                "*" if v is None else "%d" % v for v in tail)))
+        return t.cuda().contiguous()
+    frames, flows, skip = (up(frames, np.uint8, T, (None, None, 3), "frames"), up(flows, np.float32, L, (None, None, 2), "flows"),
+                           up(skip, np.uint8, L, (None, None), "skip"))
+    pos, occ = up(pos, np.float32, T, (None, 2), "pos"), up(occ, np.uint8, T, (None,), "occ")
+    shapes = {tuple(t.shape[2:4]) for t in (frames, flows, skip) if t is not None}
+    counts = {t.shape[2] for t in (pos, occ) if t is not None}
+    if len(shapes) > 1 or len(counts) > 1:
+        raise ValueError("augment_clips: frames, flows and skip of one size [..,H,W,..], pos and occ of one P expected")
+    H, W = shapes.pop() if shapes else (1, 1)                      # (no plane is read: any size serves)
+    P = counts.pop() if counts else 0
+    if not (0 < w < 1 << 31 and 0 < h < 1 << 31):
+        raise ValueError("augment_clips: a crop of at least one pixel expected")
+    form = {"video": ((B, T, 3, h, w), torch.float32), "flows": ((B, L, 2, h, w), torch.float32), "valid": ((B, L, h, w), torch.uint8),
+            "tracks": ((B, T, P, 2), torch.float32), "vis": ((B, T, P), torch.uint8)}
+    outs = {}
+    for k in want:
+        shape, dt = form[k]
+        t = (out or {}).get(k)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device="cuda")
+        elif not (t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape and t.dtype == dt):
+            raise ValueError("augment_clips: out[%r]: a contiguous CUDA %s tensor of shape %s expected" % (k, dt, shape))
+        outs[k] = t
+    table = (capi.ClipFrame * (B * T))(*[clip_frame(f) for s in samples for f in s])
+    link_table = (C.c_int32 * (2 * L))(*[v for l in links for v in l]) if L else None
+    ptr = lambda t: None if t is None else _dev_ptr(t)
+    rc = state.lib.ArapFlow_AugmentClips(state.handle, W, H, w, h, B, T, L, P, ptr(frames), link_table, ptr(flows), ptr(skip),
+                                         ptr(pos), ptr(occ), table, _f3(scale, "scale"), _f3(bias, "bias"), float(tau),
+                                         *[ptr(outs.get(k)) for k in CLIP_OUTPUTS])
+    if rc == -1:
+        raise ValueError("ArapFlow_AugmentClips: bad arguments")
+    if rc != 0:
+        raise RuntimeError("ArapFlow_AugmentClips failed: %d" % rc)
     return outs
 
 

@@ -937,6 +937,74 @@ int ArapFlow_AugmentPairs(Opt_State* state, unsigned W, unsigned H, unsigned w, 
                           const float scale[3], const float bias[3], float tau, void* img1, void* img2, void* out_flow,
                           void* valid);
 
+/* Training clips (DESIGN.md "Training clips"; the numpy twin is tests/clip_ref.py): B clips of one source size W x H, each
+ * of T frames, L flow links and P tracked points, every frame under its own augmentation, cropped to w x h, normalised
+ * and laid out planar, in at most two launches.  Notation and arithmetic are those of "Training batches" above: q, the
+ * taps, mix, the used / bad-tap rule and the spread guard are reused word for word (the kernels call the same device
+ * functions), every float operator is one IEEE float32 operation in the order of the parentheses, no fused multiply-add.
+ * Shapes: W * H < 2^31; B * T * w * h < 2^31; 1 <= B <= ARAPFLOW_AUG_MAX_BATCH; 1 <= T <= ARAPFLOW_CLIP_MAX_FRAMES and
+ * B * T <= 256; 0 <= L <= ARAPFLOW_CLIP_MAX_LINKS and B * L * w * h < 2^31; 0 <= P and B * T * P < 2^31.
+ * DEVICE inputs:
+ *   frames   uint8[B][T][H][W][3]
+ *   flows    float[B][L][H][W][2]: link l is a flow on the pixels of frame links[l][0] towards frame links[l][1]
+ *   skip     uint8[B][L][H][W] or NULL: non-zero = no ground truth at that pixel of that link
+ *   pos      float[B][T][P][2]: a point's position in each source frame
+ *   occ      uint8[B][T][P]: 255 (non-zero) = hidden in that frame
+ * HOST inputs: links int32[L][2], one table per call, 0 <= i, j < T and i != j, repeats allowed; samples
+ * ArapFlow_ClipFrame[B][T]; scale[3], bias[3], tau as in ArapFlow_AugmentPairs.
+ * DEVICE outputs, each NULL when not wanted (then it is not computed; an input that only unasked outputs need is not read,
+ * may be NULL and takes no part in the checks: video needs frames; out_flows and valid need links and flows; tracks needs
+ * pos; vis needs pos and occ):
+ *   video      float[B][T][3][h][w]
+ *   out_flows  float[B][L][2][h][w]
+ *   valid      uint8[B][L][h][w], 0 or 255
+ *   tracks     float[B][T][P][2]
+ *   vis        uint8[B][T][P], 0 or 255
+ * A frame's description, ArapFlow_ClipFrame (120 bytes): T, output pixel -> source point of this frame; gain, gamma, the
+ * tone curve; fill and n_erase <= ARAPFLOW_AUG_MAX_ERASE rectangles erase[i] = (x0, y0, x1, y1), half-open, output pixels.
+ *   Tables (ArapFlow_ClipTables, a pure host function; the device call uses the same code, and ArapFlow_AugmentTables is
+ *     made of the same per-frame pieces): P = the inverse of T as a map and lut[c][i], by the expressions given for P2
+ *     and lut[k] above.
+ *   Video:  video[b][t] = img of "Training batches" with T = T_{b,t} and that frame's lut, then fill[c] where (x, y) lies
+ *     in any of that frame's rectangles.  Any frame may carry rectangles.
+ *   Links:  for link l = (i, j), out_flows[b][l] and valid[b][l] are the pair definition's out_flow and valid with
+ *     T1 := T_{b,i}, P2 := P_{b,j} and the flow and skip planes [b][l].  Rectangles do not touch valid.
+ *   Tracks: p = pos[b][t][k], P = P_{b,t}:
+ *     o      = ((P.a * p.x + P.b * p.y) + P.c, (P.d * p.x + P.e * p.y) + P.f)
+ *     fin    = |o.x| <= FLT_MAX && |o.y| <= FLT_MAX (false on NaN); where it is false, o = (0, 0)
+ *     in     = fin && o.x >= 0 && o.x <= (float)(w - 1) && o.y >= 0 && o.y <= (float)(h - 1)
+ *     erased (only where in): rx = (int)floorf(o.x + 0.5f), ry alike; (rx, ry) lies in any rectangle of frame (b, t)
+ *     tracks = o, always (a hidden point keeps its position);  vis = (occ == 0 && in && !erased) ? 255 : 0
+ * Two kernels at the most: k_augment_clip (grid (tiles, T + L, B): a block is a 64 x 16 tile of one frame or one link)
+ * when video, out_flows or valid is asked, k_clip_tracks (grid (ceil(P / 256), T, B)) when tracks or vis is.  No
+ * atomics, no scratch: two runs give identical bytes.  The per-frame table and the link table live in device memory the
+ * state owns (allocated at the first call, grown with B * T) and are copied stream-ordered, in one copy, before the call
+ * returns.
+ * ArapFlow_ClipTables returns 0; -1 on a null pointer, a non-finite coefficient of T, det(T) == 0 in double, or a gain
+ * or gamma that is not finite and > 0.  (n_erase, the rectangles and fill are not read.)
+ * ArapFlow_AugmentClips is asynchronous on the state's stream.  Returns 0; -1, and nothing is launched or written, on: a
+ * null state, samples, scale or bias; every output NULL; a zero W, H, w, h, B or T; a limit above exceeded; out_flows or
+ * valid asked with L == 0 or null links; tracks or vis asked with P == 0; a null input that an asked output needs; a
+ * link out of range or with i == j (where a link output is asked); a frame that ArapFlow_ClipTables refuses or whose
+ * n_erase exceeds ARAPFLOW_AUG_MAX_ERASE; tau NaN or negative; an output overlapping an input it reads or another
+ * output; else a HIP error code. */
+#define ARAPFLOW_CLIP_MAX_FRAMES 16
+#define ARAPFLOW_CLIP_MAX_LINKS 32
+typedef struct ArapFlow_ClipFrame {
+    float T[6];
+    float gain[3], gamma;
+    float fill[3];
+    uint32_t n_erase;
+    int32_t erase[ARAPFLOW_AUG_MAX_ERASE][4];
+} ArapFlow_ClipFrame;
+int ArapFlow_ClipTables(const ArapFlow_ClipFrame* frame, const float scale[3], const float bias[3], float P[6],
+                        float lut[3][256]);
+int ArapFlow_AugmentClips(Opt_State* state, unsigned W, unsigned H, unsigned w, unsigned h, unsigned B, unsigned T,
+                          unsigned L, unsigned P, const void* frames, const int32_t* links, const void* flows,
+                          const void* skip, const void* pos, const void* occ, const ArapFlow_ClipFrame* samples,
+                          const float scale[3], const float bias[3], float tau, void* video, void* out_flows, void* valid,
+                          void* tracks, void* vis);
+
 #ifdef __cplusplus
 }
 #endif
