@@ -60,7 +60,8 @@ constexpr int RES_MAX_TILES = RES_WGS * RES_TILES_PER_WG;   // 4608 tiles (one g
 constexpr int LROW = RT_X + 2;           // 34
 constexpr int LROWS = RT_Y + 2;          // 10
 constexpr int LPLANE = LROW * LROWS;     // 340 floats
-constexpr int LTILE = 5 * LPLANE;        // float2 (px,py) plane | float2 (cos,sin) plane | float pa plane
+constexpr int LTILE = 5 * LPLANE;        // float4 {px, py, cos, sin} cells | float pa plane
+static_assert((LTILE * 4) % 16 == 0, "every tile's cells are 16-byte aligned");
 constexpr int RES_LDS_BYTES = RES_TILES_PER_WG * LTILE * 4      // halo'd p / cos / sin tiles
                               + ((RES_MAX_HALO * 8 + 15) / 16) * 16   // halo list (u16), then the decoded halo table (uint2)
                               + RES_TILES_PER_WG * 8 + 8 + 384  // tile origins, tables, scratch
@@ -249,6 +250,7 @@ __device__ __forceinline__ void ld_zentry(const unsigned long long* zx_b, __amdg
 // inside the spin, has it issued on every trip.  It emits nothing and waits for nothing.
 #define RES_GRANULE_FENCE() asm volatile("" ::: "memory")
 typedef float v2f_t __attribute__((ext_vector_type(2)));
+typedef float v3f_t __attribute__((ext_vector_type(3)));      // (16 bytes in memory, 12 of them stored)
 // (a.x*b.x + c.x, a.y*b.y + c.y) with one rounding each: v_pk_fma_f32
 __device__ __forceinline__ float2 fma2(float2 a, float2 b, float2 c)
 {
@@ -608,9 +610,10 @@ __device__ __forceinline__ double block_sum8(double v, double* wsum /* LDS, 4 do
 
 // grid = 512 workgroups (groups x wgs), block = 256, dynamic LDS = RES_LDS_BYTES (two workgroups per CU)
 //
-// LDS map: 9 halo'd tiles x {px,py,pa,cos,sin} (61 200 B); halo table (uint2 per halo cell, <= 720; it
-// starts life as the u16 cell list); tile origins int2[9]; the 10-entry M^-1_O table; broadcast + reduction scratch;
-// the staging area of the border z (9 x 80 float4, 11 520 B).
+// LDS map: 9 halo'd tiles of 6 800 B (61 200 B), each 340 cells float4 {px, py, cos, sin} followed by 340 float pa;
+// halo table (uint2 per halo cell, <= 720; it starts life as the u16 cell list); tile origins int2[9]; the 10-entry
+// M^-1_O table; broadcast + reduction scratch; the staging area of the border z (9 x 80 entries of 16 bytes, three words
+// of each written, 11 520 B).
 // Registers per lane: r(3) delta(3) Ap(3) M^-1_A M^-1_O flags per slot (12 x NS), the four edge weights and the fit
 // weight (5 x NS, one VGPR each: RES_WPIN) and, up to 7 slots, the own search direction p (3 x NS, updated in place; z =
 // M^-1 r of phase B stays in Ap's registers until the update), the own (cos, sin) (2 x NS, RES_CSREG_SLOTS) and the p of
@@ -632,7 +635,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     constexpr bool ONE_TRIP = FLAT && RES_SWEEP1 != 0;         // every group of a flat launch has <= 64 workgroups
     // own search direction in registers across iterations, z kept from phase B to the update phase (in Ap's registers)
     constexpr bool PREG = NS <= (FLAT ? RES_PREG_SLOTS_FLAT : RES_PREG_SLOTS);
-    // own (cos, sin) in registers: phase A reads 12 values per slot from LDS, the LDS copy serves the neighbours only
+    // own (cos, sin) in registers: phase A reads the four neighbours (8 reads per slot) from LDS, the LDS copy serves them only
     // (the instrumented build carries its stamps in VGPRs: one slot less, here and for the halo's p below, or it spills)
     constexpr bool CSREG = NS <= (FLAT ? RES_CSREG_SLOTS_FLAT : RES_CSREG_SLOTS) - (STAMPS ? 1 : 0);
     constexpr int WFIT = SPEND ? RES_WREG_FIT_FLAT : RES_WREG_FIT;    // the fit weight lives in registers up to this many slots
@@ -668,7 +671,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     double* wsum = (double*)(bcast + 6);                                  // 4 doubles (+ 1 at wsum[8])
     unsigned* nbits = (unsigned*)(wsum + 10);                             // [16] bitmap: ranks owning my halo vertices
     unsigned* nremote = nbits + 16;                                       // [1] some of them sit on another XCD
-    float4* zst = (float4*)((char*)lds + RES_LDS_BYTES - RES_TILES_PER_WG * RES_ZX * 16);     // [9][RES_ZX] border z, staged: (z_x, z_y, z_alpha, z_y)
+    float4* zst = (float4*)((char*)lds + RES_LDS_BYTES - RES_TILES_PER_WG * RES_ZX * 16);     // [9][RES_ZX] border z, staged: (z_x, z_y, z_alpha, -): 16-byte entries, three words written
     unsigned long long* gran_group = rd.gran + me.gran;
     unsigned long long* granx_group = FLAT ? nullptr : rd.gran + RES_GRAN_X + me.gran;
 
@@ -717,10 +720,10 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     float we[WREG ? NS : 1][5];
     const int loff = lx + W * ly;                      // this lane's vertex inside a tile: index = ibase + loff
 
-    // LDS tile t: float2 P2[340] (px,py) | float2 CS[340] (cos,sin) | float PA[340]; cell = row*34 + col
+    // LDS tile t: float4 PC[340] {px, py, cos, sin} | float PA[340]; cell = row*34 + col.  A neighbour's p and its
+    // (cos, sin) are one 16-byte read in phase A; the update phase rewrites the first half of a cell only.
     const int cell = (ly + 1) * LROW + (lx + 1);
-#define TP2(T) ((float2*)(T))
-#define TCS(T) ((float2*)(T) + LPLANE)
+#define TPC(T) ((float4*)(T))
 #define TPA(T) ((T) + 4 * LPLANE)
 
     // ---- prologue: load state, p0 and cos/sin with halos ------------------------------------------
@@ -789,8 +792,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         const float2 p0 = make_float2(mo_[j] * rx[j], mo_[j] * ry[j]);            // p0 = M^-1 r (k_gn_init)
         const float pa0 = ma_[j] * ra[j];
         if (act) {
-            TP2(T)[cell] = p0;
-            TCS(T)[cell] = qC[j];
+            TPC(T)[cell] = make_float4(p0.x, p0.y, qC[j].x, qC[j].y);
             TPA(T)[cell] = pa0;
         }
         if (PREG) {                                    // what the own cell holds: p0, or the zero it was filled with
@@ -801,12 +803,12 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
         if (vF[j] & F_ACT) {
             const int hc = vrow * LROW + (lx + 1);
             const float mo = moLUT[__popc(vF[j] & 15u) + 5 * (int)((vF[j] >> 4) & 1u)];
-            TP2(T)[hc] = make_float2(mo * vR[j].x, mo * vR[j].y); TCS(T)[hc] = vC[j]; TPA(T)[hc] = vM[j] * vRa[j];
+            TPC(T)[hc] = make_float4(mo * vR[j].x, mo * vR[j].y, vC[j].x, vC[j].y); TPA(T)[hc] = vM[j] * vRa[j];
         }
         if (hF[j] & F_ACT) {
             const int hc = (ly + 1) * LROW + hcol;
             const float mo = moLUT[__popc(hF[j] & 15u) + 5 * (int)((hF[j] >> 4) & 1u)];
-            TP2(T)[hc] = make_float2(mo * hR[j].x, mo * hR[j].y); TCS(T)[hc] = hC[j]; TPA(T)[hc] = hM[j] * hRa[j];
+            TPC(T)[hc] = make_float4(mo * hR[j].x, mo * hR[j].y, hC[j].x, hC[j].y); TPA(T)[hc] = hM[j] * hRa[j];
         }
         fl[j] = qF[j];
         ibase[j] = __builtin_amdgcn_readfirstlane(x0 + W * y0);        // uniform: vertex index of the tile origin
@@ -835,7 +837,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     const int nh = *nhalo;
     // this lane's share of the halo list, decoded once into an LDS table (the u16 list is dead after decoding and
     // registers are needed elsewhere): entry c = tid + u * 256 holds {global vertex index of the halo cell,
-    // (byte offset in the float2 planes) / 8 | (byte offset in the float plane) / 4 << 16}
+    // (byte offset of the cell, whose first half is its p) / 8 | (byte offset in the float plane) / 4 << 16}
     uint2* htab = (uint2*)hlist;                                          // [RES_MAX_HALO]
     // (with fewer than nine slots in use there are registers to spare: the entries stay in VGPRs and the update phase
     //  starts its z loads without an LDS round trip)
@@ -853,7 +855,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 const int row = rem / LROW, col = rem - row * LROW;
                 const int2 tb = tbase[k];
                 const int gx = tb.x + col - 1, gy = tb.y + row - 1;
-                e[u].y = (unsigned)(k * (LTILE / 2) + rem) | ((unsigned)(k * LTILE + 4 * LPLANE + rem) << 16);
+                e[u].y = (unsigned)(k * (LTILE / 2) + 2 * rem) | ((unsigned)(k * LTILE + 4 * LPLANE + rem) << 16);
                 // which workgroup of the group owns that vertex (the even deal above)?  -> neighbour bitmap
                 // the tile that holds (gx, gy): band gy / 8, column (gx - first x of that band) / 32 (the halo vertex is
                 // active, so it is not left of its band's first tile)
@@ -882,13 +884,13 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     }
     static_assert(RES_TILES_PER_WG * LTILE < 65536 && LTILE % 2 == 0, "halo table packs 16-bit cell offsets");
 
-    // byte offsets of this lane's cell and its four neighbours inside a tile's float2 planes / float plane
+    // byte offsets of this lane's cell and its four neighbours inside a tile's 16-byte cells / float plane
     unsigned offP[5], offA[5];
     {
         const int dn[5] = {0, 1, -1, LROW, -LROW};
 #pragma unroll
         for (int n = 0; n < 5; ++n) {
-            offP[n] = (unsigned)(cell + dn[n]) * 8u;
+            offP[n] = (unsigned)(cell + dn[n]) * 16u;
             offA[n] = (unsigned)(cell + dn[n]) * 4u;
             asm volatile("" : "+v"(offP[n]));
             asm volatile("" : "+v"(offA[n]));
@@ -997,8 +999,8 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
     if (STAMPS) t0 = __builtin_amdgcn_s_memrealtime();
     for (int l = 0; l < L && alive; ++l) {
         // ---------------- phase A: Ap = J^T J p, sigma = p.Ap --------------------------------------
-        // Software pipelined over the tile slots: the 15 LDS reads of slot j+1 (own cell + 4 neighbours x
-        // {(px,py), (cos,sin), pa}; 13 with the own p in registers, PREG, 12 with the own cos/sin too, CSREG) are issued
+        // Software pipelined over the tile slots: the 10 LDS reads of slot j+1 (own cell and own pa + 4 neighbours x
+        // {cell, pa}; 8 with the own p and the own cos/sin in registers, PREG and CSREG) are issued
         // before the arithmetic of slot j,
         // so that with only two wavefronts per SIMD the LDS round trip hides behind ~70 VALU instructions instead of
         // stalling every slot.
@@ -1022,36 +1024,37 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             for (int j = 0; j < (CSREG ? NS : 0); ++j) asm volatile("" : "+v"(csr[j]));
         }
         double acc = 0.0;
-        float2 Lpv[2], Lcs[2], LqO[2][4], Lcn[2][4];
+        float4 Lown[2], Lq[2][4];                          // own cell (where its p is not in registers), neighbour cells
+        float2 Lcs[2];                                     // own (cos, sin) alone (own p in registers, cos/sin not)
         float Lpa[2], LqA[2][4];
-        // Every read has its own opaque base (cell, +1, -1, +row, -row; float2 and float planes) plus an immediate
-        // offset: that keeps them single ds_read_b64 / ds_read_b32 (2 LDS cycles per wave instruction); merged into
-        // ds_read2_b64 by the compiler they take 8 cycles per pair (MI355X_MICROARCH.md, LDS table).
+        // A neighbour's cell {px, py, cos, sin} is ONE ds_read_b128 (4 LDS cycles per wave instruction, what the two
+        // ds_read_b64 of split planes take together: half the LDS instructions for the same bytes; an LDS instruction
+        // costs this issue-bound phase about 4.5 cycles per wavefront whatever it carries: DESIGN.md section 4, Round 11).
+        // The pa of the four neighbours stay four ds_read_b32: a ds_read2_b32 of two opposite neighbours has 8-bit
+        // offsets that do not reach from one tile to the next, so each pair needs its address formed per slot (measured,
+        // inside the keep rule's spread: the dropped table).  Every read has its own opaque base (cell, +1, -1, +row,
+        // -row; cells and float plane) plus an immediate offset: that keeps the compiler from pairing reads of one base
+        // into ds_read2_b64, 8 cycles per pair (MI355X_MICROARCH.md, LDS table).
         // The reads of slot j+1 go out in two batches (own cell + two neighbours before the arithmetic of slot j, the
-        // other two neighbours in the middle of it): lgkmcnt is a 4-bit counter, and with all 15 reads outstanding the
-        // wait for slot j's operands also waits for the first read of slot j+1.
+        // other two neighbours in the middle of it; in a batch the cells first, what the first products need):
+        // lgkmcnt is a 4-bit counter, and with all reads outstanding the wait for slot j's operands also waits for the
+        // first read of slot j+1.
 #define RES_LOAD_A(J)                                                                                  \
         {                                                                                              \
             const int s_ = (J) & 1;                                                                    \
             const char* T_ = (const char*)lds + (J) * (LTILE * 4);                                     \
-            if (!PREG) Lpv[s_] = *(const float2*)(T_ + offP[0]);                                       \
-            if (!CSREG) Lcs[s_] = *(const float2*)(T_ + offP[0] + LPLANE * 8);                         \
+            if (!PREG) Lown[s_] = *(const float4*)(T_ + offP[0]);                                      \
+            else if (!CSREG) Lcs[s_] = *(const float2*)(T_ + offP[0] + 8);                             \
             if (!PREG) Lpa[s_] = *(const float*)(T_ + offA[0] + LPLANE * 16);                          \
-            _Pragma("unroll") for (int n_ = 0; n_ < 2; ++n_) {                                         \
-                LqO[s_][n_] = *(const float2*)(T_ + offP[n_ + 1]);                                     \
-                Lcn[s_][n_] = *(const float2*)(T_ + offP[n_ + 1] + LPLANE * 8);                        \
-                LqA[s_][n_] = *(const float*)(T_ + offA[n_ + 1] + LPLANE * 16);                        \
-            }                                                                                          \
+            _Pragma("unroll") for (int n_ = 0; n_ < 2; ++n_) Lq[s_][n_] = *(const float4*)(T_ + offP[n_ + 1]); \
+            _Pragma("unroll") for (int n_ = 0; n_ < 2; ++n_) LqA[s_][n_] = *(const float*)(T_ + offA[n_ + 1] + LPLANE * 16); \
         }
 #define RES_LOAD_B(J)                                                                                  \
         {                                                                                              \
             const int s_ = (J) & 1;                                                                    \
             const char* T_ = (const char*)lds + (J) * (LTILE * 4);                                     \
-            _Pragma("unroll") for (int n_ = 2; n_ < 4; ++n_) {                                         \
-                LqO[s_][n_] = *(const float2*)(T_ + offP[n_ + 1]);                                     \
-                Lcn[s_][n_] = *(const float2*)(T_ + offP[n_ + 1] + LPLANE * 8);                        \
-                LqA[s_][n_] = *(const float*)(T_ + offA[n_ + 1] + LPLANE * 16);                        \
-            }                                                                                          \
+            _Pragma("unroll") for (int n_ = 2; n_ < 4; ++n_) Lq[s_][n_] = *(const float4*)(T_ + offP[n_ + 1]); \
+            _Pragma("unroll") for (int n_ = 2; n_ < 4; ++n_) LqA[s_][n_] = *(const float*)(T_ + offA[n_ + 1] + LPLANE * 16); \
         }
         RES_LOAD_A(0)
         RES_LOAD_B(0)
@@ -1070,11 +1073,13 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 // Branch free: every lane evaluates all four edges (LDS reads stay inside the halo'd tile, whose
                 // never-written cells were zero-filled in the prologue, so every operand is finite) and an edge
                 // whose flag bit is clear gets the weight +0: fma(0, u, a) = a exactly.
-                const float2 pv = PREG ? pxy[PREG ? j : 0] : Lpv[sj];
-                const float2 csv = CSREG ? make_float2(csr[CSREG ? j : 0].x, csr[CSREG ? j : 0].y) : Lcs[sj];     // (ci, si)
+                const float2 pv = PREG ? pxy[PREG ? j : 0] : make_float2(Lown[sj].x, Lown[sj].y);
+                v2f_t own2 = (v2f_t){Lown[sj].z, Lown[sj].w};      // (the second half of the own cell as a pair of its own: RES_EDGE)
+                if (!PREG) asm("" : "+v"(own2));
+                const float2 csv = CSREG ? make_float2(csr[CSREG ? j : 0].x, csr[CSREG ? j : 0].y)
+                                 : PREG ? Lcs[sj] : make_float2(own2.x, own2.y);             // (ci, si)
                 const float pa_ = PREG ? pal[PREG ? j : 0] : Lpa[sj];
                 const float ci = csv.x, si = csv.y;
-                const float2 pa2 = make_float2(pa_, pa_);
                 float2 axy = make_float2(0.f, 0.f);
                 float aa = 0.f;
                 // On the pixel grid d = U(c)-U(n) = -s, so q = R'(A(c))d and h = R'(A(n))d are signed copies of
@@ -1082,28 +1087,36 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
                 // block is the generic k_pcg_a expression
                 //   t = fma(-q, pa, dP) ; a_xy = fma(wr2, fma(-h, qA, dP + t), a_xy) ; aa = fma(-wr2, fma(qx,tx,qy ty), aa)
                 // on (x,y) pairs (v_pk_fma_f32), value for value (only the sign of an exact zero may differ).
-#define RES_EDGE(BITNO, E, NQX, NQY, NHX, NHY, QX, QY)                                                 \
+#define RES_EDGE(BITNO, E, NQX, NQY, PX, PY, NHX, NHY, AX, AY, QX, QY)                                               \
                 {                                                                                      \
-                    const float2 qO = LqO[sj][E], cn2 = Lcn[sj][E];                                    \
+                    const float2 qO = make_float2(Lq[sj][E].x, Lq[sj][E].y);                           \
+                    /* (the second half as a register pair of its own: taken word by word from the cell,  \
+                        its signed copies cost a v_xor_b32 each instead of a neg bit of the packed FMA) */ \
+                    v2f_t cn2 = (v2f_t){Lq[sj][E].z, Lq[sj][E].w};                                     \
+                    asm("" : "+v"(cn2));                                                               \
                     const float qA = LqA[sj][E];                                                       \
                     const float cn = cn2.x, sn = cn2.y;                                                \
                     const float w = (BITNO < NWR) ? we[WREG ? j : 0][BITNO] : keep_if<BITNO>(f, wr2);  \
                     const float2 e = pv - qO;                                                          \
-                    const float2 t = fma2(make_float2(NQX, NQY), pa2, e);                              \
-                    const float2 u = fma2(make_float2(NHX, NHY), make_float2(qA, qA), e + t);          \
+                    const float2 t = fma2(make_float2(NQX, NQY), make_float2(PX, PY), e);              \
+                    const float2 u = fma2(make_float2(NHX, NHY), make_float2(AX, AY), e + t);          \
                     axy = fma2(make_float2(w, w), u, axy);                                             \
                     aa = fmaf(-w, fmaf(QX, t.x, (QY) * t.y), aa);                                      \
                     (void)cn; (void)sn;                                                                \
                 }
                 // (the four rows below are the sign table of jtj_edge_grid<S>, arap_pcg.h)
-                //     bit no edge    -q          -h          q
-                RES_EDGE(0, 0,     -si,  ci,   -sn,  cn,    si, -ci)      // s=( 1, 0): q=( si,-ci) h=( sn,-cn)
-                RES_EDGE(1, 1,      si, -ci,    sn, -cn,   -si,  ci)      // s=(-1, 0): q=(-si, ci) h=(-sn, cn)
+                // -q multiplies the own pa, -h the neighbour's (qA, qA).  Where they are a (cos, sin) pair SWAPPED, their
+                // signs stand on the pa pair: (-sn) qA and sn (-qA) are the same product bit for bit, and a swapped pair from
+                // one half of a 16-byte cell folds into the packed FMA (op_sel) only without a sign of its own -- with it the
+                // compiler builds the pair with a v_xor_b32 and a v_mov_b32 (two VALU instructions per product).
+                //     bit no edge    -q = (|q|) x (signs on pa)   -h = (|h|) x (signs on qA)    q
+                RES_EDGE(0, 0,      si,  ci,  -pa_,  pa_,    sn,  cn,  -qA,  qA,    si, -ci)      // s=( 1, 0): q=( si,-ci) h=( sn,-cn)
+                RES_EDGE(1, 1,      si,  ci,   pa_, -pa_,    sn,  cn,   qA, -qA,   -si,  ci)      // s=(-1, 0): q=(-si, ci) h=(-sn, cn)
                 __builtin_amdgcn_sched_barrier(0);
                 if (j + 1 < NS) RES_LOAD_B(j + 1)
                 __builtin_amdgcn_sched_barrier(0);
-                RES_EDGE(2, 2,     -ci, -si,   -cn, -sn,    ci,  si)      // s=( 0, 1): q=( ci, si) h=( cn, sn)
-                RES_EDGE(3, 3,      ci,  si,    cn,  sn,   -ci, -si)      // s=( 0,-1): q=(-ci,-si) h=(-cn,-sn)
+                RES_EDGE(2, 2,     -ci, -si,   pa_,  pa_,   -cn, -sn,   qA,  qA,    ci,  si)      // s=( 0, 1): q=( ci, si) h=( cn, sn)
+                RES_EDGE(3, 3,      ci,  si,   pa_,  pa_,    cn,  sn,   qA,  qA,   -ci, -si)      // s=( 0,-1): q=(-ci,-si) h=(-cn,-sn)
 #undef RES_EDGE
                 {
                     const float wf = (WREG && NS <= WFIT) ? we[WREG ? j : 0][4] : keep_if<4>(f, wf2);
@@ -1153,7 +1166,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             // cost their issue slot whatever the number of active lanes: from here they would be 21 nearly empty store
             // instructions per wave, from the staging area 9 full ones.)
             if (zent >= 0) {
-                zst[j * RES_ZX + zent] = make_float4(zx, zy, za, zy);
+                *(v3f_t*)(zst + j * RES_ZX + zent) = (v3f_t){zx, zy, za};       // one ds_write_b96, no fourth word to form
             }
             // The first term IS the partial: +0.0 + t = t unless t is -0.0, and z.r is never -0.0 -- z_x r_x = mo r_x^2 and
             // z_y r_y are products of equal signs (mo > 0), so the inner fma is +0.0 or positive, and a sum rounds to -0.0
@@ -1174,21 +1187,24 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
             // component a {tag, bits} granule, while wave 0 is busy with the group sum; nothing waits for these stores --
             // the reader checks the tags (update phase below), and they have a whole group sum to travel.
             if (wave != 0) {
-                // granule g of the export = half g & 1 of staged entry g >> 1: (z_x, z_y) -> {z_x, low half of z_y},
-                // (z_alpha, z_y) -> {z_alpha, high half of z_y}; a thread's granules all have its parity (the stride is even)
+                // granule g of the export, from the three words of staged entry g >> 1: an even one is {z_x, low half of z_y},
+                // an odd one {z_alpha, high half of z_y}.  Its value is word 2 g of the staging area either way, z_y the word
+                // behind it (even) or in front of it (odd); a thread's granules all have its parity (the stride is even), so
+                // the choice is made once per thread
                 unsigned long long* const out = zx_b + (size_t)tfirst * RES_ZG;
-                const float2* const st2 = (const float2*)zst;
+                const float* const stv = (const float*)zst;
+                const float* const sty = (tid & 1) ? stv - 1 : stv + 1;
                 const unsigned sh = (tid & 1) ? 16u : 0u;
                 static_assert(((RES_THREADS - 64) & 1) == 0, "a thread keeps the parity of its granules");
                 if (zfast) {
                     for (int g = tid - 64; g < tp * RES_ZG; g += RES_THREADS - 64) {
-                        const float2 v = st2[g];
-                        st_tagged(out + g, (ztag << 16) | ((__float_as_uint(v.y) >> sh) & 0xffffu), v.x, true);
+                        const float vx = stv[2 * g], vy = sty[2 * g];
+                        st_tagged(out + g, (ztag << 16) | ((__float_as_uint(vy) >> sh) & 0xffffu), vx, true);
                     }
                 } else {
                     for (int g = tid - 64; g < tp * RES_ZG; g += RES_THREADS - 64) {
-                        const float2 v = st2[g];
-                        st_tagged(out + g, (ztag << 16) | ((__float_as_uint(v.y) >> sh) & 0xffffu), v.x, false);
+                        const float vx = stv[2 * g], vy = sty[2 * g];
+                        st_tagged(out + g, (ztag << 16) | ((__float_as_uint(vy) >> sh) & 0xffffu), vx, false);
                     }
                 }
             }
@@ -1418,8 +1434,7 @@ __global__ __launch_bounds__(RES_THREADS, 2) void k_pcg_resident(PlanDev pd, Res
 #undef RES_HPK
 #undef RES_PRIO
 #undef RES_PRIO_END
-#undef TP2
-#undef TCS
+#undef TPC
 #undef TPA
 
 }  // namespace arap

@@ -12,6 +12,16 @@
 //   lds64   ds_read_b64, 16 in flight per lane, conflict free (lane-consecutive 8-byte cells)
 //   lds32   ds_read_b32, likewise
 //   mixlds  mix + the 15 LDS reads of a phase-A vertex (10 x ds_read_b64, 5 x ds_read_b32) per 48 VALU: do the pipes overlap?
+//   mixlds_now / mixlds_cell / mixlds_c128 / mixlds_celladd   what ONE LDS instruction costs in phase A as the 7-slot flat
+//           loop has it (13 v_pk_fma_f32, 8 v_pk_add_f32, 17 v_fma_f32, no v_and_b32: the weights are in registers), on a
+//           conflict-free image at the tile's strides (row of 34 cells, lanes 0-31 one row, 32-63 the next; neighbours
+//           +1, -1, +row, -row, each from its own base register).  The same 20 words per vertex arrive as
+//             now      8 ds_read_b64 + 4 ds_read_b32     (float2 p plane | float2 cos/sin plane | float pa plane)
+//             cell     4 ds_read_b128 + 2 ds_read2_b32   (float4 {px, py, cos, sin} cells | float pa plane)
+//             c128     4 ds_read_b128 + 4 ds_read_b32
+//             celladd  cell + the two v_add_u32 that form the ds_read2_b32 addresses of a tile slot (their 8-bit offsets
+//                      do not reach from one tile to the next)
+//           and are consumed by the same 12 VALU instructions (8 v_pk_add_f32, 4 v_add_f32) in all four.
 // Every kernel stamps s_memtime / s_memrealtime around its loop in wave 0 of every workgroup: cycles and the clock held.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -23,6 +33,7 @@
 #define HC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct Stamp { unsigned long long cyc, rt; };
 
@@ -41,6 +52,19 @@ __global__ __launch_bounds__(256, 2) void k_issue(float* out, Stamp* stamps, int
     const v2f a2 = (v2f){a, a}, b2 = (v2f){b, b};
     const unsigned m = 0x7fffffffu;
     const unsigned base64 = (unsigned)tid * 8u, base32 = (unsigned)tid * 4u;
+    // the resident kernel's tile: cell = row * 34 + col of this lane's vertex, its neighbours +1, -1, +row, -row
+    const int cell = ((((tid >> 6) << 1) | ((tid >> 5) & 1)) + 1) * 34 + (tid & 31) + 1;
+    unsigned aP8[4], aP4[4], aC16[4];
+    {
+        const int dn[4] = {1, -1, 34, -34};
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            aP8[n] = (unsigned)(cell + dn[n]) * 8u; aP4[n] = (unsigned)(cell + dn[n]) * 4u; aC16[n] = (unsigned)(cell + dn[n]) * 16u;
+            asm volatile("" : "+v"(aP8[n]), "+v"(aP4[n]), "+v"(aC16[n]));
+        }
+    }
+    unsigned aPA[2] = {aP4[1] + 5440u, aP4[3] + 5440u};
+    asm volatile("" : "+v"(aPA[0]), "+v"(aPA[1]));
     unsigned long long c0 = 0, r0 = 0;
     if ((tid & 63) == 0) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
     for (int it = 0; it < iters; ++it) {
@@ -79,6 +103,61 @@ __global__ __launch_bounds__(256, 2) void k_issue(float* out, Stamp* stamps, int
 #pragma unroll
                 for (int i = 0; i < 5; ++i) asm volatile("v_add_f32 %0, %0, %1" : "+v"(acc[i]) : "v"(l32[i]));
             }
+        } else if (MODE >= 6) {
+            v2f p64[4], c64[4];
+            v4f q128[4];
+            float pa[4];
+            v2f pa2[2];
+            unsigned ax = aPA[0], ay = aPA[1];          // (cell: the pa plane's addresses are at hand, formed before the loop)
+            if (MODE == 6) {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    asm volatile("ds_read_b64 %0, %1" : "=v"(p64[n]) : "v"(aP8[n]));
+                    asm volatile("ds_read_b64 %0, %1 offset:2720" : "=v"(c64[n]) : "v"(aP8[n]));
+                    asm volatile("ds_read_b32 %0, %1 offset:5440" : "=v"(pa[n]) : "v"(aP4[n]));
+                }
+            } else {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) asm volatile("ds_read_b128 %0, %1" : "=v"(q128[n]) : "v"(aC16[n]));
+                if (MODE == 8) {
+#pragma unroll
+                    for (int n = 0; n < 4; ++n) asm volatile("ds_read_b32 %0, %1 offset:5440" : "=v"(pa[n]) : "v"(aP4[n]));
+                } else {
+                    if (MODE == 9) {
+                        asm volatile("v_add_u32 %0, 0x1540, %1" : "=v"(ax) : "v"(aP4[1]));
+                        asm volatile("v_add_u32 %0, 0x1540, %1" : "=v"(ay) : "v"(aP4[3]));
+                    }
+                    asm volatile("ds_read2_b32 %0, %1 offset1:2" : "=v"(pa2[0]) : "v"(ax));
+                    asm volatile("ds_read2_b32 %0, %1 offset1:68" : "=v"(pa2[1]) : "v"(ay));
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 13; ++i) asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(acc2[i]) : "v"(a2), "v"(b2));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc2[(i + 5) & 15]) : "v"(b2));
+#pragma unroll
+            for (int i = 0; i < 17; ++i) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(acc[i & 15]) : "v"(a), "v"(b));
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (MODE == 6) {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc2[n]) : "v"(p64[n]));
+                    asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc2[n + 4]) : "v"(c64[n]));
+                }
+            } else {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc2[n]) : "v"(__builtin_shufflevector(q128[n], q128[n], 0, 1)));
+                    asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc2[n + 4]) : "v"(__builtin_shufflevector(q128[n], q128[n], 2, 3)));
+                }
+            }
+            if (MODE == 6 || MODE == 8) {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) asm volatile("v_add_f32 %0, %0, %1" : "+v"(acc[n]) : "v"(pa[n]));
+            } else {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) asm volatile("v_add_f32 %0, %0, %1" : "+v"(acc[n]) : "v"(pa2[n >> 1][n & 1]));
+            }
         } else if (MODE == 3) {
             v2f l[16];
 #pragma unroll
@@ -114,13 +193,16 @@ __global__ __launch_bounds__(256, 2) void k_issue(float* out, Stamp* stamps, int
 }
 
 typedef void (*Kern)(float*, Stamp*, int, float, float);
-struct Mode { const char* name; Kern k; int valu_per_iter, pk_per_iter, lds64_per_iter, lds32_per_iter; };
+struct Mode { const char* name; Kern k; int valu_per_iter, pk_per_iter, lds64_per_iter, lds32_per_iter, lds_insts_per_iter; };
 
 int main(int argc, char** argv)
 {
     const Mode modes[] = {
-        {"fma", k_issue<0>, 64, 0, 0, 0}, {"pkfma", k_issue<1>, 64, 64, 0, 0}, {"mix", k_issue<2>, 48, 21, 0, 0},
-        {"lds64", k_issue<3>, 0, 0, 64, 0}, {"lds32", k_issue<4>, 0, 0, 0, 64}, {"mixlds", k_issue<5>, 63, 31, 10, 5},
+        {"fma", k_issue<0>, 64, 0, 0, 0, 0}, {"pkfma", k_issue<1>, 64, 64, 0, 0, 0}, {"mix", k_issue<2>, 48, 21, 0, 0, 0},
+        {"lds64", k_issue<3>, 0, 0, 64, 0, 64}, {"lds32", k_issue<4>, 0, 0, 0, 64, 64}, {"mixlds", k_issue<5>, 63, 31, 10, 5, 15},
+        // (the same 80 bytes per lane in all four: counted as 8 x 8 + 4 x 4)
+        {"mixlds_now", k_issue<6>, 50, 29, 8, 4, 12}, {"mixlds_cell", k_issue<7>, 50, 29, 8, 4, 6},
+        {"mixlds_c128", k_issue<8>, 50, 29, 8, 4, 8}, {"mixlds_celladd", k_issue<9>, 52, 29, 8, 4, 6},
     };
     int iters = 20000;
     const char* only = nullptr;
@@ -134,7 +216,9 @@ int main(int argc, char** argv)
     hipEvent_t e0, e1;
     HC(hipEventCreate(&e0)); HC(hipEventCreate(&e1));
     for (const Mode& m : modes) {
-        if (only && strcmp(only, m.name)) continue;
+        // a name selects that kernel; "cells" the four phase-A read forms; no name the kernels of the ceilings record
+        const bool cellk = !strncmp(m.name, "mixlds_", 7);
+        if (only ? (strcmp(only, "cells") ? strcmp(only, m.name) != 0 : !cellk) : cellk) continue;
         for (int per_cu = 2; per_cu >= 1; --per_cu) {
             const int lds_bytes = per_cu == 2 ? 80768 : 163840 - 1024, wgs = 256 * per_cu;
             HC(hipFuncSetAttribute((const void*)m.k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
@@ -157,10 +241,11 @@ int main(int argc, char** argv)
                          l32 = (double)m.lds32_per_iter * iters * per_cu;
             printf("{\"kernel\": \"%s\", \"waves_per_simd\": %d, \"ms\": %.4f, \"loop_cycles_median\": %.0f, \"clock_MHz\": %.0f, "
                    "\"valu_insts_per_simd\": %.0f, \"cycles_per_valu_inst_per_simd\": %s, \"pk_share\": %.2f, "
-                   "\"lds_b64_per_cu\": %.0f, \"lds_b32_per_cu\": %.0f, \"lds_bytes_per_clk_per_cu\": %.1f}\n",
+                   "\"lds_b64_per_cu\": %.0f, \"lds_b32_per_cu\": %.0f, \"lds_bytes_per_clk_per_cu\": %.1f, "
+                   "\"lds_insts_per_iter\": %d, \"cycles_per_iter_per_wave\": %.3f}\n",
                    m.name, per_cu, ms, c, mhz, valu, valu > 0 ? (std::to_string(c / valu)).c_str() : "null",
                    m.valu_per_iter ? (double)m.pk_per_iter / m.valu_per_iter : 0.0, 4 * l64, 4 * l32,
-                   (4 * l64 * 512.0 + 4 * l32 * 256.0) / c);
+                   (4 * l64 * 512.0 + 4 * l32 * 256.0) / c, m.lds_insts_per_iter, c / ((double)iters * per_cu));
             fflush(stdout);
         }
     }
